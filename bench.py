@@ -26,6 +26,11 @@ walks it once in --batch-frame batches (distinct inputs every step); the all-red
 same for every world size.
 
 Only the `cpu_baseline` / `parity` legs touch oracle/ (the checker); the timed path is liborbx.so.
+
+A plain run (no --full) sets up, warms up, times the steps, writes --dump-outputs if given and prints the headline
+line (`metric`, `value`, `unit`, `ms_per_step`, ...).  --full runs everything else after the timed region as well:
+`value_full_work`, `value_sustained`, the `stream` block, per-stage and roofline figures, the D2H rates, the extra
+call shapes, `parity` and `cpu_baseline`.
 """
 import argparse
 import hashlib
@@ -54,6 +59,39 @@ def host_threads():
     except AttributeError:
         ncores = os.cpu_count() or 1
     return max(1, min(ncores, 32))
+
+
+def host_frames(gen, n, first):
+    """gen(count, first) of streams.py over frames [first, first + n), in chunks on up to 16 host threads (numpy
+    releases the GIL).  Frame i depends on i only, so the array is the same as one gen(n, first) call."""
+    import concurrent.futures as cf
+
+    nthr = min(host_threads(), 16)
+    step = (n + nthr - 1) // nthr
+    with cf.ThreadPoolExecutor(nthr) as ex:
+        parts = list(ex.map(lambda s: gen(min(step, n - s), first + s), range(0, n, step)))
+    return np.concatenate(parts)
+
+
+def dump_outputs(d, res, max_bytes=56 << 20):
+    """--dump-outputs: what the last timed step computed (`res`: orbx_batch_fetch of its result block, slots past a
+    frame's count zero) as .npy files of float32 / float64.  Every frame: `counts`, and `frame_sums` (per frame: sum
+    of x, y, level, descriptor bytes, orientation over its keypoints).  A fixed sample of frames (seed 0, at most 256,
+    at most `max_bytes`): every output array of those frames, `sample_frames` holding their indices in the batch."""
+    os.makedirs(d, exist_ok=True)
+    n, cap = res["kps"].shape[:2]
+    f64 = np.float64
+    sums = np.stack([res["kps"][..., 0].sum(1, dtype=f64), res["kps"][..., 1].sum(1, dtype=f64),
+                     res["levels"].sum(1, dtype=f64), res["desc"].reshape(n, -1).sum(1, dtype=f64),
+                     res["angles"].sum(1, dtype=f64)], axis=1)
+    per_frame = cap * 4 * (2 + 2 + 1 + 1 + 1 + 32)  # float32 bytes of one frame's slots in the sampled arrays
+    ns = max(1, min(n, 256, max_bytes // max(per_frame, 1)))
+    idx = np.sort(np.random.default_rng(0).choice(n, ns, replace=False))
+    arrays = {"counts": res["counts"].astype(f64), "frame_sums": sums, "sample_frames": idx.astype(f64)}
+    for k in ("kps", "kps_level", "angles", "responses", "levels", "desc"):
+        arrays[k] = res[k][idx].astype(np.float32)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def oracle_results(frames, params_kw):
@@ -206,7 +244,16 @@ def main():
                          "on one stream); implied by --only-timed, whose rocprofv3 kernel durations must not overlap")
     ap.add_argument("--pmc-file", default=PMC_FILE,
                     help="per-kernel counters from separate rocprofv3 --pmc passes of THIS build (tools/pmc_collect.sh)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run every other measurement and check as well (full-work and "
+                         "sustained rates, the strong-scaling stream block, stage / roofline figures, D2H rates, "
+                         "LK / matcher / single-frame figures, parity with the oracle, cpu_baseline); without it the "
+                         "run prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's result block) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -254,7 +301,7 @@ def main():
         nlocal = last - first
         nbatches = (nlocal + B - 1) // B
         batches = [(d_all[i * B:min((i + 1) * B, nlocal)], min(B, nlocal - i * B)) for i in range(nbatches)]
-        frames0 = batches[0][0].cpu().numpy()
+        frames0 = batches[0][0].cpu().numpy() if args.full else None  # (read by --full's extra passes only)
         steps = args.steps if args.steps is not None else nbatches
         wl += "; stream mode: %d frames total, rank block %d" % (total, nlocal)
     else:
@@ -262,9 +309,9 @@ def main():
         steps = args.steps if args.steps is not None else 20
         f0 = pkg.shard.frame_range(rank, world, R * B)[0]
         if args.workload == "kitti":
-            host = [pkg.streams.stream_a(B, first=f0 + r * B) for r in range(R)]
+            host = [host_frames(pkg.streams.stream_a, B, f0 + r * B) for r in range(R)]
         else:
-            host = [pkg.streams.stream_b(B, H, W, first=f0 + r * B) for r in range(R)]
+            host = [host_frames(lambda n_, f_: pkg.streams.stream_b(n_, H, W, f_), B, f0 + r * B) for r in range(R)]
         batches = [(torch.from_numpy(h).to(dev), B) for h in host]
         frames0 = host[0]
     torch.cuda.synchronize()
@@ -324,11 +371,34 @@ def main():
     # ---- what the timed region itself produced: the result blocks of its LAST TWO steps (one per lane when
     # pipelined), copied out before anything else runs; compared with the oracle at the end (`parity.timed_region`)
     timed_out = []
-    if not stream_mode and steps >= 2:
+    if args.full and not stream_mode and steps >= 2:
         for prev in (False, True):
             hv = ctx.batch_host_view(previous=prev)
             timed_out.append({"batch": (steps - 1 - (1 if prev else 0)) % len(batches), "counts": hv["counts"].copy(),
                               "kps": hv["kps"].copy(), "desc": hv["desc"].copy()})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx.batch_fetch(0, batches[(steps - 1) % len(batches)][1], cap))
+
+    # ---- the headline line: all a plain run prints
+    head = {
+        "metric": "ORB detect+describe frames/sec (1241x376, 8 lvls)" if args.workload == "kitti"
+                  else "ORB detect+describe frames/sec (1920x1080, 12 lvls)",
+        "value": nframes_all / dt, "unit": "frames/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
+        "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "strong" if stream_mode else "weak",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "config": {"workload": wl, "frames_per_step_per_gpu": B, "distinct_resident_batches": len(batches),
+                   "sharding": "frame-parallel, no data-path collective",
+                   "fast_early_exit": not args.full_work, "pyramid_blur_fused": not args.unfused,
+                   "pyramid_top_rows_first": bool(pyr_done[0] < pyr_done[1]), "pipelined_batches": pipelined},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        ctx.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the same timed region with every FAST tile working and every pyramid row produced (`value_full_work`:
     # what a stream that never fills its caps in the top rows gets), and a sustained run (`value_sustained`)
@@ -611,7 +681,6 @@ def main():
     csum = grp.sum_checksum(cs0)
 
     if rank == 0:
-        fps = nframes_all / dt
         # ---- roofline.  Algorithmic bytes (SURVEY.md §8d / BASELINE.md §4): blur 2 B/px, FAST 1 B/px over all
         # pyramid pixels; pyramid = level 0 read + every level written; per launch = per frame x batch.
         alg = {"pyramid": (W * H + pyr_px) * B, "blur": 2.0 * pyr_px * B, "fast_nms": 1.0 * pyr_px * B}
@@ -692,16 +761,7 @@ def main():
         achieved = fracs[dom]
         both_full = gbs(alg["blur"] + alg["fast_nms"], blur_ms + full_ms["fast_nms"])
         both_timed = gbs(alg["blur"] + alg["fast_nms"] * work_frac, blur_ms + roof_ms["fast_nms"])
-        out = {
-            "metric": "ORB detect+describe frames/sec (1241x376, 8 lvls)" if args.workload == "kitti"
-                      else "ORB detect+describe frames/sec (1920x1080, 12 lvls)",
-            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
-            "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "strong" if stream_mode else "weak",
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": wl, "frames_per_step_per_gpu": B, "distinct_resident_batches": len(batches),
-                       "sharding": "frame-parallel, no data-path collective",
-                       "fast_early_exit": not args.full_work, "pyramid_blur_fused": not args.unfused,
-                       "pyramid_top_rows_first": bool(pyr_done[0] < pyr_done[1]), "pipelined_batches": pipelined},
+        out = dict(head, **{
             "roofline": {"bound": "hbm", "kernel": "k_blur3 (stand-alone)" if dom == "blur_alone" else fast_kernel + (" (every tile working)" if fast_kernel == "k_fast3" else " (every unit working)"),
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": kern.get(dom, {}).get("hbm_traffic_bytes_per_launch"),
@@ -729,7 +789,7 @@ def main():
             "match_consecutive": {"ms_per_batch": match_ms, "pairs": B - 1, "matches_pair0": n_matches,
                                   "what": "Hamming 2-NN + 0.8 ratio test, frame i -> i+1, device-resident"},
             "keypoints_batch0": n_kp, "desc_checksum": csum,
-        }
+        })
         if stream_info:
             out["stream"] = stream_info
         if not args.no_cpu_baseline:

@@ -7,7 +7,8 @@
   orbx_detect_and_compute_batch_device (three-kernel selection, adaptive fall-back of the top-rows-first pipeline);
 * batches on a caller's stream mixed with pipelined ones (the lane's pools and the result block follow
   their previous user's event);
-* the compact result copy (orbx_batch_prefetch_compact).
+* the compact result copy (orbx_batch_prefetch_compact);
+* a plain bench.py run: its headline line and what `--dump-outputs` writes of its last timed step.
 This is the check the reference left commented out in src/compare.cpp:39-62, at scale."""
 import concurrent.futures as cf
 
@@ -268,3 +269,35 @@ def test_config4_1080p_as_a_batch(pkg):
         c.wait()
         compare(c.batch_host_view(), refs)
         compare(c.batch_host_view(previous=True), refs)
+
+
+def test_plain_bench_line_and_dumped_outputs_match_oracle(pkg, tmp_path):
+    """A plain `bench.py` run prints the headline fields only, and `--dump-outputs` writes what its last timed step
+    computed: 3 steps over 2 resident batches of 16 stream-A frames end on batch 0 (frames 0..15), so the dumped counts,
+    per-frame sums and sampled result arrays must equal the oracle on those frames."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "16", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert not {"roofline", "parity", "cpu_baseline", "stream", "value_full_work"} & set(line)
+
+    refs = oracle_on(pkg.streams.stream_a(16, first=0), PK)
+    dump = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert all(a.dtype in (np.float32, np.float64) for a in dump.values())
+    assert np.array_equal(dump["counts"], [len(ref["kps"]) for ref in refs])
+    sums = [[ref["kps"][:, 0].sum(), ref["kps"][:, 1].sum(), ref["levels"].sum(), ref["desc"].astype(np.int64).sum()]
+            for ref in refs]
+    assert np.array_equal(dump["frame_sums"][:, :4], sums)
+    idx = dump["sample_frames"].astype(np.int64)
+    assert len(idx) == 16
+    compare({k: dump[k] for k in ("kps", "kps_level", "angles", "responses", "levels", "desc")}
+            | {"counts": dump["counts"][idx]}, [refs[i] for i in idx])

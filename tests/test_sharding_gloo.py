@@ -100,7 +100,7 @@ def _run_bench_stream(world, port, frames_per_eighth):
     import json
 
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--stream-frames",
-            str(frames_per_eighth), "--batch", "16", "--warmup", "1", "--no-cpu-baseline", "--only-timed",
+            str(frames_per_eighth), "--batch", "16", "--warmup", "1", "--no-cpu-baseline", "--only-timed", "--full",
             "--dist-backend", "gloo", "--all-ranks-on-device0"]
     procs = []
     for r in range(world):
@@ -127,12 +127,12 @@ def test_two_gloo_ranks_with_the_gpu_worker_equal_one_rank(pkg):
 
 
 def _run_bench_default(world, port, strong):
-    """bench.py's DEFAULT mode (what the driver launches: weak-scaling timed region) with the configs[3] `stream` block
-    beside it, `world` gloo ranks on GPU 0."""
+    """bench.py's DEFAULT mode (what the driver launches: weak-scaling timed region) with --full, which adds the
+    configs[3] `stream` block beside it, `world` gloo ranks on GPU 0."""
     import json
 
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--batch", "16", "--steps", "4",
-            "--warmup", "1", "--no-cpu-baseline", "--only-timed", "--strong-frames", str(strong),
+            "--warmup", "1", "--no-cpu-baseline", "--only-timed", "--full", "--strong-frames", str(strong),
             "--dist-backend", "gloo", "--all-ranks-on-device0"]
     procs = []
     for r in range(world):
@@ -147,7 +147,7 @@ def _run_bench_default(world, port, strong):
 
 @pytest.mark.gpu
 def test_default_bench_line_carries_the_strong_scaling_block(pkg):
-    """The line a driver `--gpus N` run gets is the weak-scaling one (`scaling: weak`); beside it the `stream` block
+    """The line a driver `--gpus N` run gets is the weak-scaling one (`scaling: weak`); with --full the `stream` block
     reports BASELINE.json configs[3] (strong scaling: a fixed stream split over the ranks) with a keypoint count and a
     checksum that do not depend on the world size."""
     one = _run_bench_default(1, 29651, 12)

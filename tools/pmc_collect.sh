@@ -13,8 +13,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 O=gpurun_out/r03c
 mkdir -p $O
-B="bench.py --only-timed --no-cpu-baseline --steps 6 --warmup 4"  # (4 warm-up steps: the adaptive first pass re-partitions the tile rows after the second batch; pmc_to_json.py leaves them out)   # bench.py's default workload: 1024 frames per launch
-B64="bench.py --only-timed --no-cpu-baseline --batch 64 --rotate 4 --steps 10 --warmup 4"  # BASELINE.json configs[2]
+B="bench.py --full --only-timed --no-cpu-baseline --steps 6 --warmup 4"  # (4 warm-up steps: the adaptive first pass re-partitions the tile rows after the second batch; pmc_to_json.py leaves them out)   # bench.py's default workload: 1024 frames per launch
+B64="bench.py --full --only-timed --no-cpu-baseline --batch 64 --rotate 4 --steps 10 --warmup 4"  # BASELINE.json configs[2]
 run() {  # name, rocprof args..., -- bench args
   local name=$1; shift
   echo "== $name: $*" >> $O/log.txt
@@ -46,7 +46,7 @@ run fast3_write --kernel-trace --pmc WRITE_SIZE -d $O/fast3_write -o run --outpu
 run fast3timed_stats --kernel-trace --stats -d $O/fast3timed_stats -o run --output-format csv -- python3 $B
 unset ORBX_FAST_IMPL
 # kernel durations at 64 frames per launch (BASELINE.json configs[2]; pools inside the Infinity Cache) and at 256
-B256="bench.py --only-timed --no-cpu-baseline --batch 256 --rotate 2 --steps 10 --warmup 4"
+B256="bench.py --full --only-timed --no-cpu-baseline --batch 256 --rotate 2 --steps 10 --warmup 4"
 for cfg in timed fullwork unfused; do
   case $cfg in
     timed) X="";;
@@ -57,14 +57,14 @@ for cfg in timed fullwork unfused; do
   run b256_${cfg}_stats --kernel-trace --stats -d $O/b256_${cfg}_stats -o run --output-format csv -- python3 $B256 $X
 done
 # BASELINE.json configs[4]: 1920x1080, 12 levels, 4000 features
-run hd_timed_stats --kernel-trace --stats -d $O/hd_timed_stats -o run --output-format csv -- python3 bench.py --workload 1080p --batch 32 --rotate 2 --steps 6 --warmup 4 --only-timed --no-cpu-baseline
-run hd_fullwork_stats --kernel-trace --stats -d $O/hd_fullwork_stats -o run --output-format csv -- python3 bench.py --workload 1080p --batch 32 --rotate 2 --steps 6 --warmup 4 --only-timed --no-cpu-baseline --full-work
+run hd_timed_stats --kernel-trace --stats -d $O/hd_timed_stats -o run --output-format csv -- python3 bench.py --full --workload 1080p --batch 32 --rotate 2 --steps 6 --warmup 4 --only-timed --no-cpu-baseline
+run hd_fullwork_stats --kernel-trace --stats -d $O/hd_fullwork_stats -o run --output-format csv -- python3 bench.py --full --workload 1080p --batch 32 --rotate 2 --steps 6 --warmup 4 --only-timed --no-cpu-baseline --full-work
 # plain bench lines (no profiler): the default line, configs[2] (64 frames per step), configs[3] at N = 1
 # (8 x 1000-frame stream walked once), configs[4]
-python3 bench.py > $O/bench_default.json 2>> $O/log.txt || echo "FAILED bench_default" >> $O/log.txt
-python3 bench.py --batch 64 --rotate 4 --no-cpu-baseline > $O/bench_batch64.json 2>> $O/log.txt || echo "FAILED bench_batch64" >> $O/log.txt
-ORBX_FAST_IMPL=3 python3 bench.py --no-cpu-baseline --strong-frames 0 > $O/bench_fast3.json 2>> $O/log.txt || echo "FAILED bench_fast3" >> $O/log.txt
-python3 bench.py --workload 1080p --batch 32 --rotate 2 --steps 10 --no-cpu-baseline > $O/bench_1080p.json 2>> $O/log.txt || echo "FAILED bench_1080p" >> $O/log.txt
+python3 bench.py --full > $O/bench_default.json 2>> $O/log.txt || echo "FAILED bench_default" >> $O/log.txt
+python3 bench.py --full --batch 64 --rotate 4 --no-cpu-baseline > $O/bench_batch64.json 2>> $O/log.txt || echo "FAILED bench_batch64" >> $O/log.txt
+ORBX_FAST_IMPL=3 python3 bench.py --full --no-cpu-baseline --strong-frames 0 > $O/bench_fast3.json 2>> $O/log.txt || echo "FAILED bench_fast3" >> $O/log.txt
+python3 bench.py --full --workload 1080p --batch 32 --rotate 2 --steps 10 --no-cpu-baseline > $O/bench_1080p.json 2>> $O/log.txt || echo "FAILED bench_1080p" >> $O/log.txt
 echo "bench lines done"
 # FETCH_SIZE / WRITE_SIZE calibration on known byte counts, per access width (tools/bw_probe.hip)
 [ -x tools/bw_probe.bin ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -o tools/bw_probe.bin tools/bw_probe.hip >> $O/log.txt 2>&1 || true

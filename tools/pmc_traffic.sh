@@ -3,7 +3,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp
 cd ${GRAFT_REPO_ROOT:-/root/repo}
-B="python3 bench.py --only-timed --steps 3 --warmup 1 --no-cpu-baseline"
+B="python3 bench.py --full --only-timed --steps 3 --warmup 1 --no-cpu-baseline"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmcF -o run --output-format csv -- $B > gpurun_out/pmcF.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmcW -o run --output-format csv -- $B > gpurun_out/pmcW.log 2>&1
 export ORBX_FAST_EARLY=0
