@@ -1753,11 +1753,12 @@ hipError_t orbx_launch_describe(hipStream_t s, const OrbxPlan& plan, int n_frame
                        d_sel_resp, d_out_count, d_out_lkp, d_out_resp, d_out_level, d_out_kp, d_out_kp16, d_out_angle, d_out_desc, d_feedback,
                        h_feedback, host);
   } else {
-    // Four waves of four keypoints, registers capped for 7 waves per SIMD (5.1 KB of LDS per wave: 7 workgroups
-    // per CU).  Measured per 256 frames: 8-wave workgroups at 6 waves per SIMD (the trig -- two threads per
-    // keypoint -- fills a wave: -1.8 % instructions) 203 us, 7-wave workgroups 221 us, this 197 us.
+    // Four waves of four keypoints, registers capped for 6 waves per SIMD: 78 VGPRs, no scratch.  The 72-register
+    // cap of 7 waves per SIMD spills 7 VGPRs + 7 SGPRs (32 B/lane of scratch) and is 4 % slower per 1024 frames
+    // (867 vs 831 us).  Earlier, per 256 frames: 8-wave workgroups at 6 waves per SIMD (the trig -- two threads per
+    // keypoint -- fills a wave: -1.8 % instructions) 203 us, 7-wave workgroups 221 us.
     dim3 grid(n_frames, (plan.out_cap + 15) / 16);
-    hipLaunchKernelGGL((k_describe2<4, 4, 7>), grid, dim3(256), 0, s, plan, d_pyr, patch_size, d_sel_count, d_sel_lkp,
+    hipLaunchKernelGGL((k_describe2<4, 4, 6>), grid, dim3(256), 0, s, plan, d_pyr, patch_size, d_sel_count, d_sel_lkp,
                        d_sel_resp, d_out_count, d_out_lkp, d_out_resp, d_out_level, d_out_kp, d_out_kp16, d_out_angle, d_out_desc, d_feedback,
                        h_feedback, host);
   }
