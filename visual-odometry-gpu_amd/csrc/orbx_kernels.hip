@@ -1248,10 +1248,12 @@ __device__ __forceinline__ float lround_f(float v) {
 }
 
 typedef float f2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2_t lround_f2(f2_t v) {
-  const f2_t t = __builtin_elementwise_trunc(v);
-  const f2_t fr = v - t;
-  return t + __builtin_elementwise_trunc(fr + fr);
+typedef int i2_t __attribute__((ext_vector_type(2)));
+// orbx_lround_small of both lanes (|v| < 32): v + copysign(0.5 - 2^-25, v) on the packed-f32 unit, then the
+// truncating v_cvt_i32_f32
+__device__ __forceinline__ i2_t lround_small2(f2_t v) {
+  const f2_t h = {0.5f - 0x1p-25f, 0.5f - 0x1p-25f};
+  return __builtin_convertvector(v + __builtin_elementwise_copysign(h, v), i2_t);
 }
 
 template <int DESC_KPW, int DESC_NW, int DESC_OCC>
@@ -1325,6 +1327,7 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
 #pragma unroll
     for (int k = 0; k < DESC_NLD; k++) {
       rowk[k] = row;
+      __builtin_assume(row >= 0 && row < DESC_ROWS + 6);
       if (k < 3) c3[k] = c;
       if (lane + 64 * k < DESC_ROWS * (DESC_PITCH / 4) && row >= DESC_R - pr && row <= DESC_R + pr) rin |= 1u << k;
       row += 5;
@@ -1380,35 +1383,58 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
     }
   }
 
-  // pass A: moments
+  // pass A: moments.  Per keypoint, every lane's partial sums of m10 and m01 (0 where the keypoint is absent or its
+  // window crosses the border); the wave sums follow for all keypoints at once
+  int pm[2][DESC_KPW];
 #pragma unroll
   for (int j = 0; j < DESC_KPW; j++) {
-    if (j < nk) {
-      const DescJob& jb = jobs[j];
-      const int q = wave * DESC_KPW + j, off = offs[j];
-      int m10 = 0, m01 = 0;
-      // full patch must lie inside the image, else angle 0 (src/orb_cpu.cpp:152-156)
-      if (!(jb.x - pr < 0 || jb.x + pr >= jb.w || jb.y - pr < 0 || jb.y + pr >= jb.h)) {
-        // straight from the registers: per dword one dot product with the x weights and one
-        // with the window mask; exact integers (< 2^24, like the reference's float sums)
-        uint2 mw[3];
+    const DescJob& jb = jobs[j];
+    const int off = offs[j];
+    pm[0][j] = pm[1][j] = 0;
+    // full patch must lie inside the image, else angle 0 (src/orb_cpu.cpp:152-156)
+    if (j < nk && !(jb.x - pr < 0 || jb.x + pr >= jb.w || jb.y - pr < 0 || jb.y + pr >= jb.h)) {
+      // straight from the registers: per dword one dot product with the x weights and one
+      // with the window mask; exact integers (< 2^24, like the reference's float sums)
+      uint2 mw[3];
 #pragma unroll
-        for (int m = 0; m < 3; m++) mw[m] = s_mw[off * (DESC_PITCH / 4) + c3[m]];
-        uint32_t X = 0, S = 0, M = 0;
+      for (int m = 0; m < 3; m++) mw[m] = s_mw[off * (DESC_PITCH / 4) + c3[m]];
+      uint32_t X = 0, S = 0, M = 0;
 #pragma unroll
-        for (int k = 0; k < DESC_NLD; k++) {
-          const uint32_t z = regs[j][k] & (uint32_t)(-(int32_t)((rin >> k) & 1u));
-          X = __builtin_amdgcn_udot4(z, mw[k % 3].x, X, false);
-          const uint32_t rs = __builtin_amdgcn_udot4(z, mw[k % 3].y, 0u, false);
-          S += rs;
-          M += __umul24((uint32_t)rowk[k], rs);  // (rows < 41, rs <= 1020: the full-rate 24-bit multiply-add)
-        }
-        m10 = wave_sum((int)X - __mul24(pr, (int)S));  // (S <= 8 x 1020, pr <= 20: 24-bit operands)
-        m01 = wave_sum((int)M - __mul24(DESC_R, (int)S));
+      for (int k = 0; k < DESC_NLD; k++) {
+        const uint32_t z = regs[j][k] & (uint32_t)(-(int32_t)((rin >> k) & 1u));
+        X = __builtin_amdgcn_udot4(z, mw[k % 3].x, X, false);
+        const uint32_t rs = __builtin_amdgcn_udot4(z, mw[k % 3].y, 0u, false);
+        S += rs;
+        M += __umul24((uint32_t)rowk[k], rs);  // (rows < 41, rs <= 1020: the full-rate 24-bit multiply-add)
       }
+      pm[0][j] = (int)X - __mul24(pr, (int)S);  // (S <= 8 x 1020, pr <= 20: 24-bit operands)
+      pm[1][j] = (int)M - __mul24(DESC_R, (int)S);
+    }
+  }
+  if constexpr (DESC_KPW == 4) {
+    // the 8 wave sums as one transposed reduction: v_permlane32_swap + add leaves two of the values summed over
+    // the wave's halves in one register (4 x), v_permlane16_swap + add four of them summed over 16-lane rows
+    // (2 x), then one 16-lane DPP sum per register -- row r of u[i] holds moment i of keypoint kpr(r)
+    int u[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+      const auto h0 = __builtin_amdgcn_permlane32_swap(pm[i][0], pm[i][1], false, false);  // [kp 0 | kp 1]
+      const auto h1 = __builtin_amdgcn_permlane32_swap(pm[i][2], pm[i][3], false, false);  // [kp 2 | kp 3]
+      const auto r = __builtin_amdgcn_permlane16_swap(h0[0] + h0[1], h1[0] + h1[1], false, false);
+      u[i] = row_sum16(r[0] + r[1]);  // rows: kp 0, 2, 1, 3
+    }
+    if ((lane & 15) == 0) {
+      const int q = wave * DESC_KPW + (((lane >> 4) & 1) << 1 | (lane >> 5));
+      s_m[q][0] = u[0];
+      s_m[q][1] = u[1];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < DESC_KPW; j++) {
+      const int m10 = wave_sum(pm[0][j]), m01 = wave_sum(pm[1][j]);
       if (lane == 0) {
-        s_m[q][0] = m10;
-        s_m[q][1] = m01;
+        s_m[wave * DESC_KPW + j][0] = m10;
+        s_m[wave * DESC_KPW + j][1] = m01;
       }
     }
   }
@@ -1441,7 +1467,7 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
   for (int j = 0; j < DESC_KPW; j++) {
     if (j < nk) {
       const DescJob& jb = jobs[j];
-      const int q = wave * DESC_KPW + j, slot = slot0 + q, off = offs[j];
+      const int q = wave * DESC_KPW + j, off = offs[j];
       desc_store_patch(lds, lane, regs[j]);
       wave_lds_sync();
       desc_box_table_fused(lds, lane);
@@ -1450,19 +1476,26 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
       const bool interior = jb.x >= DESC_R && jb.y >= DESC_R && jb.x < jb.w - DESC_R && jb.y < jb.h - DESC_R;
       u64 d[4];
       if (interior) {
-        // no test can be skipped: lround as float arithmetic (trunc(v) + trunc(2 * frac), exact), the
-        // table index as one exact fma, the constant part of the index in the instruction offset
+        // no test can be skipped: lround as a biased add and a truncating convert (orbx_lround_small),
+        // the table index as one 24-bit multiply-add, the constant part of the index in the instruction offset
         const uint16_t* tbl = &lds.hs[18 * DESC_HP + 18 + off];
-        // both points of a test side by side in the packed-f32 lanes (v_pk_mul/add/fma_f32);
+        // entry (x, y): the index as one v_mad_i32_i24 (40 is an inline constant), then one shift-and-add to the
+        // address; the empty asm (no instruction) keeps the compiler from distributing the scaling over the
+        // multiply-add, which costs a third instruction per look-up
+        auto at = [&](int x, int y) {
+          int i = __mul24(y, DESC_HP) + x;
+          asm("" : "+v"(i));
+          return tbl[i];
+        };
+        // both points of a test side by side in the packed-f32 lanes (v_pk_mul/add_f32);
         // no contraction (the TU is built with -ffp-contract=off), so each product and sum
         // rounds like the reference's scalar code
-        const f2_t C2 = {c, c}, S2 = {s, s}, HP2 = {(float)DESC_HP, (float)DESC_HP};
+        const f2_t C2 = {c, c}, S2 = {s, s};
 #pragma unroll
         for (int k = 0; k < 4; k++) {
           const f2_t X = patx[k], Y = paty[k];
-          const f2_t rx = lround_f2(C2 * X - S2 * Y), ry = lround_f2(S2 * X + C2 * Y);
-          const f2_t idx = __builtin_elementwise_fma(ry, HP2, rx);
-          d[k] = __ballot(tbl[(int)idx.x] < tbl[(int)idx.y]);
+          const i2_t rx = lround_small2(C2 * X - S2 * Y), ry = lround_small2(S2 * X + C2 * Y);
+          d[k] = __ballot(at(rx.x, ry.x) < at(rx.y, ry.y));
         }
       } else {
 #pragma unroll
@@ -1481,41 +1514,39 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
         }
       }
       wave_lds_sync();
-      if (lane == 0) {
-        orbx_keypoint g;  // kp.x *= scale on int (src/orb.cpp:94-98)
-        g.x = (int)__fmul_rn((float)jb.x, scale[j]);
-        g.y = (int)__fmul_rn((float)jb.y, scale[j]);
-        out_kp[fo + slot] = g;
-        // the same once more as x | y << 16 (coordinates <= 16384): the compact host record, 4 bytes less per slot
-        out_kp16[fo + slot] = (uint32_t)g.x | ((uint32_t)g.y << 16);
-        u64* dd = reinterpret_cast<u64*>(out_desc + fo + slot);
-        dd[0] = d[0];
-        dd[1] = d[1];
-        dd[2] = d[2];
-        dd[3] = d[3];
-        if (host.desc) {
-          s_rec_kp[q] = (uint32_t)g.x | ((uint32_t)g.y << 16);
-          u64* sd = reinterpret_cast<u64*>(s_rec_desc[q]);
-          sd[0] = d[0];
-          sd[1] = d[1];
-          sd[2] = d[2];
-          sd[3] = d[3];
-        }
+      if (lane == 0) {  // the keypoint's record to LDS; the workgroup stores all of them at the end
+        // kp.x *= scale on int (src/orb.cpp:94-98), packed as x | y << 16 (coordinates <= 16384)
+        const int gx = (int)__fmul_rn((float)jb.x, scale[j]), gy = (int)__fmul_rn((float)jb.y, scale[j]);
+        s_rec_kp[q] = (uint32_t)gx | ((uint32_t)gy << 16);
+        u64* sd = reinterpret_cast<u64*>(s_rec_desc[q]);
+        sd[0] = d[0];
+        sd[1] = d[1];
+        sd[2] = d[2];
+        sd[3] = d[3];
       }
     }
   }
-  // The compact record of the workgroup's keypoints, straight into the PINNED HOST mirror of the result block: three
-  // coalesced stores (16 x 32 B of descriptors, 16 x 4 B of packed keypoints, 16 x 4 B of angles) that travel the
-  // host link while the kernel runs -- no copy kernel afterwards, no wait between two streams (orbx_set_host_results)
-  if (host.desc) {  // kernel argument: uniform
-    __syncthreads();
-    const int nq = min(DESC_KPB, count - slot0);
-    if (tid < 2 * nq) {
-      const uint4 v = reinterpret_cast<const uint4*>(s_rec_desc[tid >> 1])[tid & 1];
-      reinterpret_cast<uint4*>(host.desc + fo + slot0)[tid] = v;
-    }
-    if (tid < nq) {
-      host.kp16[fo + slot0 + tid] = s_rec_kp[tid];
+  // The records of the workgroup's keypoints leave in coalesced stores (16 x 32 B of descriptors, 16 x 8 B and
+  // 16 x 4 B of keypoints): per keypoint, a lane moves the ballots of its descriptor into vector registers once.
+  // With host.desc, the compact record also goes straight into the PINNED HOST mirror of the result block (the
+  // descriptors, packed keypoints and angles) and travels the host link while the kernel runs -- no copy kernel
+  // afterwards, no wait between two streams (orbx_set_host_results)
+  __syncthreads();
+  const int nq = min(DESC_KPB, count - slot0);
+  if (tid < 2 * nq) {
+    const uint4 v = reinterpret_cast<const uint4*>(s_rec_desc[tid >> 1])[tid & 1];
+    reinterpret_cast<uint4*>(out_desc + fo + slot0)[tid] = v;
+    if (host.desc) reinterpret_cast<uint4*>(host.desc + fo + slot0)[tid] = v;
+  }
+  if (tid < nq) {
+    const uint32_t kp16 = s_rec_kp[tid];
+    orbx_keypoint g;
+    g.x = (int)(kp16 & 0xffffu);
+    g.y = (int)(kp16 >> 16);
+    out_kp[fo + slot0 + tid] = g;
+    out_kp16[fo + slot0 + tid] = kp16;
+    if (host.desc) {
+      host.kp16[fo + slot0 + tid] = kp16;
       host.angle[fo + slot0 + tid] = __uint_as_float(s_rec_angle[tid]);
     }
   }

@@ -225,3 +225,15 @@ ORBX_HD int orbx_lroundf(float v) {
   if (frac >= 0.5f) t += 1;
   return ((int32_t)orbx_f2u(v) < 0) ? -t : t;
 }
+
+// The same for |v| < 32, for the rotated BRIEF tests (|v| <= 13 * sqrt(2)), in three instructions on the GPU (bit
+// insert, add, truncating convert): lroundf(v) is the TRUNCATION of orbx_lround_biased(v) = v + copysign(h, v),
+// rounded to nearest, with h = 0.5 - 2^-25, the largest float below 0.5.  For v >= 0: a half-way v = n + 0.5 sums
+// to n + 1 - 2^-25, which rounds to n + 1 (n = 0: a tie, to the even 1.0; n >= 1: ulp >= 2^-23); the float below
+// it, n + 0.5 - u, sums to at most n + 1 - u - 2^-25, which rounds to n + 1 - u at most and truncates to n.
+// Negative v mirror this.  tests/test_describe_rounding.py checks every float with |v| < 32 against lroundf.
+ORBX_HD float orbx_lround_biased(float v) {
+  ORBX_NO_CONTRACT
+  return v + __builtin_copysignf(0.5f - 0x1p-25f, v);
+}
+ORBX_HD int orbx_lround_small(float v) { return (int)orbx_lround_biased(v); }

@@ -9,13 +9,19 @@ typedef short ss2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
-// wave-wide integer sum, result in every lane.  DPP within the 16-lane rows
-// (no LDS-crossbar round trips), then the four row sums are combined on the SALU.
-__device__ __forceinline__ int wave_sum(int v) {
+// sum over each 16-lane row, result in every lane of the row (DPP only)
+__device__ __forceinline__ int row_sum16(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0xB1 /*quad_perm:[1,0,3,2]*/, 0xf, 0xf, true);
   v += __builtin_amdgcn_update_dpp(0, v, 0x4E /*quad_perm:[2,3,0,1]*/, 0xf, 0xf, true);
   v += __builtin_amdgcn_update_dpp(0, v, 0x141 /*row_half_mirror*/, 0xf, 0xf, true);
   v += __builtin_amdgcn_update_dpp(0, v, 0x140 /*row_mirror*/, 0xf, 0xf, true);
+  return v;
+}
+
+// wave-wide integer sum, result in every lane.  DPP within the 16-lane rows
+// (no LDS-crossbar round trips), then the four row sums are combined on the SALU.
+__device__ __forceinline__ int wave_sum(int v) {
+  v = row_sum16(v);
   return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
          __builtin_amdgcn_readlane(v, 48);
 }
