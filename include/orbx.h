@@ -384,6 +384,39 @@ int orbx_lk_track(orbx_ctx* ctx, const uint8_t* prev, int prev_stride, const uin
  * (max_level + 1 unless a level would not be larger than the window); -1 on bad arguments */
 int orbx_lk_pyramid_levels(int width, int height, int win_size, int max_level);
 
+/* ---- next row: relative pose -------------------------------
+ * Replaces the reference's get_pose,
+ *   cv::findEssentialMat(pts1, pts2, K, cv::RANSAC, 0.999, 1.0, mask);
+ *   cv::recoverPose(E, pts1, pts2, K, R, t, mask);
+ * (both calls in src/feature_matching.cpp:185-206 and in src/feature_tracking.cpp:222-242)
+ * OpenCV is absent from the image this library was written in: the algorithm keeps OpenCV 4.x's structure
+ * (Nistér five-point RANSAC, Sampson error, RANSACUpdateNumIters, recoverPose's four candidates and
+ * distanceThresh 50) and fixes every choice OpenCV leaves to its RNG or to LAPACK;
+ * parity with OpenCV is unpinned.  K: row-major double[9] (fx = K[0], fy = K[4], cx = K[2], cy = K[5]).
+ * Conventions: x2 = R x1 + t, |t| = 1; E has unit Frobenius norm.  Degenerate input (n < 5, no model, a
+ * solver failure) returns ORBX_OK with inliers = good = 0, E = 0, R = I, t = 0 and an all-zero mask.
+ * inliers: RANSAC inliers of E; good: those that triangulate in front of both cameras (the final mask);
+ * iters: RANSAC iterations run.  The samples depend on (seed, iteration) only. */
+/* get_pose on host arrays: pts*_xy are n float (x, y) pairs (matched keypoints or LK output); mask
+ * (n bytes, may be NULL) receives recoverPose's final mask.  src/feature_matching.cpp:185-206,
+ * src/feature_tracking.cpp:222-242 */
+int orbx_estimate_pose(orbx_ctx* ctx, const float* pts1_xy, const float* pts2_xy, int n, const double* K, double prob,
+                       double threshold, int max_iters, uint64_t seed, double* E, double* R, double* t, uint8_t* mask,
+                       int32_t* inliers, int32_t* good, int32_t* iters);
+/* Device-resident: poses every pair matched by the last orbx_batch_match_consecutive, on the batch's stream,
+ * from the matches and both frames' level-0 keypoints (int -> float -> double), in the compact query order
+ * orbx_batch_match_fetch returns.  ORBX_ERR_INVALID_ARG if the last batch has not been matched.
+ * src/feature_matching.cpp:185-206, src/feature_tracking.cpp:222-242 */
+int orbx_batch_pose_consecutive(orbx_ctx* ctx, const double* K, double prob, double threshold, int max_iters,
+                                uint64_t seed);
+/* results of pairs [first, first + n) of the last orbx_batch_pose_consecutive; E, R: 9 doubles per pair,
+ * t: 3; any output may be NULL */
+int orbx_batch_pose_fetch(orbx_ctx* ctx, int first, int n, double* E, double* R, double* t, int32_t* inliers,
+                          int32_t* good, int32_t* iters);
+/* the final mask of one pair, one byte per match in orbx_batch_match_fetch order; *count = match count,
+ * ORBX_ERR_CAPACITY if > capacity */
+int orbx_batch_pose_mask(orbx_ctx* ctx, int pair, uint8_t* mask, int capacity, int* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,108 @@
+// Test infrastructure: a plain sequential restatement of the relative-pose step
+// (findEssentialMat(RANSAC) + recoverPose, DESIGN.md §9 rank 5 rules 1-7), in
+// OpenCV's loop order: for (i = 0; i < niters; ++i) over samples, models and
+// points.  Only the per-sample arithmetic (solver, Sampson error, log, SVD,
+// triangulation, sample hash) comes from orbx_pose_math.h; the orchestration
+// below is written independently of the kernels, so the GPU test that compares
+// the two checks the kernels' chunked, parallel decomposition.
+//
+// Built by tests/test_pose.py with
+//   g++ -O2 -std=c++17 -ffp-contract=off -fno-fast-math -shared -fPIC
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../visual-odometry-gpu_amd/csrc/orbx_pose_math.h"
+
+extern "C" {
+
+double seq_log(double x) { return pose_log(x); }
+double seq_sqrt(double x) { return pose_sqrt(x); }
+int seq_update_niters(double p, double ep, int max_iters) { return pose_update_niters(p, ep, max_iters); }
+
+// pts: x1[5], y1[5], x2[5], y2[5] (normalised); models: 10 x 9
+int seq_solve5(const double* pts, double* models) {
+  double w[POSE_WS];
+  for (int k = 0; k < 5; k++) pose_put_point<1>(w, k, pts[k], pts[5 + k], pts[10 + k], pts[15 + k]);
+  const int n = pose_solve5<1>(w);
+  memcpy(models, w + POSE_WS_MODELS, sizeof(double) * 9 * n);
+  return n;
+}
+
+int seq_decompose(const double* E, double* R1, double* R2, double* t) { return pose_decompose(E, R1, R2, t); }
+
+// the whole get_pose: pts*_xy are n float (x, y) pairs in pixels, K row-major 3x3
+int seq_estimate_pose(const float* pts1_xy, const float* pts2_xy, int n, const double* K, double prob,
+                      double threshold, int max_iters, uint64_t seed, double* E, double* R, double* t,
+                      uint8_t* mask, int* inliers, int* good, int* iters) {
+  for (int i = 0; i < 9; i++) {
+    E[i] = 0.0;
+    R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  }
+  t[0] = t[1] = t[2] = 0.0;
+  *inliers = *good = *iters = 0;
+  if (mask)
+    for (int i = 0; i < n; i++) mask[i] = 0;
+  if (n < 5) return 0;
+  // rule 1: normalisation
+  const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+  std::vector<double> x1(n), y1(n), x2(n), y2(n);
+  for (int i = 0; i < n; i++) {
+    x1[i] = ((double)pts1_xy[2 * i] - cx) / fx;
+    y1[i] = ((double)pts1_xy[2 * i + 1] - cy) / fy;
+    x2[i] = ((double)pts2_xy[2 * i] - cx) / fx;
+    y2[i] = ((double)pts2_xy[2 * i + 1] - cy) / fy;
+  }
+  const double thr = threshold / ((fx + fy) / 2.0);
+  const float tf = (float)(thr * thr);
+  // rule 5: RANSACPointSetRegistrator::run
+  int niters = max_iters, best = 0;
+  double bestE[9] = {0};
+  double w[POSE_WS];
+  int i = 0;
+  for (i = 0; i < niters; ++i) {
+    uint32_t idx[5];
+    if (!pose_sample(seed, (uint32_t)i, (uint32_t)n, idx)) continue;
+    for (int k = 0; k < 5; k++) pose_put_point<1>(w, k, x1[idx[k]], y1[idx[k]], x2[idx[k]], y2[idx[k]]);
+    const int nm = pose_solve5<1>(w);
+    for (int m = 0; m < nm; m++) {
+      const double* Em = w + POSE_WS_MODELS + 9 * m;
+      int count = 0;
+      for (int p = 0; p < n; p++) count += pose_sampson(Em, x1[p], y1[p], x2[p], y2[p]) <= tf;
+      if (count > (best > 4 ? best : 4)) {
+        best = count;
+        memcpy(bestE, Em, sizeof bestE);
+        niters = pose_update_niters(prob, (double)(n - count) / n, niters);
+      }
+    }
+  }
+  *iters = i;
+  if (best == 0) return 0;
+  // rule 6: recoverPose on the inliers of the best model
+  std::vector<uint8_t> inl(n);
+  for (int p = 0; p < n; p++) inl[p] = pose_sampson(bestE, x1[p], y1[p], x2[p], y2[p]) <= tf;
+  double R1[9], R2[9], tu[3];
+  if (!pose_decompose(bestE, R1, R2, tu)) {
+    *iters = i;
+    return 0;
+  }
+  const double* Rc[4] = {R1, R2, R1, R2};
+  const double sg[4] = {1.0, 1.0, -1.0, -1.0};
+  int cnt[4] = {0, 0, 0, 0};
+  for (int c = 0; c < 4; c++)
+    for (int p = 0; p < n; p++) cnt[c] += inl[p] && pose_point_good(Rc[c], tu, sg[c], x1[p], y1[p], x2[p], y2[p]);
+  int ch = 0;
+  for (int c = 1; c < 4; c++)
+    if (cnt[c] > cnt[ch]) ch = c;
+  memcpy(E, bestE, sizeof bestE);
+  memcpy(R, Rc[ch], sizeof(double) * 9);
+  for (int k = 0; k < 3; k++) t[k] = sg[ch] * tu[k];
+  *inliers = best;
+  *good = cnt[ch];
+  if (mask)
+    for (int p = 0; p < n; p++) mask[p] = inl[p] && pose_point_good(Rc[ch], tu, sg[ch], x1[p], y1[p], x2[p], y2[p]);
+  return 0;
+}
+
+}  // extern "C"

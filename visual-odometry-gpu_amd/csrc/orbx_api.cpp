@@ -192,6 +192,12 @@ struct orbx_ctx {
   size_t lk_host_bytes = 0;
   int lk_w = 0, lk_h = 0, lk_top = -1, lk_win = 0, lk_last = -1;  // lk_last: buffer holding the last `next`
   int match_pairs = 0;
+  // batch serial: bumped by every batch run; match_serial: the serial the last batch match was made on
+  long long batch_serial = 0, match_serial = -1;
+  // relative pose (orbx_pose.hip): batched results (pb_*) and the host-array entry's own buffers (ph_*)
+  DevBuf pb_pts, pb_n, pb_out, pb_mask, ph_in, ph_pts, ph_n, ph_out, ph_mask;
+  int pose_pairs = 0, pose_cap = 0;
+  hipStream_t pose_stream = nullptr;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -1237,6 +1243,7 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
   if (lanes) c->next_lane ^= 1;
   c->out_layout = make_out_layout(n, c->plan.out_cap > 0 ? c->plan.out_cap : 1);
   c->last_n = n;
+  c->batch_serial++;
   c->last_stream = s;
   c->layoutb[blk] = c->out_layout;
   c->nb[blk] = n;
@@ -1409,7 +1416,8 @@ void orbx_destroy(orbx_ctx* c) {
   }
   DevBuf* sb[] = {&c->s_img_a, &c->s_img_b, &c->s_f32,  &c->s_u16, &c->s_mask, &c->s_kps,   &c->s_f32b, &c->s_desc,
                   &c->s_i32,   &c->s_kern,  &c->s_tiles, &c->m_q,    &c->m_t,   &c->m_idx,  &c->m_dist,  &c->m_match, &c->m_cnt,
-                  &c->lk_img[0], &c->lk_img[1], &c->lk_deriv, &c->lk_io};
+                  &c->lk_img[0], &c->lk_img[1], &c->lk_deriv, &c->lk_io, &c->pb_pts, &c->pb_n, &c->pb_out,
+                  &c->pb_mask, &c->ph_in, &c->ph_pts, &c->ph_n, &c->ph_out, &c->ph_mask};
   if (c->lk_host) (void)hipHostFree(c->lk_host);
   for (DevBuf* b : sb)
     if (b->p) (void)hipFree(b->p);
@@ -2413,6 +2421,7 @@ int orbx_batch_match_consecutive(orbx_ctx* c, double ratio) {
   HIPCHK(c, orbx_launch_knn2(s, n - 1, cap, desc, counts, (size_t)cap, desc + cap, counts + 1, (size_t)cap, ratio,
                              (int32_t*)c->m_idx.p, (int32_t*)c->m_dist.p, (int32_t*)c->m_match.p, (size_t)cap));
   c->match_pairs = n - 1;
+  c->match_serial = c->batch_serial;
   return ORBX_OK;
 }
 
@@ -2570,6 +2579,126 @@ int orbx_lk_pyramid_levels(int width, int height, int win_size, int max_level) {
   if (width < 1 || height < 1 || win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
     return -1;
   return lk_geometry(width, height, win_size, max_level).top + 1;
+}
+
+}  // extern "C"
+
+// ---- relative pose (next row) ---------------------------
+
+namespace {
+bool pose_args_ok(const double* K, double prob, double threshold, int max_iters) {
+  return K && K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) &&
+         std::isfinite(K[5]) && std::isfinite(prob) && std::isfinite(threshold) && threshold >= 0 && max_iters >= 0;
+}
+void pose_unpack(const OrbxPoseOut& r, double* E, double* R, double* t, int32_t* inliers, int32_t* good,
+                 int32_t* iters) {
+  if (E) memcpy(E, r.E, sizeof r.E);
+  if (R) memcpy(R, r.R, sizeof r.R);
+  if (t) memcpy(t, r.t, sizeof r.t);
+  if (inliers) *inliers = r.inliers;
+  if (good) *good = r.good;
+  if (iters) *iters = r.iters;
+}
+}  // namespace
+
+extern "C" {
+
+int orbx_estimate_pose(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, int n, const double* K, double prob,
+                       double threshold, int max_iters, uint64_t seed, double* E, double* R, double* t, uint8_t* mask,
+                       int32_t* inliers, int32_t* good, int32_t* iters) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (n < 0 || (n > 0 && (!pts1_xy || !pts2_xy)) || !E || !R || !t || !inliers || !good || !iters ||
+      !pose_args_ok(K, prob, threshold, max_iters))
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
+  const int cap = n > 0 ? n : 1;
+  int st;
+  if ((st = ensure(c, c->ph_in, sizeof(float) * 4 * (size_t)cap)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ph_pts, sizeof(OrbxPosePt) * (size_t)cap)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ph_n, sizeof(int32_t))) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ph_out, sizeof(OrbxPoseOut))) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ph_mask, (size_t)cap)) != ORBX_OK) return st;
+  hipStream_t s = c->stream;
+  float* d_p1 = (float*)c->ph_in.p;
+  float* d_p2 = d_p1 + 2 * (size_t)cap;
+  if (n > 0) {
+    HIPCHK(c, hipMemcpyAsync(d_p1, pts1_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_p2, pts2_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(c, orbx_launch_pose_prep_host(s, n, d_p1, d_p2, K, (OrbxPosePt*)c->ph_pts.p, (int32_t*)c->ph_n.p));
+  HIPCHK(c, orbx_launch_pose_ransac(s, 1, cap, (const OrbxPosePt*)c->ph_pts.p, (const int32_t*)c->ph_n.p, K, prob,
+                                    threshold, max_iters, seed, (OrbxPoseOut*)c->ph_out.p, (uint8_t*)c->ph_mask.p));
+  OrbxPoseOut r;
+  HIPCHK(c, hipMemcpyAsync(&r, c->ph_out.p, sizeof r, hipMemcpyDeviceToHost, s));
+  if (mask && n > 0) HIPCHK(c, hipMemcpyAsync(mask, c->ph_mask.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  pose_unpack(r, E, R, t, inliers, good, iters);
+  return ORBX_OK;
+}
+
+int orbx_batch_pose_consecutive(orbx_ctx* c, const double* K, double prob, double threshold, int max_iters,
+                                uint64_t seed) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!pose_args_ok(K, prob, threshold, max_iters)) return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
+  if (c->match_pairs <= 0 || c->match_serial != c->batch_serial)
+    return fail(c, ORBX_ERR_INVALID_ARG, "the last batch has not been matched (orbx_batch_match_consecutive)");
+  // the pose buffers are ONE set per context, like the matcher's
+  if (c->lane_stream[1]) HIPCHK(c, lanes_sync(c));
+  const int npairs = c->match_pairs, cap = c->plan.out_cap > 0 ? c->plan.out_cap : 1;
+  const size_t e = (size_t)npairs * cap;
+  int st;
+  if ((st = ensure(c, c->pb_pts, sizeof(OrbxPosePt) * e)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->pb_n, sizeof(int32_t) * (size_t)npairs)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->pb_out, sizeof(OrbxPoseOut) * (size_t)npairs)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->pb_mask, e)) != ORBX_OK) return st;
+  const OutLayout& o = c->out_layout;
+  hipStream_t s = c->last_stream ? c->last_stream : c->stream;
+  HIPCHK(c, orbx_launch_pose_prep_batch(s, npairs, cap, (const int32_t*)(c->d_out + o.counts),
+                                        (const orbx_keypoint*)(c->d_out + o.kp), (const int32_t*)c->m_match.p, K,
+                                        (OrbxPosePt*)c->pb_pts.p, (int32_t*)c->pb_n.p));
+  HIPCHK(c, orbx_launch_pose_ransac(s, npairs, cap, (const OrbxPosePt*)c->pb_pts.p, (const int32_t*)c->pb_n.p, K, prob,
+                                    threshold, max_iters, seed, (OrbxPoseOut*)c->pb_out.p, (uint8_t*)c->pb_mask.p));
+  c->pose_pairs = npairs;
+  c->pose_cap = cap;
+  c->pose_stream = s;
+  return ORBX_OK;
+}
+
+int orbx_batch_pose_fetch(orbx_ctx* c, int first, int n, double* E, double* R, double* t, int32_t* inliers,
+                          int32_t* good, int32_t* iters) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (c->pose_pairs <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been posed");
+  if (first < 0 || n < 0 || first + n > c->pose_pairs)
+    return fail(c, ORBX_ERR_INVALID_ARG, "pairs outside the last posed batch");
+  if (n == 0) return ORBX_OK;
+  std::vector<OrbxPoseOut> r((size_t)n);
+  HIPCHK(c, hipMemcpyAsync(r.data(), (const OrbxPoseOut*)c->pb_out.p + first, sizeof(OrbxPoseOut) * (size_t)n,
+                           hipMemcpyDeviceToHost, c->pose_stream));
+  HIPCHK(c, hipStreamSynchronize(c->pose_stream));
+  for (int i = 0; i < n; i++)
+    pose_unpack(r[(size_t)i], E ? E + 9 * i : nullptr, R ? R + 9 * i : nullptr, t ? t + 3 * i : nullptr,
+                inliers ? inliers + i : nullptr, good ? good + i : nullptr, iters ? iters + i : nullptr);
+  return ORBX_OK;
+}
+
+int orbx_batch_pose_mask(orbx_ctx* c, int pair, uint8_t* mask, int capacity, int* count) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!count || capacity < 0 || (capacity > 0 && !mask)) return fail(c, ORBX_ERR_INVALID_ARG, "bad mask arguments");
+  if (pair < 0 || pair >= c->pose_pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last posed batch");
+  int32_t np = 0;
+  HIPCHK(c, hipMemcpyAsync(&np, (const int32_t*)c->pb_n.p + pair, sizeof np, hipMemcpyDeviceToHost, c->pose_stream));
+  HIPCHK(c, hipStreamSynchronize(c->pose_stream));
+  *count = np;
+  if (np > capacity) return fail(c, ORBX_ERR_CAPACITY, "capacity smaller than the pair's match count");
+  if (np > 0) {
+    HIPCHK(c, hipMemcpyAsync(mask, (const uint8_t*)c->pb_mask.p + (size_t)pair * c->pose_cap, (size_t)np,
+                             hipMemcpyDeviceToHost, c->pose_stream));
+    HIPCHK(c, hipStreamSynchronize(c->pose_stream));
+  }
+  return ORBX_OK;
 }
 
 }  // extern "C"

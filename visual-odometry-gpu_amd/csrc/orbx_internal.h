@@ -258,3 +258,20 @@ hipError_t orbx_launch_select_flat(hipStream_t s, const float* d_resp, int n, in
 hipError_t orbx_launch_knn2(hipStream_t s, int npairs, int max_nq, const orbx_descriptor* d_q, const int32_t* d_qcount,
                             size_t qstride, const orbx_descriptor* d_t, const int32_t* d_tcount, size_t tstride,
                             double ratio, int32_t* d_idx, int32_t* d_dist, int32_t* d_match, size_t ostride);
+
+// relative pose (orbx_pose.hip): one normalised correspondence, one pair's result
+struct OrbxPosePt {
+  double x1, y1, x2, y2;
+};
+struct OrbxPoseOut {
+  double E[9], R[9], t[3];
+  int32_t inliers, good, iters, pad;
+};
+hipError_t orbx_launch_pose_prep_batch(hipStream_t s, int npairs, int cap, const int32_t* d_counts,
+                                       const orbx_keypoint* d_kp, const int32_t* d_match, const double* K,
+                                       OrbxPosePt* d_pts, int32_t* d_npts);
+hipError_t orbx_launch_pose_prep_host(hipStream_t s, int n, const float* d_p1, const float* d_p2, const double* K,
+                                      OrbxPosePt* d_pts, int32_t* d_npts);
+hipError_t orbx_launch_pose_ransac(hipStream_t s, int npairs, int cap, const OrbxPosePt* d_pts, const int32_t* d_npts,
+                                   const double* K, double prob, double threshold, int max_iters, uint64_t seed,
+                                   OrbxPoseOut* d_out, uint8_t* d_mask);

@@ -639,4 +639,27 @@ inline void track_optical_flow(LKTracker& lk, const Image* img1, const Image& im
   pts2 = v2;
 }
 
+// ---- relative pose (next row) -----------------------------------
+// VisualOdom::get_pose (src/feature_matching.cpp:185-206, src/feature_tracking.cpp:222-242):
+//   E = cv::findEssentialMat(pts1, pts2, K, cv::RANSAC, 0.999, 1.0, mask); cv::recoverPose(E, pts1, pts2, K, R, t, mask);
+// K, R: row-major 3x3; t: unit translation with x2 = R x1 + t; mask: recoverPose's final mask.
+inline void get_pose(const std::vector<Point2f>& pts1, const std::vector<Point2f>& pts2, const double K[9],
+                     double R[9], double t[3], std::vector<uint8_t>& mask, double prob = 0.999,
+                     double threshold = 1.0, int max_iters = 1000, uint64_t seed = 0) {
+  if (pts1.size() != pts2.size()) throw std::invalid_argument("get_pose: pts1 and pts2 differ in size");
+  const int n = (int)pts1.size();
+  std::vector<float> a((size_t)2 * n), b((size_t)2 * n);
+  for (int i = 0; i < n; i++) {
+    a[2 * i] = pts1[(size_t)i].x, a[2 * i + 1] = pts1[(size_t)i].y;
+    b[2 * i] = pts2[(size_t)i].x, b[2 * i + 1] = pts2[(size_t)i].y;
+  }
+  mask.assign((size_t)n, 0);
+  double E[9];
+  int32_t inliers = 0, good = 0, iters = 0;
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c, orbx_estimate_pose(c, a.data(), b.data(), n, K, prob, threshold, max_iters, seed, E, R, t,
+                              n > 0 ? mask.data() : nullptr, &inliers, &good, &iters),
+        "orbx_estimate_pose");
+}
+
 }  // namespace orbx

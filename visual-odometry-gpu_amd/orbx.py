@@ -34,6 +34,7 @@ EXPORTS = [
     "orbx_orientations", "orbx_brief", "orbx_harris", "orbx_blur5_sep", "orbx_blur5_273", "orbx_conv2d",
     "orbx_gaussian_blur_conv", "orbx_gaussian_kernel", "orbx_sobel", "orbx_build_pyramid_level",
     "orbx_select_top", "orbx_knn2", "orbx_match_ratio", "orbx_batch_match_consecutive", "orbx_batch_match_fetch",
+    "orbx_estimate_pose", "orbx_batch_pose_consecutive", "orbx_batch_pose_fetch", "orbx_batch_pose_mask",
 ]
 
 
@@ -502,6 +503,70 @@ def _matcher_methods():
 
 
 _matcher_methods()
+
+
+def _pose_methods():
+    """Relative pose: findEssentialMat(RANSAC) + recoverPose (include/orbx.h)."""
+
+    def _K(K):
+        K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))
+        return K, K.ctypes.data_as(C.POINTER(C.c_double))
+
+    def estimate_pose(self, pts1, pts2, K, prob=0.999, threshold=1.0, max_iters=1000, seed=0):
+        """get_pose on (n, 2) point arrays: dict with E, R (3x3), t (3,), mask (n,), inliers, good, iters."""
+        p1 = np.ascontiguousarray(np.asarray(pts1, np.float32).reshape(-1, 2))
+        p2 = np.ascontiguousarray(np.asarray(pts2, np.float32).reshape(-1, 2))
+        if p1.shape != p2.shape:
+            raise ValueError("pts1 and pts2 differ in shape")
+        n = p1.shape[0]
+        K, kp = _K(K)
+        E, R, t = np.zeros(9), np.zeros(9), np.zeros(3)
+        mask = np.zeros(max(n, 1), np.uint8)
+        inl, good, iters = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        f = self._lib.orbx_estimate_pose
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
+                      C.c_int, C.c_uint64] + [C.c_void_p] * 7
+        self._chk(f(self._h, _ptr(p1), _ptr(p2), n, kp, prob, threshold, max_iters, seed, _ptr(E), _ptr(R), _ptr(t),
+                    _ptr(mask), C.byref(inl), C.byref(good), C.byref(iters)))
+        return {"E": E.reshape(3, 3), "R": R.reshape(3, 3), "t": t, "mask": mask[:n], "inliers": inl.value,
+                "good": good.value, "iters": iters.value}
+
+    def batch_pose_consecutive(self, K, prob=0.999, threshold=1.0, max_iters=1000, seed=0):
+        """Poses every pair of the last batch_match_consecutive on the device (no host round trip)."""
+        K, kp = _K(K)
+        f = self._lib.orbx_batch_pose_consecutive
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_uint64]
+        self._chk(f(self._h, kp, prob, threshold, max_iters, seed))
+        v = BatchView()
+        self._chk(self._lib.orbx_batch_results_device(self._h, C.byref(v)))
+        self._pose_pairs = v.n - 1
+
+    def batch_pose_fetch(self, first=0, n=None):
+        """dict of arrays for pairs [first, first + n): E, R (n, 3, 3), t (n, 3), inliers, good, iters (n,)."""
+        if n is None:
+            n = getattr(self, "_pose_pairs", 0) - first
+        m = max(n, 0)  # a negative n (nothing posed yet) is the C entry's to refuse
+        E, R, t = np.zeros((m, 3, 3)), np.zeros((m, 3, 3)), np.zeros((m, 3))
+        inl, good, iters = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        self._chk(self._lib.orbx_batch_pose_fetch(self._h, first, n, _ptr(E), _ptr(R), _ptr(t), _ptr(inl), _ptr(good),
+                                                  _ptr(iters)))
+        return {"E": E, "R": R, "t": t, "inliers": inl, "good": good, "iters": iters}
+
+    def batch_pose_mask(self, pair):
+        """final mask of one pair, in batch_match_fetch order."""
+        cnt = C.c_int(0)
+        st = self._lib.orbx_batch_pose_mask(self._h, pair, None, 0, C.byref(cnt))
+        if st not in (OK, ERR_CAPACITY):
+            self._chk(st)
+        mask = np.zeros(max(cnt.value, 1), np.uint8)
+        self._chk(self._lib.orbx_batch_pose_mask(self._h, pair, _ptr(mask), cnt.value, C.byref(cnt)))
+        return mask[:cnt.value]
+
+    for f in (estimate_pose, batch_pose_consecutive, batch_pose_fetch, batch_pose_mask):
+        setattr(Context, f.__name__, f)
+
+
+_pose_methods()
 
 
 def gaussian_kernel(K, sigma=-1.0):
