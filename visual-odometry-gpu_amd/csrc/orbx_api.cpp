@@ -1103,7 +1103,9 @@ int enqueue_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int row_stride, s
   // result block sections are laid out for (n, pool slot capacity)
   c->out_layout = make_out_layout(n, P.out_cap > 0 ? P.out_cap : 1);
   const OutLayout& o = c->out_layout;
-  static const int spread = [] {  // ORBX_SELECT_SPREAD=0/1 forces the fused / the three-kernel selection (A/B timing)
+  // ORBX_SELECT_SPREAD=0/1 forces the fused / the three-kernel selection (A/B timing); frames whose candidates do not
+  // fit the fused kernel's LDS take the three kernels whatever it says (orbx_launch_level_select_auto)
+  static const int spread = [] {
     const char* e = getenv("ORBX_SELECT_SPREAD");
     return e ? atoi(e) : -1;
   }();

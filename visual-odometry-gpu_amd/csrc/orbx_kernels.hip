@@ -492,10 +492,16 @@ __device__ __forceinline__ float harris_fast(const uint8_t* img, int w, int h, i
   return __fsub_rn(det, __fmul_rn(__fmul_rn(kk, trace), trace));
 }
 
+// harris_fast<K> takes (K+2)^2 windows that leave the image by at most one pixel (k_level_select's two Harris passes
+// must agree with harris_any on this, bit-identity depends on it)
+__device__ __forceinline__ bool harris_fast_ok(int w, int h, int x, int y, int K) {
+  const int m = K / 2 + 1;
+  return x >= m - 1 && y >= m - 1 && x <= w - m && y <= h - m && w >= 4 && h >= 4;
+}
+
 __device__ __forceinline__ float harris_any(const uint8_t* img, int w, int h, int pitch, int x, int y,
                                             const float* __restrict__ g, int K, float kk) {
-  const int m = K / 2 + 1;  // the fast path takes (K+2)^2 windows that leave the image by at most one pixel
-  if (x >= m - 1 && y >= m - 1 && x <= w - m && y <= h - m && w >= 4 && h >= 4) {
+  if (harris_fast_ok(w, h, x, y, K)) {
     if (K == 7) return harris_fast<7>(img, w, h, pitch, x, y, g, kk);
     if (K == 5) return harris_fast<5>(img, w, h, pitch, x, y, g, kk);
     if (K == 3) return harris_fast<3>(img, w, h, pitch, x, y, g, kk);
@@ -637,152 +643,235 @@ __global__ __launch_bounds__(256) void k_harris2_flat(const uint8_t* __restrict_
 
 // ---------------------------------------------------------------------------
 // 4-6 fused: ordered compaction -> Harris -> top-N selection, one 512-thread
-// workgroup per (level, frame).  The three separate kernels were each bound by
-// launch + latency (512..2048 short workgroups, 10 + 35 + 22 us per batch); one
-// workgroup now carries its level's candidates from the survivor mask to the
-// selected list through LDS, with no intermediate global traffic and two
-// launches fewer.
-//   phase 1  row-major walk of the mask words (block scan of popcounts), first
-//            `cap` survivors -> LDS (src/orb_cpu.cpp:108-110 order and cap)
-//   phase 2  Harris response per candidate (thread per candidate, harris_any)
-//   phase 3  rank by the 64-bit (response desc, index asc) key, keep `quota`
+// workgroup per group of levels of a frame: all of them in large batches (no
+// lane idles but in a level's last run of 64), one in small batches (more
+// workgroups than frames; see orbx_launch_level_select).  Ranks come from
+// sorted runs instead of n^2 key compares per level.
+//   phase 1  wave w walks the masks of the group's levels w, w + 8, ...: row-major order,
+//            wave scan of popcounts, first `cap` survivors -> LDS slots of the
+//            level (src/orb_cpu.cpp:108-110 order and cap).  Row-major mode:
+//            straight to the output slots, done.
+//   phase 2  Harris, thread per candidate, a wave per run of 64 candidates of
+//            one level (the group's runs dealt over the 8 waves) -> (response desc, index asc)
+//            u64 keys, each run sorted in registers (bitonic)
+//   phase 3  a key's rank is its place in its run plus a binary search in every
+//            other run of its level; ranks < quota are written
+// A level owns LVL_RUN-aligned slots [slot_l, slot_l + cap rounded up); keys past
+// its count are 0, below every real key (the low word ~index is never 0).
 // The selected keypoints of level l go to the STATIC slots [out_off_l, out_off_l
 // + quota_l) of the frame (out_off_l = sum of the lower levels' quotas) plus a
 // per-level count; k_describe2 compacts them into the final order.
 #define LVL_THREADS 512
-__global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_level_select(OrbxPlan plan, int mode, const u64* __restrict__ mask,
-                                                              const uint8_t* __restrict__ pyr,
-                                                              const float* __restrict__ gauss, int K, float kk,
-                                                              orbx_keypoint* __restrict__ sel_lkp,
-                                                              float* __restrict__ sel_resp,
-                                                              int32_t* __restrict__ sel_count,
-                                                              uint32_t* __restrict__ need) {
+#define LVL_WAVES (LVL_THREADS / 64)
+#define LVL_Q 16    // mask words per lane and round of a compaction walk (1024 per wave in flight)
+#define LVL_RUN 64  // keys per sorted run
+#define LVL_MAX_SLOTS 4096  // candidate slots of a frame the kernel holds in LDS (16 B each)
+
+// LDS slots of a plan's frame in k_level_select (each level's cap rounded up to whole runs)
+__host__ __device__ inline int lvl_slots(const OrbxPlan& plan, int nl) {
+  int s = 0;
+  for (int l = 0; l < nl; l++) s += (plan.L[l].cap + LVL_RUN - 1) & ~(LVL_RUN - 1);
+  return s;
+}
+
+__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
+  const int lo = __shfl_xor((int)(uint32_t)v, m), hi = __shfl_xor((int)(uint32_t)(v >> 32), m);
+  return ((u64)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
+// the 64 keys of a wave, one per lane, sorted descending (lane 0 holds the largest)
+__device__ __forceinline__ u64 wave_sort_desc(u64 k, int lane) {
+#pragma unroll
+  for (int b = 2; b <= 64; b <<= 1)
+#pragma unroll
+    for (int j = b >> 1; j > 0; j >>= 1) {
+      const u64 o = shfl_xor_u64(k, j);
+      // the lower lane of a pair keeps the larger key in blocks sorted descending ((lane & b) == 0)
+      const bool keep_max = ((lane & j) == 0) == ((lane & b) == 0);
+      k = keep_max ? (o > k ? o : k) : (o < k ? o : k);
+    }
+  return k;
+}
+
+// run r of the level-ordered list of runs of levels [l0, l1) -> (level, run within it); uniform
+__device__ __forceinline__ int lvl_of_run(const int* s_runs, int l0, int l1, int& r) {
+  int l = l0;
+  while (l < l1 - 1) {
+    const int c = __builtin_amdgcn_readfirstlane(s_runs[l]);
+    if (r < c) break;
+    r -= c;
+    l++;
+  }
+  return l;
+}
+
+// KF: the Harris window of the fast path (3, 5 or 7; 0: none, every candidate through harris_at)
+template <int KF>
+__global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_level_select(
+    OrbxPlan plan, int lpg, int mode, const u64* __restrict__ mask, const uint8_t* __restrict__ pyr,
+    const float* __restrict__ gauss, int K, float kk, orbx_keypoint* __restrict__ sel_lkp,
+    float* __restrict__ sel_resp, int32_t* __restrict__ sel_count, uint32_t* __restrict__ need) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-  __shared__ int s_wsum[4][LVL_THREADS / 64];
-  // grid = (frames, levels), the frame index dispatched fastest.  Workgroups are dealt round-robin over
-  // the 8 XCDs in linear order: with (levels, frames) and 8 levels every XCD got ONE level of every
-  // frame, level 0 (7x the work of level 7) all on one XCD, and the launch took as long as that XCD
-  // needed (84 us per 256 frames; XCD placement is a matter of speed only).
-  const int f = blockIdx.x, l = blockIdx.y;
-  const OrbxLevel& L = plan.L[l];
-  const int cap = L.cap, cap2 = (cap + 1) & ~1;
-  u64* s_key = reinterpret_cast<u64*>(s_dyn);                         // [cap2]
-  uint32_t* s_kp = reinterpret_cast<uint32_t*>(s_dyn + 8 * (size_t)cap2);  // [cap]  y << 16 | x
-  float* s_r = reinterpret_cast<float*>(s_dyn + 12 * (size_t)cap2);   // [cap]
-  const u64* m = mask + (size_t)f * plan.mask_words + L.mask_off;
-  const int nwords = L.h * L.mask_wpr;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int s_n[ORBX_MAX_LEVELS];      // candidates of each level
+  __shared__ int s_runs[ORBX_MAX_LEVELS];   // runs of 64 keys of each level
+  // grid = (frames, level groups), the frame index dispatched fastest: workgroups are dealt round-robin over the 8
+  // XCDs.  Workgroup (f, g) selects levels [g * lpg, (g + 1) * lpg) of frame f
+  const int f = blockIdx.x, nl = plan.nlevels;
+  const int l0 = blockIdx.y * lpg, l1 = min(l0 + lpg, nl);
+  const int nslots = lvl_slots(plan, nl);
+  u64* s_key = reinterpret_cast<u64*>(s_dyn);                            // [nslots]
+  uint32_t* s_kp = reinterpret_cast<uint32_t*>(s_dyn + 8 * (size_t)nslots);  // [nslots]  y << 16 | x
+  float* s_r = reinterpret_cast<float*>(s_dyn + 12 * (size_t)nslots);     // [nslots]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const size_t fo = (size_t)f * plan.out_cap;
 
-  // phase 1: ordered compaction.  Four chunks of LVL_THREADS words per round: their loads are in
-  // flight together (one memory round trip per 2048 words; level 0 usually needs one round)
-  int base = 0;
-  for (int w0 = 0; w0 < nwords && base < cap; w0 += 4 * LVL_THREADS) {
-    u64 v[4];
+  // phase 1: ordered compaction, one wave per level
+  for (int l = l0 + wave; l < l1; l += LVL_WAVES) {
+    const OrbxLevel& L = plan.L[l];
+    const int cap = L.cap, slot = lvl_slots(plan, l);
+    const u64* m = mask + (size_t)f * plan.mask_words + L.mask_off;
+    const int nwords = L.h * L.mask_wpr;
+    int base = 0, last = -1;  // last: row of survivor cap - 1 (in the lane that found it)
+    for (int w0 = 0; w0 < nwords && base < cap; w0 += 64 * LVL_Q) {
+      u64 v[LVL_Q];
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int i = w0 + LVL_THREADS * q + tid;
-      v[q] = i < nwords ? m[i] : 0ull;
-    }
-    int incl[4], c[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      c[q] = __popcll(v[q]);
-      incl[q] = wave_scan_incl(c[q]);
-      if (lane == 63) s_wsum[q][wave] = incl[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      int woff = 0, tot = 0;
-#pragma unroll
-      for (int k = 0; k < LVL_THREADS / 64; k++) {
-        const int sv = s_wsum[q][k];
-        if (k < wave) woff += sv;
-        tot += sv;
+      for (int q = 0; q < LVL_Q; q++) {
+        const int i = w0 + 64 * q + lane;
+        v[q] = i < nwords ? m[i] : 0ull;
       }
-      int pos = base + woff + incl[q] - c[q];
-      if (c[q] && pos < cap) {
-        const int i = w0 + LVL_THREADS * q + tid;
-        const int y = i / L.mask_wpr, xw = i - y * L.mask_wpr;
-        u64 w = v[q];
-        while (w && pos < cap) {
-          const int b = __ffsll((long long)w) - 1;
-          w &= w - 1;
-          s_kp[pos++] = ((uint32_t)y << 16) | (uint32_t)orbx_mask_x(L, xw, b);
+#pragma unroll
+      for (int q = 0; q < LVL_Q; q++) {
+        const int c = __popcll(v[q]);
+        const int incl = wave_scan_incl(c);
+        int pos = base + incl - c;
+        if (c && pos < cap) {
+          const int i = w0 + 64 * q + lane;
+          const int y = i / L.mask_wpr, xw = i - y * L.mask_wpr;
+          u64 w = v[q];
+          while (w && pos < cap) {
+            const int b = __ffsll((long long)w) - 1;
+            w &= w - 1;
+            const int x = orbx_mask_x(L, xw, b);
+            if (mode == ORBX_SELECT_ROWMAJOR) {  // cap == quota: the survivor is selected
+              orbx_keypoint kp;
+              kp.x = x;
+              kp.y = y;
+              sel_lkp[fo + L.out_off + pos] = kp;
+              sel_resp[fo + L.out_off + pos] = 0.0f;
+            } else {
+              s_kp[slot + pos] = ((uint32_t)y << 16) | (uint32_t)x;
+            }
+            if (pos == cap - 1) last = y;
+            pos++;
+          }
         }
+        base += __builtin_amdgcn_readlane(incl, 63);
       }
-      base += tot;
     }
-    __syncthreads();
-  }
-  const int n = base < cap ? base : cap;
-  const int keep = n < L.quota ? n : L.quota;
-  const size_t so = (size_t)f * plan.out_cap + L.out_off;
-  if (tid == 0) sel_count[f * plan.nlevels + l] = keep;
-  // How many rows of the level did it take to fill the cap (all of them if it never filled)?  The maximum over the
-  // batch's frames goes to the host, which sizes the first pass of the top-rows-first pipeline by it (orbx_api.cpp,
-  // adapt_tile_rows): a heuristic's input, results never depend on it.
-  if (need && tid == 0 && cap > 0) atomicMax(&need[l], base >= cap ? (s_kp[cap - 1] >> 16) + 1u : (uint32_t)L.h);
-
-  if (mode == ORBX_SELECT_ROWMAJOR) {
-    for (int i = tid; i < keep; i += LVL_THREADS) {
-      const uint32_t p = s_kp[i];
-      orbx_keypoint kp;
-      kp.x = (int)(p & 0xffffu);
-      kp.y = (int)(p >> 16);
-      sel_lkp[so + i] = kp;
-      sel_resp[so + i] = 0.0f;
+    const int n = base < cap ? base : cap;
+    const int keep = n < L.quota ? n : L.quota;
+    const int runs = (n + LVL_RUN - 1) / LVL_RUN;
+    const u64 found = __ballot(last >= 0);
+    const int last_row = found ? __builtin_amdgcn_readlane(last, __ffsll((long long)found) - 1) : L.h - 1;
+    if (lane == 0) {
+      s_n[l] = n;
+      s_runs[l] = runs;
+      sel_count[f * nl + l] = keep;
+      // How many rows of the level did it take to fill the cap (all of them if it never filled)?  The maximum over
+      // the batch's frames goes to the host, which sizes the first pass of the top-rows-first pipeline by it
+      // (orbx_api.cpp, adapt_tile_rows): a heuristic's input, results never depend on it.
+      if (need && cap > 0) atomicMax(&need[l], (uint32_t)last_row + 1u);
     }
-    return;
   }
+  if (mode == ORBX_SELECT_ROWMAJOR) return;
+  __syncthreads();
 
-  // phase 2: Harris responses -> (response desc, index asc) keys
-  const uint8_t* img = pyr + (size_t)f * plan.frame_bytes + L.img_off;
-  const int n2 = (n + 1) & ~1;
-  for (int i = tid; i < n2; i += LVL_THREADS) {
-    u64 key = 0ull;  // padding: the smallest key, never outranks anything
-    if (i < n) {
-      const uint32_t p = s_kp[i];
-      const float r = harris_any(img, L.w, L.h, L.pitch, (int)(p & 0xffffu), (int)(p >> 16), gauss, K, kk);
-      s_r[i] = r;
-      uint32_t u = orbx_f2u(r);
+  int nruns = 0;
+  for (int l = l0; l < l1; l++) nruns += s_runs[l];
+  nruns = __builtin_amdgcn_readfirstlane(nruns);
+  // phases 2 + 3a: a wave takes one run of 64 candidates of one level at a time (the level's image, size and slots
+  // stay wave-uniform).  First pass: Harris of the candidates that harris_any would give its window-K fast path.
+  // Second pass, over the same runs: the rest through harris_at, then the run's keys are sorted in registers.  With
+  // both paths in one loop the kernel spills at 128 registers.
+  const uint8_t* img_f = pyr + (size_t)f * plan.frame_bytes;
+  if (KF > 0) {
+    for (int t = wave; t < nruns; t += LVL_WAVES) {
+      int r = t;
+      const int l = lvl_of_run(s_runs, l0, l1, r);
+      const OrbxLevel& L = plan.L[l];
+      const int slot = lvl_slots(plan, l), i = LVL_RUN * r + lane;
+      const bool live = i < __builtin_amdgcn_readfirstlane(s_n[l]);
+      const uint32_t p = live ? s_kp[slot + i] : 0u;
+      const int x = (int)(p & 0xffffu), y = (int)(p >> 16);
+      const bool fast = live && harris_fast_ok(L.w, L.h, x, y, KF);
+      if (fast) s_r[slot + i] = harris_fast<KF>(img_f + L.img_off, L.w, L.h, L.pitch, x, y, gauss, kk);
+    }
+  }
+  for (int t = wave; t < nruns; t += LVL_WAVES) {
+    int r = t;
+    const int l = lvl_of_run(s_runs, l0, l1, r);
+    const OrbxLevel& L = plan.L[l];
+    const int slot = lvl_slots(plan, l), i = LVL_RUN * r + lane;
+    u64 key = 0ull;  // past the level's count: below every real key
+    if (i < __builtin_amdgcn_readfirstlane(s_n[l])) {
+      const uint32_t p = s_kp[slot + i];
+      const int x = (int)(p & 0xffffu), y = (int)(p >> 16);
+      const bool fast = KF > 0 && harris_fast_ok(L.w, L.h, x, y, KF);
+      float resp;
+      if (fast) {
+        resp = s_r[slot + i];
+      } else {
+        resp = harris_at(img_f + L.img_off, L.w, L.h, L.pitch, x, y, gauss, K, kk);
+        s_r[slot + i] = resp;
+      }
+      uint32_t u = orbx_f2u(resp);
       if (u == 0x80000000u) u = 0u;
       u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
       key = ((u64)u << 32) | (uint32_t)~(uint32_t)i;
     }
-    s_key[i] = key;
+    s_key[slot + i] = wave_sort_desc(key, lane);
   }
   __syncthreads();
-
-  // phase 3: rank and scatter
-  for (int i = tid; i < n; i += LVL_THREADS) {
-    const u64 ki = s_key[i];
-    int rank = 0;
-#pragma unroll 4
-    for (int j = 0; j < n2; j += 2) {
-      const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(&s_key[j]);
-      rank += v.x > ki;
-      rank += v.y > ki;
+  // phase 3b: rank = place in the own run + keys above it in the level's other runs
+  for (int t = wave; t < nruns; t += LVL_WAVES) {
+    int r = t;
+    const int l = lvl_of_run(s_runs, l0, l1, r);
+    const int slot = lvl_slots(plan, l);
+    const int runs = __builtin_amdgcn_readfirstlane(s_runs[l]);
+    const u64 k = s_key[slot + LVL_RUN * r + lane];
+    int rank = lane;
+    for (int o = 0; o < runs; o++) {
+      if (o == r) continue;
+      const u64* run = s_key + slot + LVL_RUN * o;
+      int c = 0;  // keys of run o above k: the largest c <= 63 with run[c - 1] > k, then run[63]
+#pragma unroll
+      for (int step = LVL_RUN / 2; step > 0; step >>= 1) c += run[c + step - 1] > k ? step : 0;
+      c += run[c] > k;
+      rank += c;
     }
-    if (rank < keep) {
-      const uint32_t p = s_kp[i];
+    const int n = __builtin_amdgcn_readfirstlane(s_n[l]);
+    const int keep = n < plan.L[l].quota ? n : plan.L[l].quota;
+    if (k != 0ull && rank < keep) {
+      const int i = (int)~(uint32_t)k;
+      const uint32_t p = s_kp[slot + i];
       orbx_keypoint kp;
       kp.x = (int)(p & 0xffffu);
       kp.y = (int)(p >> 16);
-      sel_lkp[so + rank] = kp;
-      sel_resp[so + rank] = s_r[i];
+      const size_t so = fo + plan.L[l].out_off + rank;
+      sel_lkp[so] = kp;
+      sel_resp[so] = s_r[slot + i];
     }
   }
 }
 
 // ---------------------------------------------------------------------------
 // 6c. The same selection as k_level_select, spread over the whole chip.  k_level_select does
-//     everything for one (level, frame) in ONE workgroup, which is the faster arrangement while
-//     a level has at most one candidate per thread (KITTI, 1000 features: 27 us vs 31 us for the
-//     three kernels below at batch 64, 119 vs 134 us for a single frame end to end).  With larger
-//     per-level caps (1920x1080, 4000 features: level 0 has ~1400 candidates) it serialises
-//     Harris and the n^2 ranking inside single workgroups (110 us at batch 16); then three short
-//     kernels take over (79 us; orbx_launch_level_select_auto):
+//     everything for one frame in ONE workgroup and holds the frame's candidates in LDS.  Caps
+//     above 512 (1920x1080, 4000 features: level 0 has ~1400 candidates), or more candidates per
+//     frame than LVL_MAX_SLOTS, go to three short kernels instead (orbx_launch_level_select_auto;
+//     measured when k_level_select still had one workgroup per (level, frame): 79 vs 110 us at
+//     batch 16):
 //       k_lvl_compact  (level, frame)                   first `cap` survivors, row-major
 //       k_lvl_harris   (256 candidates, level, frame)   thread per candidate
 //       k_lvl_rank     (64 candidates, level, frame)    4 threads per candidate
@@ -1736,16 +1825,23 @@ hipError_t orbx_launch_level_select(hipStream_t s, const OrbxPlan& plan, int n_f
                                     const unsigned long long* d_mask, const uint8_t* d_pyr, const float* d_gauss,
                                     int window, float k, orbx_keypoint* d_sel_lkp, float* d_sel_resp,
                                     int32_t* d_sel_count, uint32_t* d_need) {
-  int maxcap = 2;
-  for (int l = 0; l < plan.nlevels; l++) maxcap = plan.L[l].cap > maxcap ? plan.L[l].cap : maxcap;
-  const size_t lds = (size_t)((maxcap + 1) & ~1) * 16;
-  dim3 grid(n_frames, plan.nlevels);
-  hipLaunchKernelGGL(k_level_select, grid, dim3(LVL_THREADS), lds, s, plan, mode, d_mask, d_pyr, d_gauss, window, k,
-                     d_sel_lkp, d_sel_resp, d_sel_count, d_need);
+  // the row-major mode writes its survivors straight to the output slots and needs no LDS
+  const int nslots = mode == ORBX_SELECT_ROWMAJOR ? 0 : lvl_slots(plan, plan.nlevels);
+  if (nslots > LVL_MAX_SLOTS) return hipErrorInvalidValue;
+  const size_t lds = (size_t)nslots * 16;
+  // A workgroup per frame and all of its levels from 256 frames (one per CU) on; below that, a workgroup per (level,
+  // frame): a few frames' runs queued over one workgroup's 8 waves leave most CUs idle.  Measured: 256 frames per
+  // step 545 k frames/s per frame vs 502 k per (level, frame); one frame end to end 0.196 vs 0.160 ms
+  const int lpg = n_frames >= 256 ? plan.nlevels : 1;
+  dim3 grid(n_frames, (plan.nlevels + lpg - 1) / lpg);
+  auto kern = window == 7 ? k_level_select<7> : window == 5 ? k_level_select<5> : window == 3 ? k_level_select<3>
+                                                                                   : k_level_select<0>;
+  hipLaunchKernelGGL(kern, grid, dim3(LVL_THREADS), lds, s, plan, lpg, mode, d_mask, d_pyr, d_gauss, window, k, d_sel_lkp,
+                     d_sel_resp, d_sel_count, d_need);
   return ORBX_LAUNCH_CHECK();
 }
 
-// one workgroup per (level, frame) or the three spread kernels, whichever suits the shape
+// one workgroup per frame or the three spread kernels, whichever suits the shape
 // (see 6c); force = 0 fused, 1 spread, -1 automatic
 hipError_t orbx_launch_level_select_auto(hipStream_t s, const OrbxPlan& plan, int n_frames, int mode, int force,
                                          const unsigned long long* d_mask, const uint8_t* d_pyr,
@@ -1754,8 +1850,10 @@ hipError_t orbx_launch_level_select_auto(hipStream_t s, const OrbxPlan& plan, in
                                          float* d_sel_resp, int32_t* d_sel_count, uint32_t* d_need) {
   int maxcap = 2;
   for (int l = 0; l < plan.nlevels; l++) maxcap = plan.L[l].cap > maxcap ? plan.L[l].cap : maxcap;
+  // the fused kernel holds a frame's candidates in LDS; the spread kernels take larger frames whatever `force` says
   const bool spread = mode == ORBX_SELECT_HARRIS &&
-                      (force >= 0 ? force != 0 : maxcap > LVL_THREADS);  // more than one candidate per thread
+                      (lvl_slots(plan, plan.nlevels) > LVL_MAX_SLOTS ||
+                       (force >= 0 ? force != 0 : maxcap > LVL_THREADS));  // more than one candidate per thread
   if (!spread)
     return orbx_launch_level_select(s, plan, n_frames, mode, d_mask, d_pyr, d_gauss, window, k, d_sel_lkp,
                                     d_sel_resp, d_sel_count, d_need);
