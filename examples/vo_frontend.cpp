@@ -1,6 +1,7 @@
 // vo_frontend.cpp -- the image-side half of the reference's tracking VO loop
 // (VisualOdom::run, src/feature_tracking.cpp:44-126) on liborbx: everything up to the point
-// where the reference hands the correspondences to cv::findEssentialMat (get_pose, out of scope).
+// where the reference hands the correspondences to cv::findEssentialMat (get_pose; examples/vo_odometry.cpp
+// continues through get_pose, get_scale and the pose chaining on the matching loop).
 //
 //   frame 0 : imread -> orb->detect -> KeyPoint::convert                    (:56-62)
 //   frame i : imread -> track_optical_flow (pyramidal LK, drop lost tracks)  (:64-67, :166-193)

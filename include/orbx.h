@@ -417,6 +417,48 @@ int orbx_batch_pose_fetch(orbx_ctx* ctx, int first, int n, double* E, double* R,
  * ORBX_ERR_CAPACITY if > capacity */
 int orbx_batch_pose_mask(orbx_ctx* ctx, int pair, uint8_t* mask, int capacity, int* count);
 
+/* ---- next row: triangulation, relative scale, trajectory ----
+ * Replaces the rest of the reference's per-frame VO step,
+ *   double scale = get_scale(R, t, pts1, pts2, points_3d);      src/feature_matching.cpp:70, :208-275
+ *   T = [R | scale * t]; cur_pose = cur_pose * T.inv();          src/feature_matching.cpp:77-82
+ * (src/feature_tracking.cpp:77-93, :244-310; src/feature_tracking_scale.py:127-164).
+ * OpenCV is absent from the image this library was written in: cv::triangulatePoints' 4x4 SVD is a fixed-sweep
+ * Jacobi iteration (DESIGN.md §9 rank 6 rule 1); parity with OpenCV is unpinned.  A point is valid iff its
+ * homogeneous w is not 0 and its three float coordinates are finite; an invalid point is (0, 0, 0) with valid = 0
+ * and enters no distance ratio. */
+/* cv::triangulatePoints(K [I|0], K [R|t], pts1, pts2) + X/w -> cv::Point3f on host arrays: pts*_xy are n float
+ * (x, y) pairs in pixels, K and R row-major double[9], t double[3]; xyz: 3 n floats, valid: n bytes.
+ * src/feature_matching.cpp:216-245, src/feature_tracking.cpp:252-281 */
+int orbx_triangulate(orbx_ctx* ctx, const float* pts1_xy, const float* pts2_xy, int n, const double* K,
+                     const double* R, const double* t, float* xyz, uint8_t* valid);
+/* the tail of get_scale on two index-aligned point lists: the upper median (nth_element at size / 2) of
+ * |prev[i] - prev[i-1]| / (|cur[i] - cur[i-1]| + 1e-6) over i in [1, min(n_prev, n_cur)), clamped to [0.1, 5];
+ * 1.0 when a list is empty or no ratio exists.  A ratio that is not finite (distances that overflow a float) counts
+ * as no ratio.  The valid arrays may be NULL (all valid).  ORBX_ERR_UNSUPPORTED
+ * beyond 20448 aligned points.  src/feature_matching.cpp:248-274, src/feature_tracking.cpp:284-309 */
+int orbx_estimate_scale(orbx_ctx* ctx, const float* prev_xyz, const uint8_t* prev_valid, int n_prev,
+                        const float* cur_xyz, const uint8_t* cur_valid, int n_cur, double* scale,
+                        int32_t* ratios_used);
+/* Device-resident: triangulates every match of every pair posed by the last orbx_batch_pose_consecutive and
+ * estimates each pair's scale against its predecessor, on the batch's stream.  The two pairs' points are joined
+ * on the shared frame's keypoint index (src/feature_tracking_scale.py:127-164: several queries on one keypoint:
+ * the largest query index wins; triplets in ascending index order) and the predecessor's points are moved into
+ * the shared frame with X' = R X + t.  Pair 0 has no predecessor: scale 1.0, 0 triplets.  K must be the K the
+ * poses were computed with.  ORBX_ERR_INVALID_ARG if the last batch has not been posed (or another batch has
+ * been enqueued since, or the match table has been rewritten by any matcher entry since the pose).  src/feature_matching.cpp:208-275 */
+int orbx_batch_scale_consecutive(orbx_ctx* ctx, const double* K);
+/* results of pairs [first, first + n) of the last orbx_batch_scale_consecutive; any output may be NULL.
+ * src/feature_matching.cpp:70 */
+int orbx_batch_scale_fetch(orbx_ctx* ctx, int first, int n, double* scale, int32_t* triplets, int32_t* ratios_used);
+/* the triangulated points of one pair (the reference's points_3d, src/feature_matching.cpp:237-245), one per match
+ * in orbx_batch_match_fetch order; *count = match count, ORBX_ERR_CAPACITY if > capacity */
+int orbx_batch_points_fetch(orbx_ctx* ctx, int pair, float* xyz, uint8_t* valid, int capacity, int* count);
+/* cur_pose = cur_pose * T.inv() with T = [R | scale * t] for n relative motions (src/feature_matching.cpp:77-82),
+ * T^-1 in closed form [R^T | -scale R^T t].  Host only, needs no context.  T0: row-major 4x4; R: 9 n, t: 3 n,
+ * scale: n doubles; poses: (n + 1) row-major 4x4, poses[0] = T0. */
+int orbx_chain_trajectory(const double* T0, const double* R, const double* t, const double* scale, int n,
+                          double* poses);
+
 #ifdef __cplusplus
 }
 #endif

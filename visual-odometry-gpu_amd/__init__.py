@@ -6,4 +6,4 @@ The directory name contains a hyphen, so import it with
 (see __graft_entry__.load_package()).
 """
 from . import orbx, shard, streams  # noqa: F401
-from .orbx import Context, OrbxError, default_params  # noqa: F401
+from .orbx import Context, OrbxError, chain_trajectory, default_params  # noqa: F401

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "orbx_internal.h"
+#include "orbx_tri_math.h"
 
 namespace {
 
@@ -194,10 +195,19 @@ struct orbx_ctx {
   int match_pairs = 0;
   // batch serial: bumped by every batch run; match_serial: the serial the last batch match was made on
   long long batch_serial = 0, match_serial = -1;
+  // bumped by every batch match: the pose step records the one it read (pose_match_gen), so the scale step, which
+  // reads m_match again, can tell that the matches are still the ones the poses were computed from
+  long long match_gen = 0, pose_match_gen = -1;
   // relative pose (orbx_pose.hip): batched results (pb_*) and the host-array entry's own buffers (ph_*)
   DevBuf pb_pts, pb_n, pb_out, pb_mask, ph_in, ph_pts, ph_n, ph_out, ph_mask;
   int pose_pairs = 0, pose_cap = 0;
   hipStream_t pose_stream = nullptr;
+  long long pose_serial = -1;  // the batch serial the last batch pose ran on
+  // triangulation and scale (orbx_scale.hip): batched results (sb_*: points, valid bytes, compact match lists,
+  // match counts, scales) and the host-array entries' own buffers (sh_*)
+  DevBuf sb_xyz, sb_valid, sb_mq, sb_mt, sb_n, sb_out, sh_in, sh_xyz, sh_valid, sh_out;
+  int scale_pairs = 0, scale_cap = 0;
+  hipStream_t scale_stream = nullptr;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -1419,7 +1429,8 @@ void orbx_destroy(orbx_ctx* c) {
   DevBuf* sb[] = {&c->s_img_a, &c->s_img_b, &c->s_f32,  &c->s_u16, &c->s_mask, &c->s_kps,   &c->s_f32b, &c->s_desc,
                   &c->s_i32,   &c->s_kern,  &c->s_tiles, &c->m_q,    &c->m_t,   &c->m_idx,  &c->m_dist,  &c->m_match, &c->m_cnt,
                   &c->lk_img[0], &c->lk_img[1], &c->lk_deriv, &c->lk_io, &c->pb_pts, &c->pb_n, &c->pb_out,
-                  &c->pb_mask, &c->ph_in, &c->ph_pts, &c->ph_n, &c->ph_out, &c->ph_mask};
+                  &c->pb_mask, &c->ph_in, &c->ph_pts, &c->ph_n, &c->ph_out, &c->ph_mask, &c->sb_xyz, &c->sb_valid,
+                  &c->sb_mq, &c->sb_mt, &c->sb_n, &c->sb_out, &c->sh_in, &c->sh_xyz, &c->sh_valid, &c->sh_out};
   if (c->lk_host) (void)hipHostFree(c->lk_host);
   for (DevBuf* b : sb)
     if (b->p) (void)hipFree(b->p);
@@ -2424,6 +2435,7 @@ int orbx_batch_match_consecutive(orbx_ctx* c, double ratio) {
                              (int32_t*)c->m_idx.p, (int32_t*)c->m_dist.p, (int32_t*)c->m_match.p, (size_t)cap));
   c->match_pairs = n - 1;
   c->match_serial = c->batch_serial;
+  c->match_gen++;
   return ORBX_OK;
 }
 
@@ -2664,6 +2676,8 @@ int orbx_batch_pose_consecutive(orbx_ctx* c, const double* K, double prob, doubl
   c->pose_pairs = npairs;
   c->pose_cap = cap;
   c->pose_stream = s;
+  c->pose_serial = c->batch_serial;
+  c->pose_match_gen = c->match_gen;
   return ORBX_OK;
 }
 
@@ -2700,6 +2714,171 @@ int orbx_batch_pose_mask(orbx_ctx* c, int pair, uint8_t* mask, int capacity, int
                              hipMemcpyDeviceToHost, c->pose_stream));
     HIPCHK(c, hipStreamSynchronize(c->pose_stream));
   }
+  return ORBX_OK;
+}
+
+}  // extern "C"
+
+// ---- triangulation, relative scale, trajectory chaining ------------
+
+namespace {
+bool finite_all(const double* v, int n) {
+  for (int i = 0; i < n; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int orbx_triangulate(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, int n, const double* K, const double* R,
+                     const double* t, float* xyz, uint8_t* valid) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (n < 0 || (n > 0 && (!pts1_xy || !pts2_xy || !xyz || !valid)) || !K || !R || !t || !finite_all(K, 9) ||
+      !finite_all(R, 9) || !finite_all(t, 3))
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad triangulation arguments");
+  if (n == 0) return ORBX_OK;
+  int st;
+  if ((st = ensure(c, c->sh_in, sizeof(float) * 4 * (size_t)n)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->sh_xyz, sizeof(float) * 3 * (size_t)n)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->sh_valid, (size_t)n)) != ORBX_OK) return st;
+  hipStream_t s = c->stream;
+  float* d_p1 = (float*)c->sh_in.p;
+  float* d_p2 = d_p1 + 2 * (size_t)n;
+  HIPCHK(c, hipMemcpyAsync(d_p1, pts1_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d_p2, pts2_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, orbx_launch_triangulate_host(s, n, d_p1, d_p2, K, R, t, (float*)c->sh_xyz.p, (uint8_t*)c->sh_valid.p));
+  HIPCHK(c, hipMemcpyAsync(xyz, c->sh_xyz.p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(valid, c->sh_valid.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return ORBX_OK;
+}
+
+int orbx_estimate_scale(orbx_ctx* c, const float* prev_xyz, const uint8_t* prev_valid, int n_prev, const float* cur_xyz,
+                        const uint8_t* cur_valid, int n_cur, double* scale, int32_t* ratios_used) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (n_prev < 0 || n_cur < 0 || (n_prev > 0 && !prev_xyz) || (n_cur > 0 && !cur_xyz) || !scale || !ratios_used)
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad scale arguments");
+  const int m = std::min(n_prev, n_cur);
+  if (m == 0) {  // src/feature_matching.cpp:248-249
+    *scale = 1.0;
+    *ratios_used = 0;
+    return ORBX_OK;
+  }
+  if ((size_t)m * 8 > ORBX_SCALE_LDS_MAX)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "more aligned points than the selection holds in LDS");
+  // only the first m points of either list enter
+  int st;
+  if ((st = ensure(c, c->sh_xyz, sizeof(float) * 6 * (size_t)m)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->sh_valid, 2 * (size_t)m)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->sh_out, sizeof(OrbxScaleOut))) != ORBX_OK) return st;
+  hipStream_t s = c->stream;
+  float* d_prev = (float*)c->sh_xyz.p;
+  float* d_cur = d_prev + 3 * (size_t)m;
+  uint8_t* d_pv = (uint8_t*)c->sh_valid.p;
+  uint8_t* d_cv = d_pv + m;
+  HIPCHK(c, hipMemcpyAsync(d_prev, prev_xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d_cur, cur_xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
+  if (prev_valid) HIPCHK(c, hipMemcpyAsync(d_pv, prev_valid, (size_t)m, hipMemcpyHostToDevice, s));
+  if (cur_valid) HIPCHK(c, hipMemcpyAsync(d_cv, cur_valid, (size_t)m, hipMemcpyHostToDevice, s));
+  HIPCHK(c, orbx_launch_scale_aligned(s, m, m, d_prev, prev_valid ? d_pv : nullptr, d_cur, cur_valid ? d_cv : nullptr,
+                                      (OrbxScaleOut*)c->sh_out.p));
+  OrbxScaleOut r;
+  HIPCHK(c, hipMemcpyAsync(&r, c->sh_out.p, sizeof r, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  *scale = r.scale;
+  *ratios_used = r.ratios_used;
+  return ORBX_OK;
+}
+
+int orbx_batch_scale_consecutive(orbx_ctx* c, const double* K) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!K || !finite_all(K, 9)) return fail(c, ORBX_ERR_INVALID_ARG, "bad scale arguments");
+  if (c->pose_pairs <= 0 || c->pose_serial != c->batch_serial)
+    return fail(c, ORBX_ERR_INVALID_ARG, "the last batch has not been posed (orbx_batch_pose_consecutive)");
+  // the triangulation reads the match table again: it must still hold the matches the poses were computed from
+  // (a host-array matcher call reuses the scratch and zeroes match_pairs; a second batch match bumps match_gen)
+  if (c->match_pairs != c->pose_pairs || c->match_serial != c->batch_serial || c->pose_match_gen != c->match_gen)
+    return fail(c, ORBX_ERR_INVALID_ARG, "the match table has been rewritten since the batch was posed");
+  const int npairs = c->pose_pairs, cap = c->pose_cap;
+  if ((size_t)cap * 16 > ORBX_SCALE_LDS_MAX)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "more result slots per frame than the join holds in LDS");
+  // the scale buffers are ONE set per context, like the pose buffers
+  if (c->lane_stream[1]) HIPCHK(c, lanes_sync(c));
+  const size_t e = (size_t)npairs * cap;
+  int st;
+  if ((st = ensure(c, c->sb_xyz, sizeof(float) * 3 * e)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->sb_valid, e)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->sb_mq, sizeof(int32_t) * e)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->sb_mt, sizeof(int32_t) * e)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->sb_n, sizeof(int32_t) * (size_t)npairs)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->sb_out, sizeof(OrbxScaleOut) * (size_t)npairs)) != ORBX_OK) return st;
+  const OutLayout& o = c->out_layout;
+  hipStream_t s = c->pose_stream;
+  HIPCHK(c, orbx_launch_triangulate_batch(s, npairs, cap, (const int32_t*)(c->d_out + o.counts),
+                                          (const orbx_keypoint*)(c->d_out + o.kp), (const int32_t*)c->m_match.p,
+                                          (const OrbxPoseOut*)c->pb_out.p, K, (float*)c->sb_xyz.p,
+                                          (uint8_t*)c->sb_valid.p, (int32_t*)c->sb_mq.p, (int32_t*)c->sb_mt.p,
+                                          (int32_t*)c->sb_n.p));
+  HIPCHK(c, orbx_launch_scale_join(s, npairs, cap, (const int32_t*)c->sb_n.p, (const int32_t*)c->sb_mq.p,
+                                   (const int32_t*)c->sb_mt.p, (const float*)c->sb_xyz.p,
+                                   (const uint8_t*)c->sb_valid.p, (const OrbxPoseOut*)c->pb_out.p,
+                                   (OrbxScaleOut*)c->sb_out.p));
+  c->scale_pairs = npairs;
+  c->scale_cap = cap;
+  c->scale_stream = s;
+  return ORBX_OK;
+}
+
+int orbx_batch_scale_fetch(orbx_ctx* c, int first, int n, double* scale, int32_t* triplets, int32_t* ratios_used) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (c->scale_pairs <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been scaled");
+  if (first < 0 || n < 0 || first + n > c->scale_pairs)
+    return fail(c, ORBX_ERR_INVALID_ARG, "pairs outside the last scaled batch");
+  if (n == 0) return ORBX_OK;
+  std::vector<OrbxScaleOut> r((size_t)n);
+  HIPCHK(c, hipMemcpyAsync(r.data(), (const OrbxScaleOut*)c->sb_out.p + first, sizeof(OrbxScaleOut) * (size_t)n,
+                           hipMemcpyDeviceToHost, c->scale_stream));
+  HIPCHK(c, hipStreamSynchronize(c->scale_stream));
+  for (int i = 0; i < n; i++) {
+    if (scale) scale[i] = r[(size_t)i].scale;
+    if (triplets) triplets[i] = r[(size_t)i].triplets;
+    if (ratios_used) ratios_used[i] = r[(size_t)i].ratios_used;
+  }
+  return ORBX_OK;
+}
+
+int orbx_batch_points_fetch(orbx_ctx* c, int pair, float* xyz, uint8_t* valid, int capacity, int* count) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!count || capacity < 0 || (capacity > 0 && (!xyz || !valid)))
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad point output arguments");
+  if (pair < 0 || pair >= c->scale_pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last scaled batch");
+  hipStream_t s = c->scale_stream;
+  int32_t np = 0;
+  HIPCHK(c, hipMemcpyAsync(&np, (const int32_t*)c->sb_n.p + pair, sizeof np, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  *count = np;
+  if (np > capacity) return fail(c, ORBX_ERR_CAPACITY, "capacity smaller than the pair's match count");
+  if (np > 0) {
+    const size_t row = (size_t)pair * c->scale_cap;
+    HIPCHK(c, hipMemcpyAsync(xyz, (const float*)c->sb_xyz.p + 3 * row, sizeof(float) * 3 * (size_t)np,
+                             hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(valid, (const uint8_t*)c->sb_valid.p + row, (size_t)np, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  return ORBX_OK;
+}
+
+int orbx_chain_trajectory(const double* T0, const double* R, const double* t, const double* scale, int n,
+                          double* poses) {
+  if (!T0 || !poses || n < 0 || (n > 0 && (!R || !t || !scale))) return ORBX_ERR_INVALID_ARG;
+  std::memcpy(poses, T0, sizeof(double) * 16);
+  for (int i = 0; i < n; i++) tri_chain(poses + 16 * i, R + 9 * i, t + 3 * i, scale[i], poses + 16 * (i + 1));
   return ORBX_OK;
 }
 

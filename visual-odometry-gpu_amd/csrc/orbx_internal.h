@@ -275,3 +275,27 @@ hipError_t orbx_launch_pose_prep_host(hipStream_t s, int n, const float* d_p1, c
 hipError_t orbx_launch_pose_ransac(hipStream_t s, int npairs, int cap, const OrbxPosePt* d_pts, const int32_t* d_npts,
                                    const double* K, double prob, double threshold, int max_iters, uint64_t seed,
                                    OrbxPoseOut* d_out, uint8_t* d_mask);
+
+// triangulation and relative scale (orbx_scale.hip): one pair's result
+struct OrbxScaleOut {
+  double scale;
+  int32_t triplets, ratios_used;
+};
+// dynamic LDS a scale kernel may ask for: a workgroup's 160 KB on gfx950 less 256 bytes for the kernels' static
+// variables; k_scale_join needs 16 bytes per result slot (at most 10 224), k_scale_aligned 8 per point (20 448)
+#define ORBX_SCALE_LDS_MAX (160 * 1024 - 256)
+// d_xyz / d_valid / d_mq / d_mt: one row of `cap` per pair, in the compact query order of orbx_batch_match_fetch
+// (the point, its valid byte, the match's query and train index); d_npts: matches per pair
+hipError_t orbx_launch_triangulate_batch(hipStream_t s, int npairs, int cap, const int32_t* d_counts,
+                                         const orbx_keypoint* d_kp, const int32_t* d_match, const OrbxPoseOut* d_pose,
+                                         const double* K, float* d_xyz, uint8_t* d_valid, int32_t* d_mq, int32_t* d_mt,
+                                         int32_t* d_npts);
+hipError_t orbx_launch_triangulate_host(hipStream_t s, int n, const float* d_p1, const float* d_p2, const double* K,
+                                        const double* R, const double* t, float* d_xyz, uint8_t* d_valid);
+hipError_t orbx_launch_scale_join(hipStream_t s, int npairs, int cap, const int32_t* d_npts, const int32_t* d_mq,
+                                  const int32_t* d_mt, const float* d_xyz, const uint8_t* d_valid,
+                                  const OrbxPoseOut* d_pose, OrbxScaleOut* d_out);
+// a NULL valid array: every point is valid
+hipError_t orbx_launch_scale_aligned(hipStream_t s, int n_prev, int n_cur, const float* d_prev,
+                                     const uint8_t* d_prev_valid, const float* d_cur, const uint8_t* d_cur_valid,
+                                     OrbxScaleOut* d_out);

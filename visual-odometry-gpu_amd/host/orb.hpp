@@ -32,6 +32,7 @@
 //     Fast.cu:8-18) and constructors print nothing;
 //   * HarrisScore takes `float k` (the reference's `int k` truncates 0.04 to 0, D7).
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -660,6 +661,64 @@ inline void get_pose(const std::vector<Point2f>& pts1, const std::vector<Point2f
   detail::check(c, orbx_estimate_pose(c, a.data(), b.data(), n, K, prob, threshold, max_iters, seed, E, R, t,
                               n > 0 ? mask.data() : nullptr, &inliers, &good, &iters),
         "orbx_estimate_pose");
+}
+
+// ---- triangulation, relative scale, pose chaining (next row) -------
+struct Point3f {  // cv::Point3f
+  float x = 0.f, y = 0.f, z = 0.f;
+};
+
+// The members of the reference's VisualOdom that the scale step carries from frame to frame
+// (src/feature_matching.cpp:119-120): the previous pair's triangulated points and the camera pose.
+// *_valid: one byte per point (cv::triangulatePoints leaves w = 0 as inf / NaN; here such a point is
+// (0, 0, 0) with valid = 0 and enters no ratio).
+struct VisualOdomState {
+  std::vector<Point3f> prev_points_3d;
+  std::vector<uint8_t> prev_valid, points_valid;  // points_valid: of the points_3d the last get_scale returned
+  std::array<double, 16> cur_pose{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};  // row-major 4x4
+  // prev_points_3d = points_3d (src/feature_matching.cpp:87), with the points' valid bytes
+  void shift(const std::vector<Point3f>& points_3d) {
+    prev_points_3d = points_3d;
+    prev_valid = points_valid;
+  }
+};
+
+// VisualOdom::get_scale (src/feature_matching.cpp:208-275, src/feature_tracking.cpp:244-310): triangulate the
+// pair's correspondences under P1 = K [I|0], P2 = K [R|t], then the clamped median of the distance ratios between
+// the previous pair's points (vo.prev_points_3d) and these, aligned by bare index as the C++ flavours do.  K, R:
+// row-major 3x3.  A prev_valid whose size differs from prev_points_3d (the points were assigned directly) counts
+// as all valid.
+inline double get_scale(const double R[9], const double t[3], const std::vector<Point2f>& pts1,
+                        const std::vector<Point2f>& pts2, const double K[9], std::vector<Point3f>& points_3d,
+                        VisualOdomState& vo) {
+  if (pts1.size() != pts2.size()) throw std::invalid_argument("get_scale: pts1 and pts2 differ in size");
+  static_assert(sizeof(Point2f) == 2 * sizeof(float) && sizeof(Point3f) == 3 * sizeof(float), "point layouts");
+  const int n = (int)pts1.size();
+  points_3d.assign((size_t)n, Point3f());
+  vo.points_valid.assign((size_t)n, 0);
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_triangulate(c, reinterpret_cast<const float*>(pts1.data()),
+                                 reinterpret_cast<const float*>(pts2.data()), n, K, R, t,
+                                 reinterpret_cast<float*>(points_3d.data()), vo.points_valid.data()),
+                "orbx_triangulate");
+  double scale = 1.0;
+  int32_t used = 0;
+  const bool have_valid = vo.prev_valid.size() == vo.prev_points_3d.size();
+  detail::check(c,
+                orbx_estimate_scale(c, reinterpret_cast<const float*>(vo.prev_points_3d.data()),
+                                    have_valid ? vo.prev_valid.data() : nullptr, (int)vo.prev_points_3d.size(),
+                                    reinterpret_cast<const float*>(points_3d.data()), vo.points_valid.data(), n, &scale,
+                                    &used),
+                "orbx_estimate_scale");
+  return scale;
+}
+
+// cur_pose = cur_pose * T.inv() with T = [R | scale * t] (src/feature_matching.cpp:77-82)
+inline void chain_pose(std::array<double, 16>& cur_pose, const double R[9], const double t[3], double scale) {
+  double poses[32];
+  detail::check(nullptr, orbx_chain_trajectory(cur_pose.data(), R, t, &scale, 1, poses), "orbx_chain_trajectory");
+  std::memcpy(cur_pose.data(), poses + 16, sizeof(double) * 16);
 }
 
 }  // namespace orbx

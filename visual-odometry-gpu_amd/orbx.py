@@ -35,6 +35,8 @@ EXPORTS = [
     "orbx_gaussian_blur_conv", "orbx_gaussian_kernel", "orbx_sobel", "orbx_build_pyramid_level",
     "orbx_select_top", "orbx_knn2", "orbx_match_ratio", "orbx_batch_match_consecutive", "orbx_batch_match_fetch",
     "orbx_estimate_pose", "orbx_batch_pose_consecutive", "orbx_batch_pose_fetch", "orbx_batch_pose_mask",
+    "orbx_triangulate", "orbx_estimate_scale", "orbx_batch_scale_consecutive", "orbx_batch_scale_fetch",
+    "orbx_batch_points_fetch", "orbx_chain_trajectory",
 ]
 
 
@@ -567,6 +569,112 @@ def _pose_methods():
 
 
 _pose_methods()
+
+
+def _scale_methods():
+    """Triangulation and relative scale: the reference's get_scale (include/orbx.h)."""
+    DP = C.POINTER(C.c_double)
+
+    def _d(a, shape):
+        a = np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
+        return a, a.ctypes.data_as(DP)
+
+    def _valid(v, n):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(np.asarray(v).reshape(-1) != 0, np.uint8)
+        if len(v) != n:
+            raise ValueError("a valid array and its point list differ in length")
+        return v
+
+    def triangulate(self, pts1, pts2, K, R, t):
+        """cv::triangulatePoints(K [I|0], K [R|t], pts1, pts2) + X/w: (xyz (n, 3) float32, valid (n,) uint8)."""
+        p1 = np.ascontiguousarray(np.asarray(pts1, np.float32).reshape(-1, 2))
+        p2 = np.ascontiguousarray(np.asarray(pts2, np.float32).reshape(-1, 2))
+        if p1.shape != p2.shape:
+            raise ValueError("pts1 and pts2 differ in shape")
+        n = p1.shape[0]
+        (K, kp), (R, rp), (t, tp) = _d(K, (3, 3)), _d(R, (3, 3)), _d(t, (3,))
+        xyz = np.zeros((max(n, 1), 3), np.float32)
+        valid = np.zeros(max(n, 1), np.uint8)
+        f = self._lib.orbx_triangulate
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, DP, DP, DP, C.c_void_p, C.c_void_p]
+        self._chk(f(self._h, _ptr(p1), _ptr(p2), n, kp, rp, tp, _ptr(xyz), _ptr(valid)))
+        return xyz[:n], valid[:n]
+
+    def estimate_scale(self, prev_xyz, cur_xyz, prev_valid=None, cur_valid=None):
+        """The tail of get_scale on two index-aligned point lists: (scale, ratios_used)."""
+        a = np.ascontiguousarray(np.asarray(prev_xyz, np.float32).reshape(-1, 3))
+        b = np.ascontiguousarray(np.asarray(cur_xyz, np.float32).reshape(-1, 3))
+        va, vb = _valid(prev_valid, len(a)), _valid(cur_valid, len(b))
+        scale, used = C.c_double(0), C.c_int32(0)
+        f = self._lib.orbx_estimate_scale
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, DP,
+                      C.POINTER(C.c_int32)]
+        self._chk(f(self._h, _ptr(a), _ptr(va), len(a), _ptr(b), _ptr(vb), len(b), C.byref(scale), C.byref(used)))
+        return scale.value, used.value
+
+    def batch_scale_consecutive(self, K):
+        """Triangulates and scales every pair of the last batch_pose_consecutive on the device."""
+        K, kp = _d(K, (3, 3))
+        f = self._lib.orbx_batch_scale_consecutive
+        f.argtypes = [C.c_void_p, DP]
+        self._chk(f(self._h, kp))
+        self._scale_pairs = getattr(self, "_pose_pairs", 0)
+
+    def batch_scale_fetch(self, first=0, n=None):
+        """dict of arrays for pairs [first, first + n): scale (float64), triplets, ratios_used (int32)."""
+        if n is None:
+            n = getattr(self, "_scale_pairs", 0) - first
+        m = max(n, 0)  # a negative n (nothing scaled yet) is the C entry's to refuse
+        scale, trip, used = np.zeros(m), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        f = self._lib.orbx_batch_scale_fetch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(f(self._h, first, n, _ptr(scale), _ptr(trip), _ptr(used)))
+        return {"scale": scale, "triplets": trip, "ratios_used": used}
+
+    def batch_points_fetch(self, pair, capacity=None):
+        """The triangulated points of one pair in batch_match_fetch order: (xyz (n, 3) float32, valid (n,) uint8).
+        capacity=None: sized from the pair's match count."""
+        f = self._lib.orbx_batch_points_fetch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        cnt = C.c_int(0)
+        if capacity is None:
+            st = f(self._h, pair, None, None, 0, C.byref(cnt))
+            if st not in (OK, ERR_CAPACITY):
+                self._chk(st)
+            capacity = cnt.value
+        xyz = np.zeros((max(capacity, 1), 3), np.float32)
+        valid = np.zeros(max(capacity, 1), np.uint8)
+        self._chk(f(self._h, pair, _ptr(xyz), _ptr(valid), capacity, C.byref(cnt)))
+        return xyz[:cnt.value], valid[:cnt.value]
+
+    for f in (triangulate, estimate_scale, batch_scale_consecutive, batch_scale_fetch, batch_points_fetch):
+        setattr(Context, f.__name__, f)
+
+
+_scale_methods()
+
+
+def chain_trajectory(T0, R, t, scale):
+    """cur_pose = cur_pose * T.inv(), T = [R | scale * t], over n relative motions (feature_matching.cpp:77-82):
+    (n + 1, 4, 4) poses with poses[0] = T0.  Host only."""
+    DP = C.POINTER(C.c_double)
+    T0 = np.ascontiguousarray(np.asarray(T0, np.float64).reshape(4, 4))
+    R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1, 3, 3))
+    t = np.ascontiguousarray(np.asarray(t, np.float64).reshape(-1, 3))
+    scale = np.ascontiguousarray(np.asarray(scale, np.float64).reshape(-1))
+    n = len(R)
+    if len(t) != n or len(scale) != n:
+        raise ValueError("R, t and scale differ in length")
+    poses = np.zeros((n + 1, 4, 4))
+    f = load().orbx_chain_trajectory
+    f.argtypes = [DP, DP, DP, DP, C.c_int, DP]
+    st = f(T0.ctypes.data_as(DP), R.ctypes.data_as(DP), t.ctypes.data_as(DP), scale.ctypes.data_as(DP), n,
+           poses.ctypes.data_as(DP))
+    if st != OK:
+        raise OrbxError(st, "orbx_chain_trajectory")
+    return poses
 
 
 def gaussian_kernel(K, sigma=-1.0):
