@@ -120,11 +120,24 @@ int orbx_detect_and_compute(orbx_ctx* ctx, const uint8_t* image, int width, int 
  * 2-4): `n` frames already in HBM at d_frames + i*frame_stride, each
  * height rows of row_stride bytes.  Runs asynchronously on the context's
  * stream (or `stream`, a hipStream_t, if non-NULL); results stay in the
- * context's device-side result slots until the next batched call. */
+ * context's device-side result slots until the next batched call.
+ * Strides and alignment: a frame may be a region of a larger image and the frames may have gaps between them.
+ *   - d_frames, row_stride and frame_stride need NO alignment: any byte address, any residue (the kernels read
+ *     the frame with byte-granular buffer descriptors and unaligned loads);
+ *   - row_stride >= width, and frame_stride >= row_stride * (height - 1) + width (frames do not overlap; the last
+ *     row of a frame need not be followed by row_stride - width padding bytes);
+ *   - row_stride * (height - 1) + width <= 2^31 - 1 (a frame is addressed with 32-bit offsets);
+ *   - 8 <= width <= max_width, 8 <= height <= max_height, 1 <= n <= max_batch.
+ * Anything else is ORBX_ERR_INVALID_ARG and leaves the context usable.  Only the width x height pixels of each
+ * frame are ever read: the bytes between rows and between frames may hold anything and never influence a result
+ * (tests/test_batch_inputs.py).  The frame size may change from call to call (the tables of the new size are
+ * rebuilt, which waits for the batches in flight). */
 int orbx_detect_and_compute_batch_device(orbx_ctx* ctx, const void* d_frames, int n, int width, int height,
                                          int row_stride, size_t frame_stride, void* stream);
 /* Same for `n` host frames (H2D copy from the caller's memory included; pass pinned memory for an
- * asynchronous copy, pageable memory is staged by the HIP runtime). */
+ * asynchronous copy, pageable memory is staged by the HIP runtime).  The same rules for row_stride and frame_stride
+ * (frame_stride is not looked at when n == 1; no 2^31 limit: the frames are packed tightly on their way to the
+ * device). */
 int orbx_detect_and_compute_batch_host(orbx_ctx* ctx, const uint8_t* frames, int n, int width, int height,
                                        int row_stride, size_t frame_stride);
 /* Blocks until the last batched call has finished. */
@@ -237,6 +250,13 @@ int orbx_fast_tile_counts(orbx_ctx* ctx, long long* worked, long long* total);
  * selection reports in which row each level's cap filled, and the FAST tile rows of the level are sized so that
  * the first pass ends just below it (the work is re-partitioned a few times per stream; never a result changes). */
 int orbx_set_top_rows_first(orbx_ctx* ctx, int mode);
+
+/* DEBUG entry, for tests only (not part of the product path, never called by bench.py): fills the working pools of
+ * both lanes -- pyramids, survivor masks, tile-row statistics, candidate / response / level-candidate pools and
+ * their counts -- with `byte` (0..255), after waiting for everything in flight.  Every batch must compute the same
+ * results whatever the pools held before it.  Of the blurred pyramid only the pixels of the current frame size's
+ * levels are filled: the padding bytes of its levels are the one thing in the pools that has to stay zero. */
+int orbx_debug_fill_pools(orbx_ctx* ctx, int byte);
 
 /* Pipelined batches (default off).  With enable = 1, consecutive orbx_detect_and_compute_batch_device calls on the
  * context's own stream (stream = NULL) alternate between two LANES -- each with its own stream and its own working

@@ -19,12 +19,12 @@
 #include "orbx_internal.h"
 #include "orbx_tri_math.h"
 
+using namespace orbx_geom;  // orbx_plan.h: the geometry of a frame size and the tables built from it
+
 namespace {
 
 thread_local std::string g_create_error;
 
-inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
-inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct DevBuf {
   void* p = nullptr;
@@ -295,256 +295,6 @@ int ensure(orbx_ctx* c, DevBuf& b, size_t bytes) {
   return ORBX_OK;
 }
 
-// ---- geometry (src/orb.cpp:62, :95, :117-118) ------------------------------
-
-float level_scale(float sf, int l) { return (float)std::pow((double)sf, (double)l); }
-
-void level_size(int w0, int h0, float sf, int l, int* wl, int* hl) {
-  if (l == 0) {
-    *wl = w0;
-    *hl = h0;
-    return;
-  }
-  const float scale = level_scale(sf, l);
-  *wl = (int)std::round((double)((float)w0 / scale));
-  *hl = (int)std::round((double)((float)h0 / scale));
-}
-
-int level_quota(int nfeatures, float sf, int nlevels, int l) {
-  // int * ((float - float) / (int - double)) * double, truncated to int
-  const float inv = 1 / sf;
-  const float num = 1 - inv;
-  const double den = 1 - std::pow((double)inv, (double)nlevels);
-  return (int)(nfeatures * ((double)num / den) * std::pow((double)inv, (double)l));
-}
-
-void make_tilemap(const OrbxPlan& plan, int tw, int th, bool use_pitch, OrbxTileMap* tm) {
-  int acc = 0;
-  for (int l = 0; l < plan.nlevels; l++) {
-    const int wcols = use_pitch ? plan.L[l].pitch : plan.L[l].w;
-    const int tx = (wcols + tw - 1) / tw, ty = (plan.L[l].h + th - 1) / th;
-    tm->begin[l] = acc;
-    tm->tiles_x[l] = tx;
-    acc += tx * ty;
-  }
-  for (int l = plan.nlevels; l <= ORBX_MAX_LEVELS; l++) tm->begin[l] = acc;
-}
-
-// band-major order of the FAST tiles (levels shrink with the level index, so the
-// levels that have a tile row b are always a prefix of the level list)
-// strips: the units of the streaming kernel of the whole path (orbx_fast4.hip: a wave per 64-dword strip and tile
-// row) instead of the 128-pixel tiles of the LDS tile kernel (stage operators)
-int make_bandmap(const OrbxPlan& plan, int nms_radius, OrbxBandMap* bm, std::string* why, bool strips = false,
-                 const int* pref_h = nullptr) {
-  std::memset(bm, 0, sizeof(*bm));
-  const int tw = ORBX_FAST3_TW, th = orbx_fast3_tile_h(nms_radius);
-  int nb = 0;
-  for (int l = 0; l < plan.nlevels; l++) {
-    bm->tiles_x[l] = strips ? orbx_fast4_strips(plan.L[l].w, nms_radius) : (plan.L[l].w + tw - 1) / tw;
-    bm->tiles_y[l] = (plan.L[l].h + th - 1) / th;
-    bm->tile_h[l] = (plan.L[l].h + bm->tiles_y[l] - 1) / bm->tiles_y[l];  // balanced tile rows
-    // pref_h[l] > 0: SHORTER tile rows for this level (the adaptive first pass of the top-rows-first pipeline:
-    // adapt_tile_rows) -- never more tile rows than ORBX_MAX_BANDS or than the level above has (band-major order)
-    if (pref_h && pref_h[l] > 0 && pref_h[l] < bm->tile_h[l]) {
-      int hh = std::max(pref_h[l], ORBX_MIN_TILE_H);
-      const int most = l > 0 ? std::min(bm->tiles_y[l - 1], ORBX_MAX_BANDS) : ORBX_MAX_BANDS;
-      while ((plan.L[l].h + hh - 1) / hh > most) hh++;
-      if (hh < bm->tile_h[l]) {
-        bm->tile_h[l] = hh;
-        bm->tiles_y[l] = (plan.L[l].h + hh - 1) / hh;
-      }
-    }
-    bm->xprefix[l + 1] = bm->xprefix[l] + bm->tiles_x[l];
-    if (l > 0 && bm->tiles_y[l] > bm->tiles_y[l - 1]) {
-      *why = "pyramid levels must not grow with the level index";
-      return ORBX_ERR_UNSUPPORTED;
-    }
-    nb = std::max(nb, bm->tiles_y[l]);
-  }
-  if (nb > ORBX_MAX_BANDS) {
-    *why = "image taller than ORBX_MAX_BANDS FAST tile rows";
-    return ORBX_ERR_UNSUPPORTED;
-  }
-  bm->nbands = nb;
-  int acc = 0;
-  for (int b = 0; b < nb; b++) {
-    bm->band_begin[b] = acc;
-    for (int l = 0; l < plan.nlevels; l++)
-      if (bm->tiles_y[l] > b) acc += bm->tiles_x[l];
-  }
-  for (int b = nb; b <= ORBX_MAX_BANDS; b++) bm->band_begin[b] = acc;
-  return ORBX_OK;
-}
-
-// FAST tiles of ONE frame in band-major order (the kernel's grid is frames x tiles with
-// the frame index dispatched fastest, so tile row b of every frame runs before tile row
-// b+1 of any frame).  Tile rows >= first_band only; a workgroup owns `strip` tiles of a row.
-void build_fast_tiles(const OrbxPlan& plan, const OrbxBandMap& bm, int first_band, int strip,
-                      std::vector<OrbxTileDesc>* out) {
-  out->clear();
-  for (int b = first_band; b < bm.nbands; b++)
-    for (int l = 0; l < plan.nlevels; l++) {
-      if (bm.tiles_y[l] <= b) continue;
-      const OrbxLevel& L = plan.L[l];
-      for (int tx = 0; tx < bm.tiles_x[l]; tx += strip) {
-        OrbxTileDesc d{};
-        d.l = l;
-        d.tx = tx;
-        d.ty = b;
-        d.f = bm.tile_h[l];
-        d.w = L.w;
-        d.h = L.h;
-        d.pitch = L.pitch;
-        d.u0 = L.cap;
-        d.u1 = L.mask_wpr;
-        d.u2 = bm.tiles_x[l];
-        d.stat_index = (uint32_t)(l * ORBX_MAX_BANDS);
-        d.img_off = (uint64_t)L.img_off;
-        d.mask_off = (uint64_t)L.mask_off;
-        out->push_back(d);
-      }
-    }
-}
-
-// tiles of ONE frame, level-major, for the blur / pyramid kernels (blockIdx.y = frame)
-void build_frame_tiles(const OrbxPlan& plan, int tw, int th, bool pyramid_fields, std::vector<OrbxTileDesc>* out) {
-  out->clear();
-  for (int l = 0; l < plan.nlevels; l++) {
-    const OrbxLevel& L = plan.L[l];
-    // pyramid tiles: 8 rows per wave where a lane keeps only 4 registers per row in flight
-    // (level 0 copy, 8-byte-window levels), else 4
-    const int rpw = pyramid_fields ? ((l == 0 || L.win8 == 1) ? 8 : 4) : 0;
-    if (pyramid_fields) th = 4 * rpw;
-    const int ntx = (L.pitch + tw - 1) / tw, nty = (L.h + th - 1) / th;
-    for (int ty = 0; ty < nty; ty++)
-      for (int tx = 0; tx < ntx; tx++) {
-        OrbxTileDesc d{};
-        d.l = l;
-        d.tx = tx;
-        d.ty = ty;
-        d.f = rpw;
-        d.w = L.w;
-        d.h = L.h;
-        d.pitch = L.pitch;
-        if (pyramid_fields) {
-          d.u0 = L.xtab_off;
-          d.u1 = L.ytab_off;
-          d.u2 = L.win8 == 1;  // (k_pyramid2 knows the one-window mode only)
-        }
-        d.img_off = (uint64_t)L.img_off;
-        out->push_back(d);
-      }
-  }
-}
-
-// strips of the streaming blur for ONE frame: per level ceil(pitch / 256) strips x balanced row bands of
-// at most ORBX_BLUR3_RH rows (one wave each; the 4 warm-up rows of the vertical pass are per band)
-void build_blur_tiles(const OrbxPlan& plan, std::vector<OrbxTileDesc>* out) {
-  out->clear();
-  for (int l = 0; l < plan.nlevels; l++) {
-    const OrbxLevel& L = plan.L[l];
-    const int ntx = (L.pitch + ORBX_BLUR3_TW - 1) / ORBX_BLUR3_TW;  // the padding bytes are (re)written as zeros
-    const int nb = (L.h + ORBX_BLUR3_RH - 1) / ORBX_BLUR3_RH, rows = (L.h + nb - 1) / nb;
-    for (int b = 0; b < nb; b++)
-      for (int tx = 0; tx < ntx; tx++) {
-        OrbxTileDesc d{};
-        d.l = l;
-        d.tx = tx;
-        d.ty = b * rows;
-        d.f = std::min(rows, L.h - b * rows);
-        d.w = L.w;
-        d.h = L.h;
-        d.pitch = L.pitch;
-        d.img_off = (uint64_t)L.img_off;
-        if (d.f > 0) out->push_back(d);
-      }
-  }
-}
-
-// units of k_blur4 for ONE frame: per level ceil(pitch / 256) strips x waves of FOUR row bands each (f = rows per
-// band: a level's height spread over the fewest waves whose bands stay within ORBX_BLUR4_RH rows)
-void build_blur4_tiles(const OrbxPlan& plan, std::vector<OrbxTileDesc>* out) {
-  out->clear();
-  for (int l = 0; l < plan.nlevels; l++) {
-    const OrbxLevel& L = plan.L[l];
-    const int ntx = (L.pitch + ORBX_BLUR4_TW - 1) / ORBX_BLUR4_TW;  // the padding bytes are (re)written as zeros
-    const int nwv = (L.h + 4 * ORBX_BLUR4_RH - 1) / (4 * ORBX_BLUR4_RH), rows = (L.h + 4 * nwv - 1) / (4 * nwv);
-    for (int wv = 0; wv < nwv; wv++)
-      for (int tx = 0; tx < ntx; tx++) {
-        OrbxTileDesc d{};
-        d.l = l;
-        d.tx = tx;
-        d.ty = wv * 4 * rows;
-        d.f = rows;
-        d.w = L.w;
-        d.h = L.h;
-        d.pitch = L.pitch;
-        d.img_off = (uint64_t)L.img_off;
-        if (d.ty < L.h) out->push_back(d);
-      }
-  }
-}
-
-// strips of the fused pyramid + blur kernel for ONE frame: 248-px strips (the halo dwords are
-// computed by lanes 0 / 63) x balanced row bands, with the level's resize-table fields.
-// part 0: every row.  Top-rows-first pipeline (enqueue_batch): part 1 = the rows the FAST tiles of the
-// first `top_rows` tile rows and the descriptors of their keypoints can read -- rows below
-// top_rows * tile_h + ORBX_TOP_MARGIN -- and part 2 = the rest, whose strips carry what the kernel's skip
-// test needs (stat_index, mask_off = tile rows of the first pass << 32 | cap).
-#define ORBX_TOP_MARGIN 21  // a descriptor reaches DESC_R = 20 rows below its keypoint (orbx_kernels.hip); Harris, FAST less
-int pyrblur_first_pass_rows(const OrbxPlan& plan, const OrbxBandMap& bm, int l, int top_rows) {
-  if (top_rows <= 0 || bm.tiles_y[l] <= top_rows) return plan.L[l].h;
-  return std::min(plan.L[l].h, top_rows * bm.tile_h[l] + ORBX_TOP_MARGIN);
-}
-void build_pyrblur_tiles(const OrbxPlan& plan, int max_rows, std::vector<OrbxTileDesc>* out, bool heavy_first = false,
-                         int part = 0, const OrbxBandMap* bm = nullptr, int top_rows = 0) {
-  out->clear();
-  bool have_reporter = false;
-  for (int l = 0; l < plan.nlevels; l++) {
-    const OrbxLevel& L = plan.L[l];
-    // dwords that hold image pixels: 62 per strip, one more in the first and in the last strip (their
-    // outer neighbour is a reflection, not another strip's dword).  The padding dwords beyond are not
-    // written by this kernel: they are zeroed when the plan is set.
-    const int dw = (L.w + 3) / 4;
-    const int ntx = dw <= 64 ? 1 : (dw - 2 + 61) / 62;
-    const int split = part == 0 ? L.h : pyrblur_first_pass_rows(plan, *bm, l, top_rows);
-    const int r0 = part == 2 ? split : 0, r1 = part == 1 ? split : L.h;
-    if (r1 <= r0) continue;
-    const int nb = (r1 - r0 + max_rows - 1) / max_rows, rows = (r1 - r0 + nb - 1) / nb;
-    for (int b = 0; b < nb; b++)
-      for (int tx = 0; tx < ntx; tx++) {
-        OrbxTileDesc d{};
-        d.l = l;
-        d.tx = tx;
-        d.ty = r0 + b * rows;
-        d.f = std::min(rows, r1 - d.ty);
-        d.w = L.w;
-        d.h = L.h;
-        d.pitch = L.pitch;
-        d.u0 = L.xtab_off;
-        d.u1 = L.ytab_off;
-        d.u2 = L.win8;
-        d.pad = (uint32_t)ntx;
-        d.img_off = (uint64_t)L.img_off;
-        if (part == 2) {
-          d.stat_index = (uint32_t)(l * ORBX_MAX_BANDS);
-          d.mask_off = ((uint64_t)(uint32_t)std::min(top_rows, bm->tiles_y[l]) << 32) | (uint32_t)L.cap;
-          if (b == 0 && tx == 0 && !have_reporter) {  // this strip's wave reports the verdicts of all the frame's levels
-            d.mask_off |= 1ull << 62;
-            have_reporter = true;
-          }
-        }
-        if (d.f > 0) out->push_back(d);
-      }
-  }
-  if (heavy_first) {
-    // estimated instructions per strip row: level 0 copies, the 8-byte-window levels resize, the others gather
-    auto cost = [](const OrbxTileDesc& d) { return (d.f + 4) * (d.l == 0 ? 35 : d.u2 == 1 ? 80 : 90); };
-    std::stable_sort(out->begin(), out->end(),
-                     [&](const OrbxTileDesc& a, const OrbxTileDesc& b) { return cost(a) > cost(b); });
-  }
-}
-
 // ORBX_PYR_GROUP=g: frames per dispatch group of the fused pyramid + blur kernel (0: frame-major grid)
 int pyr_group_env() {
   static const int v = [] {
@@ -574,79 +324,12 @@ int fast_impl_env() {
   return e && atoi(e) == 3 ? 3 : 4;
 }
 
-int build_plan(const orbx_params& p, int w0, int h0, OrbxPlan* plan, std::string* why, int fast_impl = 3) {
-  std::memset(plan, 0, sizeof(*plan));
-  plan->nlevels = p.nlevels;
-  plan->w0 = w0;
-  plan->h0 = h0;
-  size_t img_off = 0, mask_off = 0;
-  int cand_off = 0, out_cap = 0, xt = 0;
-  for (int l = 0; l < p.nlevels; l++) {
-    OrbxLevel& L = plan->L[l];
-    level_size(w0, h0, p.scale_factor, l, &L.w, &L.h);
-    if (L.w < 8 || L.h < 8) {
-      *why = "pyramid level " + std::to_string(l) + " is smaller than 8x8 (" + std::to_string(L.w) + "x" +
-             std::to_string(L.h) + ")";
-      return ORBX_ERR_UNSUPPORTED;
-    }
-    L.pitch = align_up(L.w, 64);
-    L.img_off = (int32_t)img_off;
-    img_off = align_up_sz(img_off + (size_t)L.pitch * L.h, 256);
-    // the whole path's FAST kernel writes its survivor masks in strip layout (orbx_fast4.hip)
-    if (fast_impl == 4) {
-      L.mask_strip_px = 4 * orbx_fast4_strip_lanes(p.nms_window / 2);
-      L.mask_wpr = 4 * orbx_fast4_strips(L.w, p.nms_window / 2);
-    } else {
-      L.mask_wpr = (L.w + 63) / 64;
-    }
-    L.mask_off = (int32_t)mask_off;
-    mask_off += (size_t)L.mask_wpr * L.h;
-    int quota;
-    if (p.select_mode == ORBX_SELECT_ROWMAJOR && p.nlevels == 1)
-      quota = p.nfeatures;  // OrientedFASTCPU::detect cap (src/orb_cpu.cpp:110)
-    else
-      quota = level_quota(p.nfeatures, p.scale_factor, p.nlevels, l);
-    if (quota < 0) quota = 0;
-    L.quota = quota;
-    L.cap = p.select_mode == ORBX_SELECT_HARRIS ? 2 * quota : quota;  // src/orb.cpp:63
-    if (L.cap > ORBX_MAX_SELECT) {
-      *why = "per-level FAST cap " + std::to_string(L.cap) + " exceeds ORBX_MAX_SELECT";
-      return ORBX_ERR_UNSUPPORTED;
-    }
-    L.cand_off = cand_off;
-    cand_off += L.cap;
-    L.out_off = out_cap;
-    out_cap += quota;
-    L.scale = level_scale(p.scale_factor, l);
-    // x table first (padded to a multiple of 4 entries = 32 bytes so that a thread's
-    // four taps are two aligned 16-byte loads), then the y table
-    L.xtab_off = xt;
-    L.ytab_off = xt + (l == 0 ? 0 : align_up(L.w, 4));
-    xt += (l == 0 ? 0 : align_up(L.w, 4) + align_up(L.h, 4));
-    if (img_off > 0x7fffffffull) {
-      *why = "pyramid frame exceeds 2 GiB";
-      return ORBX_ERR_UNSUPPORTED;
-    }
-  }
-  plan->frame_bytes = (int32_t)img_off;
-  plan->mask_words = (int32_t)mask_off;
-  // (the selection output lives in the candidate pools, at the result blocks' stride: in the row-major mode, where a
-  // level's cap is its quota, the rounded-up slot count below is the larger of the two)
-  plan->cand_total = std::max(cand_off, (out_cap + 15) & ~15);
-  // slots per frame of the result blocks: the sum of the quotas, rounded up to 16 -- a describe workgroup's 16 slots
-  // are then whole 64-byte lines of every section (fewer, full-line writes when the record goes to the host mirror)
-  plan->out_cap = (out_cap + 15) & ~15;
-  return ORBX_OK;
-}
-
 // 8-bit bilinear coefficient tables: OpenCV 4.x generic 8UC1 INTER_LINEAR path
 // (imgproc/src/resize.cpp: scale = 1/((double)dst/src); fx = (float)((dx+0.5)*
 // scale-0.5); sx = floor(fx); clamp with fx=0; 11-bit coefficients by cvRound).
 // OpenCV is not part of this image: PARITY UNPINNED (DESIGN.md "Pyramid").
 void make_taps(OrbxPlan& plan, std::vector<OrbxResizeTap>* taps) {
-  size_t total = 0;
-  for (int l = 1; l < plan.nlevels; l++) total += (size_t)align_up(plan.L[l].w, 4) + align_up(plan.L[l].h, 4);
-  taps->assign(total ? total : 1, OrbxResizeTap{0, 0, 0});
+  taps->assign(taps_count(plan), OrbxResizeTap{0, 0, 0});
   for (int l = 1; l < plan.nlevels; l++) {
     const OrbxLevel& L = plan.L[l];
     const double scale_x = 1. / ((double)L.w / plan.w0), scale_y = 1. / ((double)L.h / plan.h0);
@@ -751,8 +434,6 @@ int validate_params(const orbx_params& p, std::string* why) {
   return ORBX_OK;
 }
 
-void blur_tiles_for_impl(int impl, const OrbxPlan& plan, std::vector<OrbxTileDesc>* out);
-
 // the working pools of lane k become the context's current ones
 void use_lane(orbx_ctx* c, int k) {
   const orbx_ctx::LanePool& L = c->lane_pool[k];
@@ -801,6 +482,9 @@ int set_plan(orbx_ctx* c, int w, int h) {
   if (c->last_stream && c->last_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->last_stream));
   HIPCHK(c, hipMemcpy(c->d_taps, c->h_taps.data(), c->h_taps.size() * sizeof(OrbxResizeTap),
                       hipMemcpyHostToDevice));
+  // no plan is set until every table below is in place: a call that fails on the way must not leave the previous
+  // size's (plan_w, plan_h) standing for tables that are half replaced
+  c->plan_w = c->plan_h = 0;
   c->plan = plan;
   // the fused pyramid + blur kernel writes only the dwords that hold image pixels; consumers rely on the
   // padding bytes of a level being zero (BRIEF's zero-extension), and another frame size re-uses the pool
@@ -815,9 +499,17 @@ int set_plan(orbx_ctx* c, int w, int h) {
   // (the adaptive first pass's shorter tile rows only where the top-rows-first pipeline can run at all: with the
   // early exit or the fused kernel switched off every tile works, and the default rows have the smaller halo share)
   c->prefs_applied = tile_prefs_apply(c);
-  if ((st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4,
-                         c->prefs_applied ? c->tile_h_pref : nullptr)) != ORBX_OK)
-    return fail(c, st, why);
+  st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4,
+                    c->prefs_applied ? c->tile_h_pref : nullptr);
+  if (c->prefs_applied && (st != ORBX_OK || (size_t)c->bm_fast.band_begin[c->bm_fast.nbands] > c->tiles_fast_capacity)) {
+    // The learned tile rows give a table the pool cannot hold (tiles_fast_capacity is an upper bound over every
+    // preference, orbx_plan.h: this is a second line of defence).  What was learned is only a partition of the work:
+    // forget it, take the default rows and run the batch -- a failure here would repeat with every batch of this size.
+    for (int l = 0; l < ORBX_MAX_LEVELS; l++) c->tile_h_pref[l] = 0;
+    c->prefs_applied = false;
+    st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4, nullptr);
+  }
+  if (st != ORBX_OK) return fail(c, st, why);
   {
     std::vector<OrbxTileDesc> t;
     blur_tiles_for_impl(c->blur_impl, plan, &t);
@@ -927,12 +619,6 @@ int blur_impl_env() {
   const char* e = getenv("ORBX_BLUR_IMPL");
   const int v = e ? atoi(e) : 2;
   return v >= 1 && v <= 3 ? v : 2;
-}
-void blur_tiles_for_impl(int impl, const OrbxPlan& plan, std::vector<OrbxTileDesc>* out) {
-  if (impl == 3)
-    build_blur4_tiles(plan, out);
-  else
-    build_blur_tiles(plan, out);
 }
 hipError_t launch_blur_auto(int impl, hipStream_t s, const OrbxPlan& P, const OrbxTileMap& tm1, const OrbxTileDesc* tiles2,
                             int ntiles2, int n, const uint8_t* src, uint8_t* dst, int first_level, int kind) {
@@ -1509,25 +1195,17 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
   CREATE_CHK(hipMemset(c->d_feedback, 0, ORBX_FEEDBACK_WORDS * 4));
   CREATE_CHK(hipHostMalloc((void**)&c->h_feedback, ORBX_FEEDBACK_WORDS * 4, hipHostMallocDefault));
   for (int i = 0; i < ORBX_FEEDBACK_WORDS; i++) c->h_feedback[i] = 0;
+  OrbxTableCapacity tcap{};  // what any frame up to the maximum needs of the table pools (orbx_plan.h: table_capacity)
+  if ((st = table_capacity(*p, M, c->fast_impl, c->blur_impl, &tcap, &why)) != ORBX_OK) {
+    orbx_destroy(c);
+    return fail(nullptr, st, why);
+  }
   {
-    OrbxBandMap bmm;  // (sized for the shortest tile rows the adaptive first pass may choose)
-    int min_pref[ORBX_MAX_LEVELS];
-    for (int l = 0; l < ORBX_MAX_LEVELS; l++) min_pref[l] = ORBX_MIN_TILE_H;
-    if ((st = make_bandmap(M, p->nms_window / 2, &bmm, &why, c->fast_impl == 4, min_pref)) != ORBX_OK) {
-      orbx_destroy(c);
-      return fail(nullptr, st, why);
-    }
-    c->tiles_fast_capacity = (size_t)bmm.band_begin[bmm.nbands];
+    c->tiles_fast_capacity = tcap.fast;
     CREATE_CHK(hipMalloc((void**)&c->d_tiles_fast, std::max<size_t>(c->tiles_fast_capacity, 1) * sizeof(OrbxTileDesc)));
-    std::vector<OrbxTileDesc> t1, t2;
-    blur_tiles_for_impl(c->blur_impl, M, &t1);
-    build_frame_tiles(M, ORBX_PYR2_TW, ORBX_PYR2_TH, true, &t2);
-    std::vector<OrbxTileDesc> t3, t4;
-    build_pyrblur_tiles(M, ORBX_PYRBLUR_RH, &t3);
-    build_pyrblur_tiles(M, ORBX_PYRBLUR_RH_SMALL, &t4);
-    c->tiles_small_capacity = t4.size() + 64;
+    c->tiles_small_capacity = tcap.small;
     CREATE_CHK(hipMalloc((void**)&c->d_tiles_pyrblur_small, c->tiles_small_capacity * sizeof(OrbxTileDesc)));
-    c->tiles_frame_capacity = std::max(std::max(t1.size(), t2.size()), t3.size()) + 256;  // (+ the extra bands of a split table)
+    c->tiles_frame_capacity = tcap.frame;
     CREATE_CHK(hipMalloc((void**)&c->d_tiles_pyrblur, c->tiles_frame_capacity * sizeof(OrbxTileDesc)));
     CREATE_CHK(hipMalloc((void**)&c->d_tiles_pyrblur_top, c->tiles_frame_capacity * sizeof(OrbxTileDesc)));
     CREATE_CHK(hipMalloc((void**)&c->d_tiles_pyrblur_rest, c->tiles_frame_capacity * sizeof(OrbxTileDesc)));
@@ -1542,10 +1220,8 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
   CREATE_CHK(hipMalloc((void**)&c->d_lresp, B * (size_t)std::max(M.cand_total, 1) * sizeof(float)));
   CREATE_CHK(hipMalloc((void**)&c->d_lcount, B * ORBX_MAX_LEVELS * sizeof(int32_t)));
   {
-    size_t taps = 1;
-    for (int l = 1; l < M.nlevels; l++) taps += (size_t)align_up(M.L[l].w, 4) + align_up(M.L[l].h, 4);
     // level sizes of smaller frames never exceed those of the largest frame
-    c->taps_capacity = taps + 16;
+    c->taps_capacity = tcap.taps;
     CREATE_CHK(hipMalloc((void**)&c->d_taps, c->taps_capacity * sizeof(OrbxResizeTap)));
   }
   {
@@ -1627,6 +1303,9 @@ int orbx_detect_and_compute_batch_device(orbx_ctx* c, const void* d_frames, int 
   if (row_stride < width) return fail(c, ORBX_ERR_INVALID_ARG, "row_stride < width");
   if (frame_stride < (size_t)row_stride * (size_t)(height - 1) + (size_t)width)
     return fail(c, ORBX_ERR_INVALID_ARG, "frame_stride smaller than a frame");
+  // the kernels address the bytes of one frame with 32-bit offsets (a buffer descriptor per frame)
+  if ((unsigned long long)row_stride * (unsigned long long)(height - 1) + (unsigned long long)width > 0x7fffffffull)
+    return fail(c, ORBX_ERR_INVALID_ARG, "row_stride * (height - 1) + width exceeds 2^31 - 1");
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   return run_batch(c, (const uint8_t*)d_frames, n, width, height, row_stride, frame_stride, s, true);
 }
@@ -1700,6 +1379,45 @@ int orbx_set_pipelined_batches(orbx_ctx* c, int enable) {
     }
   }
   c->pipelined = enable != 0;
+  return ORBX_OK;
+}
+
+// Debug entry (tests): every working pool of both lanes is filled with `byte`, so that a kernel that consumes a word
+// an earlier batch, another frame size or another tile partition left behind shows in the results.
+int orbx_debug_fill_pools(orbx_ctx* c, int byte) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (byte < 0 || byte > 255) return fail(c, ORBX_ERR_INVALID_ARG, "byte must be in [0, 255]");
+  if (c->last_stream) HIPCHK(c, hipStreamSynchronize(c->last_stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, lanes_sync(c));
+  const OrbxPlan& M = c->plan_max;
+  const size_t B = (size_t)c->p.max_batch, nc = (size_t)std::max(M.cand_total, 1);
+  for (const orbx_ctx::LanePool& L : c->lane_pool) {
+    if (!L.d_mask) continue;  // (lane 1 exists once the pipelined mode has been switched on)
+    HIPCHK(c, hipMemsetAsync(L.d_pyr, byte, B * (size_t)M.frame_bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(L.d_mask, byte, B * (size_t)M.mask_words * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(L.d_row_stat, byte, B * ORBX_FAST_STAT_WORDS * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(L.d_cand, byte, B * nc * sizeof(orbx_keypoint), c->stream));
+    HIPCHK(c, hipMemsetAsync(L.d_cand_count, byte, B * ORBX_MAX_LEVELS * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(L.d_cand_total, byte, B * ORBX_MAX_LEVELS * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(L.d_resp, byte, B * nc * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(L.d_lcand, byte, B * nc * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(L.d_lresp, byte, B * nc * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(L.d_lcount, byte, B * ORBX_MAX_LEVELS * sizeof(int32_t), c->stream));
+    // The blurred pyramid is the one pool that must hold zeroes: the padding bytes of its levels (set_plan zeroes
+    // them, the fused pyramid + blur kernel never writes them, BRIEF reads them as the zero extension of a row).  So
+    // only the PIXELS of the current plan's levels are filled -- what a skipped strip of the top-rows-first pipeline
+    // leaves behind -- and nothing before a plan is set.
+    if (L.d_pyr_blur && c->plan_w > 0)
+      for (size_t f = 0; f < B; f++)
+        for (int l = 0; l < c->plan.nlevels; l++) {
+          const OrbxLevel& V = c->plan.L[l];
+          HIPCHK(c, hipMemset2DAsync(L.d_pyr_blur + f * (size_t)c->plan.frame_bytes + (size_t)V.img_off, (size_t)V.pitch, byte,
+                                     (size_t)V.w, (size_t)V.h, c->stream));
+        }
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return ORBX_OK;
 }
 

@@ -6,56 +6,13 @@
 
 #include "../../include/orbx.h"
 
-// ---- HBM layout ------------------------------------------------------------
-// A "pyramid frame" holds all levels of one input frame back to back:
-//   level l at byte offset img_off, `h` rows of `pitch` bytes, pitch = W_l
-//   rounded up to 64 (so every tile row starts 4-byte aligned and a 64-pixel
-//   tile row never straddles the allocation), level offsets 256-B aligned.
-// The NMS survivor mask of a level is h rows of `mask_wpr` 64-bit words
-// (bit x&63 of word x>>6), all levels back to back at mask_off (in words).
-// Candidate keypoints / Harris responses of a frame live in `cand_total`
-// slots, level l owning [cand_off, cand_off + cap).
-struct OrbxLevel {
-  int32_t w, h, pitch;
-  int32_t img_off;   // bytes, within a pyramid frame
-  int32_t mask_wpr;  // u64 words per mask row
-  int32_t mask_off;  // u64 words, within a frame's mask block
-  int32_t cap;       // FAST cap (row-major)        src/orb.cpp:63
-  int32_t quota;     // kept after selection        src/orb.cpp:62
-  int32_t cand_off;  // first candidate slot
-  int32_t xtab_off;  // first entry of this level's resize x-table
-  int32_t ytab_off;  // first entry of this level's resize y-table
-  float scale;       // (float)pow(scaleFactor, l)  src/orb.cpp:95
-  int32_t out_off;   // first STATIC selection slot of this level = sum of the lower levels' quotas
-  int32_t win8;      // resize: 1: the 4 source pairs of any aligned group of 4 outputs fit one 8-byte window; 3: a strip's source span fits the LDS staging rows of k_pyrblur; 0: neither (2-byte gathers)
-  // 0: classic mask rows (bit x & 63 of word x >> 6).  > 0: STRIP layout of the streaming FAST kernel
-  // (orbx_fast4.hip): 4 words per strip and row, word 4 s + q of a row holds pixels mask_strip_px * s + 64 q + bit
-  // (a strip's first / last halo pixels are zero bits), so x = (xw >> 2) * mask_strip_px + (xw & 3) * 64 + bit
-  int32_t mask_strip_px;
-};
+#include "orbx_plan.h"  // levels, plans, tile tables and their constants (host arithmetic, no HIP)
+
 // pixel x of bit `b` of mask word `xw` of a row
 __host__ __device__ inline int orbx_mask_x(const OrbxLevel& L, int xw, int b) {
   return L.mask_strip_px ? (xw >> 2) * L.mask_strip_px + (xw & 3) * 64 + b : xw * 64 + b;
 }
 
-struct OrbxPlan {
-  int32_t nlevels;
-  int32_t w0, h0;
-  int32_t frame_bytes;  // pyramid frame stride (bytes)
-  int32_t mask_words;   // mask stride per frame (u64 words)
-  int32_t cand_total;   // candidate slots per frame
-  int32_t out_cap;      // result slots per frame (sum of quotas)
-  OrbxLevel L[ORBX_MAX_LEVELS];
-};
-
-// blockIdx.x -> (level, tile) map for one kernel's tile size
-struct OrbxTileMap {
-  int32_t begin[ORBX_MAX_LEVELS + 1];  // first tile id of each level (+ total)
-  int32_t tiles_x[ORBX_MAX_LEVELS];
-};
-
-// band-major workgroup order of the FAST kernel (see decode_band)
-#define ORBX_MAX_BANDS 64
 // FAST early-exit state per frame (u64 words): tile-row statistics [level][band], then one
 // "dead from band" word per level
 #define ORBX_FAST_STAT_WORDS (ORBX_MAX_LEVELS * ORBX_MAX_BANDS + ORBX_MAX_LEVELS)
@@ -63,51 +20,6 @@ struct OrbxTileMap {
 // [0] levels skipped, [1] levels produced (running totals), [2 + l] rows level l needed to fill its cap (maximum
 // over the frames of the last batch; 0: not reported)
 #define ORBX_FEEDBACK_WORDS (2 + ORBX_MAX_LEVELS)
-// smallest FAST tile-row height the adaptive first pass may choose (orbx_api.cpp, adapt_tile_rows)
-#define ORBX_MIN_TILE_H 16
-struct OrbxBandMap {
-  int32_t nbands;
-  int32_t band_begin[ORBX_MAX_BANDS + 1];  // tiles PER FRAME before band b (+ total)
-  int32_t tiles_x[ORBX_MAX_LEVELS];
-  int32_t tiles_y[ORBX_MAX_LEVELS];
-  int32_t tile_h[ORBX_MAX_LEVELS];       // rows per FAST tile of the level (balanced: ceil(h / tiles_y))
-  int32_t xprefix[ORBX_MAX_LEVELS + 1];  // prefix sums of tiles_x
-};
-
-// One 64-byte record per workgroup, read with a single scalar load: everything a
-// tile kernel needs to know about its tile.  Replaces the chains of dependent
-// scalar loads that decoding blockIdx through the plan / tile maps costs at the
-// start of every wave (~20 s_load round trips for the FAST kernel).
-//   FAST table   : one entry per (tile row, level, tx) of ONE frame in band-major order
-//                  (grid = frames x tiles, frame index dispatched fastest); `f` = rows per tile
-//                  of this level.
-//   pyramid      : one entry per (level, tx, ty) of ONE frame (blockIdx.y = frame); u0/u1/u2
-//                  carry xtab_off / ytab_off / win8 and `f` the rows per wave.
-//   blur         : one entry per (level, 256-px strip, row band): tx = strip, ty = first row,
-//                  f = rows of the band.
-//                  fused pyramid + blur, second pass of the top-rows-first pipeline: stat_index = first
-//                  tile-row statistic of the level, mask_off = (FAST tile rows of the first pass) << 32 | cap,
-//                  bit 62 set in ONE strip per frame (its wave reports how many levels of the frame were skipped).
-//   img_off / mask_off are offsets inside one frame's pyramid / mask block.
-struct OrbxTileDesc {
-  int32_t l, tx, ty, f;
-  int32_t w, h, pitch;
-  int32_t u0;  // FAST: cap            pyramid: xtab_off
-  int32_t u1;  // FAST: mask_wpr       pyramid: ytab_off
-  int32_t u2;  // FAST: tiles_x        pyramid: win8
-  uint32_t stat_index;  // FAST: first tile-row statistic of (frame, level)
-  uint32_t pad;
-  uint64_t img_off;   // bytes from the pyramid base
-  uint64_t mask_off;  // u64 words from the mask base (FAST)
-};
-static_assert(sizeof(OrbxTileDesc) == 64, "one 64-byte scalar load per workgroup");
-
-// 8-bit bilinear resize coefficient (OpenCV-style 11-bit fixed point)
-struct OrbxResizeTap {
-  int32_t ofs;     // source index (clamped)
-  int16_t c0, c1;  // weights of src[ofs], src[ofs+1]; c0+c1 ~ 2048
-};
-
 // the levels whose lower rows the second pass of the top-rows-first pipeline may skip (orbx_api.cpp, enqueue_batch)
 struct OrbxTopLevels {
   int32_t n;
@@ -119,49 +31,6 @@ struct OrbxTopLevels {
 struct OrbxFastParams {
   int32_t threshold, n, nms_radius;
 };
-
-// tile geometry of the FAST/NMS kernel (orbx_fast.hip): 128 output pixels wide (two mask words per
-// row); 34 dword columns x 7 row segments of walking threads, 7 rows per walk (at most 8: a flag byte per
-// pixel column), so the score region of a tile has 49 rows and a tile 49 - 2 * nms_radius output rows
-#define ORBX_FAST3_TW 128
-#define ORBX_FAST3_K 7
-constexpr int orbx_fast3_tile_h(int nms_radius) {
-  return (256 / (ORBX_FAST3_TW / 4 + 2)) * ORBX_FAST3_K - 2 * nms_radius;
-}
-// streaming FAST kernel (orbx_fast4.hip): a wave owns a strip of 64 dwords; the outer `halo` dwords of a side are
-// context for the ring (3 px) and the NMS window (R px) of the pixels next to them; tile rows as above
-constexpr int orbx_fast4_halo(int nms_radius) { return (nms_radius + 3 + 3) / 4; }
-constexpr int orbx_fast4_strip_lanes(int nms_radius) { return 64 - 2 * orbx_fast4_halo(nms_radius); }
-constexpr int orbx_fast4_strips(int w, int nms_radius) {
-  const int ndw = (w + 3) / 4, s = orbx_fast4_strip_lanes(nms_radius), n = (ndw - 2 * orbx_fast4_halo(nms_radius) + s - 1) / s;
-  return n < 1 ? 1 : n;
-}
-// tile geometry of the blur kernel
-#define ORBX_BLUR_TW 64
-#define ORBX_BLUR_TH 16
-// register-streaming separable blur (orbx_blur.hip): a wave owns a strip of 256 pixels (one aligned
-// 256-byte segment per row) over a band of at most ORBX_BLUR3_RH rows
-#define ORBX_BLUR3_TW 256
-#define ORBX_BLUR3_RH 64
-// k_blur4: 16 pixels per lane, a wave = a 256-px strip x 4 row bands of at most ORBX_BLUR4_RH rows
-#define ORBX_BLUR4_TW 256
-#define ORBX_BLUR4_RH 96
-// fused pyramid + blur: the halo dwords are computed, not loaded, so lanes 0 / 63 are halo-only
-#define ORBX_PYRBLUR_TW 248
-// LDS staging of the source rows of the levels whose pairs do not fit the 8-byte window (scale > 2): bytes of a
-// source row a strip may need.  (Measured per level of 1241x376, 256 frames: scale 2.1: 41 us staged / 56 us with
-// 2-byte gathers, 2.5: 35 / 43, 3.0: 27 / 32, 3.5 (896 bytes): 30 / 29 -- the staged loads cost the texture
-// addresser a cycle per four lane-dwords like any other, and at 8 x 104 bytes they are as many as the gathers'.)
-#define ORBX_PYR_STAGE_BYTES 832
-// rows per band of the fused kernel: the y taps of a band's input rows (rows + 6) sit one per lane
-#define ORBX_PYRBLUR_RH 58
-#define ORBX_PYRBLUR_RH_SMALL 12  // few frames per call: many short waves instead
-// pyramid kernel: a wave owns 256 x 8 pixels (level 0 and the levels resized through 8-byte
-// windows) or 256 x 4, a workgroup four times that; OrbxTileDesc::f carries the rows per wave
-#define ORBX_PYR2_TW 256
-#define ORBX_PYR2_TH 16  // smallest tile height (sizes the tile table pool)
-
-#define ORBX_MAX_SELECT 4096  // largest per-level FAST cap the selection kernel holds in LDS (16 B per candidate)
 
 // ---- pyramidal Lucas-Kanade tracking (orbx_lk.hip) ---------------------------
 #define ORBX_LK_MAX_LEVELS 8

@@ -1,0 +1,556 @@
+// orbx_plan.h -- the geometry of a frame size: level sizes, the per-frame layout of the working pools, the tile /
+// strip tables of the kernels and the capacities a context sizes its table pools with.  Host arithmetic only, no
+// HIP in it: orbx_api.cpp runs this code, and tests/cpp/plan_capacity_sweep.cpp calls the very same functions to
+// check that every frame a context accepts fits the pools its maximum provides.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/orbx.h"
+
+// ---- HBM layout ------------------------------------------------------------
+// A "pyramid frame" holds all levels of one input frame back to back:
+//   level l at byte offset img_off, `h` rows of `pitch` bytes, pitch = W_l
+//   rounded up to 64 (so every tile row starts 4-byte aligned and a 64-pixel
+//   tile row never straddles the allocation), level offsets 256-B aligned.
+// The NMS survivor mask of a level is h rows of `mask_wpr` 64-bit words
+// (bit x&63 of word x>>6), all levels back to back at mask_off (in words).
+// Candidate keypoints / Harris responses of a frame live in `cand_total`
+// slots, level l owning [cand_off, cand_off + cap).
+struct OrbxLevel {
+  int32_t w, h, pitch;
+  int32_t img_off;   // bytes, within a pyramid frame
+  int32_t mask_wpr;  // u64 words per mask row
+  int32_t mask_off;  // u64 words, within a frame's mask block
+  int32_t cap;       // FAST cap (row-major)        src/orb.cpp:63
+  int32_t quota;     // kept after selection        src/orb.cpp:62
+  int32_t cand_off;  // first candidate slot
+  int32_t xtab_off;  // first entry of this level's resize x-table
+  int32_t ytab_off;  // first entry of this level's resize y-table
+  float scale;       // (float)pow(scaleFactor, l)  src/orb.cpp:95
+  int32_t out_off;   // first STATIC selection slot of this level = sum of the lower levels' quotas
+  int32_t win8;      // resize: 1: the 4 source pairs of any aligned group of 4 outputs fit one 8-byte window; 3: a strip's source span fits the LDS staging rows of k_pyrblur; 0: neither (2-byte gathers)
+  // 0: classic mask rows (bit x & 63 of word x >> 6).  > 0: STRIP layout of the streaming FAST kernel
+  // (orbx_fast4.hip): 4 words per strip and row, word 4 s + q of a row holds pixels mask_strip_px * s + 64 q + bit
+  // (a strip's first / last halo pixels are zero bits), so x = (xw >> 2) * mask_strip_px + (xw & 3) * 64 + bit
+  int32_t mask_strip_px;
+};
+
+struct OrbxPlan {
+  int32_t nlevels;
+  int32_t w0, h0;
+  int32_t frame_bytes;  // pyramid frame stride (bytes)
+  int32_t mask_words;   // mask stride per frame (u64 words)
+  int32_t cand_total;   // candidate slots per frame
+  int32_t out_cap;      // result slots per frame (sum of quotas)
+  OrbxLevel L[ORBX_MAX_LEVELS];
+};
+
+// blockIdx.x -> (level, tile) map for one kernel's tile size
+struct OrbxTileMap {
+  int32_t begin[ORBX_MAX_LEVELS + 1];  // first tile id of each level (+ total)
+  int32_t tiles_x[ORBX_MAX_LEVELS];
+};
+
+// band-major workgroup order of the FAST kernel (see decode_band)
+#define ORBX_MAX_BANDS 64
+// smallest FAST tile-row height the adaptive first pass may choose (orbx_api.cpp, adapt_tile_rows)
+#define ORBX_MIN_TILE_H 16
+struct OrbxBandMap {
+  int32_t nbands;
+  int32_t band_begin[ORBX_MAX_BANDS + 1];  // tiles PER FRAME before band b (+ total)
+  int32_t tiles_x[ORBX_MAX_LEVELS];
+  int32_t tiles_y[ORBX_MAX_LEVELS];
+  int32_t tile_h[ORBX_MAX_LEVELS];       // rows per FAST tile of the level (balanced: ceil(h / tiles_y))
+  int32_t xprefix[ORBX_MAX_LEVELS + 1];  // prefix sums of tiles_x
+};
+
+// One 64-byte record per workgroup, read with a single scalar load: everything a
+// tile kernel needs to know about its tile.  Replaces the chains of dependent
+// scalar loads that decoding blockIdx through the plan / tile maps costs at the
+// start of every wave (~20 s_load round trips for the FAST kernel).
+//   FAST table   : one entry per (tile row, level, tx) of ONE frame in band-major order
+//                  (grid = frames x tiles, frame index dispatched fastest); `f` = rows per tile
+//                  of this level.
+//   pyramid      : one entry per (level, tx, ty) of ONE frame (blockIdx.y = frame); u0/u1/u2
+//                  carry xtab_off / ytab_off / win8 and `f` the rows per wave.
+//   blur         : one entry per (level, 256-px strip, row band): tx = strip, ty = first row,
+//                  f = rows of the band.
+//                  fused pyramid + blur, second pass of the top-rows-first pipeline: stat_index = first
+//                  tile-row statistic of the level, mask_off = (FAST tile rows of the first pass) << 32 | cap,
+//                  bit 62 set in ONE strip per frame (its wave reports how many levels of the frame were skipped).
+//   img_off / mask_off are offsets inside one frame's pyramid / mask block.
+struct OrbxTileDesc {
+  int32_t l, tx, ty, f;
+  int32_t w, h, pitch;
+  int32_t u0;  // FAST: cap            pyramid: xtab_off
+  int32_t u1;  // FAST: mask_wpr       pyramid: ytab_off
+  int32_t u2;  // FAST: tiles_x        pyramid: win8
+  uint32_t stat_index;  // FAST: first tile-row statistic of (frame, level)
+  uint32_t pad;
+  uint64_t img_off;   // bytes from the pyramid base
+  uint64_t mask_off;  // u64 words from the mask base (FAST)
+};
+static_assert(sizeof(OrbxTileDesc) == 64, "one 64-byte scalar load per workgroup");
+
+// 8-bit bilinear resize coefficient (OpenCV-style 11-bit fixed point)
+struct OrbxResizeTap {
+  int32_t ofs;     // source index (clamped)
+  int16_t c0, c1;  // weights of src[ofs], src[ofs+1]; c0+c1 ~ 2048
+};
+
+// tile geometry of the FAST/NMS kernel (orbx_fast.hip): 128 output pixels wide (two mask words per
+// row); 34 dword columns x 7 row segments of walking threads, 7 rows per walk (at most 8: a flag byte per
+// pixel column), so the score region of a tile has 49 rows and a tile 49 - 2 * nms_radius output rows
+#define ORBX_FAST3_TW 128
+#define ORBX_FAST3_K 7
+constexpr int orbx_fast3_tile_h(int nms_radius) {
+  return (256 / (ORBX_FAST3_TW / 4 + 2)) * ORBX_FAST3_K - 2 * nms_radius;
+}
+// streaming FAST kernel (orbx_fast4.hip): a wave owns a strip of 64 dwords; the outer `halo` dwords of a side are
+// context for the ring (3 px) and the NMS window (R px) of the pixels next to them; tile rows as above
+constexpr int orbx_fast4_halo(int nms_radius) { return (nms_radius + 3 + 3) / 4; }
+constexpr int orbx_fast4_strip_lanes(int nms_radius) { return 64 - 2 * orbx_fast4_halo(nms_radius); }
+constexpr int orbx_fast4_strips(int w, int nms_radius) {
+  const int ndw = (w + 3) / 4, s = orbx_fast4_strip_lanes(nms_radius), n = (ndw - 2 * orbx_fast4_halo(nms_radius) + s - 1) / s;
+  return n < 1 ? 1 : n;
+}
+// tile geometry of the blur kernel
+#define ORBX_BLUR_TW 64
+#define ORBX_BLUR_TH 16
+// register-streaming separable blur (orbx_blur.hip): a wave owns a strip of 256 pixels (one aligned
+// 256-byte segment per row) over a band of at most ORBX_BLUR3_RH rows
+#define ORBX_BLUR3_TW 256
+#define ORBX_BLUR3_RH 64
+// k_blur4: 16 pixels per lane, a wave = a 256-px strip x 4 row bands of at most ORBX_BLUR4_RH rows
+#define ORBX_BLUR4_TW 256
+#define ORBX_BLUR4_RH 96
+// fused pyramid + blur: the halo dwords are computed, not loaded, so lanes 0 / 63 are halo-only
+#define ORBX_PYRBLUR_TW 248
+// LDS staging of the source rows of the levels whose pairs do not fit the 8-byte window (scale > 2): bytes of a
+// source row a strip may need.  (Measured per level of 1241x376, 256 frames: scale 2.1: 41 us staged / 56 us with
+// 2-byte gathers, 2.5: 35 / 43, 3.0: 27 / 32, 3.5 (896 bytes): 30 / 29 -- the staged loads cost the texture
+// addresser a cycle per four lane-dwords like any other, and at 8 x 104 bytes they are as many as the gathers'.)
+#define ORBX_PYR_STAGE_BYTES 832
+// rows per band of the fused kernel: the y taps of a band's input rows (rows + 6) sit one per lane
+#define ORBX_PYRBLUR_RH 58
+#define ORBX_PYRBLUR_RH_SMALL 12  // few frames per call: many short waves instead
+// pyramid kernel: a wave owns 256 x 8 pixels (level 0 and the levels resized through 8-byte
+// windows) or 256 x 4, a workgroup four times that; OrbxTileDesc::f carries the rows per wave
+#define ORBX_PYR2_TW 256
+#define ORBX_PYR2_TH 16  // smallest tile height (sizes the tile table pool)
+
+#define ORBX_MAX_SELECT 4096  // largest per-level FAST cap the selection kernel holds in LDS (16 B per candidate)
+
+// a descriptor reaches DESC_R = 20 rows below its keypoint (orbx_kernels.hip); Harris, FAST less
+#define ORBX_TOP_MARGIN 21
+
+namespace orbx_geom {
+
+inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// ---- geometry (src/orb.cpp:62, :95, :117-118) ------------------------------
+
+inline float level_scale(float sf, int l) { return (float)std::pow((double)sf, (double)l); }
+
+inline void level_size(int w0, int h0, float sf, int l, int* wl, int* hl) {
+  if (l == 0) {
+    *wl = w0;
+    *hl = h0;
+    return;
+  }
+  const float scale = level_scale(sf, l);
+  *wl = (int)std::round((double)((float)w0 / scale));
+  *hl = (int)std::round((double)((float)h0 / scale));
+}
+
+inline int level_quota(int nfeatures, float sf, int nlevels, int l) {
+  // int * ((float - float) / (int - double)) * double, truncated to int
+  const float inv = 1 / sf;
+  const float num = 1 - inv;
+  const double den = 1 - std::pow((double)inv, (double)nlevels);
+  return (int)(nfeatures * ((double)num / den) * std::pow((double)inv, (double)l));
+}
+
+inline void make_tilemap(const OrbxPlan& plan, int tw, int th, bool use_pitch, OrbxTileMap* tm) {
+  int acc = 0;
+  for (int l = 0; l < plan.nlevels; l++) {
+    const int wcols = use_pitch ? plan.L[l].pitch : plan.L[l].w;
+    const int tx = (wcols + tw - 1) / tw, ty = (plan.L[l].h + th - 1) / th;
+    tm->begin[l] = acc;
+    tm->tiles_x[l] = tx;
+    acc += tx * ty;
+  }
+  for (int l = plan.nlevels; l <= ORBX_MAX_LEVELS; l++) tm->begin[l] = acc;
+}
+
+// units per tile row of a level: strips of the streaming kernel of the whole path (orbx_fast4.hip: a wave per
+// 64-dword strip and tile row) or the 128-pixel tiles of the LDS tile kernel (stage operators)
+inline int fast_tiles_x(int w, int nms_radius, bool strips) {
+  return strips ? orbx_fast4_strips(w, nms_radius) : (w + ORBX_FAST3_TW - 1) / ORBX_FAST3_TW;
+}
+
+// band-major order of the FAST tiles (levels shrink with the level index, so the
+// levels that have a tile row b are always a prefix of the level list)
+inline int make_bandmap(const OrbxPlan& plan, int nms_radius, OrbxBandMap* bm, std::string* why, bool strips = false,
+                        const int* pref_h = nullptr) {
+  std::memset(bm, 0, sizeof(*bm));
+  const int th = orbx_fast3_tile_h(nms_radius);
+  int nb = 0;
+  for (int l = 0; l < plan.nlevels; l++) {
+    bm->tiles_x[l] = fast_tiles_x(plan.L[l].w, nms_radius, strips);
+    bm->tiles_y[l] = (plan.L[l].h + th - 1) / th;
+    bm->tile_h[l] = (plan.L[l].h + bm->tiles_y[l] - 1) / bm->tiles_y[l];  // balanced tile rows
+    // pref_h[l] > 0: SHORTER tile rows for this level (the adaptive first pass of the top-rows-first pipeline:
+    // adapt_tile_rows) -- never more tile rows than ORBX_MAX_BANDS or than the level above has (band-major order)
+    if (pref_h && pref_h[l] > 0 && pref_h[l] < bm->tile_h[l]) {
+      int hh = std::max(pref_h[l], ORBX_MIN_TILE_H);
+      const int most = l > 0 ? std::min(bm->tiles_y[l - 1], ORBX_MAX_BANDS) : ORBX_MAX_BANDS;
+      while ((plan.L[l].h + hh - 1) / hh > most) hh++;
+      if (hh < bm->tile_h[l]) {
+        bm->tile_h[l] = hh;
+        bm->tiles_y[l] = (plan.L[l].h + hh - 1) / hh;
+      }
+    }
+    bm->xprefix[l + 1] = bm->xprefix[l] + bm->tiles_x[l];
+    if (l > 0 && bm->tiles_y[l] > bm->tiles_y[l - 1]) {
+      *why = "pyramid levels must not grow with the level index";
+      return ORBX_ERR_UNSUPPORTED;
+    }
+    nb = std::max(nb, bm->tiles_y[l]);
+  }
+  if (nb > ORBX_MAX_BANDS) {
+    *why = "image taller than ORBX_MAX_BANDS FAST tile rows";
+    return ORBX_ERR_UNSUPPORTED;
+  }
+  bm->nbands = nb;
+  int acc = 0;
+  for (int b = 0; b < nb; b++) {
+    bm->band_begin[b] = acc;
+    for (int l = 0; l < plan.nlevels; l++)
+      if (bm->tiles_y[l] > b) acc += bm->tiles_x[l];
+  }
+  for (int b = nb; b <= ORBX_MAX_BANDS; b++) bm->band_begin[b] = acc;
+  return ORBX_OK;
+}
+
+// The table builders below return the number of entries and fill `out` unless it is NULL (count only).
+
+// FAST tiles of ONE frame in band-major order (the kernel's grid is frames x tiles with
+// the frame index dispatched fastest, so tile row b of every frame runs before tile row
+// b+1 of any frame).  Tile rows >= first_band only; a workgroup owns `strip` tiles of a row.
+inline size_t build_fast_tiles(const OrbxPlan& plan, const OrbxBandMap& bm, int first_band, int strip,
+                               std::vector<OrbxTileDesc>* out) {
+  size_t cnt = 0;
+  if (out) out->clear();
+  for (int b = first_band; b < bm.nbands; b++)
+    for (int l = 0; l < plan.nlevels; l++) {
+      if (bm.tiles_y[l] <= b) continue;
+      const OrbxLevel& L = plan.L[l];
+      for (int tx = 0; tx < bm.tiles_x[l]; tx += strip) {
+        OrbxTileDesc d{};
+        d.l = l;
+        d.tx = tx;
+        d.ty = b;
+        d.f = bm.tile_h[l];
+        d.w = L.w;
+        d.h = L.h;
+        d.pitch = L.pitch;
+        d.u0 = L.cap;
+        d.u1 = L.mask_wpr;
+        d.u2 = bm.tiles_x[l];
+        d.stat_index = (uint32_t)(l * ORBX_MAX_BANDS);
+        d.img_off = (uint64_t)L.img_off;
+        d.mask_off = (uint64_t)L.mask_off;
+        if (out) out->push_back(d);
+        cnt++;
+      }
+    }
+  return cnt;
+}
+
+// tiles of ONE frame, level-major, for the blur / pyramid kernels (blockIdx.y = frame)
+inline size_t build_frame_tiles(const OrbxPlan& plan, int tw, int th, bool pyramid_fields, std::vector<OrbxTileDesc>* out) {
+  size_t cnt = 0;
+  if (out) out->clear();
+  for (int l = 0; l < plan.nlevels; l++) {
+    const OrbxLevel& L = plan.L[l];
+    // pyramid tiles: 8 rows per wave where a lane keeps only 4 registers per row in flight
+    // (level 0 copy, 8-byte-window levels), else 4
+    const int rpw = pyramid_fields ? ((l == 0 || L.win8 == 1) ? 8 : 4) : 0;
+    if (pyramid_fields) th = 4 * rpw;
+    const int ntx = (L.pitch + tw - 1) / tw, nty = (L.h + th - 1) / th;
+    for (int ty = 0; ty < nty; ty++)
+      for (int tx = 0; tx < ntx; tx++) {
+        OrbxTileDesc d{};
+        d.l = l;
+        d.tx = tx;
+        d.ty = ty;
+        d.f = rpw;
+        d.w = L.w;
+        d.h = L.h;
+        d.pitch = L.pitch;
+        if (pyramid_fields) {
+          d.u0 = L.xtab_off;
+          d.u1 = L.ytab_off;
+          d.u2 = L.win8 == 1;  // (k_pyramid2 knows the one-window mode only)
+        }
+        d.img_off = (uint64_t)L.img_off;
+        if (out) out->push_back(d);
+        cnt++;
+      }
+  }
+  return cnt;
+}
+
+// strips of the streaming blur for ONE frame: per level ceil(pitch / 256) strips x balanced row bands of
+// at most ORBX_BLUR3_RH rows (one wave each; the 4 warm-up rows of the vertical pass are per band)
+inline size_t build_blur_tiles(const OrbxPlan& plan, std::vector<OrbxTileDesc>* out) {
+  size_t cnt = 0;
+  if (out) out->clear();
+  for (int l = 0; l < plan.nlevels; l++) {
+    const OrbxLevel& L = plan.L[l];
+    const int ntx = (L.pitch + ORBX_BLUR3_TW - 1) / ORBX_BLUR3_TW;  // the padding bytes are (re)written as zeros
+    const int nb = (L.h + ORBX_BLUR3_RH - 1) / ORBX_BLUR3_RH, rows = (L.h + nb - 1) / nb;
+    for (int b = 0; b < nb; b++)
+      for (int tx = 0; tx < ntx; tx++) {
+        OrbxTileDesc d{};
+        d.l = l;
+        d.tx = tx;
+        d.ty = b * rows;
+        d.f = std::min(rows, L.h - b * rows);
+        d.w = L.w;
+        d.h = L.h;
+        d.pitch = L.pitch;
+        d.img_off = (uint64_t)L.img_off;
+        if (d.f > 0) {
+          if (out) out->push_back(d);
+          cnt++;
+        }
+      }
+  }
+  return cnt;
+}
+
+// units of k_blur4 for ONE frame: per level ceil(pitch / 256) strips x waves of FOUR row bands each (f = rows per
+// band: a level's height spread over the fewest waves whose bands stay within ORBX_BLUR4_RH rows)
+inline size_t build_blur4_tiles(const OrbxPlan& plan, std::vector<OrbxTileDesc>* out) {
+  size_t cnt = 0;
+  if (out) out->clear();
+  for (int l = 0; l < plan.nlevels; l++) {
+    const OrbxLevel& L = plan.L[l];
+    const int ntx = (L.pitch + ORBX_BLUR4_TW - 1) / ORBX_BLUR4_TW;  // the padding bytes are (re)written as zeros
+    const int nwv = (L.h + 4 * ORBX_BLUR4_RH - 1) / (4 * ORBX_BLUR4_RH), rows = (L.h + 4 * nwv - 1) / (4 * nwv);
+    for (int wv = 0; wv < nwv; wv++)
+      for (int tx = 0; tx < ntx; tx++) {
+        OrbxTileDesc d{};
+        d.l = l;
+        d.tx = tx;
+        d.ty = wv * 4 * rows;
+        d.f = rows;
+        d.w = L.w;
+        d.h = L.h;
+        d.pitch = L.pitch;
+        d.img_off = (uint64_t)L.img_off;
+        if (d.ty < L.h) {
+          if (out) out->push_back(d);
+          cnt++;
+        }
+      }
+  }
+  return cnt;
+}
+
+// the strip table of the stand-alone blur is built for the kernel that reads it (ORBX_BLUR_IMPL: 3 = k_blur4)
+inline size_t blur_tiles_for_impl(int impl, const OrbxPlan& plan, std::vector<OrbxTileDesc>* out) {
+  return impl == 3 ? build_blur4_tiles(plan, out) : build_blur_tiles(plan, out);
+}
+
+// strips of the fused pyramid + blur kernel for ONE frame: 248-px strips (the halo dwords are
+// computed by lanes 0 / 63) x balanced row bands, with the level's resize-table fields.
+// part 0: every row.  Top-rows-first pipeline (enqueue_batch): part 1 = the rows the FAST tiles of the
+// first `top_rows` tile rows and the descriptors of their keypoints can read -- rows below
+// top_rows * tile_h + ORBX_TOP_MARGIN -- and part 2 = the rest, whose strips carry what the kernel's skip
+// test needs (stat_index, mask_off = tile rows of the first pass << 32 | cap).
+inline int pyrblur_first_pass_rows(const OrbxPlan& plan, const OrbxBandMap& bm, int l, int top_rows) {
+  if (top_rows <= 0 || bm.tiles_y[l] <= top_rows) return plan.L[l].h;
+  return std::min(plan.L[l].h, top_rows * bm.tile_h[l] + ORBX_TOP_MARGIN);
+}
+inline size_t build_pyrblur_tiles(const OrbxPlan& plan, int max_rows, std::vector<OrbxTileDesc>* out,
+                                  bool heavy_first = false, int part = 0, const OrbxBandMap* bm = nullptr,
+                                  int top_rows = 0) {
+  size_t cnt = 0;
+  if (out) out->clear();
+  bool have_reporter = false;
+  for (int l = 0; l < plan.nlevels; l++) {
+    const OrbxLevel& L = plan.L[l];
+    // dwords that hold image pixels: 62 per strip, one more in the first and in the last strip (their
+    // outer neighbour is a reflection, not another strip's dword).  The padding dwords beyond are not
+    // written by this kernel: they are zeroed when the plan is set.
+    const int dw = (L.w + 3) / 4;
+    const int ntx = dw <= 64 ? 1 : (dw - 2 + 61) / 62;
+    const int split = part == 0 ? L.h : pyrblur_first_pass_rows(plan, *bm, l, top_rows);
+    const int r0 = part == 2 ? split : 0, r1 = part == 1 ? split : L.h;
+    if (r1 <= r0) continue;
+    const int nb = (r1 - r0 + max_rows - 1) / max_rows, rows = (r1 - r0 + nb - 1) / nb;
+    for (int b = 0; b < nb; b++)
+      for (int tx = 0; tx < ntx; tx++) {
+        OrbxTileDesc d{};
+        d.l = l;
+        d.tx = tx;
+        d.ty = r0 + b * rows;
+        d.f = std::min(rows, r1 - d.ty);
+        d.w = L.w;
+        d.h = L.h;
+        d.pitch = L.pitch;
+        d.u0 = L.xtab_off;
+        d.u1 = L.ytab_off;
+        d.u2 = L.win8;
+        d.pad = (uint32_t)ntx;
+        d.img_off = (uint64_t)L.img_off;
+        if (part == 2) {
+          d.stat_index = (uint32_t)(l * ORBX_MAX_BANDS);
+          d.mask_off = ((uint64_t)(uint32_t)std::min(top_rows, bm->tiles_y[l]) << 32) | (uint32_t)L.cap;
+          if (b == 0 && tx == 0 && !have_reporter) {  // this strip's wave reports the verdicts of all the frame's levels
+            d.mask_off |= 1ull << 62;
+            have_reporter = true;
+          }
+        }
+        if (d.f > 0) {
+          if (out) out->push_back(d);
+          cnt++;
+        }
+      }
+  }
+  if (heavy_first && out) {
+    // estimated instructions per strip row: level 0 copies, the 8-byte-window levels resize, the others gather
+    auto cost = [](const OrbxTileDesc& d) { return (d.f + 4) * (d.l == 0 ? 35 : d.u2 == 1 ? 80 : 90); };
+    std::stable_sort(out->begin(), out->end(),
+                     [&](const OrbxTileDesc& a, const OrbxTileDesc& b) { return cost(a) > cost(b); });
+  }
+  return cnt;
+}
+
+// fast_impl 4: the streaming FAST kernel's strip layout of the survivor masks, 3: classic mask rows
+inline int build_plan(const orbx_params& p, int w0, int h0, OrbxPlan* plan, std::string* why, int fast_impl = 3) {
+  std::memset(plan, 0, sizeof(*plan));
+  plan->nlevels = p.nlevels;
+  plan->w0 = w0;
+  plan->h0 = h0;
+  size_t img_off = 0, mask_off = 0;
+  int cand_off = 0, out_cap = 0, xt = 0;
+  for (int l = 0; l < p.nlevels; l++) {
+    OrbxLevel& L = plan->L[l];
+    level_size(w0, h0, p.scale_factor, l, &L.w, &L.h);
+    if (L.w < 8 || L.h < 8) {
+      *why = "pyramid level " + std::to_string(l) + " is smaller than 8x8 (" + std::to_string(L.w) + "x" +
+             std::to_string(L.h) + ")";
+      return ORBX_ERR_UNSUPPORTED;
+    }
+    L.pitch = align_up(L.w, 64);
+    L.img_off = (int32_t)img_off;
+    img_off = align_up_sz(img_off + (size_t)L.pitch * L.h, 256);
+    // the whole path's FAST kernel writes its survivor masks in strip layout (orbx_fast4.hip)
+    if (fast_impl == 4) {
+      L.mask_strip_px = 4 * orbx_fast4_strip_lanes(p.nms_window / 2);
+      L.mask_wpr = 4 * orbx_fast4_strips(L.w, p.nms_window / 2);
+    } else {
+      L.mask_wpr = (L.w + 63) / 64;
+    }
+    L.mask_off = (int32_t)mask_off;
+    mask_off += (size_t)L.mask_wpr * L.h;
+    int quota;
+    if (p.select_mode == ORBX_SELECT_ROWMAJOR && p.nlevels == 1)
+      quota = p.nfeatures;  // OrientedFASTCPU::detect cap (src/orb_cpu.cpp:110)
+    else
+      quota = level_quota(p.nfeatures, p.scale_factor, p.nlevels, l);
+    if (quota < 0) quota = 0;
+    L.quota = quota;
+    L.cap = p.select_mode == ORBX_SELECT_HARRIS ? 2 * quota : quota;  // src/orb.cpp:63
+    if (L.cap > ORBX_MAX_SELECT) {
+      *why = "per-level FAST cap " + std::to_string(L.cap) + " exceeds ORBX_MAX_SELECT";
+      return ORBX_ERR_UNSUPPORTED;
+    }
+    L.cand_off = cand_off;
+    cand_off += L.cap;
+    L.out_off = out_cap;
+    out_cap += quota;
+    L.scale = level_scale(p.scale_factor, l);
+    // x table first (padded to a multiple of 4 entries = 32 bytes so that a thread's
+    // four taps are two aligned 16-byte loads), then the y table
+    L.xtab_off = xt;
+    L.ytab_off = xt + (l == 0 ? 0 : align_up(L.w, 4));
+    xt += (l == 0 ? 0 : align_up(L.w, 4) + align_up(L.h, 4));
+    if (img_off > 0x7fffffffull) {
+      *why = "pyramid frame exceeds 2 GiB";
+      return ORBX_ERR_UNSUPPORTED;
+    }
+  }
+  plan->frame_bytes = (int32_t)img_off;
+  plan->mask_words = (int32_t)mask_off;
+  // (the selection output lives in the candidate pools, at the result blocks' stride: in the row-major mode, where a
+  // level's cap is its quota, the rounded-up slot count below is the larger of the two)
+  plan->cand_total = std::max(cand_off, (out_cap + 15) & ~15);
+  // slots per frame of the result blocks: the sum of the quotas, rounded up to 16 -- a describe workgroup's 16 slots
+  // are then whole 64-byte lines of every section (fewer, full-line writes when the record goes to the host mirror)
+  plan->out_cap = (out_cap + 15) & ~15;
+  return ORBX_OK;
+}
+
+// entries of the resize-tap table of a plan (make_taps in orbx_api.cpp fills them; at least one)
+inline size_t taps_count(const OrbxPlan& plan) {
+  size_t total = 0;
+  for (int l = 1; l < plan.nlevels; l++) total += (size_t)align_up(plan.L[l].w, 4) + align_up(plan.L[l].h, 4);
+  return total ? total : 1;
+}
+
+// ---- what a context allocates for the tables of ANY frame it accepts ----------------------------------------------
+// A context is created for max_width x max_height and takes every frame from 8 x 8 up to that size; each frame size
+// gets its own tables (set_plan) in pools allocated once, from the plan of the maximum M.  Level sizes are monotone
+// in the frame size (level_size: a rounded quotient by the same scale), and so is every table whose rows and columns
+// are ceilings of a level's width / height over a constant -- all of them but the FAST table, whose tile rows are
+// BALANCED and, with the adaptive first pass's preferred heights, clamped to "at most ORBX_MAX_BANDS / as many as
+// the level above": neither is monotone in the height, so a frame a little smaller than the maximum can have more
+// tile rows than the maximum itself has under any ONE preference vector.  Its capacity is therefore an upper bound
+// that holds for every height up to the maximum's and every preference: per level, the maximum's units per tile row
+// times the most tile rows make_bandmap can give a level of that height or less -- tile rows are never shorter than
+// ORBX_MIN_TILE_H unless the level is, and never more than ORBX_MAX_BANDS in a table that make_bandmap accepts.
+struct OrbxTableCapacity {
+  size_t fast;   // FAST tile table (OrbxTileDesc entries per frame)
+  size_t frame;  // blur, pyramid and fused pyramid + blur (whole / first pass / second pass) tables, each
+  size_t small;  // fused pyramid + blur, short bands
+  size_t taps;   // resize-tap table (OrbxResizeTap entries)
+};
+inline size_t fast_tiles_upper_bound(const OrbxPlan& M, int nms_radius, bool strips) {
+  size_t cap = 0;
+  for (int l = 0; l < M.nlevels; l++) {
+    const int rows = std::min(ORBX_MAX_BANDS, (M.L[l].h + ORBX_MIN_TILE_H - 1) / ORBX_MIN_TILE_H);
+    cap += (size_t)fast_tiles_x(M.L[l].w, nms_radius, strips) * (size_t)rows;
+  }
+  return cap;
+}
+// M: build_plan of the maximum (its win8 fields still zero: the pyramid tiles of the pool are then the short ones,
+// ORBX_PYR2_TH rows -- the most).  Fails where the maximum itself has no FAST table (make_bandmap's reasons).
+inline int table_capacity(const orbx_params& p, const OrbxPlan& M, int fast_impl, int blur_impl, OrbxTableCapacity* cap,
+                          std::string* why) {
+  OrbxBandMap bm;
+  const int st = make_bandmap(M, p.nms_window / 2, &bm, why, fast_impl == 4, nullptr);
+  if (st != ORBX_OK) return st;
+  cap->fast = fast_tiles_upper_bound(M, p.nms_window / 2, fast_impl == 4);
+  const size_t t1 = blur_tiles_for_impl(blur_impl, M, nullptr);
+  const size_t t2 = build_frame_tiles(M, ORBX_PYR2_TW, ORBX_PYR2_TH, true, nullptr);
+  const size_t t3 = build_pyrblur_tiles(M, ORBX_PYRBLUR_RH, nullptr);
+  cap->frame = std::max(std::max(t1, t2), t3) + 256;  // (+ the extra bands of a split table)
+  cap->small = build_pyrblur_tiles(M, ORBX_PYRBLUR_RH_SMALL, nullptr) + 64;
+  cap->taps = taps_count(M) + 16;
+  return ORBX_OK;
+}
+
+}  // namespace orbx_geom

@@ -36,7 +36,7 @@ EXPORTS = [
     "orbx_select_top", "orbx_knn2", "orbx_match_ratio", "orbx_batch_match_consecutive", "orbx_batch_match_fetch",
     "orbx_estimate_pose", "orbx_batch_pose_consecutive", "orbx_batch_pose_fetch", "orbx_batch_pose_mask",
     "orbx_triangulate", "orbx_estimate_scale", "orbx_batch_scale_consecutive", "orbx_batch_scale_fetch",
-    "orbx_batch_points_fetch", "orbx_chain_trajectory",
+    "orbx_batch_points_fetch", "orbx_chain_trajectory", "orbx_debug_fill_pools",
 ]
 
 
@@ -309,6 +309,10 @@ class Context:
     def set_top_rows_first(self, mode=2):
         """0: one pass, 1: the pyramid top rows first whenever eligible, 2: adaptive (default)."""
         self._chk(self._lib.orbx_set_top_rows_first(self._h, int(mode)))
+
+    def debug_fill_pools(self, byte):
+        """DEBUG (tests): fill the working pools of both lanes with `byte` (orbx_debug_fill_pools)."""
+        self._chk(self._lib.orbx_debug_fill_pools(self._h, int(byte)))
 
     def lk_track(self, prev, nxt, pts, win=21, max_level=3, max_iters=30, epsilon=0.01):
         """cv::calcOpticalFlowPyrLK(prev, next, pts, ...) as called at feature_tracking.cpp:175-181.
