@@ -479,6 +479,50 @@ int orbx_batch_points_fetch(orbx_ctx* ctx, int pair, float* xyz, uint8_t* valid,
 int orbx_chain_trajectory(const double* T0, const double* R, const double* t, const double* scale, int n,
                           double* poses);
 
+/* ---- next row: sliding-window bundle adjustment ---------------------
+ * Replaces the reference's Ceres solve of one window of poses and landmarks,
+ *   ReprojectionError: angle-axis + translation, world -> camera, pinhole      src/with_bundle_adjustment.cpp:27-68
+ *   the problem: HuberLoss, pose 0 constant, SPARSE_SCHUR, 200 iterations      src/with_bundle_adjustment.cpp:612-679
+ *   write-back only on CONVERGENCE                                             src/with_bundle_adjustment.cpp:683
+ * as Levenberg-Marquardt with the Schur complement on the landmarks, one GPU workgroup per window, in binary64.
+ * Ceres is absent from the image this library was written in: every choice it leaves to its internals is fixed
+ * in DESIGN.md §9 rank 7; parity with Ceres is unpinned.
+ * Pose block: 6 doubles, angle-axis (3) then translation (3); point block: 3 doubles, world frame.  A window has
+ * 2 .. ORBX_BA_MAX_POSES poses and 1 .. 65536 landmarks (more: ORBX_ERR_UNSUPPORTED); every landmark has at least
+ * one observation and every (landmark, pose) at most one.  Observations may come in any order.  The reference's
+ * values are huber_delta = 1.0 and max_iters = 200.  ORBX_ERR_INVALID_ARG: an index out of range, a duplicate
+ * (landmark, pose), a landmark without observation, a pose count outside [2, 8], huber_delta <= 0, max_iters outside
+ * [1, 1000], a non-finite input.  On any error nothing is written. */
+#define ORBX_BA_MAX_POSES 8
+typedef enum {
+  ORBX_BA_CONVERGENCE = 0,    /* a tolerance was reached: the blocks hold the solution */
+  ORBX_BA_NO_CONVERGENCE = 1, /* max_iters iterations ran: the blocks are unchanged */
+  ORBX_BA_FAILURE = 2         /* non-finite initial cost, an observation at depth 0 at the start, or a rotation
+                                 angle beyond 1e5 rad: the blocks are unchanged */
+} orbx_ba_termination;
+typedef struct {
+  int32_t termination; /* orbx_ba_termination */
+  int32_t iterations;  /* trust-region iterations run */
+  int32_t successful_steps;
+  int32_t reserved;
+  double initial_cost; /* 1/2 sum rho(|r|^2) */
+  double final_cost;
+} orbx_ba_summary;
+/* run_bundle_adjustment's solve of one window on host arrays: K row-major double[9]; poses6: 6 n_poses doubles,
+ * points3: 3 n_points doubles, both in / out (rewritten only on convergence); observation k sees landmark
+ * obs_point[k] from pose obs_pose[k] at pixel obs_xy[2k], obs_xy[2k + 1].  src/with_bundle_adjustment.cpp:612-720 */
+int orbx_bundle_adjust(orbx_ctx* ctx, const double* K, int n_poses, double* poses6, int n_points, double* points3,
+                       int n_obs, const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
+                       double huber_delta, int max_iters, orbx_ba_summary* summary);
+/* n_windows independent windows in one launch.  Window w owns poses [pose_offset[w], pose_offset[w + 1]), points
+ * [point_offset[w], point_offset[w + 1]) and observations [obs_offset[w], obs_offset[w + 1]); each offset array has
+ * n_windows + 1 entries and starts at 0; obs_point / obs_pose index inside the window.  A window's result does not
+ * depend on the batch it is in.  summaries: n_windows entries.  src/with_bundle_adjustment.cpp:612-720 */
+int orbx_bundle_adjust_batch(orbx_ctx* ctx, const double* K, int n_windows, const int32_t* pose_offset,
+                             double* poses6, const int32_t* point_offset, double* points3, const int32_t* obs_offset,
+                             const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
+                             double huber_delta, int max_iters, orbx_ba_summary* summaries);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,9 @@ struct orbx_ctx {
   DevBuf sb_xyz, sb_valid, sb_mq, sb_mt, sb_n, sb_out, sh_in, sh_xyz, sh_valid, sh_out;
   int scale_pairs = 0, scale_cap = 0;
   hipStream_t scale_stream = nullptr;
+  // bundle adjustment (orbx_ba.hip): the staged windows (offsets, parameter blocks, CSR observations), the
+  // workgroups' workspaces and the summaries; grown on first use
+  DevBuf ba_off, ba_poses, ba_points, ba_rows, ba_opose, ba_oxy, ba_wp, ba_wo, ba_slot, ba_out;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -1116,7 +1119,9 @@ void orbx_destroy(orbx_ctx* c) {
                   &c->s_i32,   &c->s_kern,  &c->s_tiles, &c->m_q,    &c->m_t,   &c->m_idx,  &c->m_dist,  &c->m_match, &c->m_cnt,
                   &c->lk_img[0], &c->lk_img[1], &c->lk_deriv, &c->lk_io, &c->pb_pts, &c->pb_n, &c->pb_out,
                   &c->pb_mask, &c->ph_in, &c->ph_pts, &c->ph_n, &c->ph_out, &c->ph_mask, &c->sb_xyz, &c->sb_valid,
-                  &c->sb_mq, &c->sb_mt, &c->sb_n, &c->sb_out, &c->sh_in, &c->sh_xyz, &c->sh_valid, &c->sh_out};
+                  &c->sb_mq, &c->sb_mt, &c->sb_n, &c->sb_out, &c->sh_in, &c->sh_xyz, &c->sh_valid, &c->sh_out,
+                  &c->ba_off, &c->ba_poses, &c->ba_points, &c->ba_rows, &c->ba_opose, &c->ba_oxy, &c->ba_wp, &c->ba_wo,
+                  &c->ba_slot, &c->ba_out};
   if (c->lk_host) (void)hipHostFree(c->lk_host);
   for (DevBuf* b : sb)
     if (b->p) (void)hipFree(b->p);
@@ -2598,6 +2603,135 @@ int orbx_chain_trajectory(const double* T0, const double* R, const double* t, co
   std::memcpy(poses, T0, sizeof(double) * 16);
   for (int i = 0; i < n; i++) tri_chain(poses + 16 * i, R + 9 * i, t + 3 * i, scale[i], poses + 16 * (i + 1));
   return ORBX_OK;
+}
+
+}  // extern "C"
+
+// ---- bundle adjustment -----------------------------------------------
+
+static_assert(sizeof(orbx_ba_summary) == 32, "orbx_ba_summary is the kernel's BaSummary");
+
+extern "C" {
+
+int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const int32_t* pose_offset, double* poses6,
+                             const int32_t* point_offset, double* points3, const int32_t* obs_offset,
+                             const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
+                             double huber_delta, int max_iters, orbx_ba_summary* summaries) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!K || !finite_all(K, 9) || n_windows < 0 || !(huber_delta > 0.0) || !std::isfinite(huber_delta) ||
+      max_iters < 1 || max_iters > 1000)
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  if (n_windows == 0) return ORBX_OK;
+  if (!pose_offset || !poses6 || !point_offset || !points3 || !obs_offset || !obs_point || !obs_pose || !obs_xy ||
+      !summaries)
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  if (pose_offset[0] != 0 || point_offset[0] != 0 || obs_offset[0] != 0)
+    return fail(c, ORBX_ERR_INVALID_ARG, "offset arrays start at 0");
+  int cap = 1, ocap = 1;
+  for (int w = 0; w < n_windows; w++) {
+    const long long W = (long long)pose_offset[w + 1] - pose_offset[w], N = (long long)point_offset[w + 1] - point_offset[w],
+                    M = (long long)obs_offset[w + 1] - obs_offset[w];
+    if (W < 2 || W > ORBX_BA_MAX_POSES) return fail(c, ORBX_ERR_INVALID_ARG, "a window has 2 .. 8 poses");
+    if (N < 1 || M < N || M > N * W)
+      return fail(c, ORBX_ERR_INVALID_ARG, "every landmark has 1 .. n_poses observations");
+    if (N > ORBX_BA_MAX_POINTS) return fail(c, ORBX_ERR_UNSUPPORTED, "more landmarks in a window than 65536");
+    cap = std::max(cap, (int)N);
+    ocap = std::max(ocap, (int)M);
+  }
+  const size_t tp = (size_t)pose_offset[n_windows], tn = (size_t)point_offset[n_windows], tm = (size_t)obs_offset[n_windows];
+  if (tn + (size_t)n_windows > 0x7fffffffu || tm > 0x7fffffffu)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "more landmarks or observations in a batch than 32-bit offsets hold");
+  if (!finite_all(poses6, (int)(6 * tp))) return fail(c, ORBX_ERR_INVALID_ARG, "a pose is not finite");
+  for (size_t i = 0; i < 3 * tn; i++)
+    if (!std::isfinite(points3[i])) return fail(c, ORBX_ERR_INVALID_ARG, "a point is not finite");
+  for (size_t i = 0; i < 2 * tm; i++)
+    if (!std::isfinite(obs_xy[i])) return fail(c, ORBX_ERR_INVALID_ARG, "an observation is not finite");
+  // CSR by (landmark, pose), per window (src/with_bundle_adjustment.cpp:651-666 adds the residual blocks landmark by
+  // landmark)
+  std::vector<int32_t> rows(tn + (size_t)n_windows), order;
+  std::vector<uint8_t> opose(tm);
+  std::vector<double> oxy(2 * tm);
+  for (int w = 0; w < n_windows; w++) {
+    const int W = pose_offset[w + 1] - pose_offset[w], N = point_offset[w + 1] - point_offset[w];
+    const int M = obs_offset[w + 1] - obs_offset[w];
+    const int32_t* op = obs_point + obs_offset[w];
+    const int32_t* oq = obs_pose + obs_offset[w];
+    for (int k = 0; k < M; k++)
+      if (op[k] < 0 || op[k] >= N || oq[k] < 0 || oq[k] >= W)
+        return fail(c, ORBX_ERR_INVALID_ARG, "an observation's landmark or pose index is out of range");
+    // every (landmark, pose) occurs at most once, so placing observation k at key landmark * W + pose and reading
+    // the keys in ascending order IS the stable sort by (landmark, pose)
+    order.assign((size_t)N * W, -1);
+    for (int k = 0; k < M; k++) {
+      int32_t& at = order[(size_t)op[k] * W + oq[k]];
+      if (at >= 0) return fail(c, ORBX_ERR_INVALID_ARG, "a landmark is observed twice by one pose");
+      at = k;
+    }
+    int32_t* row = rows.data() + point_offset[w] + w;
+    std::fill(row, row + N + 1, 0);
+    size_t dst = (size_t)obs_offset[w];
+    for (size_t key = 0; key < order.size(); key++) {
+      const int o = order[key];
+      if (o < 0) continue;
+      row[op[o] + 1]++;
+      opose[dst] = (uint8_t)oq[o];
+      oxy[2 * dst] = obs_xy[2 * ((size_t)obs_offset[w] + o)];
+      oxy[2 * dst + 1] = obs_xy[2 * ((size_t)obs_offset[w] + o) + 1];
+      dst++;
+    }
+    for (int j = 0; j < N; j++) {
+      if (row[j + 1] == 0) return fail(c, ORBX_ERR_INVALID_ARG, "a landmark has no observation");
+      row[j + 1] += row[j];
+    }
+  }
+  // workgroups: as many as windows, bounded by ORBX_BA_MAX_GROUPS and by the workspace budget
+  const size_t per_group = sizeof(double) * ((size_t)ORBX_BA_WS_POINT * cap + (size_t)ORBX_BA_WS_OBS * ocap) + 8 * (size_t)cap;
+  int groups = std::min(n_windows, ORBX_BA_MAX_GROUPS);
+  groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)groups, ORBX_BA_WS_BUDGET / per_group));
+  const size_t noff = (size_t)n_windows + 1;
+  int st;
+  if ((st = ensure(c, c->ba_off, sizeof(int32_t) * 3 * noff)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ba_poses, sizeof(double) * 6 * tp)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ba_points, sizeof(double) * 3 * tn)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ba_rows, sizeof(int32_t) * rows.size())) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ba_opose, tm)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ba_oxy, sizeof(double) * 2 * tm)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ba_wp, sizeof(double) * ORBX_BA_WS_POINT * (size_t)cap * groups)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ba_wo, sizeof(double) * ORBX_BA_WS_OBS * (size_t)ocap * groups)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ba_slot, 8 * (size_t)cap * groups)) != ORBX_OK) return st;
+  if ((st = ensure(c, c->ba_out, sizeof(orbx_ba_summary) * (size_t)n_windows)) != ORBX_OK) return st;
+  hipStream_t s = c->stream;
+  int32_t* d_off = (int32_t*)c->ba_off.p;
+  HIPCHK(c, hipMemcpyAsync(d_off, pose_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d_off + noff, point_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d_off + 2 * noff, obs_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba_poses.p, poses6, sizeof(double) * 6 * tp, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba_points.p, points3, sizeof(double) * 3 * tn, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba_rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba_opose.p, opose.data(), tm, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba_oxy.p, oxy.data(), sizeof(double) * 2 * tm, hipMemcpyHostToDevice, s));
+  const double K4[4] = {K[0], K[4], K[2], K[5]};
+  HIPCHK(c, orbx_launch_ba(s, n_windows, groups, max_iters, K4, huber_delta, d_off, d_off + noff, d_off + 2 * noff,
+                           (double*)c->ba_poses.p, (double*)c->ba_points.p, (const int32_t*)c->ba_rows.p,
+                           (const uint8_t*)c->ba_opose.p, (const double*)c->ba_oxy.p, cap, ocap, (double*)c->ba_wp.p,
+                           (double*)c->ba_wo.p, (unsigned long long*)c->ba_slot.p, c->ba_out.p));
+  // the staged vectors are pageable: their copies above have left the host before the calls returned
+  HIPCHK(c, hipMemcpyAsync(poses6, c->ba_poses.p, sizeof(double) * 6 * tp, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(points3, c->ba_points.p, sizeof(double) * 3 * tn, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(summaries, c->ba_out.p, sizeof(orbx_ba_summary) * (size_t)n_windows, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return ORBX_OK;
+}
+
+int orbx_bundle_adjust(orbx_ctx* c, const double* K, int n_poses, double* poses6, int n_points, double* points3,
+                       int n_obs, const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
+                       double huber_delta, int max_iters, orbx_ba_summary* summary) {
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (n_poses < 0 || n_points < 0 || n_obs < 0) return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  const int32_t po[2] = {0, n_poses}, pt[2] = {0, n_points}, ob[2] = {0, n_obs};
+  return orbx_bundle_adjust_batch(c, K, 1, po, poses6, pt, points3, ob, obs_point, obs_pose, obs_xy, huber_delta,
+                                  max_iters, summary);
 }
 
 }  // extern "C"

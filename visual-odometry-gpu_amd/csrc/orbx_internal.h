@@ -168,3 +168,23 @@ hipError_t orbx_launch_scale_join(hipStream_t s, int npairs, int cap, const int3
 hipError_t orbx_launch_scale_aligned(hipStream_t s, int n_prev, int n_cur, const float* d_prev,
                                      const uint8_t* d_prev_valid, const float* d_cur, const uint8_t* d_cur_valid,
                                      OrbxScaleOut* d_out);
+
+// ---- bundle adjustment (orbx_ba.hip): one workgroup per window, each owning a workspace ----------------------
+// workspace doubles per landmark (accepted and candidate point, V, gradient, Jacobi scale, inverse block, scaled
+// gradient, damping) and per observation (the 6x3 coupling block W)
+#define ORBX_BA_WS_POINT 30
+#define ORBX_BA_WS_OBS 18
+// landmarks of one window: bounded so that 32-bit indices into a workspace row never overflow and a window of
+// 5 poses x 4096 landmarks fits with room to spare
+#define ORBX_BA_MAX_POINTS 65536
+// workgroups per launch: each solves windows group, group + groups, ... (bounds the workspace); fewer when their
+// workspaces together would exceed the budget
+#define ORBX_BA_MAX_GROUPS 512
+#define ORBX_BA_WS_BUDGET ((size_t)2 << 30)
+// d_rows: per window, (landmarks + 1) offsets into the window's observations, window w's first at
+// d_pt_off[w] + w; d_out: one BaSummary (= orbx_ba_summary) per window; K4 = fx, fy, cx, cy
+hipError_t orbx_launch_ba(hipStream_t s, int n_windows, int groups, int max_iters, const double* K4, double delta,
+                          const int32_t* d_pose_off, const int32_t* d_pt_off, const int32_t* d_obs_off,
+                          double* d_poses, double* d_points, const int32_t* d_rows, const uint8_t* d_obs_pose,
+                          const double* d_obs_xy, int cap, int ocap, double* d_ws_pt, double* d_ws_obs,
+                          unsigned long long* d_ws_slot, void* d_out);

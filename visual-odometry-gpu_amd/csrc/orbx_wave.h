@@ -26,6 +26,24 @@ __device__ __forceinline__ int wave_sum(int v) {
          __builtin_amdgcn_readlane(v, 48);
 }
 
+// wave-wide binary64 sum, the same bits in every lane: an xor butterfly over lane distances 1, 2, 4, 8, 16, 32, so
+// lane l adds its partner's value at every step and the combination order is a fixed function of the lane index
+// (IEEE addition is commutative: both lanes of a pair hold the same sum).  Every lane of the wave must be active.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) v = v + __shfl_xor(v, d, 64);
+  return v;
+}
+// the same butterfly with `a > b ? a : b`
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const double o = __shfl_xor(v, d, 64);
+    v = v > o ? v : o;
+  }
+  return v;
+}
+
 // wave-wide inclusive prefix sum (lane i gets v_0 + ... + v_i) with DPP only
 // (GCN cross-lane scan: row_shr 1/2/3, row_shr 4 and 8 with bank masks, then
 // row_bcast 15 / 31 across the 16-lane rows)

@@ -721,4 +721,212 @@ inline void chain_pose(std::array<double, 16>& cur_pose, const double R[9], cons
   std::memcpy(cur_pose.data(), poses + 16, sizeof(double) * 16);
 }
 
+// ---- sliding-window bundle adjustment (next row) --------------------
+// The host glue of src/with_bundle_adjustment.cpp around the solve (orbx_bundle_adjust).  Poses of a window are
+// camera -> world, row-major 4x4, as the reference's pose_window.
+struct Point2d {  // cv::Point2d
+  double x = 0.0, y = 0.0;
+};
+struct Point3d {  // cv::Point3d
+  double x = 0.0, y = 0.0, z = 0.0;
+};
+struct Landmark {  // src/with_bundle_adjustment.cpp:20-25
+  int id = 0;
+  Point3d pos;
+  std::vector<std::pair<int, Point2d>> observations;  // (frame index in the window, pixel)
+};
+using Track = std::vector<std::pair<int, Point2f>>;
+using Pose4x4 = std::array<double, 16>;
+
+namespace detail {
+// world -> camera [R | t] of a camera -> world pose (the reference's pose.inv(), in closed form)
+inline void invert_rigid(const Pose4x4& T, double R[9], double t[3]) {
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) R[i * 3 + j] = T[(size_t)(j * 4 + i)];
+  for (int i = 0; i < 3; i++) t[i] = -(R[i * 3] * T[3] + R[i * 3 + 1] * T[7] + R[i * 3 + 2] * T[11]);
+}
+inline Pose4x4 compose_inverse(const double R[9], const double t[3]) {  // ([R | t])^-1 as a 4x4
+  Pose4x4 T{{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}};
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) T[(size_t)(i * 4 + j)] = R[j * 3 + i];
+    T[(size_t)(i * 4 + 3)] = -(R[0 * 3 + i] * t[0] + R[1 * 3 + i] * t[1] + R[2 * 3 + i] * t[2]);
+  }
+  return T;
+}
+// cv::Rodrigues, vector -> matrix
+inline void rodrigues(const double w[3], double R[9]) {
+  const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  double k[3] = {w[0], w[1], w[2]}, s = 1.0, c1 = 0.5;  // th -> 0: R = I + [w]x + [w]x^2 / 2
+  if (th > 1e-12) {
+    for (double& v : k) v /= th;
+    s = std::sin(th), c1 = 1.0 - std::cos(th);
+  }
+  const double K2[9] = {-(k[1] * k[1] + k[2] * k[2]), k[0] * k[1], k[0] * k[2], k[0] * k[1], -(k[0] * k[0] + k[2] * k[2]),
+                        k[1] * k[2], k[0] * k[2], k[1] * k[2], -(k[0] * k[0] + k[1] * k[1])};
+  const double K1[9] = {0, -k[2], k[1], k[2], 0, -k[0], -k[1], k[0], 0};
+  for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + s * K1[i] + c1 * K2[i];
+}
+// cv::Rodrigues, matrix -> vector, angle in [0, pi] (through the unit quaternion: stable near pi)
+inline void rodrigues_inv(const double R[9], double w[3]) {
+  double q[4] = {1.0 + R[0] + R[4] + R[8], R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+  if (q[0] < 1e-3) {
+    int i = 0;
+    if (R[4] > R[0]) i = 1;
+    if (R[8] > R[i * 4]) i = 2;
+    const int j = (i + 1) % 3, k = (i + 2) % 3;
+    q[1 + i] = 1.0 + R[i * 4] - R[j * 4] - R[k * 4];
+    q[1 + j] = R[i * 3 + j] + R[j * 3 + i];
+    q[1 + k] = R[i * 3 + k] + R[k * 3 + i];
+    q[0] = R[k * 3 + j] - R[j * 3 + k];
+  }
+  const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const double sg = q[0] < 0 ? -1.0 : 1.0;
+  for (double& v : q) v = sg * v / n;
+  const double s = std::sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const double f = s > 0 ? 2.0 * std::atan2(s, q[0]) / s : 0.0;
+  for (int i = 0; i < 3; i++) w[i] = f * q[1 + i];
+}
+}  // namespace detail
+
+// trackPointsAcrossWindow (src/with_bundle_adjustment.cpp:464-499): the points of frame 0 propagated frame by
+// frame; a track ends with the first frame LK loses it in.  One LK call per consecutive image pair on all live
+// points replaces the reference's one call per point and pair (LK treats every point on its own).
+inline std::vector<Track> track_points_across_window(LKTracker& lk, const std::vector<Image>& imgs_window,
+                                                     const std::vector<Point2f>& keypoints0) {
+  std::vector<Track> tracks(keypoints0.size());
+  std::vector<size_t> live(keypoints0.size());
+  std::vector<Point2f> prev = keypoints0, next;
+  for (size_t i = 0; i < keypoints0.size(); i++) {
+    tracks[i].emplace_back(0, keypoints0[i]);
+    live[i] = i;
+  }
+  std::vector<uint8_t> status;
+  std::vector<float> err;
+  for (size_t fi = 1; fi < imgs_window.size() && !live.empty(); fi++) {
+    // after the first pair the tracker still holds the pyramid of imgs_window[fi - 1]
+    lk.calcOpticalFlowPyrLK(fi == 1 ? &imgs_window[0] : nullptr, imgs_window[fi], prev, next, status, err, Size(21, 21),
+                            3, TermCriteria(30, 0.01));
+    std::vector<size_t> still;
+    std::vector<Point2f> kept;
+    for (size_t k = 0; k < live.size(); k++)
+      if (status[k]) {
+        tracks[live[k]].emplace_back((int)fi, next[k]);
+        still.push_back(live[k]);
+        kept.push_back(next[k]);
+      }
+    live.swap(still);
+    prev.swap(kept);
+  }
+  return tracks;
+}
+
+// buildLandmarksFromFirstTwoFramesAndTracks (src/with_bundle_adjustment.cpp:502-575): the baseline gate
+// 0.1 .. 100 on |t0 - t1| of the world -> camera translations, triangulation of every track seen in frame 1 from
+// frames 0 / 1, the reference's depth check `X.z > 0` (on the world-frame point, as there), the track's
+// observations attached.  The triangulation runs in camera 0's frame (orbx_triangulate with the relative pose)
+// and the point is then moved to the world frame; the reference solves the DLT in world coordinates.  The two
+// agree up to rounding and the conditioning of the 4x4 system; parity is unpinned either way.
+inline bool build_landmarks(const std::vector<Pose4x4>& pose_window, const double K[9], const std::vector<Track>& tracks,
+                            std::vector<Landmark>& landmarks) {
+  if (pose_window.size() < 2) return false;
+  double R0[9], t0[3], R1[9], t1[3];
+  detail::invert_rigid(pose_window[0], R0, t0);
+  detail::invert_rigid(pose_window[1], R1, t1);
+  const double baseline = std::sqrt((t0[0] - t1[0]) * (t0[0] - t1[0]) + (t0[1] - t1[1]) * (t0[1] - t1[1]) +
+                                    (t0[2] - t1[2]) * (t0[2] - t1[2]));
+  if (baseline < 0.1 || baseline > 100) return false;
+  double Rr[9], tr[3];  // camera 0 -> camera 1
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) Rr[i * 3 + j] = R1[i * 3] * R0[j * 3] + R1[i * 3 + 1] * R0[j * 3 + 1] + R1[i * 3 + 2] * R0[j * 3 + 2];
+  for (int i = 0; i < 3; i++) tr[i] = t1[i] - (Rr[i * 3] * t0[0] + Rr[i * 3 + 1] * t0[1] + Rr[i * 3 + 2] * t0[2]);
+  std::vector<float> p0, p1;
+  std::vector<size_t> original;
+  for (size_t i = 0; i < tracks.size(); i++)
+    for (const auto& obs : tracks[i])
+      if (obs.first == 1 && !tracks[i].empty()) {
+        p0.push_back(tracks[i][0].second.x), p0.push_back(tracks[i][0].second.y);
+        p1.push_back(obs.second.x), p1.push_back(obs.second.y);
+        original.push_back(i);
+        break;
+      }
+  const int n = (int)original.size();
+  std::vector<float> xyz((size_t)3 * n);
+  std::vector<uint8_t> valid((size_t)n);
+  if (n > 0) {
+    orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+    detail::check(c, orbx_triangulate(c, p0.data(), p1.data(), n, K, Rr, tr, xyz.data(), valid.data()), "orbx_triangulate");
+  }
+  landmarks.reserve(landmarks.size() + (size_t)n);
+  for (int j = 0; j < n; j++) {
+    if (!valid[(size_t)j]) continue;
+    const double d[3] = {xyz[3 * (size_t)j] - t0[0], xyz[3 * (size_t)j + 1] - t0[1], xyz[3 * (size_t)j + 2] - t0[2]};
+    Landmark lm;
+    lm.pos.x = R0[0] * d[0] + R0[3] * d[1] + R0[6] * d[2];  // X = R0^T (x - t0)
+    lm.pos.y = R0[1] * d[0] + R0[4] * d[1] + R0[7] * d[2];
+    lm.pos.z = R0[2] * d[0] + R0[5] * d[1] + R0[8] * d[2];
+    if (lm.pos.z <= 0) continue;  // "Simple depth check", :559
+    lm.id = j;
+    for (const auto& obs : tracks[original[(size_t)j]])
+      lm.observations.emplace_back(obs.first, Point2d{(double)obs.second.x, (double)obs.second.y});
+    landmarks.push_back(std::move(lm));
+  }
+  return true;
+}
+
+// The solve and write-back of run_bundle_adjustment (src/with_bundle_adjustment.cpp:612-720): world -> camera
+// angle-axis blocks from the camera -> world poses, orbx_bundle_adjust (HuberLoss(1.0), 200 iterations, pose 0
+// constant), and -- only on convergence -- each pose written back iff it moved by less than 0.5 rad and 50 units
+// (:708-718).  updated[i]: pose i was written back.  Returns false when there is nothing to solve.
+inline bool run_bundle_adjustment(std::vector<Pose4x4>& pose_window, const double K[9],
+                                  const std::vector<Landmark>& landmarks, orbx_ba_summary* summary = nullptr,
+                                  std::vector<uint8_t>* updated = nullptr, double huber_delta = 1.0,
+                                  int max_iters = 200) {
+  const int W = (int)pose_window.size();
+  if (updated) updated->assign((size_t)W, 0);
+  if (landmarks.empty() || W < 2) return false;
+  std::vector<double> poses((size_t)6 * W), points, xy;
+  std::vector<int32_t> op, oq;
+  for (int i = 0; i < W; i++) {
+    double R[9], t[3];
+    detail::invert_rigid(pose_window[(size_t)i], R, t);
+    detail::rodrigues_inv(R, &poses[(size_t)6 * i]);
+    for (int k = 0; k < 3; k++) poses[(size_t)6 * i + 3 + k] = t[k];
+  }
+  for (const Landmark& lm : landmarks) {
+    int used = 0;
+    for (const auto& obs : lm.observations) {
+      if (obs.first < 0 || obs.first >= W) continue;  // :655
+      op.push_back((int32_t)(points.size() / 3)), oq.push_back(obs.first);
+      xy.push_back(obs.second.x), xy.push_back(obs.second.y);
+      used++;
+    }
+    if (used) points.push_back(lm.pos.x), points.push_back(lm.pos.y), points.push_back(lm.pos.z);
+  }
+  if (points.empty()) return false;
+  const std::vector<double> old = poses;
+  orbx_ba_summary s{};
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c, orbx_bundle_adjust(c, K, W, poses.data(), (int)(points.size() / 3), points.data(), (int)op.size(),
+                                      op.data(), oq.data(), xy.data(), huber_delta, max_iters, &s),
+                "orbx_bundle_adjust");
+  if (summary) *summary = s;
+  if (s.termination != ORBX_BA_CONVERGENCE) return true;  // :683
+  for (int i = 0; i < W; i++) {
+    double R[9], Ro[9], Rd[9], wd[3];
+    detail::rodrigues(&poses[(size_t)6 * i], R);
+    detail::rodrigues(&old[(size_t)6 * i], Ro);
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) Rd[a * 3 + b] = R[a * 3] * Ro[b * 3] + R[a * 3 + 1] * Ro[b * 3 + 1] + R[a * 3 + 2] * Ro[b * 3 + 2];
+    detail::rodrigues_inv(Rd, wd);
+    const double angle = std::sqrt(wd[0] * wd[0] + wd[1] * wd[1] + wd[2] * wd[2]);
+    double tn = 0.0;
+    for (int k = 0; k < 3; k++) tn += (poses[(size_t)6 * i + 3 + k] - old[(size_t)6 * i + 3 + k]) * (poses[(size_t)6 * i + 3 + k] - old[(size_t)6 * i + 3 + k]);
+    if (angle < 0.5 && std::sqrt(tn) < 50.0) {  // MAX_ROT_DIFF, MAX_TRANS_DIFF
+      pose_window[(size_t)i] = detail::compose_inverse(R, &poses[(size_t)6 * i + 3]);
+      if (updated) (*updated)[(size_t)i] = 1;
+    }
+  }
+  return true;
+}
+
 }  // namespace orbx

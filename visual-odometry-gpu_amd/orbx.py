@@ -37,6 +37,7 @@ EXPORTS = [
     "orbx_estimate_pose", "orbx_batch_pose_consecutive", "orbx_batch_pose_fetch", "orbx_batch_pose_mask",
     "orbx_triangulate", "orbx_estimate_scale", "orbx_batch_scale_consecutive", "orbx_batch_scale_fetch",
     "orbx_batch_points_fetch", "orbx_chain_trajectory", "orbx_debug_fill_pools",
+    "orbx_bundle_adjust", "orbx_bundle_adjust_batch",
 ]
 
 
@@ -658,6 +659,72 @@ def _scale_methods():
 
 
 _scale_methods()
+
+
+BA_CONVERGENCE, BA_NO_CONVERGENCE, BA_FAILURE = range(3)
+BA_MAX_POSES = 8
+
+
+class BaSummary(C.Structure):
+    _fields_ = [("termination", C.c_int32), ("iterations", C.c_int32), ("successful_steps", C.c_int32),
+                ("reserved", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("termination", "iterations", "successful_steps", "initial_cost",
+                                              "final_cost")}
+
+
+def _ba_methods():
+    """Sliding-window bundle adjustment: the reference's Ceres solve (include/orbx.h)."""
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+
+    def _d(a, shape):
+        a = np.array(np.asarray(a, np.float64).reshape(shape), order="C")  # a copy: the entry writes in place
+        return a, a.ctypes.data_as(DP)
+
+    def _i(a):
+        a = np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
+        return a, a.ctypes.data_as(IP)
+
+    def bundle_adjust(self, K, poses, points, obs_point, obs_pose, obs_xy, huber_delta=1.0, max_iters=200):
+        """One window: (poses (W, 6), points (N, 3), summary dict).  poses: angle-axis + translation, world ->
+        camera; pose 0 is constant.  The outputs equal the inputs unless the summary says convergence."""
+        (K, kp), (poses, pp), (points, xp) = _d(K, (3, 3)), _d(poses, (-1, 6)), _d(points, (-1, 3))
+        (op, opp), (oq, oqp), (xy, xyp) = _i(obs_point), _i(obs_pose), _d(obs_xy, (-1, 2))
+        if not len(op) == len(oq) == len(xy):
+            raise ValueError("obs_point, obs_pose and obs_xy differ in length")
+        out = BaSummary()
+        f = self._lib.orbx_bundle_adjust
+        f.argtypes = [C.c_void_p, DP, C.c_int, DP, C.c_int, DP, C.c_int, IP, IP, DP, C.c_double, C.c_int,
+                      C.POINTER(BaSummary)]
+        self._chk(f(self._h, kp, len(poses), pp, len(points), xp, len(op), opp, oqp, xyp, huber_delta, max_iters,
+                    C.byref(out)))
+        return poses, points, out.as_dict()
+
+    def bundle_adjust_batch(self, K, windows, huber_delta=1.0, max_iters=200):
+        """Many independent windows in one launch.  windows: a sequence of (poses, points, obs_point, obs_pose,
+        obs_xy) with window-local indices; returns a list of (poses, points, summary dict)."""
+        n = len(windows)
+        cat = lambda k, dt, sh: np.concatenate([np.asarray(w[k], dt).reshape(sh) for w in windows]) if n else np.zeros(sh, dt)
+        off = lambda k, sh: np.concatenate([[0], np.cumsum([len(np.asarray(w[k]).reshape(sh)) for w in windows])]).astype(np.int32)
+        (K, kp) = _d(K, (3, 3))
+        (poses, pp), (points, xp), (xy, xyp) = _d(cat(0, np.float64, (-1, 6)), (-1, 6)), _d(cat(1, np.float64, (-1, 3)), (-1, 3)), _d(cat(4, np.float64, (-1, 2)), (-1, 2))
+        (op, opp), (oq, oqp) = _i(cat(2, np.int32, (-1,))), _i(cat(3, np.int32, (-1,)))
+        (po, pop), (xo, xop), (oo, oop) = _i(off(0, (-1, 6))), _i(off(1, (-1, 3))), _i(off(2, (-1,)))
+        if not len(op) == len(oq) == len(xy):
+            raise ValueError("obs_point, obs_pose and obs_xy differ in length")
+        out = (BaSummary * max(n, 1))()
+        f = self._lib.orbx_bundle_adjust_batch
+        f.argtypes = [C.c_void_p, DP, C.c_int, IP, DP, IP, DP, IP, IP, IP, DP, C.c_double, C.c_int,
+                      C.POINTER(BaSummary)]
+        self._chk(f(self._h, kp, n, pop, pp, xop, xp, oop, opp, oqp, xyp, huber_delta, max_iters, out))
+        return [(poses[po[w]:po[w + 1]], points[xo[w]:xo[w + 1]], out[w].as_dict()) for w in range(n)]
+
+    for f in (bundle_adjust, bundle_adjust_batch):
+        setattr(Context, f.__name__, f)
+
+
+_ba_methods()
 
 
 def chain_trajectory(T0, R, t, scale):
