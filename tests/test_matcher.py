@@ -38,7 +38,11 @@ def rand_desc(seed, n, near=None, flips=20):
     return d
 
 
-@pytest.mark.parametrize("nq,nt", [(0, 5), (5, 0), (3, 1), (1, 2), (100, 257), (300, 256), (513, 1000)])
+# the sizes the VO chain really runs at (3000 and 4000 features per frame), and one query against a full train set
+PRODUCTION_SIZES = [(2996, 2996), (3000, 4096), (4097, 4000), (257, 3000), (1, 3000)]
+
+
+@pytest.mark.parametrize("nq,nt", [(0, 5), (5, 0), (3, 1), (1, 2), (100, 257), (300, 256), (513, 1000)] + PRODUCTION_SIZES)
 def test_oracle_knn2_vs_numpy(nq, nt):
     t = rand_desc(nt, nt)
     q = rand_desc(1000 + nq, nq, near=t)
@@ -62,7 +66,8 @@ def test_oracle_ratio_rule():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("nq,nt", [(0, 5), (5, 0), (3, 1), (1, 2), (100, 257), (300, 256), (513, 1000), (1000, 995)])
+@pytest.mark.parametrize("nq,nt", [(0, 5), (5, 0), (3, 1), (1, 2), (100, 257), (300, 256), (513, 1000), (1000, 995)]
+                         + PRODUCTION_SIZES)
 def test_gpu_knn2_and_ratio(pkg, nq, nt):
     t = rand_desc(nt, nt)
     q = rand_desc(1000 + nq, nq, near=t)
@@ -76,6 +81,55 @@ def test_gpu_knn2_and_ratio(pkg, nq, nt):
             got = c.match_ratio(q, t, ratio)
             ref = O.match_ratio(q, t, ratio)
             for a, b in zip(got, ref):
+                assert np.array_equal(a, b)
+
+
+def tie_heavy(nq, nt, seed=40):
+    """both sets drawn with replacement from 40 distinct descriptors: nearly every query has several train
+    descriptors at its smallest distance (0) and several at the second smallest"""
+    rng = np.random.default_rng(seed)
+    pool = rng.integers(0, 256, (40, 32), dtype=np.uint8)
+    return pool[rng.integers(0, 40, nq)], pool[rng.integers(0, 40, nt)]
+
+
+def check_ties(knn2, match_ratio):
+    for nq, nt in ((300, 1000), (1000, 257), (2996, 2996)):
+        q, t = tie_heavy(nq, nt)
+        idx, dist = knn2(q, t)
+        ridx, rdist = np_knn2(q, t)
+        assert np.array_equal(idx, ridx) and np.array_equal(dist, rdist)
+        # ties on the first AND the second neighbour: the two lowest train indices of the query's own descriptor
+        both = (dist[:, 0] == 0) & (dist[:, 1] == 0)
+        assert both.mean() > 0.9
+        for i in np.nonzero(both)[0][:200]:
+            same = np.nonzero((t == q[i]).all(1))[0]
+            assert tuple(idx[i]) == (same[0], same[1])
+        for ratio in (0.8, 1.0):
+            qi, ti, d1 = match_ratio(q, t, ratio)
+            keep = dist[:, 0] < ratio * dist[:, 1]  # (0 < 0: a query whose two neighbours are exact copies is no match)
+            assert np.array_equal(qi, np.nonzero(keep)[0]) and np.array_equal(ti, idx[keep, 0])
+            assert np.array_equal(d1, dist[keep, 0]) and not keep[both].any()
+    # all descriptors identical: d1 = d2 = 0 everywhere, neighbours 0 and 1, no match at 0.8 nor at 1.0
+    for nq, nt in ((70, 300), (257, 2), (1, 3000)):
+        one = rand_desc(9, 1)
+        q, t = np.repeat(one, nq, 0), np.repeat(one, nt, 0)
+        idx, dist = knn2(q, t)
+        assert np.array_equal(idx, np.tile(np.array([0, 1], np.int32), (nq, 1))) and not dist.any()
+        for ratio in (0.8, 1.0):
+            assert all(len(a) == 0 for a in match_ratio(q, t, ratio))
+
+
+def test_oracle_ties_and_identical_descriptors():
+    check_ties(O.knn2, O.match_ratio)
+
+
+@pytest.mark.gpu
+def test_gpu_ties_and_identical_descriptors(pkg):
+    with pkg.Context(pkg.default_params("gpu", max_width=64, max_height=64)) as c:
+        check_ties(c.knn2, c.match_ratio)
+        for nq, nt in ((300, 1000), (2996, 2996)):
+            q, t = tie_heavy(nq, nt)
+            for a, b in zip(c.knn2(q, t), O.knn2(q, t)):
                 assert np.array_equal(a, b)
 
 
