@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -63,6 +64,67 @@ OutLayout make_out_layout(int n, int cap) {
   return o;
 }
 
+// One block of the ring of result blocks (orbx_ctx::blocks): the device allocation, its pinned host mirror and
+// what the batch that last wrote it left there.
+struct Block {
+  uint8_t* d = nullptr;
+  uint8_t* h = nullptr;      // pinned mirror
+  uint8_t* h_dev = nullptr;  // the device-visible address of the pinned mirror
+  OutLayout layout{};
+  int n = 0;                  // frames in the block (0: never written)
+  int cap = 1;                // slots per frame the block was written with
+  bool copy_pending = false;  // an asynchronous D2H of the block has been enqueued (ev_copied)
+  bool copy_compact = false;  // ... of its compact prefix only (orbx_batch_prefetch_compact)
+  bool host_written = false;  // orbx_set_host_results: the describe kernel wrote the compact record to the mirror
+  hipEvent_t ev_done = nullptr, ev_copied = nullptr;
+  hipStream_t stream = nullptr;  // the stream of the batch that last wrote the block
+};
+
+// One lane of the pipelined mode: a set of working pools (pyramids, mask, statistics, candidates; sized for
+// max_batch frames of max_width x max_height), the stream its batches run on, and the event / stream of the
+// pools' last user.
+struct Lane {
+  uint8_t *d_pyr = nullptr, *d_pyr_blur = nullptr;
+  unsigned long long *d_mask = nullptr, *d_row_stat = nullptr;
+  orbx_keypoint* d_cand = nullptr;
+  int32_t *d_cand_count = nullptr, *d_cand_total = nullptr;
+  float* d_resp = nullptr;
+  uint32_t* d_lcand = nullptr;  // spread selection: packed candidates, their responses, counts
+  float* d_lresp = nullptr;
+  int32_t* d_lcount = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_pool = nullptr;
+  hipStream_t pool_stream = nullptr;
+};
+
+// a per-workgroup tile descriptor table (see OrbxTileDesc) of the current plan, in a pool sized for the largest frame
+struct TileTable {
+  OrbxTileDesc* d = nullptr;
+  int count = 0;
+  size_t capacity = 0;
+};
+enum {
+  T_FAST,  // one frame, band-major
+  T_BLUR,
+  T_PYR2,
+  T_PYRBLUR,  // fused pyramid + blur strips
+  // the same strips cut into short row bands: few frames per call (the reference's one-frame call shape)
+  // fill the chip only with many short waves, where a large batch wants few tall ones
+  T_PYRBLUR_SMALL,
+  // top-rows-first pipeline: the strips of the first pass and of the second one
+  T_PYRBLUR_TOP,
+  T_PYRBLUR_REST,
+  kTileTables
+};
+
+// the events of one timed batched call
+// (slots ORBX_NUM_STAGE_TIMES + 1, + 2: the boundaries inside the top-rows-first pipeline)
+struct TimingSet {
+  hipEvent_t ev[ORBX_NUM_STAGE_TIMES + 3] = {};
+  int mode = 0;
+  bool split = false;  // the call ran the top-rows-first pipeline
+};
+
 }  // namespace
 
 // what a captured launch sequence depends on (run_batch)
@@ -87,99 +149,43 @@ struct orbx_ctx {
   OrbxPlan plan_max{};
   OrbxTileMap tm_blur{};  // 5x5 /273 variant (LDS tile kernel)
   OrbxBandMap bm_fast{};
-  unsigned long long* d_row_stat = nullptr;
-  // per-workgroup tile descriptor tables (see OrbxTileDesc)
-  OrbxTileDesc* d_tiles_fast = nullptr;  // one frame, band-major
-  size_t tiles_fast_capacity = 0;
-  int fast_tiles_count = 0;
-  OrbxTileDesc* d_tiles_blur = nullptr;
-  OrbxTileDesc* d_tiles_pyr2 = nullptr;
-  OrbxTileDesc* d_tiles_pyrblur = nullptr;  // fused pyramid + blur strips
-  int pyrblur_tiles_count = 0;
-  // the same strips cut into short row bands: few frames per call (the reference's one-frame call shape)
-  // fill the chip only with many short waves, where a large batch wants few tall ones
-  OrbxTileDesc* d_tiles_pyrblur_small = nullptr;
-  int pyrblur_small_count = 0;
-  // top-rows-first pipeline: the strips of the first pass and of the second one
-  OrbxTileDesc* d_tiles_pyrblur_top = nullptr;
-  OrbxTileDesc* d_tiles_pyrblur_rest = nullptr;
-  int pyrblur_top_count = 0, pyrblur_rest_count = 0;
+  TileTable tiles[kTileTables];
   OrbxTopLevels top_levels{};  // the levels the second pass may skip
-  size_t tiles_frame_capacity = 0, tiles_small_capacity = 0;
-  int blur_tiles_count = 0, pyr2_tiles_count = 0;
   DevBuf s_tiles;  // stage-API tables
   std::vector<OrbxResizeTap> h_taps;
   int plan_w = 0, plan_h = 0;
 
-  // pools (sized for max_batch frames of max_width x max_height)
-  uint8_t* d_in = nullptr;  // staged host frames, tight pitch
-  uint8_t* d_pyr = nullptr;
-  uint8_t* d_pyr_blur = nullptr;
-  unsigned long long* d_mask = nullptr;
-  orbx_keypoint* d_cand = nullptr;
-  int32_t* d_cand_count = nullptr;
-  int32_t* d_cand_total = nullptr;
-  float* d_resp = nullptr;
+  uint8_t* d_in = nullptr;  // staged host frames, tight pitch (max_batch frames of max_width x max_height)
   // captured launch sequences of the most recent batch shapes (run_batch), round-robin replacement
   static constexpr int kGraphs = 16;  // (input, result block, lane) triples: 8 resident inputs over 4 blocks x 2 lanes
   hipGraphExec_t g_exec[kGraphs] = {};
   OrbxGraphKey g_key[kGraphs] = {};
   int g_next = 0;
   int plan_serial = 0;  // bumped whenever set_plan rebuilds the plan / tables
-  uint32_t* d_lcand = nullptr;  // spread selection: packed candidates, their responses, counts
-  float* d_lresp = nullptr;
-  int32_t* d_lcount = nullptr;
   OrbxResizeTap* d_taps = nullptr;
   size_t taps_capacity = 0;
   float* d_gauss = nullptr;
   // Result blocks.  A ring of kBlocks, used in turn by consecutive batches, each with a pinned host
   // mirror: the D2H copy of batch i (orbx_batch_prefetch, on its own copy stream) overlaps the
-  // kernels of batch i+1, which write the other block.  d_out / h_out / out_layout / last_n always
-  // describe the block of the most recent batch.
+  // kernels of batch i+1, which write the other block.  blocks[blk] is the block of the most recent batch.
   // (a ring of kBlocks blocks: with two, the copy of batch i -- about as long as a step at 256 frames per batch --
   // had to finish before batch i + 2 could start; with four it overlaps two following batches)
   static constexpr int kBlocks = 4;
-  uint8_t* d_outb[kBlocks] = {};
-  uint8_t* h_outb[kBlocks] = {};
-  uint8_t* h_outb_dev[kBlocks] = {};   // the device-visible addresses of the pinned mirrors
-  int host_results = 0;                // orbx_set_host_results: the describe kernel writes the compact record to the mirror
-  bool host_written[kBlocks] = {};     // ... and did so for the batch in this block
-  OutLayout layoutb[kBlocks] = {};
-  int nb[kBlocks] = {};    // frames in the block (0: never written)
-  int capb[kBlocks] = {1, 1, 1, 1};  // slots per frame the block was written with
-  bool copy_pending[kBlocks] = {};  // an asynchronous D2H of the block has been enqueued (ev_copied)
-  bool copy_compact[kBlocks] = {};  // ... of its compact prefix only (orbx_batch_prefetch_compact)
+  Block blocks[kBlocks];
   int blk = 0;
+  int host_results = 0;  // orbx_set_host_results: the describe kernel writes the compact record to the mirror
   int next_lane = 1;  // pipelined mode: the lane of the next batch (alternates)
   hipStream_t cstream = nullptr;
-  hipEvent_t ev_done[kBlocks] = {}, ev_copied[kBlocks] = {};
-  uint8_t* d_out = nullptr;
-  uint8_t* h_out = nullptr;  // pinned mirror
-  OutLayout out_layout{};
-  int out_cap = 0;  // slot capacity of the pool (plan_max.out_cap)
-  // Pipelined batches (orbx_set_pipelined_batches): two LANES, each with its own stream and its own working pools
-  // (pyramids, mask, statistics, candidates); consecutive device-resident batches alternate between them -- batch
-  // k uses lane k & 1 = its result block -- so the kernels of one batch overlap the tails and the nearly empty
-  // launches of the other.  lane_pool[0] / lane_stream[0] are the context's own pools / stream; the d_* members
-  // above always point at the pools of the most recent batch's lane.
-  struct LanePool {
-    uint8_t *d_pyr = nullptr, *d_pyr_blur = nullptr;
-    unsigned long long *d_mask = nullptr, *d_row_stat = nullptr;
-    orbx_keypoint* d_cand = nullptr;
-    int32_t *d_cand_count = nullptr, *d_cand_total = nullptr, *d_lcount = nullptr;
-    float *d_resp = nullptr, *d_lresp = nullptr;
-    uint32_t* d_lcand = nullptr;
-  };
-  LanePool lane_pool[2];
-  hipStream_t lane_stream[2] = {nullptr, nullptr};
+  // Pipelined batches (orbx_set_pipelined_batches): two LANES, each with its own stream and its own working pools;
+  // consecutive device-resident batches alternate between them -- batch k uses lane k & 1 = its result block --
+  // so the kernels of one batch overlap the tails and the nearly empty launches of the other.  lanes[0] has the
+  // pools every context has, and its stream is the context's own; lanes[lane] is the lane of the most recent batch.
   // Stream order is the only ordering inside a lane.  A batch that comes to a lane's pools, or to a result block,
   // on ANOTHER stream than their previous user (a caller's stream, the other lane) first makes its stream wait for
-  // that user's event: ev_pool[k] / pool_stream[k] for the pools of lane k, ev_done[b] / blk_stream[b] for block b.
-  hipEvent_t ev_pool[2] = {nullptr, nullptr};
-  hipStream_t pool_stream[2] = {nullptr, nullptr};
-  hipStream_t blk_stream[kBlocks] = {};
+  // that user's event: Lane::ev_pool / pool_stream for the pools of a lane, Block::ev_done / stream for a block.
+  Lane lanes[2];
+  int lane = 0;
   bool pipelined = false;
-  int last_n = 0;
   bool last_two_pass = false;  // the last batch built its pyramid top rows first (enqueue_batch)
   hipStream_t last_stream = nullptr;
 
@@ -235,10 +241,7 @@ struct orbx_ctx {
   bool prefs_applied = false;  // the current tile tables were built with tile_h_pref
   // ring of event sets: one per timed batched call, so that several calls can be
   // in flight before their stage times are read (no host sync between steps)
-  // (slots ORBX_NUM_STAGE_TIMES + 1, + 2: the boundaries inside the top-rows-first pipeline)
-  hipEvent_t evr[ORBX_EVENT_SETS][ORBX_NUM_STAGE_TIMES + 3] = {};
-  int ev_mode[ORBX_EVENT_SETS] = {};
-  bool ev_split[ORBX_EVENT_SETS] = {};
+  TimingSet evr[ORBX_EVENT_SETS];
   long long ev_calls = 0;  // timed batched calls so far
   hipEvent_t ev[2] = {};   // orbx_bench_stage
 };
@@ -285,8 +288,8 @@ int ensure(orbx_ctx* c, DevBuf& b, size_t bytes) {
   if (b.bytes >= bytes && b.p) return ORBX_OK;
   if (b.p) {  // nothing in flight may still use the old allocation: the context's stream, both lanes, a caller's stream
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (hipStream_t ls : c->lane_stream)
-      if (ls && ls != c->stream) HIPCHK(c, hipStreamSynchronize(ls));
+    for (const Lane& L : c->lanes)
+      if (L.stream && L.stream != c->stream) HIPCHK(c, hipStreamSynchronize(L.stream));
     if (c->last_stream && c->last_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->last_stream));
     HIPCHK(c, hipFree(b.p));
     b.p = nullptr;
@@ -297,23 +300,36 @@ int ensure(orbx_ctx* c, DevBuf& b, size_t bytes) {
   b.bytes = bytes;
   return ORBX_OK;
 }
+#define ENSURE(c, buf, bytes)                        \
+  do {                                               \
+    const int _st = ensure((c), (buf), (bytes));     \
+    if (_st != ORBX_OK) return _st;                  \
+  } while (0)
+
+// the stream the last batch ran on (the context's own before any batch)
+hipStream_t batch_stream(const orbx_ctx* c) { return c->last_stream ? c->last_stream : c->stream; }
+// the lane and the result block of the most recent batch
+const Lane& cur_lane(const orbx_ctx* c) { return c->lanes[c->lane]; }
+const Block& last_block(const orbx_ctx* c) { return c->blocks[c->blk]; }
+// slots per frame of a result block written under plan P (nfeatures too small for any quota: one empty slot)
+int slots_per_frame(const OrbxPlan& P) { return P.out_cap > 0 ? P.out_cap : 1; }
+
+// an integer environment switch (the ones read once per process keep the value in a static of their reader)
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // ORBX_PYR_GROUP=g: frames per dispatch group of the fused pyramid + blur kernel (0: frame-major grid)
 int pyr_group_env() {
-  static const int v = [] {
-    const char* e = getenv("ORBX_PYR_GROUP");
-    return e ? atoi(e) : 32;
-  }();
+  static const int v = env_int("ORBX_PYR_GROUP", 32);
   return v;
 }
 
 // ORBX_TOP_ROWS=k: FAST tile rows of the first pass of the top-rows-first pipeline (0: one pass)
 int top_rows_env() {
-  static const int v = [] {
-    const char* e = getenv("ORBX_TOP_ROWS");
-    return e ? atoi(e) : 2;
-  }();
-  return v < 0 ? 0 : v;
+  static const int v = std::max(env_int("ORBX_TOP_ROWS", 2), 0);
+  return v;
 }
 
 // Which FAST + NMS kernel the whole path runs: the register-streaming kernel (orbx_fast4.hip; the default) or, with
@@ -322,10 +338,7 @@ int top_rows_env() {
 // in production -- the short tile rows of the adaptive first pass, most units exiting early -- the streaming kernel
 // has less to do per unit (no tile fill, no barriers): same-box A/B 519 k vs 499 k frames/s (tools/ab_fast2.sh).
 // Read when a context is created (A/B timing in one process).
-int fast_impl_env() {
-  const char* e = getenv("ORBX_FAST_IMPL");
-  return e && atoi(e) == 3 ? 3 : 4;
-}
+int fast_impl_env() { return env_int("ORBX_FAST_IMPL", 4) == 3 ? 3 : 4; }
 
 // 8-bit bilinear coefficient tables: OpenCV 4.x generic 8UC1 INTER_LINEAR path
 // (imgproc/src/resize.cpp: scale = 1/((double)dst/src); fx = (float)((dx+0.5)*
@@ -437,26 +450,58 @@ int validate_params(const orbx_params& p, std::string* why) {
   return ORBX_OK;
 }
 
-// the working pools of lane k become the context's current ones
-void use_lane(orbx_ctx* c, int k) {
-  const orbx_ctx::LanePool& L = c->lane_pool[k];
-  c->d_pyr = L.d_pyr;
-  c->d_pyr_blur = L.d_pyr_blur;
-  c->d_mask = L.d_mask;
-  c->d_row_stat = L.d_row_stat;
-  c->d_cand = L.d_cand;
-  c->d_cand_count = L.d_cand_count;
-  c->d_cand_total = L.d_cand_total;
-  c->d_resp = L.d_resp;
-  c->d_lcand = L.d_lcand;
-  c->d_lresp = L.d_lresp;
-  c->d_lcount = L.d_lcount;
+// The working pools of a lane, stated once: where the pointer lives, the bytes max_batch frames of the largest
+// size need (0: no such pool in this context), and whether the pool starts out zeroed.
+struct PoolRef {
+  void** p;
+  size_t bytes;
+  bool zero;
+};
+std::array<PoolRef, 11> lane_pools(const orbx_ctx* c, Lane& L) {
+  const OrbxPlan& M = c->plan_max;
+  const size_t B = (size_t)c->p.max_batch, nc = B * (size_t)std::max(M.cand_total, 1);
+  const size_t frames = B * (size_t)M.frame_bytes, levels = B * ORBX_MAX_LEVELS * sizeof(int32_t);
+  return {{
+      {(void**)&L.d_pyr, frames, false},
+      // (zeroed: the padding bytes of a level stay zero, see set_plan; no pool when nothing is blurred)
+      {(void**)&L.d_pyr_blur, c->p.blur_levels != ORBX_BLUR_NONE ? frames : 0, true},
+      {(void**)&L.d_mask, B * (size_t)M.mask_words * 8, true},
+      {(void**)&L.d_row_stat, B * ORBX_FAST_STAT_WORDS * 8, false},
+      {(void**)&L.d_cand, nc * sizeof(orbx_keypoint), false},
+      {(void**)&L.d_cand_count, levels, false},
+      {(void**)&L.d_cand_total, levels, false},
+      {(void**)&L.d_resp, nc * sizeof(float), false},
+      {(void**)&L.d_lcand, nc * sizeof(uint32_t), false},
+      {(void**)&L.d_lresp, nc * sizeof(float), false},
+      {(void**)&L.d_lcount, levels, false},
+  }};
+}
+hipError_t alloc_lane_pools(orbx_ctx* c, Lane& L) {
+  for (const PoolRef& r : lane_pools(c, L)) {
+    if (r.bytes == 0) continue;
+    hipError_t e = hipMalloc(r.p, r.bytes + 256);  // (256 bytes of slack behind each pool)
+    if (e == hipSuccess && r.zero) e = hipMemset(*r.p, 0, r.bytes);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+// the pools of a lane and the stream of the second one (nothing of the lane may be in flight)
+void free_lane(orbx_ctx* c, Lane& L) {
+  for (const PoolRef& r : lane_pools(c, L)) {
+    if (*r.p) (void)hipFree(*r.p);
+    *r.p = nullptr;
+  }
+  if (L.stream != c->stream) {  // (lane 0 runs on the context's own stream)
+    if (L.stream) (void)hipStreamDestroy(L.stream);
+    L.stream = nullptr;
+  }
+  L.pool_stream = nullptr;
 }
 // everything either lane has in flight has finished
 hipError_t lanes_sync(orbx_ctx* c) {
-  for (hipStream_t s : c->lane_stream)
-    if (s) {
-      const hipError_t e = hipStreamSynchronize(s);
+  for (const Lane& L : c->lanes)
+    if (L.stream) {
+      const hipError_t e = hipStreamSynchronize(L.stream);
       if (e != hipSuccess) return e;
     }
   return hipSuccess;
@@ -467,6 +512,16 @@ bool fast_early_on(const orbx_ctx* c);
 int top_rows_env();
 bool tile_prefs_apply(const orbx_ctx* c) {
   return c->top_mode == 2 && top_rows_env() > 0 && fast_early_on(c) && fused_pyrblur(c);
+}
+
+// a table of the new plan goes to its pool
+int upload_tiles(orbx_ctx* c, int table, const std::vector<OrbxTileDesc>& t, const char* too_large) {
+  TileTable& T = c->tiles[table];
+  if (t.size() > T.capacity) return fail(c, ORBX_ERR_UNSUPPORTED, too_large);
+  if (!t.empty())  // (no second pass / no FAST tile at all: nothing to copy)
+    HIPCHK(c, hipMemcpy(T.d, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
+  T.count = (int)t.size();
+  return ORBX_OK;
 }
 
 int set_plan(orbx_ctx* c, int w, int h) {
@@ -480,9 +535,8 @@ int set_plan(orbx_ctx* c, int w, int h) {
   make_taps(plan, &c->h_taps);
   if (c->h_taps.size() > c->taps_capacity) return fail(c, ORBX_ERR_UNSUPPORTED, "resize table exceeds pool");
   // the table may still be in use by an in-flight batch of the previous size
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(batch_stream(c)));
   HIPCHK(c, lanes_sync(c));
-  if (c->last_stream && c->last_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->last_stream));
   HIPCHK(c, hipMemcpy(c->d_taps, c->h_taps.data(), c->h_taps.size() * sizeof(OrbxResizeTap),
                       hipMemcpyHostToDevice));
   // no plan is set until every table below is in place: a call that fails on the way must not leave the previous
@@ -491,21 +545,19 @@ int set_plan(orbx_ctx* c, int w, int h) {
   c->plan = plan;
   // the fused pyramid + blur kernel writes only the dwords that hold image pixels; consumers rely on the
   // padding bytes of a level being zero (BRIEF's zero-extension), and another frame size re-uses the pool
-  if (c->d_pyr_blur) {  // (on the context's stream, and waited for: batches may run on a caller's stream)
-    HIPCHK(c, hipMemsetAsync(c->d_pyr_blur, 0, (size_t)c->p.max_batch * (size_t)c->plan_max.frame_bytes, c->stream));
-    const orbx_ctx::LanePool& other = c->lane_pool[c->d_pyr_blur == c->lane_pool[0].d_pyr_blur ? 1 : 0];
-    if (other.d_pyr_blur)  // the other lane's pool as well
-      HIPCHK(c, hipMemsetAsync(other.d_pyr_blur, 0, (size_t)c->p.max_batch * (size_t)c->plan_max.frame_bytes, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
+  // (both lanes' pools; on the context's stream, and waited for: batches may run on a caller's stream)
+  for (const Lane& L : c->lanes)
+    if (L.d_pyr_blur)
+      HIPCHK(c, hipMemsetAsync(L.d_pyr_blur, 0, (size_t)c->p.max_batch * (size_t)c->plan_max.frame_bytes, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   make_tilemap(plan, ORBX_BLUR_TW, ORBX_BLUR_TH, true, &c->tm_blur);
   // (the adaptive first pass's shorter tile rows only where the top-rows-first pipeline can run at all: with the
   // early exit or the fused kernel switched off every tile works, and the default rows have the smaller halo share)
   c->prefs_applied = tile_prefs_apply(c);
   st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4,
                     c->prefs_applied ? c->tile_h_pref : nullptr);
-  if (c->prefs_applied && (st != ORBX_OK || (size_t)c->bm_fast.band_begin[c->bm_fast.nbands] > c->tiles_fast_capacity)) {
-    // The learned tile rows give a table the pool cannot hold (tiles_fast_capacity is an upper bound over every
+  if (c->prefs_applied && (st != ORBX_OK || (size_t)c->bm_fast.band_begin[c->bm_fast.nbands] > c->tiles[T_FAST].capacity)) {
+    // The learned tile rows give a table the pool cannot hold (the FAST table's capacity is an upper bound over every
     // preference, orbx_plan.h: this is a second line of defence).  What was learned is only a partition of the work:
     // forget it, take the default rows and run the batch -- a failure here would repeat with every batch of this size.
     for (int l = 0; l < ORBX_MAX_LEVELS; l++) c->tile_h_pref[l] = 0;
@@ -513,50 +565,31 @@ int set_plan(orbx_ctx* c, int w, int h) {
     st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4, nullptr);
   }
   if (st != ORBX_OK) return fail(c, st, why);
-  {
-    std::vector<OrbxTileDesc> t;
-    blur_tiles_for_impl(c->blur_impl, plan, &t);
-    if (t.size() > c->tiles_frame_capacity) return fail(c, ORBX_ERR_UNSUPPORTED, "blur tile table exceeds pool");
-    HIPCHK(c, hipMemcpy(c->d_tiles_blur, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-    c->blur_tiles_count = (int)t.size();
-    build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, pyr_group_env() > 0);
-    if (t.size() > c->tiles_frame_capacity) return fail(c, ORBX_ERR_UNSUPPORTED, "strip table exceeds pool");
-    HIPCHK(c, hipMemcpy(c->d_tiles_pyrblur, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-    c->pyrblur_tiles_count = (int)t.size();
-    build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, pyr_group_env() > 0, 1, &c->bm_fast, top_rows_env());
-    if (t.size() > c->tiles_frame_capacity) return fail(c, ORBX_ERR_UNSUPPORTED, "strip table exceeds pool");
-    HIPCHK(c, hipMemcpy(c->d_tiles_pyrblur_top, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-    c->pyrblur_top_count = (int)t.size();
-    build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, pyr_group_env() > 0, 2, &c->bm_fast, top_rows_env());
-    if (t.size() > c->tiles_frame_capacity) return fail(c, ORBX_ERR_UNSUPPORTED, "strip table exceeds pool");
-    if (!t.empty())
-      HIPCHK(c, hipMemcpy(c->d_tiles_pyrblur_rest, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-    c->pyrblur_rest_count = (int)t.size();
-    c->top_levels = OrbxTopLevels{};
-    for (int l = 0; l < plan.nlevels; l++)
-      if (pyrblur_first_pass_rows(plan, c->bm_fast, l, top_rows_env()) < plan.L[l].h) {
-        const int i = c->top_levels.n++;
-        c->top_levels.stat_index[i] = l * ORBX_MAX_BANDS;
-        c->top_levels.rows[i] = std::min(top_rows_env(), c->bm_fast.tiles_y[l]);
-        c->top_levels.cap[i] = plan.L[l].cap;
-      }
-    build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH_SMALL, &t);
-    if (t.size() > c->tiles_small_capacity) return fail(c, ORBX_ERR_UNSUPPORTED, "strip table exceeds pool");
-    HIPCHK(c, hipMemcpy(c->d_tiles_pyrblur_small, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-    c->pyrblur_small_count = (int)t.size();
-    build_frame_tiles(plan, ORBX_PYR2_TW, ORBX_PYR2_TH, true, &t);
-    if (t.size() > c->tiles_frame_capacity) return fail(c, ORBX_ERR_UNSUPPORTED, "pyramid tile table exceeds pool");
-    HIPCHK(c, hipMemcpy(c->d_tiles_pyr2, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-    c->pyr2_tiles_count = (int)t.size();
-  }
-  {
-    std::vector<OrbxTileDesc> t;
-    build_fast_tiles(plan, c->bm_fast, 0, 1, &t);
-    if (t.size() > c->tiles_fast_capacity) return fail(c, ORBX_ERR_UNSUPPORTED, "FAST tile table exceeds pool");
-    c->fast_tiles_count = (int)t.size();
-    if (!t.empty())
-      HIPCHK(c, hipMemcpy(c->d_tiles_fast, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-  }
+  const bool grouped = pyr_group_env() > 0;
+  const int top = top_rows_env();
+  std::vector<OrbxTileDesc> t;
+  blur_tiles_for_impl(c->blur_impl, plan, &t);
+  if ((st = upload_tiles(c, T_BLUR, t, "blur tile table exceeds pool")) != ORBX_OK) return st;
+  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped);
+  if ((st = upload_tiles(c, T_PYRBLUR, t, "strip table exceeds pool")) != ORBX_OK) return st;
+  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 1, &c->bm_fast, top);
+  if ((st = upload_tiles(c, T_PYRBLUR_TOP, t, "strip table exceeds pool")) != ORBX_OK) return st;
+  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 2, &c->bm_fast, top);
+  if ((st = upload_tiles(c, T_PYRBLUR_REST, t, "strip table exceeds pool")) != ORBX_OK) return st;
+  c->top_levels = OrbxTopLevels{};
+  for (int l = 0; l < plan.nlevels; l++)
+    if (pyrblur_first_pass_rows(plan, c->bm_fast, l, top) < plan.L[l].h) {
+      const int i = c->top_levels.n++;
+      c->top_levels.stat_index[i] = l * ORBX_MAX_BANDS;
+      c->top_levels.rows[i] = std::min(top, c->bm_fast.tiles_y[l]);
+      c->top_levels.cap[i] = plan.L[l].cap;
+    }
+  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH_SMALL, &t);
+  if ((st = upload_tiles(c, T_PYRBLUR_SMALL, t, "strip table exceeds pool")) != ORBX_OK) return st;
+  build_frame_tiles(plan, ORBX_PYR2_TW, ORBX_PYR2_TH, true, &t);
+  if ((st = upload_tiles(c, T_PYR2, t, "pyramid tile table exceeds pool")) != ORBX_OK) return st;
+  build_fast_tiles(plan, c->bm_fast, 0, 1, &t);
+  if ((st = upload_tiles(c, T_FAST, t, "FAST tile table exceeds pool")) != ORBX_OK) return st;
   c->plan_serial++;
   c->plan_w = w;
   c->plan_h = h;
@@ -565,18 +598,15 @@ int set_plan(orbx_ctx* c, int w, int h) {
 
 hipError_t launch_pyramid_auto(orbx_ctx* c, hipStream_t s, int n, const uint8_t* d_in, int in_stride,
                                size_t in_frame_stride) {
-  return orbx_launch_pyramid2(s, c->d_tiles_pyr2, c->pyr2_tiles_count, c->plan.frame_bytes, c->plan.w0, c->plan.h0, n,
-                              d_in, in_stride, in_frame_stride, c->d_taps, c->d_pyr);
+  return orbx_launch_pyramid2(s, c->tiles[T_PYR2].d, c->tiles[T_PYR2].count, c->plan.frame_bytes, c->plan.w0, c->plan.h0, n,
+                              d_in, in_stride, in_frame_stride, c->d_taps, cur_lane(c).d_pyr);
 }
 
 
 bool blur_enabled(const orbx_ctx* c) { return c->p.blur_levels != ORBX_BLUR_NONE; }
 // ORBX_FUSE=0: separate pyramid and blur kernels (same results; A/B timing and per-kernel profiles)
 bool fused_pyrblur(const orbx_ctx* c) {
-  static const int env = [] {
-    const char* e = getenv("ORBX_FUSE");
-    return e ? atoi(e) : 1;
-  }();
+  static const int env = env_int("ORBX_FUSE", 1);
   return env && c->fuse && c->p.blur_levels == ORBX_BLUR_ALL && c->p.blur_kind == ORBX_BLUR_SEP16;
 }
 const uint8_t* final_pyr(const orbx_ctx* c);
@@ -585,10 +615,7 @@ const uint8_t* final_pyr(const orbx_ctx* c);
 // first `cap` row-major survivors exit early (see decode_band in the kernels);
 // ORBX_FAST_EARLY=0 disables that (every tile does the full work).
 int fast_early_env() {  // ORBX_FAST_EARLY=0: every tile does the full work (results are identical)
-  static const int v = [] {
-    const char* e = getenv("ORBX_FAST_EARLY");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = env_int("ORBX_FAST_EARLY", 1);
   return v;
 }
 bool fast_early_on(const orbx_ctx* c) { return fast_early_env() && c->fast_early; }
@@ -596,22 +623,23 @@ bool fast_early_on(const orbx_ctx* c) { return fast_early_env() && c->fast_early
 // FAST + NMS over tiles [first, first + count) of the context's band-major table
 hipError_t launch_fast_tiles(orbx_ctx* c, hipStream_t s, int first, int count, int n, OrbxFastParams fp,
                              unsigned long long* stat, int chunk_scale = 1) {
+  const OrbxTileDesc* tiles = c->tiles[T_FAST].d + first;
+  unsigned long long* mask = cur_lane(c).d_mask;
   if (c->fast_impl == 4)
-    return orbx_launch_fast4(s, c->d_tiles_fast + first, count, n, final_pyr(c), c->plan.frame_bytes, c->plan.mask_words, fp,
-                             c->d_mask, stat);
-  return orbx_launch_fast_nms(s, c->d_tiles_fast + first, count, n, final_pyr(c), c->plan.frame_bytes, c->plan.mask_words,
-                              fp, c->d_mask, nullptr, stat, chunk_scale);
+    return orbx_launch_fast4(s, tiles, count, n, final_pyr(c), c->plan.frame_bytes, c->plan.mask_words, fp, mask, stat);
+  return orbx_launch_fast_nms(s, tiles, count, n, final_pyr(c), c->plan.frame_bytes, c->plan.mask_words, fp, mask, nullptr,
+                              stat, chunk_scale);
 }
 
 hipError_t launch_fast_whole(orbx_ctx* c, hipStream_t s, int n, OrbxFastParams fp, bool stats_zeroed = false) {
-  unsigned long long* stat = fast_early_on(c) ? c->d_row_stat : nullptr;
+  unsigned long long* stat = fast_early_on(c) ? cur_lane(c).d_row_stat : nullptr;
   if (stat && !stats_zeroed) {
     hipError_t e = hipMemsetAsync(stat, 0, (size_t)n * ORBX_FAST_STAT_WORDS * 8, s);
     if (e != hipSuccess) return e;
   }
   // (a two-launch variant -- tile row 0 first, the rest in strips of several tiles per
   // workgroup -- was measured slower: the kernel boundary costs more than the cheaper exits save)
-  return launch_fast_tiles(c, s, 0, c->fast_tiles_count, n, fp, stat);
+  return launch_fast_tiles(c, s, 0, c->tiles[T_FAST].count, n, fp, stat);
 }
 
 // separable kind -> register-streaming kernel; /273 kind -> LDS tile kernel.
@@ -619,8 +647,7 @@ hipError_t launch_fast_whole(orbx_ctx* c, hipStream_t s, int n, OrbxFastParams f
 // lane (measured 9 % slower: the blur's vertical pass dominates its instruction count, and 94 registers leave 5
 // waves per SIMD); 1: the first-generation LDS tile kernel.  The strip table is built for the kernel that reads it.
 int blur_impl_env() {
-  const char* e = getenv("ORBX_BLUR_IMPL");
-  const int v = e ? atoi(e) : 2;
+  const int v = env_int("ORBX_BLUR_IMPL", 2);
   return v >= 1 && v <= 3 ? v : 2;
 }
 hipError_t launch_blur_auto(int impl, hipStream_t s, const OrbxPlan& P, const OrbxTileMap& tm1, const OrbxTileDesc* tiles2,
@@ -631,7 +658,7 @@ hipError_t launch_blur_auto(int impl, hipStream_t s, const OrbxPlan& P, const Or
     return orbx_launch_blur3(s, tiles2, ntiles2, P.frame_bytes, n, src, dst, first_level);
   return orbx_launch_blur(s, P, tm1, n, src, dst, first_level, kind);
 }
-const uint8_t* final_pyr(const orbx_ctx* c) { return blur_enabled(c) ? c->d_pyr_blur : c->d_pyr; }
+const uint8_t* final_pyr(const orbx_ctx* c) { return blur_enabled(c) ? cur_lane(c).d_pyr_blur : cur_lane(c).d_pyr; }
 
 // Top-rows-first pipeline: wanted for the next batch?  (Eligibility -- fused kernel, early exit on, large
 // batch -- is checked where the launches are made.)
@@ -726,108 +753,100 @@ bool adapt_tile_rows(orbx_ctx* c) {
   return true;
 }
 
-// the launches of the whole path for n frames already on the device (the plan is set)
-int enqueue_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int row_stride, size_t frame_stride, hipStream_t s) {
+// the launches of the whole path for n frames already on the device, into result block B (the plan, the current
+// lane and the block's layout are set)
+int enqueue_batch(orbx_ctx* c, Block& B, const uint8_t* d_frames, int n, int row_stride, size_t frame_stride, hipStream_t s) {
   const OrbxPlan& P = c->plan;
+  const Lane& L = cur_lane(c);
+  const TileTable &whole = c->tiles[T_PYRBLUR], &shortb = c->tiles[T_PYRBLUR_SMALL], &top = c->tiles[T_PYRBLUR_TOP],
+                  &rest = c->tiles[T_PYRBLUR_REST];
   const int tm = c->timing;
-  hipEvent_t* evs = c->evr[c->ev_calls % ORBX_EVENT_SETS];
+  TimingSet& ts = c->evr[c->ev_calls % ORBX_EVENT_SETS];
   // event slots: 0 start | 1 pyramid | 2 blur | 3 fast | 4 compact | 5 harris | 6 select | 7 describe
   auto mark = [&](int slot, bool roofline_edge) -> hipError_t {
-    if (tm == 1 || (tm == 2 && roofline_edge)) return hipEventRecord(evs[slot], s);
+    if (tm == 1 || (tm == 2 && roofline_edge)) return hipEventRecord(ts.ev[slot], s);
     return hipSuccess;
   };
+  const bool fused = fused_pyrblur(c);
+  // (a wave per strip: below ~4096 waves the chip is far from full and the short-band table wins)
+  const bool small = (long long)n * whole.count < 4096;
+  // Top rows first.  The FAST early exit rests on the row-major cap (src/orb_cpu.cpp:108-110, src/orb.cpp:63):
+  // once the top tile rows of a level hold `cap` survivors, nothing below them is ever looked at -- not by
+  // FAST (its tiles exit), not by the selection (it stops at the first cap survivors), not by Harris or
+  // the descriptors (their keypoints lie in those top rows).  So the pyramid is produced in two passes:
+  //   1. the rows the first ORBX_TOP_ROWS FAST tile rows (and the descriptors of their keypoints) can read,
+  //   2. FAST on those tile rows,
+  //   3. the remaining rows -- a strip whose (frame, level) already has its cap survivors is skipped,
+  //   4. FAST on the remaining tile rows (their tiles exit the same way).
+  // What a skipped strip leaves in the pool (rows of an earlier batch) is never read.  Results are
+  // identical either way (tests/test_gpu_parity.py, tests/test_batch64_parity.py).
+  const bool two_pass = fused && !small && fast_early_on(c) && top_rows_wanted(c) && rest.count > 0 &&
+                        c->bm_fast.nbands > top_rows_env();
   // tile-row statistics of the FAST early exit: zeroed up front so that the events around the FAST stage bracket
-  // the kernel alone -- except in the top-rows-first pipeline (decided below; the same test here), whose first
-  // pyramid pass clears them itself: a memset node less per batch
-  const bool small0 = (long long)n * c->pyrblur_tiles_count < 4096;
-  const bool two_pass0 = fused_pyrblur(c) && !small0 && fast_early_on(c) && top_rows_wanted(c) && c->pyrblur_rest_count > 0 &&
-                         c->bm_fast.nbands > top_rows_env();
-  if (!two_pass0) HIPCHK(c, hipMemsetAsync(c->d_row_stat, 0, (size_t)n * ORBX_FAST_STAT_WORDS * 8, s));
+  // the kernel alone -- except in the top-rows-first pipeline, whose first pyramid pass clears them itself: a
+  // memset node less per batch
+  if (!two_pass) HIPCHK(c, hipMemsetAsync(L.d_row_stat, 0, (size_t)n * ORBX_FAST_STAT_WORDS * 8, s));
   HIPCHK(c, mark(0, false));
   OrbxFastParams fp{c->p.threshold, c->p.n, c->p.nms_window / 2};
-  bool two_pass = false;
-  if (fused_pyrblur(c)) {
+  if (fused) {
     // blur on every level: pyramid and blur in one pass, the un-blurred pyramid is never materialised
     // (the event slots then read: pyramid = 0, blur = the fused kernel)
     HIPCHK(c, mark(1, true));
-    // (a wave per strip: below ~4096 waves the chip is far from full and the short-band table wins)
-    const bool small = (long long)n * c->pyrblur_tiles_count < 4096;
-    // Top rows first.  The FAST early exit rests on the row-major cap (src/orb_cpu.cpp:108-110, src/orb.cpp:63):
-    // once the top tile rows of a level hold `cap` survivors, nothing below them is ever looked at -- not by
-    // FAST (its tiles exit), not by the selection (it stops at the first cap survivors), not by Harris or
-    // the descriptors (their keypoints lie in those top rows).  So the pyramid is produced in two passes:
-    //   1. the rows the first ORBX_TOP_ROWS FAST tile rows (and the descriptors of their keypoints) can read,
-    //   2. FAST on those tile rows,
-    //   3. the remaining rows -- a strip whose (frame, level) already has its cap survivors is skipped,
-    //   4. FAST on the remaining tile rows (their tiles exit the same way).
-    // What a skipped strip leaves in the pool (rows of an earlier batch) is never read.  Results are
-    // identical either way (tests/test_gpu_parity.py, tests/test_batch64_parity.py).
-    two_pass = !small && fast_early_on(c) && top_rows_wanted(c) && c->pyrblur_rest_count > 0 &&
-               c->bm_fast.nbands > top_rows_env();
     if (!two_pass) {
-      HIPCHK(c, orbx_launch_pyrblur(s, small ? c->d_tiles_pyrblur_small : c->d_tiles_pyrblur,
-                                    small ? c->pyrblur_small_count : c->pyrblur_tiles_count, P.frame_bytes, P.w0, P.h0, n,
-                                    d_frames, row_stride, frame_stride, c->d_taps, c->d_pyr_blur,
-                                    small ? 0 : pyr_group_env()));
+      const TileTable& T = small ? shortb : whole;
+      HIPCHK(c, orbx_launch_pyrblur(s, T.d, T.count, P.frame_bytes, P.w0, P.h0, n, d_frames, row_stride, frame_stride,
+                                    c->d_taps, L.d_pyr_blur, small ? 0 : pyr_group_env()));
     } else {
       const int first_tiles = c->bm_fast.band_begin[top_rows_env()];
-      HIPCHK(c, orbx_launch_pyrblur(s, c->d_tiles_pyrblur_top, c->pyrblur_top_count, P.frame_bytes, P.w0, P.h0, n, d_frames,
-                                    row_stride, frame_stride, c->d_taps, c->d_pyr_blur, pyr_group_env(), nullptr, c->d_feedback, nullptr,
-                                    c->d_row_stat));
+      HIPCHK(c, orbx_launch_pyrblur(s, top.d, top.count, P.frame_bytes, P.w0, P.h0, n, d_frames, row_stride, frame_stride,
+                                    c->d_taps, L.d_pyr_blur, pyr_group_env(), nullptr, c->d_feedback, nullptr,
+                                    L.d_row_stat));
       HIPCHK(c, mark(ORBX_NUM_STAGE_TIMES + 1, true));
-      HIPCHK(c, launch_fast_tiles(c, s, 0, first_tiles, n, fp, c->d_row_stat));
+      HIPCHK(c, launch_fast_tiles(c, s, 0, first_tiles, n, fp, L.d_row_stat));
       HIPCHK(c, mark(ORBX_NUM_STAGE_TIMES + 2, true));
-      HIPCHK(c, orbx_launch_pyrblur(s, c->d_tiles_pyrblur_rest, c->pyrblur_rest_count, P.frame_bytes, P.w0, P.h0, n,
-                                    d_frames, row_stride, frame_stride, c->d_taps, c->d_pyr_blur, pyr_group_env(),
-                                    c->d_row_stat, c->d_feedback, &c->top_levels));
+      HIPCHK(c, orbx_launch_pyrblur(s, rest.d, rest.count, P.frame_bytes, P.w0, P.h0, n, d_frames, row_stride,
+                                    frame_stride, c->d_taps, L.d_pyr_blur, pyr_group_env(), L.d_row_stat, c->d_feedback,
+                                    &c->top_levels));
       HIPCHK(c, mark(2, true));
-      HIPCHK(c, launch_fast_tiles(c, s, first_tiles, c->fast_tiles_count - first_tiles, n, fp, c->d_row_stat, 4));
+      HIPCHK(c, launch_fast_tiles(c, s, first_tiles, c->tiles[T_FAST].count - first_tiles, n, fp, L.d_row_stat, 4));
     }
   } else {
     HIPCHK(c, launch_pyramid_auto(c, s, n, d_frames, row_stride, frame_stride));
     HIPCHK(c, mark(1, true));
     if (blur_enabled(c))
-      HIPCHK(c, launch_blur_auto(c->blur_impl, s, P, c->tm_blur, c->d_tiles_blur, c->blur_tiles_count, n, c->d_pyr,
-                                 c->d_pyr_blur, c->p.blur_levels == ORBX_BLUR_UPPER ? 1 : 0, c->p.blur_kind));
+      HIPCHK(c, launch_blur_auto(c->blur_impl, s, P, c->tm_blur, c->tiles[T_BLUR].d, c->tiles[T_BLUR].count, n, L.d_pyr,
+                                 L.d_pyr_blur, c->p.blur_levels == ORBX_BLUR_UPPER ? 1 : 0, c->p.blur_kind));
   }
   if (!two_pass) {
     HIPCHK(c, mark(2, true));
     HIPCHK(c, launch_fast_whole(c, s, n, fp, true));
   }
-  c->ev_split[c->ev_calls % ORBX_EVENT_SETS] = two_pass;
+  ts.split = two_pass;
   c->last_two_pass = two_pass;
   HIPCHK(c, mark(3, true));
   HIPCHK(c, mark(4, false));  // (compaction, Harris and selection are one kernel: its time is the "select" slot)
   HIPCHK(c, mark(5, false));
-  // result block sections are laid out for (n, pool slot capacity)
-  c->out_layout = make_out_layout(n, P.out_cap > 0 ? P.out_cap : 1);
-  const OutLayout& o = c->out_layout;
+  const OutLayout& o = B.layout;
   // ORBX_SELECT_SPREAD=0/1 forces the fused / the three-kernel selection (A/B timing); frames whose candidates do not
   // fit the fused kernel's LDS take the three kernels whatever it says (orbx_launch_level_select_auto)
-  static const int spread = [] {
-    const char* e = getenv("ORBX_SELECT_SPREAD");
-    return e ? atoi(e) : -1;
-  }();
-  HIPCHK(c, orbx_launch_level_select_auto(s, P, n, c->p.select_mode, spread, c->d_mask, final_pyr(c), c->d_gauss,
-                                          c->p.harris_window, c->p.harris_k, c->d_lcand, c->d_lcount, c->d_lresp,
-                                          c->d_cand, c->d_resp, c->d_cand_count, two_pass ? c->d_feedback + 2 : nullptr));
+  static const int spread = env_int("ORBX_SELECT_SPREAD", -1);
+  HIPCHK(c, orbx_launch_level_select_auto(s, P, n, c->p.select_mode, spread, L.d_mask, final_pyr(c), c->d_gauss,
+                                          c->p.harris_window, c->p.harris_k, L.d_lcand, L.d_lcount, L.d_lresp,
+                                          L.d_cand, L.d_resp, L.d_cand_count, two_pass ? c->d_feedback + 2 : nullptr));
   HIPCHK(c, mark(6, false));
   if (P.out_cap <= 0)  // nfeatures too small for any quota: no describe launch, so the counts are zeroed here
-    HIPCHK(c, hipMemsetAsync(c->d_out + o.counts, 0, sizeof(int32_t) * (size_t)n, s));
+    HIPCHK(c, hipMemsetAsync(B.d + o.counts, 0, sizeof(int32_t) * (size_t)n, s));
   // orbx_set_host_results: the kernel also writes the compact record into the pinned mirror of the block
   OrbxHostRecord hr{};
-  if (c->host_results && P.out_cap > 0) {
-    uint8_t* hd = nullptr;
-    for (int i = 0; i < orbx_ctx::kBlocks; i++)
-      if (c->h_out == c->h_outb[i]) hd = c->h_outb_dev[i];
-    if (hd) hr = OrbxHostRecord{(int32_t*)(hd + o.counts), (uint32_t*)(hd + o.kp16), (float*)(hd + o.angle), (orbx_descriptor*)(hd + o.desc)};
-  }
-  HIPCHK(c, orbx_launch_describe(s, P, n, final_pyr(c), c->p.patch_size, c->d_cand_count, c->d_cand, c->d_resp,
-                                 (int32_t*)(c->d_out + o.counts), (orbx_keypoint*)(c->d_out + o.lkp),
-                                 (float*)(c->d_out + o.resp), (int32_t*)(c->d_out + o.level),
-                                 (orbx_keypoint*)(c->d_out + o.kp), (uint32_t*)(c->d_out + o.kp16),
-                                 (float*)(c->d_out + o.angle),
-                                 (orbx_descriptor*)(c->d_out + o.desc), two_pass ? c->d_feedback : nullptr,
+  if (c->host_results && P.out_cap > 0 && B.h_dev)
+    hr = OrbxHostRecord{(int32_t*)(B.h_dev + o.counts), (uint32_t*)(B.h_dev + o.kp16), (float*)(B.h_dev + o.angle),
+                        (orbx_descriptor*)(B.h_dev + o.desc)};
+  HIPCHK(c, orbx_launch_describe(s, P, n, final_pyr(c), c->p.patch_size, L.d_cand_count, L.d_cand, L.d_resp,
+                                 (int32_t*)(B.d + o.counts), (orbx_keypoint*)(B.d + o.lkp),
+                                 (float*)(B.d + o.resp), (int32_t*)(B.d + o.level),
+                                 (orbx_keypoint*)(B.d + o.kp), (uint32_t*)(B.d + o.kp16),
+                                 (float*)(B.d + o.angle),
+                                 (orbx_descriptor*)(B.d + o.desc), two_pass ? c->d_feedback : nullptr,
                                  two_pass ? const_cast<uint32_t*>(c->h_feedback) : nullptr, &hr));
   HIPCHK(c, mark(7, false));
   return ORBX_OK;
@@ -864,13 +883,12 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
     if (adapt_tile_rows(c) || (any_pref && tile_prefs_apply(c) != c->prefs_applied)) c->plan_w = 0;
   }
   const bool lanes = may_pipeline && c->pipelined && s == c->stream && w == c->plan_w && h == c->plan_h;
-  const int lane = lanes ? c->next_lane : 0;
+  c->lane = lanes ? c->next_lane : 0;
+  Lane& L = c->lanes[c->lane];
   if (lanes) {
-    use_lane(c, lane);
-    s = c->lane_stream[lane];
+    s = L.stream;
   } else {
-    if (c->lane_stream[1]) HIPCHK(c, lanes_sync(c));
-    use_lane(c, 0);
+    if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
     // the pools (pyramids, mask, result block) are reused by every batch: a batch still in
     // flight on a DIFFERENT stream must have finished before this one may touch them
     if (c->last_stream && c->last_stream != s) HIPCHK(c, hipStreamSynchronize(c->last_stream));
@@ -881,34 +899,24 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
   // this batch writes the other result block; if that block is still the source of an
   // asynchronous D2H copy (orbx_batch_prefetch two batches ago), the kernels wait for the copy
   const int blk = (c->blk + 1) % orbx_ctx::kBlocks;
-  if (c->copy_pending[blk]) HIPCHK(c, hipStreamWaitEvent(s, c->ev_copied[blk], 0));
+  Block& B = c->blocks[blk];
+  if (B.copy_pending) HIPCHK(c, hipStreamWaitEvent(s, B.ev_copied, 0));
   // the previous users of this lane's pools and of this result block, if they ran on another stream (a batch on a
   // caller's stream between pipelined batches, or the other way round): device-side waits, no host stall
-  if (c->pool_stream[lane] && c->pool_stream[lane] != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_pool[lane], 0));
-  if (c->blk_stream[blk] && c->blk_stream[blk] != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done[blk], 0));
-  // The block becomes "the last batch" only once its launches are enqueued: after a failed call orbx_batch_fetch
-  // must not hand out what an older batch left in it.
-  c->nb[blk] = 0;
-  c->copy_pending[blk] = false;
-  c->copy_compact[blk] = false;
-  uint8_t* const prev_d_out = c->d_out;
-  uint8_t* const prev_h_out = c->h_out;
-  const OutLayout prev_layout = c->out_layout;
-  c->d_out = c->d_outb[blk];  // (enqueue_batch writes through c->d_out)
-  c->h_out = c->h_outb[blk];
-  auto fail_restore = [&](int status) {
-    c->d_out = prev_d_out;
-    c->h_out = prev_h_out;
-    c->out_layout = prev_layout;
-    return status;
-  };
-  static const int use_graph = [] {
-    const char* e = getenv("ORBX_GRAPH");
-    return e ? atoi(e) : 1;
-  }();
+  if (L.pool_stream && L.pool_stream != s) HIPCHK(c, hipStreamWaitEvent(s, L.ev_pool, 0));
+  if (B.stream && B.stream != s) HIPCHK(c, hipStreamWaitEvent(s, B.ev_done, 0));
+  // The block becomes "the last batch" only once its launches are enqueued (B.n and c->blk below): after a failed
+  // call orbx_batch_fetch must not hand out what an older batch left in it.
+  B.n = 0;
+  B.copy_pending = false;
+  B.copy_compact = false;
+  // result block sections are laid out for (n, pool slot capacity)
+  B.cap = slots_per_frame(c->plan);
+  B.layout = make_out_layout(n, B.cap);
+  static const int use_graph = env_int("ORBX_GRAPH", 1);
   const int tm = c->timing;
   if (use_graph && tm == 0) {
-    const OrbxGraphKey key{d_frames, frame_stride, n, w, h, row_stride, (fast_early_on(c) ? 1 : 0) | (fused_pyrblur(c) ? 2 : 0) | (top_rows_wanted(c) ? 4 : 0) | (lanes ? 8 : 0) | (lane << 4) | (c->host_results ? 64 : 0),
+    const OrbxGraphKey key{d_frames, frame_stride, n, w, h, row_stride, (fast_early_on(c) ? 1 : 0) | (fused_pyrblur(c) ? 2 : 0) | (top_rows_wanted(c) ? 4 : 0) | (lanes ? 8 : 0) | (c->lane << 4) | (c->host_results ? 64 : 0),
                            c->plan_serial, blk};
     int gi = -1;
     for (int i = 0; i < orbx_ctx::kGraphs; i++)
@@ -919,51 +927,46 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
       drop_graph(c, gi);
       hipGraph_t g = nullptr;
       const hipError_t be = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-      if (be != hipSuccess) return fail_restore(fail(c, ORBX_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(be)));
-      st = enqueue_batch(c, d_frames, n, row_stride, frame_stride, s);
+      if (be != hipSuccess) return fail(c, ORBX_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(be));
+      st = enqueue_batch(c, B, d_frames, n, row_stride, frame_stride, s);
       const hipError_t ee = hipStreamEndCapture(s, &g);
       if (st != ORBX_OK) {
         if (g) (void)hipGraphDestroy(g);
-        return fail_restore(st);
+        return st;
       }
-      if (ee != hipSuccess) return fail_restore(fail(c, ORBX_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ee)));
+      if (ee != hipSuccess) return fail(c, ORBX_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ee));
       const hipError_t ie = hipGraphInstantiate(&c->g_exec[gi], g, nullptr, nullptr, 0);
       (void)hipGraphDestroy(g);
       if (ie != hipSuccess) {
         c->g_exec[gi] = nullptr;
-        return fail_restore(fail(c, ORBX_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)));
+        return fail(c, ORBX_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
       }
       c->g_key[gi] = key;
     }
     const hipError_t le = hipGraphLaunch(c->g_exec[gi], s);
-    if (le != hipSuccess) return fail_restore(fail(c, ORBX_ERR_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le)));
+    if (le != hipSuccess) return fail(c, ORBX_ERR_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
   } else {
-    if ((st = enqueue_batch(c, d_frames, n, row_stride, frame_stride, s)) != ORBX_OK) return fail_restore(st);
+    if ((st = enqueue_batch(c, B, d_frames, n, row_stride, frame_stride, s)) != ORBX_OK) return st;
   }
   c->blk = blk;
   if (lanes) c->next_lane ^= 1;
-  c->out_layout = make_out_layout(n, c->plan.out_cap > 0 ? c->plan.out_cap : 1);
-  c->last_n = n;
   c->batch_serial++;
   c->last_stream = s;
-  c->layoutb[blk] = c->out_layout;
-  c->nb[blk] = n;
-  c->capb[blk] = c->plan.out_cap > 0 ? c->plan.out_cap : 1;
-  c->copy_pending[blk] = false;
-  c->host_written[blk] = c->host_results && c->plan.out_cap > 0;
-  HIPCHK(c, hipEventRecord(c->ev_done[blk], s));
-  if (c->host_written[blk]) {
+  B.n = n;
+  B.host_written = c->host_results && c->plan.out_cap > 0;
+  HIPCHK(c, hipEventRecord(B.ev_done, s));
+  if (B.host_written) {
     // orbx_set_host_results: the compact record is in the pinned mirror when the batch ends -- the block counts as
     // compact-copied from the start (the copy stream is not involved; orbx_batch_prefetch_compact has nothing to do)
-    HIPCHK(c, hipEventRecord(c->ev_copied[blk], s));
-    c->copy_pending[blk] = true;
-    c->copy_compact[blk] = true;
+    HIPCHK(c, hipEventRecord(B.ev_copied, s));
+    B.copy_pending = true;
+    B.copy_compact = true;
   }
-  HIPCHK(c, hipEventRecord(c->ev_pool[lane], s));
-  c->pool_stream[lane] = s;
-  c->blk_stream[blk] = s;
+  HIPCHK(c, hipEventRecord(L.ev_pool, s));
+  L.pool_stream = s;
+  B.stream = s;
   if (tm != 0) {
-    c->ev_mode[c->ev_calls % ORBX_EVENT_SETS] = tm;
+    c->evr[c->ev_calls % ORBX_EVENT_SETS].mode = tm;
     c->ev_calls++;
   }
   return ORBX_OK;
@@ -1003,8 +1006,7 @@ OrbxPlan flat_plan(int w, int h, int cap) {
 // upload a host image into a zero-padded, 64-aligned-pitch scratch image
 int upload_flat(orbx_ctx* c, DevBuf& b, const uint8_t* img, int w, int h, int stride, int* pitch) {
   const int p = align_up(w, 64);
-  int st = ensure(c, b, (size_t)p * h + 256);
-  if (st != ORBX_OK) return st;
+  ENSURE(c, b, (size_t)p * h + 256);
   HIPCHK(c, hipMemsetAsync(b.p, 0, (size_t)p * h, c->stream));
   HIPCHK(c, hipMemcpy2DAsync(b.p, p, img, stride, w, h, hipMemcpyHostToDevice, c->stream));
   *pitch = p;
@@ -1074,43 +1076,28 @@ const char* orbx_version(void) { return "liborbx 0.1.0 gfx950"; }
 
 const char* orbx_last_error_string(const orbx_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
-namespace {
-// the second lane's pools and stream (nothing of it may be in flight)
-void free_lane1(orbx_ctx* c) {
-  orbx_ctx::LanePool& L = c->lane_pool[1];
-  void* lb[] = {L.d_pyr, L.d_pyr_blur, L.d_mask, L.d_row_stat, L.d_cand, L.d_cand_count, L.d_cand_total, L.d_resp,
-                L.d_lcand, L.d_lresp, L.d_lcount};
-  for (void* b : lb)
-    if (b) (void)hipFree(b);
-  L = orbx_ctx::LanePool{};
-  if (c->lane_stream[1]) (void)hipStreamDestroy(c->lane_stream[1]);
-  c->lane_stream[1] = nullptr;
-  c->pool_stream[1] = nullptr;
-}
-}  // namespace
-
 void orbx_destroy(orbx_ctx* c) {
   DeviceGuard _dg(c);
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->lane_stream[1]) (void)hipStreamSynchronize(c->lane_stream[1]);
-  use_lane(c, 0);  // (the list below frees the context's own pools)
-  free_lane1(c);   // the second lane of the pipelined mode (also what a failed enable left behind)
+  if (c->lanes[1].stream) (void)hipStreamSynchronize(c->lanes[1].stream);
   for (int i = 0; i < orbx_ctx::kGraphs; i++) drop_graph(c, i);
-  void* bufs[] = {c->d_in,   c->d_pyr,  c->d_pyr_blur, c->d_mask, c->d_cand, c->d_cand_count, c->d_cand_total,
-                  c->d_resp, c->d_taps, c->d_gauss,    c->d_row_stat, c->d_tiles_fast, c->d_tiles_blur, c->d_tiles_pyr2, c->d_tiles_pyrblur, c->d_tiles_pyrblur_small,
-                  c->d_tiles_pyrblur_top, c->d_tiles_pyrblur_rest, c->d_feedback, c->d_lcand, c->d_lresp, c->d_lcount};
+  for (Lane& L : c->lanes) {  // (the second lane of the pipelined mode: also what a failed enable left behind)
+    free_lane(c, L);
+    if (L.ev_pool) (void)hipEventDestroy(L.ev_pool);
+  }
+  for (TileTable& T : c->tiles)
+    if (T.d) (void)hipFree(T.d);
+  void* bufs[] = {c->d_in, c->d_taps, c->d_gauss, c->d_feedback};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->h_feedback) (void)hipHostFree(const_cast<uint32_t*>(c->h_feedback));
-  for (int i = 0; i < orbx_ctx::kBlocks; i++) {
-    if (c->h_outb[i]) (void)hipHostFree(c->h_outb[i]);
-    if (c->d_outb[i]) (void)hipFree(c->d_outb[i]);
-    if (c->ev_done[i]) (void)hipEventDestroy(c->ev_done[i]);
-    if (c->ev_copied[i]) (void)hipEventDestroy(c->ev_copied[i]);
+  for (Block& B : c->blocks) {
+    if (B.h) (void)hipHostFree(B.h);
+    if (B.d) (void)hipFree(B.d);
+    if (B.ev_done) (void)hipEventDestroy(B.ev_done);
+    if (B.ev_copied) (void)hipEventDestroy(B.ev_copied);
   }
-  for (auto& e : c->ev_pool)
-    if (e) (void)hipEventDestroy(e);
   if (c->cstream) {
     (void)hipStreamSynchronize(c->cstream);
     (void)hipStreamDestroy(c->cstream);
@@ -1127,8 +1114,8 @@ void orbx_destroy(orbx_ctx* c) {
     if (b->p) (void)hipFree(b->p);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
-  for (auto& set : c->evr)
-    for (auto& e : set)
+  for (TimingSet& set : c->evr)
+    for (auto& e : set.ev)
       if (e) (void)hipEventDestroy(e);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -1187,15 +1174,12 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
   } while (0)
 
   CREATE_CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  c->lanes[0].stream = c->stream;  // lane 0 of the pipelined mode runs on the context's own stream
   for (auto& e : c->ev) CREATE_CHK(hipEventCreate(&e));
-  for (auto& set : c->evr)
-    for (auto& e : set) CREATE_CHK(hipEventCreate(&e));
+  for (TimingSet& set : c->evr)
+    for (auto& e : set.ev) CREATE_CHK(hipEventCreate(&e));
   CREATE_CHK(hipMalloc((void**)&c->d_in, B * (size_t)p->max_width * p->max_height + 256));
-  CREATE_CHK(hipMalloc((void**)&c->d_pyr, B * (size_t)M.frame_bytes + 256));
-  if (p->blur_levels != ORBX_BLUR_NONE)
-    CREATE_CHK(hipMalloc((void**)&c->d_pyr_blur, B * (size_t)M.frame_bytes + 256));
-  CREATE_CHK(hipMalloc((void**)&c->d_mask, B * (size_t)M.mask_words * 8 + 256));
-  CREATE_CHK(hipMalloc((void**)&c->d_row_stat, B * ORBX_FAST_STAT_WORDS * 8));
+  CREATE_CHK(alloc_lane_pools(c, c->lanes[0]));
   CREATE_CHK(hipMalloc((void**)&c->d_feedback, ORBX_FEEDBACK_WORDS * 4));
   CREATE_CHK(hipMemset(c->d_feedback, 0, ORBX_FEEDBACK_WORDS * 4));
   CREATE_CHK(hipHostMalloc((void**)&c->h_feedback, ORBX_FEEDBACK_WORDS * 4, hipHostMallocDefault));
@@ -1205,25 +1189,11 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
     orbx_destroy(c);
     return fail(nullptr, st, why);
   }
-  {
-    c->tiles_fast_capacity = tcap.fast;
-    CREATE_CHK(hipMalloc((void**)&c->d_tiles_fast, std::max<size_t>(c->tiles_fast_capacity, 1) * sizeof(OrbxTileDesc)));
-    c->tiles_small_capacity = tcap.small;
-    CREATE_CHK(hipMalloc((void**)&c->d_tiles_pyrblur_small, c->tiles_small_capacity * sizeof(OrbxTileDesc)));
-    c->tiles_frame_capacity = tcap.frame;
-    CREATE_CHK(hipMalloc((void**)&c->d_tiles_pyrblur, c->tiles_frame_capacity * sizeof(OrbxTileDesc)));
-    CREATE_CHK(hipMalloc((void**)&c->d_tiles_pyrblur_top, c->tiles_frame_capacity * sizeof(OrbxTileDesc)));
-    CREATE_CHK(hipMalloc((void**)&c->d_tiles_pyrblur_rest, c->tiles_frame_capacity * sizeof(OrbxTileDesc)));
-    CREATE_CHK(hipMalloc((void**)&c->d_tiles_blur, c->tiles_frame_capacity * sizeof(OrbxTileDesc)));
-    CREATE_CHK(hipMalloc((void**)&c->d_tiles_pyr2, c->tiles_frame_capacity * sizeof(OrbxTileDesc)));
-  }
-  CREATE_CHK(hipMalloc((void**)&c->d_cand, B * (size_t)std::max(M.cand_total, 1) * sizeof(orbx_keypoint)));
-  CREATE_CHK(hipMalloc((void**)&c->d_cand_count, B * ORBX_MAX_LEVELS * sizeof(int32_t)));
-  CREATE_CHK(hipMalloc((void**)&c->d_cand_total, B * ORBX_MAX_LEVELS * sizeof(int32_t)));
-  CREATE_CHK(hipMalloc((void**)&c->d_resp, B * (size_t)std::max(M.cand_total, 1) * sizeof(float)));
-  CREATE_CHK(hipMalloc((void**)&c->d_lcand, B * (size_t)std::max(M.cand_total, 1) * sizeof(uint32_t)));
-  CREATE_CHK(hipMalloc((void**)&c->d_lresp, B * (size_t)std::max(M.cand_total, 1) * sizeof(float)));
-  CREATE_CHK(hipMalloc((void**)&c->d_lcount, B * ORBX_MAX_LEVELS * sizeof(int32_t)));
+  for (TileTable& T : c->tiles) T.capacity = tcap.frame;
+  c->tiles[T_FAST].capacity = tcap.fast;
+  c->tiles[T_PYRBLUR_SMALL].capacity = tcap.small;
+  for (TileTable& T : c->tiles)
+    CREATE_CHK(hipMalloc((void**)&T.d, std::max<size_t>(T.capacity, 1) * sizeof(OrbxTileDesc)));
   {
     // level sizes of smaller frames never exceed those of the largest frame
     c->taps_capacity = tcap.taps;
@@ -1236,9 +1206,8 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
     CREATE_CHK(hipMalloc((void**)&c->d_gauss, g.size() * sizeof(float)));
     CREATE_CHK(hipMemcpy(c->d_gauss, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  c->out_cap = std::max(M.out_cap, 1);
   {
-    const OutLayout o = make_out_layout((int)B, c->out_cap);
+    const OutLayout o = make_out_layout((int)B, slots_per_frame(M));  // (the largest block any batch can need)
     {
       // The copy stream gets the HIGHEST priority -- not for the copies' sake: streams of one priority share a few
       // hardware queues, and the copy of a batch is enqueued behind a wait for the batch's end.  In a queue shared
@@ -1249,33 +1218,16 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
       CREATE_CHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
       CREATE_CHK(hipStreamCreateWithPriority(&c->cstream, hipStreamNonBlocking, greatest));
     }
-    for (int i = 0; i < orbx_ctx::kBlocks; i++) {
-      CREATE_CHK(hipMalloc((void**)&c->d_outb[i], o.total));
-      CREATE_CHK(hipHostMalloc((void**)&c->h_outb[i], o.total, hipHostMallocDefault));
-      CREATE_CHK(hipHostGetDevicePointer((void**)&c->h_outb_dev[i], c->h_outb[i], 0));
-      CREATE_CHK(hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming));
-      CREATE_CHK(hipEventCreateWithFlags(&c->ev_copied[i], hipEventDisableTiming));
+    for (Block& blk : c->blocks) {
+      CREATE_CHK(hipMalloc((void**)&blk.d, o.total));
+      CREATE_CHK(hipHostMalloc((void**)&blk.h, o.total, hipHostMallocDefault));
+      CREATE_CHK(hipHostGetDevicePointer((void**)&blk.h_dev, blk.h, 0));
+      CREATE_CHK(hipEventCreateWithFlags(&blk.ev_done, hipEventDisableTiming));
+      CREATE_CHK(hipEventCreateWithFlags(&blk.ev_copied, hipEventDisableTiming));
     }
-    for (auto& e : c->ev_pool) CREATE_CHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->d_out = c->d_outb[0];
-    c->h_out = c->h_outb[0];
+    for (Lane& L : c->lanes) CREATE_CHK(hipEventCreateWithFlags(&L.ev_pool, hipEventDisableTiming));
   }
 #undef CREATE_CHK
-  {  // lane 0 of the pipelined mode = the context's own pools and stream
-    orbx_ctx::LanePool& L = c->lane_pool[0];
-    L.d_pyr = c->d_pyr;
-    L.d_pyr_blur = c->d_pyr_blur;
-    L.d_mask = c->d_mask;
-    L.d_row_stat = c->d_row_stat;
-    L.d_cand = c->d_cand;
-    L.d_cand_count = c->d_cand_count;
-    L.d_cand_total = c->d_cand_total;
-    L.d_resp = c->d_resp;
-    L.d_lcand = c->d_lcand;
-    L.d_lresp = c->d_lresp;
-    L.d_lcount = c->d_lcount;
-    c->lane_stream[0] = c->stream;
-  }
   *out = c;
   return ORBX_OK;
 }
@@ -1338,7 +1290,7 @@ int orbx_detect_and_compute_batch_host(orbx_ctx* c, const uint8_t* frames, int n
 int orbx_wait(orbx_ctx* c) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
-  HIPCHK(c, hipStreamSynchronize(c->last_stream ? c->last_stream : c->stream));
+  HIPCHK(c, hipStreamSynchronize(batch_stream(c)));
   HIPCHK(c, lanes_sync(c));
   return ORBX_OK;
 }
@@ -1355,30 +1307,12 @@ int orbx_set_pipelined_batches(orbx_ctx* c, int enable) {
   if (!c) return ORBX_ERR_INVALID_ARG;
   if (c->last_stream) HIPCHK(c, hipStreamSynchronize(c->last_stream));
   HIPCHK(c, lanes_sync(c));
-  if (enable && !c->lane_stream[1]) {  // the second lane: a stream and a second set of working pools
-    const orbx_params* p = &c->p;
-    const OrbxPlan& M = c->plan_max;
-    const size_t B = (size_t)p->max_batch;
-    orbx_ctx::LanePool& L = c->lane_pool[1];
-    const size_t nc = (size_t)std::max(M.cand_total, 1);
-    hipError_t e = hipMalloc((void**)&L.d_pyr, B * (size_t)M.frame_bytes + 256);
-    if (e == hipSuccess && p->blur_levels != ORBX_BLUR_NONE) {
-      e = hipMalloc((void**)&L.d_pyr_blur, B * (size_t)M.frame_bytes + 256);
-      if (e == hipSuccess) e = hipMemset(L.d_pyr_blur, 0, B * (size_t)M.frame_bytes);  // (the padding bytes of a level stay zero)
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&L.d_mask, B * (size_t)M.mask_words * 8 + 256);
-    if (e == hipSuccess) e = hipMemset(L.d_mask, 0, B * (size_t)M.mask_words * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&L.d_row_stat, B * ORBX_FAST_STAT_WORDS * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&L.d_cand, B * nc * sizeof(orbx_keypoint));
-    if (e == hipSuccess) e = hipMalloc((void**)&L.d_cand_count, B * ORBX_MAX_LEVELS * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&L.d_cand_total, B * ORBX_MAX_LEVELS * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&L.d_resp, B * nc * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&L.d_lcand, B * nc * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&L.d_lresp, B * nc * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&L.d_lcount, B * ORBX_MAX_LEVELS * sizeof(int32_t));
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->lane_stream[1], hipStreamNonBlocking);
+  Lane& L = c->lanes[1];
+  if (enable && !L.stream) {  // the second lane: a stream and a second set of working pools
+    hipError_t e = alloc_lane_pools(c, L);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking);
     if (e != hipSuccess) {  // (at batch 512 the second pool set is GBs: running out of memory is the realistic failure)
-      free_lane1(c);
+      free_lane(c, L);
       c->pipelined = false;
       return fail(c, ORBX_ERR_HIP, std::string("second lane of the pipelined mode: ") + hipGetErrorString(e));
     }
@@ -1396,26 +1330,16 @@ int orbx_debug_fill_pools(orbx_ctx* c, int byte) {
   if (c->last_stream) HIPCHK(c, hipStreamSynchronize(c->last_stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, lanes_sync(c));
-  const OrbxPlan& M = c->plan_max;
-  const size_t B = (size_t)c->p.max_batch, nc = (size_t)std::max(M.cand_total, 1);
-  for (const orbx_ctx::LanePool& L : c->lane_pool) {
+  for (Lane& L : c->lanes) {
     if (!L.d_mask) continue;  // (lane 1 exists once the pipelined mode has been switched on)
-    HIPCHK(c, hipMemsetAsync(L.d_pyr, byte, B * (size_t)M.frame_bytes, c->stream));
-    HIPCHK(c, hipMemsetAsync(L.d_mask, byte, B * (size_t)M.mask_words * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(L.d_row_stat, byte, B * ORBX_FAST_STAT_WORDS * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(L.d_cand, byte, B * nc * sizeof(orbx_keypoint), c->stream));
-    HIPCHK(c, hipMemsetAsync(L.d_cand_count, byte, B * ORBX_MAX_LEVELS * sizeof(int32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(L.d_cand_total, byte, B * ORBX_MAX_LEVELS * sizeof(int32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(L.d_resp, byte, B * nc * sizeof(float), c->stream));
-    HIPCHK(c, hipMemsetAsync(L.d_lcand, byte, B * nc * sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(L.d_lresp, byte, B * nc * sizeof(float), c->stream));
-    HIPCHK(c, hipMemsetAsync(L.d_lcount, byte, B * ORBX_MAX_LEVELS * sizeof(int32_t), c->stream));
+    for (const PoolRef& r : lane_pools(c, L))
+      if (*r.p && *r.p != L.d_pyr_blur) HIPCHK(c, hipMemsetAsync(*r.p, byte, r.bytes, c->stream));
     // The blurred pyramid is the one pool that must hold zeroes: the padding bytes of its levels (set_plan zeroes
     // them, the fused pyramid + blur kernel never writes them, BRIEF reads them as the zero extension of a row).  So
     // only the PIXELS of the current plan's levels are filled -- what a skipped strip of the top-rows-first pipeline
     // leaves behind -- and nothing before a plan is set.
     if (L.d_pyr_blur && c->plan_w > 0)
-      for (size_t f = 0; f < B; f++)
+      for (size_t f = 0; f < (size_t)c->p.max_batch; f++)
         for (int l = 0; l < c->plan.nlevels; l++) {
           const OrbxLevel& V = c->plan.L[l];
           HIPCHK(c, hipMemset2DAsync(L.d_pyr_blur + f * (size_t)c->plan.frame_bytes + (size_t)V.img_off, (size_t)V.pitch, byte,
@@ -1452,11 +1376,11 @@ int orbx_set_top_rows_first(orbx_ctx* c, int mode) {
 int orbx_fast_tile_counts(orbx_ctx* c, long long* worked, long long* total) {
   DeviceGuard _dg(c);
   if (!c || !worked || !total) return ORBX_ERR_INVALID_ARG;
-  if (c->plan_w == 0 || c->last_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "run a batch first");
-  const int n = c->last_n;
+  if (c->plan_w == 0 || last_block(c).n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "run a batch first");
+  const int n = last_block(c).n;
   std::vector<unsigned long long> h((size_t)n * ORBX_FAST_STAT_WORDS);
   HIPCHK(c, hipStreamSynchronize(c->last_stream));
-  HIPCHK(c, hipMemcpy(h.data(), c->d_row_stat, h.size() * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(h.data(), cur_lane(c).d_row_stat, h.size() * 8, hipMemcpyDeviceToHost));
   long long w = 0;
   for (int f = 0; f < n; f++)
     for (int l = 0; l < c->plan.nlevels; l++)
@@ -1470,8 +1394,8 @@ int orbx_fast_tile_counts(orbx_ctx* c, long long* worked, long long* total) {
 int orbx_pyramid_pixel_counts(orbx_ctx* c, long long* produced, long long* total) {
   DeviceGuard _dg(c);
   if (!c || !produced || !total) return ORBX_ERR_INVALID_ARG;
-  if (c->plan_w == 0 || c->last_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "run a batch first");
-  const int n = c->last_n, top = top_rows_env();
+  if (c->plan_w == 0 || last_block(c).n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "run a batch first");
+  const int n = last_block(c).n, top = top_rows_env();
   long long per_frame = 0;
   for (int l = 0; l < c->plan.nlevels; l++) per_frame += (long long)c->plan.L[l].w * c->plan.L[l].h;
   *total = per_frame * n;
@@ -1479,7 +1403,7 @@ int orbx_pyramid_pixel_counts(orbx_ctx* c, long long* produced, long long* total
   if (!c->last_two_pass) return ORBX_OK;
   std::vector<unsigned long long> h((size_t)n * ORBX_FAST_STAT_WORDS);
   HIPCHK(c, hipStreamSynchronize(c->last_stream));
-  HIPCHK(c, hipMemcpy(h.data(), c->d_row_stat, h.size() * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(h.data(), cur_lane(c).d_row_stat, h.size() * 8, hipMemcpyDeviceToHost));
   long long done = 0;
   for (int f = 0; f < n; f++)
     for (int l = 0; l < c->plan.nlevels; l++) {
@@ -1507,8 +1431,9 @@ int orbx_stage_times_history(orbx_ctx* c, int back, float* ms) {
   if (back < 0 || back >= ORBX_EVENT_SETS || back >= c->ev_calls)
     return fail(c, ORBX_ERR_INVALID_ARG, "no timed batched call that far back");
   const long long call = c->ev_calls - 1 - back;
-  hipEvent_t* evs = c->evr[call % ORBX_EVENT_SETS];
-  const int mode = c->ev_mode[call % ORBX_EVENT_SETS];
+  const TimingSet& ts = c->evr[call % ORBX_EVENT_SETS];
+  const hipEvent_t* evs = ts.ev;
+  const int mode = ts.mode;
   std::memset(ms, 0, sizeof(float) * ORBX_NUM_STAGE_TIMES);
   if (mode == 1) {
     for (int i = 0; i < ORBX_NUM_STAGE_TIMES - 1; i++) HIPCHK(c, hipEventElapsedTime(&ms[i], evs[i], evs[i + 1]));
@@ -1517,7 +1442,7 @@ int orbx_stage_times_history(orbx_ctx* c, int back, float* ms) {
     HIPCHK(c, hipEventElapsedTime(&ms[1], evs[1], evs[2]));
     HIPCHK(c, hipEventElapsedTime(&ms[2], evs[2], evs[3]));
   }
-  if (c->ev_split[call % ORBX_EVENT_SETS]) {
+  if (ts.split) {
     // top-rows-first pipeline: events 1 | pyramid+blur (top) | N+1 | FAST (top) | N+2 | pyramid+blur (rest) | 2 | FAST (rest) | 3
     float a = 0, b = 0, d = 0, e = 0;
     HIPCHK(c, hipEventElapsedTime(&a, evs[1], evs[ORBX_NUM_STAGE_TIMES + 1]));
@@ -1535,18 +1460,19 @@ int orbx_last_stage_times(orbx_ctx* c, float* ms) { return orbx_stage_times_hist
 int orbx_batch_results_device(orbx_ctx* c, orbx_batch_view* v) {
   DeviceGuard _dg(c);
   if (!c || !v) return ORBX_ERR_INVALID_ARG;
-  if (c->last_n <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been run");
-  const OutLayout& o = c->out_layout;
-  v->counts = (const int32_t*)(c->d_out + o.counts);
-  v->keypoints = (const orbx_keypoint*)(c->d_out + o.kp);
-  v->keypoints16 = (const uint32_t*)(c->d_out + o.kp16);
-  v->level_kps = (const orbx_keypoint*)(c->d_out + o.lkp);
-  v->orientations = (const float*)(c->d_out + o.angle);
-  v->responses = (const float*)(c->d_out + o.resp);
-  v->levels = (const int32_t*)(c->d_out + o.level);
-  v->descriptors = (const orbx_descriptor*)(c->d_out + o.desc);
-  v->slot_capacity = c->plan.out_cap > 0 ? c->plan.out_cap : 1;
-  v->n = c->last_n;
+  const Block& B = last_block(c);
+  if (B.n <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been run");
+  const OutLayout& o = B.layout;
+  v->counts = (const int32_t*)(B.d + o.counts);
+  v->keypoints = (const orbx_keypoint*)(B.d + o.kp);
+  v->keypoints16 = (const uint32_t*)(B.d + o.kp16);
+  v->level_kps = (const orbx_keypoint*)(B.d + o.lkp);
+  v->orientations = (const float*)(B.d + o.angle);
+  v->responses = (const float*)(B.d + o.resp);
+  v->levels = (const int32_t*)(B.d + o.level);
+  v->descriptors = (const orbx_descriptor*)(B.d + o.desc);
+  v->slot_capacity = B.cap;
+  v->n = B.n;
   return ORBX_OK;
 }
 
@@ -1556,30 +1482,31 @@ namespace {
 int fetch_block(orbx_ctx* c, int b, int first, int n, int32_t* counts, orbx_keypoint* keypoints, float* orientations,
                 orbx_descriptor* descriptors, float* responses, int32_t* levels, orbx_keypoint* level_kps,
                 int capacity) {
+  Block& B = c->blocks[b];
   if (!counts) return fail(c, ORBX_ERR_INVALID_ARG, "counts is NULL");
-  if (first < 0 || n < 1 || first + n > c->nb[b]) return fail(c, ORBX_ERR_INVALID_ARG, "frame range outside batch");
+  if (first < 0 || n < 1 || first + n > B.n) return fail(c, ORBX_ERR_INVALID_ARG, "frame range outside batch");
   if (capacity < 0) return fail(c, ORBX_ERR_INVALID_ARG, "capacity < 0");
-  const OutLayout& o = c->layoutb[b];
-  const int cap = c->capb[b];
-  const uint8_t* h = c->h_outb[b];
-  if (c->copy_pending[b] && c->copy_compact[b] && (responses || levels || level_kps)) {
+  const OutLayout& o = B.layout;
+  const int cap = B.cap;
+  const uint8_t* h = B.h;
+  if (B.copy_pending && B.copy_compact && (responses || levels || level_kps)) {
     // only the compact prefix is on its way: fetch the other sections now (blocking)
-    HIPCHK(c, hipEventSynchronize(c->ev_copied[b]));
-    HIPCHK(c, hipMemcpyAsync(c->h_outb[b] + o.compact, c->d_outb[b] + o.compact, o.total - o.compact, hipMemcpyDeviceToHost,
+    HIPCHK(c, hipEventSynchronize(B.ev_copied));
+    HIPCHK(c, hipMemcpyAsync(B.h + o.compact, B.d + o.compact, o.total - o.compact, hipMemcpyDeviceToHost,
                              c->cstream));
     HIPCHK(c, hipStreamSynchronize(c->cstream));
-    c->copy_compact[b] = false;
-  } else if (c->copy_pending[b]) {
-    HIPCHK(c, hipEventSynchronize(c->ev_copied[b]));
+    B.copy_compact = false;
+  } else if (B.copy_pending) {
+    HIPCHK(c, hipEventSynchronize(B.ev_copied));
   } else if (b == c->blk) {
     // blocking fetch of the last batch: the copy goes behind the batch on ITS stream (no hop to the copy
     // stream: the synchronous one-frame call is latency-bound)
-    hipStream_t s = c->last_stream ? c->last_stream : c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->h_outb[b], c->d_outb[b], o.total, hipMemcpyDeviceToHost, s));
+    hipStream_t s = batch_stream(c);
+    HIPCHK(c, hipMemcpyAsync(B.h, B.d, o.total, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
   } else {
-    HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_done[b], 0));
-    HIPCHK(c, hipMemcpyAsync(c->h_outb[b], c->d_outb[b], o.total, hipMemcpyDeviceToHost, c->cstream));
+    HIPCHK(c, hipStreamWaitEvent(c->cstream, B.ev_done, 0));
+    HIPCHK(c, hipMemcpyAsync(B.h, B.d, o.total, hipMemcpyDeviceToHost, c->cstream));
     HIPCHK(c, hipStreamSynchronize(c->cstream));
   }
   const int32_t* hc = (const int32_t*)(h + o.counts);
@@ -1620,20 +1547,20 @@ int orbx_batch_results_host(orbx_ctx* c, int previous, orbx_batch_view* v) {
   DeviceGuard _dg(c);
   if (!c || !v) return ORBX_ERR_INVALID_ARG;
   if (previous < 0 || previous >= orbx_ctx::kBlocks) return fail(c, ORBX_ERR_INVALID_ARG, "previous must be 0..3 (a ring of four result blocks)");
-  const int b = (c->blk + orbx_ctx::kBlocks - previous) % orbx_ctx::kBlocks;
-  if (c->nb[b] <= 0) return fail(c, ORBX_ERR_INVALID_ARG, previous ? "there is no batch that far back" : "no batch has been run");
-  const OutLayout& o = c->layoutb[b];
-  if (c->copy_pending[b]) {
-    HIPCHK(c, hipEventSynchronize(c->ev_copied[b]));
+  Block& B = c->blocks[(c->blk + orbx_ctx::kBlocks - previous) % orbx_ctx::kBlocks];
+  if (B.n <= 0) return fail(c, ORBX_ERR_INVALID_ARG, previous ? "there is no batch that far back" : "no batch has been run");
+  const OutLayout& o = B.layout;
+  if (B.copy_pending) {
+    HIPCHK(c, hipEventSynchronize(B.ev_copied));
   } else {
-    HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_done[b], 0));
-    HIPCHK(c, hipMemcpyAsync(c->h_outb[b], c->d_outb[b], o.total, hipMemcpyDeviceToHost, c->cstream));
-    HIPCHK(c, hipEventRecord(c->ev_copied[b], c->cstream));
-    c->copy_pending[b] = true;
-    HIPCHK(c, hipEventSynchronize(c->ev_copied[b]));
+    HIPCHK(c, hipStreamWaitEvent(c->cstream, B.ev_done, 0));
+    HIPCHK(c, hipMemcpyAsync(B.h, B.d, o.total, hipMemcpyDeviceToHost, c->cstream));
+    HIPCHK(c, hipEventRecord(B.ev_copied, c->cstream));
+    B.copy_pending = true;
+    HIPCHK(c, hipEventSynchronize(B.ev_copied));
   }
-  const uint8_t* h = c->h_outb[b];
-  const bool compact = c->copy_compact[b];  // (those sections of the mirror were not copied: NULL in the view)
+  const uint8_t* h = B.h;
+  const bool compact = B.copy_compact;  // (those sections of the mirror were not copied: NULL in the view)
   v->counts = (const int32_t*)(h + o.counts);
   v->keypoints = compact ? nullptr : (const orbx_keypoint*)(h + o.kp);
   v->keypoints16 = (const uint32_t*)(h + o.kp16);
@@ -1642,33 +1569,33 @@ int orbx_batch_results_host(orbx_ctx* c, int previous, orbx_batch_view* v) {
   v->responses = compact ? nullptr : (const float*)(h + o.resp);
   v->levels = compact ? nullptr : (const int32_t*)(h + o.level);
   v->descriptors = (const orbx_descriptor*)(h + o.desc);
-  v->slot_capacity = c->capb[b];
-  v->n = c->nb[b];
+  v->slot_capacity = B.cap;
+  v->n = B.n;
   return ORBX_OK;
 }
 
 namespace {
 int prefetch_block(orbx_ctx* c, bool compact) {
-  const int b = c->blk;
-  if (c->nb[b] <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been run");
-  const OutLayout& o = c->layoutb[b];
-  if (c->copy_pending[b]) {
-    if (compact || !c->copy_compact[b]) return ORBX_OK;
+  Block& B = c->blocks[c->blk];
+  if (B.n <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been run");
+  const OutLayout& o = B.layout;
+  if (B.copy_pending) {
+    if (compact || !B.copy_compact) return ORBX_OK;
     // a compact copy is on its way and the whole block is wanted after all: the other sections follow it
-    HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_done[b], 0));  // (host results: the compact part never was on this stream)
-    HIPCHK(c, hipMemcpyAsync(c->h_outb[b] + o.compact, c->d_outb[b] + o.compact, o.total - o.compact, hipMemcpyDeviceToHost,
+    HIPCHK(c, hipStreamWaitEvent(c->cstream, B.ev_done, 0));  // (host results: the compact part never was on this stream)
+    HIPCHK(c, hipMemcpyAsync(B.h + o.compact, B.d + o.compact, o.total - o.compact, hipMemcpyDeviceToHost,
                              c->cstream));
-    HIPCHK(c, hipEventRecord(c->ev_copied[b], c->cstream));
-    c->copy_compact[b] = false;
+    HIPCHK(c, hipEventRecord(B.ev_copied, c->cstream));
+    B.copy_compact = false;
     return ORBX_OK;
   }
   // (a block the describe kernel has written its compact record into -- orbx_set_host_results -- never gets here:
   // it is compact-pending from the moment the batch is enqueued)
-  HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_done[b], 0));
-  HIPCHK(c, hipMemcpyAsync(c->h_outb[b], c->d_outb[b], compact ? o.compact : o.total, hipMemcpyDeviceToHost, c->cstream));
-  HIPCHK(c, hipEventRecord(c->ev_copied[b], c->cstream));
-  c->copy_pending[b] = true;
-  c->copy_compact[b] = compact;
+  HIPCHK(c, hipStreamWaitEvent(c->cstream, B.ev_done, 0));
+  HIPCHK(c, hipMemcpyAsync(B.h, B.d, compact ? o.compact : o.total, hipMemcpyDeviceToHost, c->cstream));
+  HIPCHK(c, hipEventRecord(B.ev_copied, c->cstream));
+  B.copy_pending = true;
+  B.copy_compact = compact;
   return ORBX_OK;
 }
 }  // namespace
@@ -1691,7 +1618,7 @@ int orbx_batch_fetch_previous(orbx_ctx* c, int first, int n, int32_t* counts, or
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
   const int b = (c->blk + orbx_ctx::kBlocks - 1) % orbx_ctx::kBlocks;
-  if (c->nb[b] <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "there is no batch before the last one");
+  if (c->blocks[b].n <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "there is no batch before the last one");
   return fetch_block(c, b, first, n, counts, keypoints, orientations, descriptors, responses, levels, level_kps,
                      capacity);
 }
@@ -1716,8 +1643,9 @@ int orbx_bench_stage(orbx_ctx* c, int n_frames, int stage, int reps, float* avg_
   DeviceGuard _dg(c);
   if (!c || !avg_ms) return ORBX_ERR_INVALID_ARG;
   if (c->plan_w == 0) return fail(c, ORBX_ERR_INVALID_ARG, "run a batch first (no pyramid built)");
-  if (n_frames < 1 || n_frames > c->last_n || reps < 1) return fail(c, ORBX_ERR_INVALID_ARG, "n_frames/reps");
+  if (n_frames < 1 || n_frames > last_block(c).n || reps < 1) return fail(c, ORBX_ERR_INVALID_ARG, "n_frames/reps");
   const OrbxPlan& P = c->plan;
+  const Lane& L = cur_lane(c);
   hipStream_t s = c->stream;
   OrbxFastParams fp{c->p.threshold, c->p.n, c->p.nms_window / 2};
   HIPCHK(c, hipStreamSynchronize(s));
@@ -1727,15 +1655,14 @@ int orbx_bench_stage(orbx_ctx* c, int n_frames, int stage, int reps, float* avg_
     switch (stage) {
       case ORBX_STAGE_BLUR:
         if (!blur_enabled(c)) return fail(c, ORBX_ERR_INVALID_ARG, "blur is disabled in this context");
-        HIPCHK(c, launch_blur_auto(c->blur_impl, s, P, c->tm_blur, c->d_tiles_blur, c->blur_tiles_count, n_frames, c->d_pyr,
-                                   c->d_pyr_blur,
-                                   c->p.blur_levels == ORBX_BLUR_UPPER ? 1 : 0, c->p.blur_kind));
+        HIPCHK(c, launch_blur_auto(c->blur_impl, s, P, c->tm_blur, c->tiles[T_BLUR].d, c->tiles[T_BLUR].count, n_frames,
+                                   L.d_pyr, L.d_pyr_blur, c->p.blur_levels == ORBX_BLUR_UPPER ? 1 : 0, c->p.blur_kind));
         break;
       case ORBX_STAGE_FAST:
         HIPCHK(c, launch_fast_whole(c, s, n_frames, fp));
         break;
       case ORBX_STAGE_COMPACT:
-        HIPCHK(c, orbx_launch_compact(s, P, n_frames, c->d_mask, c->d_cand, c->d_cand_count, c->d_cand_total, 0));
+        HIPCHK(c, orbx_launch_compact(s, P, n_frames, L.d_mask, L.d_cand, L.d_cand_count, L.d_cand_total, 0));
         break;
       default:
         return fail(c, ORBX_ERR_INVALID_ARG, "stage not benchmarkable in isolation");
@@ -1767,12 +1694,12 @@ int orbx_fast_score(orbx_ctx* c, const uint8_t* image, int width, int height, in
   if ((st = make_bandmap(P, 0, &bm, &why)) != ORBX_OK) return fail(c, st, why);
   std::vector<OrbxTileDesc> t;
   build_fast_tiles(P, bm, 0, 1, &t);
-  if ((st = ensure(c, c->s_tiles, t.size() * sizeof(OrbxTileDesc))) != ORBX_OK) return st;
+  ENSURE(c, c->s_tiles, t.size() * sizeof(OrbxTileDesc));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(c->s_tiles.p, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
   const size_t npx = (size_t)width * height;
-  if ((st = ensure(c, c->s_u16, npx * 2)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->s_mask, (size_t)P.mask_words * 8)) != ORBX_OK) return st;
+  ENSURE(c, c->s_u16, npx * 2);
+  ENSURE(c, c->s_mask, (size_t)P.mask_words * 8);
   OrbxFastParams fp{threshold, n, 0};
   HIPCHK(c, orbx_launch_fast_nms(c->stream, (const OrbxTileDesc*)c->s_tiles.p, (int)t.size(), 1,
                                  (const uint8_t*)c->s_img_a.p, P.frame_bytes, P.mask_words, fp,
@@ -1786,9 +1713,8 @@ int orbx_fast_score(orbx_ctx* c, const uint8_t* image, int width, int height, in
 
 static int compact_and_fetch(orbx_ctx* c, const OrbxPlan& P, int nfeatures, orbx_keypoint* keypoints, int* count,
                              int* total) {
-  int st;
-  if ((st = ensure(c, c->s_kps, sizeof(orbx_keypoint) * (size_t)std::max(nfeatures, 1))) != ORBX_OK) return st;
-  if ((st = ensure(c, c->s_i32, 64)) != ORBX_OK) return st;
+  ENSURE(c, c->s_kps, sizeof(orbx_keypoint) * (size_t)std::max(nfeatures, 1));
+  ENSURE(c, c->s_i32, 64);
   int32_t* d_cnt = (int32_t*)c->s_i32.p;
   HIPCHK(c, orbx_launch_compact(c->stream, P, 1, (const unsigned long long*)c->s_mask.p, (orbx_keypoint*)c->s_kps.p,
                                 d_cnt, d_cnt + 1, 1));
@@ -1819,10 +1745,10 @@ int orbx_fast(orbx_ctx* c, const uint8_t* image, int width, int height, int stri
   if ((st = make_bandmap(P, nms_window / 2, &bm, &why)) != ORBX_OK) return fail(c, st, why);
   std::vector<OrbxTileDesc> t;
   build_fast_tiles(P, bm, 0, 1, &t);
-  if ((st = ensure(c, c->s_tiles, t.size() * sizeof(OrbxTileDesc))) != ORBX_OK) return st;
+  ENSURE(c, c->s_tiles, t.size() * sizeof(OrbxTileDesc));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(c->s_tiles.p, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-  if ((st = ensure(c, c->s_mask, (size_t)P.mask_words * 8)) != ORBX_OK) return st;
+  ENSURE(c, c->s_mask, (size_t)P.mask_words * 8);
   OrbxFastParams fp{threshold, n, nms_window / 2};
   // stage operator: exact totals are part of the contract -> no early exit
   HIPCHK(c, orbx_launch_fast_nms(c->stream, (const OrbxTileDesc*)c->s_tiles.p, (int)t.size(), 1,
@@ -1838,11 +1764,10 @@ int orbx_nms(orbx_ctx* c, const float* scores, int width, int height, int nms_wi
   if (!scores || !count || (!keypoints && nfeatures > 0) || nfeatures < 0 || width < 1 || height < 1 ||
       nms_window < 0 || nms_window / 2 > 3)
     return fail(c, ORBX_ERR_INVALID_ARG, "bad NMS() arguments");
-  int st;
   const size_t npx = (size_t)width * height;
-  if ((st = ensure(c, c->s_f32, npx * 4)) != ORBX_OK) return st;
+  ENSURE(c, c->s_f32, npx * 4);
   OrbxPlan P = flat_plan(width, height, nfeatures);
-  if ((st = ensure(c, c->s_mask, (size_t)P.mask_words * 8)) != ORBX_OK) return st;
+  ENSURE(c, c->s_mask, (size_t)P.mask_words * 8);
   HIPCHK(c, hipMemcpyAsync(c->s_f32.p, scores, npx * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, orbx_launch_nms_f32(c->stream, (const float*)c->s_f32.p, width, height, nms_window / 2, threshold,
                                 (unsigned long long*)c->s_mask.p, P.L[0].mask_wpr));
@@ -1867,9 +1792,9 @@ static int describe_stage(orbx_ctx* c, const uint8_t* image, int width, int heig
   int pitch;
   st = upload_flat(c, c->s_img_a, image, width, height, stride, &pitch);
   if (st != ORBX_OK) return st;
-  if ((st = ensure(c, c->s_kps, sizeof(orbx_keypoint) * (size_t)nkp)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->s_f32b, sizeof(float) * (size_t)nkp)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->s_desc, sizeof(orbx_descriptor) * (size_t)nkp)) != ORBX_OK) return st;
+  ENSURE(c, c->s_kps, sizeof(orbx_keypoint) * (size_t)nkp);
+  ENSURE(c, c->s_f32b, sizeof(float) * (size_t)nkp);
+  ENSURE(c, c->s_desc, sizeof(orbx_descriptor) * (size_t)nkp);
   HIPCHK(c, hipMemcpyAsync(c->s_kps.p, keypoints, sizeof(orbx_keypoint) * (size_t)nkp, hipMemcpyHostToDevice,
                            c->stream));
   if (angles_in)
@@ -1917,9 +1842,9 @@ int orbx_harris(orbx_ctx* c, const uint8_t* image, int width, int height, int st
   if (st != ORBX_OK) return st;
   std::vector<float> g((size_t)window * window);
   gaussian_kernel(window, -1.0f, g.data());
-  if ((st = ensure(c, c->s_kern, g.size() * 4)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->s_kps, sizeof(orbx_keypoint) * (size_t)nkp)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->s_f32b, sizeof(float) * (size_t)nkp)) != ORBX_OK) return st;
+  ENSURE(c, c->s_kern, g.size() * 4);
+  ENSURE(c, c->s_kps, sizeof(orbx_keypoint) * (size_t)nkp);
+  ENSURE(c, c->s_f32b, sizeof(float) * (size_t)nkp);
   HIPCHK(c, hipMemcpyAsync(c->s_kern.p, g.data(), g.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->s_kps.p, keypoints, sizeof(orbx_keypoint) * (size_t)nkp, hipMemcpyHostToDevice,
                            c->stream));
@@ -1940,12 +1865,12 @@ static int blur_stage(orbx_ctx* c, const uint8_t* image, int width, int height, 
   st = upload_flat(c, c->s_img_a, image, width, height, stride, &pitch);
   if (st != ORBX_OK) return st;
   OrbxPlan P = flat_plan(width, height, 0);
-  if ((st = ensure(c, c->s_img_b, (size_t)P.frame_bytes + 256)) != ORBX_OK) return st;
+  ENSURE(c, c->s_img_b, (size_t)P.frame_bytes + 256);
   OrbxTileMap tm;
   make_tilemap(P, ORBX_BLUR_TW, ORBX_BLUR_TH, true, &tm);
   std::vector<OrbxTileDesc> t;
   blur_tiles_for_impl(c->blur_impl, P, &t);
-  if ((st = ensure(c, c->s_tiles, t.size() * sizeof(OrbxTileDesc))) != ORBX_OK) return st;
+  ENSURE(c, c->s_tiles, t.size() * sizeof(OrbxTileDesc));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(c->s_tiles.p, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
   HIPCHK(c, launch_blur_auto(c->blur_impl, c->stream, P, tm, (const OrbxTileDesc*)c->s_tiles.p, (int)t.size(), 1,
@@ -1976,13 +1901,13 @@ static int conv_stage(orbx_ctx* c, const uint8_t* image, int width, int height, 
   if (wo < 1 || ho < 1) return fail(c, ORBX_ERR_INVALID_ARG, "image smaller than the kernel");
   if (reflect_pad && (width < K / 2 + 1 || height < K / 2 + 1))
     return fail(c, ORBX_ERR_INVALID_ARG, "image too small for REFLECT_101 padding");
-  int st, pitch;
+  int pitch;
   const int p = align_up(width, 64);
-  if ((st = ensure(c, c->s_img_a, (size_t)p * height + 256)) != ORBX_OK) return st;
+  ENSURE(c, c->s_img_a, (size_t)p * height + 256);
   HIPCHK(c, hipMemcpy2DAsync(c->s_img_a.p, p, image, stride, width, height, hipMemcpyHostToDevice, c->stream));
   pitch = p;
-  if ((st = ensure(c, c->s_img_b, (size_t)wo * ho + 256)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->s_kern, (size_t)K * K * 4)) != ORBX_OK) return st;
+  ENSURE(c, c->s_img_b, (size_t)wo * ho + 256);
+  ENSURE(c, c->s_kern, (size_t)K * K * 4);
   HIPCHK(c, hipMemcpyAsync(c->s_kern.p, kernel, (size_t)K * K * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, orbx_launch_conv2d(c->stream, (const uint8_t*)c->s_img_a.p, width, height, pitch,
                                (const float*)c->s_kern.p, K, reflect_pad, (uint8_t*)c->s_img_b.p, wo));
@@ -2031,9 +1956,9 @@ int orbx_build_pyramid_level(orbx_ctx* c, const uint8_t* image, int width, int h
   HIPCHK(c, hipMemcpy2DAsync(c->d_in, width, image, stride, width, height, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, launch_pyramid_auto(c, c->stream, 1, c->d_in, width, (size_t)width * height));
   if (blur_enabled(c))
-    HIPCHK(c, launch_blur_auto(c->blur_impl, c->stream, P, c->tm_blur, c->d_tiles_blur, c->blur_tiles_count, 1, c->d_pyr,
-                               c->d_pyr_blur,
-                               c->p.blur_levels == ORBX_BLUR_UPPER ? 1 : 0, c->p.blur_kind));
+    HIPCHK(c, launch_blur_auto(c->blur_impl, c->stream, P, c->tm_blur, c->tiles[T_BLUR].d, c->tiles[T_BLUR].count, 1,
+                               cur_lane(c).d_pyr, cur_lane(c).d_pyr_blur, c->p.blur_levels == ORBX_BLUR_UPPER ? 1 : 0,
+                               c->p.blur_kind));
   const OrbxLevel& L = P.L[level];
   HIPCHK(c, hipMemcpy2DAsync(dst, L.w, final_pyr(c) + L.img_off, L.pitch, L.w, L.h, hipMemcpyDeviceToHost,
                              c->stream));
@@ -2051,9 +1976,8 @@ int orbx_select_top(orbx_ctx* c, const float* responses, int n, int keep, int32_
   const int m = std::min(n, keep);
   *kept = m;
   if (m == 0) return ORBX_OK;
-  int st;
-  if ((st = ensure(c, c->s_f32b, sizeof(float) * (size_t)n)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->s_i32, sizeof(int32_t) * (size_t)n)) != ORBX_OK) return st;
+  ENSURE(c, c->s_f32b, sizeof(float) * (size_t)n);
+  ENSURE(c, c->s_i32, sizeof(int32_t) * (size_t)n);
   HIPCHK(c, hipMemcpyAsync(c->s_f32b.p, responses, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, orbx_launch_select_flat(c->stream, (const float*)c->s_f32b.p, n, keep, (int32_t*)c->s_i32.p));
   HIPCHK(c, hipMemcpyAsync(indices, c->s_i32.p, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
@@ -2073,13 +1997,12 @@ static int knn_host(orbx_ctx* c, const orbx_descriptor* query, int nq, const orb
   dist->assign((size_t)2 * nq, -1);
   match->assign((size_t)nq, -1);
   if (nq == 0) return ORBX_OK;
-  int st;
-  if ((st = ensure(c, c->m_q, sizeof(orbx_descriptor) * (size_t)nq)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->m_t, sizeof(orbx_descriptor) * (size_t)std::max(nt, 1))) != ORBX_OK) return st;
-  if ((st = ensure(c, c->m_idx, sizeof(int32_t) * 2 * (size_t)nq)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->m_dist, sizeof(int32_t) * 2 * (size_t)nq)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->m_match, sizeof(int32_t) * (size_t)nq)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->m_cnt, 64)) != ORBX_OK) return st;
+  ENSURE(c, c->m_q, sizeof(orbx_descriptor) * (size_t)nq);
+  ENSURE(c, c->m_t, sizeof(orbx_descriptor) * (size_t)std::max(nt, 1));
+  ENSURE(c, c->m_idx, sizeof(int32_t) * 2 * (size_t)nq);
+  ENSURE(c, c->m_dist, sizeof(int32_t) * 2 * (size_t)nq);
+  ENSURE(c, c->m_match, sizeof(int32_t) * (size_t)nq);
+  ENSURE(c, c->m_cnt, 64);
   const int32_t cnt[2] = {nq, nt};
   hipStream_t s = c->stream;
   HIPCHK(c, hipMemcpyAsync(c->m_cnt.p, cnt, sizeof(cnt), hipMemcpyHostToDevice, s));
@@ -2140,19 +2063,18 @@ int orbx_match_ratio(orbx_ctx* c, const orbx_descriptor* query, int nq, const or
 int orbx_batch_match_consecutive(orbx_ctx* c, double ratio) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
-  if (c->last_n < 2) return fail(c, ORBX_ERR_INVALID_ARG, "needs a batch of at least two frames");
+  const Block& B = last_block(c);
+  if (B.n < 2) return fail(c, ORBX_ERR_INVALID_ARG, "needs a batch of at least two frames");
   // the match buffers are ONE set per context: a match of the other lane's batch may still be writing them
-  if (c->lane_stream[1]) HIPCHK(c, lanes_sync(c));
-  const int n = c->last_n, cap = c->plan.out_cap > 0 ? c->plan.out_cap : 1;
+  if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
+  const int n = B.n, cap = B.cap;
   const size_t e = (size_t)(n - 1) * cap;
-  int st;
-  if ((st = ensure(c, c->m_idx, sizeof(int32_t) * 2 * e)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->m_dist, sizeof(int32_t) * 2 * e)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->m_match, sizeof(int32_t) * e)) != ORBX_OK) return st;
-  const OutLayout& o = c->out_layout;
-  const int32_t* counts = (const int32_t*)(c->d_out + o.counts);
-  const orbx_descriptor* desc = (const orbx_descriptor*)(c->d_out + o.desc);
-  hipStream_t s = c->last_stream ? c->last_stream : c->stream;
+  ENSURE(c, c->m_idx, sizeof(int32_t) * 2 * e);
+  ENSURE(c, c->m_dist, sizeof(int32_t) * 2 * e);
+  ENSURE(c, c->m_match, sizeof(int32_t) * e);
+  const int32_t* counts = (const int32_t*)(B.d + B.layout.counts);
+  const orbx_descriptor* desc = (const orbx_descriptor*)(B.d + B.layout.desc);
+  hipStream_t s = batch_stream(c);
   // pair p: query = frame p, train = frame p+1 (same arrays, shifted by one slot block)
   HIPCHK(c, orbx_launch_knn2(s, n - 1, cap, desc, counts, (size_t)cap, desc + cap, counts + 1, (size_t)cap, ratio,
                              (int32_t*)c->m_idx.p, (int32_t*)c->m_dist.p, (int32_t*)c->m_match.p, (size_t)cap));
@@ -2169,11 +2091,12 @@ int orbx_batch_match_fetch(orbx_ctx* c, int pair, int32_t* query_idx, int32_t* t
   if (!count || capacity < 0 || (capacity > 0 && (!query_idx || !train_idx)))
     return fail(c, ORBX_ERR_INVALID_ARG, "bad match output arguments");
   if (pair < 0 || pair >= c->match_pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last matched batch");
-  const int cap = c->plan.out_cap > 0 ? c->plan.out_cap : 1;
-  hipStream_t s = c->last_stream ? c->last_stream : c->stream;
+  const Block& B = last_block(c);
+  const int cap = B.cap;
+  hipStream_t s = batch_stream(c);
   int32_t nq = 0;
   std::vector<int32_t> vm((size_t)cap), vd((size_t)2 * cap);
-  HIPCHK(c, hipMemcpyAsync(&nq, (const int32_t*)(c->d_out + c->out_layout.counts) + pair, sizeof(int32_t),
+  HIPCHK(c, hipMemcpyAsync(&nq, (const int32_t*)(B.d + B.layout.counts) + pair, sizeof(int32_t),
                            hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(vm.data(), (const int32_t*)c->m_match.p + (size_t)pair * cap, sizeof(int32_t) * cap,
                            hipMemcpyDeviceToHost, s));
@@ -2226,8 +2149,7 @@ OrbxLkPyr lk_pyr(const LkGeom& g, const uint8_t* img, const uint8_t* deriv) {
 }
 // host image -> level 0, then pyrDown level by level
 int lk_upload(orbx_ctx* c, const LkGeom& g, DevBuf& b, const uint8_t* img, int stride) {
-  int st = ensure(c, b, g.img_bytes + 256);
-  if (st != ORBX_OK) return st;
+  ENSURE(c, b, g.img_bytes + 256);
   uint8_t* base = (uint8_t*)b.p;
   if (stride == g.w[0])
     HIPCHK(c, hipMemcpyAsync(base, img, (size_t)g.w[0] * g.h[0], hipMemcpyHostToDevice, c->stream));
@@ -2271,7 +2193,7 @@ int orbx_lk_track(orbx_ctx* c, const uint8_t* prev, int prev_stride, const uint8
   const int in = 1 - ip;
   c->lk_last = -1;  // invalid until this call has succeeded
   if ((st = lk_upload(c, g, c->lk_img[in], next, next_stride)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->lk_deriv, g.der_bytes + 256)) != ORBX_OK) return st;
+  ENSURE(c, c->lk_deriv, g.der_bytes + 256);
   const uint8_t* pimg = (const uint8_t*)c->lk_img[ip].p;
   for (int l = 0; l <= g.top; l++)
     HIPCHK(c, orbx_launch_lk_scharr(c->stream, pimg + g.img_off[l], g.w[l], g.h[l], g.pitch[l],
@@ -2280,7 +2202,7 @@ int orbx_lk_track(orbx_ctx* c, const uint8_t* prev, int prev_stride, const uint8
   const size_t o_out = sizeof(float) * 2 * (size_t)n, o_err = 2 * o_out, o_st = o_err + sizeof(float) * (size_t)n;
   const size_t io_bytes = o_st + (size_t)n;
   if (n > 0) {
-    if ((st = ensure(c, c->lk_io, io_bytes)) != ORBX_OK) return st;
+    ENSURE(c, c->lk_io, io_bytes);
     if (c->lk_host_bytes < io_bytes) {  // pinned staging: small pageable copies cost ~15 us each
       if (c->lk_host) (void)hipHostFree(c->lk_host);
       c->lk_host = nullptr;
@@ -2349,12 +2271,11 @@ int orbx_estimate_pose(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, 
       !pose_args_ok(K, prob, threshold, max_iters))
     return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
   const int cap = n > 0 ? n : 1;
-  int st;
-  if ((st = ensure(c, c->ph_in, sizeof(float) * 4 * (size_t)cap)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ph_pts, sizeof(OrbxPosePt) * (size_t)cap)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ph_n, sizeof(int32_t))) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ph_out, sizeof(OrbxPoseOut))) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ph_mask, (size_t)cap)) != ORBX_OK) return st;
+  ENSURE(c, c->ph_in, sizeof(float) * 4 * (size_t)cap);
+  ENSURE(c, c->ph_pts, sizeof(OrbxPosePt) * (size_t)cap);
+  ENSURE(c, c->ph_n, sizeof(int32_t));
+  ENSURE(c, c->ph_out, sizeof(OrbxPoseOut));
+  ENSURE(c, c->ph_mask, (size_t)cap);
   hipStream_t s = c->stream;
   float* d_p1 = (float*)c->ph_in.p;
   float* d_p2 = d_p1 + 2 * (size_t)cap;
@@ -2381,18 +2302,18 @@ int orbx_batch_pose_consecutive(orbx_ctx* c, const double* K, double prob, doubl
   if (c->match_pairs <= 0 || c->match_serial != c->batch_serial)
     return fail(c, ORBX_ERR_INVALID_ARG, "the last batch has not been matched (orbx_batch_match_consecutive)");
   // the pose buffers are ONE set per context, like the matcher's
-  if (c->lane_stream[1]) HIPCHK(c, lanes_sync(c));
-  const int npairs = c->match_pairs, cap = c->plan.out_cap > 0 ? c->plan.out_cap : 1;
+  if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
+  const Block& B = last_block(c);
+  const int npairs = c->match_pairs, cap = B.cap;
   const size_t e = (size_t)npairs * cap;
-  int st;
-  if ((st = ensure(c, c->pb_pts, sizeof(OrbxPosePt) * e)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->pb_n, sizeof(int32_t) * (size_t)npairs)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->pb_out, sizeof(OrbxPoseOut) * (size_t)npairs)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->pb_mask, e)) != ORBX_OK) return st;
-  const OutLayout& o = c->out_layout;
-  hipStream_t s = c->last_stream ? c->last_stream : c->stream;
-  HIPCHK(c, orbx_launch_pose_prep_batch(s, npairs, cap, (const int32_t*)(c->d_out + o.counts),
-                                        (const orbx_keypoint*)(c->d_out + o.kp), (const int32_t*)c->m_match.p, K,
+  ENSURE(c, c->pb_pts, sizeof(OrbxPosePt) * e);
+  ENSURE(c, c->pb_n, sizeof(int32_t) * (size_t)npairs);
+  ENSURE(c, c->pb_out, sizeof(OrbxPoseOut) * (size_t)npairs);
+  ENSURE(c, c->pb_mask, e);
+  const OutLayout& o = B.layout;
+  hipStream_t s = batch_stream(c);
+  HIPCHK(c, orbx_launch_pose_prep_batch(s, npairs, cap, (const int32_t*)(B.d + o.counts),
+                                        (const orbx_keypoint*)(B.d + o.kp), (const int32_t*)c->m_match.p, K,
                                         (OrbxPosePt*)c->pb_pts.p, (int32_t*)c->pb_n.p));
   HIPCHK(c, orbx_launch_pose_ransac(s, npairs, cap, (const OrbxPosePt*)c->pb_pts.p, (const int32_t*)c->pb_n.p, K, prob,
                                     threshold, max_iters, seed, (OrbxPoseOut*)c->pb_out.p, (uint8_t*)c->pb_mask.p));
@@ -2462,10 +2383,9 @@ int orbx_triangulate(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, in
       !finite_all(R, 9) || !finite_all(t, 3))
     return fail(c, ORBX_ERR_INVALID_ARG, "bad triangulation arguments");
   if (n == 0) return ORBX_OK;
-  int st;
-  if ((st = ensure(c, c->sh_in, sizeof(float) * 4 * (size_t)n)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->sh_xyz, sizeof(float) * 3 * (size_t)n)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->sh_valid, (size_t)n)) != ORBX_OK) return st;
+  ENSURE(c, c->sh_in, sizeof(float) * 4 * (size_t)n);
+  ENSURE(c, c->sh_xyz, sizeof(float) * 3 * (size_t)n);
+  ENSURE(c, c->sh_valid, (size_t)n);
   hipStream_t s = c->stream;
   float* d_p1 = (float*)c->sh_in.p;
   float* d_p2 = d_p1 + 2 * (size_t)n;
@@ -2493,10 +2413,9 @@ int orbx_estimate_scale(orbx_ctx* c, const float* prev_xyz, const uint8_t* prev_
   if ((size_t)m * 8 > ORBX_SCALE_LDS_MAX)
     return fail(c, ORBX_ERR_UNSUPPORTED, "more aligned points than the selection holds in LDS");
   // only the first m points of either list enter
-  int st;
-  if ((st = ensure(c, c->sh_xyz, sizeof(float) * 6 * (size_t)m)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->sh_valid, 2 * (size_t)m)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->sh_out, sizeof(OrbxScaleOut))) != ORBX_OK) return st;
+  ENSURE(c, c->sh_xyz, sizeof(float) * 6 * (size_t)m);
+  ENSURE(c, c->sh_valid, 2 * (size_t)m);
+  ENSURE(c, c->sh_out, sizeof(OrbxScaleOut));
   hipStream_t s = c->stream;
   float* d_prev = (float*)c->sh_xyz.p;
   float* d_cur = d_prev + 3 * (size_t)m;
@@ -2530,19 +2449,19 @@ int orbx_batch_scale_consecutive(orbx_ctx* c, const double* K) {
   if ((size_t)cap * 16 > ORBX_SCALE_LDS_MAX)
     return fail(c, ORBX_ERR_UNSUPPORTED, "more result slots per frame than the join holds in LDS");
   // the scale buffers are ONE set per context, like the pose buffers
-  if (c->lane_stream[1]) HIPCHK(c, lanes_sync(c));
+  if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
   const size_t e = (size_t)npairs * cap;
-  int st;
-  if ((st = ensure(c, c->sb_xyz, sizeof(float) * 3 * e)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->sb_valid, e)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->sb_mq, sizeof(int32_t) * e)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->sb_mt, sizeof(int32_t) * e)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->sb_n, sizeof(int32_t) * (size_t)npairs)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->sb_out, sizeof(OrbxScaleOut) * (size_t)npairs)) != ORBX_OK) return st;
-  const OutLayout& o = c->out_layout;
+  ENSURE(c, c->sb_xyz, sizeof(float) * 3 * e);
+  ENSURE(c, c->sb_valid, e);
+  ENSURE(c, c->sb_mq, sizeof(int32_t) * e);
+  ENSURE(c, c->sb_mt, sizeof(int32_t) * e);
+  ENSURE(c, c->sb_n, sizeof(int32_t) * (size_t)npairs);
+  ENSURE(c, c->sb_out, sizeof(OrbxScaleOut) * (size_t)npairs);
+  const Block& B = last_block(c);
+  const OutLayout& o = B.layout;
   hipStream_t s = c->pose_stream;
-  HIPCHK(c, orbx_launch_triangulate_batch(s, npairs, cap, (const int32_t*)(c->d_out + o.counts),
-                                          (const orbx_keypoint*)(c->d_out + o.kp), (const int32_t*)c->m_match.p,
+  HIPCHK(c, orbx_launch_triangulate_batch(s, npairs, cap, (const int32_t*)(B.d + o.counts),
+                                          (const orbx_keypoint*)(B.d + o.kp), (const int32_t*)c->m_match.p,
                                           (const OrbxPoseOut*)c->pb_out.p, K, (float*)c->sb_xyz.p,
                                           (uint8_t*)c->sb_valid.p, (int32_t*)c->sb_mq.p, (int32_t*)c->sb_mt.p,
                                           (int32_t*)c->sb_n.p));
@@ -2690,17 +2609,16 @@ int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const 
   int groups = std::min(n_windows, ORBX_BA_MAX_GROUPS);
   groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)groups, ORBX_BA_WS_BUDGET / per_group));
   const size_t noff = (size_t)n_windows + 1;
-  int st;
-  if ((st = ensure(c, c->ba_off, sizeof(int32_t) * 3 * noff)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ba_poses, sizeof(double) * 6 * tp)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ba_points, sizeof(double) * 3 * tn)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ba_rows, sizeof(int32_t) * rows.size())) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ba_opose, tm)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ba_oxy, sizeof(double) * 2 * tm)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ba_wp, sizeof(double) * ORBX_BA_WS_POINT * (size_t)cap * groups)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ba_wo, sizeof(double) * ORBX_BA_WS_OBS * (size_t)ocap * groups)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ba_slot, 8 * (size_t)cap * groups)) != ORBX_OK) return st;
-  if ((st = ensure(c, c->ba_out, sizeof(orbx_ba_summary) * (size_t)n_windows)) != ORBX_OK) return st;
+  ENSURE(c, c->ba_off, sizeof(int32_t) * 3 * noff);
+  ENSURE(c, c->ba_poses, sizeof(double) * 6 * tp);
+  ENSURE(c, c->ba_points, sizeof(double) * 3 * tn);
+  ENSURE(c, c->ba_rows, sizeof(int32_t) * rows.size());
+  ENSURE(c, c->ba_opose, tm);
+  ENSURE(c, c->ba_oxy, sizeof(double) * 2 * tm);
+  ENSURE(c, c->ba_wp, sizeof(double) * ORBX_BA_WS_POINT * (size_t)cap * groups);
+  ENSURE(c, c->ba_wo, sizeof(double) * ORBX_BA_WS_OBS * (size_t)ocap * groups);
+  ENSURE(c, c->ba_slot, 8 * (size_t)cap * groups);
+  ENSURE(c, c->ba_out, sizeof(orbx_ba_summary) * (size_t)n_windows);
   hipStream_t s = c->stream;
   int32_t* d_off = (int32_t*)c->ba_off.p;
   HIPCHK(c, hipMemcpyAsync(d_off, pose_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
