@@ -523,6 +523,63 @@ int orbx_bundle_adjust_batch(orbx_ctx* ctx, const double* K, int n_windows, cons
                              const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
                              double huber_delta, int max_iters, orbx_ba_summary* summaries);
 
+/* ---- next row: Shi-Tomasi corners --------------------------------------
+ * Replaces
+ *   cv::goodFeaturesToTrack(imgs_window[0], keypoints0, 2000, 0.01, 8)    src/with_bundle_adjustment.cpp:586-593
+ *   the same call                                                         src/t.cpp:285
+ * with the arguments the reference leaves at their defaults fixed: no mask, blockSize 3, gradientSize 3, minimum
+ * eigenvalue (no Harris).  OpenCV is absent from the image this library was written in: the algorithm keeps OpenCV
+ * 4.x's structure (cornerMinEigenVal, threshold at qualityLevel * max, 3x3 dilate maxima, sort, minimum-distance
+ * grid) and fixes every choice OpenCV leaves to its SIMD build (rules 1-6); parity with OpenCV
+ * is unpinned.  Corners are (float)x, (float)y pairs in acceptance order (strongest first; equal responses: the larger
+ * row-major index first), ASSIGN semantics.
+ * Arguments: 8 <= width <= max_width, 8 <= height <= max_height; quality_level finite, in (0, 1]; min_distance finite,
+ * >= 0 (below 1: no suppression); anything else is ORBX_ERR_INVALID_ARG.  min_distance above
+ * ORBX_GFTT_MAX_MIN_DISTANCE (the cell arithmetic is 32-bit; no frame a context accepts is a quarter as wide) is
+ * ORBX_ERR_UNSUPPORTED.  max_corners <= 0: no limit (host entry only).  On any error nothing is written but *count
+ * of ORBX_ERR_CAPACITY. */
+#define ORBX_GFTT_MAX_MIN_DISTANCE 65536.0
+/* cv::cornerMinEigenVal(image, eig, 3, 3) (the response map inside goodFeaturesToTrack,
+ * src/with_bundle_adjustment.cpp:592): host image in, eig = height x width floats, tightly packed. */
+int orbx_corner_min_eigen_val(orbx_ctx* ctx, const uint8_t* image, int width, int height, int stride, float* eig);
+/* cv::goodFeaturesToTrack on one host image (src/with_bundle_adjustment.cpp:586-593, src/t.cpp:285).  *count =
+ * corners found; if it exceeds `capacity`, ORBX_ERR_CAPACITY is returned, *count is the capacity required and
+ * corners_xy is not written.  Runs as a good-features batch of one frame: it replaces the results of the last
+ * orbx_good_features_batch_device. */
+int orbx_good_features_to_track(orbx_ctx* ctx, const uint8_t* image, int width, int height, int stride,
+                                int max_corners, double quality_level, double min_distance, float* corners_xy,
+                                int capacity, int* count);
+/* The same for `n` frames in device memory, asynchronously on the context's stream (or `stream`, a hipStream_t):
+ * the frame, stride and alignment rules of orbx_detect_and_compute_batch_device hold unchanged, and
+ * max_corners >= 1.  The results go to a block of their OWN -- counts and min(max_corners, (width - 2)(height - 2))
+ * corner slots per frame -- so the last ORB batch, its matches, poses and scales stay as they are.
+ * src/with_bundle_adjustment.cpp:586-593
+ * Workspace: 16 bytes per pixel and frame (response map, candidate pool for EVERY interior pixel, cell grid),
+ * allocated at the first good-features call for min(max_batch, frames that fit the limit) frames of max_width x
+ * max_height and freed by orbx_destroy; a batch of more frames runs in slices, one after the other on the same
+ * stream, with identical results.  A caller's stream is used during the call only: later calls, fetches and
+ * orbx_destroy wait for an event recorded behind the batch, so the stream may be destroyed once the call returns. */
+int orbx_good_features_batch_device(orbx_ctx* ctx, const void* d_frames, int n, int width, int height, int row_stride,
+                                    size_t frame_stride, int max_corners, double quality_level, double min_distance,
+                                    void* stream);
+/* The bound of that workspace in bytes (default ORBX_GFTT_WORKSPACE_DEFAULT; 0 restores it).  One frame of
+ * max_width x max_height is always granted.  Waits for the good-features batch in flight and releases the
+ * workspace; the next call allocates the new size.  src/with_bundle_adjustment.cpp:592 */
+#define ORBX_GFTT_WORKSPACE_DEFAULT ((size_t)1 << 30)
+int orbx_good_features_workspace_limit(orbx_ctx* ctx, size_t bytes);
+/* Device-side results of the last good-features batch, for consumers that stay on the GPU (valid until the next
+ * good-features call; written on the batch's stream). */
+typedef struct {
+  const int32_t* counts;   /* [n] */
+  const float* corners_xy; /* [n][slot_capacity][2]; the first counts[f] of frame f are valid */
+  int32_t slot_capacity;
+  int32_t n;
+} orbx_good_features_view;
+int orbx_good_features_results_device(orbx_ctx* ctx, orbx_good_features_view* view);
+/* Waits for the last good-features batch and copies frames [first, first + n): counts (n entries) and
+ * corners_xy (n x slot_capacity x 2 floats, the view's stride; may be NULL).  src/with_bundle_adjustment.cpp:586-593 */
+int orbx_good_features_fetch(orbx_ctx* ctx, int first, int n, int32_t* counts, float* corners_xy);
+
 #ifdef __cplusplus
 }
 #endif

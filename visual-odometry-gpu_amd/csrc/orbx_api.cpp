@@ -217,6 +217,16 @@ struct orbx_ctx {
   // bundle adjustment (orbx_ba.hip): the staged windows (offsets, parameter blocks, CSR observations), the
   // workgroups' workspaces and the summaries; grown on first use
   DevBuf ba_off, ba_poses, ba_points, ba_rows, ba_opose, ba_oxy, ba_wp, ba_wo, ba_slot, ba_out;
+  // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames (response maps | key pools | cell grids
+  // | per-frame maximum and candidate count), allocated on first use and bounded by gf_ws_limit; the staged host
+  // image of the one-frame entries; and the entry's OWN result block (counts | corners), untouched by the ORB path
+  DevBuf gf_ws, gf_img, gf_res;
+  size_t gf_ws_limit = ORBX_GFTT_WORKSPACE_DEFAULT;
+  int gf_n = 0, gf_cap = 0;  // frames and slots per frame of the last good-features batch (gf_n == 0: none)
+  // the stream the last good-features call ran on, kept for COMPARISON only (a caller's stream may be gone by the
+  // next call), and the event recorded behind that call's work: what later calls, fetches and orbx_destroy wait for
+  hipStream_t gf_stream = nullptr;
+  hipEvent_t gf_ev = nullptr;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -1108,7 +1118,11 @@ void orbx_destroy(orbx_ctx* c) {
                   &c->pb_mask, &c->ph_in, &c->ph_pts, &c->ph_n, &c->ph_out, &c->ph_mask, &c->sb_xyz, &c->sb_valid,
                   &c->sb_mq, &c->sb_mt, &c->sb_n, &c->sb_out, &c->sh_in, &c->sh_xyz, &c->sh_valid, &c->sh_out,
                   &c->ba_off, &c->ba_poses, &c->ba_points, &c->ba_rows, &c->ba_opose, &c->ba_oxy, &c->ba_wp, &c->ba_wo,
-                  &c->ba_slot, &c->ba_out};
+                  &c->ba_slot, &c->ba_out, &c->gf_ws, &c->gf_img, &c->gf_res};
+  if (c->gf_ev) {
+    (void)hipEventSynchronize(c->gf_ev);
+    (void)hipEventDestroy(c->gf_ev);
+  }
   if (c->lk_host) (void)hipHostFree(c->lk_host);
   for (DevBuf* b : sb)
     if (b->p) (void)hipFree(b->p);
@@ -2650,6 +2664,270 @@ int orbx_bundle_adjust(orbx_ctx* c, const double* K, int n_poses, double* poses6
   const int32_t po[2] = {0, n_poses}, pt[2] = {0, n_points}, ob[2] = {0, n_obs};
   return orbx_bundle_adjust_batch(c, K, 1, po, poses6, pt, points3, ob, obs_point, obs_pose, obs_xy, huber_delta,
                                   max_iters, summary);
+}
+
+}  // extern "C"
+
+// ---- Shi-Tomasi corners (next row) ------------------------
+namespace {
+
+// the sections of the workspace for m frames of w x h with a cell grid of grid_stride words per frame
+struct GfLayout {
+  size_t map, keys, grid, cnt, total, pool, grid_stride;
+};
+GfLayout gf_layout(int m, int w, int h, size_t grid_stride) {
+  GfLayout o;
+  const size_t px = (size_t)w * h;
+  o.pool = (size_t)(w - 2) * (h - 2);
+  o.grid_stride = grid_stride;
+  o.map = 0;
+  o.keys = align_up_sz(sizeof(float) * px * m, 256);
+  o.grid = align_up_sz(o.keys + sizeof(unsigned long long) * o.pool * m, 256);
+  o.cnt = align_up_sz(o.grid + sizeof(uint32_t) * grid_stride * m, 256);
+  o.total = o.cnt + 2 * sizeof(uint32_t) * (size_t)m;  // maxima, then candidate counts
+  return o;
+}
+// the largest grid of a w x h frame: w * h cells of one slot (cell 1) or, from cell 2 on, at most
+// ceil(w / 2) * ceil(h / 2) cells of four -- both within (w + 1)(h + 1) words
+size_t gf_grid_bound(int w, int h) { return (size_t)(w + 1) * (h + 1); }
+
+struct GfArgs {
+  int cap, suppress, cell, gw, gh, slots;
+  double quality, min_distance;
+};
+
+int gf_check_params(orbx_ctx* c, double quality, double min_distance) {
+  if (!std::isfinite(quality) || !(quality > 0.0) || quality > 1.0)
+    return fail(c, ORBX_ERR_INVALID_ARG, "quality_level must be finite, in (0, 1]");
+  if (!std::isfinite(min_distance) || min_distance < 0.0)
+    return fail(c, ORBX_ERR_INVALID_ARG, "min_distance must be finite, >= 0");
+  if (min_distance > ORBX_GFTT_MAX_MIN_DISTANCE)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "min_distance above ORBX_GFTT_MAX_MIN_DISTANCE");
+  return ORBX_OK;
+}
+
+GfArgs gf_args(int w, int h, int max_corners, double quality, double min_distance) {
+  GfArgs a;
+  const long long pool = (long long)(w - 2) * (h - 2);
+  a.cap = (int)(max_corners > 0 ? std::min<long long>(max_corners, pool) : pool);
+  a.quality = quality;
+  a.min_distance = min_distance;
+  a.suppress = min_distance >= 1.0;
+  a.cell = a.suppress ? (int)std::nearbyint(min_distance) : 1;  // cvRound: half to even (default rounding mode)
+  a.gw = (w + a.cell - 1) / a.cell;
+  a.gh = (h + a.cell - 1) / a.cell;
+  a.slots = a.cell == 1 ? 1 : 4;
+  return a;
+}
+
+// waits for the good-features work enqueued so far, on whatever stream it ran: through the event recorded behind it,
+// never through the stream itself (a caller's stream need not outlive its batch's end)
+int gf_wait(orbx_ctx* c) {
+  if (c->gf_ev) HIPCHK(c, hipEventSynchronize(c->gf_ev));
+  return ORBX_OK;
+}
+
+// a good-features call on stream s: earlier good-features work on another stream has to be done (one workspace)
+int gf_enter(orbx_ctx* c, hipStream_t s) {
+  if (!c->gf_ev) HIPCHK(c, hipEventCreateWithFlags(&c->gf_ev, hipEventDisableTiming));
+  if (c->gf_stream != s) {
+    const int st = gf_wait(c);
+    if (st != ORBX_OK) return st;
+  }
+  c->gf_stream = s;
+  return ORBX_OK;
+}
+
+// records the event behind whatever a good-features call has enqueued on s, on every way out of the call
+struct GfMark {
+  orbx_ctx* c;
+  hipStream_t s;
+  ~GfMark() {
+    if (c->gf_ev) (void)hipEventRecord(c->gf_ev, s);
+  }
+};
+
+// the workspace: allocated once, for as many frames of the largest size as the limit holds (at least one, at most
+// max_batch)
+int gf_workspace(orbx_ctx* c) {
+  if (c->gf_ws.p) return ORBX_OK;
+  const int mw = c->p.max_width, mh = c->p.max_height;
+  const size_t one = gf_layout(1, mw, mh, gf_grid_bound(mw, mh)).total + 1024;
+  const size_t frames = std::min<size_t>(std::max<size_t>(c->gf_ws_limit / one, 1), (size_t)c->p.max_batch);
+  ENSURE(c, c->gf_ws, gf_layout((int)frames, mw, mh, gf_grid_bound(mw, mh)).total + 1024);
+  return ORBX_OK;
+}
+
+// frames of w x h per slice
+int gf_slice_frames(const orbx_ctx* c, int n, int w, int h, size_t grid_stride) {
+  const size_t one = gf_layout(1, w, h, grid_stride).total + 1024;  // (the sections' alignment: < 1024 bytes)
+  const size_t fit = std::max<size_t>((c->gf_ws.bytes - 1024) / one, 1);
+  const int m = (int)std::min<size_t>(fit, (size_t)n);
+  const int slices = (n + m - 1) / m;
+  return (n + slices - 1) / slices;  // even slices
+}
+
+// enqueues the three stages for n device frames; the results go to gf_res (counts | corners)
+int gf_run(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row_stride, size_t frame_stride,
+           const GfArgs& a, hipStream_t s) {
+  int st = gf_enter(c, s);
+  if (st != ORBX_OK) return st;
+  const GfMark mark{c, s};
+  c->gf_n = 0;  // (a failed call leaves no "last batch")
+  if ((st = gf_workspace(c)) != ORBX_OK) return st;
+  const size_t o_corners = align_up_sz(sizeof(int32_t) * (size_t)n, 256);
+  const size_t res_bytes = o_corners + sizeof(float) * 2 * (size_t)a.cap * n;
+  if (c->gf_res.p && c->gf_res.bytes < res_bytes && (st = gf_wait(c)) != ORBX_OK) return st;  // (still written?)
+  ENSURE(c, c->gf_res, res_bytes);
+  const size_t grid_stride = a.suppress ? (size_t)a.gw * a.gh * a.slots : 0;
+  const int per = gf_slice_frames(c, n, w, h, grid_stride);
+  int32_t* d_counts = (int32_t*)c->gf_res.p;
+  float* d_corners = (float*)((uint8_t*)c->gf_res.p + o_corners);
+  for (int f0 = 0; f0 < n; f0 += per) {
+    const int m = std::min(per, n - f0);
+    const GfLayout L = gf_layout(m, w, h, grid_stride);
+    uint8_t* ws = (uint8_t*)c->gf_ws.p;
+    uint32_t* d_max = (uint32_t*)(ws + L.cnt);
+    int32_t* d_ncand = (int32_t*)(d_max + m);
+    HIPCHK(c, hipMemsetAsync(d_max, 0, 2 * sizeof(uint32_t) * (size_t)m, s));
+    if (a.suppress) HIPCHK(c, hipMemsetAsync(ws + L.grid, 0xff, sizeof(uint32_t) * grid_stride * m, s));
+    HIPCHK(c, orbx_launch_gftt_response(s, d_frames + frame_stride * (size_t)f0, m, w, h, row_stride, frame_stride,
+                                        (float*)(ws + L.map), d_max));
+    HIPCHK(c, orbx_launch_gftt_candidates(s, (const float*)(ws + L.map), m, w, h, d_max, a.quality,
+                                          (unsigned long long*)(ws + L.keys), L.pool, d_ncand));
+    HIPCHK(c, orbx_launch_gftt_select(s, m, w, (unsigned long long*)(ws + L.keys), L.pool, d_ncand, a.min_distance,
+                                      a.cell, a.gw, a.gh, a.slots, (uint32_t*)(ws + L.grid), grid_stride, a.cap,
+                                      d_counts + f0, d_corners + (size_t)2 * a.cap * f0));
+  }
+  c->gf_n = n;
+  c->gf_cap = a.cap;
+  return ORBX_OK;
+}
+
+// a host image, tightly packed, in gf_img on the context's stream
+int gf_upload(orbx_ctx* c, const uint8_t* image, int w, int h, int stride) {
+  int st = gf_enter(c, c->stream);
+  if (st != ORBX_OK) return st;
+  const GfMark mark{c, c->stream};
+  ENSURE(c, c->gf_img, (size_t)w * h);
+  HIPCHK(c, hipMemcpy2DAsync(c->gf_img.p, w, image, stride, w, h, hipMemcpyHostToDevice, c->stream));
+  return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_corner_min_eigen_val(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, float* eig) {
+  DeviceGuard _dg(c);
+  int st = check_image(c, image, width, height, stride);
+  if (st != ORBX_OK) return st;
+  if (!eig) return fail(c, ORBX_ERR_INVALID_ARG, "eig is NULL");
+  if ((st = gf_upload(c, image, width, height, stride)) != ORBX_OK) return st;
+  const GfMark mark{c, c->stream};
+  if ((st = gf_workspace(c)) != ORBX_OK) return st;
+  const GfLayout L = gf_layout(1, width, height, 0);
+  uint8_t* ws = (uint8_t*)c->gf_ws.p;
+  HIPCHK(c, hipMemsetAsync(ws + L.cnt, 0, 2 * sizeof(uint32_t), c->stream));
+  HIPCHK(c, orbx_launch_gftt_response(c->stream, (const uint8_t*)c->gf_img.p, 1, width, height, width,
+                                      (size_t)width * height, (float*)(ws + L.map), (uint32_t*)(ws + L.cnt)));
+  HIPCHK(c, hipMemcpyAsync(eig, ws + L.map, sizeof(float) * (size_t)width * height, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ORBX_OK;
+}
+
+int orbx_good_features_to_track(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, int max_corners,
+                                double quality_level, double min_distance, float* corners_xy, int capacity,
+                                int* count) {
+  DeviceGuard _dg(c);
+  int st = check_image(c, image, width, height, stride);
+  if (st != ORBX_OK) return st;
+  if (!count || capacity < 0 || (capacity > 0 && !corners_xy))
+    return fail(c, ORBX_ERR_INVALID_ARG, "count / corners_xy is NULL or capacity < 0");
+  if ((st = gf_check_params(c, quality_level, min_distance)) != ORBX_OK) return st;
+  if ((st = gf_upload(c, image, width, height, stride)) != ORBX_OK) return st;
+  const GfArgs a = gf_args(width, height, max_corners, quality_level, min_distance);
+  if ((st = gf_run(c, (const uint8_t*)c->gf_img.p, 1, width, height, width, (size_t)width * height, a, c->stream)) !=
+      ORBX_OK)
+    return st;
+  int32_t found = 0;
+  HIPCHK(c, hipMemcpyAsync(&found, c->gf_res.p, sizeof(found), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (found > capacity) {
+    *count = found;
+    return fail(c, ORBX_ERR_CAPACITY, "corners_xy is too small");
+  }
+  if (found > 0)
+    HIPCHK(c, hipMemcpy(corners_xy, (const uint8_t*)c->gf_res.p + align_up_sz(sizeof(int32_t), 256),
+                        sizeof(float) * 2 * (size_t)found, hipMemcpyDeviceToHost));
+  *count = found;
+  return ORBX_OK;
+}
+
+int orbx_good_features_batch_device(orbx_ctx* c, const void* d_frames, int n, int width, int height, int row_stride,
+                                    size_t frame_stride, int max_corners, double quality_level, double min_distance,
+                                    void* stream) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!d_frames) return fail(c, ORBX_ERR_INVALID_ARG, "d_frames is NULL");
+  if (n < 1 || n > c->p.max_batch) return fail(c, ORBX_ERR_INVALID_ARG, "n outside [1, max_batch]");
+  if (width < 8 || height < 8 || width > c->p.max_width || height > c->p.max_height)
+    return fail(c, ORBX_ERR_INVALID_ARG, "image size outside [8, max_width] x [8, max_height]");
+  if (row_stride < width) return fail(c, ORBX_ERR_INVALID_ARG, "row_stride < width");
+  if (frame_stride < (size_t)row_stride * (size_t)(height - 1) + (size_t)width)
+    return fail(c, ORBX_ERR_INVALID_ARG, "frame_stride smaller than a frame");
+  // the kernel addresses the bytes of one frame with 32-bit offsets (a buffer descriptor per frame)
+  if ((unsigned long long)row_stride * (unsigned long long)(height - 1) + (unsigned long long)width > 0x7fffffffull)
+    return fail(c, ORBX_ERR_INVALID_ARG, "row_stride * (height - 1) + width exceeds 2^31 - 1");
+  if (max_corners < 1) return fail(c, ORBX_ERR_INVALID_ARG, "max_corners < 1");
+  const int st = gf_check_params(c, quality_level, min_distance);
+  if (st != ORBX_OK) return st;
+  return gf_run(c, (const uint8_t*)d_frames, n, width, height, row_stride, frame_stride,
+                gf_args(width, height, max_corners, quality_level, min_distance),
+                stream ? (hipStream_t)stream : c->stream);
+}
+
+int orbx_good_features_workspace_limit(orbx_ctx* c, size_t bytes) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  const int st = gf_wait(c);
+  if (st != ORBX_OK) return st;
+  if (c->gf_ws.p) {
+    HIPCHK(c, hipFree(c->gf_ws.p));
+    c->gf_ws = DevBuf{};
+  }
+  c->gf_ws_limit = bytes ? bytes : ORBX_GFTT_WORKSPACE_DEFAULT;
+  return ORBX_OK;
+}
+
+int orbx_good_features_results_device(orbx_ctx* c, orbx_good_features_view* v) {
+  DeviceGuard _dg(c);
+  if (!c || !v) return ORBX_ERR_INVALID_ARG;
+  if (c->gf_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no good-features batch has run");
+  v->counts = (const int32_t*)c->gf_res.p;
+  v->corners_xy = (const float*)((const uint8_t*)c->gf_res.p + align_up_sz(sizeof(int32_t) * (size_t)c->gf_n, 256));
+  v->slot_capacity = c->gf_cap;
+  v->n = c->gf_n;
+  return ORBX_OK;
+}
+
+int orbx_good_features_fetch(orbx_ctx* c, int first, int n, int32_t* counts, float* corners_xy) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (c->gf_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no good-features batch has run");
+  if (!counts || first < 0 || n < 1 || first >= c->gf_n || n > c->gf_n - first)
+    return fail(c, ORBX_ERR_INVALID_ARG, "counts is NULL or [first, first + n) outside the batch");
+  const int st = gf_wait(c);
+  if (st != ORBX_OK) return st;
+  const uint8_t* res = (const uint8_t*)c->gf_res.p;
+  HIPCHK(c, hipMemcpy(counts, res + sizeof(int32_t) * (size_t)first, sizeof(int32_t) * (size_t)n,
+                      hipMemcpyDeviceToHost));
+  if (corners_xy) {
+    const size_t row = sizeof(float) * 2 * (size_t)c->gf_cap;
+    HIPCHK(c, hipMemcpy(corners_xy, res + align_up_sz(sizeof(int32_t) * (size_t)c->gf_n, 256) + row * first, row * n,
+                        hipMemcpyDeviceToHost));
+  }
+  return ORBX_OK;
 }
 
 }  // extern "C"

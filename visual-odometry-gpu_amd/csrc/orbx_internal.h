@@ -188,3 +188,16 @@ hipError_t orbx_launch_ba(hipStream_t s, int n_windows, int groups, int max_iter
                           double* d_poses, double* d_points, const int32_t* d_rows, const uint8_t* d_obs_pose,
                           const double* d_obs_xy, int cap, int ocap, double* d_ws_pt, double* d_ws_obs,
                           unsigned long long* d_ws_slot, void* d_out);
+
+// ---- Shi-Tomasi corners (orbx_gftt.hip): n frames per launch, every array per frame ---------
+// d_map: w * h floats; d_max: the largest response as a bit pattern (zeroed by the caller); d_keys: `pool` =
+// (w - 2)(h - 2) keys; d_ncand: candidates (zeroed by the caller); d_grid: grid_stride >= gw * gh * slots words, all
+// 0xff (min_distance >= 1 only); cap: result slots
+hipError_t orbx_launch_gftt_response(hipStream_t s, const uint8_t* d_frames, int n, int w, int h, int row_stride,
+                                     size_t frame_stride, float* d_map, uint32_t* d_max);
+hipError_t orbx_launch_gftt_candidates(hipStream_t s, const float* d_map, int n, int w, int h, const uint32_t* d_max,
+                                       double quality, unsigned long long* d_keys, size_t pool, int32_t* d_ncand);
+hipError_t orbx_launch_gftt_select(hipStream_t s, int n, int w, unsigned long long* d_keys, size_t pool,
+                                   const int32_t* d_ncand, double min_distance, int cell, int gw, int gh, int slots,
+                                   uint32_t* d_grid, size_t grid_stride, int cap, int32_t* d_counts,
+                                   float* d_corners);

@@ -929,4 +929,72 @@ inline bool run_bundle_adjustment(std::vector<Pose4x4>& pose_window, const doubl
   return true;
 }
 
+// ---- Shi-Tomasi corners (next row) ----------------------------------
+// cv::goodFeaturesToTrack(image, corners, maxCorners, qualityLevel, minDistance)
+//                                           src/with_bundle_adjustment.cpp:586-593, src/t.cpp:285
+// (no mask, blockSize 3, gradientSize 3, minimum eigenvalue: the defaults the reference leaves in place).
+// The handle owns the context, hence the workspace of the detector, as LKTracker owns its pyramids.
+class CornerDetector {
+ public:
+  CornerDetector() : ctx_([] {
+    orbx_params p = detail::gpu_defaults();
+    p.nlevels = 1;
+    return std::make_shared<detail::Ctx>(p);
+  }()) {}
+  orbx_ctx* get(int w, int h) { return ctx_->get(w, h); }
+
+ private:
+  std::shared_ptr<detail::Ctx> ctx_;
+};
+
+// corners are ASSIGNED; maxCorners <= 0: no limit
+inline void goodFeaturesToTrack(CornerDetector& handle, const Image& image, std::vector<Point2f>& corners,
+                                int maxCorners, double qualityLevel, double minDistance) {
+  static_assert(sizeof(Point2f) == 2 * sizeof(float), "point layout");
+  orbx_ctx* c = handle.get(image.width, image.height);
+  int count = 0;
+  // sized for the usual case first; ORBX_ERR_CAPACITY reports what an unlimited call needs
+  size_t capacity = maxCorners > 0 ? (size_t)maxCorners : 4096;
+  for (;;) {
+    corners.resize(capacity);
+    const int st = orbx_good_features_to_track(c, image.data, image.width, image.height, image.stride, maxCorners,
+                                               qualityLevel, minDistance, reinterpret_cast<float*>(corners.data()),
+                                               (int)capacity, &count);
+    if (st == ORBX_ERR_CAPACITY && (size_t)count > capacity) {
+      capacity = (size_t)count;
+      continue;
+    }
+    if (st != ORBX_OK) corners.clear();
+    detail::check(c, st, "goodFeaturesToTrack");
+    break;
+  }
+  corners.resize((size_t)count);
+}
+#ifdef ORBX_WITH_OPENCV
+inline void goodFeaturesToTrack(CornerDetector& handle, const cv::Mat& image, std::vector<cv::Point2f>& corners,
+                                int maxCorners, double qualityLevel, double minDistance) {
+  std::vector<Point2f> out;
+  goodFeaturesToTrack(handle, Image(image), out, maxCorners, qualityLevel, minDistance);
+  corners.clear();
+  for (const Point2f& p : out) corners.emplace_back(p.x, p.y);
+}
+#endif
+
+// The initial keypoints of run_bundle_adjustment (src/with_bundle_adjustment.cpp:586-593): the caller's
+// observations of frame 0 if there are any, else goodFeaturesToTrack(img0, 2000, 0.01, 8).
+inline std::vector<Point2f> initial_keypoints(CornerDetector& handle, const std::vector<Point2d>& observations0,
+                                              const Image& img0) {
+  std::vector<Point2f> keypoints0;
+  if (!observations0.empty()) {
+    for (const Point2d& p : observations0) {
+      Point2f q;
+      q.x = (float)p.x, q.y = (float)p.y;
+      keypoints0.push_back(q);
+    }
+  } else {
+    goodFeaturesToTrack(handle, img0, keypoints0, 2000, 0.01, 8);
+  }
+  return keypoints0;
+}
+
 }  // namespace orbx

@@ -38,6 +38,8 @@ EXPORTS = [
     "orbx_triangulate", "orbx_estimate_scale", "orbx_batch_scale_consecutive", "orbx_batch_scale_fetch",
     "orbx_batch_points_fetch", "orbx_chain_trajectory", "orbx_debug_fill_pools",
     "orbx_bundle_adjust", "orbx_bundle_adjust_batch",
+    "orbx_corner_min_eigen_val", "orbx_good_features_to_track", "orbx_good_features_batch_device",
+    "orbx_good_features_workspace_limit", "orbx_good_features_results_device", "orbx_good_features_fetch",
 ]
 
 
@@ -725,6 +727,100 @@ def _ba_methods():
 
 
 _ba_methods()
+
+
+class GoodFeaturesView(C.Structure):
+    _fields_ = [("counts", C.c_void_p), ("corners_xy", C.c_void_p), ("slot_capacity", C.c_int32), ("n", C.c_int32)]
+
+
+def _gftt_methods():
+    """Shi-Tomasi corners: cv::goodFeaturesToTrack (include/orbx.h; DESIGN.md §9 rank 8)."""
+
+    def _view(a):
+        # a row-strided uint8 view (a region of a larger image) is handed over as it is
+        if isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1 and \
+                a.strides[0] >= a.shape[1]:
+            return a
+        return _img(a)
+
+    def corner_min_eigen_val(self, image):
+        """cv::cornerMinEigenVal(image, eig, 3, 3): the (h, w) float32 response map."""
+        image = _view(image)
+        h, w = image.shape
+        out = np.zeros((h, w), np.float32)
+        f = self._lib.orbx_corner_min_eigen_val
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        self._chk(f(self._h, _ptr(image), w, h, image.strides[0], _ptr(out)))
+        return out
+
+    def good_features_to_track(self, image, max_corners=2000, quality_level=0.01, min_distance=8.0, capacity=None):
+        """cv::goodFeaturesToTrack(image, corners, maxCorners, qualityLevel, minDistance) as called at
+        with_bundle_adjustment.cpp:586-593: (n, 2) float32 corners (x, y), strongest first.  max_corners <= 0: no
+        limit.  capacity=None: sized for the call (max_corners, or every interior pixel)."""
+        image = _view(image)
+        h, w = image.shape
+        if capacity is None:
+            capacity = max_corners if max_corners > 0 else max((w - 2) * (h - 2), 1)
+        out = np.zeros((max(capacity, 1), 2), np.float32)
+        cnt = C.c_int(0)
+        f = self._lib.orbx_good_features_to_track
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                      C.c_int, C.POINTER(C.c_int)]
+        self._chk(f(self._h, _ptr(image), w, h, image.strides[0], max_corners, quality_level, min_distance, _ptr(out),
+                    capacity, C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def good_features_batch(self, frames, max_corners=2000, quality_level=0.01, min_distance=8.0, stream=None):
+        """orbx_good_features_batch_device on (n, h, w) uint8 frames: a torch device tensor (any strides with unit
+        pixel stride; the caller has synchronised its producer, or passes the producer's stream) or a numpy array
+        (copied to the device first).  Asynchronous; good_features_fetch delivers the results."""
+        import torch
+
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).cuda()
+            torch.cuda.synchronize()
+        if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda or frames.stride(2) != 1:
+            raise ValueError("frames must be (n, h, w) uint8 on the device with unit pixel stride")
+        self._gf_frames = frames  # kept alive until the next batch
+        n, h, w = frames.shape
+        rs = frames.stride(1)
+        fs = max(frames.stride(0), rs * (h - 1) + w) if n == 1 else frames.stride(0)
+        f = self._lib.orbx_good_features_batch_device
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_double,
+                      C.c_double, C.c_void_p]
+        self._chk(f(self._h, C.c_void_p(frames.data_ptr()), n, w, h, rs, fs, max_corners, quality_level,
+                    min_distance, C.c_void_p(stream) if stream else None))
+
+    def good_features_view(self):
+        """The device-side result block of the last good-features batch (orbx_good_features_results_device)."""
+        v = GoodFeaturesView()
+        self._chk(self._lib.orbx_good_features_results_device(self._h, C.byref(v)))
+        return v
+
+    def good_features_fetch(self, first=0, n=None):
+        """Results of frames [first, first + n) of the last good-features batch: a list of (count, 2) float32 arrays."""
+        v = self.good_features_view()
+        if n is None:
+            n = v.n - first
+        counts = np.zeros(max(n, 1), np.int32)
+        xy = np.zeros((max(n, 1), v.slot_capacity, 2), np.float32)
+        f = self._lib.orbx_good_features_fetch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(f(self._h, first, n, _ptr(counts), _ptr(xy)))
+        return [xy[i, :counts[i]].copy() for i in range(n)]
+
+    def good_features_workspace_limit(self, nbytes):
+        """Bound of the good-features workspace in bytes (0: the default); a larger batch runs in slices."""
+        f = self._lib.orbx_good_features_workspace_limit
+        f.argtypes = [C.c_void_p, C.c_size_t]
+        self._chk(f(self._h, nbytes))
+
+    for f in (corner_min_eigen_val, good_features_to_track, good_features_batch, good_features_view,
+              good_features_fetch, good_features_workspace_limit):
+        setattr(Context, f.__name__, f)
+
+
+_gftt_methods()
 
 
 def chain_trajectory(T0, R, t, scale):
