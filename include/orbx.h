@@ -580,6 +580,71 @@ int orbx_good_features_results_device(orbx_ctx* ctx, orbx_good_features_view* vi
  * corners_xy (n x slot_capacity x 2 floats, the view's stride; may be NULL).  src/with_bundle_adjustment.cpp:586-593 */
 int orbx_good_features_fetch(orbx_ctx* ctx, int first, int n, int32_t* counts, float* corners_xy);
 
+/* ---- next row: Lucas-Kanade over frame windows ---------------------------
+ * Replaces
+ *   trackPointsAcrossWindow: the points of a window's first frame followed frame by frame through the window, a
+ *   track ending with the first pair that loses it                         src/with_bundle_adjustment.cpp:464-499
+ *   track_optical_flow over a stream (windows of two frames)               src/feature_tracking.cpp:166-193
+ * for n_windows windows of window_len consecutive frames each in ONE tracking launch per slice.  Every pair is
+ * computed exactly as orbx_lk_track computes it (one text of the arithmetic in the kernels), and the point that
+ * leaves a pair enters the next one with the same float bits.
+ * Result layout (a block of its OWN; slot_capacity slots per window):
+ *   tracks_xy[w][slot][k]  the point in frame window_first[w] + k; entry 0 is the input point (tracks[i][0])
+ *   seen[w][slot]          frames the point was observed in, 1 .. window_len for a live slot
+ *   err[w][slot][k - 1]    the error orbx_lk_track reports for the pair (k - 1, k)
+ * Everything past `seen`, and every slot at or beyond counts[w], is written as 0: whole arrays compare equal.
+ * A counts[w] above slot_capacity is clamped.
+ * Arguments: the frame, stride and alignment rules of orbx_detect_and_compute_batch_device hold unchanged, with
+ * 8 <= width <= max_width, 8 <= height <= max_height and 2 <= n_frames <= max_batch; win_size, max_level, max_iters,
+ * epsilon as orbx_lk_track; window_len >= 2, n_windows >= 1, slot_capacity >= 1; window_first[w] >= 0 and
+ * window_first[w] + window_len <= n_frames (windows may overlap and come in any order).  Anything else is
+ * ORBX_ERR_INVALID_ARG: nothing is written, the previous windows result stays fetchable and the context usable.
+ * The frames are read IN PLACE (level 0 of the pyramids is the caller's memory; it must stay unchanged until the call
+ * has finished on the device); d_points_xy / d_counts may be the view of orbx_good_features_results_device.
+ * Asynchronous on the context's stream (or `stream`, a hipStream_t).  A caller's stream is used during the call only:
+ * later calls, fetches and orbx_destroy wait for an event recorded behind the batch.  The last ORB batch with its
+ * matches, poses and scales, the good-features block and the state of orbx_lk_track (its cached pyramids and the
+ * prev == NULL continuation) stay as they are.
+ * Workspace: per frame of a slice the pyramid levels 1 .. top (bytes w_l * h_l, each level rounded up to 256) and
+ * the int16 derivative pairs of the levels 0 .. top (4 * w_l * h_l, rounded likewise) -- with 4 levels
+ * (1/3 - 1/192) + 4 * (4/3 - 1/192) = 5.64 bytes per pixel, 2.63 MB for a 1241 x 376 frame.  It is allocated on demand
+ * for min(n_frames, max(frames that fit the limit, window_len)) frames and freed by orbx_destroy.  When the frames of
+ * all windows do not fit, the windows run in slices of whole consecutive windows, one after the other on the same
+ * stream, with identical results (a slice covers the frames from its lowest to its highest one). */
+int orbx_lk_track_windows_device(orbx_ctx* ctx, const void* d_frames, int n_frames, int width, int height,
+                                 int row_stride, size_t frame_stride,
+                                 const int32_t* window_first /* host, [n_windows] */, int n_windows, int window_len,
+                                 const float* d_points_xy /* device, [n_windows][slot_capacity][2] */,
+                                 const int32_t* d_counts /* device, [n_windows]; NULL: every slot is a point */,
+                                 int slot_capacity, int win_size, int max_level, int max_iters, double epsilon,
+                                 void* stream);
+/* Device-side results of the last windows call (valid until the next one; written on its stream).
+ * src/with_bundle_adjustment.cpp:464-499 */
+typedef struct {
+  const float* tracks_xy; /* [n_windows][slot_capacity][window_len][2] */
+  const int32_t* seen;    /* [n_windows][slot_capacity] */
+  const float* err;       /* [n_windows][slot_capacity][window_len - 1] */
+  int32_t slot_capacity, window_len, n_windows;
+} orbx_lk_windows_view;
+int orbx_lk_windows_results_device(orbx_ctx* ctx, orbx_lk_windows_view* view);
+/* Waits for the last windows call and copies windows [first, first + n) in the view's layout; each of the three
+ * arrays may be NULL.  src/with_bundle_adjustment.cpp:464-499 */
+int orbx_lk_windows_fetch(orbx_ctx* ctx, int first, int n, float* tracks_xy, int32_t* seen, float* err);
+/* The bound of the windows workspace in bytes (default ORBX_LK_WORKSPACE_DEFAULT; 0 restores it).  The frames of one
+ * window are always granted.  Waits for the windows call in flight and releases the workspace; the next call
+ * allocates the new size.  src/with_bundle_adjustment.cpp:464-499 */
+#define ORBX_LK_WORKSPACE_DEFAULT ((size_t)1 << 30)
+int orbx_lk_workspace_limit(orbx_ctx* ctx, size_t bytes);
+/* Host convenience: ONE window of n_frames host frames (frame i at frames + i * frame_stride) and n host points in,
+ * tracks_xy (n x n_frames x 2 floats), seen (n) and err (n x (n_frames - 1), may be NULL) out.  Synchronous; runs as
+ * a windows batch of one window and replaces the last windows result.  n == 0: nothing is done.  The frames are staged
+ * in a buffer of the entry's own, so n_frames is bounded by 65535, not by max_batch; every other rule is that of
+ * orbx_lk_track_windows_device.
+ * src/with_bundle_adjustment.cpp:464-499, src/feature_tracking.cpp:166-193 */
+int orbx_lk_track_window(orbx_ctx* ctx, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
+                         size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen, float* err,
+                         int win_size, int max_level, int max_iters, double epsilon);
+
 #ifdef __cplusplus
 }
 #endif

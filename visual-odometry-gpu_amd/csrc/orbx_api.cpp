@@ -227,6 +227,17 @@ struct orbx_ctx {
   // next call), and the event recorded behind that call's work: what later calls, fetches and orbx_destroy wait for
   hipStream_t gf_stream = nullptr;
   hipEvent_t gf_ev = nullptr;
+  // Lucas-Kanade over frame windows (k_lk_track_windows): the workspace of one slice of frames (pyramid levels above
+  // 0 | derivative maps), bounded by lkw_ws_limit; the window table; the staged frames and points of the one-window
+  // host entry; and the entry's OWN result block (tracks | seen | err).  Nothing here is shared with orbx_lk_track.
+  DevBuf lkw_ws, lkw_first, lkw_img, lkw_pts, lkw_res;
+  size_t lkw_ws_limit = ORBX_LK_WORKSPACE_DEFAULT;
+  int lkw_n = 0, lkw_cap = 0, lkw_len = 0;  // windows, slots per window, frames per window of the last call (0: none)
+  hipStream_t lkw_stream = nullptr;  // for comparison only, as gf_stream
+  hipEvent_t lkw_ev = nullptr;       // recorded behind every windows call
+  void* lkw_first_host = nullptr;    // pinned mirror of the window table, and the event behind its upload
+  size_t lkw_first_host_bytes = 0;
+  hipEvent_t lkw_first_ev = nullptr;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -1118,11 +1129,18 @@ void orbx_destroy(orbx_ctx* c) {
                   &c->pb_mask, &c->ph_in, &c->ph_pts, &c->ph_n, &c->ph_out, &c->ph_mask, &c->sb_xyz, &c->sb_valid,
                   &c->sb_mq, &c->sb_mt, &c->sb_n, &c->sb_out, &c->sh_in, &c->sh_xyz, &c->sh_valid, &c->sh_out,
                   &c->ba_off, &c->ba_poses, &c->ba_points, &c->ba_rows, &c->ba_opose, &c->ba_oxy, &c->ba_wp, &c->ba_wo,
-                  &c->ba_slot, &c->ba_out, &c->gf_ws, &c->gf_img, &c->gf_res};
+                  &c->ba_slot, &c->ba_out, &c->gf_ws, &c->gf_img, &c->gf_res,
+                  &c->lkw_ws, &c->lkw_first, &c->lkw_img, &c->lkw_pts, &c->lkw_res};
   if (c->gf_ev) {
     (void)hipEventSynchronize(c->gf_ev);
     (void)hipEventDestroy(c->gf_ev);
   }
+  if (c->lkw_ev) {
+    (void)hipEventSynchronize(c->lkw_ev);
+    (void)hipEventDestroy(c->lkw_ev);
+  }
+  if (c->lkw_first_ev) (void)hipEventDestroy(c->lkw_first_ev);
+  if (c->lkw_first_host) (void)hipHostFree(c->lkw_first_host);
   if (c->lk_host) (void)hipHostFree(c->lk_host);
   for (DevBuf* b : sb)
     if (b->p) (void)hipFree(b->p);
@@ -2252,6 +2270,306 @@ int orbx_lk_pyramid_levels(int width, int height, int win_size, int max_level) {
   if (width < 1 || height < 1 || win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
     return -1;
   return lk_geometry(width, height, win_size, max_level).top + 1;
+}
+
+}  // extern "C"
+
+// ---- Lucas-Kanade over frame windows ---------------------------------------------------------
+// trackPointsAcrossWindow (src/with_bundle_adjustment.cpp:464-499) for many windows per launch; with windows of two
+// frames, track_optical_flow (src/feature_tracking.cpp:166-193) over a stream.
+
+namespace {
+
+// the workspace of ONE frame: the pyramid levels above 0 (level 0 is read in place), then the derivative maps of
+// every level
+struct LkwLayout {
+  LkGeom g;
+  size_t img_bytes, frame_bytes;  // levels 1 .. top; img_bytes + derivative maps
+};
+LkwLayout lkw_layout(int w, int h, int win, int max_level) {
+  LkwLayout o;
+  o.g = lk_geometry(w, h, win, max_level);
+  o.img_bytes = o.g.top >= 1 ? o.g.img_bytes - o.g.img_off[1] : 0;
+  o.frame_bytes = o.img_bytes + o.g.der_bytes;
+  return o;
+}
+
+int lkw_wait(orbx_ctx* c) {
+  if (c->lkw_ev) HIPCHK(c, hipEventSynchronize(c->lkw_ev));
+  return ORBX_OK;
+}
+
+// a windows call on stream s: earlier windows work on another stream has to be done (one workspace, one result block)
+int lkw_enter(orbx_ctx* c, hipStream_t s) {
+  if (!c->lkw_ev) HIPCHK(c, hipEventCreateWithFlags(&c->lkw_ev, hipEventDisableTiming));
+  if (c->lkw_stream != s) {
+    const int st = lkw_wait(c);
+    if (st != ORBX_OK) return st;
+  }
+  c->lkw_stream = s;
+  return ORBX_OK;
+}
+
+struct LkwMark {
+  orbx_ctx* c;
+  hipStream_t s;
+  ~LkwMark() {
+    if (c->lkw_ev) (void)hipEventRecord(c->lkw_ev, s);
+  }
+};
+
+// a buffer of the windows path of at least `bytes`: the new allocation is made BEFORE the old one is released, so
+// that a failed call keeps what it had
+int lkw_grow(orbx_ctx* c, DevBuf& b, size_t bytes) {
+  if (b.p && b.bytes >= bytes) return ORBX_OK;
+  const int st = lkw_wait(c);  // (the old allocation may still be read or written)
+  if (st != ORBX_OK) return st;
+  bytes = align_up_sz(std::max<size_t>(bytes, 256), 256);
+  void* p = nullptr;
+  HIPCHK(c, hipMalloc(&p, bytes));
+  if (b.p) (void)hipFree(b.p);
+  b.p = p;
+  b.bytes = bytes;
+  return ORBX_OK;
+}
+
+struct LkwResult {
+  size_t o_seen, o_err, bytes;  // tracks at 0
+};
+LkwResult lkw_result(int n_windows, int cap, int len) {
+  LkwResult r;
+  const size_t slots = (size_t)n_windows * cap;
+  r.o_seen = align_up_sz(sizeof(float) * 2 * slots * len, 256);
+  r.o_err = align_up_sz(r.o_seen + sizeof(int32_t) * slots, 256);
+  r.bytes = r.o_err + sizeof(float) * slots * (len - 1);
+  return r;
+}
+
+// max_frames: max_batch for the device entry; the host entry stages into a buffer of its own (65535: blockIdx.z)
+int lkw_check_frames(orbx_ctx* c, const void* d_frames, int n_frames, int max_frames, int width, int height,
+                     int row_stride, size_t frame_stride) {
+  if (!d_frames) return fail(c, ORBX_ERR_INVALID_ARG, "frames is NULL");
+  if (n_frames < 2 || n_frames > max_frames)
+    return fail(c, ORBX_ERR_INVALID_ARG, "n_frames outside [2, " + std::to_string(max_frames) + "]");
+  if (width < 8 || height < 8 || width > c->p.max_width || height > c->p.max_height)
+    return fail(c, ORBX_ERR_INVALID_ARG, "image size outside [8, max_width] x [8, max_height]");
+  if (row_stride < width) return fail(c, ORBX_ERR_INVALID_ARG, "row_stride < width");
+  if (frame_stride < (size_t)row_stride * (size_t)(height - 1) + (size_t)width)
+    return fail(c, ORBX_ERR_INVALID_ARG, "frame_stride smaller than a frame");
+  if ((unsigned long long)row_stride * (unsigned long long)(height - 1) + (unsigned long long)width > 0x7fffffffull)
+    return fail(c, ORBX_ERR_INVALID_ARG, "row_stride * (height - 1) + width exceeds 2^31 - 1");
+  return ORBX_OK;
+}
+
+int lkw_check_params(orbx_ctx* c, int win_size, int max_level, int* max_iters, double* epsilon) {
+  if (win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
+    return fail(c, ORBX_ERR_INVALID_ARG, "win_size must be in [3, 31], max_level in [0, 7]");
+  if (!(*epsilon == *epsilon)) return fail(c, ORBX_ERR_INVALID_ARG, "epsilon is NaN");
+  // TermCriteria sanitising of calcOpticalFlowPyrLK, as orbx_lk_track
+  *max_iters = std::min(std::max(*max_iters, 0), 100);
+  *epsilon = std::min(std::max(*epsilon, 0.0), 10.0);
+  return ORBX_OK;
+}
+
+// enqueues the pyramids and the tracking of every window on s; arguments are checked
+int lkw_run(orbx_ctx* c, const uint8_t* d_frames, int n_frames, int w, int h, int row_stride, size_t frame_stride,
+            const int32_t* window_first, int n_windows, int window_len, const float* d_points,
+            const int32_t* d_counts, int cap, int win, int max_level, int max_iters, double epsilon, hipStream_t s) {
+  int st = lkw_enter(c, s);
+  if (st != ORBX_OK) return st;
+  const LkwMark mark{c, s};
+  // points and counts may be the good-features block, written on another stream
+  if (c->gf_ev && c->gf_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->gf_ev, 0));
+  const LkwLayout L = lkw_layout(w, h, win, max_level);
+  // frames per slice: what the limit holds, at least one window, at most the batch
+  const size_t fit =
+      std::min<size_t>(std::max<size_t>(c->lkw_ws_limit / L.frame_bytes, (size_t)window_len), (size_t)n_frames);
+  const LkwResult R = lkw_result(n_windows, cap, window_len);
+  if ((st = lkw_grow(c, c->lkw_ws, fit * L.frame_bytes + 256)) != ORBX_OK) return st;
+  if ((st = lkw_grow(c, c->lkw_first, sizeof(int32_t) * (size_t)n_windows)) != ORBX_OK) return st;
+  const void* old_res = c->lkw_res.p;
+  if ((st = lkw_grow(c, c->lkw_res, R.bytes)) != ORBX_OK) return st;
+  if (c->lkw_res.p != old_res) c->lkw_n = 0;  // (a larger block: the previous result went with the old one)
+  // The window table goes up through a pinned mirror (a copy from pageable memory would make the host wait for the
+  // stream).  The mirror is reused: the previous call's copy has to have read it.
+  const size_t table = sizeof(int32_t) * (size_t)n_windows;
+  if (!c->lkw_first_ev) HIPCHK(c, hipEventCreateWithFlags(&c->lkw_first_ev, hipEventDisableTiming));
+  HIPCHK(c, hipEventSynchronize(c->lkw_first_ev));
+  if (c->lkw_first_host_bytes < table) {
+    if (c->lkw_first_host) (void)hipHostFree(c->lkw_first_host);
+    c->lkw_first_host = nullptr;
+    c->lkw_first_host_bytes = 0;
+    HIPCHK(c, hipHostMalloc(&c->lkw_first_host, align_up_sz(table, 4096), hipHostMallocDefault));
+    c->lkw_first_host_bytes = align_up_sz(table, 4096);
+  }
+  // from here on the previous result is being replaced
+  c->lkw_n = 0;
+  std::memcpy(c->lkw_first_host, window_first, table);
+  HIPCHK(c, hipMemcpyAsync(c->lkw_first.p, c->lkw_first_host, table, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(c->lkw_first_ev, s));
+  uint8_t* ws = (uint8_t*)c->lkw_ws.p;
+  uint8_t* res = (uint8_t*)c->lkw_res.p;
+  const LkGeom& g = L.g;
+  const size_t img_base = g.top >= 1 ? g.img_off[1] : 0;  // workspace offsets count from level 1
+  const size_t slot_stride = (size_t)cap;
+  // slices of whole consecutive windows whose frames [lo, hi) fit the workspace
+  for (int w0 = 0; w0 < n_windows;) {
+    int lo = window_first[w0], hi = lo + window_len, w1 = w0 + 1;
+    while (w1 < n_windows && w1 - w0 < 65535) {
+      const int nlo = std::min(lo, window_first[w1]), nhi = std::max(hi, window_first[w1] + window_len);
+      if ((size_t)(nhi - nlo) > fit) break;
+      lo = nlo;
+      hi = nhi;
+      w1++;
+    }
+    const int m = hi - lo;
+    uint8_t* ws_img = ws;                                // [m][levels 1 .. top]
+    uint8_t* ws_der = ws + align_up_sz(L.img_bytes * m, 256);  // [m][levels 0 .. top]
+    const uint8_t* f_lo = d_frames + frame_stride * (size_t)lo;
+    for (int l = 1; l <= g.top; l++) {
+      const uint8_t* src = l == 1 ? f_lo : ws_img + (g.img_off[l - 1] - img_base);
+      HIPCHK(c, orbx_launch_lk_pyrdown_frames(s, m, src, g.w[l - 1], g.h[l - 1], l == 1 ? row_stride : g.pitch[l - 1],
+                                              l == 1 ? frame_stride : L.img_bytes, ws_img + (g.img_off[l] - img_base),
+                                              g.w[l], g.h[l], g.pitch[l], L.img_bytes));
+    }
+    for (int l = 0; l <= g.top; l++)
+      HIPCHK(c, orbx_launch_lk_scharr_frames(s, m, l == 0 ? f_lo : ws_img + (g.img_off[l] - img_base), g.w[l], g.h[l],
+                                             l == 0 ? row_stride : g.pitch[l], l == 0 ? frame_stride : L.img_bytes,
+                                             reinterpret_cast<int16_t*>(ws_der + g.der_off[l]), g.der_bytes));
+    OrbxLkFrames F;
+    std::memset(&F, 0, sizeof(F));
+    F.top = g.top;
+    F.first = lo;
+    F.frame_stride = frame_stride;
+    F.img_stride = L.img_bytes;
+    F.der_stride = g.der_bytes / sizeof(int16_t);
+    for (int l = 0; l <= g.top; l++) {
+      F.L[l].img = l == 0 ? d_frames : ws_img + (g.img_off[l] - img_base);
+      F.L[l].deriv = reinterpret_cast<const int16_t*>(ws_der + g.der_off[l]);
+      F.L[l].w = g.w[l];
+      F.L[l].h = g.h[l];
+      F.L[l].pitch = l == 0 ? row_stride : g.pitch[l];
+    }
+    HIPCHK(c, orbx_launch_lk_track_windows(
+                  s, F, (const int32_t*)c->lkw_first.p + w0, w1 - w0, window_len, d_points + 2 * slot_stride * w0,
+                  d_counts ? d_counts + w0 : nullptr, cap, (float*)res + 2 * slot_stride * window_len * w0,
+                  (int32_t*)(res + R.o_seen) + slot_stride * w0,
+                  (float*)(res + R.o_err) + slot_stride * (window_len - 1) * w0, win, max_iters, epsilon * epsilon));
+    w0 = w1;
+  }
+  c->lkw_n = n_windows;
+  c->lkw_cap = cap;
+  c->lkw_len = window_len;
+  return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_lk_track_windows_device(orbx_ctx* c, const void* d_frames, int n_frames, int width, int height,
+                                 int row_stride, size_t frame_stride, const int32_t* window_first, int n_windows,
+                                 int window_len, const float* d_points_xy, const int32_t* d_counts, int slot_capacity,
+                                 int win_size, int max_level, int max_iters, double epsilon, void* stream) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  int st = lkw_check_frames(c, d_frames, n_frames, c->p.max_batch, width, height, row_stride, frame_stride);
+  if (st != ORBX_OK) return st;
+  if ((st = lkw_check_params(c, win_size, max_level, &max_iters, &epsilon)) != ORBX_OK) return st;
+  if (!window_first || !d_points_xy) return fail(c, ORBX_ERR_INVALID_ARG, "window_first / d_points_xy is NULL");
+  if (n_windows < 1 || window_len < 2 || slot_capacity < 1)
+    return fail(c, ORBX_ERR_INVALID_ARG, "n_windows < 1, window_len < 2 or slot_capacity < 1");
+  for (int i = 0; i < n_windows; i++)
+    if (window_first[i] < 0 || window_first[i] > n_frames - window_len)
+      return fail(c, ORBX_ERR_INVALID_ARG, "a window does not lie inside the frames");
+  return lkw_run(c, (const uint8_t*)d_frames, n_frames, width, height, row_stride, frame_stride, window_first,
+                 n_windows, window_len, d_points_xy, d_counts, slot_capacity, win_size, max_level, max_iters, epsilon,
+                 stream ? (hipStream_t)stream : c->stream);
+}
+
+int orbx_lk_workspace_limit(orbx_ctx* c, size_t bytes) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  const int st = lkw_wait(c);
+  if (st != ORBX_OK) return st;
+  if (c->lkw_ws.p) {
+    HIPCHK(c, hipFree(c->lkw_ws.p));
+    c->lkw_ws = DevBuf{};
+  }
+  c->lkw_ws_limit = bytes ? bytes : ORBX_LK_WORKSPACE_DEFAULT;
+  return ORBX_OK;
+}
+
+int orbx_lk_windows_results_device(orbx_ctx* c, orbx_lk_windows_view* v) {
+  DeviceGuard _dg(c);
+  if (!c || !v) return ORBX_ERR_INVALID_ARG;
+  if (c->lkw_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
+  const LkwResult R = lkw_result(c->lkw_n, c->lkw_cap, c->lkw_len);
+  const uint8_t* res = (const uint8_t*)c->lkw_res.p;
+  v->tracks_xy = (const float*)res;
+  v->seen = (const int32_t*)(res + R.o_seen);
+  v->err = (const float*)(res + R.o_err);
+  v->slot_capacity = c->lkw_cap;
+  v->window_len = c->lkw_len;
+  v->n_windows = c->lkw_n;
+  return ORBX_OK;
+}
+
+int orbx_lk_windows_fetch(orbx_ctx* c, int first, int n, float* tracks_xy, int32_t* seen, float* err) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (c->lkw_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
+  if (first < 0 || n < 1 || first >= c->lkw_n || n > c->lkw_n - first)
+    return fail(c, ORBX_ERR_INVALID_ARG, "[first, first + n) outside the batch");
+  const int st = lkw_wait(c);
+  if (st != ORBX_OK) return st;
+  const LkwResult R = lkw_result(c->lkw_n, c->lkw_cap, c->lkw_len);
+  const uint8_t* res = (const uint8_t*)c->lkw_res.p;
+  const size_t slots = (size_t)c->lkw_cap, len = (size_t)c->lkw_len;
+  if (tracks_xy)
+    HIPCHK(c, hipMemcpy(tracks_xy, res + sizeof(float) * 2 * slots * len * first, sizeof(float) * 2 * slots * len * n,
+                        hipMemcpyDeviceToHost));
+  if (seen)
+    HIPCHK(c, hipMemcpy(seen, res + R.o_seen + sizeof(int32_t) * slots * first, sizeof(int32_t) * slots * n,
+                        hipMemcpyDeviceToHost));
+  if (err)
+    HIPCHK(c, hipMemcpy(err, res + R.o_err + sizeof(float) * slots * (len - 1) * first,
+                        sizeof(float) * slots * (len - 1) * n, hipMemcpyDeviceToHost));
+  return ORBX_OK;
+}
+
+int orbx_lk_track_window(orbx_ctx* c, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
+                         size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen, float* err,
+                         int win_size, int max_level, int max_iters, double epsilon) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  int st = lkw_check_frames(c, frames, n_frames, 65535, width, height, row_stride, frame_stride);
+  if (st != ORBX_OK) return st;
+  if ((st = lkw_check_params(c, win_size, max_level, &max_iters, &epsilon)) != ORBX_OK) return st;
+  if (n < 0 || (n > 0 && (!pts_xy || !tracks_xy || !seen)))
+    return fail(c, ORBX_ERR_INVALID_ARG, "n < 0 or pts_xy / tracks_xy / seen is NULL");
+  if (n == 0) return ORBX_OK;  // no points: nothing to track, the last result stays
+  if ((st = lkw_enter(c, c->stream)) != ORBX_OK) return st;
+  const size_t tight = (size_t)width * height;
+  {
+    const LkwMark mark{c, c->stream};
+    if ((st = lkw_grow(c, c->lkw_img, tight * n_frames)) != ORBX_OK) return st;
+    if ((st = lkw_grow(c, c->lkw_pts, sizeof(float) * 2 * (size_t)n)) != ORBX_OK) return st;
+    if (row_stride == width && frame_stride == tight) {
+      HIPCHK(c, hipMemcpyAsync(c->lkw_img.p, frames, tight * n_frames, hipMemcpyHostToDevice, c->stream));
+    } else {
+      for (int i = 0; i < n_frames; i++)
+        HIPCHK(c, hipMemcpy2DAsync((uint8_t*)c->lkw_img.p + tight * i, width, frames + frame_stride * i, row_stride,
+                                   width, height, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->lkw_pts.p, pts_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  }
+  const int32_t first = 0;
+  if ((st = lkw_run(c, (const uint8_t*)c->lkw_img.p, n_frames, width, height, width, tight, &first, 1, n_frames,
+                    (const float*)c->lkw_pts.p, nullptr, n, win_size, max_level, max_iters, epsilon, c->stream)) !=
+      ORBX_OK)
+    return st;
+  return orbx_lk_windows_fetch(c, 0, 1, tracks_xy, seen, err);
 }
 
 }  // extern "C"

@@ -50,6 +50,26 @@ hipError_t orbx_launch_lk_scharr(hipStream_t s, const uint8_t* d_img, int w, int
 hipError_t orbx_launch_lk_track(hipStream_t s, const OrbxLkPyr& prev, const OrbxLkPyr& next, int n,
                                 const float* d_prev_pts, float* d_next_pts, uint8_t* d_status, float* d_err, int win,
                                 int max_iters, double eps2);
+// The pyramids of the frames of one slice (k_lk_track_windows).  L describes frame `first`:
+// level 0 is read IN PLACE from the caller's frames (L[0].img = frame 0 of the batch, frames frame_stride bytes
+// apart), the levels above and every derivative map live in the workspace, img_stride bytes / der_stride int16
+// apart from frame to frame.
+struct OrbxLkFrames {
+  OrbxLkLevel L[ORBX_LK_MAX_LEVELS];
+  size_t frame_stride, img_stride, der_stride;
+  int32_t top, first;
+};
+// the same kernels with the frame in blockIdx.z (frames <= 65535): one launch per level for a slice of frames
+hipError_t orbx_launch_lk_pyrdown_frames(hipStream_t s, int frames, const uint8_t* d_src, int sw, int sh, int spitch,
+                                         size_t src_frame_stride, uint8_t* d_dst, int dw, int dh, int dpitch,
+                                         size_t dst_frame_stride);
+hipError_t orbx_launch_lk_scharr_frames(hipStream_t s, int frames, const uint8_t* d_img, int w, int h, int pitch,
+                                        size_t img_frame_stride, int16_t* d_deriv, size_t deriv_frame_bytes);
+// grid (ceil(slot_capacity / 4), n_windows): n_windows <= 65535.  d_counts may be NULL (every slot is a point)
+hipError_t orbx_launch_lk_track_windows(hipStream_t s, const OrbxLkFrames& frames, const int32_t* d_window_first,
+                                        int n_windows, int window_len, const float* d_points, const int32_t* d_counts,
+                                        int slot_capacity, float* d_tracks, int32_t* d_seen, float* d_err, int win,
+                                        int max_iters, double eps2);
 
 // ---- launchers (orbx_kernels.hip) ------------------------------------------
 // All take the stream explicitly and never synchronise or allocate.

@@ -12,12 +12,15 @@
 // Kernels
 //   k_lk_pyrdown  cv::pyrDown (5x5 [1 4 6 4 1]^2 / 256, REFLECT_101), thread per output pixel
 //   k_lk_scharr   Scharr (3,10,3) derivative pairs as int16, REFLECT_101, thread per pixel
+//                 (both take the frame in blockIdx.z: one launch per level for all frames of a slice)
 //   k_lk_track    ONE WAVEFRONT PER POINT walks the levels top -> 0.  The 21x21 template
 //                 (intensity + two gradients, int16) and a 26x26 neighbourhood of the next
 //                 image live in the wave's LDS slice; every Newton step samples the 441
 //                 window pixels from LDS (7 per lane) and reduces the two mismatch sums with
 //                 DPP; the neighbourhood is re-fetched only when the window leaves it.  All
 //                 control flow is wave-uniform, there is no workgroup barrier.
+//   k_lk_track_windows  the same body (lk_track_point) in a loop over the frame pairs of a window: one wavefront
+//                 per (window, point slot), the point handed from pair to pair in registers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,10 +34,14 @@ __device__ __forceinline__ int lk_reflect(int p, int len) {
   return p;
 }
 
+// blockIdx.z: the frame (source and destination `sframe` / `dframe` bytes apart; one frame: grid z = 1)
 __global__ __launch_bounds__(256) void k_lk_pyrdown(const uint8_t* __restrict__ src, int sw, int sh, int spitch,
-                                                    uint8_t* __restrict__ dst, int dw, int dh, int dpitch) {
+                                                    size_t sframe, uint8_t* __restrict__ dst, int dw, int dh,
+                                                    int dpitch, size_t dframe) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= dw || y >= dh) return;
+  src += sframe * blockIdx.z;
+  dst += dframe * blockIdx.z;
   int xs[5];
 #pragma unroll
   for (int j = 0; j < 5; j++) xs[j] = lk_reflect(2 * x + j - 2, sw);
@@ -48,10 +55,13 @@ __global__ __launch_bounds__(256) void k_lk_pyrdown(const uint8_t* __restrict__ 
   dst[(size_t)y * dpitch + x] = (uint8_t)((sum + 128) >> 8);
 }
 
+// blockIdx.z: the frame (images `iframe` bytes, derivative maps `dframe` short2 apart)
 __global__ __launch_bounds__(256) void k_lk_scharr(const uint8_t* __restrict__ img, int w, int h, int pitch,
-                                                   short2* __restrict__ deriv) {
+                                                   size_t iframe, short2* __restrict__ deriv, size_t dframe) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= w || y >= h) return;
+  img += iframe * blockIdx.z;
+  deriv += dframe * blockIdx.z;
   const uint8_t* r0 = img + (size_t)lk_reflect(y - 1, h) * pitch;
   const uint8_t* r1 = img + (size_t)y * pitch;
   const uint8_t* r2 = img + (size_t)lk_reflect(y + 1, h) * pitch;
@@ -172,45 +182,77 @@ __device__ __forceinline__ int lk_sample_cached(const LkCache& c, int inx, int i
   return lk_descale(p[0] * w.w00 + p[1] * w.w01 + p[c.jce] * w.w10 + p[c.jce + 1] * w.w11, 14 - 5);
 }
 
-// NIT: passes of the 64 lanes over the win x win window, known at compile time for the
-// reference's 21 x 21 window (7: the loops unroll and the LDS / global reads of a pass set are
-// all in flight together), 0 = run-time trip count for any other window size
-template <int NIT>
-__global__ __launch_bounds__(256) void k_lk_track(OrbxLkPyr P, OrbxLkPyr N, int n, const float2* __restrict__ prev_pts,
-                                                  float2* __restrict__ next_pts, uint8_t* __restrict__ status,
-                                                  float* __restrict__ err, int win, int max_iters, double eps2) {
-  // per wave: the template, (intensity, dx, dy) as int16 (4th lane of the short4 unused)
-  __shared__ short4 s_tpl[4][LK_MAX_WIN * LK_MAX_WIN];
-  __shared__ uint8_t s_jc[4][LK_JC_MAX * LK_JC_MAX];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + wave;
-  if (i >= n) return;  // whole wave
-  short4* tpl = s_tpl[wave];
+// What a wave needs besides its point: its LDS slice and the window constants (all wave-uniform)
+struct LkWave {
+  short4* tpl;  // the template, (intensity, dx, dy) as int16 (4th lane of the short4 unused)
   LkCache jc;
-  jc.px = s_jc[wave];
-  jc.jce = win + 1 + 2 * LK_JC_MARGIN;
-  jc.rcp = (65536u + (uint32_t)jc.jce - 1u) / (uint32_t)jc.jce;  // idx / jce for idx < 36^2
-  jc.x0 = jc.y0 = 0;
-  jc.valid = false;
-  const int nitem = win * win;
-  const uint32_t rcp = (65536u + (uint32_t)win - 1u) / (uint32_t)win;  // idx / win == (idx * rcp) >> 16 for idx < 961
-  const float half = (float)(win - 1) * 0.5f;
-  const float flt_scale = 1.f / (float)(1 << 20);
-  // the point is the same in every lane: keep it (and everything derived from it) wave-uniform
-  float2 pp = prev_pts[i];
-  pp.x = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pp.x)));
-  pp.y = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pp.y)));
-  int st = 1;
-  float ev = 0.f;
-  float outx = 0.f, outy = 0.f;
-  for (int level = P.top; level >= 0; level--) {
-    const OrbxLkLevel& I = P.L[level];
-    const OrbxLkLevel& J = N.L[level];
+  int lane, win, nitem, max_iters;
+  uint32_t rcp;  // idx / win == (idx * rcp) >> 16 for idx < 961
+  float half, flt_scale;
+  double eps2;
+};
+
+__device__ __forceinline__ LkWave lk_wave_setup(short4* tpl, uint8_t* jc_px, int lane, int win, int max_iters,
+                                                double eps2) {
+  LkWave W;
+  W.tpl = tpl;
+  W.jc.px = jc_px;
+  W.jc.jce = win + 1 + 2 * LK_JC_MARGIN;
+  W.jc.rcp = (65536u + (uint32_t)W.jc.jce - 1u) / (uint32_t)W.jc.jce;  // idx / jce for idx < 36^2
+  W.jc.x0 = W.jc.y0 = 0;
+  W.jc.valid = false;
+  W.lane = lane;
+  W.win = win;
+  W.nitem = win * win;
+  W.max_iters = max_iters;
+  W.rcp = (65536u + (uint32_t)win - 1u) / (uint32_t)win;
+  W.half = (float)(win - 1) * 0.5f;
+  W.flt_scale = 1.f / (float)(1 << 20);
+  W.eps2 = eps2;
+  return W;
+}
+
+// The pyramids of one image pair as the kernels hand them to the body: level(l) is wave-uniform
+struct LkPyrArg {  // k_lk_track: the kernel argument as it is
+  const OrbxLkPyr& P;
+  __device__ __forceinline__ OrbxLkLevel level(int l) const { return P.L[l]; }
+};
+struct LkPyrFrame {  // k_lk_track_windows: frame f of the slice
+  const OrbxLkFrames& F;
+  int f;
+  __device__ __forceinline__ OrbxLkLevel level(int l) const {
+    OrbxLkLevel L = F.L[l];
+    L.img += l == 0 ? F.frame_stride * (size_t)f : F.img_stride * (size_t)(f - F.first);
+    L.deriv += F.der_stride * (size_t)(f - F.first);
+    return L;
+  }
+};
+
+// ONE text of the tracker's arithmetic: the point pp of image P followed into image N, from the top level down to
+// the error value.  Used by k_lk_track (one pair) and by k_lk_track_windows (the pairs of a window, one after the
+// other).  NIT: passes of the 64 lanes over the win x win window, known at compile time for the reference's
+// 21 x 21 window (7: the loops unroll and the LDS / global reads of a pass set are all in flight together),
+// 0 = run-time trip count for any other window size.  Everything but `lane` is wave-uniform.
+template <int NIT, class Pyr>
+__device__ __forceinline__ void lk_track_point(const Pyr& P, const Pyr& N, int top, float2 pp, LkWave& W, float& outx,
+                                               float& outy, int& st, float& ev) {
+  short4* tpl = W.tpl;
+  LkCache& jc = W.jc;
+  const int lane = W.lane, win = W.win, nitem = W.nitem, max_iters = W.max_iters;
+  const uint32_t rcp = W.rcp;
+  const float half = W.half, flt_scale = W.flt_scale;
+  const double eps2 = W.eps2;
+  st = 1;
+  ev = 0.f;
+  outx = 0.f;
+  outy = 0.f;
+  for (int level = top; level >= 0; level--) {
+    const OrbxLkLevel I = P.level(level), J = N.level(level);
     jc.valid = false;
     const float sc = (float)(1.0 / (double)(1 << level));
     float px = __fmul_rn(pp.x, sc), py = __fmul_rn(pp.y, sc);
     float nx, ny;
-    if (level == P.top) {
+    if (level == top) {
       nx = px;
       ny = py;
     } else {
@@ -310,6 +352,25 @@ __global__ __launch_bounds__(256) void k_lk_track(OrbxLkPyr P, OrbxLkPyr N, int 
       ev = __fmul_rn(lk_exact_sum_f32(e), __fdiv_rn(1.f, (float)(32 * win * win)));
     }
   }
+}
+
+template <int NIT>
+__global__ __launch_bounds__(256) void k_lk_track(OrbxLkPyr P, OrbxLkPyr N, int n, const float2* __restrict__ prev_pts,
+                                                  float2* __restrict__ next_pts, uint8_t* __restrict__ status,
+                                                  float* __restrict__ err, int win, int max_iters, double eps2) {
+  __shared__ short4 s_tpl[4][LK_MAX_WIN * LK_MAX_WIN];
+  __shared__ uint8_t s_jc[4][LK_JC_MAX * LK_JC_MAX];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + wave;
+  if (i >= n) return;  // whole wave
+  LkWave W = lk_wave_setup(s_tpl[wave], s_jc[wave], lane, win, max_iters, eps2);
+  // the point is the same in every lane: keep it (and everything derived from it) wave-uniform
+  float2 pp = prev_pts[i];
+  pp.x = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pp.x)));
+  pp.y = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pp.y)));
+  int st;
+  float ev, outx, outy;
+  lk_track_point<NIT>(LkPyrArg{P}, LkPyrArg{N}, P.top, pp, W, outx, outy, st, ev);
   if (lane == 0) {
     next_pts[i] = make_float2(outx, outy);
     status[i] = (uint8_t)st;
@@ -317,18 +378,84 @@ __global__ __launch_bounds__(256) void k_lk_track(OrbxLkPyr P, OrbxLkPyr N, int 
   }
 }
 
+// trackPointsAcrossWindow (src/with_bundle_adjustment.cpp:464-499) for every (window, point slot) of a slice: ONE
+// WAVEFRONT per slot follows its point through the pairs (f0, f0 + 1), (f0 + 1, f0 + 2), ... of its window; the point
+// that leaves a pair enters the next one from registers, and the wave stops at the first pair that loses it.
+// Outputs (lane 0, plain stores): tracks[window][slot][k] = the point in frame f0 + k (k = 0: the input point),
+// seen[window][slot] = frames the point was observed in, err[window][slot][k - 1] = the pair's error; everything past
+// `seen`, and every slot at or beyond counts[window], is written as 0.  grid (ceil(cap / 4), windows of the slice).
+template <int NIT>
+__global__ __launch_bounds__(256) void k_lk_track_windows(OrbxLkFrames F, const int32_t* __restrict__ window_first,
+                                                          int window_len, const float2* __restrict__ points,
+                                                          const int32_t* __restrict__ counts, int cap,
+                                                          float2* __restrict__ tracks, int32_t* __restrict__ seen,
+                                                          float* __restrict__ err, int win, int max_iters,
+                                                          double eps2) {
+  __shared__ short4 s_tpl[4][LK_MAX_WIN * LK_MAX_WIN];
+  __shared__ uint8_t s_jc[4][LK_JC_MAX * LK_JC_MAX];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + wave, w = blockIdx.y;
+  if (slot >= cap) return;  // whole wave
+  const size_t at = (size_t)w * cap + slot;
+  float2* trk = tracks + at * window_len;
+  float* er = err + at * (window_len - 1);
+  int count = counts ? counts[w] : cap;
+  count = __builtin_amdgcn_readfirstlane(count < cap ? count : cap);
+  int k = 0;  // frames the point has been observed in
+  if (slot < count) {
+    const int f0 = __builtin_amdgcn_readfirstlane(window_first[w]);
+    LkWave W = lk_wave_setup(s_tpl[wave], s_jc[wave], lane, win, max_iters, eps2);
+    float2 pp = points[at];
+    pp.x = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pp.x)));
+    pp.y = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pp.y)));
+    if (lane == 0) trk[0] = pp;
+    for (k = 1; k < window_len; k++) {
+      int st;
+      float ev, outx, outy;
+      lk_track_point<NIT>(LkPyrFrame{F, f0 + k - 1}, LkPyrFrame{F, f0 + k}, F.top, pp, W, outx, outy, st, ev);
+      if (!st) break;
+      pp = make_float2(outx, outy);
+      if (lane == 0) {
+        trk[k] = pp;
+        er[k - 1] = ev;
+      }
+    }
+  }
+  // the zero tail: frames k .. window_len - 1 and their pairs, a lane each
+  for (int j = k + lane; j < window_len; j += 64) {
+    trk[j] = make_float2(0.f, 0.f);
+    if (j > 0) er[j - 1] = 0.f;
+  }
+  if (lane == 0) seen[at] = k;
+}
+
 }  // namespace
 
 hipError_t orbx_launch_lk_pyrdown(hipStream_t s, const uint8_t* d_src, int sw, int sh, int spitch, uint8_t* d_dst,
                                   int dw, int dh, int dpitch) {
-  dim3 grid((dw + 63) / 64, (dh + 3) / 4);
-  hipLaunchKernelGGL(k_lk_pyrdown, grid, dim3(256), 0, s, d_src, sw, sh, spitch, d_dst, dw, dh, dpitch);
+  return orbx_launch_lk_pyrdown_frames(s, 1, d_src, sw, sh, spitch, 0, d_dst, dw, dh, dpitch, 0);
+}
+
+hipError_t orbx_launch_lk_pyrdown_frames(hipStream_t s, int frames, const uint8_t* d_src, int sw, int sh, int spitch,
+                                         size_t src_frame_stride, uint8_t* d_dst, int dw, int dh, int dpitch,
+                                         size_t dst_frame_stride) {
+  if (frames < 1 || frames > 65535) return hipErrorInvalidValue;
+  dim3 grid((dw + 63) / 64, (dh + 3) / 4, frames);
+  hipLaunchKernelGGL(k_lk_pyrdown, grid, dim3(256), 0, s, d_src, sw, sh, spitch, src_frame_stride, d_dst, dw, dh,
+                     dpitch, dst_frame_stride);
   return hipGetLastError();
 }
 
 hipError_t orbx_launch_lk_scharr(hipStream_t s, const uint8_t* d_img, int w, int h, int pitch, int16_t* d_deriv) {
-  dim3 grid((w + 63) / 64, (h + 3) / 4);
-  hipLaunchKernelGGL(k_lk_scharr, grid, dim3(256), 0, s, d_img, w, h, pitch, reinterpret_cast<short2*>(d_deriv));
+  return orbx_launch_lk_scharr_frames(s, 1, d_img, w, h, pitch, 0, d_deriv, 0);
+}
+
+hipError_t orbx_launch_lk_scharr_frames(hipStream_t s, int frames, const uint8_t* d_img, int w, int h, int pitch,
+                                        size_t img_frame_stride, int16_t* d_deriv, size_t deriv_frame_bytes) {
+  if (frames < 1 || frames > 65535 || (deriv_frame_bytes & 3)) return hipErrorInvalidValue;
+  dim3 grid((w + 63) / 64, (h + 3) / 4, frames);
+  hipLaunchKernelGGL(k_lk_scharr, grid, dim3(256), 0, s, d_img, w, h, pitch, img_frame_stride,
+                     reinterpret_cast<short2*>(d_deriv), deriv_frame_bytes / 4);
   return hipGetLastError();
 }
 
@@ -345,5 +472,23 @@ hipError_t orbx_launch_lk_track(hipStream_t s, const OrbxLkPyr& prev, const Orbx
   else
     hipLaunchKernelGGL(k_lk_track<0>, dim3((n + 3) / 4), dim3(256), 0, s, prev, next, n, pp, np_, d_status, d_err, win,
                        max_iters, eps2);
+  return hipGetLastError();
+}
+
+hipError_t orbx_launch_lk_track_windows(hipStream_t s, const OrbxLkFrames& frames, const int32_t* d_window_first,
+                                        int n_windows, int window_len, const float* d_points, const int32_t* d_counts,
+                                        int slot_capacity, float* d_tracks, int32_t* d_seen, float* d_err, int win,
+                                        int max_iters, double eps2) {
+  if (n_windows < 1 || n_windows > 65535 || window_len < 2 || slot_capacity < 1) return hipErrorInvalidValue;
+  if (win < 3 || win > LK_MAX_WIN) return hipErrorInvalidValue;
+  const dim3 grid((slot_capacity + 3) / 4, n_windows);
+  const float2* pts = reinterpret_cast<const float2*>(d_points);
+  float2* trk = reinterpret_cast<float2*>(d_tracks);
+  if (win == 21)
+    hipLaunchKernelGGL(k_lk_track_windows<7>, grid, dim3(256), 0, s, frames, d_window_first, window_len, pts, d_counts,
+                       slot_capacity, trk, d_seen, d_err, win, max_iters, eps2);
+  else
+    hipLaunchKernelGGL(k_lk_track_windows<0>, grid, dim3(256), 0, s, frames, d_window_first, window_len, pts, d_counts,
+                       slot_capacity, trk, d_seen, d_err, win, max_iters, eps2);
   return hipGetLastError();
 }

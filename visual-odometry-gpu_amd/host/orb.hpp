@@ -617,6 +617,37 @@ class LKTracker {
                   "calcOpticalFlowPyrLK");
   }
 
+  // trackPointsAcrossWindow's tracking (src/with_bundle_adjustment.cpp:464-499) in ONE launch: pts0 of imgs[0]
+  // followed through imgs[1], imgs[2], ...  tracks: pts0.size() x imgs.size() points (entry 0: the input point),
+  // seen: frames each point was observed in, err: pts0.size() x (imgs.size() - 1); zero past `seen`.  The pairs are
+  // computed as calcOpticalFlowPyrLK computes them; the cached pyramid of the per-pair calls is left alone.
+  void trackWindow(const std::vector<Image>& imgs, const std::vector<Point2f>& pts0, std::vector<Point2f>& tracks,
+                   std::vector<int32_t>& seen, std::vector<float>& err, Size winSize = Size(21, 21), int maxLevel = 3,
+                   TermCriteria criteria = TermCriteria()) {
+    if (winSize.width != winSize.height) throw std::runtime_error("trackWindow: square windows only");
+    if (imgs.size() < 2) throw std::runtime_error("trackWindow: a window has at least two frames");
+    const int w = imgs[0].width, h = imgs[0].height, nf = (int)imgs.size(), n = (int)pts0.size();
+    // the frames side by side in one allocation (the entry takes one base address and a frame stride)
+    std::vector<uint8_t> packed((size_t)w * h * nf);
+    for (int f = 0; f < nf; f++) {
+      if (imgs[(size_t)f].width != w || imgs[(size_t)f].height != h)
+        throw std::runtime_error("trackWindow: image sizes differ");
+      for (int y = 0; y < h; y++)
+        std::memcpy(packed.data() + ((size_t)f * h + y) * w, imgs[(size_t)f].data + (size_t)y * imgs[(size_t)f].stride,
+                    (size_t)w);
+    }
+    orbx_ctx* c = ctx_->get(w, h);
+    tracks.assign((size_t)n * nf, Point2f());
+    seen.assign((size_t)n, 0);
+    err.assign((size_t)n * (nf - 1), 0.f);
+    detail::check(c,
+                  orbx_lk_track_window(c, packed.data(), nf, w, h, w, (size_t)w * h,
+                                       reinterpret_cast<const float*>(pts0.data()), n,
+                                       reinterpret_cast<float*>(tracks.data()), seen.data(), err.data(), winSize.width,
+                                       maxLevel, criteria.maxCount, criteria.epsilon),
+                  "trackWindow");
+  }
+
  private:
   std::shared_ptr<detail::Ctx> ctx_;
 };
@@ -817,6 +848,23 @@ inline std::vector<Track> track_points_across_window(LKTracker& lk, const std::v
     live.swap(still);
     prev.swap(kept);
   }
+  return tracks;
+}
+
+// The same in one launch (LKTracker::trackWindow): no host compaction between the pairs, no round trip per pair.
+// Returns exactly what track_points_across_window returns.
+inline std::vector<Track> track_points_across_window_one_launch(LKTracker& lk, const std::vector<Image>& imgs_window,
+                                                                const std::vector<Point2f>& keypoints0) {
+  std::vector<Track> tracks(keypoints0.size());
+  for (size_t i = 0; i < keypoints0.size(); i++) tracks[i].emplace_back(0, keypoints0[i]);
+  if (imgs_window.size() < 2 || keypoints0.empty()) return tracks;
+  std::vector<Point2f> xy;
+  std::vector<int32_t> seen;
+  std::vector<float> err;
+  lk.trackWindow(imgs_window, keypoints0, xy, seen, err, Size(21, 21), 3, TermCriteria(30, 0.01));
+  const size_t nf = imgs_window.size();
+  for (size_t i = 0; i < keypoints0.size(); i++)
+    for (int k = 1; k < seen[i]; k++) tracks[i].emplace_back(k, xy[i * nf + (size_t)k]);
   return tracks;
 }
 

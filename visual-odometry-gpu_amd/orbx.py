@@ -40,6 +40,8 @@ EXPORTS = [
     "orbx_bundle_adjust", "orbx_bundle_adjust_batch",
     "orbx_corner_min_eigen_val", "orbx_good_features_to_track", "orbx_good_features_batch_device",
     "orbx_good_features_workspace_limit", "orbx_good_features_results_device", "orbx_good_features_fetch",
+    "orbx_lk_track_windows_device", "orbx_lk_windows_results_device", "orbx_lk_windows_fetch",
+    "orbx_lk_workspace_limit", "orbx_lk_track_window",
 ]
 
 
@@ -821,6 +823,120 @@ def _gftt_methods():
 
 
 _gftt_methods()
+
+
+class LkWindowsView(C.Structure):
+    _fields_ = [("tracks_xy", C.c_void_p), ("seen", C.c_void_p), ("err", C.c_void_p), ("slot_capacity", C.c_int32),
+                ("window_len", C.c_int32), ("n_windows", C.c_int32)]
+
+
+def _lk_window_methods():
+    """Lucas-Kanade over frame windows: trackPointsAcrossWindow for many windows per launch (include/orbx.h;
+    DESIGN.md §9 rank 9)."""
+
+    def lk_track_windows(self, frames, window_first, window_len, points, counts=None, win=21, max_level=3,
+                         max_iters=30, epsilon=0.01, slot_capacity=None, stream=None):
+        """orbx_lk_track_windows_device.  frames: (n, h, w) uint8, a torch device tensor (any strides with unit pixel
+        stride; read in place) or a numpy array (copied to the device first).  points: (n_windows, slot_capacity, 2)
+        float32 and counts: (n_windows,) int32 or None, each a torch device tensor, a numpy array or a raw device
+        address (then slot_capacity is required) -- e.g. the fields of good_features_view().  Device tensors: the
+        caller has synchronised their producer, or passes the producer's stream.  Asynchronous; lk_windows_fetch
+        delivers the results."""
+        import torch
+
+        uploaded = any(isinstance(a, np.ndarray) for a in (frames, points, counts))
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).cuda()
+        if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda or frames.stride(2) != 1:
+            raise ValueError("frames must be (n, h, w) uint8 on the device with unit pixel stride")
+        window_first = np.ascontiguousarray(window_first, np.int32).reshape(-1)
+        nw = len(window_first)
+        if isinstance(points, np.ndarray):
+            points = torch.from_numpy(np.ascontiguousarray(points, np.float32)).cuda()
+        if isinstance(counts, np.ndarray):
+            counts = torch.from_numpy(np.ascontiguousarray(counts, np.int32)).cuda()
+        keep = [frames]
+        if torch.is_tensor(points):
+            if points.dtype != torch.float32 or not points.is_cuda or not points.is_contiguous() or \
+                    points.dim() != 3 or points.shape[0] != nw or points.shape[2] != 2:
+                raise ValueError("points must be (n_windows, slot_capacity, 2) float32, contiguous, on the device")
+            if slot_capacity is None:
+                slot_capacity = points.shape[1]
+            elif slot_capacity != points.shape[1]:
+                raise ValueError("slot_capacity differs from points.shape[1]")
+            keep.append(points)
+            points = points.data_ptr()
+        elif slot_capacity is None:
+            raise ValueError("a raw points address needs slot_capacity")
+        if torch.is_tensor(counts):
+            if counts.dtype != torch.int32 or not counts.is_cuda or not counts.is_contiguous() or counts.numel() != nw:
+                raise ValueError("counts must be (n_windows,) int32, contiguous, on the device")
+            keep.append(counts)
+            counts = counts.data_ptr()
+        if uploaded:
+            torch.cuda.synchronize()  # the uploads above ran on torch's stream
+        self._lkw_keep = keep  # kept alive until the next call
+        n, h, w = frames.shape
+        rs = frames.stride(1)
+        fs = max(frames.stride(0), rs * (h - 1) + w) if n == 1 else frames.stride(0)
+        f = self._lib.orbx_lk_track_windows_device
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
+                      C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        self._chk(f(self._h, C.c_void_p(frames.data_ptr()), n, w, h, rs, fs, _ptr(window_first), nw, window_len,
+                    C.c_void_p(points), C.c_void_p(counts) if counts else None, slot_capacity, win, max_level,
+                    max_iters, epsilon, C.c_void_p(stream) if stream else None))
+
+    def lk_windows_view(self):
+        """The device-side result block of the last windows call (orbx_lk_windows_results_device)."""
+        v = LkWindowsView()
+        self._chk(self._lib.orbx_lk_windows_results_device(self._h, C.byref(v)))
+        return v
+
+    def lk_windows_fetch(self, first=0, n=None):
+        """Windows [first, first + n) of the last windows call: tracks (n, slots, window_len, 2) float32, seen
+        (n, slots) int32, err (n, slots, window_len - 1) float32, zero past `seen` and in unused slots."""
+        v = self.lk_windows_view()
+        if n is None:
+            n = v.n_windows - first
+        m = max(n, 1)
+        tracks = np.zeros((m, v.slot_capacity, v.window_len, 2), np.float32)
+        seen = np.zeros((m, v.slot_capacity), np.int32)
+        err = np.zeros((m, v.slot_capacity, v.window_len - 1), np.float32)
+        f = self._lib.orbx_lk_windows_fetch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(f(self._h, first, n, _ptr(tracks), _ptr(seen), _ptr(err)))
+        return tracks, seen, err
+
+    def lk_workspace_limit(self, nbytes):
+        """Bound of the windows workspace in bytes (0: the default); more frames run in slices of whole windows."""
+        f = self._lib.orbx_lk_workspace_limit
+        f.argtypes = [C.c_void_p, C.c_size_t]
+        self._chk(f(self._h, nbytes))
+
+    def lk_track_window(self, frames, pts, win=21, max_level=3, max_iters=30, epsilon=0.01):
+        """orbx_lk_track_window: one window of host frames (n_frames, h, w) and host points (n, 2).  Returns tracks
+        (n, n_frames, 2), seen (n,), err (n, n_frames - 1)."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        if frames.ndim != 3:
+            raise ValueError("frames must be (n_frames, h, w) uint8")
+        nf, h, w = frames.shape
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = len(pts)
+        tracks = np.zeros((max(n, 1), nf, 2), np.float32)
+        seen = np.zeros(max(n, 1), np.int32)
+        err = np.zeros((max(n, 1), max(nf - 1, 1)), np.float32)
+        f = self._lib.orbx_lk_track_window
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
+                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]
+        self._chk(f(self._h, _ptr(frames), nf, w, h, w, w * h, _ptr(pts), n, _ptr(tracks), _ptr(seen), _ptr(err), win,
+                    max_level, max_iters, epsilon))
+        return tracks[:n].copy(), seen[:n].copy(), err[:n, :nf - 1].copy()
+
+    for f in (lk_track_windows, lk_windows_view, lk_windows_fetch, lk_workspace_limit, lk_track_window):
+        setattr(Context, f.__name__, f)
+
+
+_lk_window_methods()
 
 
 def chain_trajectory(T0, R, t, scale):
