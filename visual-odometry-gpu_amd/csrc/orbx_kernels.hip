@@ -1225,8 +1225,10 @@ __device__ __forceinline__ void describe_wave(const DescJob& jb, DescLds& lds, i
 //     trig    thread j: angle_j, cos_j, sin_j
 //     pass C  patch -> LDS again (L1/L2 hit), separable 5x5 box table,
 //             256 rotated tests, 4 ballots
-//   Keypoints whose whole 41x41 neighbourhood is inside the image (wave-uniform
-//   test) skip the per-test bounds checks.
+//   No test carries a bounds check.  For a keypoint within 20 px of the border
+//   (wave-uniform test) the patch dwords outside the level are zeroed in LDS and
+//   the table entries that the reference's skip rule excludes are tagged, so that
+//   the comparison itself yields the skipped test's 0.
 // KPW keypoints per wave (template parameter of k_describe2): 4 for throughput (the trig runs in 16 of a
 // workgroup's threads), 1 for the few-keypoint / single-frame case where the chip is nearly empty and the
 // latency of four descriptor passes in a row is what counts
@@ -1234,28 +1236,43 @@ __device__ __forceinline__ void describe_wave(const DescJob& jb, DescLds& lds, i
 
 #define DESC_NLD ((DESC_ROWS * (DESC_PITCH / 4) + 63) / 64)  // dwords per lane per patch (8)
 
-// global -> registers (all loads of a patch issued back to back; the caller
-// fetches the patches of ALL its keypoints before using the first one)
-__device__ __forceinline__ void desc_fetch_patch(const DescJob& jb, int lane, uint32_t (&regs)[DESC_NLD],
-                                                 int& off_out) {
-  const int px0 = jb.x - DESC_R, py0 = jb.y - DESC_R;
-  const int ax0 = px0 & ~3;
-  off_out = px0 - ax0;
-  int row = lane / (DESC_PITCH / 4), c = lane - row * (DESC_PITCH / 4);
+// A keypoint whose 41 x 48 neighbourhood (rows py0.., bytes ax0..) crosses the level's border: the rows
+// [rlo, rhi] and the byte columns [clo, chi] of the neighbourhood that lie inside the level, all wave-uniform.
+// 0 <= y < h and 0 <= x < w <= pitch give rlo <= 20 <= rhi and clo <= 20 <= chi.
+struct DescClip {
+  int rlo, rhi, clo, chi;
+};
+__device__ __forceinline__ DescClip desc_clip(const DescJob& jb) {
+  const int py0 = jb.y - DESC_R, ax0 = (jb.x - DESC_R) & ~3;
+  return {max(-py0, 0), min(jb.h - 1 - py0, DESC_ROWS - 1), max(-ax0, 0), min(jb.pitch - 4 - ax0, DESC_PITCH - 4)};
+}
+// how a keypoint's neighbourhood lies in its level (wave-uniform): every dword inside the (zero-padded) level /
+// only rows above the level missing (keypoints of the top rows: the common border case) / anything else
+enum { DESC_INSIDE = 0, DESC_TOP = 1, DESC_CLIPPED = 2 };
+__device__ __forceinline__ int desc_kind(const DescJob& jb) {
+  const int py0 = jb.y - DESC_R, ax0 = (jb.x - DESC_R) & ~3;
+  const bool below = py0 + DESC_ROWS <= jb.h, cols = ax0 >= 0 && ax0 + DESC_PITCH <= jb.pitch;
+  return below && cols ? (py0 >= 0 ? DESC_INSIDE : DESC_TOP) : DESC_CLIPPED;
+}
+
+// global -> registers for a border keypoint (`base` = the neighbourhood's offset in the level, wrapped where it
+// starts before the level): the same unconditional, back-to-back loads as the interior fetch, with row and dword
+// column clamped into the level, so that every address stays inside [img, img + pitch * h).  What a clamped
+// address delivers is overwritten with zeros in LDS (desc_zero_outside); the moments never see it, they are
+// taken only where the whole orientation window is inside the level.  rowk[] never exceeds the last row of the
+// neighbourhood, so for KIND == DESC_TOP the lower clamp is all there is.
+template <int KIND>
+__device__ __forceinline__ void desc_fetch_border(const DescJob& jb, uint32_t base, const int (&rowk)[DESC_NLD],
+                                                  const int (&c3)[3], uint32_t (&regs)[DESC_NLD]) {
+  const DescClip cl = desc_clip(jb);
+  int cb[3];
+#pragma unroll
+  for (int m = 0; m < 3; m++) cb[m] = KIND == DESC_TOP ? 4 * c3[m] : min(max(4 * c3[m], cl.clo), cl.chi);
 #pragma unroll
   for (int k = 0; k < DESC_NLD; k++) {
-    const int gy = py0 + row, gx = ax0 + 4 * c;
-    uint32_t v = 0;
-    if (lane + 64 * k < DESC_ROWS * (DESC_PITCH / 4) && (unsigned)gy < (unsigned)jb.h &&
-        (unsigned)gx < (unsigned)jb.pitch)
-      v = *reinterpret_cast<const uint32_t*>(jb.img + (uint32_t)(gy * jb.pitch + gx));
-    regs[k] = v;
-    row += 5;
-    c += 4;
-    if (c >= DESC_PITCH / 4) {
-      c -= DESC_PITCH / 4;
-      row += 1;
-    }
+    const int r = KIND == DESC_TOP ? max(rowk[k], cl.rlo) : min(max(rowk[k], cl.rlo), cl.rhi);
+    regs[k] = *reinterpret_cast<const uint32_t*>(
+        jb.img + (base + (__umul24((uint32_t)r, (uint32_t)jb.pitch) + (uint32_t)cb[k % 3])));
   }
 }
 
@@ -1271,6 +1288,45 @@ __device__ __forceinline__ void desc_store_patch(L& lds, int lane, const uint32_
 #pragma unroll
   for (int k = 0; k < DESC_NLD; k++)
     if (lane + 64 * k < DESC_ROWS * (DESC_PITCH / 4)) lds.patch[lane + 64 * k] = regs[k];
+}
+
+// After desc_store_patch of a border keypoint: the dwords of the LDS patch that lie outside the level become zero
+// (a wave's LDS writes land in order, so these follow the patch without a barrier).  Whole rows above and below
+// go 64 dwords at a time, the dword columns left and right one column of 41 rows at a time; every trip count is
+// wave-uniform, and none of it needs the lane's patch geometry, whose registers are free again by now.  Left and
+// right have to be cleared explicitly: a level whose width is a multiple of 64 has no padding, and a read past a
+// row's end delivers the neighbouring row.
+template <class L>
+__device__ __forceinline__ void desc_zero_outside(L& lds, int lane, const DescClip& cl) {
+  constexpr int RD = DESC_PITCH / 4;  // dwords per row
+  for (int i = lane; i < RD * cl.rlo; i += 64) lds.patch[i] = 0;
+  for (int i = RD * (cl.rhi + 1) + lane; i < RD * DESC_ROWS; i += 64) lds.patch[i] = 0;
+  if (lane < DESC_ROWS) {
+    for (int c = 0; c < cl.clo / 4; c++) lds.patch[lane * RD + c] = 0;
+    for (int c = cl.chi / 4 + 1; c < RD; c++) lds.patch[lane * RD + c] = 0;
+  }
+}
+
+// The reference skips a test unless both rotated centres lie in [2, w - 1] x [2, h - 1] (src/orb_cpu.cpp:240-245:
+// the bit is then 0).  For a keypoint within 20 px of the border, after the box table is complete: every entry
+// whose centre is outside that range is overwritten with DESC_TAG.  Entry (r, j) has the centre
+// (x - 18 - off + j, y - 18 + r), so the entries to tag are whole rows above and below (20 dwords each, written 64
+// dwords at a time) and whole columns left and right (one column of 37 rows at a time); every trip count is
+// wave-uniform.  The look-ups then need no bounds test: see the signed / unsigned reads in k_describe2.
+#define DESC_TAG 0x8000u
+template <class L>
+__device__ __forceinline__ void desc_tag_outside(L& lds, int lane, const DescJob& jb, int off) {
+  constexpr int RD = DESC_HP / 2;  // dwords per table row
+  const int rlo = min(max(DESC_R - jb.y, 0), DESC_BROWS), rhi = max(min(jb.h + 17 - jb.y, DESC_BROWS - 1), -1);
+  const int jlo = min(max(DESC_R + off - jb.x, 0), DESC_HP), jhi = max(min(jb.w + 17 + off - jb.x, DESC_HP - 1), -1);
+  uint32_t* t32 = reinterpret_cast<uint32_t*>(lds.hs);
+  for (int i = lane; i < RD * rlo; i += 64) t32[i] = DESC_TAG * 0x10001u;
+  for (int i = RD * (rhi + 1) + lane; i < RD * DESC_BROWS; i += 64) t32[i] = DESC_TAG * 0x10001u;
+  if (lane < DESC_BROWS) {
+    for (int j = 0; j < jlo; j++) lds.hs[lane * DESC_HP + j] = DESC_TAG;
+    for (int j = jhi + 1; j < DESC_HP; j++) lds.hs[lane * DESC_HP + j] = DESC_TAG;
+  }
+  wave_lds_sync();
 }
 
 __device__ __forceinline__ DescJob desc_job(const OrbxPlan& plan, const uint8_t* pyr, int f, orbx_keypoint kp,
@@ -1415,8 +1471,10 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
     int row = lane / (DESC_PITCH / 4), c = lane - row * (DESC_PITCH / 4);
 #pragma unroll
     for (int k = 0; k < DESC_NLD; k++) {
-      rowk[k] = row;
-      __builtin_assume(row >= 0 && row < DESC_ROWS + 6);
+      // (the lane dwords past the neighbourhood's end, rows 41 and 42 at k = 7, take its last row: never stored,
+      // weight 0 in the moments, and a border keypoint's unconditional loads stay inside the level)
+      rowk[k] = min(row, DESC_ROWS - 1);
+      __builtin_assume(rowk[k] >= 0 && rowk[k] < DESC_ROWS);
       if (k < 3) c3[k] = c;
       if (lane + 64 * k < DESC_ROWS * (DESC_PITCH / 4) && row >= DESC_R - pr && row <= DESC_R + pr) rin |= 1u << k;
       row += 5;
@@ -1456,10 +1514,11 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
   for (int j = 0; j < DESC_KPW; j++) {
     const DescJob& jb = jobs[j];
     const int py0 = jb.y - DESC_R, ax0 = (jb.x - DESC_R) & ~3;
-    // wave-uniform: every dword of the 41 x 48 neighbourhood lies inside the (zero-padded) level
-    if (py0 >= 0 && py0 + DESC_ROWS <= jb.h && ax0 >= 0 && ax0 + DESC_PITCH <= jb.pitch) {
-      offs[j] = jb.x - DESC_R - ax0;
-      const uint32_t base = (uint32_t)(py0 * jb.pitch + ax0);
+    offs[j] = jb.x - DESC_R - ax0;
+    // (wraps for a neighbourhood that starts before the level; the sums below bring it back)
+    const uint32_t base = (uint32_t)(py0 * jb.pitch + ax0);
+    const int kind = desc_kind(jb);
+    if (kind == DESC_INSIDE) {
 #pragma unroll
       for (int k = 0; k < DESC_NLD; k++) {
         regs[j][k] = 0;
@@ -1467,8 +1526,10 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
           // (full-rate 24-bit multiply: rows < 41, pitch <= 16384 -- v_mul_lo_u32 is a quarter-rate instruction)
           regs[j][k] = *reinterpret_cast<const uint32_t*>(jb.img + (base + (__umul24((uint32_t)rowk[k], (uint32_t)jb.pitch) + 4u * (uint32_t)c3[k % 3])));
       }
+    } else if (kind == DESC_TOP) {
+      desc_fetch_border<DESC_TOP>(jb, base, rowk, c3, regs[j]);
     } else {
-      desc_fetch_patch(jb, lane, regs[j], offs[j]);
+      desc_fetch_border<DESC_CLIPPED>(jb, base, rowk, c3, regs[j]);
     }
   }
 
@@ -1557,50 +1618,45 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
     if (j < nk) {
       const DescJob& jb = jobs[j];
       const int q = wave * DESC_KPW + j, off = offs[j];
+      // (opaque copies of the keypoint's coordinates: the border bounds are worked out again here, on the scalar
+      // unit, instead of staying live in SGPRs for all four keypoints from the fetch on, which spills)
+      DescJob jc = jb;
+      asm("" : "+s"(jc.x), "+s"(jc.y));
       desc_store_patch(lds, lane, regs[j]);
+      if (desc_kind(jc) != DESC_INSIDE) desc_zero_outside(lds, lane, desc_clip(jc));
       wave_lds_sync();
       desc_box_table_fused(lds, lane);
       const float c = s_cs[q][0], s = s_cs[q][1];
-      // every rotated centre is within 18 px of the keypoint; with a 20 px margin no test can be skipped
-      const bool interior = jb.x >= DESC_R && jb.y >= DESC_R && jb.x < jb.w - DESC_R && jb.y < jb.h - DESC_R;
+      // every rotated centre is within 18 px of the keypoint; with a 20 px margin no test can be skipped.  For any
+      // other keypoint the table entries a skipped test would read are tagged (desc_tag_outside)
+      const bool interior = jc.x >= DESC_R && jc.y >= DESC_R && jc.x < jc.w - DESC_R && jc.y < jc.h - DESC_R;
+      if (!interior) desc_tag_outside(lds, lane, jc, off);
       u64 d[4];
-      if (interior) {
-        // no test can be skipped: lround as a biased add and a truncating convert (orbx_lround_small),
-        // the table index as one 24-bit multiply-add, the constant part of the index in the instruction offset
-        const uint16_t* tbl = &lds.hs[18 * DESC_HP + 18 + off];
-        // entry (x, y): the index as one v_mad_i32_i24 (40 is an inline constant), then one shift-and-add to the
-        // address; the empty asm (no instruction) keeps the compiler from distributing the scaling over the
-        // multiply-add, which costs a third instruction per look-up
-        auto at = [&](int x, int y) {
-          int i = __mul24(y, DESC_HP) + x;
-          asm("" : "+v"(i));
-          return tbl[i];
-        };
-        // both points of a test side by side in the packed-f32 lanes (v_pk_mul/add_f32);
-        // no contraction (the TU is built with -ffp-contract=off), so each product and sum
-        // rounds like the reference's scalar code
-        const f2_t C2 = {c, c}, S2 = {s, s};
+      // lround as a biased add and a truncating convert (orbx_lround_small: rotated pattern coordinates stay below
+      // 26), the table index as one 24-bit multiply-add, the constant part of the index in the instruction offset.
+      // |dx|, |dy| <= 18 and the 37 x 40 table make every look-up memory-safe without clamps.
+      const uint16_t* tbl = &lds.hs[18 * DESC_HP + 18 + off];
+      // entry (x, y): the index as one v_mad_i32_i24 (40 is an inline constant), then one shift-and-add to the
+      // address; the empty asm (no instruction) keeps the compiler from distributing the scaling over the
+      // multiply-add, which costs a third instruction per look-up
+      auto idx = [&](int x, int y) {
+        int i = __mul24(y, DESC_HP) + x;
+        asm("" : "+v"(i));
+        return i;
+      };
+      // both points of a test side by side in the packed-f32 lanes (v_pk_mul/add_f32);
+      // no contraction (the TU is built with -ffp-contract=off), so each product and sum
+      // rounds like the reference's scalar code
+      const f2_t C2 = {c, c}, S2 = {s, s};
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const f2_t X = patx[k], Y = paty[k];
-          const i2_t rx = lround_small2(C2 * X - S2 * Y), ry = lround_small2(S2 * X + C2 * Y);
-          d[k] = __ballot(at(rx.x, ry.x) < at(rx.y, ry.y));
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const float x1 = patx[k].x, y1 = paty[k].x, x2 = patx[k].y, y2 = paty[k].y;
-          const int dx1 = orbx_lroundf(__fsub_rn(__fmul_rn(c, x1), __fmul_rn(s, y1)));
-          const int dy1 = orbx_lroundf(__fadd_rn(__fmul_rn(s, x1), __fmul_rn(c, y1)));
-          const int dx2 = orbx_lroundf(__fsub_rn(__fmul_rn(c, x2), __fmul_rn(s, y2)));
-          const int dy2 = orbx_lroundf(__fadd_rn(__fmul_rn(s, x2), __fmul_rn(c, y2)));
-          const int cx1 = jb.x + dx1, cy1 = jb.y + dy1, cx2 = jb.x + dx2, cy2 = jb.y + dy2;
-          const bool ok = !(cx1 < 2 || cy1 < 2 || cx1 > jb.w - 1 || cy1 > jb.h - 1 || cx2 < 2 || cy2 < 2 ||
-                            cx2 > jb.w - 1 || cy2 > jb.h - 1);
-          const int s1 = lds.hs[(dy1 + 18) * DESC_HP + dx1 + 18 + off];
-          const int s2 = lds.hs[(dy2 + 18) * DESC_HP + dx2 + 18 + off];
-          d[k] = __ballot(ok && s1 < s2);
-        }
+      for (int k = 0; k < 4; k++) {
+        const f2_t X = patx[k], Y = paty[k];
+        const i2_t rx = lround_small2(C2 * X - S2 * Y), ry = lround_small2(S2 * X + C2 * Y);
+        // the first sum read as u16, the second as i16: sums are <= 6375, so nothing changes for them, and a
+        // tagged entry (0x8000) is larger than any sum in the first place and smaller in the second -- the bit
+        // of a test that the reference skips comes out as 0 without a compare of its own
+        const int s1 = tbl[idx(rx.x, ry.x)], s2 = reinterpret_cast<const int16_t*>(tbl)[idx(rx.y, ry.y)];
+        d[k] = __ballot(s1 < s2);
       }
       wave_lds_sync();
       if (lane == 0) {  // the keypoint's record to LDS; the workgroup stores all of them at the end
