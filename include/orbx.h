@@ -395,6 +395,9 @@ int orbx_batch_match_fetch(orbx_ctx* ctx, int pair, int32_t* query_idx, int32_t*
  * `img1 = img2.clone()`, src/feature_tracking.cpp:112; its pyramid is still on the
  * device).  prev_pts_xy / next_pts_xy: n (x, y) float pairs; status: n bytes (1 =
  * tracked); err (optional): n floats, mean absolute window difference at level 0.
+ * A coordinate that is NaN, or whose floor does not fit an int32, is outside the image wherever a window position
+ * is tested (the previous point, every Newton step, the error window): status 0 and err 0 at level 0, the level
+ * skipped above it; the position is passed through as it is, NaN included (LK rule 9).
  * OpenCV is absent from the image this library was written in: the arithmetic
  * restates OpenCV 4.x's published algorithm (parity unpinned). */
 int orbx_lk_track(orbx_ctx* ctx, const uint8_t* prev, int prev_stride, const uint8_t* next, int next_stride,

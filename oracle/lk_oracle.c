@@ -86,6 +86,16 @@ static int lk_d(const lk_level* L, int x, int y, int c) {
 }
 static int lk_descale(int v, int n) { return (v + (1 << (n - 1))) >> n; }
 
+/* The integer origin floor(v) of a window along an axis of `len` samples, or 0 (not stored) if the window is outside:
+ * v is NaN, floor(v) does not fit an int32, or floor(v) is not in [-win, len).  Stated on the float so that nothing
+ * depends on what a float-to-int conversion makes of NaN or of a value out of range. */
+static int lk_origin(float v, int win, int len, int* ip) {
+  const float f = floorf(v);
+  if (!(f >= -2147483648.f && f < 2147483648.f)) return 0; /* false for NaN */
+  *ip = (int)f;
+  return *ip >= -win && *ip < len;
+}
+
 static int lk_build(const uint8_t* img, int w, int h, int stride, int win, int max_level, int with_deriv,
                     lk_level* lv) {
   lv[0].w = w;
@@ -156,8 +166,8 @@ int oracle_lk_track(const uint8_t* prev, const uint8_t* next, int w, int h, int 
       next_pts[2 * i + 1] = ny;
       px -= half;
       py -= half;
-      const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-      if (ipx < -win || ipx >= I->w || ipy < -win || ipy >= I->h) {
+      int ipx = 0, ipy = 0;
+      if (!lk_origin(px, win, I->w, &ipx) || !lk_origin(py, win, I->h, &ipy)) {
         if (level == 0) {
           status[i] = 0;
           if (err) err[i] = 0.f;
@@ -200,8 +210,8 @@ int oracle_lk_track(const uint8_t* prev, const uint8_t* next, int w, int h, int 
       ny -= half;
       float pdx = 0.f, pdy = 0.f;
       for (int j = 0; j < max_iters; j++) {
-        const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-        if (inx < -win || inx >= J->w || iny < -win || iny >= J->h) {
+        int inx = 0, iny = 0;
+        if (!lk_origin(nx, win, J->w, &inx) || !lk_origin(ny, win, J->h, &iny)) {
           if (level == 0) status[i] = 0;
           break;
         }
@@ -235,8 +245,8 @@ int oracle_lk_track(const uint8_t* prev, const uint8_t* next, int w, int h, int 
       }
       if (status[i] && err && level == 0) {
         const float ex = next_pts[2 * i] - half, ey = next_pts[2 * i + 1] - half;
-        const int inx = (int)floorf(ex), iny = (int)floorf(ey);
-        if (inx < -win || inx >= J->w || iny < -win || iny >= J->h) {
+        int inx = 0, iny = 0;
+        if (!lk_origin(ex, win, J->w, &inx) || !lk_origin(ey, win, J->h, &iny)) {
           status[i] = 0;
           continue;
         }

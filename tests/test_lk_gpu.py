@@ -1,8 +1,11 @@
-"""Pyramidal Lucas-Kanade tracker: HIP path vs the CPU oracle, bit for bit
-(positions compared as float bit patterns, status and error exactly), through the C ABI."""
+"""Pyramidal Lucas-Kanade tracker: HIP path vs the CPU oracle and vs the numpy restatement
+written from the rules (tests/lk_ref.py), bit for bit (positions compared as float bit patterns, status and error
+exactly), through the C ABI."""
 import numpy as np
 import pytest
 
+import lk_cases as K
+import lk_ref
 import oracle_lib as O
 from test_lk_oracle import smooth_image
 
@@ -20,13 +23,25 @@ def same(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
-def check(ctx, prev, nxt, pts, **kw):
+def check(ctx, prev, nxt, pts, ref=None, **kw):
+    """ref: lk_ref.track's result if the caller holds it; otherwise it is computed here for the small cases (up to
+    150 points on up to 2^16 pixels); the large ones are compared with the oracle only"""
     ro, rs, re, _ = O.lk_track(prev, nxt, pts, **kw)
     go, gs, ge = ctx.lk_track(prev, nxt, pts, **kw)
-    assert np.array_equal(gs, rs)
+    assert np.array_equal(gs, rs), np.flatnonzero(gs != rs)
     assert same(go, ro), np.abs(go - ro).max()
     assert same(ge, re)
+    if ref is None and len(pts) <= 150 and nxt.size <= 1 << 16:
+        ref = lk_ref.track(prev, nxt, pts, **kw)
+    if ref is not None:
+        assert np.array_equal(gs, ref[1]), np.flatnonzero(gs != ref[1])
+        assert same(go, ref[0]) and same(ge, ref[2])
     return go, gs, ge
+
+
+def check_case(ctx, name):
+    prev, nxt, pts, kw = K.case(name)
+    return check(ctx, prev, nxt, pts, ref=K.ref(name), **kw)
 
 
 def test_kitti_pair_reference_parameters(ctx):
@@ -94,3 +109,56 @@ def test_min_eigenvalue_borderline_case(ctx):
     import os
     z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lk_min_eig_case.npz"))
     check(ctx, z["a"], z["b"], z["pts"], win=14, max_level=0, max_iters=31, epsilon=0.0)
+    check_case(ctx, "min-eig")  # the same input, with the restatement beside the oracle
+
+
+def test_every_window_size(ctx):
+    """the two magic-reciprocal divisions (by win and by win + 5) and the LDS layout depend on win"""
+    for win in range(3, 32):
+        check_case(ctx, "win-%d" % win)
+
+
+@pytest.mark.parametrize("k", range(len(K.SPECIAL_PARAMS)))
+def test_special_points(ctx, k):
+    """tests/lk_cases.py special_points: both sides of every bound, weights of 16384 / 0, NaN, infinities and values
+    beyond int32 -- a NaN coordinate is outside (status 0, error 0), it does not enter at origin 0"""
+    pts = K.case("special-%d" % k)[2]
+    out, st, err = check_case(ctx, "special-%d" % k)
+    nan = np.isnan(pts).any(1)
+    assert nan.sum() == 3 and not st[nan].any() and not err[nan].any()
+    assert np.array_equal(np.isnan(out[nan]), np.isnan(pts[nan]))
+
+
+def test_final_position_outside_the_next_image(ctx):
+    """tests/golden/lk_err_out_cases.npz: the error stage's own bounds test (tests/test_lk_ref.py asserts from the
+    trace that these inputs reach it)"""
+    for name in K.err_out_cases():
+        assert any(r["reason"] == "err_out" for r in K.ref(name)[4])
+        check_case(ctx, name)
+
+
+def test_next_image_cache_is_refetched(ctx):
+    """A 4.6 x 3.3 px shift walked by the Newton steps of one level: the window's integer origin leaves the 2 px
+    margin of the LDS cache of the next image, which then has to be fetched again -- asserted from the trace, for
+    neighbourhoods inside the image (the plain loads) and over its border (the reflected ones)."""
+    inside = border = 0
+    for name in K.refetch_cases():
+        for r in K.ref(name)[4]:
+            if r["moved"] is not None and r["moved"] > 2:
+                inside += bool(r["inside"])
+                border += not r["inside"]
+    print("origins that moved more than 2 px: %d inside, %d over the border" % (inside, border))
+    assert inside >= 30 and border >= 30, (inside, border)
+    for name in K.refetch_cases():
+        check_case(ctx, name)
+
+
+def test_point_counts_around_the_workgroup(ctx):
+    """four waves (points) per workgroup: counts that leave 1, 3, 0 and 1 waves in the last one, and 257"""
+    prev, nxt, _, kw = K.case("win-21")
+    rng = np.random.default_rng(257)
+    pts = np.stack([rng.uniform(-8, 96, 257), rng.uniform(-8, 80, 257)], 1).astype(np.float32)
+    ref = lk_ref.track(prev, nxt, pts, **kw)
+    assert 0 < ref[1].sum() < 257
+    for n in (1, 3, 4, 5, 257):
+        check(ctx, prev, nxt, pts[:n], ref=[a[:n] for a in ref[:3]], **kw)

@@ -3,8 +3,14 @@
 pyrDown / Scharr on small hand-checkable inputs (independent numpy restatement) and the tracker's
 behaviour on synthetic motion with a known answer."""
 import numpy as np
+import pytest
 
+import lk_ref
 import oracle_lib as O
+from lk_ref import np_pyr_down, np_scharr
+
+# the two restatements of the tracker: the C oracle, and numpy written from the rules (tests/lk_ref.py)
+TRACKERS = pytest.mark.parametrize("track", [O.lk_track, lk_ref.track], ids=["oracle", "numpy"])
 
 
 def smooth_image(seed, h, w):
@@ -24,27 +30,6 @@ def smooth_image(seed, h, w):
     return f
 
 
-def np_pyr_down(img):
-    h, w = img.shape
-    k = np.array([1, 4, 6, 4, 1])
-    p = np.pad(img.astype(np.int64), 2, mode="reflect")
-    dh, dw = (h + 1) // 2, (w + 1) // 2
-    out = np.zeros((dh, dw), np.int64)
-    for i in range(5):
-        for j in range(5):
-            out += k[i] * k[j] * p[i:i + 2 * dh:2, j:j + 2 * dw:2][:dh, :dw]
-    return ((out + 128) >> 8).astype(np.uint8)
-
-
-def np_scharr(img):
-    p = np.pad(img.astype(np.int64), 1, mode="reflect")
-    h, w = img.shape
-    s = lambda dy, dx: p[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
-    dx = 3 * (s(-1, 1) - s(-1, -1)) + 10 * (s(0, 1) - s(0, -1)) + 3 * (s(1, 1) - s(1, -1))
-    dy = 3 * (s(1, -1) - s(-1, -1)) + 10 * (s(1, 0) - s(-1, 0)) + 3 * (s(1, 1) - s(-1, 1))
-    return np.stack([dx, dy], -1).astype(np.int16)
-
-
 def test_pyr_down_and_scharr_vs_numpy():
     rng = np.random.default_rng(0)
     for shape in ((31, 47), (64, 64), (33, 2 * 21 + 3), (376, 1241)):
@@ -58,14 +43,15 @@ def test_pyr_down_and_scharr_vs_numpy():
     assert np.all(d[2:-2, 2:-2, 0] == 16 * 2 * 3) and not d[2:-2, 2:-2, 1].any()  # (3+10+3) * (I[x+1]-I[x-1])
 
 
-def test_tracker_recovers_known_translation():
+@TRACKERS
+def test_tracker_recovers_known_translation(track):
     f = smooth_image(1, 240, 320)
     prev = f(0, 0)
     rng = np.random.default_rng(2)
     pts = np.stack([rng.uniform(40, 280, 200), rng.uniform(40, 200, 200)], 1).astype(np.float32)
     for dx, dy in ((0.0, 0.0), (1.25, -0.5), (-3.6, 2.3), (7.5, 5.25), (-13.0, 9.0)):
         nxt = f(-dx, -dy)  # content moves by (+dx, +dy)
-        out, st, err, top = O.lk_track(prev, nxt, pts)
+        out, st, err, top = track(prev, nxt, pts)
         assert top == 3
         assert st.mean() > 0.97, (dx, dy, st.mean())
         e = np.abs(out[st == 1] - pts[st == 1] - np.float32([dx, dy]))
@@ -73,21 +59,22 @@ def test_tracker_recovers_known_translation():
         assert np.median(err[st == 1]) < 2.0
 
 
-def test_tracker_status_and_levels():
+@TRACKERS
+def test_tracker_status_and_levels(track):
     f = smooth_image(3, 120, 160)
     prev, nxt = f(0, 0), f(-2.0, 0.0)
     pts = np.float32([[80, 60], [-40, 60], [400, 60], [80, -50], [159, 119], [0, 0]])
-    out, st, err, top = O.lk_track(prev, nxt, pts)
+    out, st, err, top = track(prev, nxt, pts)
     assert top == 2  # 160x120 -> 80x60 -> 40x30 -> (20x15 is not larger than the 21x21 window)
     assert st[0] == 1 and abs(out[0, 0] - 82) < 0.1 and abs(out[0, 1] - 60) < 0.1
     assert st[1] == 0 and st[2] == 0 and st[3] == 0  # window entirely outside the image
     # a textureless pair: the minimum-eigenvalue test rejects every point
     flat = np.full((120, 160), 90, np.uint8)
-    out, st, err, _ = O.lk_track(flat, flat, pts[:1])
+    out, st, err, _ = track(flat, flat, pts[:1])
     assert st[0] == 0
     # zero iterations: the point is only propagated through the levels
-    out, st, err, _ = O.lk_track(prev, nxt, pts[:1], max_iters=0)
+    out, st, err, _ = track(prev, nxt, pts[:1], max_iters=0)
     assert st[0] == 1 and np.array_equal(out[0], pts[0])
     # n = 0
-    out, st, err, _ = O.lk_track(prev, nxt, np.zeros((0, 2), np.float32))
+    out, st, err, _ = track(prev, nxt, np.zeros((0, 2), np.float32))
     assert len(out) == 0

@@ -5,6 +5,8 @@ including the zero tail."""
 import numpy as np
 import pytest
 
+import lk_cases as K
+import lk_ref
 import lk_window_ref as R
 import oracle_lib as O
 from test_lk_oracle import smooth_image
@@ -137,6 +139,33 @@ def test_flat_window_and_smallest_frame(ctx):
     ctx.lk_track_windows(small, [0], 3, pts[None])
     same([a[0] for a in ctx.lk_windows_fetch()], ref)
     same(ctx.lk_track_window(small, pts), ref)
+
+
+def test_special_points_against_the_numpy_restatement(ctx):
+    """Three overlapping windows of three 56 x 48 frames, 64 slots, ragged counts, the special points of
+    tests/lk_cases.py (bounds from both sides, NaN, infinities, values beyond int32) among random ones: the chain of
+    tests/lk_window_ref.py on the numpy tracker (tests/lk_ref.py) and on the oracle, bit for bit.  A NaN point is seen
+    in its first frame only."""
+    h, w = 48, 56
+    frames = R.shifted_frames(7, h, w, 5, (-1.3, 0.6))
+    special = K.special_points(21, w, h)
+    rng = np.random.default_rng(56)
+    pts = np.stack([rng.uniform(-12, w + 12, (3, 64)), rng.uniform(-12, h + 12, (3, 64))], 2).astype(np.float32)
+    pts[0, :len(special)] = special
+    pts[1, 2:5] = special[21:24]               # the NaN points inside a window of 5 points
+    pts[2, 64 - len(special):] = special[::-1]
+    first, counts = [0, 2, 1], np.int32([64, 5, 61])
+    ref = R.track_windows(frames, first, 3, pts, counts, track=lk_ref.track, **R.REFERENCE)
+    assert [R.lengths(ref[1][k], 3)[2] > 0 for k in range(3)] == [True] * 3  # tracks that live through each window
+    ctx.lk_track_windows(frames, first, 3, pts, counts)
+    got = ctx.lk_windows_fetch()
+    same(got, ref)
+    same(got, R.track_windows(frames, first, 3, pts, counts, **R.REFERENCE))
+    tracks, seen, err = got
+    nan = np.isnan(pts).any(2) & (np.arange(64)[None] < counts[:, None])
+    assert nan.sum() == 3 + 3 + 3 and (seen[nan] == 1).all()
+    assert np.array_equal(bits(tracks[nan][:, 0]), bits(pts[nan])) and not tracks[nan][:, 1:].any() and not err[nan].any()
+    same(ctx.lk_track_window(frames[:3], pts[0]), [a[0] for a in ref])  # the host entry
 
 
 def strided(frames, fill_seed):

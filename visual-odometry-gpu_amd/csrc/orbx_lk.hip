@@ -130,6 +130,15 @@ __device__ __forceinline__ short2 lk_deriv_at(const OrbxLkLevel& L, int X, int Y
   return reinterpret_cast<const short2*>(L.deriv)[(size_t)Y * L.w + X];
 }
 
+// The integer origin floor(v) of a window along an axis of `len` samples; false if the window is outside: v is NaN,
+// floor(v) does not fit an int32, or floor(v) is not in [-win, len).  (The conversion alone would turn NaN into 0,
+// an origin inside the image.)  Wave-uniform.
+__device__ __forceinline__ bool lk_origin(float v, int win, int len, int& i) {
+  const float f = floorf(v);
+  i = (int)f;
+  return f >= -2147483648.f && f < 2147483648.f && i >= -win && i < len;
+}
+
 #define LK_MAX_WIN 31
 // one pass over the window items of a lane: unrolled when the trip count is a template constant
 #define LK_ITEM_LOOP                                                                           \
@@ -263,8 +272,8 @@ __device__ __forceinline__ void lk_track_point(const Pyr& P, const Pyr& N, int t
     outy = ny;
     px -= half;
     py -= half;
-    const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-    if (ipx < -win || ipx >= I.w || ipy < -win || ipy >= I.h) {
+    int ipx, ipy;
+    if (!lk_origin(px, win, I.w, ipx) || !lk_origin(py, win, I.h, ipy)) {
       if (level == 0) {
         st = 0;
         ev = 0.f;
@@ -303,8 +312,8 @@ __device__ __forceinline__ void lk_track_point(const Pyr& P, const Pyr& N, int t
     ny -= half;
     float pdx = 0.f, pdy = 0.f;
     for (int j = 0; j < max_iters; j++) {
-      const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-      if (inx < -win || inx >= J.w || iny < -win || iny >= J.h) {
+      int inx, iny;
+      if (!lk_origin(nx, win, J.w, inx) || !lk_origin(ny, win, J.h, iny)) {
         if (level == 0) st = 0;
         break;
       }
@@ -336,8 +345,8 @@ __device__ __forceinline__ void lk_track_point(const Pyr& P, const Pyr& N, int t
     }
     if (st && level == 0) {
       const float ex = __fsub_rn(outx, half), ey = __fsub_rn(outy, half);
-      const int inx = (int)floorf(ex), iny = (int)floorf(ey);
-      if (inx < -win || inx >= J.w || iny < -win || iny >= J.h) {
+      int inx, iny;
+      if (!lk_origin(ex, win, J.w, inx) || !lk_origin(ey, win, J.h, iny)) {
         st = 0;
         continue;
       }
