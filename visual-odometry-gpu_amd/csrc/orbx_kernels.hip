@@ -414,77 +414,109 @@ __device__ __forceinline__ float harris_at(const uint8_t* img, int w, int h, int
 // Fast path for window K <= 7 and keypoints whose (K+2)^2 pixel neighbourhood leaves
 // the image by at most ONE row / column (FAST keypoints keep 3 px from the border,
 // so with K = 7 that is every keypoint of the whole path; the reflected row is a
-// different row pointer, the reflected column one v_perm per row): the
-// neighbourhood is fetched once with 3 aligned dword loads per row and
-// byte-aligned in registers (v_alignbyte), pixels are converted with
-// v_cvt_f32_ubyteN, Sobel sums are shared between neighbouring taps.  Every
-// intermediate is a small exact integer in float, and the weighted
-// accumulation keeps the (i,j) order and the separate mul/mul/add roundings of
-// harris_at, so the result is bit-identical to it.
+// different row pointer, the reflected column one v_perm per row).  A row of the
+// neighbourhood is 3 aligned dword loads, byte-aligned in registers (v_alignbyte)
+// and unpacked with v_perm into u16 PAIRS: E[k] = (p[2k], p[2k+1]) and
+// O[k] = (p[2k+1], p[2k+2]).  The Sobel sums are formed two at a time on those pairs
+// (v_pk_add_u16 / v_pk_sub_i16; a 1-2-1 sum is at most 1020, a difference at most
+// 1020 in magnitude), and only gx and gy become floats (v_cvt_f32_i32 on a 16-bit
+// half).  The rows are requested a few ahead of the row being consumed, so the live
+// set is two packed rows of vertical partial sums, three packed rows of horizontal
+// sums and the dwords in flight (the compiler's scheduler moves the loads as the
+// register bound of the kernel allows: k_level_select<7> and k_lvl_harris fit 80
+// VGPRs without scratch, `make resource-usage`).
+// Every integer intermediate is exact, and the weighted accumulation keeps the
+// (i,j) order and the separate mul/mul/add roundings of harris_at, so the result
+// is bit-identical to it.
+#define HARRIS_AHEAD 2  // rows fetched ahead of the row being unpacked
 template <int K>
 __device__ __forceinline__ float harris_fast(const uint8_t* img, int w, int h, int pitch, int x, int y,
                                              const float* __restrict__ g, float kk) {
   constexpr int r = K / 2, P = K + 2;
+  constexpr int NE = (P + 1) / 2, NH = (K + 1) / 2;  // pairs of a pixel row / of a row of Sobel sums
   static_assert(P <= 9, "the third dword of a row supplies pixel 8 only");
   const int xs = x - r - 1;               // >= -1
   const int a0 = xs & ~3, off = xs - a0;  // xs == -1: a0 = -4, off = 3
-  // BORDER_REFLECT_101 of the one column that may lie outside: pixel -1 is pixel 1
-  // (byte 2 of the first aligned group), pixel w is pixel w-2 (byte 2 of the second)
-  const uint32_t sel_l = xs < 0 ? 0x03020102u : 0x03020100u;
-  const uint32_t sel_r = xs + P - 1 >= w ? 0x0c0c0c06u : 0x0c0c0c00u;
-  // all (K+2) x 3 dword loads first (one memory latency), then the window is
-  // consumed row by row with three rolling pixel rows / horizontal sums, which
-  // keeps the live set around 100 VGPRs instead of 160+
+  // BORDER_REFLECT_101 of the one column that may lie outside: pixel -1 is pixel 1 (window pixel 0 takes window
+  // pixel 2), pixel w is pixel w-2 (window pixel P-1 takes window pixel P-3).  perm(a, b, sel): selector bytes
+  // 0..3 pick from b, 4..7 from a
+  constexpr int dr = P - 1, sr = P - 3;
+  constexpr uint32_t id = 0x03020100u;
+  constexpr uint32_t rfl = (id & ~(0xffu << (8 * (dr & 3)))) | ((uint32_t)(4 + (sr & 3)) << (8 * (dr & 3)));
+  const uint32_t sel_l = xs < 0 ? 0x03020102u : id;
+  const uint32_t sel_r = xs + P - 1 >= w ? rfl : id;
   uint32_t raw[P][3];
-#pragma unroll
-  for (int i = 0; i < P; i++) {
+  auto fetch = [&](int i) {
     int yy = y - r - 1 + i;  // only the first / last row can be outside (by one)
     if (i == 0) yy = yy < 0 ? 1 : yy;
     if (i == P - 1) yy = yy >= h ? h - 2 : yy;
     const int o = yy * pitch + a0;
     // o == -4 only in row 0 with the left column reflected; that dword supplies nothing
     // but the replaced pixel, so any readable address will do
-    raw[i][0] = *reinterpret_cast<const uint32_t*>(img + max(o, 0));
-    raw[i][1] = *reinterpret_cast<const uint32_t*>(img + (o + 4));
-    raw[i][2] = *reinterpret_cast<const uint32_t*>(img + (o + 8));  // may run into the next row / the pool's tail slack
-  }
-  auto cvt_row = [&](int i, float (&out)[P]) {
+    // (unsigned 32-bit offsets from the level's base: one address register per load, not a 64-bit pair)
+    const uint32_t o1 = (uint32_t)(o + 4);
+    raw[i][0] = *reinterpret_cast<const uint32_t*>(img + (uint32_t)max(o, 0));
+    raw[i][1] = *reinterpret_cast<const uint32_t*>(img + o1);
+    raw[i][2] = *reinterpret_cast<const uint32_t*>(img + o1 + 4);  // may run into the next row / the pool's tail slack
+  };
+  // window pixels a and b of a row as one u16 pair (b past the row: 0)
+  auto pair = [&](const uint32_t (&q)[3], int pa, int pb) {
+    const uint32_t sel = 0x0c000c00u | (uint32_t)(pa & 3) | (pb < P ? (uint32_t)(4 + (pb & 3)) << 16 : 0x000c0000u);
+    return __builtin_amdgcn_perm(q[pb < P ? pb >> 2 : 0], q[pa >> 2], sel);
+  };
+  // row i: E pairs in e[], horizontal 1-2-1 sums (hs[2k], hs[2k+1]) in hs[]
+  auto unpack = [&](int i, uint32_t (&e)[NE], uint32_t (&hs)[NH]) {
     uint32_t q[3] = {__builtin_amdgcn_alignbyte(raw[i][1], raw[i][0], off),
                      __builtin_amdgcn_alignbyte(raw[i][2], raw[i][1], off), raw[i][2] >> (8 * off)};
-    q[2] = __builtin_amdgcn_perm(q[1], q[2], sel_r);
+    q[dr >> 2] = __builtin_amdgcn_perm(q[sr >> 2], q[dr >> 2], sel_r);
     q[0] = __builtin_amdgcn_perm(q[0], q[0], sel_l);
 #pragma unroll
-    for (int j = 0; j < P; j++) out[j] = (float)((q[j >> 2] >> (8 * (j & 3))) & 0xffu);
-  };
-  auto hsum = [&](const float (&pr)[P], float (&out)[K]) {
+    for (int k = 0; k < NE; k++) e[k] = pair(q, 2 * k, 2 * k + 1);
 #pragma unroll
-    for (int j = 0; j < K; j++) out[j] = pr[j] + 2.0f * pr[j + 1] + pr[j + 2];
+    for (int k = 0; k < NH; k++) {
+      const uint32_t o = pair(q, 2 * k + 1, 2 * k + 2);
+      hs[k] = pk_add(pk_add(e[k], o), pk_add(o, e[k + 1]));
+    }
   };
-  float pr[3][P], hs[3][K];
-  cvt_row(0, pr[0]);
-  cvt_row(1, pr[1]);
-  hsum(pr[0], hs[0]);
-  hsum(pr[1], hs[1]);
+#pragma unroll
+  for (int i = 0; i < HARRIS_AHEAD && i < P; i++) fetch(i);
+  // t[k]: rows i and i+1 added (vertical partial sum), the window row's 1-2-1 column sum is t(i) + t(i+1)
+  uint32_t e0[NE], e1[NE], t[NE], hs[3][NH];
+  if (HARRIS_AHEAD < P) fetch(HARRIS_AHEAD);
+  unpack(0, e0, hs[0]);
+  if (HARRIS_AHEAD + 1 < P) fetch(HARRIS_AHEAD + 1);
+  unpack(1, e1, hs[1]);
+#pragma unroll
+  for (int k = 0; k < NE; k++) t[k] = pk_add(e0[k], e1[k]);
   float a = 0.f, b = 0.f, c = 0.f;
 #pragma unroll
   for (int i = 0; i < K; i++) {
-    // rows i, i+1, i+2 of the patch live in slots i%3, (i+1)%3, (i+2)%3
-    float(&p0)[P] = pr[i % 3];
-    float(&p1)[P] = pr[(i + 1) % 3];
-    float(&p2)[P] = pr[(i + 2) % 3];
-    cvt_row(i + 2, p2);
-    hsum(p2, hs[(i + 2) % 3]);
-    float vs[P];
+    // patch rows i, i+1, i+2 feed window row i; their hs live in slots i%3, (i+1)%3, (i+2)%3; e1 is row i+1
+    if (i + 2 + HARRIS_AHEAD < P) fetch(i + 2 + HARRIS_AHEAD);
+    uint32_t e2[NE], vs[NE];
+    unpack(i + 2, e2, hs[(i + 2) % 3]);
 #pragma unroll
-    for (int j = 0; j < P; j++) vs[j] = p0[j] + 2.0f * p1[j] + p2[j];
+    for (int k = 0; k < NE; k++) {
+      const uint32_t t2 = pk_add(e1[k], e2[k]);
+      vs[k] = pk_add(t[k], t2);
+      t[k] = t2;
+      e1[k] = e2[k];
+    }
 #pragma unroll
-    for (int j = 0; j < K; j++) {
-      const float gx = vs[j + 2] - vs[j];
-      const float gy = hs[(i + 2) % 3][j] - hs[i % 3][j];
-      const float wgt = g[i * K + j];
-      a = __fadd_rn(a, __fmul_rn(__fmul_rn(gx, gx), wgt));
-      c = __fadd_rn(c, __fmul_rn(__fmul_rn(gy, gy), wgt));
-      b = __fadd_rn(b, __fmul_rn(__fmul_rn(gx, gy), wgt));
+    for (int k = 0; k < NH; k++) {
+      const uint32_t gx2 = pk_sub(vs[k + 1], vs[k]);  // (vs[2k+2] - vs[2k], vs[2k+3] - vs[2k+1])
+      const uint32_t gy2 = pk_sub(hs[(i + 2) % 3][k], hs[i % 3][k]);
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int j = 2 * k + s;
+        if (j >= K) break;
+        const float gx = s ? (float)((int32_t)gx2 >> 16) : (float)(int16_t)gx2;
+        const float gy = s ? (float)((int32_t)gy2 >> 16) : (float)(int16_t)gy2;
+        const float wgt = g[i * K + j];
+        a = __fadd_rn(a, __fmul_rn(__fmul_rn(gx, gx), wgt));
+        c = __fadd_rn(c, __fmul_rn(__fmul_rn(gy, gy), wgt));
+        b = __fadd_rn(b, __fmul_rn(__fmul_rn(gx, gy), wgt));
+      }
     }
   }
   const float det = __fsub_rn(__fmul_rn(a, c), __fmul_rn(b, b));
@@ -663,7 +695,7 @@ __global__ __launch_bounds__(256) void k_harris2_flat(const uint8_t* __restrict_
 // per-level count; k_describe2 compacts them into the final order.
 #define LVL_THREADS 512
 #define LVL_WAVES (LVL_THREADS / 64)
-#define LVL_Q 16    // mask words per lane and round of a compaction walk (1024 per wave in flight)
+#define LVL_Q 16    // consecutive mask words a lane owns in a chunk of a compaction walk (1024 per wave and chunk)
 #define LVL_RUN 64  // keys per sorted run
 #define LVL_MAX_SLOTS 4096  // candidate slots of a frame the kernel holds in LDS (16 B each)
 
@@ -705,9 +737,18 @@ __device__ __forceinline__ int lvl_of_run(const int* s_runs, int l0, int l1, int
   return l;
 }
 
+// The lane index, worked out again where it is used (v_mbcnt of an all-ones mask) instead of being carried in a
+// register from the kernel's entry: the zero it starts from passes through an empty `asm`, so the compiler can neither
+// merge this with an earlier copy nor hoist it, and the value is not live before this point
+__device__ __forceinline__ int lane_reread() {
+  uint32_t z = 0;
+  asm volatile("" : "+v"(z));
+  return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+}
+
 // KF: the Harris window of the fast path (3, 5 or 7; 0: none, every candidate through harris_at)
 template <int KF>
-__global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_level_select(
+__global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_level_select(
     OrbxPlan plan, int lpg, int mode, const u64* __restrict__ mask, const uint8_t* __restrict__ pyr,
     const float* __restrict__ gauss, int K, float kk, orbx_keypoint* __restrict__ sel_lkp,
     float* __restrict__ sel_resp, int32_t* __restrict__ sel_count, uint32_t* __restrict__ need) {
@@ -733,21 +774,23 @@ __global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     const u64* m = mask + (size_t)f * plan.mask_words + L.mask_off;
     const int nwords = L.h * L.mask_wpr;
     int base = 0, last = -1;  // last: row of survivor cap - 1 (in the lane that found it)
+    // A lane owns LVL_Q consecutive words of the chunk: their popcounts and the prefix over them stay in its
+    // registers, ONE wave scan of the lanes' totals places them, and the lane emits its words in order (row-major)
     for (int w0 = 0; w0 < nwords && base < cap; w0 += 64 * LVL_Q) {
+      const int i0 = w0 + LVL_Q * lane;
       u64 v[LVL_Q];
+      int tot = 0;
 #pragma unroll
       for (int q = 0; q < LVL_Q; q++) {
-        const int i = w0 + 64 * q + lane;
-        v[q] = i < nwords ? m[i] : 0ull;
+        v[q] = i0 + q < nwords ? m[i0 + q] : 0ull;
+        tot += __popcll(v[q]);
       }
+      const int incl = wave_scan_incl(tot);
+      int pos = base + incl - tot;
+      if (tot && pos < cap) {
+        int y = i0 / L.mask_wpr, xw = i0 - y * L.mask_wpr;
 #pragma unroll
-      for (int q = 0; q < LVL_Q; q++) {
-        const int c = __popcll(v[q]);
-        const int incl = wave_scan_incl(c);
-        int pos = base + incl - c;
-        if (c && pos < cap) {
-          const int i = w0 + 64 * q + lane;
-          const int y = i / L.mask_wpr, xw = i - y * L.mask_wpr;
+        for (int q = 0; q < LVL_Q; q++) {
           u64 w = v[q];
           while (w && pos < cap) {
             const int b = __ffsll((long long)w) - 1;
@@ -765,9 +808,13 @@ __global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
             if (pos == cap - 1) last = y;
             pos++;
           }
+          if (++xw == L.mask_wpr) {
+            xw = 0;
+            y++;
+          }
         }
-        base += __builtin_amdgcn_readlane(incl, 63);
       }
+      base += __builtin_amdgcn_readlane(incl, 63);
     }
     const int n = base < cap ? base : cap;
     const int keep = n < L.quota ? n : L.quota;
@@ -795,24 +842,30 @@ __global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
   // Second pass, over the same runs: the rest through harris_at, then the run's keys are sorted in registers.  With
   // both paths in one loop the kernel spills at 128 registers.
   const uint8_t* img_f = pyr + (size_t)f * plan.frame_bytes;
-  if (KF > 0) {
+  if constexpr (KF > 0) {
     for (int t = wave; t < nruns; t += LVL_WAVES) {
       int r = t;
       const int l = lvl_of_run(s_runs, l0, l1, r);
       const OrbxLevel& L = plan.L[l];
-      const int slot = lvl_slots(plan, l), i = LVL_RUN * r + lane;
+      const int slot = lvl_slots(plan, l), i = LVL_RUN * r + lane_reread();
       const bool live = i < __builtin_amdgcn_readfirstlane(s_n[l]);
       const uint32_t p = live ? s_kp[slot + i] : 0u;
       const int x = (int)(p & 0xffffu), y = (int)(p >> 16);
       const bool fast = live && harris_fast_ok(L.w, L.h, x, y, KF);
-      if (fast) s_r[slot + i] = harris_fast<KF>(img_f + L.img_off, L.w, L.h, L.pitch, x, y, gauss, kk);
+      if (fast) {
+        const float resp = harris_fast<KF>(img_f + L.img_off, L.w, L.h, L.pitch, x, y, gauss, kk);
+        // the lane index is read again here instead of being carried through the Harris arithmetic, whose live set
+        // decides the kernel's register count (80 VGPRs: 6 waves per SIMD)
+        s_r[slot + LVL_RUN * r + lane_reread()] = resp;
+      }
     }
   }
   for (int t = wave; t < nruns; t += LVL_WAVES) {
     int r = t;
     const int l = lvl_of_run(s_runs, l0, l1, r);
     const OrbxLevel& L = plan.L[l];
-    const int slot = lvl_slots(plan, l), i = LVL_RUN * r + lane;
+    const int ln = lane_reread();
+    const int slot = lvl_slots(plan, l), i = LVL_RUN * r + ln;
     u64 key = 0ull;  // past the level's count: below every real key
     if (i < __builtin_amdgcn_readfirstlane(s_n[l])) {
       const uint32_t p = s_kp[slot + i];
@@ -830,7 +883,7 @@ __global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
       u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
       key = ((u64)u << 32) | (uint32_t)~(uint32_t)i;
     }
-    s_key[slot + i] = wave_sort_desc(key, lane);
+    s_key[slot + i] = wave_sort_desc(key, ln);
   }
   __syncthreads();
   // phase 3b: rank = place in the own run + keys above it in the level's other runs
@@ -839,8 +892,9 @@ __global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     const int l = lvl_of_run(s_runs, l0, l1, r);
     const int slot = lvl_slots(plan, l);
     const int runs = __builtin_amdgcn_readfirstlane(s_runs[l]);
-    const u64 k = s_key[slot + LVL_RUN * r + lane];
-    int rank = lane;
+    const int ln = lane_reread();
+    const u64 k = s_key[slot + LVL_RUN * r + ln];
+    int rank = ln;
     for (int o = 0; o < runs; o++) {
       if (o == r) continue;
       const u64* run = s_key + slot + LVL_RUN * o;
@@ -935,7 +989,7 @@ __global__ __launch_bounds__(256) void k_lvl_compact(OrbxPlan plan, const u64* _
   if (need && tid == 0 && cap > 0) atomicMax(&need[l], base >= cap ? (out[cap - 1] >> 16) + 1u : (uint32_t)L.h);
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_lvl_harris(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_lvl_harris(
     OrbxPlan plan, const uint8_t* __restrict__ pyr, const float* __restrict__ gauss, int K, float kk,
     const uint32_t* __restrict__ cand, const int32_t* __restrict__ ncand, float* __restrict__ resp) {
   const int l = blockIdx.y, f = blockIdx.z;
