@@ -279,6 +279,31 @@ def test_device_chain_from_good_features(ctx):
     same([a[0] for a in got], ref)
 
 
+def test_device_chain_from_good_features_across_callers_streams(pkg, ctx):
+    """the same chain with the corners made on one caller's stream and tracked on another, and no host synchronisation
+    in between: the tracker's stream has to wait for the good-features event before it reads the view"""
+    import ctypes as C
+
+    import torch
+
+    crops = np.stack([np.ascontiguousarray(O.load_kitti(i)[100:260, 300:620]) for i in (0, 1)])
+    t = torch.from_numpy(crops).cuda()
+    torch.cuda.synchronize()
+    hip = pkg.orbx.load()
+    sa, sb = C.c_void_p(), C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(sa)) == 0 and hip.hipStreamCreate(C.byref(sb)) == 0
+    ctx.good_features_batch(t, 2000, 0.01, 8.0, stream=sa.value)
+    v = ctx.good_features_view()
+    ctx.lk_track_windows(t, [0], 2, v.corners_xy, v.counts, slot_capacity=v.slot_capacity, stream=sb.value)
+    got = ctx.lk_windows_fetch()
+    corners = ctx.good_features_fetch()[0]
+    assert hip.hipStreamDestroy(sb) == 0 and hip.hipStreamDestroy(sa) == 0
+    assert 100 < len(corners) <= v.slot_capacity
+    ref = R.track_window(crops, corners, slots=v.slot_capacity, **R.REFERENCE)
+    assert (ref[1][:len(corners)] == 2).mean() > 0.9
+    same([a[0] for a in got], ref)
+
+
 def test_reference_shape(ctx):
     """the two full KITTI frames as one window of two: 3000 FAST corners, 21 x 21, 3 levels, 30 iterations, 0.01"""
     a, b = O.load_kitti(0), O.load_kitti(1)

@@ -1,294 +1,29 @@
-// orbx_api.cpp -- C-ABI host layer of liborbx.so (see include/orbx.h).
+// orbx_api.cpp -- C-ABI host layer of liborbx.so (see include/orbx.h): the context and the batched ORB path.
 //
 // Owns the context (device memory pools, stream, per-size plan), validates
 // arguments, sequences the kernel launches of orbx_kernels.hip and moves
-// results.  There is NO CPU fallback anywhere in this file: if the HIP
-// runtime or a gfx950 device is missing every entry point fails loudly with
+// results.  The subsystems beside the batched path are driven from files of their own, on the context and the
+// helpers of orbx_host.h: orbx_api_stage.cpp (stage operators, matcher), orbx_api_lk.cpp (Lucas-Kanade),
+// orbx_api_geom.cpp (pose, scale, bundle adjustment), orbx_api_gftt.cpp (good features).  There is NO CPU fallback
+// anywhere in the host layer: if the HIP runtime or a gfx950 device is missing every entry point fails loudly with
 // ORBX_ERR_NO_DEVICE / ORBX_ERR_HIP.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <array>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <string>
-#include <vector>
 
-#include "orbx_internal.h"
-#include "orbx_tri_math.h"
+#include "orbx_host.h"
 
-using namespace orbx_geom;  // orbx_plan.h: the geometry of a frame size and the tables built from it
+using namespace orbx_host;
 
 namespace {
-
 thread_local std::string g_create_error;
-
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-// result block of a batch: one device allocation + one pinned host mirror so
-// a whole batch comes back with a single D2H copy
-// sections: counts | kp | angle | desc || lkp | resp | level -- what the reference's own output consists of
-// (keypoints, orientations, descriptors: include/orb.hpp:37) first, so that orbx_batch_prefetch_compact moves one
-// contiguous prefix of `compact` bytes
-struct OutLayout {
-  size_t counts, kp16, kp, lkp, angle, resp, level, desc, compact, total;
-};
-
-OutLayout make_out_layout(int n, int cap) {
-  OutLayout o;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t r = off;
-    off = align_up_sz(off + bytes, 256);
-    return r;
-  };
-  const size_t e = (size_t)n * (size_t)cap;
-  // the compact record first (orbx_batch_prefetch_compact copies [0, compact)): 40 bytes per slot
-  o.counts = take(sizeof(int32_t) * (size_t)n);
-  o.kp16 = take(sizeof(uint32_t) * e);
-  o.angle = take(sizeof(float) * e);
-  o.desc = take(sizeof(orbx_descriptor) * e);
-  o.compact = off;
-  o.kp = take(sizeof(orbx_keypoint) * e);
-  o.lkp = take(sizeof(orbx_keypoint) * e);
-  o.resp = take(sizeof(float) * e);
-  o.level = take(sizeof(int32_t) * e);
-  o.total = off;
-  return o;
-}
-
-// One block of the ring of result blocks (orbx_ctx::blocks): the device allocation, its pinned host mirror and
-// what the batch that last wrote it left there.
-struct Block {
-  uint8_t* d = nullptr;
-  uint8_t* h = nullptr;      // pinned mirror
-  uint8_t* h_dev = nullptr;  // the device-visible address of the pinned mirror
-  OutLayout layout{};
-  int n = 0;                  // frames in the block (0: never written)
-  int cap = 1;                // slots per frame the block was written with
-  bool copy_pending = false;  // an asynchronous D2H of the block has been enqueued (ev_copied)
-  bool copy_compact = false;  // ... of its compact prefix only (orbx_batch_prefetch_compact)
-  bool host_written = false;  // orbx_set_host_results: the describe kernel wrote the compact record to the mirror
-  hipEvent_t ev_done = nullptr, ev_copied = nullptr;
-  hipStream_t stream = nullptr;  // the stream of the batch that last wrote the block
-};
-
-// One lane of the pipelined mode: a set of working pools (pyramids, mask, statistics, candidates; sized for
-// max_batch frames of max_width x max_height), the stream its batches run on, and the event / stream of the
-// pools' last user.
-struct Lane {
-  uint8_t *d_pyr = nullptr, *d_pyr_blur = nullptr;
-  unsigned long long *d_mask = nullptr, *d_row_stat = nullptr;
-  orbx_keypoint* d_cand = nullptr;
-  int32_t *d_cand_count = nullptr, *d_cand_total = nullptr;
-  float* d_resp = nullptr;
-  uint32_t* d_lcand = nullptr;  // spread selection: packed candidates, their responses, counts
-  float* d_lresp = nullptr;
-  int32_t* d_lcount = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_pool = nullptr;
-  hipStream_t pool_stream = nullptr;
-};
-
-// a per-workgroup tile descriptor table (see OrbxTileDesc) of the current plan, in a pool sized for the largest frame
-struct TileTable {
-  OrbxTileDesc* d = nullptr;
-  int count = 0;
-  size_t capacity = 0;
-};
-enum {
-  T_FAST,  // one frame, band-major
-  T_BLUR,
-  T_PYR2,
-  T_PYRBLUR,  // fused pyramid + blur strips
-  // the same strips cut into short row bands: few frames per call (the reference's one-frame call shape)
-  // fill the chip only with many short waves, where a large batch wants few tall ones
-  T_PYRBLUR_SMALL,
-  // top-rows-first pipeline: the strips of the first pass and of the second one
-  T_PYRBLUR_TOP,
-  T_PYRBLUR_REST,
-  kTileTables
-};
-
-// the events of one timed batched call
-// (slots ORBX_NUM_STAGE_TIMES + 1, + 2: the boundaries inside the top-rows-first pipeline)
-struct TimingSet {
-  hipEvent_t ev[ORBX_NUM_STAGE_TIMES + 3] = {};
-  int mode = 0;
-  bool split = false;  // the call ran the top-rows-first pipeline
-};
-
 }  // namespace
 
-// what a captured launch sequence depends on (run_batch)
-struct OrbxGraphKey {
-  const uint8_t* d_frames;
-  size_t frame_stride;
-  int n, w, h, row_stride, early, plan_serial, block;  // early: switches (early exit, fusion, two passes)
-  bool operator==(const OrbxGraphKey& o) const {
-    return d_frames == o.d_frames && frame_stride == o.frame_stride && n == o.n && w == o.w && h == o.h &&
-           row_stride == o.row_stride && early == o.early && plan_serial == o.plan_serial && block == o.block;
-  }
-};
-
-struct orbx_ctx {
-  orbx_params p{};
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-
-  // geometry for the current frame size, and for the largest size (capacity)
-  OrbxPlan plan{};
-  OrbxPlan plan_max{};
-  OrbxTileMap tm_blur{};  // 5x5 /273 variant (LDS tile kernel)
-  OrbxBandMap bm_fast{};
-  TileTable tiles[kTileTables];
-  OrbxTopLevels top_levels{};  // the levels the second pass may skip
-  DevBuf s_tiles;  // stage-API tables
-  std::vector<OrbxResizeTap> h_taps;
-  int plan_w = 0, plan_h = 0;
-
-  uint8_t* d_in = nullptr;  // staged host frames, tight pitch (max_batch frames of max_width x max_height)
-  // captured launch sequences of the most recent batch shapes (run_batch), round-robin replacement
-  static constexpr int kGraphs = 16;  // (input, result block, lane) triples: 8 resident inputs over 4 blocks x 2 lanes
-  hipGraphExec_t g_exec[kGraphs] = {};
-  OrbxGraphKey g_key[kGraphs] = {};
-  int g_next = 0;
-  int plan_serial = 0;  // bumped whenever set_plan rebuilds the plan / tables
-  OrbxResizeTap* d_taps = nullptr;
-  size_t taps_capacity = 0;
-  float* d_gauss = nullptr;
-  // Result blocks.  A ring of kBlocks, used in turn by consecutive batches, each with a pinned host
-  // mirror: the D2H copy of batch i (orbx_batch_prefetch, on its own copy stream) overlaps the
-  // kernels of batch i+1, which write the other block.  blocks[blk] is the block of the most recent batch.
-  // (a ring of kBlocks blocks: with two, the copy of batch i -- about as long as a step at 256 frames per batch --
-  // had to finish before batch i + 2 could start; with four it overlaps two following batches)
-  static constexpr int kBlocks = 4;
-  Block blocks[kBlocks];
-  int blk = 0;
-  int host_results = 0;  // orbx_set_host_results: the describe kernel writes the compact record to the mirror
-  int next_lane = 1;  // pipelined mode: the lane of the next batch (alternates)
-  hipStream_t cstream = nullptr;
-  // Pipelined batches (orbx_set_pipelined_batches): two LANES, each with its own stream and its own working pools;
-  // consecutive device-resident batches alternate between them -- batch k uses lane k & 1 = its result block --
-  // so the kernels of one batch overlap the tails and the nearly empty launches of the other.  lanes[0] has the
-  // pools every context has, and its stream is the context's own; lanes[lane] is the lane of the most recent batch.
-  // Stream order is the only ordering inside a lane.  A batch that comes to a lane's pools, or to a result block,
-  // on ANOTHER stream than their previous user (a caller's stream, the other lane) first makes its stream wait for
-  // that user's event: Lane::ev_pool / pool_stream for the pools of a lane, Block::ev_done / stream for a block.
-  Lane lanes[2];
-  int lane = 0;
-  bool pipelined = false;
-  bool last_two_pass = false;  // the last batch built its pyramid top rows first (enqueue_batch)
-  hipStream_t last_stream = nullptr;
-
-  // stage-API scratch (grown on demand; never touched by the batched path)
-  DevBuf s_img_a, s_img_b, s_f32, s_u16, s_mask, s_kps, s_f32b, s_desc, s_i32, s_kern;
-  DevBuf m_q, m_t, m_idx, m_dist, m_match, m_cnt;  // matcher (stage API and batch)
-  // Lucas-Kanade tracker: two image pyramids (ping-pong: the `next` of one call is the
-  // `prev` of the following one), the derivative pyramid of the current `prev`, point buffers
-  DevBuf lk_img[2], lk_deriv, lk_io;  // lk_io: prev points | next points | err | status, one block
-  void* lk_host = nullptr;            // pinned mirror of lk_io (one H2D + one D2H per call)
-  size_t lk_host_bytes = 0;
-  int lk_w = 0, lk_h = 0, lk_top = -1, lk_win = 0, lk_last = -1;  // lk_last: buffer holding the last `next`
-  int match_pairs = 0;
-  // batch serial: bumped by every batch run; match_serial: the serial the last batch match was made on
-  long long batch_serial = 0, match_serial = -1;
-  // bumped by every batch match: the pose step records the one it read (pose_match_gen), so the scale step, which
-  // reads m_match again, can tell that the matches are still the ones the poses were computed from
-  long long match_gen = 0, pose_match_gen = -1;
-  // relative pose (orbx_pose.hip): batched results (pb_*) and the host-array entry's own buffers (ph_*)
-  DevBuf pb_pts, pb_n, pb_out, pb_mask, ph_in, ph_pts, ph_n, ph_out, ph_mask;
-  int pose_pairs = 0, pose_cap = 0;
-  hipStream_t pose_stream = nullptr;
-  long long pose_serial = -1;  // the batch serial the last batch pose ran on
-  // triangulation and scale (orbx_scale.hip): batched results (sb_*: points, valid bytes, compact match lists,
-  // match counts, scales) and the host-array entries' own buffers (sh_*)
-  DevBuf sb_xyz, sb_valid, sb_mq, sb_mt, sb_n, sb_out, sh_in, sh_xyz, sh_valid, sh_out;
-  int scale_pairs = 0, scale_cap = 0;
-  hipStream_t scale_stream = nullptr;
-  // bundle adjustment (orbx_ba.hip): the staged windows (offsets, parameter blocks, CSR observations), the
-  // workgroups' workspaces and the summaries; grown on first use
-  DevBuf ba_off, ba_poses, ba_points, ba_rows, ba_opose, ba_oxy, ba_wp, ba_wo, ba_slot, ba_out;
-  // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames (response maps | key pools | cell grids
-  // | per-frame maximum and candidate count), allocated on first use and bounded by gf_ws_limit; the staged host
-  // image of the one-frame entries; and the entry's OWN result block (counts | corners), untouched by the ORB path
-  DevBuf gf_ws, gf_img, gf_res;
-  size_t gf_ws_limit = ORBX_GFTT_WORKSPACE_DEFAULT;
-  int gf_n = 0, gf_cap = 0;  // frames and slots per frame of the last good-features batch (gf_n == 0: none)
-  // the stream the last good-features call ran on, kept for COMPARISON only (a caller's stream may be gone by the
-  // next call), and the event recorded behind that call's work: what later calls, fetches and orbx_destroy wait for
-  hipStream_t gf_stream = nullptr;
-  hipEvent_t gf_ev = nullptr;
-  // Lucas-Kanade over frame windows (k_lk_track_windows): the workspace of one slice of frames (pyramid levels above
-  // 0 | derivative maps), bounded by lkw_ws_limit; the window table; the staged frames and points of the one-window
-  // host entry; and the entry's OWN result block (tracks | seen | err).  Nothing here is shared with orbx_lk_track.
-  DevBuf lkw_ws, lkw_first, lkw_img, lkw_pts, lkw_res;
-  size_t lkw_ws_limit = ORBX_LK_WORKSPACE_DEFAULT;
-  int lkw_n = 0, lkw_cap = 0, lkw_len = 0;  // windows, slots per window, frames per window of the last call (0: none)
-  hipStream_t lkw_stream = nullptr;  // for comparison only, as gf_stream
-  hipEvent_t lkw_ev = nullptr;       // recorded behind every windows call
-  void* lkw_first_host = nullptr;    // pinned mirror of the window table, and the event behind its upload
-  size_t lkw_first_host_bytes = 0;
-  hipEvent_t lkw_first_ev = nullptr;
-
-  int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
-  int fast_early = 1;
-  int blur_impl = 2;  // ORBX_BLUR_IMPL, read at creation (launch_blur_auto)
-  int fast_impl = 4;  // 4: streaming kernel (orbx_fast4.hip, the default), 3: LDS tile kernel (orbx_fast.hip); ORBX_FAST_IMPL, read at creation
-  int fuse = 1;  // pyramid + blur in one kernel when blur runs on every level (orbx_set_fused_pyramid_blur)
-  // Top-rows-first pipeline (enqueue_batch): 0 never, 1 whenever eligible, 2 adaptive -- the second pass
-  // counts the (frame, level)s it skipped / had to produce (d_feedback, running totals, written to the pinned
-  // h_feedback by the last kernel of every two-pass batch and read WITHOUT waiting at the start of later ones); while
-  // fewer than a quarter are skipped the batches run in one pass, and every 128th one probes again.
-  int top_mode = 2;
-  bool top_on = true;          // the adaptive verdict
-  int top_single_batches = 0;  // one-pass batches since the verdict turned negative
-  uint32_t* d_feedback = nullptr;
-  volatile uint32_t* h_feedback = nullptr;
-  uint32_t feedback_seen[2] = {0, 0};
-  // adaptive first pass (adapt_tile_rows): rows each level needed to fill its cap -- maximum of the current and of
-  // the previous observation window --, the tile-row heights chosen from them (0: the default), bookkeeping
-  uint32_t need_cur[ORBX_MAX_LEVELS] = {}, need_prev[ORBX_MAX_LEVELS] = {};
-  int tile_h_pref[ORBX_MAX_LEVELS] = {};
-  int need_batches = 0, need_window = 2, retiles = 0, learn_w = 0, learn_h = 0;
-  bool prefs_applied = false;  // the current tile tables were built with tile_h_pref
-  // ring of event sets: one per timed batched call, so that several calls can be
-  // in flight before their stage times are read (no host sync between steps)
-  TimingSet evr[ORBX_EVENT_SETS];
-  long long ev_calls = 0;  // timed batched calls so far
-  hipEvent_t ev[2] = {};   // orbx_bench_stage
-};
-
-namespace {
-
-// Every entry point that takes a context runs on the context's device, whatever the caller's
-// current device is (another context's, torch.cuda.set_device, ...), and leaves the caller's
-// current device as it found it.
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(const orbx_ctx* c) {
-    if (!c) return;
-    enter(c->device);
-  }
-  explicit DeviceGuard(int dev) { enter(dev); }
-  void enter(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
+// ---- what the other files of the host layer call too (declared in orbx_host.h) ----
+namespace orbx_host {
 
 int fail(orbx_ctx* c, int status, const std::string& msg) {
   if (c)
@@ -297,13 +32,6 @@ int fail(orbx_ctx* c, int status, const std::string& msg) {
     g_create_error = msg;
   return status;
 }
-
-#define HIPCHK(c, expr)                                                                              \
-  do {                                                                                               \
-    hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess)                                                                            \
-      return fail((c), ORBX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));             \
-  } while (0)
 
 int ensure(orbx_ctx* c, DevBuf& b, size_t bytes) {
   if (b.bytes >= bytes && b.p) return ORBX_OK;
@@ -321,17 +49,104 @@ int ensure(orbx_ctx* c, DevBuf& b, size_t bytes) {
   b.bytes = bytes;
   return ORBX_OK;
 }
-#define ENSURE(c, buf, bytes)                        \
-  do {                                               \
-    const int _st = ensure((c), (buf), (bytes));     \
-    if (_st != ORBX_OK) return _st;                  \
-  } while (0)
 
-// the stream the last batch ran on (the context's own before any batch)
 hipStream_t batch_stream(const orbx_ctx* c) { return c->last_stream ? c->last_stream : c->stream; }
-// the lane and the result block of the most recent batch
 const Lane& cur_lane(const orbx_ctx* c) { return c->lanes[c->lane]; }
 const Block& last_block(const orbx_ctx* c) { return c->blocks[c->blk]; }
+hipError_t lanes_sync(orbx_ctx* c) {
+  for (const Lane& L : c->lanes)
+    if (L.stream) {
+      const hipError_t e = hipStreamSynchronize(L.stream);
+      if (e != hipSuccess) return e;
+    }
+  return hipSuccess;
+}
+
+int check_image(orbx_ctx* c, const void* img, int w, int h, int stride) {
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!img) return fail(c, ORBX_ERR_INVALID_ARG, "image is NULL");
+  if (w < 8 || h < 8 || w > c->p.max_width || h > c->p.max_height)
+    return fail(c, ORBX_ERR_INVALID_ARG, "image size outside [8, max_width] x [8, max_height]");
+  if (stride < w) return fail(c, ORBX_ERR_INVALID_ARG, "stride < width");
+  return ORBX_OK;
+}
+
+bool finite_all(const double* v, int n) {
+  for (int i = 0; i < n; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+// createGaussianKernel (src/GaussianBlur.cpp:7-37), host side like the reference
+int gaussian_kernel(int K, float sigma, float* kernel) {
+  if (K <= 0 || (K % 2) == 0 || !kernel) return ORBX_ERR_INVALID_ARG;
+  if (sigma <= 0.0f) sigma = 0.3f * ((K - 1) * 0.5f) + 0.8f;
+  const int half = K / 2;
+  float sum = 0.0f;
+  for (int y = -half; y <= half; ++y)
+    for (int x = -half; x <= half; ++x) {
+      const float value = std::exp(-(float)(x * x + y * y) / (2 * sigma * sigma));
+      kernel[(y + half) * K + (x + half)] = value;
+      sum += value;
+    }
+  for (int i = 0; i < K * K; ++i) kernel[i] /= sum;
+  return ORBX_OK;
+}
+
+// separable kind -> register-streaming kernel; /273 kind -> LDS tile kernel (impl: see blur_impl_env)
+hipError_t launch_blur_auto(int impl, hipStream_t s, const OrbxPlan& P, const OrbxTileMap& tm1, const OrbxTileDesc* tiles2,
+                            int ntiles2, int n, const uint8_t* src, uint8_t* dst, int first_level, int kind) {
+  if (kind == ORBX_BLUR_SEP16 && impl == 3)
+    return orbx_launch_blur4(s, tiles2, ntiles2, P.frame_bytes, n, src, dst, first_level);
+  if (kind == ORBX_BLUR_SEP16 && impl != 1)
+    return orbx_launch_blur3(s, tiles2, ntiles2, P.frame_bytes, n, src, dst, first_level);
+  return orbx_launch_blur(s, P, tm1, n, src, dst, first_level, kind);
+}
+
+int SideWork::wait(orbx_ctx* c) {
+  if (ev) HIPCHK(c, hipEventSynchronize(ev));
+  return ORBX_OK;
+}
+
+int SideWork::enter(orbx_ctx* c, hipStream_t s) {
+  if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  if (stream != s) {
+    const int st = wait(c);
+    if (st != ORBX_OK) return st;
+  }
+  stream = s;
+  return ORBX_OK;
+}
+
+int set_workspace_limit(orbx_ctx* c, SideWork& side, DevBuf& ws, size_t* limit, size_t bytes, size_t dflt) {
+  const int st = side.wait(c);
+  if (st != ORBX_OK) return st;
+  if (ws.p) {
+    HIPCHK(c, hipFree(ws.p));
+    ws = DevBuf{};
+  }
+  *limit = bytes ? bytes : dflt;
+  return ORBX_OK;
+}
+
+int check_device_frames(orbx_ctx* c, const void* d_frames, int n, int n_min, int n_max, int w, int h, int row_stride,
+                        size_t frame_stride, const FramesWhat& what) {
+  if (!d_frames) return fail(c, ORBX_ERR_INVALID_ARG, what.null_msg);
+  if (n < n_min || n > n_max) return fail(c, ORBX_ERR_INVALID_ARG, what.range_msg);
+  if (w < 8 || h < 8 || w > c->p.max_width || h > c->p.max_height)
+    return fail(c, ORBX_ERR_INVALID_ARG, "image size outside [8, max_width] x [8, max_height]");
+  if (row_stride < w) return fail(c, ORBX_ERR_INVALID_ARG, "row_stride < width");
+  if (frame_stride < (size_t)row_stride * (size_t)(h - 1) + (size_t)w)
+    return fail(c, ORBX_ERR_INVALID_ARG, "frame_stride smaller than a frame");
+  if ((unsigned long long)row_stride * (unsigned long long)(h - 1) + (unsigned long long)w > 0x7fffffffull)
+    return fail(c, ORBX_ERR_INVALID_ARG, "row_stride * (height - 1) + width exceeds 2^31 - 1");
+  return ORBX_OK;
+}
+
+}  // namespace orbx_host
+
+namespace {
+
 // slots per frame of a result block written under plan P (nfeatures too small for any quota: one empty slot)
 int slots_per_frame(const OrbxPlan& P) { return P.out_cap > 0 ? P.out_cap : 1; }
 
@@ -432,21 +247,6 @@ void make_taps(OrbxPlan& plan, std::vector<OrbxResizeTap>* taps) {
   }
 }
 
-// createGaussianKernel (src/GaussianBlur.cpp:7-37), host side like the reference
-int gaussian_kernel(int K, float sigma, float* kernel) {
-  if (K <= 0 || (K % 2) == 0 || !kernel) return ORBX_ERR_INVALID_ARG;
-  if (sigma <= 0.0f) sigma = 0.3f * ((K - 1) * 0.5f) + 0.8f;
-  const int half = K / 2;
-  float sum = 0.0f;
-  for (int y = -half; y <= half; ++y)
-    for (int x = -half; x <= half; ++x) {
-      const float value = std::exp(-(float)(x * x + y * y) / (2 * sigma * sigma));
-      kernel[(y + half) * K + (x + half)] = value;
-      sum += value;
-    }
-  for (int i = 0; i < K * K; ++i) kernel[i] /= sum;
-  return ORBX_OK;
-}
 
 int validate_params(const orbx_params& p, std::string* why) {
   auto bad = [&](const char* m) {
@@ -517,15 +317,6 @@ void free_lane(orbx_ctx* c, Lane& L) {
     L.stream = nullptr;
   }
   L.pool_stream = nullptr;
-}
-// everything either lane has in flight has finished
-hipError_t lanes_sync(orbx_ctx* c) {
-  for (const Lane& L : c->lanes)
-    if (L.stream) {
-      const hipError_t e = hipStreamSynchronize(L.stream);
-      if (e != hipSuccess) return e;
-    }
-  return hipSuccess;
 }
 
 bool fused_pyrblur(const orbx_ctx* c);
@@ -663,21 +454,12 @@ hipError_t launch_fast_whole(orbx_ctx* c, hipStream_t s, int n, OrbxFastParams f
   return launch_fast_tiles(c, s, 0, c->tiles[T_FAST].count, n, fp, stat);
 }
 
-// separable kind -> register-streaming kernel; /273 kind -> LDS tile kernel.
 // ORBX_BLUR_IMPL (read when a context is created): 2 (default) k_blur3, 4 pixels per lane; 3: k_blur4, 16 pixels per
 // lane (measured 9 % slower: the blur's vertical pass dominates its instruction count, and 94 registers leave 5
 // waves per SIMD); 1: the first-generation LDS tile kernel.  The strip table is built for the kernel that reads it.
 int blur_impl_env() {
   const int v = env_int("ORBX_BLUR_IMPL", 2);
   return v >= 1 && v <= 3 ? v : 2;
-}
-hipError_t launch_blur_auto(int impl, hipStream_t s, const OrbxPlan& P, const OrbxTileMap& tm1, const OrbxTileDesc* tiles2,
-                            int ntiles2, int n, const uint8_t* src, uint8_t* dst, int first_level, int kind) {
-  if (kind == ORBX_BLUR_SEP16 && impl == 3)
-    return orbx_launch_blur4(s, tiles2, ntiles2, P.frame_bytes, n, src, dst, first_level);
-  if (kind == ORBX_BLUR_SEP16 && impl != 1)
-    return orbx_launch_blur3(s, tiles2, ntiles2, P.frame_bytes, n, src, dst, first_level);
-  return orbx_launch_blur(s, P, tm1, n, src, dst, first_level, kind);
 }
 const uint8_t* final_pyr(const orbx_ctx* c) { return blur_enabled(c) ? cur_lane(c).d_pyr_blur : cur_lane(c).d_pyr; }
 
@@ -993,46 +775,6 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
   return ORBX_OK;
 }
 
-int check_image(orbx_ctx* c, const void* img, int w, int h, int stride) {
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!img) return fail(c, ORBX_ERR_INVALID_ARG, "image is NULL");
-  if (w < 8 || h < 8 || w > c->p.max_width || h > c->p.max_height)
-    return fail(c, ORBX_ERR_INVALID_ARG, "image size outside [8, max_width] x [8, max_height]");
-  if (stride < w) return fail(c, ORBX_ERR_INVALID_ARG, "stride < width");
-  return ORBX_OK;
-}
-
-// single-level plan over a scratch image, for the stage-level operators
-OrbxPlan flat_plan(int w, int h, int cap) {
-  OrbxPlan P;
-  std::memset(&P, 0, sizeof(P));
-  P.nlevels = 1;
-  P.w0 = w;
-  P.h0 = h;
-  OrbxLevel& L = P.L[0];
-  L.w = w;
-  L.h = h;
-  L.pitch = align_up(w, 64);
-  L.mask_wpr = (w + 63) / 64;
-  L.cap = cap;
-  L.quota = cap;
-  L.scale = 1.0f;
-  P.frame_bytes = (int32_t)align_up_sz((size_t)L.pitch * h, 256);
-  P.mask_words = L.mask_wpr * h;
-  P.cand_total = cap;
-  P.out_cap = cap;
-  return P;
-}
-
-// upload a host image into a zero-padded, 64-aligned-pitch scratch image
-int upload_flat(orbx_ctx* c, DevBuf& b, const uint8_t* img, int w, int h, int stride, int* pitch) {
-  const int p = align_up(w, 64);
-  ENSURE(c, b, (size_t)p * h + 256);
-  HIPCHK(c, hipMemsetAsync(b.p, 0, (size_t)p * h, c->stream));
-  HIPCHK(c, hipMemcpy2DAsync(b.p, p, img, stride, w, h, hipMemcpyHostToDevice, c->stream));
-  *pitch = p;
-  return ORBX_OK;
-}
 
 }  // namespace
 
@@ -1123,27 +865,16 @@ void orbx_destroy(orbx_ctx* c) {
     (void)hipStreamSynchronize(c->cstream);
     (void)hipStreamDestroy(c->cstream);
   }
-  DevBuf* sb[] = {&c->s_img_a, &c->s_img_b, &c->s_f32,  &c->s_u16, &c->s_mask, &c->s_kps,   &c->s_f32b, &c->s_desc,
-                  &c->s_i32,   &c->s_kern,  &c->s_tiles, &c->m_q,    &c->m_t,   &c->m_idx,  &c->m_dist,  &c->m_match, &c->m_cnt,
-                  &c->lk_img[0], &c->lk_img[1], &c->lk_deriv, &c->lk_io, &c->pb_pts, &c->pb_n, &c->pb_out,
-                  &c->pb_mask, &c->ph_in, &c->ph_pts, &c->ph_n, &c->ph_out, &c->ph_mask, &c->sb_xyz, &c->sb_valid,
-                  &c->sb_mq, &c->sb_mt, &c->sb_n, &c->sb_out, &c->sh_in, &c->sh_xyz, &c->sh_valid, &c->sh_out,
-                  &c->ba_off, &c->ba_poses, &c->ba_points, &c->ba_rows, &c->ba_opose, &c->ba_oxy, &c->ba_wp, &c->ba_wo,
-                  &c->ba_slot, &c->ba_out, &c->gf_ws, &c->gf_img, &c->gf_res,
-                  &c->lkw_ws, &c->lkw_first, &c->lkw_img, &c->lkw_pts, &c->lkw_res};
-  if (c->gf_ev) {
-    (void)hipEventSynchronize(c->gf_ev);
-    (void)hipEventDestroy(c->gf_ev);
-  }
-  if (c->lkw_ev) {
-    (void)hipEventSynchronize(c->lkw_ev);
-    (void)hipEventDestroy(c->lkw_ev);
-  }
-  if (c->lkw_first_ev) (void)hipEventDestroy(c->lkw_first_ev);
-  if (c->lkw_first_host) (void)hipHostFree(c->lkw_first_host);
-  if (c->lk_host) (void)hipHostFree(c->lk_host);
-  for (DevBuf* b : sb)
-    if (b->p) (void)hipFree(b->p);
+  // every subsystem releases what it owns.  The windows tracker before the good features: each waits for its own
+  // event before its buffers go, and the tracker may be reading the good-features block.
+  c->lkw.release();
+  c->gf.release();
+  c->s.release();
+  c->m.release();
+  c->lk.release();
+  c->pose.release();
+  c->scale.release();
+  c->ba.release();
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (TimingSet& set : c->evr)
@@ -1708,274 +1439,6 @@ int orbx_bench_stage(orbx_ctx* c, int n_frames, int stage, int reps, float* avg_
   return ORBX_OK;
 }
 
-// ---- stage-level operators --------------------------------------------------
-
-int orbx_fast_score(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, int threshold, int n,
-                    float* scores) {
-  DeviceGuard _dg(c);
-  int st = check_image(c, image, width, height, stride);
-  if (st != ORBX_OK) return st;
-  if (!scores || n < 1 || n > 16 || threshold < 0 || threshold > 255)
-    return fail(c, ORBX_ERR_INVALID_ARG, "scores NULL or n/threshold out of range");
-  int pitch;
-  st = upload_flat(c, c->s_img_a, image, width, height, stride, &pitch);
-  if (st != ORBX_OK) return st;
-  OrbxPlan P = flat_plan(width, height, 0);
-  OrbxBandMap bm;
-  std::string why;
-  if ((st = make_bandmap(P, 0, &bm, &why)) != ORBX_OK) return fail(c, st, why);
-  std::vector<OrbxTileDesc> t;
-  build_fast_tiles(P, bm, 0, 1, &t);
-  ENSURE(c, c->s_tiles, t.size() * sizeof(OrbxTileDesc));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->s_tiles.p, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-  const size_t npx = (size_t)width * height;
-  ENSURE(c, c->s_u16, npx * 2);
-  ENSURE(c, c->s_mask, (size_t)P.mask_words * 8);
-  OrbxFastParams fp{threshold, n, 0};
-  HIPCHK(c, orbx_launch_fast_nms(c->stream, (const OrbxTileDesc*)c->s_tiles.p, (int)t.size(), 1,
-                                 (const uint8_t*)c->s_img_a.p, P.frame_bytes, P.mask_words, fp,
-                                 (unsigned long long*)c->s_mask.p, (uint16_t*)c->s_u16.p, nullptr));
-  std::vector<uint16_t> h(npx);
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->s_u16.p, npx * 2, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < npx; i++) scores[i] = (float)h[i];
-  return ORBX_OK;
-}
-
-static int compact_and_fetch(orbx_ctx* c, const OrbxPlan& P, int nfeatures, orbx_keypoint* keypoints, int* count,
-                             int* total) {
-  ENSURE(c, c->s_kps, sizeof(orbx_keypoint) * (size_t)std::max(nfeatures, 1));
-  ENSURE(c, c->s_i32, 64);
-  int32_t* d_cnt = (int32_t*)c->s_i32.p;
-  HIPCHK(c, orbx_launch_compact(c->stream, P, 1, (const unsigned long long*)c->s_mask.p, (orbx_keypoint*)c->s_kps.p,
-                                d_cnt, d_cnt + 1, 1));
-  int32_t h[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (h[0] > 0)
-    HIPCHK(c, hipMemcpy(keypoints, c->s_kps.p, sizeof(orbx_keypoint) * (size_t)h[0], hipMemcpyDeviceToHost));
-  *count = h[0];
-  if (total) *total = h[1];
-  return ORBX_OK;
-}
-
-int orbx_fast(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, int threshold, int n,
-              int nms_window, int nfeatures, orbx_keypoint* keypoints, int* count, int* total) {
-  DeviceGuard _dg(c);
-  int st = check_image(c, image, width, height, stride);
-  if (st != ORBX_OK) return st;
-  if (!count || (!keypoints && nfeatures > 0) || nfeatures < 0 || n < 1 || n > 16 || threshold < 0 ||
-      threshold > 255 || nms_window < 0 || nms_window / 2 > 3)
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad Fast() arguments");
-  int pitch;
-  st = upload_flat(c, c->s_img_a, image, width, height, stride, &pitch);
-  if (st != ORBX_OK) return st;
-  OrbxPlan P = flat_plan(width, height, nfeatures);
-  OrbxBandMap bm;
-  std::string why;
-  if ((st = make_bandmap(P, nms_window / 2, &bm, &why)) != ORBX_OK) return fail(c, st, why);
-  std::vector<OrbxTileDesc> t;
-  build_fast_tiles(P, bm, 0, 1, &t);
-  ENSURE(c, c->s_tiles, t.size() * sizeof(OrbxTileDesc));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->s_tiles.p, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-  ENSURE(c, c->s_mask, (size_t)P.mask_words * 8);
-  OrbxFastParams fp{threshold, n, nms_window / 2};
-  // stage operator: exact totals are part of the contract -> no early exit
-  HIPCHK(c, orbx_launch_fast_nms(c->stream, (const OrbxTileDesc*)c->s_tiles.p, (int)t.size(), 1,
-                                 (const uint8_t*)c->s_img_a.p, P.frame_bytes, P.mask_words, fp,
-                                 (unsigned long long*)c->s_mask.p, nullptr, nullptr));
-  return compact_and_fetch(c, P, nfeatures, keypoints, count, total);
-}
-
-int orbx_nms(orbx_ctx* c, const float* scores, int width, int height, int nms_window, int nfeatures,
-             float threshold, orbx_keypoint* keypoints, int* count, int* total) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!scores || !count || (!keypoints && nfeatures > 0) || nfeatures < 0 || width < 1 || height < 1 ||
-      nms_window < 0 || nms_window / 2 > 3)
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad NMS() arguments");
-  const size_t npx = (size_t)width * height;
-  ENSURE(c, c->s_f32, npx * 4);
-  OrbxPlan P = flat_plan(width, height, nfeatures);
-  ENSURE(c, c->s_mask, (size_t)P.mask_words * 8);
-  HIPCHK(c, hipMemcpyAsync(c->s_f32.p, scores, npx * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, orbx_launch_nms_f32(c->stream, (const float*)c->s_f32.p, width, height, nms_window / 2, threshold,
-                                (unsigned long long*)c->s_mask.p, P.L[0].mask_wpr));
-  return compact_and_fetch(c, P, nfeatures, keypoints, count, total);
-}
-
-static int describe_stage(orbx_ctx* c, const uint8_t* image, int width, int height, int stride,
-                          const orbx_keypoint* keypoints, int nkp, int patch_size, const float* angles_in,
-                          float* angles_out, orbx_descriptor* desc_out) {
-  int st = check_image(c, image, width, height, stride);
-  if (st != ORBX_OK) return st;
-  if (nkp < 0 || (nkp > 0 && !keypoints)) return fail(c, ORBX_ERR_INVALID_ARG, "keypoints NULL / nkp < 0");
-  if (patch_size < 1 || patch_size / 2 > 20) return fail(c, ORBX_ERR_INVALID_ARG, "patch_size must be in [1, 41]");
-  if (nkp == 0) return ORBX_OK;
-  for (int i = 0; i < nkp; i++)
-    if (keypoints[i].x < 0 || keypoints[i].y < 0 || keypoints[i].x >= width || keypoints[i].y >= height)
-      return fail(c, ORBX_ERR_INVALID_ARG, "keypoint outside the image");
-  if (angles_in)
-    for (int i = 0; i < nkp; i++)
-      if (!(std::fabs(angles_in[i]) < 100.0f))
-        return fail(c, ORBX_ERR_INVALID_ARG, "orientation must be finite and |angle| < 100 rad");
-  int pitch;
-  st = upload_flat(c, c->s_img_a, image, width, height, stride, &pitch);
-  if (st != ORBX_OK) return st;
-  ENSURE(c, c->s_kps, sizeof(orbx_keypoint) * (size_t)nkp);
-  ENSURE(c, c->s_f32b, sizeof(float) * (size_t)nkp);
-  ENSURE(c, c->s_desc, sizeof(orbx_descriptor) * (size_t)nkp);
-  HIPCHK(c, hipMemcpyAsync(c->s_kps.p, keypoints, sizeof(orbx_keypoint) * (size_t)nkp, hipMemcpyHostToDevice,
-                           c->stream));
-  if (angles_in)
-    HIPCHK(c, hipMemcpyAsync(c->s_f32b.p, angles_in, sizeof(float) * (size_t)nkp, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, orbx_launch_describe_flat(c->stream, (const uint8_t*)c->s_img_a.p, width, height, pitch,
-                                      (const orbx_keypoint*)c->s_kps.p, nkp, patch_size, angles_in != nullptr,
-                                      desc_out != nullptr, (float*)c->s_f32b.p, (orbx_descriptor*)c->s_desc.p));
-  if (angles_out)
-    HIPCHK(c, hipMemcpyAsync(angles_out, c->s_f32b.p, sizeof(float) * (size_t)nkp, hipMemcpyDeviceToHost, c->stream));
-  if (desc_out)
-    HIPCHK(c, hipMemcpyAsync(desc_out, c->s_desc.p, sizeof(orbx_descriptor) * (size_t)nkp, hipMemcpyDeviceToHost,
-                             c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ORBX_OK;
-}
-
-int orbx_orientations(orbx_ctx* c, const uint8_t* image, int width, int height, int stride,
-                      const orbx_keypoint* keypoints, int nkp, int patch_size, float* orientations) {
-  DeviceGuard _dg(c);
-  if (c && nkp > 0 && !orientations) return fail(c, ORBX_ERR_INVALID_ARG, "orientations is NULL");
-  return describe_stage(c, image, width, height, stride, keypoints, nkp, patch_size, nullptr, orientations, nullptr);
-}
-
-int orbx_brief(orbx_ctx* c, const uint8_t* image, int width, int height, int stride,
-               const orbx_keypoint* keypoints, const float* orientations, int nkp, orbx_descriptor* descriptors) {
-  DeviceGuard _dg(c);
-  if (c && nkp > 0 && (!orientations || !descriptors))
-    return fail(c, ORBX_ERR_INVALID_ARG, "orientations/descriptors is NULL");
-  return describe_stage(c, image, width, height, stride, keypoints, nkp, 31, orientations, nullptr, descriptors);
-}
-
-int orbx_harris(orbx_ctx* c, const uint8_t* image, int width, int height, int stride,
-                const orbx_keypoint* keypoints, int nkp, int window, float k, float* responses) {
-  DeviceGuard _dg(c);
-  int st = check_image(c, image, width, height, stride);
-  if (st != ORBX_OK) return st;
-  if (nkp < 0 || (nkp > 0 && (!keypoints || !responses)) || window < 1 || (window % 2) == 0 || window > 15)
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad HarrisScore() arguments");
-  if (nkp == 0) return ORBX_OK;
-  for (int i = 0; i < nkp; i++)
-    if (keypoints[i].x < 0 || keypoints[i].y < 0 || keypoints[i].x >= width || keypoints[i].y >= height)
-      return fail(c, ORBX_ERR_INVALID_ARG, "keypoint outside the image");
-  int pitch;
-  st = upload_flat(c, c->s_img_a, image, width, height, stride, &pitch);
-  if (st != ORBX_OK) return st;
-  std::vector<float> g((size_t)window * window);
-  gaussian_kernel(window, -1.0f, g.data());
-  ENSURE(c, c->s_kern, g.size() * 4);
-  ENSURE(c, c->s_kps, sizeof(orbx_keypoint) * (size_t)nkp);
-  ENSURE(c, c->s_f32b, sizeof(float) * (size_t)nkp);
-  HIPCHK(c, hipMemcpyAsync(c->s_kern.p, g.data(), g.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->s_kps.p, keypoints, sizeof(orbx_keypoint) * (size_t)nkp, hipMemcpyHostToDevice,
-                           c->stream));
-  HIPCHK(c, orbx_launch_harris_flat(c->stream, (const uint8_t*)c->s_img_a.p, width, height, pitch,
-                                    (const orbx_keypoint*)c->s_kps.p, nkp, (const float*)c->s_kern.p, window, k,
-                                    (float*)c->s_f32b.p));
-  HIPCHK(c, hipMemcpyAsync(responses, c->s_f32b.p, sizeof(float) * (size_t)nkp, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ORBX_OK;
-}
-
-static int blur_stage(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, uint8_t* dst,
-                      int dst_stride, int kind) {
-  int st = check_image(c, image, width, height, stride);
-  if (st != ORBX_OK) return st;
-  if (!dst || dst_stride < width) return fail(c, ORBX_ERR_INVALID_ARG, "dst NULL or dst_stride < width");
-  int pitch;
-  st = upload_flat(c, c->s_img_a, image, width, height, stride, &pitch);
-  if (st != ORBX_OK) return st;
-  OrbxPlan P = flat_plan(width, height, 0);
-  ENSURE(c, c->s_img_b, (size_t)P.frame_bytes + 256);
-  OrbxTileMap tm;
-  make_tilemap(P, ORBX_BLUR_TW, ORBX_BLUR_TH, true, &tm);
-  std::vector<OrbxTileDesc> t;
-  blur_tiles_for_impl(c->blur_impl, P, &t);
-  ENSURE(c, c->s_tiles, t.size() * sizeof(OrbxTileDesc));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->s_tiles.p, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-  HIPCHK(c, launch_blur_auto(c->blur_impl, c->stream, P, tm, (const OrbxTileDesc*)c->s_tiles.p, (int)t.size(), 1,
-                             (const uint8_t*)c->s_img_a.p, (uint8_t*)c->s_img_b.p, 0, kind));
-  HIPCHK(c, hipMemcpy2DAsync(dst, dst_stride, c->s_img_b.p, pitch, width, height, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ORBX_OK;
-}
-
-int orbx_blur5_sep(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, uint8_t* dst,
-                   int dst_stride) {
-  DeviceGuard _dg(c);
-  return blur_stage(c, image, width, height, stride, dst, dst_stride, ORBX_BLUR_SEP16);
-}
-
-int orbx_blur5_273(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, uint8_t* dst,
-                   int dst_stride) {
-  DeviceGuard _dg(c);
-  return blur_stage(c, image, width, height, stride, dst, dst_stride, ORBX_BLUR_K273);
-}
-
-static int conv_stage(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, const float* kernel,
-                      int K, int reflect_pad, uint8_t* dst) {
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!image || !kernel || !dst || width < 1 || height < 1 || stride < width || K < 1 || (K % 2) == 0 || K > 31)
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad conv2d() arguments (kernel_size must be odd, <= 31)");
-  const int wo = reflect_pad ? width : width - K + 1, ho = reflect_pad ? height : height - K + 1;
-  if (wo < 1 || ho < 1) return fail(c, ORBX_ERR_INVALID_ARG, "image smaller than the kernel");
-  if (reflect_pad && (width < K / 2 + 1 || height < K / 2 + 1))
-    return fail(c, ORBX_ERR_INVALID_ARG, "image too small for REFLECT_101 padding");
-  int pitch;
-  const int p = align_up(width, 64);
-  ENSURE(c, c->s_img_a, (size_t)p * height + 256);
-  HIPCHK(c, hipMemcpy2DAsync(c->s_img_a.p, p, image, stride, width, height, hipMemcpyHostToDevice, c->stream));
-  pitch = p;
-  ENSURE(c, c->s_img_b, (size_t)wo * ho + 256);
-  ENSURE(c, c->s_kern, (size_t)K * K * 4);
-  HIPCHK(c, hipMemcpyAsync(c->s_kern.p, kernel, (size_t)K * K * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, orbx_launch_conv2d(c->stream, (const uint8_t*)c->s_img_a.p, width, height, pitch,
-                               (const float*)c->s_kern.p, K, reflect_pad, (uint8_t*)c->s_img_b.p, wo));
-  HIPCHK(c, hipMemcpyAsync(dst, c->s_img_b.p, (size_t)wo * ho, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ORBX_OK;
-}
-
-int orbx_conv2d(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, const float* kernel,
-                int kernel_size, uint8_t* dst) {
-  DeviceGuard _dg(c);
-  return conv_stage(c, image, width, height, stride, kernel, kernel_size, 0, dst);
-}
-
-int orbx_gaussian_kernel(int kernel_size, float sigma, float* kernel) {
-  return gaussian_kernel(kernel_size, sigma, kernel);
-}
-
-int orbx_gaussian_blur_conv(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, int kernel_size,
-                            uint8_t* dst) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (kernel_size < 1 || (kernel_size % 2) == 0 || kernel_size > 31)
-    return fail(c, ORBX_ERR_INVALID_ARG, "kernel_size must be odd and <= 31 (src/GaussianBlur.cpp:8-11)");
-  std::vector<float> g((size_t)kernel_size * kernel_size);
-  gaussian_kernel(kernel_size, -1.0f, g.data());
-  return conv_stage(c, image, width, height, stride, g.data(), kernel_size, 1, dst);
-}
-
-int orbx_sobel(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, int dir, uint8_t* dst) {
-  DeviceGuard _dg(c);
-  static const float SX[9] = {-1.f, 0.f, 1.f, -2.f, 0.f, 2.f, -1.f, 0.f, 1.f};   // src/Sobel.cpp:6-10
-  static const float SY[9] = {-1.f, -2.f, -1.f, 0.f, 0.f, 0.f, 1.f, 2.f, 1.f};   // src/Sobel.cpp:12-16
-  return conv_stage(c, image, width, height, stride, dir == 0 ? SX : SY, 3, 1, dst);
-}
-
 int orbx_build_pyramid_level(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, int level,
                              uint8_t* dst, int* level_w, int* level_h) {
   DeviceGuard _dg(c);
@@ -1997,1254 +1460,6 @@ int orbx_build_pyramid_level(orbx_ctx* c, const uint8_t* image, int width, int h
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (level_w) *level_w = L.w;
   if (level_h) *level_h = L.h;
-  return ORBX_OK;
-}
-
-int orbx_select_top(orbx_ctx* c, const float* responses, int n, int keep, int32_t* indices, int* kept) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (n < 0 || keep < 0 || (n > 0 && (!responses || !indices)) || !kept)
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad select_top arguments");
-  const int m = std::min(n, keep);
-  *kept = m;
-  if (m == 0) return ORBX_OK;
-  ENSURE(c, c->s_f32b, sizeof(float) * (size_t)n);
-  ENSURE(c, c->s_i32, sizeof(int32_t) * (size_t)n);
-  HIPCHK(c, hipMemcpyAsync(c->s_f32b.p, responses, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, orbx_launch_select_flat(c->stream, (const float*)c->s_f32b.p, n, keep, (int32_t*)c->s_i32.p));
-  HIPCHK(c, hipMemcpyAsync(indices, c->s_i32.p, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ORBX_OK;
-}
-
-// ---- descriptor matching (next row) -----------------------------------------
-
-static int knn_host(orbx_ctx* c, const orbx_descriptor* query, int nq, const orbx_descriptor* train, int nt,
-                    double ratio, std::vector<int32_t>* idx, std::vector<int32_t>* dist,
-                    std::vector<int32_t>* match) {
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (nq < 0 || nt < 0 || (nq > 0 && !query) || (nt > 0 && !train))
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad matcher arguments");
-  idx->assign((size_t)2 * nq, -1);
-  dist->assign((size_t)2 * nq, -1);
-  match->assign((size_t)nq, -1);
-  if (nq == 0) return ORBX_OK;
-  ENSURE(c, c->m_q, sizeof(orbx_descriptor) * (size_t)nq);
-  ENSURE(c, c->m_t, sizeof(orbx_descriptor) * (size_t)std::max(nt, 1));
-  ENSURE(c, c->m_idx, sizeof(int32_t) * 2 * (size_t)nq);
-  ENSURE(c, c->m_dist, sizeof(int32_t) * 2 * (size_t)nq);
-  ENSURE(c, c->m_match, sizeof(int32_t) * (size_t)nq);
-  ENSURE(c, c->m_cnt, 64);
-  const int32_t cnt[2] = {nq, nt};
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->m_cnt.p, cnt, sizeof(cnt), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->m_q.p, query, sizeof(orbx_descriptor) * (size_t)nq, hipMemcpyHostToDevice, s));
-  if (nt > 0) HIPCHK(c, hipMemcpyAsync(c->m_t.p, train, sizeof(orbx_descriptor) * (size_t)nt, hipMemcpyHostToDevice, s));
-  HIPCHK(c, orbx_launch_knn2(s, 1, nq, (const orbx_descriptor*)c->m_q.p, (const int32_t*)c->m_cnt.p, 0,
-                             (const orbx_descriptor*)c->m_t.p, (const int32_t*)c->m_cnt.p + 1, 0, ratio,
-                             (int32_t*)c->m_idx.p, (int32_t*)c->m_dist.p, (int32_t*)c->m_match.p, 0));
-  HIPCHK(c, hipMemcpyAsync(idx->data(), c->m_idx.p, sizeof(int32_t) * 2 * (size_t)nq, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(dist->data(), c->m_dist.p, sizeof(int32_t) * 2 * (size_t)nq, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(match->data(), c->m_match.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  c->match_pairs = 0;  // the scratch no longer holds a batch's matches
-  return ORBX_OK;
-}
-
-static int compact_matches(orbx_ctx* c, const int32_t* match, const int32_t* dist2, int nq, int32_t* query_idx,
-                           int32_t* train_idx, int32_t* dist1, int capacity, int* count) {
-  int n = 0;
-  for (int i = 0; i < nq; i++)
-    if (match[i] >= 0) {
-      if (n < capacity) {
-        query_idx[n] = i;
-        train_idx[n] = match[i];
-        if (dist1) dist1[n] = dist2[2 * i];
-      }
-      n++;
-    }
-  *count = n;
-  return n > capacity ? fail(c, ORBX_ERR_CAPACITY, "capacity smaller than match count") : (int)ORBX_OK;
-}
-
-int orbx_knn2(orbx_ctx* c, const orbx_descriptor* query, int nq, const orbx_descriptor* train, int nt,
-              int32_t* idx, int32_t* dist) {
-  DeviceGuard _dg(c);
-  if (c && nq > 0 && (!idx || !dist)) return fail(c, ORBX_ERR_INVALID_ARG, "idx/dist is NULL");
-  std::vector<int32_t> vi, vd, vm;
-  int st = knn_host(c, query, nq, train, nt, 0.8, &vi, &vd, &vm);
-  if (st != ORBX_OK) return st;
-  if (nq > 0) {
-    std::memcpy(idx, vi.data(), sizeof(int32_t) * 2 * (size_t)nq);
-    std::memcpy(dist, vd.data(), sizeof(int32_t) * 2 * (size_t)nq);
-  }
-  return ORBX_OK;
-}
-
-int orbx_match_ratio(orbx_ctx* c, const orbx_descriptor* query, int nq, const orbx_descriptor* train, int nt,
-                     double ratio, int32_t* query_idx, int32_t* train_idx, int32_t* dist1, int capacity, int* count) {
-  DeviceGuard _dg(c);
-  if (c && (!count || capacity < 0 || (capacity > 0 && (!query_idx || !train_idx))))
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad match output arguments");
-  std::vector<int32_t> vi, vd, vm;
-  int st = knn_host(c, query, nq, train, nt, ratio, &vi, &vd, &vm);
-  if (st != ORBX_OK) return st;
-  return compact_matches(c, vm.data(), vd.data(), nq, query_idx, train_idx, dist1, capacity, count);
-}
-
-int orbx_batch_match_consecutive(orbx_ctx* c, double ratio) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  const Block& B = last_block(c);
-  if (B.n < 2) return fail(c, ORBX_ERR_INVALID_ARG, "needs a batch of at least two frames");
-  // the match buffers are ONE set per context: a match of the other lane's batch may still be writing them
-  if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
-  const int n = B.n, cap = B.cap;
-  const size_t e = (size_t)(n - 1) * cap;
-  ENSURE(c, c->m_idx, sizeof(int32_t) * 2 * e);
-  ENSURE(c, c->m_dist, sizeof(int32_t) * 2 * e);
-  ENSURE(c, c->m_match, sizeof(int32_t) * e);
-  const int32_t* counts = (const int32_t*)(B.d + B.layout.counts);
-  const orbx_descriptor* desc = (const orbx_descriptor*)(B.d + B.layout.desc);
-  hipStream_t s = batch_stream(c);
-  // pair p: query = frame p, train = frame p+1 (same arrays, shifted by one slot block)
-  HIPCHK(c, orbx_launch_knn2(s, n - 1, cap, desc, counts, (size_t)cap, desc + cap, counts + 1, (size_t)cap, ratio,
-                             (int32_t*)c->m_idx.p, (int32_t*)c->m_dist.p, (int32_t*)c->m_match.p, (size_t)cap));
-  c->match_pairs = n - 1;
-  c->match_serial = c->batch_serial;
-  c->match_gen++;
-  return ORBX_OK;
-}
-
-int orbx_batch_match_fetch(orbx_ctx* c, int pair, int32_t* query_idx, int32_t* train_idx, int32_t* dist1,
-                           int capacity, int* count) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!count || capacity < 0 || (capacity > 0 && (!query_idx || !train_idx)))
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad match output arguments");
-  if (pair < 0 || pair >= c->match_pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last matched batch");
-  const Block& B = last_block(c);
-  const int cap = B.cap;
-  hipStream_t s = batch_stream(c);
-  int32_t nq = 0;
-  std::vector<int32_t> vm((size_t)cap), vd((size_t)2 * cap);
-  HIPCHK(c, hipMemcpyAsync(&nq, (const int32_t*)(B.d + B.layout.counts) + pair, sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(vm.data(), (const int32_t*)c->m_match.p + (size_t)pair * cap, sizeof(int32_t) * cap,
-                           hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(vd.data(), (const int32_t*)c->m_dist.p + (size_t)2 * pair * cap, sizeof(int32_t) * 2 * cap,
-                           hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  return compact_matches(c, vm.data(), vd.data(), nq, query_idx, train_idx, dist1, capacity, count);
-}
-
-}  // extern "C"
-
-// ---- pyramidal Lucas-Kanade tracking (src/feature_tracking.cpp:166-193) ------------------
-
-namespace {
-struct LkGeom {
-  int top = 0;
-  int w[ORBX_LK_MAX_LEVELS], h[ORBX_LK_MAX_LEVELS], pitch[ORBX_LK_MAX_LEVELS];
-  size_t img_off[ORBX_LK_MAX_LEVELS], der_off[ORBX_LK_MAX_LEVELS];
-  size_t img_bytes = 0, der_bytes = 0;
-};
-// buildOpticalFlowPyramid: halve ((w+1)/2) until a level would not be larger than the window
-LkGeom lk_geometry(int w, int h, int win, int max_level) {
-  LkGeom g;
-  for (int l = 0; l <= max_level; l++) {
-    const int lw = l == 0 ? w : (g.w[l - 1] + 1) / 2, lh = l == 0 ? h : (g.h[l - 1] + 1) / 2;
-    if (l > 0 && (lw <= win || lh <= win)) break;
-    g.w[l] = lw;
-    g.h[l] = lh;
-    g.pitch[l] = lw;  // tight: a host image with stride == width goes up in ONE contiguous copy
-    g.img_off[l] = g.img_bytes;
-    g.img_bytes += align_up_sz((size_t)g.pitch[l] * lh, 256);
-    g.der_off[l] = g.der_bytes;
-    g.der_bytes += align_up_sz((size_t)lw * lh * 4, 256);
-    g.top = l;
-  }
-  return g;
-}
-OrbxLkPyr lk_pyr(const LkGeom& g, const uint8_t* img, const uint8_t* deriv) {
-  OrbxLkPyr P;
-  std::memset(&P, 0, sizeof(P));
-  P.top = g.top;
-  for (int l = 0; l <= g.top; l++) {
-    P.L[l].img = img + g.img_off[l];
-    P.L[l].deriv = deriv ? reinterpret_cast<const int16_t*>(deriv + g.der_off[l]) : nullptr;
-    P.L[l].w = g.w[l];
-    P.L[l].h = g.h[l];
-    P.L[l].pitch = g.pitch[l];
-  }
-  return P;
-}
-// host image -> level 0, then pyrDown level by level
-int lk_upload(orbx_ctx* c, const LkGeom& g, DevBuf& b, const uint8_t* img, int stride) {
-  ENSURE(c, b, g.img_bytes + 256);
-  uint8_t* base = (uint8_t*)b.p;
-  if (stride == g.w[0])
-    HIPCHK(c, hipMemcpyAsync(base, img, (size_t)g.w[0] * g.h[0], hipMemcpyHostToDevice, c->stream));
-  else  // (row-by-row in the runtime: slow, but only for padded host images)
-    HIPCHK(c, hipMemcpy2DAsync(base, g.pitch[0], img, stride, g.w[0], g.h[0], hipMemcpyHostToDevice, c->stream));
-  for (int l = 1; l <= g.top; l++)
-    HIPCHK(c, orbx_launch_lk_pyrdown(c->stream, base + g.img_off[l - 1], g.w[l - 1], g.h[l - 1], g.pitch[l - 1],
-                                     base + g.img_off[l], g.w[l], g.h[l], g.pitch[l]));
-  return ORBX_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int orbx_lk_track(orbx_ctx* c, const uint8_t* prev, int prev_stride, const uint8_t* next, int next_stride, int width,
-                  int height, const float* prev_pts_xy, int n, float* next_pts_xy, uint8_t* status, float* err,
-                  int win_size, int max_level, int max_iters, double epsilon) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!next || n < 0 || (n > 0 && (!prev_pts_xy || !next_pts_xy || !status)))
-    return fail(c, ORBX_ERR_INVALID_ARG, "next image / point arrays are NULL");
-  if (width < 1 || height < 1 || next_stride < width || (prev && prev_stride < width))
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad image size or stride");
-  if (win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
-    return fail(c, ORBX_ERR_INVALID_ARG, "win_size must be in [3, 31], max_level in [0, 7]");
-  // TermCriteria sanitising of calcOpticalFlowPyrLK
-  max_iters = std::min(std::max(max_iters, 0), 100);
-  epsilon = std::min(std::max(epsilon, 0.0), 10.0);
-  const LkGeom g = lk_geometry(width, height, win_size, max_level);
-  int st;
-  int ip;  // buffer holding the `prev` pyramid
-  if (prev) {
-    ip = c->lk_last == 0 ? 1 : 0;
-    if ((st = lk_upload(c, g, c->lk_img[ip], prev, prev_stride)) != ORBX_OK) return st;
-  } else {
-    // the previous call's `next` image is this call's `prev` (img1 = img2.clone(), feature_tracking.cpp:112)
-    if (c->lk_last < 0 || c->lk_w != width || c->lk_h != height || c->lk_top != g.top || c->lk_win != win_size)
-      return fail(c, ORBX_ERR_INVALID_ARG, "prev == NULL needs a previous orbx_lk_track call of the same geometry");
-    ip = c->lk_last;
-  }
-  const int in = 1 - ip;
-  c->lk_last = -1;  // invalid until this call has succeeded
-  if ((st = lk_upload(c, g, c->lk_img[in], next, next_stride)) != ORBX_OK) return st;
-  ENSURE(c, c->lk_deriv, g.der_bytes + 256);
-  const uint8_t* pimg = (const uint8_t*)c->lk_img[ip].p;
-  for (int l = 0; l <= g.top; l++)
-    HIPCHK(c, orbx_launch_lk_scharr(c->stream, pimg + g.img_off[l], g.w[l], g.h[l], g.pitch[l],
-                                    reinterpret_cast<int16_t*>((uint8_t*)c->lk_deriv.p + g.der_off[l])));
-  uint8_t* hio = nullptr;
-  const size_t o_out = sizeof(float) * 2 * (size_t)n, o_err = 2 * o_out, o_st = o_err + sizeof(float) * (size_t)n;
-  const size_t io_bytes = o_st + (size_t)n;
-  if (n > 0) {
-    ENSURE(c, c->lk_io, io_bytes);
-    if (c->lk_host_bytes < io_bytes) {  // pinned staging: small pageable copies cost ~15 us each
-      if (c->lk_host) (void)hipHostFree(c->lk_host);
-      c->lk_host = nullptr;
-      c->lk_host_bytes = 0;
-      HIPCHK(c, hipHostMalloc(&c->lk_host, align_up_sz(io_bytes, 4096), hipHostMallocDefault));
-      c->lk_host_bytes = align_up_sz(io_bytes, 4096);
-    }
-    hio = (uint8_t*)c->lk_host;
-    uint8_t* dio = (uint8_t*)c->lk_io.p;
-    std::memcpy(hio, prev_pts_xy, o_out);
-    HIPCHK(c, hipMemcpyAsync(dio, hio, o_out, hipMemcpyHostToDevice, c->stream));
-    const OrbxLkPyr P = lk_pyr(g, pimg, (const uint8_t*)c->lk_deriv.p);
-    const OrbxLkPyr N = lk_pyr(g, (const uint8_t*)c->lk_img[in].p, nullptr);
-    HIPCHK(c, orbx_launch_lk_track(c->stream, P, N, n, (const float*)dio, (float*)(dio + o_out), dio + o_st,
-                                   (float*)(dio + o_err), win_size, max_iters, epsilon * epsilon));
-    HIPCHK(c, hipMemcpyAsync(hio + o_out, dio + o_out, io_bytes - o_out, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (n > 0) {
-    std::memcpy(next_pts_xy, hio + o_out, o_out);
-    std::memcpy(status, hio + o_st, (size_t)n);
-    if (err) std::memcpy(err, hio + o_err, sizeof(float) * (size_t)n);
-  }
-  c->lk_w = width;
-  c->lk_h = height;
-  c->lk_top = g.top;
-  c->lk_win = win_size;
-  c->lk_last = in;
-  return ORBX_OK;
-}
-
-int orbx_lk_pyramid_levels(int width, int height, int win_size, int max_level) {
-  if (width < 1 || height < 1 || win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
-    return -1;
-  return lk_geometry(width, height, win_size, max_level).top + 1;
-}
-
-}  // extern "C"
-
-// ---- Lucas-Kanade over frame windows ---------------------------------------------------------
-// trackPointsAcrossWindow (src/with_bundle_adjustment.cpp:464-499) for many windows per launch; with windows of two
-// frames, track_optical_flow (src/feature_tracking.cpp:166-193) over a stream.
-
-namespace {
-
-// the workspace of ONE frame: the pyramid levels above 0 (level 0 is read in place), then the derivative maps of
-// every level
-struct LkwLayout {
-  LkGeom g;
-  size_t img_bytes, frame_bytes;  // levels 1 .. top; img_bytes + derivative maps
-};
-LkwLayout lkw_layout(int w, int h, int win, int max_level) {
-  LkwLayout o;
-  o.g = lk_geometry(w, h, win, max_level);
-  o.img_bytes = o.g.top >= 1 ? o.g.img_bytes - o.g.img_off[1] : 0;
-  o.frame_bytes = o.img_bytes + o.g.der_bytes;
-  return o;
-}
-
-int lkw_wait(orbx_ctx* c) {
-  if (c->lkw_ev) HIPCHK(c, hipEventSynchronize(c->lkw_ev));
-  return ORBX_OK;
-}
-
-// a windows call on stream s: earlier windows work on another stream has to be done (one workspace, one result block)
-int lkw_enter(orbx_ctx* c, hipStream_t s) {
-  if (!c->lkw_ev) HIPCHK(c, hipEventCreateWithFlags(&c->lkw_ev, hipEventDisableTiming));
-  if (c->lkw_stream != s) {
-    const int st = lkw_wait(c);
-    if (st != ORBX_OK) return st;
-  }
-  c->lkw_stream = s;
-  return ORBX_OK;
-}
-
-struct LkwMark {
-  orbx_ctx* c;
-  hipStream_t s;
-  ~LkwMark() {
-    if (c->lkw_ev) (void)hipEventRecord(c->lkw_ev, s);
-  }
-};
-
-// a buffer of the windows path of at least `bytes`: the new allocation is made BEFORE the old one is released, so
-// that a failed call keeps what it had
-int lkw_grow(orbx_ctx* c, DevBuf& b, size_t bytes) {
-  if (b.p && b.bytes >= bytes) return ORBX_OK;
-  const int st = lkw_wait(c);  // (the old allocation may still be read or written)
-  if (st != ORBX_OK) return st;
-  bytes = align_up_sz(std::max<size_t>(bytes, 256), 256);
-  void* p = nullptr;
-  HIPCHK(c, hipMalloc(&p, bytes));
-  if (b.p) (void)hipFree(b.p);
-  b.p = p;
-  b.bytes = bytes;
-  return ORBX_OK;
-}
-
-struct LkwResult {
-  size_t o_seen, o_err, bytes;  // tracks at 0
-};
-LkwResult lkw_result(int n_windows, int cap, int len) {
-  LkwResult r;
-  const size_t slots = (size_t)n_windows * cap;
-  r.o_seen = align_up_sz(sizeof(float) * 2 * slots * len, 256);
-  r.o_err = align_up_sz(r.o_seen + sizeof(int32_t) * slots, 256);
-  r.bytes = r.o_err + sizeof(float) * slots * (len - 1);
-  return r;
-}
-
-// max_frames: max_batch for the device entry; the host entry stages into a buffer of its own (65535: blockIdx.z)
-int lkw_check_frames(orbx_ctx* c, const void* d_frames, int n_frames, int max_frames, int width, int height,
-                     int row_stride, size_t frame_stride) {
-  if (!d_frames) return fail(c, ORBX_ERR_INVALID_ARG, "frames is NULL");
-  if (n_frames < 2 || n_frames > max_frames)
-    return fail(c, ORBX_ERR_INVALID_ARG, "n_frames outside [2, " + std::to_string(max_frames) + "]");
-  if (width < 8 || height < 8 || width > c->p.max_width || height > c->p.max_height)
-    return fail(c, ORBX_ERR_INVALID_ARG, "image size outside [8, max_width] x [8, max_height]");
-  if (row_stride < width) return fail(c, ORBX_ERR_INVALID_ARG, "row_stride < width");
-  if (frame_stride < (size_t)row_stride * (size_t)(height - 1) + (size_t)width)
-    return fail(c, ORBX_ERR_INVALID_ARG, "frame_stride smaller than a frame");
-  if ((unsigned long long)row_stride * (unsigned long long)(height - 1) + (unsigned long long)width > 0x7fffffffull)
-    return fail(c, ORBX_ERR_INVALID_ARG, "row_stride * (height - 1) + width exceeds 2^31 - 1");
-  return ORBX_OK;
-}
-
-int lkw_check_params(orbx_ctx* c, int win_size, int max_level, int* max_iters, double* epsilon) {
-  if (win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
-    return fail(c, ORBX_ERR_INVALID_ARG, "win_size must be in [3, 31], max_level in [0, 7]");
-  if (!(*epsilon == *epsilon)) return fail(c, ORBX_ERR_INVALID_ARG, "epsilon is NaN");
-  // TermCriteria sanitising of calcOpticalFlowPyrLK, as orbx_lk_track
-  *max_iters = std::min(std::max(*max_iters, 0), 100);
-  *epsilon = std::min(std::max(*epsilon, 0.0), 10.0);
-  return ORBX_OK;
-}
-
-// enqueues the pyramids and the tracking of every window on s; arguments are checked
-int lkw_run(orbx_ctx* c, const uint8_t* d_frames, int n_frames, int w, int h, int row_stride, size_t frame_stride,
-            const int32_t* window_first, int n_windows, int window_len, const float* d_points,
-            const int32_t* d_counts, int cap, int win, int max_level, int max_iters, double epsilon, hipStream_t s) {
-  int st = lkw_enter(c, s);
-  if (st != ORBX_OK) return st;
-  const LkwMark mark{c, s};
-  // points and counts may be the good-features block, written on another stream
-  if (c->gf_ev && c->gf_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->gf_ev, 0));
-  const LkwLayout L = lkw_layout(w, h, win, max_level);
-  // frames per slice: what the limit holds, at least one window, at most the batch
-  const size_t fit =
-      std::min<size_t>(std::max<size_t>(c->lkw_ws_limit / L.frame_bytes, (size_t)window_len), (size_t)n_frames);
-  const LkwResult R = lkw_result(n_windows, cap, window_len);
-  if ((st = lkw_grow(c, c->lkw_ws, fit * L.frame_bytes + 256)) != ORBX_OK) return st;
-  if ((st = lkw_grow(c, c->lkw_first, sizeof(int32_t) * (size_t)n_windows)) != ORBX_OK) return st;
-  const void* old_res = c->lkw_res.p;
-  if ((st = lkw_grow(c, c->lkw_res, R.bytes)) != ORBX_OK) return st;
-  if (c->lkw_res.p != old_res) c->lkw_n = 0;  // (a larger block: the previous result went with the old one)
-  // The window table goes up through a pinned mirror (a copy from pageable memory would make the host wait for the
-  // stream).  The mirror is reused: the previous call's copy has to have read it.
-  const size_t table = sizeof(int32_t) * (size_t)n_windows;
-  if (!c->lkw_first_ev) HIPCHK(c, hipEventCreateWithFlags(&c->lkw_first_ev, hipEventDisableTiming));
-  HIPCHK(c, hipEventSynchronize(c->lkw_first_ev));
-  if (c->lkw_first_host_bytes < table) {
-    if (c->lkw_first_host) (void)hipHostFree(c->lkw_first_host);
-    c->lkw_first_host = nullptr;
-    c->lkw_first_host_bytes = 0;
-    HIPCHK(c, hipHostMalloc(&c->lkw_first_host, align_up_sz(table, 4096), hipHostMallocDefault));
-    c->lkw_first_host_bytes = align_up_sz(table, 4096);
-  }
-  // from here on the previous result is being replaced
-  c->lkw_n = 0;
-  std::memcpy(c->lkw_first_host, window_first, table);
-  HIPCHK(c, hipMemcpyAsync(c->lkw_first.p, c->lkw_first_host, table, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipEventRecord(c->lkw_first_ev, s));
-  uint8_t* ws = (uint8_t*)c->lkw_ws.p;
-  uint8_t* res = (uint8_t*)c->lkw_res.p;
-  const LkGeom& g = L.g;
-  const size_t img_base = g.top >= 1 ? g.img_off[1] : 0;  // workspace offsets count from level 1
-  const size_t slot_stride = (size_t)cap;
-  // slices of whole consecutive windows whose frames [lo, hi) fit the workspace
-  for (int w0 = 0; w0 < n_windows;) {
-    int lo = window_first[w0], hi = lo + window_len, w1 = w0 + 1;
-    while (w1 < n_windows && w1 - w0 < 65535) {
-      const int nlo = std::min(lo, window_first[w1]), nhi = std::max(hi, window_first[w1] + window_len);
-      if ((size_t)(nhi - nlo) > fit) break;
-      lo = nlo;
-      hi = nhi;
-      w1++;
-    }
-    const int m = hi - lo;
-    uint8_t* ws_img = ws;                                // [m][levels 1 .. top]
-    uint8_t* ws_der = ws + align_up_sz(L.img_bytes * m, 256);  // [m][levels 0 .. top]
-    const uint8_t* f_lo = d_frames + frame_stride * (size_t)lo;
-    for (int l = 1; l <= g.top; l++) {
-      const uint8_t* src = l == 1 ? f_lo : ws_img + (g.img_off[l - 1] - img_base);
-      HIPCHK(c, orbx_launch_lk_pyrdown_frames(s, m, src, g.w[l - 1], g.h[l - 1], l == 1 ? row_stride : g.pitch[l - 1],
-                                              l == 1 ? frame_stride : L.img_bytes, ws_img + (g.img_off[l] - img_base),
-                                              g.w[l], g.h[l], g.pitch[l], L.img_bytes));
-    }
-    for (int l = 0; l <= g.top; l++)
-      HIPCHK(c, orbx_launch_lk_scharr_frames(s, m, l == 0 ? f_lo : ws_img + (g.img_off[l] - img_base), g.w[l], g.h[l],
-                                             l == 0 ? row_stride : g.pitch[l], l == 0 ? frame_stride : L.img_bytes,
-                                             reinterpret_cast<int16_t*>(ws_der + g.der_off[l]), g.der_bytes));
-    OrbxLkFrames F;
-    std::memset(&F, 0, sizeof(F));
-    F.top = g.top;
-    F.first = lo;
-    F.frame_stride = frame_stride;
-    F.img_stride = L.img_bytes;
-    F.der_stride = g.der_bytes / sizeof(int16_t);
-    for (int l = 0; l <= g.top; l++) {
-      F.L[l].img = l == 0 ? d_frames : ws_img + (g.img_off[l] - img_base);
-      F.L[l].deriv = reinterpret_cast<const int16_t*>(ws_der + g.der_off[l]);
-      F.L[l].w = g.w[l];
-      F.L[l].h = g.h[l];
-      F.L[l].pitch = l == 0 ? row_stride : g.pitch[l];
-    }
-    HIPCHK(c, orbx_launch_lk_track_windows(
-                  s, F, (const int32_t*)c->lkw_first.p + w0, w1 - w0, window_len, d_points + 2 * slot_stride * w0,
-                  d_counts ? d_counts + w0 : nullptr, cap, (float*)res + 2 * slot_stride * window_len * w0,
-                  (int32_t*)(res + R.o_seen) + slot_stride * w0,
-                  (float*)(res + R.o_err) + slot_stride * (window_len - 1) * w0, win, max_iters, epsilon * epsilon));
-    w0 = w1;
-  }
-  c->lkw_n = n_windows;
-  c->lkw_cap = cap;
-  c->lkw_len = window_len;
-  return ORBX_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int orbx_lk_track_windows_device(orbx_ctx* c, const void* d_frames, int n_frames, int width, int height,
-                                 int row_stride, size_t frame_stride, const int32_t* window_first, int n_windows,
-                                 int window_len, const float* d_points_xy, const int32_t* d_counts, int slot_capacity,
-                                 int win_size, int max_level, int max_iters, double epsilon, void* stream) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  int st = lkw_check_frames(c, d_frames, n_frames, c->p.max_batch, width, height, row_stride, frame_stride);
-  if (st != ORBX_OK) return st;
-  if ((st = lkw_check_params(c, win_size, max_level, &max_iters, &epsilon)) != ORBX_OK) return st;
-  if (!window_first || !d_points_xy) return fail(c, ORBX_ERR_INVALID_ARG, "window_first / d_points_xy is NULL");
-  if (n_windows < 1 || window_len < 2 || slot_capacity < 1)
-    return fail(c, ORBX_ERR_INVALID_ARG, "n_windows < 1, window_len < 2 or slot_capacity < 1");
-  for (int i = 0; i < n_windows; i++)
-    if (window_first[i] < 0 || window_first[i] > n_frames - window_len)
-      return fail(c, ORBX_ERR_INVALID_ARG, "a window does not lie inside the frames");
-  return lkw_run(c, (const uint8_t*)d_frames, n_frames, width, height, row_stride, frame_stride, window_first,
-                 n_windows, window_len, d_points_xy, d_counts, slot_capacity, win_size, max_level, max_iters, epsilon,
-                 stream ? (hipStream_t)stream : c->stream);
-}
-
-int orbx_lk_workspace_limit(orbx_ctx* c, size_t bytes) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  const int st = lkw_wait(c);
-  if (st != ORBX_OK) return st;
-  if (c->lkw_ws.p) {
-    HIPCHK(c, hipFree(c->lkw_ws.p));
-    c->lkw_ws = DevBuf{};
-  }
-  c->lkw_ws_limit = bytes ? bytes : ORBX_LK_WORKSPACE_DEFAULT;
-  return ORBX_OK;
-}
-
-int orbx_lk_windows_results_device(orbx_ctx* c, orbx_lk_windows_view* v) {
-  DeviceGuard _dg(c);
-  if (!c || !v) return ORBX_ERR_INVALID_ARG;
-  if (c->lkw_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
-  const LkwResult R = lkw_result(c->lkw_n, c->lkw_cap, c->lkw_len);
-  const uint8_t* res = (const uint8_t*)c->lkw_res.p;
-  v->tracks_xy = (const float*)res;
-  v->seen = (const int32_t*)(res + R.o_seen);
-  v->err = (const float*)(res + R.o_err);
-  v->slot_capacity = c->lkw_cap;
-  v->window_len = c->lkw_len;
-  v->n_windows = c->lkw_n;
-  return ORBX_OK;
-}
-
-int orbx_lk_windows_fetch(orbx_ctx* c, int first, int n, float* tracks_xy, int32_t* seen, float* err) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (c->lkw_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
-  if (first < 0 || n < 1 || first >= c->lkw_n || n > c->lkw_n - first)
-    return fail(c, ORBX_ERR_INVALID_ARG, "[first, first + n) outside the batch");
-  const int st = lkw_wait(c);
-  if (st != ORBX_OK) return st;
-  const LkwResult R = lkw_result(c->lkw_n, c->lkw_cap, c->lkw_len);
-  const uint8_t* res = (const uint8_t*)c->lkw_res.p;
-  const size_t slots = (size_t)c->lkw_cap, len = (size_t)c->lkw_len;
-  if (tracks_xy)
-    HIPCHK(c, hipMemcpy(tracks_xy, res + sizeof(float) * 2 * slots * len * first, sizeof(float) * 2 * slots * len * n,
-                        hipMemcpyDeviceToHost));
-  if (seen)
-    HIPCHK(c, hipMemcpy(seen, res + R.o_seen + sizeof(int32_t) * slots * first, sizeof(int32_t) * slots * n,
-                        hipMemcpyDeviceToHost));
-  if (err)
-    HIPCHK(c, hipMemcpy(err, res + R.o_err + sizeof(float) * slots * (len - 1) * first,
-                        sizeof(float) * slots * (len - 1) * n, hipMemcpyDeviceToHost));
-  return ORBX_OK;
-}
-
-int orbx_lk_track_window(orbx_ctx* c, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
-                         size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen, float* err,
-                         int win_size, int max_level, int max_iters, double epsilon) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  int st = lkw_check_frames(c, frames, n_frames, 65535, width, height, row_stride, frame_stride);
-  if (st != ORBX_OK) return st;
-  if ((st = lkw_check_params(c, win_size, max_level, &max_iters, &epsilon)) != ORBX_OK) return st;
-  if (n < 0 || (n > 0 && (!pts_xy || !tracks_xy || !seen)))
-    return fail(c, ORBX_ERR_INVALID_ARG, "n < 0 or pts_xy / tracks_xy / seen is NULL");
-  if (n == 0) return ORBX_OK;  // no points: nothing to track, the last result stays
-  if ((st = lkw_enter(c, c->stream)) != ORBX_OK) return st;
-  const size_t tight = (size_t)width * height;
-  {
-    const LkwMark mark{c, c->stream};
-    if ((st = lkw_grow(c, c->lkw_img, tight * n_frames)) != ORBX_OK) return st;
-    if ((st = lkw_grow(c, c->lkw_pts, sizeof(float) * 2 * (size_t)n)) != ORBX_OK) return st;
-    if (row_stride == width && frame_stride == tight) {
-      HIPCHK(c, hipMemcpyAsync(c->lkw_img.p, frames, tight * n_frames, hipMemcpyHostToDevice, c->stream));
-    } else {
-      for (int i = 0; i < n_frames; i++)
-        HIPCHK(c, hipMemcpy2DAsync((uint8_t*)c->lkw_img.p + tight * i, width, frames + frame_stride * i, row_stride,
-                                   width, height, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipMemcpyAsync(c->lkw_pts.p, pts_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  }
-  const int32_t first = 0;
-  if ((st = lkw_run(c, (const uint8_t*)c->lkw_img.p, n_frames, width, height, width, tight, &first, 1, n_frames,
-                    (const float*)c->lkw_pts.p, nullptr, n, win_size, max_level, max_iters, epsilon, c->stream)) !=
-      ORBX_OK)
-    return st;
-  return orbx_lk_windows_fetch(c, 0, 1, tracks_xy, seen, err);
-}
-
-}  // extern "C"
-
-// ---- relative pose (next row) ---------------------------
-
-namespace {
-bool pose_args_ok(const double* K, double prob, double threshold, int max_iters) {
-  return K && K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) &&
-         std::isfinite(K[5]) && std::isfinite(prob) && std::isfinite(threshold) && threshold >= 0 && max_iters >= 0;
-}
-void pose_unpack(const OrbxPoseOut& r, double* E, double* R, double* t, int32_t* inliers, int32_t* good,
-                 int32_t* iters) {
-  if (E) memcpy(E, r.E, sizeof r.E);
-  if (R) memcpy(R, r.R, sizeof r.R);
-  if (t) memcpy(t, r.t, sizeof r.t);
-  if (inliers) *inliers = r.inliers;
-  if (good) *good = r.good;
-  if (iters) *iters = r.iters;
-}
-}  // namespace
-
-extern "C" {
-
-int orbx_estimate_pose(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, int n, const double* K, double prob,
-                       double threshold, int max_iters, uint64_t seed, double* E, double* R, double* t, uint8_t* mask,
-                       int32_t* inliers, int32_t* good, int32_t* iters) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (n < 0 || (n > 0 && (!pts1_xy || !pts2_xy)) || !E || !R || !t || !inliers || !good || !iters ||
-      !pose_args_ok(K, prob, threshold, max_iters))
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
-  const int cap = n > 0 ? n : 1;
-  ENSURE(c, c->ph_in, sizeof(float) * 4 * (size_t)cap);
-  ENSURE(c, c->ph_pts, sizeof(OrbxPosePt) * (size_t)cap);
-  ENSURE(c, c->ph_n, sizeof(int32_t));
-  ENSURE(c, c->ph_out, sizeof(OrbxPoseOut));
-  ENSURE(c, c->ph_mask, (size_t)cap);
-  hipStream_t s = c->stream;
-  float* d_p1 = (float*)c->ph_in.p;
-  float* d_p2 = d_p1 + 2 * (size_t)cap;
-  if (n > 0) {
-    HIPCHK(c, hipMemcpyAsync(d_p1, pts1_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_p2, pts2_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
-  }
-  HIPCHK(c, orbx_launch_pose_prep_host(s, n, d_p1, d_p2, K, (OrbxPosePt*)c->ph_pts.p, (int32_t*)c->ph_n.p));
-  HIPCHK(c, orbx_launch_pose_ransac(s, 1, cap, (const OrbxPosePt*)c->ph_pts.p, (const int32_t*)c->ph_n.p, K, prob,
-                                    threshold, max_iters, seed, (OrbxPoseOut*)c->ph_out.p, (uint8_t*)c->ph_mask.p));
-  OrbxPoseOut r;
-  HIPCHK(c, hipMemcpyAsync(&r, c->ph_out.p, sizeof r, hipMemcpyDeviceToHost, s));
-  if (mask && n > 0) HIPCHK(c, hipMemcpyAsync(mask, c->ph_mask.p, (size_t)n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  pose_unpack(r, E, R, t, inliers, good, iters);
-  return ORBX_OK;
-}
-
-int orbx_batch_pose_consecutive(orbx_ctx* c, const double* K, double prob, double threshold, int max_iters,
-                                uint64_t seed) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!pose_args_ok(K, prob, threshold, max_iters)) return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
-  if (c->match_pairs <= 0 || c->match_serial != c->batch_serial)
-    return fail(c, ORBX_ERR_INVALID_ARG, "the last batch has not been matched (orbx_batch_match_consecutive)");
-  // the pose buffers are ONE set per context, like the matcher's
-  if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
-  const Block& B = last_block(c);
-  const int npairs = c->match_pairs, cap = B.cap;
-  const size_t e = (size_t)npairs * cap;
-  ENSURE(c, c->pb_pts, sizeof(OrbxPosePt) * e);
-  ENSURE(c, c->pb_n, sizeof(int32_t) * (size_t)npairs);
-  ENSURE(c, c->pb_out, sizeof(OrbxPoseOut) * (size_t)npairs);
-  ENSURE(c, c->pb_mask, e);
-  const OutLayout& o = B.layout;
-  hipStream_t s = batch_stream(c);
-  HIPCHK(c, orbx_launch_pose_prep_batch(s, npairs, cap, (const int32_t*)(B.d + o.counts),
-                                        (const orbx_keypoint*)(B.d + o.kp), (const int32_t*)c->m_match.p, K,
-                                        (OrbxPosePt*)c->pb_pts.p, (int32_t*)c->pb_n.p));
-  HIPCHK(c, orbx_launch_pose_ransac(s, npairs, cap, (const OrbxPosePt*)c->pb_pts.p, (const int32_t*)c->pb_n.p, K, prob,
-                                    threshold, max_iters, seed, (OrbxPoseOut*)c->pb_out.p, (uint8_t*)c->pb_mask.p));
-  c->pose_pairs = npairs;
-  c->pose_cap = cap;
-  c->pose_stream = s;
-  c->pose_serial = c->batch_serial;
-  c->pose_match_gen = c->match_gen;
-  return ORBX_OK;
-}
-
-int orbx_batch_pose_fetch(orbx_ctx* c, int first, int n, double* E, double* R, double* t, int32_t* inliers,
-                          int32_t* good, int32_t* iters) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (c->pose_pairs <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been posed");
-  if (first < 0 || n < 0 || first + n > c->pose_pairs)
-    return fail(c, ORBX_ERR_INVALID_ARG, "pairs outside the last posed batch");
-  if (n == 0) return ORBX_OK;
-  std::vector<OrbxPoseOut> r((size_t)n);
-  HIPCHK(c, hipMemcpyAsync(r.data(), (const OrbxPoseOut*)c->pb_out.p + first, sizeof(OrbxPoseOut) * (size_t)n,
-                           hipMemcpyDeviceToHost, c->pose_stream));
-  HIPCHK(c, hipStreamSynchronize(c->pose_stream));
-  for (int i = 0; i < n; i++)
-    pose_unpack(r[(size_t)i], E ? E + 9 * i : nullptr, R ? R + 9 * i : nullptr, t ? t + 3 * i : nullptr,
-                inliers ? inliers + i : nullptr, good ? good + i : nullptr, iters ? iters + i : nullptr);
-  return ORBX_OK;
-}
-
-int orbx_batch_pose_mask(orbx_ctx* c, int pair, uint8_t* mask, int capacity, int* count) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!count || capacity < 0 || (capacity > 0 && !mask)) return fail(c, ORBX_ERR_INVALID_ARG, "bad mask arguments");
-  if (pair < 0 || pair >= c->pose_pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last posed batch");
-  int32_t np = 0;
-  HIPCHK(c, hipMemcpyAsync(&np, (const int32_t*)c->pb_n.p + pair, sizeof np, hipMemcpyDeviceToHost, c->pose_stream));
-  HIPCHK(c, hipStreamSynchronize(c->pose_stream));
-  *count = np;
-  if (np > capacity) return fail(c, ORBX_ERR_CAPACITY, "capacity smaller than the pair's match count");
-  if (np > 0) {
-    HIPCHK(c, hipMemcpyAsync(mask, (const uint8_t*)c->pb_mask.p + (size_t)pair * c->pose_cap, (size_t)np,
-                             hipMemcpyDeviceToHost, c->pose_stream));
-    HIPCHK(c, hipStreamSynchronize(c->pose_stream));
-  }
-  return ORBX_OK;
-}
-
-}  // extern "C"
-
-// ---- triangulation, relative scale, trajectory chaining ------------
-
-namespace {
-bool finite_all(const double* v, int n) {
-  for (int i = 0; i < n; i++)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-}  // namespace
-
-extern "C" {
-
-int orbx_triangulate(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, int n, const double* K, const double* R,
-                     const double* t, float* xyz, uint8_t* valid) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (n < 0 || (n > 0 && (!pts1_xy || !pts2_xy || !xyz || !valid)) || !K || !R || !t || !finite_all(K, 9) ||
-      !finite_all(R, 9) || !finite_all(t, 3))
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad triangulation arguments");
-  if (n == 0) return ORBX_OK;
-  ENSURE(c, c->sh_in, sizeof(float) * 4 * (size_t)n);
-  ENSURE(c, c->sh_xyz, sizeof(float) * 3 * (size_t)n);
-  ENSURE(c, c->sh_valid, (size_t)n);
-  hipStream_t s = c->stream;
-  float* d_p1 = (float*)c->sh_in.p;
-  float* d_p2 = d_p1 + 2 * (size_t)n;
-  HIPCHK(c, hipMemcpyAsync(d_p1, pts1_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d_p2, pts2_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
-  HIPCHK(c, orbx_launch_triangulate_host(s, n, d_p1, d_p2, K, R, t, (float*)c->sh_xyz.p, (uint8_t*)c->sh_valid.p));
-  HIPCHK(c, hipMemcpyAsync(xyz, c->sh_xyz.p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(valid, c->sh_valid.p, (size_t)n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  return ORBX_OK;
-}
-
-int orbx_estimate_scale(orbx_ctx* c, const float* prev_xyz, const uint8_t* prev_valid, int n_prev, const float* cur_xyz,
-                        const uint8_t* cur_valid, int n_cur, double* scale, int32_t* ratios_used) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (n_prev < 0 || n_cur < 0 || (n_prev > 0 && !prev_xyz) || (n_cur > 0 && !cur_xyz) || !scale || !ratios_used)
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad scale arguments");
-  const int m = std::min(n_prev, n_cur);
-  if (m == 0) {  // src/feature_matching.cpp:248-249
-    *scale = 1.0;
-    *ratios_used = 0;
-    return ORBX_OK;
-  }
-  if ((size_t)m * 8 > ORBX_SCALE_LDS_MAX)
-    return fail(c, ORBX_ERR_UNSUPPORTED, "more aligned points than the selection holds in LDS");
-  // only the first m points of either list enter
-  ENSURE(c, c->sh_xyz, sizeof(float) * 6 * (size_t)m);
-  ENSURE(c, c->sh_valid, 2 * (size_t)m);
-  ENSURE(c, c->sh_out, sizeof(OrbxScaleOut));
-  hipStream_t s = c->stream;
-  float* d_prev = (float*)c->sh_xyz.p;
-  float* d_cur = d_prev + 3 * (size_t)m;
-  uint8_t* d_pv = (uint8_t*)c->sh_valid.p;
-  uint8_t* d_cv = d_pv + m;
-  HIPCHK(c, hipMemcpyAsync(d_prev, prev_xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d_cur, cur_xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
-  if (prev_valid) HIPCHK(c, hipMemcpyAsync(d_pv, prev_valid, (size_t)m, hipMemcpyHostToDevice, s));
-  if (cur_valid) HIPCHK(c, hipMemcpyAsync(d_cv, cur_valid, (size_t)m, hipMemcpyHostToDevice, s));
-  HIPCHK(c, orbx_launch_scale_aligned(s, m, m, d_prev, prev_valid ? d_pv : nullptr, d_cur, cur_valid ? d_cv : nullptr,
-                                      (OrbxScaleOut*)c->sh_out.p));
-  OrbxScaleOut r;
-  HIPCHK(c, hipMemcpyAsync(&r, c->sh_out.p, sizeof r, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  *scale = r.scale;
-  *ratios_used = r.ratios_used;
-  return ORBX_OK;
-}
-
-int orbx_batch_scale_consecutive(orbx_ctx* c, const double* K) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!K || !finite_all(K, 9)) return fail(c, ORBX_ERR_INVALID_ARG, "bad scale arguments");
-  if (c->pose_pairs <= 0 || c->pose_serial != c->batch_serial)
-    return fail(c, ORBX_ERR_INVALID_ARG, "the last batch has not been posed (orbx_batch_pose_consecutive)");
-  // the triangulation reads the match table again: it must still hold the matches the poses were computed from
-  // (a host-array matcher call reuses the scratch and zeroes match_pairs; a second batch match bumps match_gen)
-  if (c->match_pairs != c->pose_pairs || c->match_serial != c->batch_serial || c->pose_match_gen != c->match_gen)
-    return fail(c, ORBX_ERR_INVALID_ARG, "the match table has been rewritten since the batch was posed");
-  const int npairs = c->pose_pairs, cap = c->pose_cap;
-  if ((size_t)cap * 16 > ORBX_SCALE_LDS_MAX)
-    return fail(c, ORBX_ERR_UNSUPPORTED, "more result slots per frame than the join holds in LDS");
-  // the scale buffers are ONE set per context, like the pose buffers
-  if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
-  const size_t e = (size_t)npairs * cap;
-  ENSURE(c, c->sb_xyz, sizeof(float) * 3 * e);
-  ENSURE(c, c->sb_valid, e);
-  ENSURE(c, c->sb_mq, sizeof(int32_t) * e);
-  ENSURE(c, c->sb_mt, sizeof(int32_t) * e);
-  ENSURE(c, c->sb_n, sizeof(int32_t) * (size_t)npairs);
-  ENSURE(c, c->sb_out, sizeof(OrbxScaleOut) * (size_t)npairs);
-  const Block& B = last_block(c);
-  const OutLayout& o = B.layout;
-  hipStream_t s = c->pose_stream;
-  HIPCHK(c, orbx_launch_triangulate_batch(s, npairs, cap, (const int32_t*)(B.d + o.counts),
-                                          (const orbx_keypoint*)(B.d + o.kp), (const int32_t*)c->m_match.p,
-                                          (const OrbxPoseOut*)c->pb_out.p, K, (float*)c->sb_xyz.p,
-                                          (uint8_t*)c->sb_valid.p, (int32_t*)c->sb_mq.p, (int32_t*)c->sb_mt.p,
-                                          (int32_t*)c->sb_n.p));
-  HIPCHK(c, orbx_launch_scale_join(s, npairs, cap, (const int32_t*)c->sb_n.p, (const int32_t*)c->sb_mq.p,
-                                   (const int32_t*)c->sb_mt.p, (const float*)c->sb_xyz.p,
-                                   (const uint8_t*)c->sb_valid.p, (const OrbxPoseOut*)c->pb_out.p,
-                                   (OrbxScaleOut*)c->sb_out.p));
-  c->scale_pairs = npairs;
-  c->scale_cap = cap;
-  c->scale_stream = s;
-  return ORBX_OK;
-}
-
-int orbx_batch_scale_fetch(orbx_ctx* c, int first, int n, double* scale, int32_t* triplets, int32_t* ratios_used) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (c->scale_pairs <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been scaled");
-  if (first < 0 || n < 0 || first + n > c->scale_pairs)
-    return fail(c, ORBX_ERR_INVALID_ARG, "pairs outside the last scaled batch");
-  if (n == 0) return ORBX_OK;
-  std::vector<OrbxScaleOut> r((size_t)n);
-  HIPCHK(c, hipMemcpyAsync(r.data(), (const OrbxScaleOut*)c->sb_out.p + first, sizeof(OrbxScaleOut) * (size_t)n,
-                           hipMemcpyDeviceToHost, c->scale_stream));
-  HIPCHK(c, hipStreamSynchronize(c->scale_stream));
-  for (int i = 0; i < n; i++) {
-    if (scale) scale[i] = r[(size_t)i].scale;
-    if (triplets) triplets[i] = r[(size_t)i].triplets;
-    if (ratios_used) ratios_used[i] = r[(size_t)i].ratios_used;
-  }
-  return ORBX_OK;
-}
-
-int orbx_batch_points_fetch(orbx_ctx* c, int pair, float* xyz, uint8_t* valid, int capacity, int* count) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!count || capacity < 0 || (capacity > 0 && (!xyz || !valid)))
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad point output arguments");
-  if (pair < 0 || pair >= c->scale_pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last scaled batch");
-  hipStream_t s = c->scale_stream;
-  int32_t np = 0;
-  HIPCHK(c, hipMemcpyAsync(&np, (const int32_t*)c->sb_n.p + pair, sizeof np, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  *count = np;
-  if (np > capacity) return fail(c, ORBX_ERR_CAPACITY, "capacity smaller than the pair's match count");
-  if (np > 0) {
-    const size_t row = (size_t)pair * c->scale_cap;
-    HIPCHK(c, hipMemcpyAsync(xyz, (const float*)c->sb_xyz.p + 3 * row, sizeof(float) * 3 * (size_t)np,
-                             hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(valid, (const uint8_t*)c->sb_valid.p + row, (size_t)np, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-  }
-  return ORBX_OK;
-}
-
-int orbx_chain_trajectory(const double* T0, const double* R, const double* t, const double* scale, int n,
-                          double* poses) {
-  if (!T0 || !poses || n < 0 || (n > 0 && (!R || !t || !scale))) return ORBX_ERR_INVALID_ARG;
-  std::memcpy(poses, T0, sizeof(double) * 16);
-  for (int i = 0; i < n; i++) tri_chain(poses + 16 * i, R + 9 * i, t + 3 * i, scale[i], poses + 16 * (i + 1));
-  return ORBX_OK;
-}
-
-}  // extern "C"
-
-// ---- bundle adjustment -----------------------------------------------
-
-static_assert(sizeof(orbx_ba_summary) == 32, "orbx_ba_summary is the kernel's BaSummary");
-
-extern "C" {
-
-int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const int32_t* pose_offset, double* poses6,
-                             const int32_t* point_offset, double* points3, const int32_t* obs_offset,
-                             const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
-                             double huber_delta, int max_iters, orbx_ba_summary* summaries) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!K || !finite_all(K, 9) || n_windows < 0 || !(huber_delta > 0.0) || !std::isfinite(huber_delta) ||
-      max_iters < 1 || max_iters > 1000)
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
-  if (n_windows == 0) return ORBX_OK;
-  if (!pose_offset || !poses6 || !point_offset || !points3 || !obs_offset || !obs_point || !obs_pose || !obs_xy ||
-      !summaries)
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
-  if (pose_offset[0] != 0 || point_offset[0] != 0 || obs_offset[0] != 0)
-    return fail(c, ORBX_ERR_INVALID_ARG, "offset arrays start at 0");
-  int cap = 1, ocap = 1;
-  for (int w = 0; w < n_windows; w++) {
-    const long long W = (long long)pose_offset[w + 1] - pose_offset[w], N = (long long)point_offset[w + 1] - point_offset[w],
-                    M = (long long)obs_offset[w + 1] - obs_offset[w];
-    if (W < 2 || W > ORBX_BA_MAX_POSES) return fail(c, ORBX_ERR_INVALID_ARG, "a window has 2 .. 8 poses");
-    if (N < 1 || M < N || M > N * W)
-      return fail(c, ORBX_ERR_INVALID_ARG, "every landmark has 1 .. n_poses observations");
-    if (N > ORBX_BA_MAX_POINTS) return fail(c, ORBX_ERR_UNSUPPORTED, "more landmarks in a window than 65536");
-    cap = std::max(cap, (int)N);
-    ocap = std::max(ocap, (int)M);
-  }
-  const size_t tp = (size_t)pose_offset[n_windows], tn = (size_t)point_offset[n_windows], tm = (size_t)obs_offset[n_windows];
-  if (tn + (size_t)n_windows > 0x7fffffffu || tm > 0x7fffffffu)
-    return fail(c, ORBX_ERR_UNSUPPORTED, "more landmarks or observations in a batch than 32-bit offsets hold");
-  if (!finite_all(poses6, (int)(6 * tp))) return fail(c, ORBX_ERR_INVALID_ARG, "a pose is not finite");
-  for (size_t i = 0; i < 3 * tn; i++)
-    if (!std::isfinite(points3[i])) return fail(c, ORBX_ERR_INVALID_ARG, "a point is not finite");
-  for (size_t i = 0; i < 2 * tm; i++)
-    if (!std::isfinite(obs_xy[i])) return fail(c, ORBX_ERR_INVALID_ARG, "an observation is not finite");
-  // CSR by (landmark, pose), per window (src/with_bundle_adjustment.cpp:651-666 adds the residual blocks landmark by
-  // landmark)
-  std::vector<int32_t> rows(tn + (size_t)n_windows), order;
-  std::vector<uint8_t> opose(tm);
-  std::vector<double> oxy(2 * tm);
-  for (int w = 0; w < n_windows; w++) {
-    const int W = pose_offset[w + 1] - pose_offset[w], N = point_offset[w + 1] - point_offset[w];
-    const int M = obs_offset[w + 1] - obs_offset[w];
-    const int32_t* op = obs_point + obs_offset[w];
-    const int32_t* oq = obs_pose + obs_offset[w];
-    for (int k = 0; k < M; k++)
-      if (op[k] < 0 || op[k] >= N || oq[k] < 0 || oq[k] >= W)
-        return fail(c, ORBX_ERR_INVALID_ARG, "an observation's landmark or pose index is out of range");
-    // every (landmark, pose) occurs at most once, so placing observation k at key landmark * W + pose and reading
-    // the keys in ascending order IS the stable sort by (landmark, pose)
-    order.assign((size_t)N * W, -1);
-    for (int k = 0; k < M; k++) {
-      int32_t& at = order[(size_t)op[k] * W + oq[k]];
-      if (at >= 0) return fail(c, ORBX_ERR_INVALID_ARG, "a landmark is observed twice by one pose");
-      at = k;
-    }
-    int32_t* row = rows.data() + point_offset[w] + w;
-    std::fill(row, row + N + 1, 0);
-    size_t dst = (size_t)obs_offset[w];
-    for (size_t key = 0; key < order.size(); key++) {
-      const int o = order[key];
-      if (o < 0) continue;
-      row[op[o] + 1]++;
-      opose[dst] = (uint8_t)oq[o];
-      oxy[2 * dst] = obs_xy[2 * ((size_t)obs_offset[w] + o)];
-      oxy[2 * dst + 1] = obs_xy[2 * ((size_t)obs_offset[w] + o) + 1];
-      dst++;
-    }
-    for (int j = 0; j < N; j++) {
-      if (row[j + 1] == 0) return fail(c, ORBX_ERR_INVALID_ARG, "a landmark has no observation");
-      row[j + 1] += row[j];
-    }
-  }
-  // workgroups: as many as windows, bounded by ORBX_BA_MAX_GROUPS and by the workspace budget
-  const size_t per_group = sizeof(double) * ((size_t)ORBX_BA_WS_POINT * cap + (size_t)ORBX_BA_WS_OBS * ocap) + 8 * (size_t)cap;
-  int groups = std::min(n_windows, ORBX_BA_MAX_GROUPS);
-  groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)groups, ORBX_BA_WS_BUDGET / per_group));
-  const size_t noff = (size_t)n_windows + 1;
-  ENSURE(c, c->ba_off, sizeof(int32_t) * 3 * noff);
-  ENSURE(c, c->ba_poses, sizeof(double) * 6 * tp);
-  ENSURE(c, c->ba_points, sizeof(double) * 3 * tn);
-  ENSURE(c, c->ba_rows, sizeof(int32_t) * rows.size());
-  ENSURE(c, c->ba_opose, tm);
-  ENSURE(c, c->ba_oxy, sizeof(double) * 2 * tm);
-  ENSURE(c, c->ba_wp, sizeof(double) * ORBX_BA_WS_POINT * (size_t)cap * groups);
-  ENSURE(c, c->ba_wo, sizeof(double) * ORBX_BA_WS_OBS * (size_t)ocap * groups);
-  ENSURE(c, c->ba_slot, 8 * (size_t)cap * groups);
-  ENSURE(c, c->ba_out, sizeof(orbx_ba_summary) * (size_t)n_windows);
-  hipStream_t s = c->stream;
-  int32_t* d_off = (int32_t*)c->ba_off.p;
-  HIPCHK(c, hipMemcpyAsync(d_off, pose_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d_off + noff, point_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d_off + 2 * noff, obs_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba_poses.p, poses6, sizeof(double) * 6 * tp, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba_points.p, points3, sizeof(double) * 3 * tn, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba_rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba_opose.p, opose.data(), tm, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba_oxy.p, oxy.data(), sizeof(double) * 2 * tm, hipMemcpyHostToDevice, s));
-  const double K4[4] = {K[0], K[4], K[2], K[5]};
-  HIPCHK(c, orbx_launch_ba(s, n_windows, groups, max_iters, K4, huber_delta, d_off, d_off + noff, d_off + 2 * noff,
-                           (double*)c->ba_poses.p, (double*)c->ba_points.p, (const int32_t*)c->ba_rows.p,
-                           (const uint8_t*)c->ba_opose.p, (const double*)c->ba_oxy.p, cap, ocap, (double*)c->ba_wp.p,
-                           (double*)c->ba_wo.p, (unsigned long long*)c->ba_slot.p, c->ba_out.p));
-  // the staged vectors are pageable: their copies above have left the host before the calls returned
-  HIPCHK(c, hipMemcpyAsync(poses6, c->ba_poses.p, sizeof(double) * 6 * tp, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(points3, c->ba_points.p, sizeof(double) * 3 * tn, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(summaries, c->ba_out.p, sizeof(orbx_ba_summary) * (size_t)n_windows, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  return ORBX_OK;
-}
-
-int orbx_bundle_adjust(orbx_ctx* c, const double* K, int n_poses, double* poses6, int n_points, double* points3,
-                       int n_obs, const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
-                       double huber_delta, int max_iters, orbx_ba_summary* summary) {
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (n_poses < 0 || n_points < 0 || n_obs < 0) return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
-  const int32_t po[2] = {0, n_poses}, pt[2] = {0, n_points}, ob[2] = {0, n_obs};
-  return orbx_bundle_adjust_batch(c, K, 1, po, poses6, pt, points3, ob, obs_point, obs_pose, obs_xy, huber_delta,
-                                  max_iters, summary);
-}
-
-}  // extern "C"
-
-// ---- Shi-Tomasi corners (next row) ------------------------
-namespace {
-
-// the sections of the workspace for m frames of w x h with a cell grid of grid_stride words per frame
-struct GfLayout {
-  size_t map, keys, grid, cnt, total, pool, grid_stride;
-};
-GfLayout gf_layout(int m, int w, int h, size_t grid_stride) {
-  GfLayout o;
-  const size_t px = (size_t)w * h;
-  o.pool = (size_t)(w - 2) * (h - 2);
-  o.grid_stride = grid_stride;
-  o.map = 0;
-  o.keys = align_up_sz(sizeof(float) * px * m, 256);
-  o.grid = align_up_sz(o.keys + sizeof(unsigned long long) * o.pool * m, 256);
-  o.cnt = align_up_sz(o.grid + sizeof(uint32_t) * grid_stride * m, 256);
-  o.total = o.cnt + 2 * sizeof(uint32_t) * (size_t)m;  // maxima, then candidate counts
-  return o;
-}
-// the largest grid of a w x h frame: w * h cells of one slot (cell 1) or, from cell 2 on, at most
-// ceil(w / 2) * ceil(h / 2) cells of four -- both within (w + 1)(h + 1) words
-size_t gf_grid_bound(int w, int h) { return (size_t)(w + 1) * (h + 1); }
-
-struct GfArgs {
-  int cap, suppress, cell, gw, gh, slots;
-  double quality, min_distance;
-};
-
-int gf_check_params(orbx_ctx* c, double quality, double min_distance) {
-  if (!std::isfinite(quality) || !(quality > 0.0) || quality > 1.0)
-    return fail(c, ORBX_ERR_INVALID_ARG, "quality_level must be finite, in (0, 1]");
-  if (!std::isfinite(min_distance) || min_distance < 0.0)
-    return fail(c, ORBX_ERR_INVALID_ARG, "min_distance must be finite, >= 0");
-  if (min_distance > ORBX_GFTT_MAX_MIN_DISTANCE)
-    return fail(c, ORBX_ERR_UNSUPPORTED, "min_distance above ORBX_GFTT_MAX_MIN_DISTANCE");
-  return ORBX_OK;
-}
-
-GfArgs gf_args(int w, int h, int max_corners, double quality, double min_distance) {
-  GfArgs a;
-  const long long pool = (long long)(w - 2) * (h - 2);
-  a.cap = (int)(max_corners > 0 ? std::min<long long>(max_corners, pool) : pool);
-  a.quality = quality;
-  a.min_distance = min_distance;
-  a.suppress = min_distance >= 1.0;
-  a.cell = a.suppress ? (int)std::nearbyint(min_distance) : 1;  // cvRound: half to even (default rounding mode)
-  a.gw = (w + a.cell - 1) / a.cell;
-  a.gh = (h + a.cell - 1) / a.cell;
-  a.slots = a.cell == 1 ? 1 : 4;
-  return a;
-}
-
-// waits for the good-features work enqueued so far, on whatever stream it ran: through the event recorded behind it,
-// never through the stream itself (a caller's stream need not outlive its batch's end)
-int gf_wait(orbx_ctx* c) {
-  if (c->gf_ev) HIPCHK(c, hipEventSynchronize(c->gf_ev));
-  return ORBX_OK;
-}
-
-// a good-features call on stream s: earlier good-features work on another stream has to be done (one workspace)
-int gf_enter(orbx_ctx* c, hipStream_t s) {
-  if (!c->gf_ev) HIPCHK(c, hipEventCreateWithFlags(&c->gf_ev, hipEventDisableTiming));
-  if (c->gf_stream != s) {
-    const int st = gf_wait(c);
-    if (st != ORBX_OK) return st;
-  }
-  c->gf_stream = s;
-  return ORBX_OK;
-}
-
-// records the event behind whatever a good-features call has enqueued on s, on every way out of the call
-struct GfMark {
-  orbx_ctx* c;
-  hipStream_t s;
-  ~GfMark() {
-    if (c->gf_ev) (void)hipEventRecord(c->gf_ev, s);
-  }
-};
-
-// the workspace: allocated once, for as many frames of the largest size as the limit holds (at least one, at most
-// max_batch)
-int gf_workspace(orbx_ctx* c) {
-  if (c->gf_ws.p) return ORBX_OK;
-  const int mw = c->p.max_width, mh = c->p.max_height;
-  const size_t one = gf_layout(1, mw, mh, gf_grid_bound(mw, mh)).total + 1024;
-  const size_t frames = std::min<size_t>(std::max<size_t>(c->gf_ws_limit / one, 1), (size_t)c->p.max_batch);
-  ENSURE(c, c->gf_ws, gf_layout((int)frames, mw, mh, gf_grid_bound(mw, mh)).total + 1024);
-  return ORBX_OK;
-}
-
-// frames of w x h per slice
-int gf_slice_frames(const orbx_ctx* c, int n, int w, int h, size_t grid_stride) {
-  const size_t one = gf_layout(1, w, h, grid_stride).total + 1024;  // (the sections' alignment: < 1024 bytes)
-  const size_t fit = std::max<size_t>((c->gf_ws.bytes - 1024) / one, 1);
-  const int m = (int)std::min<size_t>(fit, (size_t)n);
-  const int slices = (n + m - 1) / m;
-  return (n + slices - 1) / slices;  // even slices
-}
-
-// enqueues the three stages for n device frames; the results go to gf_res (counts | corners)
-int gf_run(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row_stride, size_t frame_stride,
-           const GfArgs& a, hipStream_t s) {
-  int st = gf_enter(c, s);
-  if (st != ORBX_OK) return st;
-  const GfMark mark{c, s};
-  c->gf_n = 0;  // (a failed call leaves no "last batch")
-  if ((st = gf_workspace(c)) != ORBX_OK) return st;
-  const size_t o_corners = align_up_sz(sizeof(int32_t) * (size_t)n, 256);
-  const size_t res_bytes = o_corners + sizeof(float) * 2 * (size_t)a.cap * n;
-  if (c->gf_res.p && c->gf_res.bytes < res_bytes && (st = gf_wait(c)) != ORBX_OK) return st;  // (still written?)
-  ENSURE(c, c->gf_res, res_bytes);
-  const size_t grid_stride = a.suppress ? (size_t)a.gw * a.gh * a.slots : 0;
-  const int per = gf_slice_frames(c, n, w, h, grid_stride);
-  int32_t* d_counts = (int32_t*)c->gf_res.p;
-  float* d_corners = (float*)((uint8_t*)c->gf_res.p + o_corners);
-  for (int f0 = 0; f0 < n; f0 += per) {
-    const int m = std::min(per, n - f0);
-    const GfLayout L = gf_layout(m, w, h, grid_stride);
-    uint8_t* ws = (uint8_t*)c->gf_ws.p;
-    uint32_t* d_max = (uint32_t*)(ws + L.cnt);
-    int32_t* d_ncand = (int32_t*)(d_max + m);
-    HIPCHK(c, hipMemsetAsync(d_max, 0, 2 * sizeof(uint32_t) * (size_t)m, s));
-    if (a.suppress) HIPCHK(c, hipMemsetAsync(ws + L.grid, 0xff, sizeof(uint32_t) * grid_stride * m, s));
-    HIPCHK(c, orbx_launch_gftt_response(s, d_frames + frame_stride * (size_t)f0, m, w, h, row_stride, frame_stride,
-                                        (float*)(ws + L.map), d_max));
-    HIPCHK(c, orbx_launch_gftt_candidates(s, (const float*)(ws + L.map), m, w, h, d_max, a.quality,
-                                          (unsigned long long*)(ws + L.keys), L.pool, d_ncand));
-    HIPCHK(c, orbx_launch_gftt_select(s, m, w, (unsigned long long*)(ws + L.keys), L.pool, d_ncand, a.min_distance,
-                                      a.cell, a.gw, a.gh, a.slots, (uint32_t*)(ws + L.grid), grid_stride, a.cap,
-                                      d_counts + f0, d_corners + (size_t)2 * a.cap * f0));
-  }
-  c->gf_n = n;
-  c->gf_cap = a.cap;
-  return ORBX_OK;
-}
-
-// a host image, tightly packed, in gf_img on the context's stream
-int gf_upload(orbx_ctx* c, const uint8_t* image, int w, int h, int stride) {
-  int st = gf_enter(c, c->stream);
-  if (st != ORBX_OK) return st;
-  const GfMark mark{c, c->stream};
-  ENSURE(c, c->gf_img, (size_t)w * h);
-  HIPCHK(c, hipMemcpy2DAsync(c->gf_img.p, w, image, stride, w, h, hipMemcpyHostToDevice, c->stream));
-  return ORBX_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int orbx_corner_min_eigen_val(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, float* eig) {
-  DeviceGuard _dg(c);
-  int st = check_image(c, image, width, height, stride);
-  if (st != ORBX_OK) return st;
-  if (!eig) return fail(c, ORBX_ERR_INVALID_ARG, "eig is NULL");
-  if ((st = gf_upload(c, image, width, height, stride)) != ORBX_OK) return st;
-  const GfMark mark{c, c->stream};
-  if ((st = gf_workspace(c)) != ORBX_OK) return st;
-  const GfLayout L = gf_layout(1, width, height, 0);
-  uint8_t* ws = (uint8_t*)c->gf_ws.p;
-  HIPCHK(c, hipMemsetAsync(ws + L.cnt, 0, 2 * sizeof(uint32_t), c->stream));
-  HIPCHK(c, orbx_launch_gftt_response(c->stream, (const uint8_t*)c->gf_img.p, 1, width, height, width,
-                                      (size_t)width * height, (float*)(ws + L.map), (uint32_t*)(ws + L.cnt)));
-  HIPCHK(c, hipMemcpyAsync(eig, ws + L.map, sizeof(float) * (size_t)width * height, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ORBX_OK;
-}
-
-int orbx_good_features_to_track(orbx_ctx* c, const uint8_t* image, int width, int height, int stride, int max_corners,
-                                double quality_level, double min_distance, float* corners_xy, int capacity,
-                                int* count) {
-  DeviceGuard _dg(c);
-  int st = check_image(c, image, width, height, stride);
-  if (st != ORBX_OK) return st;
-  if (!count || capacity < 0 || (capacity > 0 && !corners_xy))
-    return fail(c, ORBX_ERR_INVALID_ARG, "count / corners_xy is NULL or capacity < 0");
-  if ((st = gf_check_params(c, quality_level, min_distance)) != ORBX_OK) return st;
-  if ((st = gf_upload(c, image, width, height, stride)) != ORBX_OK) return st;
-  const GfArgs a = gf_args(width, height, max_corners, quality_level, min_distance);
-  if ((st = gf_run(c, (const uint8_t*)c->gf_img.p, 1, width, height, width, (size_t)width * height, a, c->stream)) !=
-      ORBX_OK)
-    return st;
-  int32_t found = 0;
-  HIPCHK(c, hipMemcpyAsync(&found, c->gf_res.p, sizeof(found), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (found > capacity) {
-    *count = found;
-    return fail(c, ORBX_ERR_CAPACITY, "corners_xy is too small");
-  }
-  if (found > 0)
-    HIPCHK(c, hipMemcpy(corners_xy, (const uint8_t*)c->gf_res.p + align_up_sz(sizeof(int32_t), 256),
-                        sizeof(float) * 2 * (size_t)found, hipMemcpyDeviceToHost));
-  *count = found;
-  return ORBX_OK;
-}
-
-int orbx_good_features_batch_device(orbx_ctx* c, const void* d_frames, int n, int width, int height, int row_stride,
-                                    size_t frame_stride, int max_corners, double quality_level, double min_distance,
-                                    void* stream) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!d_frames) return fail(c, ORBX_ERR_INVALID_ARG, "d_frames is NULL");
-  if (n < 1 || n > c->p.max_batch) return fail(c, ORBX_ERR_INVALID_ARG, "n outside [1, max_batch]");
-  if (width < 8 || height < 8 || width > c->p.max_width || height > c->p.max_height)
-    return fail(c, ORBX_ERR_INVALID_ARG, "image size outside [8, max_width] x [8, max_height]");
-  if (row_stride < width) return fail(c, ORBX_ERR_INVALID_ARG, "row_stride < width");
-  if (frame_stride < (size_t)row_stride * (size_t)(height - 1) + (size_t)width)
-    return fail(c, ORBX_ERR_INVALID_ARG, "frame_stride smaller than a frame");
-  // the kernel addresses the bytes of one frame with 32-bit offsets (a buffer descriptor per frame)
-  if ((unsigned long long)row_stride * (unsigned long long)(height - 1) + (unsigned long long)width > 0x7fffffffull)
-    return fail(c, ORBX_ERR_INVALID_ARG, "row_stride * (height - 1) + width exceeds 2^31 - 1");
-  if (max_corners < 1) return fail(c, ORBX_ERR_INVALID_ARG, "max_corners < 1");
-  const int st = gf_check_params(c, quality_level, min_distance);
-  if (st != ORBX_OK) return st;
-  return gf_run(c, (const uint8_t*)d_frames, n, width, height, row_stride, frame_stride,
-                gf_args(width, height, max_corners, quality_level, min_distance),
-                stream ? (hipStream_t)stream : c->stream);
-}
-
-int orbx_good_features_workspace_limit(orbx_ctx* c, size_t bytes) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  const int st = gf_wait(c);
-  if (st != ORBX_OK) return st;
-  if (c->gf_ws.p) {
-    HIPCHK(c, hipFree(c->gf_ws.p));
-    c->gf_ws = DevBuf{};
-  }
-  c->gf_ws_limit = bytes ? bytes : ORBX_GFTT_WORKSPACE_DEFAULT;
-  return ORBX_OK;
-}
-
-int orbx_good_features_results_device(orbx_ctx* c, orbx_good_features_view* v) {
-  DeviceGuard _dg(c);
-  if (!c || !v) return ORBX_ERR_INVALID_ARG;
-  if (c->gf_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no good-features batch has run");
-  v->counts = (const int32_t*)c->gf_res.p;
-  v->corners_xy = (const float*)((const uint8_t*)c->gf_res.p + align_up_sz(sizeof(int32_t) * (size_t)c->gf_n, 256));
-  v->slot_capacity = c->gf_cap;
-  v->n = c->gf_n;
-  return ORBX_OK;
-}
-
-int orbx_good_features_fetch(orbx_ctx* c, int first, int n, int32_t* counts, float* corners_xy) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  if (c->gf_n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no good-features batch has run");
-  if (!counts || first < 0 || n < 1 || first >= c->gf_n || n > c->gf_n - first)
-    return fail(c, ORBX_ERR_INVALID_ARG, "counts is NULL or [first, first + n) outside the batch");
-  const int st = gf_wait(c);
-  if (st != ORBX_OK) return st;
-  const uint8_t* res = (const uint8_t*)c->gf_res.p;
-  HIPCHK(c, hipMemcpy(counts, res + sizeof(int32_t) * (size_t)first, sizeof(int32_t) * (size_t)n,
-                      hipMemcpyDeviceToHost));
-  if (corners_xy) {
-    const size_t row = sizeof(float) * 2 * (size_t)c->gf_cap;
-    HIPCHK(c, hipMemcpy(corners_xy, res + align_up_sz(sizeof(int32_t) * (size_t)c->gf_n, 256) + row * first, row * n,
-                        hipMemcpyDeviceToHost));
-  }
   return ORBX_OK;
 }
 

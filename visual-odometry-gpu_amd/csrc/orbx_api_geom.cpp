@@ -1,0 +1,414 @@
+// orbx_api_geom.cpp -- host layer of liborbx.so (orbx_host.h): relative pose, triangulation / scale / trajectory
+// chaining, and bundle adjustment.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "orbx_host.h"
+#include "orbx_tri_math.h"
+
+using namespace orbx_host;
+
+// ---- relative pose (next row) ---------------------------
+
+namespace {
+bool pose_args_ok(const double* K, double prob, double threshold, int max_iters) {
+  return K && K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) &&
+         std::isfinite(K[5]) && std::isfinite(prob) && std::isfinite(threshold) && threshold >= 0 && max_iters >= 0;
+}
+void pose_unpack(const OrbxPoseOut& r, double* E, double* R, double* t, int32_t* inliers, int32_t* good,
+                 int32_t* iters) {
+  if (E) memcpy(E, r.E, sizeof r.E);
+  if (R) memcpy(R, r.R, sizeof r.R);
+  if (t) memcpy(t, r.t, sizeof r.t);
+  if (inliers) *inliers = r.inliers;
+  if (good) *good = r.good;
+  if (iters) *iters = r.iters;
+}
+}  // namespace
+
+extern "C" {
+
+int orbx_estimate_pose(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, int n, const double* K, double prob,
+                       double threshold, int max_iters, uint64_t seed, double* E, double* R, double* t, uint8_t* mask,
+                       int32_t* inliers, int32_t* good, int32_t* iters) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (n < 0 || (n > 0 && (!pts1_xy || !pts2_xy)) || !E || !R || !t || !inliers || !good || !iters ||
+      !pose_args_ok(K, prob, threshold, max_iters))
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
+  const int cap = n > 0 ? n : 1;
+  ENSURE(c, c->pose.ph_in, sizeof(float) * 4 * (size_t)cap);
+  ENSURE(c, c->pose.ph_pts, sizeof(OrbxPosePt) * (size_t)cap);
+  ENSURE(c, c->pose.ph_n, sizeof(int32_t));
+  ENSURE(c, c->pose.ph_out, sizeof(OrbxPoseOut));
+  ENSURE(c, c->pose.ph_mask, (size_t)cap);
+  hipStream_t s = c->stream;
+  float* d_p1 = (float*)c->pose.ph_in.p;
+  float* d_p2 = d_p1 + 2 * (size_t)cap;
+  if (n > 0) {
+    HIPCHK(c, hipMemcpyAsync(d_p1, pts1_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_p2, pts2_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(c, orbx_launch_pose_prep_host(s, n, d_p1, d_p2, K, (OrbxPosePt*)c->pose.ph_pts.p, (int32_t*)c->pose.ph_n.p));
+  HIPCHK(c, orbx_launch_pose_ransac(s, 1, cap, (const OrbxPosePt*)c->pose.ph_pts.p, (const int32_t*)c->pose.ph_n.p, K, prob,
+                                    threshold, max_iters, seed, (OrbxPoseOut*)c->pose.ph_out.p, (uint8_t*)c->pose.ph_mask.p));
+  OrbxPoseOut r;
+  HIPCHK(c, hipMemcpyAsync(&r, c->pose.ph_out.p, sizeof r, hipMemcpyDeviceToHost, s));
+  if (mask && n > 0) HIPCHK(c, hipMemcpyAsync(mask, c->pose.ph_mask.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  pose_unpack(r, E, R, t, inliers, good, iters);
+  return ORBX_OK;
+}
+
+int orbx_batch_pose_consecutive(orbx_ctx* c, const double* K, double prob, double threshold, int max_iters,
+                                uint64_t seed) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!pose_args_ok(K, prob, threshold, max_iters)) return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
+  if (c->m.pairs <= 0 || c->m.serial != c->batch_serial)
+    return fail(c, ORBX_ERR_INVALID_ARG, "the last batch has not been matched (orbx_batch_match_consecutive)");
+  // the pose buffers are ONE set per context, like the matcher's
+  if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
+  const Block& B = last_block(c);
+  const int npairs = c->m.pairs, cap = B.cap;
+  const size_t e = (size_t)npairs * cap;
+  ENSURE(c, c->pose.pb_pts, sizeof(OrbxPosePt) * e);
+  ENSURE(c, c->pose.pb_n, sizeof(int32_t) * (size_t)npairs);
+  ENSURE(c, c->pose.pb_out, sizeof(OrbxPoseOut) * (size_t)npairs);
+  ENSURE(c, c->pose.pb_mask, e);
+  const OutLayout& o = B.layout;
+  hipStream_t s = batch_stream(c);
+  HIPCHK(c, orbx_launch_pose_prep_batch(s, npairs, cap, (const int32_t*)(B.d + o.counts),
+                                        (const orbx_keypoint*)(B.d + o.kp), (const int32_t*)c->m.match.p, K,
+                                        (OrbxPosePt*)c->pose.pb_pts.p, (int32_t*)c->pose.pb_n.p));
+  HIPCHK(c, orbx_launch_pose_ransac(s, npairs, cap, (const OrbxPosePt*)c->pose.pb_pts.p, (const int32_t*)c->pose.pb_n.p, K, prob,
+                                    threshold, max_iters, seed, (OrbxPoseOut*)c->pose.pb_out.p, (uint8_t*)c->pose.pb_mask.p));
+  c->pose.pairs = npairs;
+  c->pose.cap = cap;
+  c->pose.stream = s;
+  c->pose.serial = c->batch_serial;
+  c->pose.match_gen = c->m.gen;
+  return ORBX_OK;
+}
+
+int orbx_batch_pose_fetch(orbx_ctx* c, int first, int n, double* E, double* R, double* t, int32_t* inliers,
+                          int32_t* good, int32_t* iters) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (c->pose.pairs <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been posed");
+  if (first < 0 || n < 0 || first + n > c->pose.pairs)
+    return fail(c, ORBX_ERR_INVALID_ARG, "pairs outside the last posed batch");
+  if (n == 0) return ORBX_OK;
+  std::vector<OrbxPoseOut> r((size_t)n);
+  HIPCHK(c, hipMemcpyAsync(r.data(), (const OrbxPoseOut*)c->pose.pb_out.p + first, sizeof(OrbxPoseOut) * (size_t)n,
+                           hipMemcpyDeviceToHost, c->pose.stream));
+  HIPCHK(c, hipStreamSynchronize(c->pose.stream));
+  for (int i = 0; i < n; i++)
+    pose_unpack(r[(size_t)i], E ? E + 9 * i : nullptr, R ? R + 9 * i : nullptr, t ? t + 3 * i : nullptr,
+                inliers ? inliers + i : nullptr, good ? good + i : nullptr, iters ? iters + i : nullptr);
+  return ORBX_OK;
+}
+
+int orbx_batch_pose_mask(orbx_ctx* c, int pair, uint8_t* mask, int capacity, int* count) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!count || capacity < 0 || (capacity > 0 && !mask)) return fail(c, ORBX_ERR_INVALID_ARG, "bad mask arguments");
+  if (pair < 0 || pair >= c->pose.pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last posed batch");
+  int32_t np = 0;
+  HIPCHK(c, hipMemcpyAsync(&np, (const int32_t*)c->pose.pb_n.p + pair, sizeof np, hipMemcpyDeviceToHost, c->pose.stream));
+  HIPCHK(c, hipStreamSynchronize(c->pose.stream));
+  *count = np;
+  if (np > capacity) return fail(c, ORBX_ERR_CAPACITY, "capacity smaller than the pair's match count");
+  if (np > 0) {
+    HIPCHK(c, hipMemcpyAsync(mask, (const uint8_t*)c->pose.pb_mask.p + (size_t)pair * c->pose.cap, (size_t)np,
+                             hipMemcpyDeviceToHost, c->pose.stream));
+    HIPCHK(c, hipStreamSynchronize(c->pose.stream));
+  }
+  return ORBX_OK;
+}
+
+}  // extern "C"
+
+// ---- triangulation, relative scale, trajectory chaining ------------
+
+extern "C" {
+
+int orbx_triangulate(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, int n, const double* K, const double* R,
+                     const double* t, float* xyz, uint8_t* valid) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (n < 0 || (n > 0 && (!pts1_xy || !pts2_xy || !xyz || !valid)) || !K || !R || !t || !finite_all(K, 9) ||
+      !finite_all(R, 9) || !finite_all(t, 3))
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad triangulation arguments");
+  if (n == 0) return ORBX_OK;
+  ENSURE(c, c->scale.sh_in, sizeof(float) * 4 * (size_t)n);
+  ENSURE(c, c->scale.sh_xyz, sizeof(float) * 3 * (size_t)n);
+  ENSURE(c, c->scale.sh_valid, (size_t)n);
+  hipStream_t s = c->stream;
+  float* d_p1 = (float*)c->scale.sh_in.p;
+  float* d_p2 = d_p1 + 2 * (size_t)n;
+  HIPCHK(c, hipMemcpyAsync(d_p1, pts1_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d_p2, pts2_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, orbx_launch_triangulate_host(s, n, d_p1, d_p2, K, R, t, (float*)c->scale.sh_xyz.p, (uint8_t*)c->scale.sh_valid.p));
+  HIPCHK(c, hipMemcpyAsync(xyz, c->scale.sh_xyz.p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(valid, c->scale.sh_valid.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return ORBX_OK;
+}
+
+int orbx_estimate_scale(orbx_ctx* c, const float* prev_xyz, const uint8_t* prev_valid, int n_prev, const float* cur_xyz,
+                        const uint8_t* cur_valid, int n_cur, double* scale, int32_t* ratios_used) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (n_prev < 0 || n_cur < 0 || (n_prev > 0 && !prev_xyz) || (n_cur > 0 && !cur_xyz) || !scale || !ratios_used)
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad scale arguments");
+  const int m = std::min(n_prev, n_cur);
+  if (m == 0) {  // src/feature_matching.cpp:248-249
+    *scale = 1.0;
+    *ratios_used = 0;
+    return ORBX_OK;
+  }
+  if ((size_t)m * 8 > ORBX_SCALE_LDS_MAX)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "more aligned points than the selection holds in LDS");
+  // only the first m points of either list enter
+  ENSURE(c, c->scale.sh_xyz, sizeof(float) * 6 * (size_t)m);
+  ENSURE(c, c->scale.sh_valid, 2 * (size_t)m);
+  ENSURE(c, c->scale.sh_out, sizeof(OrbxScaleOut));
+  hipStream_t s = c->stream;
+  float* d_prev = (float*)c->scale.sh_xyz.p;
+  float* d_cur = d_prev + 3 * (size_t)m;
+  uint8_t* d_pv = (uint8_t*)c->scale.sh_valid.p;
+  uint8_t* d_cv = d_pv + m;
+  HIPCHK(c, hipMemcpyAsync(d_prev, prev_xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d_cur, cur_xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
+  if (prev_valid) HIPCHK(c, hipMemcpyAsync(d_pv, prev_valid, (size_t)m, hipMemcpyHostToDevice, s));
+  if (cur_valid) HIPCHK(c, hipMemcpyAsync(d_cv, cur_valid, (size_t)m, hipMemcpyHostToDevice, s));
+  HIPCHK(c, orbx_launch_scale_aligned(s, m, m, d_prev, prev_valid ? d_pv : nullptr, d_cur, cur_valid ? d_cv : nullptr,
+                                      (OrbxScaleOut*)c->scale.sh_out.p));
+  OrbxScaleOut r;
+  HIPCHK(c, hipMemcpyAsync(&r, c->scale.sh_out.p, sizeof r, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  *scale = r.scale;
+  *ratios_used = r.ratios_used;
+  return ORBX_OK;
+}
+
+int orbx_batch_scale_consecutive(orbx_ctx* c, const double* K) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!K || !finite_all(K, 9)) return fail(c, ORBX_ERR_INVALID_ARG, "bad scale arguments");
+  if (c->pose.pairs <= 0 || c->pose.serial != c->batch_serial)
+    return fail(c, ORBX_ERR_INVALID_ARG, "the last batch has not been posed (orbx_batch_pose_consecutive)");
+  // the triangulation reads the match table again: it must still hold the matches the poses were computed from
+  // (a host-array matcher call reuses the scratch and zeroes m.pairs; a second batch match bumps m.gen)
+  if (c->m.pairs != c->pose.pairs || c->m.serial != c->batch_serial || c->pose.match_gen != c->m.gen)
+    return fail(c, ORBX_ERR_INVALID_ARG, "the match table has been rewritten since the batch was posed");
+  const int npairs = c->pose.pairs, cap = c->pose.cap;
+  if ((size_t)cap * 16 > ORBX_SCALE_LDS_MAX)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "more result slots per frame than the join holds in LDS");
+  // the scale buffers are ONE set per context, like the pose buffers
+  if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
+  const size_t e = (size_t)npairs * cap;
+  ENSURE(c, c->scale.sb_xyz, sizeof(float) * 3 * e);
+  ENSURE(c, c->scale.sb_valid, e);
+  ENSURE(c, c->scale.sb_mq, sizeof(int32_t) * e);
+  ENSURE(c, c->scale.sb_mt, sizeof(int32_t) * e);
+  ENSURE(c, c->scale.sb_n, sizeof(int32_t) * (size_t)npairs);
+  ENSURE(c, c->scale.sb_out, sizeof(OrbxScaleOut) * (size_t)npairs);
+  const Block& B = last_block(c);
+  const OutLayout& o = B.layout;
+  hipStream_t s = c->pose.stream;
+  HIPCHK(c, orbx_launch_triangulate_batch(s, npairs, cap, (const int32_t*)(B.d + o.counts),
+                                          (const orbx_keypoint*)(B.d + o.kp), (const int32_t*)c->m.match.p,
+                                          (const OrbxPoseOut*)c->pose.pb_out.p, K, (float*)c->scale.sb_xyz.p,
+                                          (uint8_t*)c->scale.sb_valid.p, (int32_t*)c->scale.sb_mq.p, (int32_t*)c->scale.sb_mt.p,
+                                          (int32_t*)c->scale.sb_n.p));
+  HIPCHK(c, orbx_launch_scale_join(s, npairs, cap, (const int32_t*)c->scale.sb_n.p, (const int32_t*)c->scale.sb_mq.p,
+                                   (const int32_t*)c->scale.sb_mt.p, (const float*)c->scale.sb_xyz.p,
+                                   (const uint8_t*)c->scale.sb_valid.p, (const OrbxPoseOut*)c->pose.pb_out.p,
+                                   (OrbxScaleOut*)c->scale.sb_out.p));
+  c->scale.pairs = npairs;
+  c->scale.cap = cap;
+  c->scale.stream = s;
+  return ORBX_OK;
+}
+
+int orbx_batch_scale_fetch(orbx_ctx* c, int first, int n, double* scale, int32_t* triplets, int32_t* ratios_used) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (c->scale.pairs <= 0) return fail(c, ORBX_ERR_INVALID_ARG, "no batch has been scaled");
+  if (first < 0 || n < 0 || first + n > c->scale.pairs)
+    return fail(c, ORBX_ERR_INVALID_ARG, "pairs outside the last scaled batch");
+  if (n == 0) return ORBX_OK;
+  std::vector<OrbxScaleOut> r((size_t)n);
+  HIPCHK(c, hipMemcpyAsync(r.data(), (const OrbxScaleOut*)c->scale.sb_out.p + first, sizeof(OrbxScaleOut) * (size_t)n,
+                           hipMemcpyDeviceToHost, c->scale.stream));
+  HIPCHK(c, hipStreamSynchronize(c->scale.stream));
+  for (int i = 0; i < n; i++) {
+    if (scale) scale[i] = r[(size_t)i].scale;
+    if (triplets) triplets[i] = r[(size_t)i].triplets;
+    if (ratios_used) ratios_used[i] = r[(size_t)i].ratios_used;
+  }
+  return ORBX_OK;
+}
+
+int orbx_batch_points_fetch(orbx_ctx* c, int pair, float* xyz, uint8_t* valid, int capacity, int* count) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!count || capacity < 0 || (capacity > 0 && (!xyz || !valid)))
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad point output arguments");
+  if (pair < 0 || pair >= c->scale.pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last scaled batch");
+  hipStream_t s = c->scale.stream;
+  int32_t np = 0;
+  HIPCHK(c, hipMemcpyAsync(&np, (const int32_t*)c->scale.sb_n.p + pair, sizeof np, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  *count = np;
+  if (np > capacity) return fail(c, ORBX_ERR_CAPACITY, "capacity smaller than the pair's match count");
+  if (np > 0) {
+    const size_t row = (size_t)pair * c->scale.cap;
+    HIPCHK(c, hipMemcpyAsync(xyz, (const float*)c->scale.sb_xyz.p + 3 * row, sizeof(float) * 3 * (size_t)np,
+                             hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(valid, (const uint8_t*)c->scale.sb_valid.p + row, (size_t)np, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  return ORBX_OK;
+}
+
+int orbx_chain_trajectory(const double* T0, const double* R, const double* t, const double* scale, int n,
+                          double* poses) {
+  if (!T0 || !poses || n < 0 || (n > 0 && (!R || !t || !scale))) return ORBX_ERR_INVALID_ARG;
+  std::memcpy(poses, T0, sizeof(double) * 16);
+  for (int i = 0; i < n; i++) tri_chain(poses + 16 * i, R + 9 * i, t + 3 * i, scale[i], poses + 16 * (i + 1));
+  return ORBX_OK;
+}
+
+}  // extern "C"
+
+// ---- bundle adjustment -----------------------------------------------
+
+static_assert(sizeof(orbx_ba_summary) == 32, "orbx_ba_summary is the kernel's BaSummary");
+
+extern "C" {
+
+int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const int32_t* pose_offset, double* poses6,
+                             const int32_t* point_offset, double* points3, const int32_t* obs_offset,
+                             const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
+                             double huber_delta, int max_iters, orbx_ba_summary* summaries) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!K || !finite_all(K, 9) || n_windows < 0 || !(huber_delta > 0.0) || !std::isfinite(huber_delta) ||
+      max_iters < 1 || max_iters > 1000)
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  if (n_windows == 0) return ORBX_OK;
+  if (!pose_offset || !poses6 || !point_offset || !points3 || !obs_offset || !obs_point || !obs_pose || !obs_xy ||
+      !summaries)
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  if (pose_offset[0] != 0 || point_offset[0] != 0 || obs_offset[0] != 0)
+    return fail(c, ORBX_ERR_INVALID_ARG, "offset arrays start at 0");
+  int cap = 1, ocap = 1;
+  for (int w = 0; w < n_windows; w++) {
+    const long long W = (long long)pose_offset[w + 1] - pose_offset[w], N = (long long)point_offset[w + 1] - point_offset[w],
+                    M = (long long)obs_offset[w + 1] - obs_offset[w];
+    if (W < 2 || W > ORBX_BA_MAX_POSES) return fail(c, ORBX_ERR_INVALID_ARG, "a window has 2 .. 8 poses");
+    if (N < 1 || M < N || M > N * W)
+      return fail(c, ORBX_ERR_INVALID_ARG, "every landmark has 1 .. n_poses observations");
+    if (N > ORBX_BA_MAX_POINTS) return fail(c, ORBX_ERR_UNSUPPORTED, "more landmarks in a window than 65536");
+    cap = std::max(cap, (int)N);
+    ocap = std::max(ocap, (int)M);
+  }
+  const size_t tp = (size_t)pose_offset[n_windows], tn = (size_t)point_offset[n_windows], tm = (size_t)obs_offset[n_windows];
+  if (tn + (size_t)n_windows > 0x7fffffffu || tm > 0x7fffffffu)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "more landmarks or observations in a batch than 32-bit offsets hold");
+  if (!finite_all(poses6, (int)(6 * tp))) return fail(c, ORBX_ERR_INVALID_ARG, "a pose is not finite");
+  for (size_t i = 0; i < 3 * tn; i++)
+    if (!std::isfinite(points3[i])) return fail(c, ORBX_ERR_INVALID_ARG, "a point is not finite");
+  for (size_t i = 0; i < 2 * tm; i++)
+    if (!std::isfinite(obs_xy[i])) return fail(c, ORBX_ERR_INVALID_ARG, "an observation is not finite");
+  // CSR by (landmark, pose), per window (src/with_bundle_adjustment.cpp:651-666 adds the residual blocks landmark by
+  // landmark)
+  std::vector<int32_t> rows(tn + (size_t)n_windows), order;
+  std::vector<uint8_t> opose(tm);
+  std::vector<double> oxy(2 * tm);
+  for (int w = 0; w < n_windows; w++) {
+    const int W = pose_offset[w + 1] - pose_offset[w], N = point_offset[w + 1] - point_offset[w];
+    const int M = obs_offset[w + 1] - obs_offset[w];
+    const int32_t* op = obs_point + obs_offset[w];
+    const int32_t* oq = obs_pose + obs_offset[w];
+    for (int k = 0; k < M; k++)
+      if (op[k] < 0 || op[k] >= N || oq[k] < 0 || oq[k] >= W)
+        return fail(c, ORBX_ERR_INVALID_ARG, "an observation's landmark or pose index is out of range");
+    // every (landmark, pose) occurs at most once, so placing observation k at key landmark * W + pose and reading
+    // the keys in ascending order IS the stable sort by (landmark, pose)
+    order.assign((size_t)N * W, -1);
+    for (int k = 0; k < M; k++) {
+      int32_t& at = order[(size_t)op[k] * W + oq[k]];
+      if (at >= 0) return fail(c, ORBX_ERR_INVALID_ARG, "a landmark is observed twice by one pose");
+      at = k;
+    }
+    int32_t* row = rows.data() + point_offset[w] + w;
+    std::fill(row, row + N + 1, 0);
+    size_t dst = (size_t)obs_offset[w];
+    for (size_t key = 0; key < order.size(); key++) {
+      const int o = order[key];
+      if (o < 0) continue;
+      row[op[o] + 1]++;
+      opose[dst] = (uint8_t)oq[o];
+      oxy[2 * dst] = obs_xy[2 * ((size_t)obs_offset[w] + o)];
+      oxy[2 * dst + 1] = obs_xy[2 * ((size_t)obs_offset[w] + o) + 1];
+      dst++;
+    }
+    for (int j = 0; j < N; j++) {
+      if (row[j + 1] == 0) return fail(c, ORBX_ERR_INVALID_ARG, "a landmark has no observation");
+      row[j + 1] += row[j];
+    }
+  }
+  // workgroups: as many as windows, bounded by ORBX_BA_MAX_GROUPS and by the workspace budget
+  const size_t per_group = sizeof(double) * ((size_t)ORBX_BA_WS_POINT * cap + (size_t)ORBX_BA_WS_OBS * ocap) + 8 * (size_t)cap;
+  int groups = std::min(n_windows, ORBX_BA_MAX_GROUPS);
+  groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)groups, ORBX_BA_WS_BUDGET / per_group));
+  const size_t noff = (size_t)n_windows + 1;
+  ENSURE(c, c->ba.off, sizeof(int32_t) * 3 * noff);
+  ENSURE(c, c->ba.poses, sizeof(double) * 6 * tp);
+  ENSURE(c, c->ba.points, sizeof(double) * 3 * tn);
+  ENSURE(c, c->ba.rows, sizeof(int32_t) * rows.size());
+  ENSURE(c, c->ba.opose, tm);
+  ENSURE(c, c->ba.oxy, sizeof(double) * 2 * tm);
+  ENSURE(c, c->ba.wp, sizeof(double) * ORBX_BA_WS_POINT * (size_t)cap * groups);
+  ENSURE(c, c->ba.wo, sizeof(double) * ORBX_BA_WS_OBS * (size_t)ocap * groups);
+  ENSURE(c, c->ba.slot, 8 * (size_t)cap * groups);
+  ENSURE(c, c->ba.out, sizeof(orbx_ba_summary) * (size_t)n_windows);
+  hipStream_t s = c->stream;
+  int32_t* d_off = (int32_t*)c->ba.off.p;
+  HIPCHK(c, hipMemcpyAsync(d_off, pose_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d_off + noff, point_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d_off + 2 * noff, obs_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba.poses.p, poses6, sizeof(double) * 6 * tp, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba.points.p, points3, sizeof(double) * 3 * tn, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba.rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba.opose.p, opose.data(), tm, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->ba.oxy.p, oxy.data(), sizeof(double) * 2 * tm, hipMemcpyHostToDevice, s));
+  const double K4[4] = {K[0], K[4], K[2], K[5]};
+  HIPCHK(c, orbx_launch_ba(s, n_windows, groups, max_iters, K4, huber_delta, d_off, d_off + noff, d_off + 2 * noff,
+                           (double*)c->ba.poses.p, (double*)c->ba.points.p, (const int32_t*)c->ba.rows.p,
+                           (const uint8_t*)c->ba.opose.p, (const double*)c->ba.oxy.p, cap, ocap, (double*)c->ba.wp.p,
+                           (double*)c->ba.wo.p, (unsigned long long*)c->ba.slot.p, c->ba.out.p));
+  // the staged vectors are pageable: their copies above have left the host before the calls returned
+  HIPCHK(c, hipMemcpyAsync(poses6, c->ba.poses.p, sizeof(double) * 6 * tp, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(points3, c->ba.points.p, sizeof(double) * 3 * tn, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(summaries, c->ba.out.p, sizeof(orbx_ba_summary) * (size_t)n_windows, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return ORBX_OK;
+}
+
+int orbx_bundle_adjust(orbx_ctx* c, const double* K, int n_poses, double* poses6, int n_points, double* points3,
+                       int n_obs, const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
+                       double huber_delta, int max_iters, orbx_ba_summary* summary) {
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (n_poses < 0 || n_points < 0 || n_obs < 0) return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  const int32_t po[2] = {0, n_poses}, pt[2] = {0, n_points}, ob[2] = {0, n_obs};
+  return orbx_bundle_adjust_batch(c, K, 1, po, poses6, pt, points3, ob, obs_point, obs_pose, obs_xy, huber_delta,
+                                  max_iters, summary);
+}
+
+}  // extern "C"

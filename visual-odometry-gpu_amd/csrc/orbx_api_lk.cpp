@@ -1,0 +1,402 @@
+// orbx_api_lk.cpp -- host layer of liborbx.so (orbx_host.h): pyramidal Lucas-Kanade tracking, per pair of host
+// images and over windows of device-resident frames.
+#include <algorithm>
+#include <cstring>
+
+#include "orbx_host.h"
+
+using namespace orbx_host;
+
+// ---- pyramidal Lucas-Kanade tracking (src/feature_tracking.cpp:166-193) ------------------
+
+namespace {
+struct LkGeom {
+  int top = 0;
+  int w[ORBX_LK_MAX_LEVELS], h[ORBX_LK_MAX_LEVELS], pitch[ORBX_LK_MAX_LEVELS];
+  size_t img_off[ORBX_LK_MAX_LEVELS], der_off[ORBX_LK_MAX_LEVELS];
+  size_t img_bytes = 0, der_bytes = 0;
+};
+// buildOpticalFlowPyramid: halve ((w+1)/2) until a level would not be larger than the window
+LkGeom lk_geometry(int w, int h, int win, int max_level) {
+  LkGeom g;
+  for (int l = 0; l <= max_level; l++) {
+    const int lw = l == 0 ? w : (g.w[l - 1] + 1) / 2, lh = l == 0 ? h : (g.h[l - 1] + 1) / 2;
+    if (l > 0 && (lw <= win || lh <= win)) break;
+    g.w[l] = lw;
+    g.h[l] = lh;
+    g.pitch[l] = lw;  // tight: a host image with stride == width goes up in ONE contiguous copy
+    g.img_off[l] = g.img_bytes;
+    g.img_bytes += align_up_sz((size_t)g.pitch[l] * lh, 256);
+    g.der_off[l] = g.der_bytes;
+    g.der_bytes += align_up_sz((size_t)lw * lh * 4, 256);
+    g.top = l;
+  }
+  return g;
+}
+OrbxLkPyr lk_pyr(const LkGeom& g, const uint8_t* img, const uint8_t* deriv) {
+  OrbxLkPyr P;
+  std::memset(&P, 0, sizeof(P));
+  P.top = g.top;
+  for (int l = 0; l <= g.top; l++) {
+    P.L[l].img = img + g.img_off[l];
+    P.L[l].deriv = deriv ? reinterpret_cast<const int16_t*>(deriv + g.der_off[l]) : nullptr;
+    P.L[l].w = g.w[l];
+    P.L[l].h = g.h[l];
+    P.L[l].pitch = g.pitch[l];
+  }
+  return P;
+}
+// host image -> level 0, then pyrDown level by level
+int lk_upload(orbx_ctx* c, const LkGeom& g, DevBuf& b, const uint8_t* img, int stride) {
+  ENSURE(c, b, g.img_bytes + 256);
+  uint8_t* base = (uint8_t*)b.p;
+  if (stride == g.w[0])
+    HIPCHK(c, hipMemcpyAsync(base, img, (size_t)g.w[0] * g.h[0], hipMemcpyHostToDevice, c->stream));
+  else  // (row-by-row in the runtime: slow, but only for padded host images)
+    HIPCHK(c, hipMemcpy2DAsync(base, g.pitch[0], img, stride, g.w[0], g.h[0], hipMemcpyHostToDevice, c->stream));
+  for (int l = 1; l <= g.top; l++)
+    HIPCHK(c, orbx_launch_lk_pyrdown(c->stream, base + g.img_off[l - 1], g.w[l - 1], g.h[l - 1], g.pitch[l - 1],
+                                     base + g.img_off[l], g.w[l], g.h[l], g.pitch[l]));
+  return ORBX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int orbx_lk_track(orbx_ctx* c, const uint8_t* prev, int prev_stride, const uint8_t* next, int next_stride, int width,
+                  int height, const float* prev_pts_xy, int n, float* next_pts_xy, uint8_t* status, float* err,
+                  int win_size, int max_level, int max_iters, double epsilon) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!next || n < 0 || (n > 0 && (!prev_pts_xy || !next_pts_xy || !status)))
+    return fail(c, ORBX_ERR_INVALID_ARG, "next image / point arrays are NULL");
+  if (width < 1 || height < 1 || next_stride < width || (prev && prev_stride < width))
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad image size or stride");
+  if (win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
+    return fail(c, ORBX_ERR_INVALID_ARG, "win_size must be in [3, 31], max_level in [0, 7]");
+  // TermCriteria sanitising of calcOpticalFlowPyrLK
+  max_iters = std::min(std::max(max_iters, 0), 100);
+  epsilon = std::min(std::max(epsilon, 0.0), 10.0);
+  const LkGeom g = lk_geometry(width, height, win_size, max_level);
+  int st;
+  int ip;  // buffer holding the `prev` pyramid
+  if (prev) {
+    ip = c->lk.last == 0 ? 1 : 0;
+    if ((st = lk_upload(c, g, c->lk.img[ip], prev, prev_stride)) != ORBX_OK) return st;
+  } else {
+    // the previous call's `next` image is this call's `prev` (img1 = img2.clone(), feature_tracking.cpp:112)
+    if (c->lk.last < 0 || c->lk.w != width || c->lk.h != height || c->lk.top != g.top || c->lk.win != win_size)
+      return fail(c, ORBX_ERR_INVALID_ARG, "prev == NULL needs a previous orbx_lk_track call of the same geometry");
+    ip = c->lk.last;
+  }
+  const int in = 1 - ip;
+  c->lk.last = -1;  // invalid until this call has succeeded
+  if ((st = lk_upload(c, g, c->lk.img[in], next, next_stride)) != ORBX_OK) return st;
+  ENSURE(c, c->lk.deriv, g.der_bytes + 256);
+  const uint8_t* pimg = (const uint8_t*)c->lk.img[ip].p;
+  for (int l = 0; l <= g.top; l++)
+    HIPCHK(c, orbx_launch_lk_scharr(c->stream, pimg + g.img_off[l], g.w[l], g.h[l], g.pitch[l],
+                                    reinterpret_cast<int16_t*>((uint8_t*)c->lk.deriv.p + g.der_off[l])));
+  uint8_t* hio = nullptr;
+  const size_t o_out = sizeof(float) * 2 * (size_t)n, o_err = 2 * o_out, o_st = o_err + sizeof(float) * (size_t)n;
+  const size_t io_bytes = o_st + (size_t)n;
+  if (n > 0) {
+    ENSURE(c, c->lk.io, io_bytes);
+    if (c->lk.host_bytes < io_bytes) {  // pinned staging: small pageable copies cost ~15 us each
+      if (c->lk.host) (void)hipHostFree(c->lk.host);
+      c->lk.host = nullptr;
+      c->lk.host_bytes = 0;
+      HIPCHK(c, hipHostMalloc(&c->lk.host, align_up_sz(io_bytes, 4096), hipHostMallocDefault));
+      c->lk.host_bytes = align_up_sz(io_bytes, 4096);
+    }
+    hio = (uint8_t*)c->lk.host;
+    uint8_t* dio = (uint8_t*)c->lk.io.p;
+    std::memcpy(hio, prev_pts_xy, o_out);
+    HIPCHK(c, hipMemcpyAsync(dio, hio, o_out, hipMemcpyHostToDevice, c->stream));
+    const OrbxLkPyr P = lk_pyr(g, pimg, (const uint8_t*)c->lk.deriv.p);
+    const OrbxLkPyr N = lk_pyr(g, (const uint8_t*)c->lk.img[in].p, nullptr);
+    HIPCHK(c, orbx_launch_lk_track(c->stream, P, N, n, (const float*)dio, (float*)(dio + o_out), dio + o_st,
+                                   (float*)(dio + o_err), win_size, max_iters, epsilon * epsilon));
+    HIPCHK(c, hipMemcpyAsync(hio + o_out, dio + o_out, io_bytes - o_out, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n > 0) {
+    std::memcpy(next_pts_xy, hio + o_out, o_out);
+    std::memcpy(status, hio + o_st, (size_t)n);
+    if (err) std::memcpy(err, hio + o_err, sizeof(float) * (size_t)n);
+  }
+  c->lk.w = width;
+  c->lk.h = height;
+  c->lk.top = g.top;
+  c->lk.win = win_size;
+  c->lk.last = in;
+  return ORBX_OK;
+}
+
+int orbx_lk_pyramid_levels(int width, int height, int win_size, int max_level) {
+  if (width < 1 || height < 1 || win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
+    return -1;
+  return lk_geometry(width, height, win_size, max_level).top + 1;
+}
+
+}  // extern "C"
+
+// ---- Lucas-Kanade over frame windows ---------------------------------------------------------
+// trackPointsAcrossWindow (src/with_bundle_adjustment.cpp:464-499) for many windows per launch; with windows of two
+// frames, track_optical_flow (src/feature_tracking.cpp:166-193) over a stream.
+
+namespace {
+
+// the workspace of ONE frame: the pyramid levels above 0 (level 0 is read in place), then the derivative maps of
+// every level
+struct LkwLayout {
+  LkGeom g;
+  size_t img_bytes, frame_bytes;  // levels 1 .. top; img_bytes + derivative maps
+};
+LkwLayout lkw_layout(int w, int h, int win, int max_level) {
+  LkwLayout o;
+  o.g = lk_geometry(w, h, win, max_level);
+  o.img_bytes = o.g.top >= 1 ? o.g.img_bytes - o.g.img_off[1] : 0;
+  o.frame_bytes = o.img_bytes + o.g.der_bytes;
+  return o;
+}
+
+// a buffer of the windows path of at least `bytes`: the new allocation is made BEFORE the old one is released, so
+// that a failed call keeps what it had
+int lkw_grow(orbx_ctx* c, DevBuf& b, size_t bytes) {
+  if (b.p && b.bytes >= bytes) return ORBX_OK;
+  const int st = c->lkw.side.wait(c);  // (the old allocation may still be read or written)
+  if (st != ORBX_OK) return st;
+  bytes = align_up_sz(std::max<size_t>(bytes, 256), 256);
+  void* p = nullptr;
+  HIPCHK(c, hipMalloc(&p, bytes));
+  if (b.p) (void)hipFree(b.p);
+  b.p = p;
+  b.bytes = bytes;
+  return ORBX_OK;
+}
+
+struct LkwResult {
+  size_t o_seen, o_err, bytes;  // tracks at 0
+};
+LkwResult lkw_result(int n_windows, int cap, int len) {
+  LkwResult r;
+  const size_t slots = (size_t)n_windows * cap;
+  r.o_seen = align_up_sz(sizeof(float) * 2 * slots * len, 256);
+  r.o_err = align_up_sz(r.o_seen + sizeof(int32_t) * slots, 256);
+  r.bytes = r.o_err + sizeof(float) * slots * (len - 1);
+  return r;
+}
+
+FramesWhat lkw_frames_what(int max_frames) {
+  return {"frames is NULL", "n_frames outside [2, " + std::to_string(max_frames) + "]"};
+}
+
+int lkw_check_params(orbx_ctx* c, int win_size, int max_level, int* max_iters, double* epsilon) {
+  if (win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
+    return fail(c, ORBX_ERR_INVALID_ARG, "win_size must be in [3, 31], max_level in [0, 7]");
+  if (!(*epsilon == *epsilon)) return fail(c, ORBX_ERR_INVALID_ARG, "epsilon is NaN");
+  // TermCriteria sanitising of calcOpticalFlowPyrLK, as orbx_lk_track
+  *max_iters = std::min(std::max(*max_iters, 0), 100);
+  *epsilon = std::min(std::max(*epsilon, 0.0), 10.0);
+  return ORBX_OK;
+}
+
+// enqueues the pyramids and the tracking of every window on s; arguments are checked
+int lkw_run(orbx_ctx* c, const uint8_t* d_frames, int n_frames, int w, int h, int row_stride, size_t frame_stride,
+            const int32_t* window_first, int n_windows, int window_len, const float* d_points,
+            const int32_t* d_counts, int cap, int win, int max_level, int max_iters, double epsilon, hipStream_t s) {
+  int st = c->lkw.side.enter(c, s);
+  if (st != ORBX_OK) return st;
+  const SideWork::Mark mark{c->lkw.side, s};
+  // points and counts may be the good-features block, written on another stream
+  if (c->gf.side.ev && c->gf.side.stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->gf.side.ev, 0));
+  const LkwLayout L = lkw_layout(w, h, win, max_level);
+  // frames per slice: what the limit holds, at least one window, at most the batch
+  const size_t fit =
+      std::min<size_t>(std::max<size_t>(c->lkw.ws_limit / L.frame_bytes, (size_t)window_len), (size_t)n_frames);
+  const LkwResult R = lkw_result(n_windows, cap, window_len);
+  if ((st = lkw_grow(c, c->lkw.ws, fit * L.frame_bytes + 256)) != ORBX_OK) return st;
+  if ((st = lkw_grow(c, c->lkw.first, sizeof(int32_t) * (size_t)n_windows)) != ORBX_OK) return st;
+  const void* old_res = c->lkw.res.p;
+  if ((st = lkw_grow(c, c->lkw.res, R.bytes)) != ORBX_OK) return st;
+  if (c->lkw.res.p != old_res) c->lkw.n = 0;  // (a larger block: the previous result went with the old one)
+  // The window table goes up through a pinned mirror (a copy from pageable memory would make the host wait for the
+  // stream).  The mirror is reused: the previous call's copy has to have read it.
+  const size_t table = sizeof(int32_t) * (size_t)n_windows;
+  if (!c->lkw.first_ev) HIPCHK(c, hipEventCreateWithFlags(&c->lkw.first_ev, hipEventDisableTiming));
+  HIPCHK(c, hipEventSynchronize(c->lkw.first_ev));
+  if (c->lkw.first_host_bytes < table) {
+    if (c->lkw.first_host) (void)hipHostFree(c->lkw.first_host);
+    c->lkw.first_host = nullptr;
+    c->lkw.first_host_bytes = 0;
+    HIPCHK(c, hipHostMalloc(&c->lkw.first_host, align_up_sz(table, 4096), hipHostMallocDefault));
+    c->lkw.first_host_bytes = align_up_sz(table, 4096);
+  }
+  // from here on the previous result is being replaced
+  c->lkw.n = 0;
+  std::memcpy(c->lkw.first_host, window_first, table);
+  HIPCHK(c, hipMemcpyAsync(c->lkw.first.p, c->lkw.first_host, table, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(c->lkw.first_ev, s));
+  uint8_t* ws = (uint8_t*)c->lkw.ws.p;
+  uint8_t* res = (uint8_t*)c->lkw.res.p;
+  const LkGeom& g = L.g;
+  const size_t img_base = g.top >= 1 ? g.img_off[1] : 0;  // workspace offsets count from level 1
+  const size_t slot_stride = (size_t)cap;
+  // slices of whole consecutive windows whose frames [lo, hi) fit the workspace
+  for (int w0 = 0; w0 < n_windows;) {
+    int lo = window_first[w0], hi = lo + window_len, w1 = w0 + 1;
+    while (w1 < n_windows && w1 - w0 < 65535) {
+      const int nlo = std::min(lo, window_first[w1]), nhi = std::max(hi, window_first[w1] + window_len);
+      if ((size_t)(nhi - nlo) > fit) break;
+      lo = nlo;
+      hi = nhi;
+      w1++;
+    }
+    const int m = hi - lo;
+    uint8_t* ws_img = ws;                                // [m][levels 1 .. top]
+    uint8_t* ws_der = ws + align_up_sz(L.img_bytes * m, 256);  // [m][levels 0 .. top]
+    const uint8_t* f_lo = d_frames + frame_stride * (size_t)lo;
+    for (int l = 1; l <= g.top; l++) {
+      const uint8_t* src = l == 1 ? f_lo : ws_img + (g.img_off[l - 1] - img_base);
+      HIPCHK(c, orbx_launch_lk_pyrdown_frames(s, m, src, g.w[l - 1], g.h[l - 1], l == 1 ? row_stride : g.pitch[l - 1],
+                                              l == 1 ? frame_stride : L.img_bytes, ws_img + (g.img_off[l] - img_base),
+                                              g.w[l], g.h[l], g.pitch[l], L.img_bytes));
+    }
+    for (int l = 0; l <= g.top; l++)
+      HIPCHK(c, orbx_launch_lk_scharr_frames(s, m, l == 0 ? f_lo : ws_img + (g.img_off[l] - img_base), g.w[l], g.h[l],
+                                             l == 0 ? row_stride : g.pitch[l], l == 0 ? frame_stride : L.img_bytes,
+                                             reinterpret_cast<int16_t*>(ws_der + g.der_off[l]), g.der_bytes));
+    OrbxLkFrames F;
+    std::memset(&F, 0, sizeof(F));
+    F.top = g.top;
+    F.first = lo;
+    F.frame_stride = frame_stride;
+    F.img_stride = L.img_bytes;
+    F.der_stride = g.der_bytes / sizeof(int16_t);
+    for (int l = 0; l <= g.top; l++) {
+      F.L[l].img = l == 0 ? d_frames : ws_img + (g.img_off[l] - img_base);
+      F.L[l].deriv = reinterpret_cast<const int16_t*>(ws_der + g.der_off[l]);
+      F.L[l].w = g.w[l];
+      F.L[l].h = g.h[l];
+      F.L[l].pitch = l == 0 ? row_stride : g.pitch[l];
+    }
+    HIPCHK(c, orbx_launch_lk_track_windows(
+                  s, F, (const int32_t*)c->lkw.first.p + w0, w1 - w0, window_len, d_points + 2 * slot_stride * w0,
+                  d_counts ? d_counts + w0 : nullptr, cap, (float*)res + 2 * slot_stride * window_len * w0,
+                  (int32_t*)(res + R.o_seen) + slot_stride * w0,
+                  (float*)(res + R.o_err) + slot_stride * (window_len - 1) * w0, win, max_iters, epsilon * epsilon));
+    w0 = w1;
+  }
+  c->lkw.n = n_windows;
+  c->lkw.cap = cap;
+  c->lkw.len = window_len;
+  return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_lk_track_windows_device(orbx_ctx* c, const void* d_frames, int n_frames, int width, int height,
+                                 int row_stride, size_t frame_stride, const int32_t* window_first, int n_windows,
+                                 int window_len, const float* d_points_xy, const int32_t* d_counts, int slot_capacity,
+                                 int win_size, int max_level, int max_iters, double epsilon, void* stream) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  int st = check_device_frames(c, d_frames, n_frames, 2, c->p.max_batch, width, height, row_stride, frame_stride,
+                               lkw_frames_what(c->p.max_batch));
+  if (st != ORBX_OK) return st;
+  if ((st = lkw_check_params(c, win_size, max_level, &max_iters, &epsilon)) != ORBX_OK) return st;
+  if (!window_first || !d_points_xy) return fail(c, ORBX_ERR_INVALID_ARG, "window_first / d_points_xy is NULL");
+  if (n_windows < 1 || window_len < 2 || slot_capacity < 1)
+    return fail(c, ORBX_ERR_INVALID_ARG, "n_windows < 1, window_len < 2 or slot_capacity < 1");
+  for (int i = 0; i < n_windows; i++)
+    if (window_first[i] < 0 || window_first[i] > n_frames - window_len)
+      return fail(c, ORBX_ERR_INVALID_ARG, "a window does not lie inside the frames");
+  return lkw_run(c, (const uint8_t*)d_frames, n_frames, width, height, row_stride, frame_stride, window_first,
+                 n_windows, window_len, d_points_xy, d_counts, slot_capacity, win_size, max_level, max_iters, epsilon,
+                 stream ? (hipStream_t)stream : c->stream);
+}
+
+int orbx_lk_workspace_limit(orbx_ctx* c, size_t bytes) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  return set_workspace_limit(c, c->lkw.side, c->lkw.ws, &c->lkw.ws_limit, bytes, ORBX_LK_WORKSPACE_DEFAULT);
+}
+
+int orbx_lk_windows_results_device(orbx_ctx* c, orbx_lk_windows_view* v) {
+  DeviceGuard _dg(c);
+  if (!c || !v) return ORBX_ERR_INVALID_ARG;
+  if (c->lkw.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
+  const LkwResult R = lkw_result(c->lkw.n, c->lkw.cap, c->lkw.len);
+  const uint8_t* res = (const uint8_t*)c->lkw.res.p;
+  v->tracks_xy = (const float*)res;
+  v->seen = (const int32_t*)(res + R.o_seen);
+  v->err = (const float*)(res + R.o_err);
+  v->slot_capacity = c->lkw.cap;
+  v->window_len = c->lkw.len;
+  v->n_windows = c->lkw.n;
+  return ORBX_OK;
+}
+
+int orbx_lk_windows_fetch(orbx_ctx* c, int first, int n, float* tracks_xy, int32_t* seen, float* err) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (c->lkw.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
+  if (first < 0 || n < 1 || first >= c->lkw.n || n > c->lkw.n - first)
+    return fail(c, ORBX_ERR_INVALID_ARG, "[first, first + n) outside the batch");
+  const int st = c->lkw.side.wait(c);
+  if (st != ORBX_OK) return st;
+  const LkwResult R = lkw_result(c->lkw.n, c->lkw.cap, c->lkw.len);
+  const uint8_t* res = (const uint8_t*)c->lkw.res.p;
+  const size_t slots = (size_t)c->lkw.cap, len = (size_t)c->lkw.len;
+  if (tracks_xy)
+    HIPCHK(c, hipMemcpy(tracks_xy, res + sizeof(float) * 2 * slots * len * first, sizeof(float) * 2 * slots * len * n,
+                        hipMemcpyDeviceToHost));
+  if (seen)
+    HIPCHK(c, hipMemcpy(seen, res + R.o_seen + sizeof(int32_t) * slots * first, sizeof(int32_t) * slots * n,
+                        hipMemcpyDeviceToHost));
+  if (err)
+    HIPCHK(c, hipMemcpy(err, res + R.o_err + sizeof(float) * slots * (len - 1) * first,
+                        sizeof(float) * slots * (len - 1) * n, hipMemcpyDeviceToHost));
+  return ORBX_OK;
+}
+
+int orbx_lk_track_window(orbx_ctx* c, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
+                         size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen, float* err,
+                         int win_size, int max_level, int max_iters, double epsilon) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  // (the host entry stages into a buffer of its own; 65535: blockIdx.z)
+  int st = check_device_frames(c, frames, n_frames, 2, 65535, width, height, row_stride, frame_stride,
+                               lkw_frames_what(65535));
+  if (st != ORBX_OK) return st;
+  if ((st = lkw_check_params(c, win_size, max_level, &max_iters, &epsilon)) != ORBX_OK) return st;
+  if (n < 0 || (n > 0 && (!pts_xy || !tracks_xy || !seen)))
+    return fail(c, ORBX_ERR_INVALID_ARG, "n < 0 or pts_xy / tracks_xy / seen is NULL");
+  if (n == 0) return ORBX_OK;  // no points: nothing to track, the last result stays
+  if ((st = c->lkw.side.enter(c, c->stream)) != ORBX_OK) return st;
+  const size_t tight = (size_t)width * height;
+  {
+    const SideWork::Mark mark{c->lkw.side, c->stream};
+    if ((st = lkw_grow(c, c->lkw.img, tight * n_frames)) != ORBX_OK) return st;
+    if ((st = lkw_grow(c, c->lkw.pts, sizeof(float) * 2 * (size_t)n)) != ORBX_OK) return st;
+    if (row_stride == width && frame_stride == tight) {
+      HIPCHK(c, hipMemcpyAsync(c->lkw.img.p, frames, tight * n_frames, hipMemcpyHostToDevice, c->stream));
+    } else {
+      for (int i = 0; i < n_frames; i++)
+        HIPCHK(c, hipMemcpy2DAsync((uint8_t*)c->lkw.img.p + tight * i, width, frames + frame_stride * i, row_stride,
+                                   width, height, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->lkw.pts.p, pts_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  }
+  const int32_t first = 0;
+  if ((st = lkw_run(c, (const uint8_t*)c->lkw.img.p, n_frames, width, height, width, tight, &first, 1, n_frames,
+                    (const float*)c->lkw.pts.p, nullptr, n, win_size, max_level, max_iters, epsilon, c->stream)) !=
+      ORBX_OK)
+    return st;
+  return orbx_lk_windows_fetch(c, 0, 1, tracks_xy, seen, err);
+}
+
+}  // extern "C"

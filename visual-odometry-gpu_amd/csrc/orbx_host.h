@@ -1,0 +1,412 @@
+// orbx_host.h -- what every part of the C-ABI host layer (orbx_api*.cpp) shares: the context and the records it is
+// made of, the error and device guards, and the helpers that more than one of those files calls (defined once, in
+// orbx_api.cpp).  Host only: included by no .hip file, and not part of the public interface.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "orbx_internal.h"
+
+namespace orbx_host {
+
+using namespace orbx_geom;  // orbx_plan.h: the geometry of a frame size and the tables built from it
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+// what a subsystem's release() does with the buffers it owns (nothing may still be using them)
+inline void free_bufs(std::initializer_list<DevBuf*> bufs) {
+  for (DevBuf* b : bufs)
+    if (b->p) (void)hipFree(b->p);
+}
+
+// result block of a batch: one device allocation + one pinned host mirror so
+// a whole batch comes back with a single D2H copy
+// sections: counts | kp16 | angle | desc || kp | lkp | resp | level -- what the reference's own output consists of
+// (keypoints, orientations, descriptors: include/orb.hpp:37) first, so that orbx_batch_prefetch_compact moves one
+// contiguous prefix of `compact` bytes
+struct OutLayout {
+  size_t counts, kp16, kp, lkp, angle, resp, level, desc, compact, total;
+};
+
+inline OutLayout make_out_layout(int n, int cap) {
+  OutLayout o;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    size_t r = off;
+    off = align_up_sz(off + bytes, 256);
+    return r;
+  };
+  const size_t e = (size_t)n * (size_t)cap;
+  // the compact record first (orbx_batch_prefetch_compact copies [0, compact)): 40 bytes per slot
+  o.counts = take(sizeof(int32_t) * (size_t)n);
+  o.kp16 = take(sizeof(uint32_t) * e);
+  o.angle = take(sizeof(float) * e);
+  o.desc = take(sizeof(orbx_descriptor) * e);
+  o.compact = off;
+  o.kp = take(sizeof(orbx_keypoint) * e);
+  o.lkp = take(sizeof(orbx_keypoint) * e);
+  o.resp = take(sizeof(float) * e);
+  o.level = take(sizeof(int32_t) * e);
+  o.total = off;
+  return o;
+}
+
+// One block of the ring of result blocks (orbx_ctx::blocks): the device allocation, its pinned host mirror and
+// what the batch that last wrote it left there.
+struct Block {
+  uint8_t* d = nullptr;
+  uint8_t* h = nullptr;      // pinned mirror
+  uint8_t* h_dev = nullptr;  // the device-visible address of the pinned mirror
+  OutLayout layout{};
+  int n = 0;                  // frames in the block (0: never written)
+  int cap = 1;                // slots per frame the block was written with
+  bool copy_pending = false;  // an asynchronous D2H of the block has been enqueued (ev_copied)
+  bool copy_compact = false;  // ... of its compact prefix only (orbx_batch_prefetch_compact)
+  bool host_written = false;  // orbx_set_host_results: the describe kernel wrote the compact record to the mirror
+  hipEvent_t ev_done = nullptr, ev_copied = nullptr;
+  hipStream_t stream = nullptr;  // the stream of the batch that last wrote the block
+};
+
+// One lane of the pipelined mode: a set of working pools (pyramids, mask, statistics, candidates; sized for
+// max_batch frames of max_width x max_height), the stream its batches run on, and the event / stream of the
+// pools' last user.
+struct Lane {
+  uint8_t *d_pyr = nullptr, *d_pyr_blur = nullptr;
+  unsigned long long *d_mask = nullptr, *d_row_stat = nullptr;
+  orbx_keypoint* d_cand = nullptr;
+  int32_t *d_cand_count = nullptr, *d_cand_total = nullptr;
+  float* d_resp = nullptr;
+  uint32_t* d_lcand = nullptr;  // spread selection: packed candidates, their responses, counts
+  float* d_lresp = nullptr;
+  int32_t* d_lcount = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_pool = nullptr;
+  hipStream_t pool_stream = nullptr;
+};
+
+// a per-workgroup tile descriptor table (see OrbxTileDesc) of the current plan, in a pool sized for the largest frame
+struct TileTable {
+  OrbxTileDesc* d = nullptr;
+  int count = 0;
+  size_t capacity = 0;
+};
+enum {
+  T_FAST,  // one frame, band-major
+  T_BLUR,
+  T_PYR2,
+  T_PYRBLUR,  // fused pyramid + blur strips
+  // the same strips cut into short row bands: few frames per call (the reference's one-frame call shape)
+  // fill the chip only with many short waves, where a large batch wants few tall ones
+  T_PYRBLUR_SMALL,
+  // top-rows-first pipeline: the strips of the first pass and of the second one
+  T_PYRBLUR_TOP,
+  T_PYRBLUR_REST,
+  kTileTables
+};
+
+// the events of one timed batched call
+// (slots ORBX_NUM_STAGE_TIMES + 1, + 2: the boundaries inside the top-rows-first pipeline)
+struct TimingSet {
+  hipEvent_t ev[ORBX_NUM_STAGE_TIMES + 3] = {};
+  int mode = 0;
+  bool split = false;  // the call ran the top-rows-first pipeline
+};
+
+int fail(orbx_ctx* c, int status, const std::string& msg);  // (c == NULL: the thread's creation error)
+
+#define HIPCHK(c, expr)                                                                              \
+  do {                                                                                               \
+    hipError_t _e = (expr);                                                                          \
+    if (_e != hipSuccess)                                                                            \
+      return fail((c), ORBX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));             \
+  } while (0)
+
+// Work that runs beside the batched path on ANY caller's stream, with one workspace and one result block per context
+// (good features, LK windows).  `stream` is the stream the last call ran on, kept for COMPARISON only (a caller's
+// stream may be gone by the next call); `ev` is recorded behind that call's work: what later calls, fetches and
+// orbx_destroy wait for.
+struct SideWork {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev = nullptr;
+  // waits for the work enqueued so far, on whatever stream it ran: through the event recorded behind it, never
+  // through the stream itself (a caller's stream need not outlive its batch's end)
+  int wait(orbx_ctx* c);
+  // a call on stream s: earlier work on another stream has to be done (one workspace, one result block)
+  int enter(orbx_ctx* c, hipStream_t s);
+  // records the event behind whatever a call has enqueued on s, on every way out of the call
+  struct Mark {
+    SideWork& w;
+    hipStream_t s;
+    ~Mark() {
+      if (w.ev) (void)hipEventRecord(w.ev, s);
+    }
+  };
+  // the last wait, and the end of the event (orbx_destroy, before the owner's buffers are freed)
+  void release() {
+    if (!ev) return;
+    (void)hipEventSynchronize(ev);
+    (void)hipEventDestroy(ev);
+  }
+};
+
+// ---- the context's parts, one per subsystem (orbx_ctx::s, m, lk, lkw, pose, scale, ba, gf) ----
+
+// stage-API scratch (grown on demand; never touched by the batched path)
+struct StageScratch {
+  DevBuf img_a, img_b, f32, u16, mask, kps, f32b, desc, i32, kern;
+  DevBuf tiles;  // stage-API tables
+  void release() { free_bufs({&img_a, &img_b, &f32, &u16, &mask, &kps, &f32b, &desc, &i32, &kern, &tiles}); }
+};
+
+struct Matcher {
+  DevBuf q, t, idx, dist, match, cnt;  // matcher (stage API and batch)
+  int pairs = 0;
+  long long serial = -1;  // the batch serial (orbx_ctx::batch_serial) the last batch match was made on
+  // bumped by every batch match: the pose step records the one it read (Pose::match_gen), so the scale step, which
+  // reads m.match again, can tell that the matches are still the ones the poses were computed from
+  long long gen = 0;
+  void release() { free_bufs({&q, &t, &idx, &dist, &match, &cnt}); }
+};
+
+// Lucas-Kanade tracker: two image pyramids (ping-pong: the `next` of one call is the
+// `prev` of the following one), the derivative pyramid of the current `prev`, point buffers
+struct LkPair {
+  DevBuf img[2], deriv, io;  // io: prev points | next points | err | status, one block
+  void* host = nullptr;      // pinned mirror of io (one H2D + one D2H per call)
+  size_t host_bytes = 0;
+  int w = 0, h = 0, top = -1, win = 0, last = -1;  // last: buffer holding the last `next`
+  void release() {
+    if (host) (void)hipHostFree(host);
+    free_bufs({&img[0], &img[1], &deriv, &io});
+  }
+};
+
+// Lucas-Kanade over frame windows (k_lk_track_windows): the workspace of one slice of frames (pyramid levels above
+// 0 | derivative maps), bounded by ws_limit; the window table; the staged frames and points of the one-window
+// host entry; and the entry's OWN result block (tracks | seen | err).  Nothing here is shared with orbx_lk_track.
+struct LkWindows {
+  DevBuf ws, first, img, pts, res;
+  size_t ws_limit = ORBX_LK_WORKSPACE_DEFAULT;
+  int n = 0, cap = 0, len = 0;  // windows, slots per window, frames per window of the last call (0: none)
+  SideWork side;                // the event is recorded behind every windows call
+  void* first_host = nullptr;   // pinned mirror of the window table, and the event behind its upload
+  size_t first_host_bytes = 0;
+  hipEvent_t first_ev = nullptr;
+  void release() {
+    side.release();
+    if (first_ev) (void)hipEventDestroy(first_ev);
+    if (first_host) (void)hipHostFree(first_host);
+    free_bufs({&ws, &first, &img, &pts, &res});
+  }
+};
+
+// relative pose (orbx_pose.hip): batched results (pb_*) and the host-array entry's own buffers (ph_*)
+struct Pose {
+  DevBuf pb_pts, pb_n, pb_out, pb_mask, ph_in, ph_pts, ph_n, ph_out, ph_mask;
+  int pairs = 0, cap = 0;
+  hipStream_t stream = nullptr;
+  long long serial = -1;     // the batch serial the last batch pose ran on
+  long long match_gen = -1;  // the Matcher::gen it read
+  void release() { free_bufs({&pb_pts, &pb_n, &pb_out, &pb_mask, &ph_in, &ph_pts, &ph_n, &ph_out, &ph_mask}); }
+};
+
+// triangulation and scale (orbx_scale.hip): batched results (sb_*: points, valid bytes, compact match lists,
+// match counts, scales) and the host-array entries' own buffers (sh_*)
+struct Scale {
+  DevBuf sb_xyz, sb_valid, sb_mq, sb_mt, sb_n, sb_out, sh_in, sh_xyz, sh_valid, sh_out;
+  int pairs = 0, cap = 0;
+  hipStream_t stream = nullptr;
+  void release() {
+    free_bufs({&sb_xyz, &sb_valid, &sb_mq, &sb_mt, &sb_n, &sb_out, &sh_in, &sh_xyz, &sh_valid, &sh_out});
+  }
+};
+
+// bundle adjustment (orbx_ba.hip): the staged windows (offsets, parameter blocks, CSR observations), the
+// workgroups' workspaces and the summaries; grown on first use
+struct BundleAdjust {
+  DevBuf off, poses, points, rows, opose, oxy, wp, wo, slot, out;
+  void release() { free_bufs({&off, &poses, &points, &rows, &opose, &oxy, &wp, &wo, &slot, &out}); }
+};
+
+// Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames (response maps | key pools | cell grids
+// | per-frame maximum and candidate count), allocated on first use and bounded by ws_limit; the staged host
+// image of the one-frame entries; and the entry's OWN result block (counts | corners), untouched by the ORB path
+struct GoodFeatures {
+  DevBuf ws, img, res;
+  size_t ws_limit = ORBX_GFTT_WORKSPACE_DEFAULT;
+  int n = 0, cap = 0;  // frames and slots per frame of the last good-features batch (n == 0: none)
+  SideWork side;
+  void release() {
+    side.release();
+    free_bufs({&ws, &img, &res});
+  }
+};
+
+}  // namespace orbx_host
+
+// what a captured launch sequence depends on (run_batch)
+struct OrbxGraphKey {
+  const uint8_t* d_frames;
+  size_t frame_stride;
+  int n, w, h, row_stride, early, plan_serial, block;  // early: switches (early exit, fusion, two passes)
+  bool operator==(const OrbxGraphKey& o) const {
+    return d_frames == o.d_frames && frame_stride == o.frame_stride && n == o.n && w == o.w && h == o.h &&
+           row_stride == o.row_stride && early == o.early && plan_serial == o.plan_serial && block == o.block;
+  }
+};
+
+struct orbx_ctx {
+  orbx_params p{};
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+
+  // geometry for the current frame size, and for the largest size (capacity)
+  OrbxPlan plan{};
+  OrbxPlan plan_max{};
+  OrbxTileMap tm_blur{};  // 5x5 /273 variant (LDS tile kernel)
+  OrbxBandMap bm_fast{};
+  orbx_host::TileTable tiles[orbx_host::kTileTables];
+  OrbxTopLevels top_levels{};  // the levels the second pass may skip
+  std::vector<OrbxResizeTap> h_taps;
+  int plan_w = 0, plan_h = 0;
+
+  uint8_t* d_in = nullptr;  // staged host frames, tight pitch (max_batch frames of max_width x max_height)
+  // captured launch sequences of the most recent batch shapes (run_batch), round-robin replacement
+  static constexpr int kGraphs = 16;  // (input, result block, lane) triples: 8 resident inputs over 4 blocks x 2 lanes
+  hipGraphExec_t g_exec[kGraphs] = {};
+  OrbxGraphKey g_key[kGraphs] = {};
+  int g_next = 0;
+  int plan_serial = 0;  // bumped whenever set_plan rebuilds the plan / tables
+  OrbxResizeTap* d_taps = nullptr;
+  size_t taps_capacity = 0;
+  float* d_gauss = nullptr;
+  // Result blocks.  A ring of kBlocks, used in turn by consecutive batches, each with a pinned host
+  // mirror: the D2H copy of batch i (orbx_batch_prefetch, on its own copy stream) overlaps the
+  // kernels of batch i+1, which write the other block.  blocks[blk] is the block of the most recent batch.
+  // (a ring of kBlocks blocks: with two, the copy of batch i -- about as long as a step at 256 frames per batch --
+  // had to finish before batch i + 2 could start; with four it overlaps two following batches)
+  static constexpr int kBlocks = 4;
+  orbx_host::Block blocks[kBlocks];
+  int blk = 0;
+  int host_results = 0;  // orbx_set_host_results: the describe kernel writes the compact record to the mirror
+  int next_lane = 1;  // pipelined mode: the lane of the next batch (alternates)
+  hipStream_t cstream = nullptr;
+  // Pipelined batches (orbx_set_pipelined_batches): two LANES, each with its own stream and its own working pools;
+  // consecutive device-resident batches alternate between them -- batch k uses lane k & 1 = its result block --
+  // so the kernels of one batch overlap the tails and the nearly empty launches of the other.  lanes[0] has the
+  // pools every context has, and its stream is the context's own; lanes[lane] is the lane of the most recent batch.
+  // Stream order is the only ordering inside a lane.  A batch that comes to a lane's pools, or to a result block,
+  // on ANOTHER stream than their previous user (a caller's stream, the other lane) first makes its stream wait for
+  // that user's event: Lane::ev_pool / pool_stream for the pools of a lane, Block::ev_done / stream for a block.
+  orbx_host::Lane lanes[2];
+  int lane = 0;
+  bool pipelined = false;
+  bool last_two_pass = false;  // the last batch built its pyramid top rows first (enqueue_batch)
+  hipStream_t last_stream = nullptr;
+
+  long long batch_serial = 0;  // bumped by every batch run
+  // The subsystems beside the batched path, each with what it owns.  They meet in three places, visible where the
+  // calls are made: pose reads the matcher's table, scale checks pose.match_gen against m.gen, and the windows
+  // tracker waits for the good-features event.
+  orbx_host::StageScratch s;
+  orbx_host::Matcher m;
+  orbx_host::LkPair lk;
+  orbx_host::LkWindows lkw;
+  orbx_host::Pose pose;
+  orbx_host::Scale scale;
+  orbx_host::BundleAdjust ba;
+  orbx_host::GoodFeatures gf;
+
+  int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
+  int fast_early = 1;
+  int blur_impl = 2;  // ORBX_BLUR_IMPL, read at creation (launch_blur_auto)
+  int fast_impl = 4;  // 4: streaming kernel (orbx_fast4.hip, the default), 3: LDS tile kernel (orbx_fast.hip); ORBX_FAST_IMPL, read at creation
+  int fuse = 1;  // pyramid + blur in one kernel when blur runs on every level (orbx_set_fused_pyramid_blur)
+  // Top-rows-first pipeline (enqueue_batch): 0 never, 1 whenever eligible, 2 adaptive -- the second pass
+  // counts the (frame, level)s it skipped / had to produce (d_feedback, running totals, written to the pinned
+  // h_feedback by the last kernel of every two-pass batch and read WITHOUT waiting at the start of later ones); while
+  // fewer than a quarter are skipped the batches run in one pass, and every 128th one probes again.
+  int top_mode = 2;
+  bool top_on = true;          // the adaptive verdict
+  int top_single_batches = 0;  // one-pass batches since the verdict turned negative
+  uint32_t* d_feedback = nullptr;
+  volatile uint32_t* h_feedback = nullptr;
+  uint32_t feedback_seen[2] = {0, 0};
+  // adaptive first pass (adapt_tile_rows): rows each level needed to fill its cap -- maximum of the current and of
+  // the previous observation window --, the tile-row heights chosen from them (0: the default), bookkeeping
+  uint32_t need_cur[ORBX_MAX_LEVELS] = {}, need_prev[ORBX_MAX_LEVELS] = {};
+  int tile_h_pref[ORBX_MAX_LEVELS] = {};
+  int need_batches = 0, need_window = 2, retiles = 0, learn_w = 0, learn_h = 0;
+  bool prefs_applied = false;  // the current tile tables were built with tile_h_pref
+  // ring of event sets: one per timed batched call, so that several calls can be
+  // in flight before their stage times are read (no host sync between steps)
+  orbx_host::TimingSet evr[ORBX_EVENT_SETS];
+  long long ev_calls = 0;  // timed batched calls so far
+  hipEvent_t ev[2] = {};   // orbx_bench_stage
+};
+
+namespace orbx_host {
+
+// Every entry point that takes a context runs on the context's device, whatever the caller's
+// current device is (another context's, torch.cuda.set_device, ...), and leaves the caller's
+// current device as it found it.
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  explicit DeviceGuard(const orbx_ctx* c) {
+    if (!c) return;
+    enter(c->device);
+  }
+  explicit DeviceGuard(int dev) { enter(dev); }
+  void enter(int dev) {
+    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+// a buffer of at least `bytes`; one that grows first waits for the context's stream, both lanes and the last
+// batch's stream (the buffers of the work beside the batched path have waits of their own: SideWork)
+int ensure(orbx_ctx* c, DevBuf& b, size_t bytes);
+#define ENSURE(c, buf, bytes)                        \
+  do {                                               \
+    const int _st = ensure((c), (buf), (bytes));     \
+    if (_st != ORBX_OK) return _st;                  \
+  } while (0)
+
+// the stream the last batch ran on (the context's own before any batch)
+hipStream_t batch_stream(const orbx_ctx* c);
+// the lane and the result block of the most recent batch
+const Lane& cur_lane(const orbx_ctx* c);
+const Block& last_block(const orbx_ctx* c);
+// everything either lane has in flight has finished
+hipError_t lanes_sync(orbx_ctx* c);
+
+int check_image(orbx_ctx* c, const void* img, int w, int h, int stride);
+// An array of n frames on the device, n in [n_min, n_max]: pointer, count, size against the context's maximum,
+// strides, and the 2^31 - 1 bound of the kernels' 32-bit frame offsets (a buffer descriptor per frame).  `what`
+// carries the caller's words for its pointer and its count.
+struct FramesWhat {
+  const char* null_msg;
+  std::string range_msg;
+};
+int check_device_frames(orbx_ctx* c, const void* d_frames, int n, int n_min, int n_max, int w, int h, int row_stride,
+                        size_t frame_stride, const FramesWhat& what);
+bool finite_all(const double* v, int n);
+int gaussian_kernel(int K, float sigma, float* kernel);
+hipError_t launch_blur_auto(int impl, hipStream_t s, const OrbxPlan& P, const OrbxTileMap& tm1, const OrbxTileDesc* tiles2,
+                            int ntiles2, int n, const uint8_t* src, uint8_t* dst, int first_level, int kind);
+// behind both *_workspace_limit entries: the workspace's users have finished, it is released (the next call allocates
+// one within the new limit), and the limit becomes `bytes`, or `dflt` for 0
+int set_workspace_limit(orbx_ctx* c, SideWork& side, DevBuf& ws, size_t* limit, size_t bytes, size_t dflt);
+
+}  // namespace orbx_host

@@ -1,5 +1,5 @@
-// orbx_internal.h -- shared between the HIP kernels (orbx_kernels.hip) and the
-// C-ABI host layer (orbx_api.cpp).  Not part of the public interface.
+// orbx_internal.h -- shared between the HIP kernels (orbx_*.hip) and the
+// C-ABI host layer (orbx_api*.cpp, which share orbx_host.h among themselves).  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
