@@ -419,7 +419,13 @@ int orbx_lk_pyramid_levels(int width, int height, int win_size, int max_level);
  * Conventions: x2 = R x1 + t, |t| = 1; E has unit Frobenius norm.  Degenerate input (n < 5, no model, a
  * solver failure) returns ORBX_OK with inliers = good = 0, E = 0, R = I, t = 0 and an all-zero mask.
  * inliers: RANSAC inliers of E; good: those that triangulate in front of both cameras (the final mask);
- * iters: RANSAC iterations run.  The samples depend on (seed, iteration) only. */
+ * iters: RANSAC iterations run.  The samples depend on (seed, iteration) only.
+ * ORBX_ERR_INVALID_ARG (nothing is launched, no output is written): K NULL or with a non-finite fx, fy, cx or cy,
+ * fx <= 0 or fy <= 0, a non-finite prob (a finite one is clamped to [0, 1]), a threshold that is negative or not
+ * finite, max_iters outside [0, ORBX_POSE_MAX_ITERS], n < 0. */
+/* An interface limit, not a measurement: a pair in which no model ever gets more than four inliers runs all
+ * max_iters iterations inside one kernel launch. */
+#define ORBX_POSE_MAX_ITERS 100000
 /* get_pose on host arrays: pts*_xy are n float (x, y) pairs (matched keypoints or LK output); mask
  * (n bytes, may be NULL) receives recoverPose's final mask.  src/feature_matching.cpp:185-206,
  * src/feature_tracking.cpp:222-242 */

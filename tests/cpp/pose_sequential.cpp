@@ -4,7 +4,8 @@
 // points.  Only the per-sample arithmetic (solver, Sampson error, log, SVD,
 // triangulation, sample hash) comes from orbx_pose_math.h; the orchestration
 // below is written independently of the kernels, so the GPU test that compares
-// the two checks the kernels' chunked, parallel decomposition.
+// the two checks the kernels' chunked, parallel decomposition.  The shared arithmetic itself is pinned through the
+// one-line exports below by tests/test_pose_ref.py, against a numpy restatement that does not use the header.
 //
 // Built by tests/test_pose.py with
 //   g++ -O2 -std=c++17 -ffp-contract=off -fno-fast-math -shared -fPIC
@@ -20,6 +21,11 @@ extern "C" {
 double seq_log(double x) { return pose_log(x); }
 double seq_sqrt(double x) { return pose_sqrt(x); }
 int seq_update_niters(double p, double ep, int max_iters) { return pose_update_niters(p, ep, max_iters); }
+int seq_sample(uint64_t seed, uint32_t iter, uint32_t n, uint32_t* idx) { return pose_sample(seed, iter, n, idx); }
+float seq_sampson(const double* E, double x1, double y1, double x2, double y2) { return pose_sampson(E, x1, y1, x2, y2); }
+int seq_point_good(const double* R, const double* t, double sgn, double x1, double y1, double x2, double y2) {
+  return pose_point_good(R, t, sgn, x1, y1, x2, y2) ? 1 : 0;
+}
 
 // pts: x1[5], y1[5], x2[5], y2[5] (normalised); models: 10 x 9
 int seq_solve5(const double* pts, double* models) {

@@ -22,18 +22,35 @@ DP = C.POINTER(C.c_double)
 NFEAT = 3000
 
 
+# conftest.py is fixed, so this cannot be a session fixture there: tests/test_pose_ref.py imports the fixture below, and
+# this list keeps the second module from compiling the library again
+_SEQ = []
+
+
 @pytest.fixture(scope="module")
 def seq(tmp_path_factory):
-    """The sequential restatement, compiled here (test infrastructure; not part of build())."""
+    """The sequential restatement, compiled here (test infrastructure; not part of build()); once per session,
+    tests/test_pose_ref.py uses this fixture too."""
+    if _SEQ:
+        return _SEQ[0]
     out = tmp_path_factory.mktemp("pose_seq") / "pose_sequential.so"
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC",
                            "-o", str(out), os.path.join(ROOT, "tests", "cpp", "pose_sequential.cpp")])
     lib = C.CDLL(str(out))
     lib.seq_log.restype = C.c_double
     lib.seq_log.argtypes = [C.c_double]
+    lib.seq_sqrt.restype = C.c_double
+    lib.seq_sqrt.argtypes = [C.c_double]
+    lib.seq_update_niters.argtypes = [C.c_double, C.c_double, C.c_int]
+    lib.seq_sample.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.seq_sampson.restype = C.c_float
+    lib.seq_sampson.argtypes = [DP] + [C.c_double] * 4
+    lib.seq_point_good.argtypes = [DP, DP] + [C.c_double] * 5
+    lib.seq_decompose.argtypes = [DP] * 4
     lib.seq_solve5.argtypes = [DP, DP]
     lib.seq_estimate_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_int, DP, C.c_double, C.c_double, C.c_int,
                                       C.c_uint64] + [C.c_void_p] * 7
+    _SEQ.append(lib)
     return lib
 
 
@@ -237,17 +254,123 @@ def gpu_cases():
     return cases
 
 
+def case_inputs(cs):
+    p1, p2, *_ = scene(cs["seed"], max(cs["n"], 1), cs["outliers"], cs["noise"])
+    kw = dict(prob=cs["prob"], threshold=cs["threshold"], max_iters=cs["max_iters"], seed=cs["rseed"])
+    return p1[:cs["n"]], p2[:cs["n"]], kw
+
+
+# k_pose_ransac solves 32 iterations per chunk and strides the points by its 64 lanes: both boundaries from either side
+GRID_N = [5, 6, 9, 33, 63, 64, 65, 127, 128, 129, 500]
+GRID_ITERS = [0, 1, 31, 32, 33, 63, 64, 65, 1000]
+GRID_PROB = [0.999, 0.0, 1.0, 0.5]
+GRID_THRESHOLD = [1.0, 0.0, 3.0]
+GRID_SCENE = [(0.0, "sigma"), (0.0, "round"), (0.3, "sigma"), (0.3, "round"), (0.6, "sigma"), (0.6, "round")]
+GRID_CHUNK_EDGES = {31, 32, 33, 63, 64, 65}
+
+
+def grid_cases():
+    """60 cases; case s takes entry s of each cycle above, wrapping round.  The scenes' seeds start where the runs end
+    on every chunk edge (with the cycles locked as they are, only two cases can end at 32); callers assert that with
+    grid_hits_the_chunk_edges.  The same locking lets threshold 0 meet max_iters of 1, 33 and 65 only."""
+    return [dict(seed=900 + s, n=GRID_N[s % 11], max_iters=GRID_ITERS[s % 9], prob=GRID_PROB[s % 4],
+                 threshold=GRID_THRESHOLD[s % 3], outliers=GRID_SCENE[s % 6][0], noise=GRID_SCENE[s % 6][1],
+                 rseed=(s * 0x9E3779B97F4A7C15 + 1) % 2**64) for s in range(60)]
+
+
+def grid_hits_the_chunk_edges(iters, cases):
+    """The set of `iters` of the grid's reference results holds every chunk edge, and a stop inside the first chunk
+    that the stopping rule chose (not max_iters)."""
+    stopped = [i for i, cs in zip(iters, cases) if 2 <= i <= 30 and i < cs["max_iters"]]
+    return GRID_CHUNK_EDGES <= set(iters) and len(stopped) > 0
+
+
+# fx != fy and a principal point away from the image centre (the normalised threshold uses (fx + fy) / 2)
+K_ANISO = np.array([[707.0912, 0.0, 571.25], [0.0, 655.5, 204.75], [0.0, 0.0, 1.0]])
+
+
+def aniso_cases():
+    out = []
+    for s, n in enumerate([65, 300]):
+        p1, p2, *_ = scene(700 + s, n, 0.3, K=K_ANISO)
+        out.append((p1, p2, dict(prob=0.999, threshold=1.0, max_iters=1000, seed=s)))
+    return out
+
+
+def bad_point_cases():
+    """(p1, p2, indices of the bad points or None for all, kw): NaN, +inf and 3e38 in every seventh point of a
+    200-point scene, in either list and either coordinate; and a list of NaN only."""
+    p1, p2, *_ = scene(77, 200, 0.2)
+    q1, q2 = p1.copy(), p2.copy()
+    bad = np.arange(0, 200, 7)
+    for j, i in enumerate(bad):
+        (q1 if j % 2 == 0 else q2)[i, (j // 2) % 2] = [np.nan, np.inf, 3e38][j % 3]
+    nan = np.full((40, 2), np.nan, np.float32)
+    return [(q1, q2, bad, dict(prob=0.999, threshold=1.0, max_iters=200, seed=3)),
+            (nan, nan.copy(), None, dict(prob=0.999, threshold=1.0, max_iters=70, seed=4))]
+
+
+def check_bad_points(r, bad, n, kw):
+    """What rules 1-7 give on such input: a bad point is never in the mask; nothing but bad points is rule 7's result
+    after max_iters iterations."""
+    if bad is None:
+        assert zero_result(r, n) and r["iters"] == kw["max_iters"]
+    else:
+        assert not r["mask"][bad].any() and r["inliers"] >= 100 and r["mask"].sum() == r["good"]
+
+
+def pose_raw(pkg, c, p1, p2, n, K, prob, threshold, max_iters, seed, with_mask=True, fill=7.0):
+    """orbx_estimate_pose through ctypes with pre-filled outputs (K and mask may be None): status and outputs."""
+    p1 = np.ascontiguousarray(p1, np.float32)
+    p2 = np.ascontiguousarray(p2, np.float32)
+    K = None if K is None else np.ascontiguousarray(K, np.float64)
+    E, R, t = np.full(9, fill), np.full(9, fill), np.full(3, fill)
+    mask = np.full(max(len(p1), 1), 9, np.uint8) if with_mask else None
+    cnt = np.full(3, -5, np.int32)
+    f = pkg.orbx.load().orbx_estimate_pose
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, DP, C.c_double, C.c_double, C.c_int,
+                  C.c_uint64] + [C.c_void_p] * 7
+    st = f(c._h, p1.ctypes.data, p2.ctypes.data, n, None if K is None else K.ctypes.data_as(DP), prob, threshold,
+           max_iters, seed, E.ctypes.data, R.ctypes.data, t.ctypes.data, None if mask is None else mask.ctypes.data,
+           cnt.ctypes.data, cnt.ctypes.data + 4, cnt.ctypes.data + 8)
+    return st, {"E": E.reshape(3, 3), "R": R.reshape(3, 3), "t": t, "mask": mask, "inliers": int(cnt[0]),
+                "good": int(cnt[1]), "iters": int(cnt[2])}
+
+
 @pytest.mark.gpu
 def test_gpu_estimate_pose_equals_sequential(pkg, seq):
     cases = gpu_cases()
     with pkg.Context(pkg.default_params("gpu")) as c:
         for cs in cases:
-            p1, p2, *_ = scene(cs["seed"], max(cs["n"], 1), cs["outliers"], cs["noise"])
-            p1, p2 = p1[:cs["n"]], p2[:cs["n"]]
-            kw = dict(prob=cs["prob"], threshold=cs["threshold"], max_iters=cs["max_iters"], seed=cs["rseed"])
+            p1, p2, kw = case_inputs(cs)
             got = c.estimate_pose(p1, p2, K_KITTI, **kw)
             ref = seq_pose(seq, p1, p2, **kw)
             assert bit_equal(got, ref), cs
+        # the chunk and lane-stride boundaries, prob 0 and 1, threshold 0
+        grid = grid_cases()
+        iters = []
+        for cs in grid:
+            p1, p2, kw = case_inputs(cs)
+            got = c.estimate_pose(p1, p2, K_KITTI, **kw)
+            ref = seq_pose(seq, p1, p2, **kw)
+            assert bit_equal(got, ref), cs
+            iters.append(ref["iters"])
+        assert grid_hits_the_chunk_edges(iters, grid), sorted(set(iters))
+        for p1, p2, kw in aniso_cases():
+            got = c.estimate_pose(p1, p2, K_ANISO, **kw)
+            ref = seq_pose(seq, p1, p2, K=K_ANISO, **kw)
+            assert ref["inliers"] >= 0.5 * len(p1) and bit_equal(got, ref), len(p1)
+        for p1, p2, bad, kw in bad_point_cases():
+            got = c.estimate_pose(p1, p2, K_KITTI, **kw)
+            ref = seq_pose(seq, p1, p2, **kw)
+            check_bad_points(ref, bad, len(p1), kw)
+            assert bit_equal(got, ref), bad
+        # mask = NULL: the same result without it
+        p1, p2, *_ = scene(11, 129, 0.3)
+        ref = seq_pose(seq, p1, p2, seed=9)
+        st, got = pose_raw(pkg, c, p1, p2, len(p1), K_KITTI, 0.999, 1.0, 1000, 9, with_mask=False)
+        got["mask"] = ref["mask"]
+        assert st == pkg.orbx.OK and ref["inliers"] > 50 and bit_equal(got, ref)
         # the degenerate ones: identical points, zero translation, N < 5 (6 more cases: 48 in all)
         p1, p2, *_ = scene(99, 60)
         q1, q2, *_ = scene(98, 400, noise="none", t=np.zeros(3), depth=(5.0, 40.0))
@@ -346,6 +469,93 @@ def test_gpu_pose_lanes_and_invalid_states(pkg):
             c.batch_match_consecutive(0.8)
         with pytest.raises(pkg.OrbxError):
             c.batch_pose_consecutive(K_KITTI)
+
+
+def header_pose_max_iters():
+    import re
+
+    text = open(os.path.join(ROOT, "include", "orbx.h")).read()
+    return int(re.search(r"#define ORBX_POSE_MAX_ITERS (\d+)", text).group(1))
+
+
+def pose_refusals(cap):
+    """(name, overrides of a valid call); K is given as (index, value) or None for NULL."""
+    nan, inf = float("nan"), float("inf")
+    out = [("K NULL", dict(K=None))]
+    out += [("K[%d] = %r" % (i, v), dict(K=(i, v))) for i in (0, 4, 2, 5) for v in (nan, inf)]
+    out += [("K[%d] = %r" % (i, v), dict(K=(i, v))) for i in (0, 4) for v in (0.0, -718.856, -inf)]
+    out += [("prob %r" % v, dict(prob=v)) for v in (nan, inf, -inf)]
+    out += [("threshold %r" % v, dict(threshold=v)) for v in (-1.0, -1e-300, nan, inf, -inf)]
+    out += [("max_iters %d" % v, dict(max_iters=v)) for v in (-1, -2**31, cap + 1)]
+    return out
+
+
+def test_pose_max_iters_is_one_value(pkg):
+    assert header_pose_max_iters() == pkg.orbx.POSE_MAX_ITERS == 100000
+
+
+@pytest.mark.gpu
+def test_gpu_pose_refusals(pkg, seq):
+    """Every bad argument is refused with ORBX_ERR_INVALID_ARG by both entries and leaves the outputs (the host
+    arrays; the last posed batch) as they were.  Every call here, refused or not, is on input whose RANSAC ends inside
+    the first chunk, and none above the cap is on input without a model."""
+    cap = pkg.orbx.POSE_MAX_ITERS
+    INV = pkg.orbx.ERR_INVALID_ARG
+    p1, p2, *_ = scene(5, 100, 0.0, noise="none")
+    ref_cap = seq_pose(seq, p1, p2, max_iters=cap)
+    assert 1 <= ref_cap["iters"] <= 32 and ref_cap["inliers"] == 100  # before any GPU call at or above the cap
+
+    def K_of(spec):
+        if spec is None:
+            return None
+        K = K_KITTI.copy()
+        K.flat[spec[0]] = spec[1]
+        return K
+
+    valid = dict(K=(8, 1.0), prob=0.999, threshold=1.0, max_iters=1000, seed=2)
+    k0, k1 = O.load_kitti(0), O.load_kitti(1)
+    p = pkg.default_params("gpu", nfeatures=500, max_width=W, max_height=H, max_batch=2)
+    with pkg.Context(p) as c:
+        def host(n=len(p1), **kw):
+            a = dict(valid, **kw)
+            return pose_raw(pkg, c, p1, p2, n, K_of(a["K"]), a["prob"], a["threshold"], a["max_iters"], a["seed"])
+
+        st, untouched = host(K=None)
+        assert st == INV
+        st, got = host()
+        assert st == pkg.orbx.OK and bit_equal(got, seq_pose(seq, p1, p2, seed=2))
+        for name, kw in pose_refusals(cap) + [("n = -1", dict(n=-1)), ("n = -2^31", dict(n=-2**31))]:
+            st, got = host(**kw)
+            assert st == INV and bit_equal(got, untouched) and got["iters"] == -5 and got["E"][0, 0] == 7.0, name
+        # the cap itself is accepted
+        got = c.estimate_pose(p1, p2, K_KITTI, max_iters=cap)
+        assert bit_equal(got, ref_cap)
+        # the batched entry: a matched batch, so that only the arguments can be what is refused
+        kitti_batch(pkg, c, np.stack([k0, k1]))
+        f = pkg.orbx.load().orbx_batch_pose_consecutive
+        f.argtypes = [C.c_void_p, DP, C.c_double, C.c_double, C.c_int, C.c_uint64]
+
+        def batch(**kw):
+            a = dict(valid, **kw)
+            K = K_of(a["K"])
+            return f(c._h, None if K is None else K.ctypes.data_as(DP), a["prob"], a["threshold"], a["max_iters"],
+                     a["seed"])
+
+        accepted = dict(prob=valid["prob"], threshold=valid["threshold"], seed=valid["seed"])
+        c.batch_pose_consecutive(K_KITTI, max_iters=valid["max_iters"], **accepted)
+        ref = c.batch_pose_fetch()
+        refm = c.batch_pose_mask(0)
+        assert ref["inliers"][0] >= 20 and ref["iters"][0] < 1000  # the pair has a model: the cap stops early too
+        for name, kw in pose_refusals(cap):
+            assert batch(**kw) == INV, name
+            got = c.batch_pose_fetch()
+            for k in ref:
+                assert np.array_equal(got[k], ref[k]), (name, k)
+            assert np.array_equal(c.batch_pose_mask(0), refm), name
+        c.batch_pose_consecutive(K_KITTI, max_iters=cap, **accepted)
+        got = c.batch_pose_fetch()
+        for k in ref:
+            assert np.array_equal(got[k], ref[k]), k
 
 
 CPP_MIRROR = r"""

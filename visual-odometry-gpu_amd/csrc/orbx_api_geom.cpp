@@ -14,7 +14,8 @@ using namespace orbx_host;
 namespace {
 bool pose_args_ok(const double* K, double prob, double threshold, int max_iters) {
   return K && K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) &&
-         std::isfinite(K[5]) && std::isfinite(prob) && std::isfinite(threshold) && threshold >= 0 && max_iters >= 0;
+         std::isfinite(K[5]) && std::isfinite(prob) && std::isfinite(threshold) && threshold >= 0 && max_iters >= 0 &&
+         max_iters <= ORBX_POSE_MAX_ITERS;
 }
 void pose_unpack(const OrbxPoseOut& r, double* E, double* R, double* t, int32_t* inliers, int32_t* good,
                  int32_t* iters) {

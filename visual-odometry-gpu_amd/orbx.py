@@ -516,6 +516,9 @@ def _matcher_methods():
 _matcher_methods()
 
 
+POSE_MAX_ITERS = 100000  # ORBX_POSE_MAX_ITERS
+
+
 def _pose_methods():
     """Relative pose: findEssentialMat(RANSAC) + recoverPose (include/orbx.h)."""
 
