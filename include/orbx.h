@@ -506,8 +506,10 @@ int orbx_chain_trajectory(const double* T0, const double* R, const double* t, co
 typedef enum {
   ORBX_BA_CONVERGENCE = 0,    /* a tolerance was reached: the blocks hold the solution */
   ORBX_BA_NO_CONVERGENCE = 1, /* max_iters iterations ran: the blocks are unchanged */
-  ORBX_BA_FAILURE = 2         /* non-finite initial cost, an observation at depth 0 at the start, or a rotation
+  ORBX_BA_FAILURE = 2,        /* non-finite initial cost, an observation at depth 0 at the start, or a rotation
                                  angle beyond 1e5 rad: the blocks are unchanged */
+  ORBX_BA_SKIPPED = 3         /* a window of a landmarks block without landmarks (orbx_bundle_adjust_landmarks_device
+                                 only): nothing was read, every other field of the summary is 0 */
 } orbx_ba_termination;
 typedef struct {
   int32_t termination; /* orbx_ba_termination */
@@ -653,6 +655,85 @@ int orbx_lk_workspace_limit(orbx_ctx* ctx, size_t bytes);
 int orbx_lk_track_window(orbx_ctx* ctx, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
                          size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen, float* err,
                          int win_size, int max_level, int max_iters, double epsilon);
+
+/* ---- next row: landmarks of tracked windows, bundle-adjusted on the device ----------
+ * Replaces
+ *   buildLandmarksFromFirstTwoFramesAndTracks: baseline gate, P0 / P1 from the first two poses, linear
+ *   triangulation of every track seen at least twice, "simple depth check"    src/with_bundle_adjustment.cpp:502-575
+ *   the Ceres solve of the window built from them                              src/with_bundle_adjustment.cpp:612-720
+ * for n_windows windows per call, from the tracks block of orbx_lk_track_windows_device to the solved poses without
+ * a host round trip beyond the window poses.  Rules: the poses are BA's own blocks (angle-axis
+ * then translation, world -> camera); the gate is 0.1 <= |t0 - t1| <= 100; the DLT runs in WORLD coordinates on the
+ * first two pixels of a track widened to double, the point stays in binary64; a landmark is kept iff its slot has
+ * seen >= 2, the homogeneous point is finite after the division and its world z is > 0.  Kept landmarks stand in
+ * ascending slot order, each with the observations k = 0 .. seen - 1 of its slot in ascending k (`seen` outside
+ * [0, window_len] is clamped); slot_of_point names the slot.  A window that is not ORBX_LM_OK owns no landmark and
+ * no observation.  OpenCV is absent from the image this library was written in: parity with
+ * cv::triangulatePoints / cv::SVD is unpinned. */
+typedef enum {
+  ORBX_LM_OK = 0,
+  ORBX_LM_BASELINE = 1, /* |t0 - t1| outside [0.1, 100]                       src/with_bundle_adjustment.cpp:515-516 */
+  ORBX_LM_EMPTY = 2,    /* the gate passed and no landmark was kept */
+  ORBX_LM_BAD_POSE = 3  /* the rotation angle of pose 0 or 1 is beyond 1e5 rad */
+} orbx_lm_status;
+/* Builds the landmarks block of n_windows windows, asynchronously on the context's stream (or `stream`, a
+ * hipStream_t).  d_tracks_xy / d_seen: device memory in the layout of orbx_lk_windows_view -- they may BE that view;
+ * a call on another stream than the last windows call's waits for that call's event.  poses6: HOST,
+ * n_windows x window_len x 6 doubles; K: host, row-major double[9].  ORBX_ERR_INVALID_ARG: window_len outside
+ * [2, ORBX_BA_MAX_POSES], n_windows < 1, slot_capacity < 1, a NULL pointer, a non-finite K or pose.
+ * ORBX_ERR_UNSUPPORTED: slot_capacity > 65536, or n_windows x (slot_capacity + 1) or n_windows x slot_capacity x
+ * window_len beyond 32-bit offsets.  On any refusal nothing is written and the previous block stays fetchable.
+ * The block is the entry's OWN, sized for every slot kept (57 + 17 window_len bytes per slot, scratch included): ORB
+ * results, matches, poses, scales, the good-features block, the LK blocks and the state of orbx_bundle_adjust_batch
+ * stay as they are.  A caller's stream is used during the call only: later calls, fetches and orbx_destroy wait for
+ * an event recorded behind the call.  src/with_bundle_adjustment.cpp:502-575 */
+int orbx_landmarks_build_device(orbx_ctx* ctx, const double* K, const float* d_tracks_xy, const int32_t* d_seen,
+                                int n_windows, int slot_capacity, int window_len, const double* poses6, void* stream);
+/* Device-side view of the last landmarks block (valid until the next build; written on its stream): exactly the
+ * arrays k_ba_lm reads.  src/with_bundle_adjustment.cpp:502-575 */
+typedef struct {
+  const int32_t* status;        /* [n_windows] orbx_lm_status */
+  const int32_t* pose_offset;   /* [n_windows + 1], w * window_len */
+  const int32_t* point_offset;  /* [n_windows + 1] */
+  const int32_t* obs_offset;    /* [n_windows + 1] */
+  const double* points3;        /* [point_offset[n_windows]][3], world frame */
+  const int32_t* rows;          /* window w: its landmarks + 1 row starts into its observations, at point_offset[w] + w */
+  const uint8_t* obs_pose;      /* [obs_offset[n_windows]] */
+  const double* obs_xy;         /* [obs_offset[n_windows]][2] */
+  const int32_t* slot_of_point; /* [point_offset[n_windows]] */
+  int32_t slot_capacity, window_len, n_windows;
+} orbx_landmarks_view;
+int orbx_landmarks_results_device(orbx_ctx* ctx, orbx_landmarks_view* view);
+/* Waits for the last build and copies windows [first, first + n) in the format of orbx_bundle_adjust_batch's
+ * arguments: status (n), pose_offset / point_offset / obs_offset (n + 1 each, starting at 0), points3,
+ * slot_of_point, and the observations as obs_point / obs_pose (int32 indices inside the window) and obs_xy.  Every
+ * array may be NULL.  *n_points / *n_obs = landmarks and observations of those windows; if one exceeds its capacity,
+ * ORBX_ERR_CAPACITY is returned, the two counts are the capacities required and nothing else is written.
+ * src/with_bundle_adjustment.cpp:502-575 */
+int orbx_landmarks_fetch(orbx_ctx* ctx, int first, int n, int32_t* status, int32_t* pose_offset, int32_t* point_offset,
+                         int32_t* obs_offset, double* points3, int32_t* slot_of_point, int point_capacity,
+                         int32_t* obs_point, int32_t* obs_pose, double* obs_xy, int obs_capacity, int* n_points,
+                         int* n_obs);
+/* Solves every window of the last landmarks block as orbx_bundle_adjust_batch solves it (the same kernel, the same
+ * bits), asynchronously on the context's stream (or `stream`), with the K of the build.  huber_delta and max_iters
+ * as orbx_bundle_adjust_batch; without a landmarks block: ORBX_ERR_INVALID_ARG.  The solve works on copies of the
+ * poses and points: the block stays as built, and a second solve starts from the same blocks.  A window that is not
+ * ORBX_LM_OK reports ORBX_BA_SKIPPED and keeps its poses.  src/with_bundle_adjustment.cpp:612-720 */
+int orbx_bundle_adjust_landmarks_device(orbx_ctx* ctx, double huber_delta, int max_iters, void* stream);
+/* Waits for the last solve and copies windows [first, first + n): poses6 (n x window_len x 6), summaries (n) and the
+ * points (in the order of the block; *count of them; ORBX_ERR_CAPACITY if > capacity, then *count is the capacity
+ * required and nothing else is written).  Each array may be NULL.  src/with_bundle_adjustment.cpp:612-720 */
+int orbx_bundle_adjust_landmarks_fetch(orbx_ctx* ctx, int first, int n, double* poses6, orbx_ba_summary* summaries,
+                                       double* points3, int capacity, int* count);
+/* Host convenience: ONE window of host tracks (n_slots x window_len x 2 floats), seen (n_slots) and poses6
+ * (window_len x 6, in / out: rewritten only on convergence) through both stages as a batch of one; synchronous;
+ * replaces the last landmarks block.  *lm_status: the window's orbx_lm_status; points3 / slot_of_point: the refined
+ * landmarks and their slots, *count of them (capacity rule as above; both may be NULL).
+ * src/with_bundle_adjustment.cpp:502-575, src/with_bundle_adjustment.cpp:612-720 */
+int orbx_bundle_adjust_tracks(orbx_ctx* ctx, const double* K, const float* tracks_xy, const int32_t* seen, int n_slots,
+                              int window_len, double* poses6, double huber_delta, int max_iters, int32_t* lm_status,
+                              orbx_ba_summary* summary, double* points3, int32_t* slot_of_point, int capacity,
+                              int* count);
 
 #ifdef __cplusplus
 }

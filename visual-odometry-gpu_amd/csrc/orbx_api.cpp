@@ -865,8 +865,9 @@ void orbx_destroy(orbx_ctx* c) {
     (void)hipStreamSynchronize(c->cstream);
     (void)hipStreamDestroy(c->cstream);
   }
-  // every subsystem releases what it owns.  The windows tracker before the good features: each waits for its own
-  // event before its buffers go, and the tracker may be reading the good-features block.
+  // every subsystem releases what it owns.  The landmarks before the windows tracker, the tracker before the good
+  // features: each waits for its own event before its buffers go, and each may be reading the next one's block.
+  c->lm.release();
   c->lkw.release();
   c->gf.release();
   c->s.release();

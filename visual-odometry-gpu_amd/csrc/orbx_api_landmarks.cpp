@@ -1,0 +1,368 @@
+// orbx_api_landmarks.cpp -- host layer of liborbx.so (orbx_host.h): landmarks of tracked windows built on the device
+// and their bundle adjustment on that block.
+// buildLandmarksFromFirstTwoFramesAndTracks (src/with_bundle_adjustment.cpp:502-575) and the solve of the window
+// (src/with_bundle_adjustment.cpp:612-720) for many windows per call.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "orbx_host.h"
+
+using namespace orbx_host;
+
+namespace {
+
+// a buffer of the landmarks path of at least `bytes`: the new allocation is made BEFORE the old one is released, so
+// that a failed call keeps what it had
+int lm_grow(orbx_ctx* c, DevBuf& b, size_t bytes) {
+  if (b.p && b.bytes >= bytes) return ORBX_OK;
+  const int st = c->lm.side.wait(c);  // (the old allocation may still be read or written)
+  if (st != ORBX_OK) return st;
+  bytes = align_up_sz(std::max<size_t>(bytes, 256), 256);
+  void* p = nullptr;
+  HIPCHK(c, hipMalloc(&p, bytes));
+  if (b.p) (void)hipFree(b.p);
+  b.p = p;
+  b.bytes = bytes;
+  return ORBX_OK;
+}
+
+struct Taker {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t r = off;
+    off = align_up_sz(off + bytes, 256);
+    return r;
+  }
+};
+
+// the result block: every array sized for every slot kept
+struct LmBlock {
+  size_t status, pose_off, pt_off, obs_off, slot, rows, points, oxy, opose, bytes;
+};
+LmBlock lm_block(int n, int cap, int len) {
+  LmBlock L;
+  Taker t;
+  const size_t slots = (size_t)n * cap, noff = (size_t)n + 1;
+  L.status = t.take(sizeof(int32_t) * n);
+  L.pose_off = t.take(sizeof(int32_t) * noff);
+  L.pt_off = t.take(sizeof(int32_t) * noff);
+  L.obs_off = t.take(sizeof(int32_t) * noff);
+  L.slot = t.take(sizeof(int32_t) * slots);
+  L.rows = t.take(sizeof(int32_t) * (slots + n));
+  L.points = t.take(sizeof(double) * 3 * slots);
+  L.oxy = t.take(sizeof(double) * 2 * slots * len);
+  L.opose = t.take(slots * len);
+  L.bytes = t.off;
+  return L;
+}
+// the scratch of a build
+struct LmScratch {
+  size_t poses, gate, partial, keep, cand, bytes;
+};
+LmScratch lm_scratch(int n, int cap, int len) {
+  LmScratch L;
+  Taker t;
+  const size_t slots = (size_t)n * cap;
+  L.poses = t.take(sizeof(double) * 6 * (size_t)n * len);
+  L.gate = t.take(sizeof(int32_t) * n);
+  L.partial = t.take(sizeof(int32_t) * 2 * (size_t)n * orbx_lm_blocks(cap));
+  L.keep = t.take(slots);
+  L.cand = t.take(sizeof(double) * 3 * slots);
+  L.bytes = t.off;
+  return L;
+}
+// what a solve works on and leaves behind
+struct LmSolve {
+  size_t poses, points, out, bytes;
+};
+LmSolve lm_solve(int n, int cap, int len) {
+  LmSolve L;
+  Taker t;
+  L.poses = t.take(sizeof(double) * 6 * (size_t)n * len);
+  L.points = t.take(sizeof(double) * 3 * (size_t)n * cap);
+  L.out = t.take(sizeof(orbx_ba_summary) * (size_t)n);
+  L.bytes = t.off;
+  return L;
+}
+
+OrbxLmBlock lm_pointers(const orbx_ctx* c, const LmBlock& L) {
+  uint8_t* b = (uint8_t*)c->lm.blk.p;
+  OrbxLmBlock o;
+  o.status = (int32_t*)(b + L.status);
+  o.pose_off = (int32_t*)(b + L.pose_off);
+  o.pt_off = (int32_t*)(b + L.pt_off);
+  o.obs_off = (int32_t*)(b + L.obs_off);
+  o.points3 = (double*)(b + L.points);
+  o.rows = (int32_t*)(b + L.rows);
+  o.opose = b + L.opose;
+  o.oxy = (double*)(b + L.oxy);
+  o.slot_of_point = (int32_t*)(b + L.slot);
+  return o;
+}
+
+int lm_check_range(orbx_ctx* c, int first, int n) {
+  if (c->lm.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no landmarks block has been built");
+  if (first < 0 || n < 1 || first >= c->lm.n || n > c->lm.n - first)
+    return fail(c, ORBX_ERR_INVALID_ARG, "[first, first + n) outside the landmarks block");
+  return ORBX_OK;
+}
+
+bool ba_params_ok(double huber_delta, int max_iters) {
+  return huber_delta > 0.0 && std::isfinite(huber_delta) && max_iters >= 1 && max_iters <= 1000;
+}
+
+// enqueues the three kernels on s; arguments are checked
+int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
+           const double* poses6, hipStream_t s) {
+  int st = c->lm.side.enter(c, s);
+  if (st != ORBX_OK) return st;
+  const SideWork::Mark mark{c->lm.side, s};
+  // the tracks may be the windows tracker's block, written on another stream
+  if (c->lkw.side.ev && c->lkw.side.stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->lkw.side.ev, 0));
+  const LmBlock B = lm_block(n, cap, len);
+  const LmScratch S = lm_scratch(n, cap, len);
+  if ((st = lm_grow(c, c->lm.scr, S.bytes)) != ORBX_OK) return st;
+  const void* old_blk = c->lm.blk.p;
+  if ((st = lm_grow(c, c->lm.blk, B.bytes)) != ORBX_OK) return st;
+  if (c->lm.blk.p != old_blk) c->lm.n = 0;  // (a larger block: the previous result went with the old one)
+  // The pose table goes up through a pinned mirror (a copy from pageable memory would make the host wait for the
+  // stream).  The mirror is reused: the previous call's copy has to have read it.
+  const size_t table = sizeof(double) * 6 * (size_t)n * len;
+  if (!c->lm.poses_ev) HIPCHK(c, hipEventCreateWithFlags(&c->lm.poses_ev, hipEventDisableTiming));
+  HIPCHK(c, hipEventSynchronize(c->lm.poses_ev));
+  if (c->lm.poses_host_bytes < table) {
+    if (c->lm.poses_host) (void)hipHostFree(c->lm.poses_host);
+    c->lm.poses_host = nullptr;
+    c->lm.poses_host_bytes = 0;
+    HIPCHK(c, hipHostMalloc(&c->lm.poses_host, align_up_sz(table, 4096), hipHostMallocDefault));
+    c->lm.poses_host_bytes = align_up_sz(table, 4096);
+  }
+  // from here on the previous block is being replaced
+  c->lm.n = 0;
+  c->lm.solved = false;
+  std::memcpy(c->lm.poses_host, poses6, table);
+  uint8_t* scr = (uint8_t*)c->lm.scr.p;
+  HIPCHK(c, hipMemcpyAsync(scr + S.poses, c->lm.poses_host, table, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(c->lm.poses_ev, s));
+  HIPCHK(c, orbx_launch_landmarks(s, K, (const double*)(scr + S.poses), d_tracks, d_seen, n, cap, len,
+                                  (double*)(scr + S.cand), scr + S.keep, (int32_t*)(scr + S.partial),
+                                  (int32_t*)(scr + S.gate), lm_pointers(c, B)));
+  std::memcpy(c->lm.K, K, sizeof c->lm.K);
+  c->lm.n = n;
+  c->lm.cap = cap;
+  c->lm.len = len;
+  return ORBX_OK;
+}
+
+int lm_check_build(orbx_ctx* c, const double* K, const void* tracks, const void* seen, int n, int cap, int len,
+                   const double* poses6) {
+  if (!K || !tracks || !seen || !poses6) return fail(c, ORBX_ERR_INVALID_ARG, "K, tracks, seen or poses6 is NULL");
+  if (n < 1 || cap < 1 || len < 2 || len > ORBX_BA_MAX_POSES)
+    return fail(c, ORBX_ERR_INVALID_ARG, "n_windows < 1, slot_capacity < 1 or window_len outside [2, 8]");
+  if (cap > ORBX_BA_MAX_POINTS) return fail(c, ORBX_ERR_UNSUPPORTED, "more slots in a window than 65536");
+  if ((unsigned long long)n * ((unsigned long long)cap + 1) > 0x7fffffffull ||
+      (unsigned long long)n * cap * len > 0x7fffffffull)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "more landmarks or observations in a batch than 32-bit offsets hold");
+  if (!finite_all(K, 9)) return fail(c, ORBX_ERR_INVALID_ARG, "K is not finite");
+  for (size_t i = 0; i < 6 * (size_t)n * len; i++)
+    if (!std::isfinite(poses6[i])) return fail(c, ORBX_ERR_INVALID_ARG, "a pose is not finite");
+  return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_landmarks_build_device(orbx_ctx* c, const double* K, const float* d_tracks_xy, const int32_t* d_seen,
+                                int n_windows, int slot_capacity, int window_len, const double* poses6, void* stream) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  const int st = lm_check_build(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, poses6);
+  if (st != ORBX_OK) return st;
+  return lm_run(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, poses6,
+                stream ? (hipStream_t)stream : c->stream);
+}
+
+int orbx_landmarks_results_device(orbx_ctx* c, orbx_landmarks_view* v) {
+  DeviceGuard _dg(c);
+  if (!c || !v) return ORBX_ERR_INVALID_ARG;
+  if (c->lm.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no landmarks block has been built");
+  const OrbxLmBlock P = lm_pointers(c, lm_block(c->lm.n, c->lm.cap, c->lm.len));
+  v->status = P.status;
+  v->pose_offset = P.pose_off;
+  v->point_offset = P.pt_off;
+  v->obs_offset = P.obs_off;
+  v->points3 = P.points3;
+  v->rows = P.rows;
+  v->obs_pose = P.opose;
+  v->obs_xy = P.oxy;
+  v->slot_of_point = P.slot_of_point;
+  v->slot_capacity = c->lm.cap;
+  v->window_len = c->lm.len;
+  v->n_windows = c->lm.n;
+  return ORBX_OK;
+}
+
+int orbx_landmarks_fetch(orbx_ctx* c, int first, int n, int32_t* status, int32_t* pose_offset, int32_t* point_offset,
+                         int32_t* obs_offset, double* points3, int32_t* slot_of_point, int point_capacity,
+                         int32_t* obs_point, int32_t* obs_pose, double* obs_xy, int obs_capacity, int* n_points,
+                         int* n_obs) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  int st = lm_check_range(c, first, n);
+  if (st != ORBX_OK) return st;
+  if (point_capacity < 0 || obs_capacity < 0) return fail(c, ORBX_ERR_INVALID_ARG, "a capacity is negative");
+  if ((st = c->lm.side.wait(c)) != ORBX_OK) return st;
+  const OrbxLmBlock P = lm_pointers(c, lm_block(c->lm.n, c->lm.cap, c->lm.len));
+  const size_t noff = (size_t)n + 1;
+  std::vector<int32_t> po(noff), oo(noff);
+  HIPCHK(c, hipMemcpy(po.data(), P.pt_off + first, sizeof(int32_t) * noff, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(oo.data(), P.obs_off + first, sizeof(int32_t) * noff, hipMemcpyDeviceToHost));
+  const int32_t p0 = po[0], o0 = oo[0];
+  const size_t np = (size_t)(po[n] - p0), no = (size_t)(oo[n] - o0);
+  if (n_points) *n_points = (int)np;
+  if (n_obs) *n_obs = (int)no;
+  const bool want_pts = points3 || slot_of_point, want_obs = obs_point || obs_pose || obs_xy;
+  if ((want_pts && np > (size_t)point_capacity) || (want_obs && no > (size_t)obs_capacity))
+    return fail(c, ORBX_ERR_CAPACITY, "landmarks fetch: a capacity is too small");
+  std::vector<int32_t> rows;
+  std::vector<uint8_t> op;
+  if (obs_point && no) {
+    rows.resize(np + (size_t)n);  // N + 1 row starts per window
+    HIPCHK(c, hipMemcpy(rows.data(), P.rows + p0 + first, sizeof(int32_t) * rows.size(), hipMemcpyDeviceToHost));
+  }
+  if (obs_pose && no) {
+    op.resize(no);
+    HIPCHK(c, hipMemcpy(op.data(), P.opose + o0, no, hipMemcpyDeviceToHost));
+  }
+  if (status) HIPCHK(c, hipMemcpy(status, P.status + first, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (points3 && np) HIPCHK(c, hipMemcpy(points3, P.points3 + 3 * (size_t)p0, sizeof(double) * 3 * np, hipMemcpyDeviceToHost));
+  if (slot_of_point && np)
+    HIPCHK(c, hipMemcpy(slot_of_point, P.slot_of_point + p0, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
+  if (obs_xy && no) HIPCHK(c, hipMemcpy(obs_xy, P.oxy + 2 * (size_t)o0, sizeof(double) * 2 * no, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < noff; i++) {
+    if (pose_offset) pose_offset[i] = (int32_t)i * c->lm.len;
+    if (point_offset) point_offset[i] = po[i] - p0;
+    if (obs_offset) obs_offset[i] = oo[i] - o0;
+  }
+  for (size_t i = 0; i < op.size(); i++) obs_pose[i] = op[i];
+  if (!rows.empty()) {
+    for (int w = 0; w < n; w++) {
+      const int32_t* row = rows.data() + (po[w] - p0) + w;
+      int32_t* dst = obs_point + (oo[w] - o0);
+      for (int j = 0; j < po[w + 1] - po[w]; j++)
+        for (int o = row[j]; o < row[j + 1]; o++) dst[o] = j;
+    }
+  }
+  return ORBX_OK;
+}
+
+int orbx_bundle_adjust_landmarks_device(orbx_ctx* c, double huber_delta, int max_iters, void* stream) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!ba_params_ok(huber_delta, max_iters)) return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  if (c->lm.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no landmarks block has been built");
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  int st = c->lm.side.enter(c, s);
+  if (st != ORBX_OK) return st;
+  const SideWork::Mark mark{c->lm.side, s};
+  const int n = c->lm.n, cap = c->lm.cap, len = c->lm.len, ocap = cap * len;
+  // workgroups: as many as windows, bounded by ORBX_BA_MAX_GROUPS and by the workspace budget
+  const size_t per_group =
+      sizeof(double) * ((size_t)ORBX_BA_WS_POINT * cap + (size_t)ORBX_BA_WS_OBS * ocap) + 8 * (size_t)cap;
+  int groups = std::min(n, ORBX_BA_MAX_GROUPS);
+  groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)groups, ORBX_BA_WS_BUDGET / per_group));
+  Taker t;
+  const size_t o_wp = t.take(sizeof(double) * ORBX_BA_WS_POINT * (size_t)cap * groups);
+  const size_t o_wo = t.take(sizeof(double) * ORBX_BA_WS_OBS * (size_t)ocap * groups);
+  const size_t o_slot = t.take(8 * (size_t)cap * groups);
+  const LmSolve V = lm_solve(n, cap, len);
+  if ((st = lm_grow(c, c->lm.ws, t.off)) != ORBX_OK) return st;
+  const void* old_sol = c->lm.sol.p;
+  if ((st = lm_grow(c, c->lm.sol, V.bytes)) != ORBX_OK) return st;
+  if (c->lm.sol.p != old_sol) c->lm.solved = false;
+  const OrbxLmBlock P = lm_pointers(c, lm_block(n, cap, len));
+  const LmScratch S = lm_scratch(n, cap, len);
+  uint8_t* sol = (uint8_t*)c->lm.sol.p;
+  uint8_t* ws = (uint8_t*)c->lm.ws.p;
+  c->lm.solved = false;
+  // the block stays as built: the solve reads and writes copies of its poses and points
+  HIPCHK(c, hipMemcpyAsync(sol + V.poses, (const uint8_t*)c->lm.scr.p + S.poses, sizeof(double) * 6 * (size_t)n * len,
+                           hipMemcpyDeviceToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(sol + V.points, P.points3, sizeof(double) * 3 * (size_t)n * cap, hipMemcpyDeviceToDevice, s));
+  const double K4[4] = {c->lm.K[0], c->lm.K[4], c->lm.K[2], c->lm.K[5]};
+  HIPCHK(c, orbx_launch_ba(s, n, groups, max_iters, K4, huber_delta, P.pose_off, P.pt_off, P.obs_off,
+                           (double*)(sol + V.poses), (double*)(sol + V.points), P.rows, P.opose, P.oxy, cap, ocap,
+                           (double*)(ws + o_wp), (double*)(ws + o_wo), (unsigned long long*)(ws + o_slot),
+                           sol + V.out));
+  c->lm.solved = true;
+  return ORBX_OK;
+}
+
+int orbx_bundle_adjust_landmarks_fetch(orbx_ctx* c, int first, int n, double* poses6, orbx_ba_summary* summaries,
+                                       double* points3, int capacity, int* count) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  int st = lm_check_range(c, first, n);
+  if (st != ORBX_OK) return st;
+  if (!c->lm.solved) return fail(c, ORBX_ERR_INVALID_ARG, "the landmarks block has not been solved");
+  if (capacity < 0) return fail(c, ORBX_ERR_INVALID_ARG, "a capacity is negative");
+  if ((st = c->lm.side.wait(c)) != ORBX_OK) return st;
+  const OrbxLmBlock P = lm_pointers(c, lm_block(c->lm.n, c->lm.cap, c->lm.len));
+  const LmSolve V = lm_solve(c->lm.n, c->lm.cap, c->lm.len);
+  const uint8_t* sol = (const uint8_t*)c->lm.sol.p;
+  int32_t p0 = 0, p1 = 0;
+  HIPCHK(c, hipMemcpy(&p0, P.pt_off + first, sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&p1, P.pt_off + first + n, sizeof(int32_t), hipMemcpyDeviceToHost));
+  const size_t np = (size_t)(p1 - p0), per_win = sizeof(double) * 6 * (size_t)c->lm.len;
+  if (count) *count = (int)np;
+  if (points3 && np > (size_t)capacity) return fail(c, ORBX_ERR_CAPACITY, "landmarks solve fetch: capacity is too small");
+  if (poses6) HIPCHK(c, hipMemcpy(poses6, sol + V.poses + per_win * first, per_win * n, hipMemcpyDeviceToHost));
+  if (summaries)
+    HIPCHK(c, hipMemcpy(summaries, sol + V.out + sizeof(orbx_ba_summary) * (size_t)first, sizeof(orbx_ba_summary) * n,
+                        hipMemcpyDeviceToHost));
+  if (points3 && np)
+    HIPCHK(c, hipMemcpy(points3, sol + V.points + sizeof(double) * 3 * (size_t)p0, sizeof(double) * 3 * np,
+                        hipMemcpyDeviceToHost));
+  return ORBX_OK;
+}
+
+int orbx_bundle_adjust_tracks(orbx_ctx* c, const double* K, const float* tracks_xy, const int32_t* seen, int n_slots,
+                              int window_len, double* poses6, double huber_delta, int max_iters, int32_t* lm_status,
+                              orbx_ba_summary* summary, double* points3, int32_t* slot_of_point, int capacity,
+                              int* count) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  int st = lm_check_build(c, K, tracks_xy, seen, 1, n_slots, window_len, poses6);
+  if (st != ORBX_OK) return st;
+  if (!ba_params_ok(huber_delta, max_iters) || !lm_status || !summary || capacity < 0)
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  hipStream_t s = c->stream;
+  if ((st = c->lm.side.enter(c, s)) != ORBX_OK) return st;
+  const size_t tb = sizeof(float) * 2 * (size_t)n_slots * window_len;
+  const size_t o_seen = align_up_sz(tb, 256);
+  {
+    const SideWork::Mark mark{c->lm.side, s};
+    if ((st = lm_grow(c, c->lm.stage, o_seen + sizeof(int32_t) * (size_t)n_slots)) != ORBX_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(c->lm.stage.p, tracks_xy, tb, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync((uint8_t*)c->lm.stage.p + o_seen, seen, sizeof(int32_t) * (size_t)n_slots,
+                             hipMemcpyHostToDevice, s));
+  }
+  const uint8_t* stage = (const uint8_t*)c->lm.stage.p;
+  if ((st = lm_run(c, K, (const float*)stage, (const int32_t*)(stage + o_seen), 1, n_slots, window_len, poses6, s)) !=
+      ORBX_OK)
+    return st;
+  if ((st = orbx_bundle_adjust_landmarks_device(c, huber_delta, max_iters, nullptr)) != ORBX_OK) return st;
+  int np = 0;
+  if ((st = orbx_bundle_adjust_landmarks_fetch(c, 0, 1, nullptr, nullptr, nullptr, 0, &np)) != ORBX_OK) return st;
+  if (count) *count = np;
+  if ((points3 || slot_of_point) && np > capacity)
+    return fail(c, ORBX_ERR_CAPACITY, "bundle_adjust_tracks: capacity is too small");
+  if ((st = orbx_landmarks_fetch(c, 0, 1, lm_status, nullptr, nullptr, nullptr, nullptr, slot_of_point, capacity,
+                                 nullptr, nullptr, nullptr, 0, nullptr, nullptr)) != ORBX_OK)
+    return st;
+  return orbx_bundle_adjust_landmarks_fetch(c, 0, 1, poses6, summary, points3, capacity, nullptr);
+}
+
+}  // extern "C"

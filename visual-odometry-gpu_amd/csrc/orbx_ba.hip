@@ -177,6 +177,10 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_lm(int n_windows, int max_ite
   for (int win = blockIdx.x; win < n_windows; win += gridDim.x) {
     __syncthreads();  // the previous window's shared state is dead
     const int W = pose_off[win + 1] - pose_off[win], N = pt_off[win + 1] - pt_off[win];
+    if (N == 0) {  // (uniform) an empty window of a landmarks block: nothing of it is read
+      if (tid == 0) out[win] = BaSummary{BA_SKIPPED, 0, 0, 0, 0.0, 0.0};
+      continue;
+    }
     const int P = W - 1;
     w.W = W, w.N = N;
     w.row = rows + pt_off[win] + win;

@@ -24,7 +24,7 @@
 #define BA_GRADIENT_TOL 1e-10
 #define BA_PARAMETER_TOL 1e-8
 
-enum { BA_CONVERGENCE = 0, BA_NO_CONVERGENCE = 1, BA_FAILURE = 2 };
+enum { BA_CONVERGENCE = 0, BA_NO_CONVERGENCE = 1, BA_FAILURE = 2, BA_SKIPPED = 3 };
 
 // ---- sin / cos for x in [0, BA_MAX_THETA]: Cody-Waite reduction by pi/2 in three 33-bit pieces (n * piece is
 // exact for n < 2^20), then fdlibm's __kernel_sin / __kernel_cos on the reduced (head, tail) pair ----------------

@@ -154,7 +154,7 @@ struct SideWork {
   }
 };
 
-// ---- the context's parts, one per subsystem (orbx_ctx::s, m, lk, lkw, pose, scale, ba, gf) ----
+// ---- the context's parts, one per subsystem (orbx_ctx::s, m, lk, lkw, pose, scale, ba, gf, lm) ----
 
 // stage-API scratch (grown on demand; never touched by the batched path)
 struct StageScratch {
@@ -231,6 +231,28 @@ struct Scale {
 struct BundleAdjust {
   DevBuf off, poses, points, rows, opose, oxy, wp, wo, slot, out;
   void release() { free_bufs({&off, &poses, &points, &rows, &opose, &oxy, &wp, &wo, &slot, &out}); }
+};
+
+// landmarks of tracked windows and their bundle adjustment on the device (orbx_landmarks.hip, orbx_ba.hip): the
+// scratch of a build (pose table | gate | partial counts | keep flags | candidate points), the entry's OWN result
+// block (statuses | offsets | slot_of_point | rows | points3 | oxy | opose: what k_ba_lm reads), the solve's copies of
+// poses and points with its summaries, the solve's workspaces, and the staged tracks of the one-window host entry.
+// Nothing here is shared with orbx_bundle_adjust_batch.
+struct Landmarks {
+  DevBuf scr, blk, sol, ws, stage;
+  double K[9] = {};
+  int n = 0, cap = 0, len = 0;  // windows, slots per window, poses per window of the last build (0: none)
+  bool solved = false;          // the block has been solved since it was built
+  SideWork side;                // the event is recorded behind every build and every solve
+  void* poses_host = nullptr;   // pinned mirror of the pose table, and the event behind its upload
+  size_t poses_host_bytes = 0;
+  hipEvent_t poses_ev = nullptr;
+  void release() {
+    side.release();
+    if (poses_ev) (void)hipEventDestroy(poses_ev);
+    if (poses_host) (void)hipHostFree(poses_host);
+    free_bufs({&scr, &blk, &sol, &ws, &stage});
+  }
 };
 
 // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames (response maps | key pools | cell grids
@@ -311,9 +333,9 @@ struct orbx_ctx {
   hipStream_t last_stream = nullptr;
 
   long long batch_serial = 0;  // bumped by every batch run
-  // The subsystems beside the batched path, each with what it owns.  They meet in three places, visible where the
-  // calls are made: pose reads the matcher's table, scale checks pose.match_gen against m.gen, and the windows
-  // tracker waits for the good-features event.
+  // The subsystems beside the batched path, each with what it owns.  They meet in four places, visible where the
+  // calls are made: pose reads the matcher's table, scale checks pose.match_gen against m.gen, the windows
+  // tracker waits for the good-features event, and the landmarks build waits for the windows tracker's.
   orbx_host::StageScratch s;
   orbx_host::Matcher m;
   orbx_host::LkPair lk;
@@ -322,6 +344,7 @@ struct orbx_ctx {
   orbx_host::Scale scale;
   orbx_host::BundleAdjust ba;
   orbx_host::GoodFeatures gf;
+  orbx_host::Landmarks lm;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;

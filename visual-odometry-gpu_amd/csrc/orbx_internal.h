@@ -209,6 +209,28 @@ hipError_t orbx_launch_ba(hipStream_t s, int n_windows, int groups, int max_iter
                           const double* d_obs_xy, int cap, int ocap, double* d_ws_pt, double* d_ws_obs,
                           unsigned long long* d_ws_slot, void* d_out);
 
+// ---- landmarks of tracked windows (orbx_landmarks.hip) ---------------------------------------
+// The block k_lm_fill writes is the block orbx_launch_ba reads: status [n], three offset arrays [n + 1], points3
+// (3 doubles per kept landmark), rows (window w's landmarks + 1 offsets at pt_off[w] + w), opose / oxy per
+// observation, and the slot each kept landmark came from.  Sized for every slot kept: n * cap points, n * cap + n
+// rows, n * cap * window_len observations.
+#define ORBX_LM_THREADS 256
+struct OrbxLmBlock {
+  int32_t *status, *pose_off, *pt_off, *obs_off;
+  double* points3;
+  int32_t* rows;
+  uint8_t* opose;
+  double* oxy;
+  int32_t* slot_of_point;
+};
+// workgroups of k_lm_triangulate per window = rows of its table of partial counts
+inline int orbx_lm_blocks(int cap) { return (cap + ORBX_LM_THREADS - 1) / ORBX_LM_THREADS; }
+// K9: row-major 3x3 (host); d_poses: 6 * window_len doubles per window; d_tracks / d_seen: the layout of
+// orbx_lk_windows_view; d_cand: 3 rows of n * cap doubles; d_keep: n * cap bytes; d_partial: 2 * n * blocks; d_gate: n
+hipError_t orbx_launch_landmarks(hipStream_t s, const double* K9, const double* d_poses, const float* d_tracks,
+                                 const int32_t* d_seen, int n_windows, int cap, int window_len, double* d_cand,
+                                 uint8_t* d_keep, int32_t* d_partial, int32_t* d_gate, const OrbxLmBlock& out);
+
 // ---- Shi-Tomasi corners (orbx_gftt.hip): n frames per launch, every array per frame ---------
 // d_map: w * h floats; d_max: the largest response as a bit pattern (zeroed by the caller); d_keys: `pool` =
 // (w - 2)(h - 2) keys; d_ncand: candidates (zeroed by the caller); d_grid: grid_stride >= gw * gh * slots words, all

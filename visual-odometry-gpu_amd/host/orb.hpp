@@ -921,6 +921,31 @@ inline bool build_landmarks(const std::vector<Pose4x4>& pose_window, const doubl
   return true;
 }
 
+namespace detail {
+// The write-back gate of run_bundle_adjustment (src/with_bundle_adjustment.cpp:683-718) after a converged solve:
+// pose i (world -> camera block `poses`, before the solve `old`) is written back as a camera -> world 4x4 iff it
+// moved by less than 0.5 rad and 50 units.
+inline void ba_write_back(std::vector<Pose4x4>& pose_window, const std::vector<double>& poses,
+                          const std::vector<double>& old, std::vector<uint8_t>* updated) {
+  const int W = (int)pose_window.size();
+  for (int i = 0; i < W; i++) {
+    double R[9], Ro[9], Rd[9], wd[3];
+    rodrigues(&poses[(size_t)6 * i], R);
+    rodrigues(&old[(size_t)6 * i], Ro);
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) Rd[a * 3 + b] = R[a * 3] * Ro[b * 3] + R[a * 3 + 1] * Ro[b * 3 + 1] + R[a * 3 + 2] * Ro[b * 3 + 2];
+    rodrigues_inv(Rd, wd);
+    const double angle = std::sqrt(wd[0] * wd[0] + wd[1] * wd[1] + wd[2] * wd[2]);
+    double tn = 0.0;
+    for (int k = 0; k < 3; k++) tn += (poses[(size_t)6 * i + 3 + k] - old[(size_t)6 * i + 3 + k]) * (poses[(size_t)6 * i + 3 + k] - old[(size_t)6 * i + 3 + k]);
+    if (angle < 0.5 && std::sqrt(tn) < 50.0) {  // MAX_ROT_DIFF, MAX_TRANS_DIFF
+      pose_window[(size_t)i] = compose_inverse(R, &poses[(size_t)6 * i + 3]);
+      if (updated) (*updated)[(size_t)i] = 1;
+    }
+  }
+}
+}  // namespace detail
+
 // The solve and write-back of run_bundle_adjustment (src/with_bundle_adjustment.cpp:612-720): world -> camera
 // angle-axis blocks from the camera -> world poses, orbx_bundle_adjust (HuberLoss(1.0), 200 iterations, pose 0
 // constant), and -- only on convergence -- each pose written back iff it moved by less than 0.5 rad and 50 units
@@ -959,21 +984,59 @@ inline bool run_bundle_adjustment(std::vector<Pose4x4>& pose_window, const doubl
                 "orbx_bundle_adjust");
   if (summary) *summary = s;
   if (s.termination != ORBX_BA_CONVERGENCE) return true;  // :683
+  detail::ba_write_back(pose_window, poses, old, updated);
+  return true;
+}
+
+// The whole window from what LKTracker::trackWindow returns: landmarks built on the device
+// from the tracks (buildLandmarksFromFirstTwoFramesAndTracks, src/with_bundle_adjustment.cpp:502-575; the DLT in
+// WORLD coordinates, the point kept in binary64) and solved there (src/with_bundle_adjustment.cpp:612-720) through
+// orbx_bundle_adjust_tracks, then the same write-back gate as run_bundle_adjustment.  xy: n x pose_window.size()
+// points, seen: n.  build_landmarks + run_bundle_adjustment triangulate in camera 0's frame through float instead:
+// the two routes differ by that, and both are unpinned against OpenCV / Ceres.  lm_status: the orbx_lm_status of
+// the window; points / slot_of_point: the refined landmarks and the track each came from.  Returns false when
+// there is nothing to solve.
+inline bool run_bundle_adjustment_on_tracks(std::vector<Pose4x4>& pose_window, const double K[9],
+                                            const std::vector<Point2f>& xy, const std::vector<int32_t>& seen,
+                                            orbx_ba_summary* summary = nullptr, std::vector<uint8_t>* updated = nullptr,
+                                            int32_t* lm_status = nullptr, std::vector<Point3d>* points = nullptr,
+                                            std::vector<int32_t>* slot_of_point = nullptr, double huber_delta = 1.0,
+                                            int max_iters = 200) {
+  static_assert(sizeof(Point2f) == 2 * sizeof(float), "point layout");
+  const int W = (int)pose_window.size();
+  const size_t n = seen.size();
+  if (updated) updated->assign((size_t)W, 0);
+  if (points) points->clear();
+  if (slot_of_point) slot_of_point->clear();
+  if (W < 2 || n == 0) return false;
+  if (xy.size() != n * (size_t)W) throw std::runtime_error("run_bundle_adjustment_on_tracks: xy is not n x window");
+  std::vector<double> poses((size_t)6 * W);
   for (int i = 0; i < W; i++) {
-    double R[9], Ro[9], Rd[9], wd[3];
-    detail::rodrigues(&poses[(size_t)6 * i], R);
-    detail::rodrigues(&old[(size_t)6 * i], Ro);
-    for (int a = 0; a < 3; a++)
-      for (int b = 0; b < 3; b++) Rd[a * 3 + b] = R[a * 3] * Ro[b * 3] + R[a * 3 + 1] * Ro[b * 3 + 1] + R[a * 3 + 2] * Ro[b * 3 + 2];
-    detail::rodrigues_inv(Rd, wd);
-    const double angle = std::sqrt(wd[0] * wd[0] + wd[1] * wd[1] + wd[2] * wd[2]);
-    double tn = 0.0;
-    for (int k = 0; k < 3; k++) tn += (poses[(size_t)6 * i + 3 + k] - old[(size_t)6 * i + 3 + k]) * (poses[(size_t)6 * i + 3 + k] - old[(size_t)6 * i + 3 + k]);
-    if (angle < 0.5 && std::sqrt(tn) < 50.0) {  // MAX_ROT_DIFF, MAX_TRANS_DIFF
-      pose_window[(size_t)i] = detail::compose_inverse(R, &poses[(size_t)6 * i + 3]);
-      if (updated) (*updated)[(size_t)i] = 1;
-    }
+    double R[9], t[3];
+    detail::invert_rigid(pose_window[(size_t)i], R, t);
+    detail::rodrigues_inv(R, &poses[(size_t)6 * i]);
+    for (int k = 0; k < 3; k++) poses[(size_t)6 * i + 3 + k] = t[k];
   }
+  const std::vector<double> old = poses;
+  orbx_ba_summary s{};
+  int32_t st = ORBX_LM_OK;
+  int count = 0;
+  std::vector<double> p3(3 * n);
+  std::vector<int32_t> slots(n);
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c, orbx_bundle_adjust_tracks(c, K, reinterpret_cast<const float*>(xy.data()), seen.data(), (int)n, W,
+                                             poses.data(), huber_delta, max_iters, &st, &s, p3.data(), slots.data(),
+                                             (int)n, &count),
+                "orbx_bundle_adjust_tracks");
+  if (summary) *summary = s;
+  if (lm_status) *lm_status = st;
+  if (st != ORBX_LM_OK) return false;
+  for (int j = 0; j < count; j++) {
+    if (points) points->push_back(Point3d{p3[3 * (size_t)j], p3[3 * (size_t)j + 1], p3[3 * (size_t)j + 2]});
+    if (slot_of_point) slot_of_point->push_back(slots[(size_t)j]);
+  }
+  if (s.termination != ORBX_BA_CONVERGENCE) return true;  // :683
+  detail::ba_write_back(pose_window, poses, old, updated);
   return true;
 }
 

@@ -42,6 +42,8 @@ EXPORTS = [
     "orbx_good_features_workspace_limit", "orbx_good_features_results_device", "orbx_good_features_fetch",
     "orbx_lk_track_windows_device", "orbx_lk_windows_results_device", "orbx_lk_windows_fetch",
     "orbx_lk_workspace_limit", "orbx_lk_track_window",
+    "orbx_landmarks_build_device", "orbx_landmarks_results_device", "orbx_landmarks_fetch",
+    "orbx_bundle_adjust_landmarks_device", "orbx_bundle_adjust_landmarks_fetch", "orbx_bundle_adjust_tracks",
 ]
 
 
@@ -668,7 +670,7 @@ def _scale_methods():
 _scale_methods()
 
 
-BA_CONVERGENCE, BA_NO_CONVERGENCE, BA_FAILURE = range(3)
+BA_CONVERGENCE, BA_NO_CONVERGENCE, BA_FAILURE, BA_SKIPPED = range(4)
 BA_MAX_POSES = 8
 
 
@@ -940,6 +942,158 @@ def _lk_window_methods():
 
 
 _lk_window_methods()
+
+
+LM_OK, LM_BASELINE, LM_EMPTY, LM_BAD_POSE = range(4)
+
+
+class LandmarksView(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("pose_offset", C.c_void_p), ("point_offset", C.c_void_p),
+                ("obs_offset", C.c_void_p), ("points3", C.c_void_p), ("rows", C.c_void_p), ("obs_pose", C.c_void_p),
+                ("obs_xy", C.c_void_p), ("slot_of_point", C.c_void_p), ("slot_capacity", C.c_int32),
+                ("window_len", C.c_int32), ("n_windows", C.c_int32)]
+
+
+def _landmark_methods():
+    """Landmarks of tracked windows built on the device and bundle-adjusted there:
+    buildLandmarksFromFirstTwoFramesAndTracks + the window's solve (include/orbx.h)."""
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+
+    def _d(a, shape):
+        a = np.array(np.asarray(a, np.float64).reshape(shape), order="C")
+        return a, a.ctypes.data_as(DP)
+
+    def landmarks_build(self, K, tracks, seen, poses, n_windows=None, slot_capacity=None, window_len=None,
+                        stream=None):
+        """orbx_landmarks_build_device.  tracks: (n_windows, slots, window_len, 2) float32 and seen: (n_windows,
+        slots) int32, each a torch device tensor, a numpy array (copied to the device first) or a raw device address
+        (then n_windows, slot_capacity and window_len are required) -- e.g. the fields of lk_windows_view().  poses:
+        host, (n_windows, window_len, 6).  Asynchronous; landmarks_fetch delivers the block."""
+        import torch
+
+        uploaded = any(isinstance(a, np.ndarray) for a in (tracks, seen))
+        if isinstance(tracks, np.ndarray):
+            tracks = torch.from_numpy(np.ascontiguousarray(tracks, np.float32)).cuda()
+        if isinstance(seen, np.ndarray):
+            seen = torch.from_numpy(np.ascontiguousarray(seen, np.int32)).cuda()
+        keep = []
+        if torch.is_tensor(tracks):
+            if tracks.dtype != torch.float32 or not tracks.is_cuda or not tracks.is_contiguous() or \
+                    tracks.dim() != 4 or tracks.shape[3] != 2:
+                raise ValueError("tracks must be (n_windows, slots, window_len, 2) float32, contiguous, on the device")
+            shape = tuple(tracks.shape[:3])
+            if (n_windows, slot_capacity, window_len) not in ((None, None, None), shape):
+                raise ValueError("n_windows / slot_capacity / window_len differ from tracks.shape")
+            n_windows, slot_capacity, window_len = shape
+            keep.append(tracks)
+            tracks = tracks.data_ptr()
+        elif None in (n_windows, slot_capacity, window_len):
+            raise ValueError("a raw tracks address needs n_windows, slot_capacity and window_len")
+        if torch.is_tensor(seen):
+            if seen.dtype != torch.int32 or not seen.is_cuda or not seen.is_contiguous() or \
+                    seen.numel() != n_windows * slot_capacity:
+                raise ValueError("seen must be (n_windows, slots) int32, contiguous, on the device")
+            keep.append(seen)
+            seen = seen.data_ptr()
+        if uploaded:
+            torch.cuda.synchronize()  # the uploads above ran on torch's stream
+        self._lm_keep = keep  # kept alive until the next build
+        (K, kp) = _d(K, (3, 3))
+        (poses, pp) = _d(poses, (-1, 6))
+        if len(poses) != max(n_windows, 0) * max(window_len, 0):
+            raise ValueError("poses must be (n_windows, window_len, 6)")
+        f = self._lib.orbx_landmarks_build_device
+        f.argtypes = [C.c_void_p, DP, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, DP, C.c_void_p]
+        self._chk(f(self._h, kp, C.c_void_p(tracks), C.c_void_p(seen), n_windows, slot_capacity, window_len, pp,
+                    C.c_void_p(stream) if stream else None))
+
+    def landmarks_view(self):
+        """The device-side landmarks block of the last build (orbx_landmarks_results_device)."""
+        v = LandmarksView()
+        self._chk(self._lib.orbx_landmarks_results_device(self._h, C.byref(v)))
+        return v
+
+    def landmarks_fetch(self, first=0, n=None):
+        """Windows [first, first + n) of the last build in the format of bundle_adjust_batch: a dict of status (n),
+        pose_offset / point_offset / obs_offset (n + 1), points3 (N, 3), slot_of_point (N), obs_point / obs_pose (M)
+        and obs_xy (M, 2)."""
+        if n is None:
+            n = self.landmarks_view().n_windows - first
+        f = self._lib.orbx_landmarks_fetch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 3 + [
+            C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        npt, nob = C.c_int(0), C.c_int(0)
+        self._chk(f(self._h, first, n, None, None, None, None, None, None, 0, None, None, None, 0, C.byref(npt),
+                    C.byref(nob)))
+        N, M, m = npt.value, nob.value, max(n, 1)
+        out = dict(status=np.zeros(m, np.int32), pose_offset=np.zeros(m + 1, np.int32),
+                   point_offset=np.zeros(m + 1, np.int32), obs_offset=np.zeros(m + 1, np.int32),
+                   points3=np.zeros((N, 3)), slot_of_point=np.zeros(N, np.int32), obs_point=np.zeros(M, np.int32),
+                   obs_pose=np.zeros(M, np.int32), obs_xy=np.zeros((M, 2)))
+        p = lambda k: _ptr(out[k]) if out[k].size else None
+        self._chk(f(self._h, first, n, p("status"), p("pose_offset"), p("point_offset"), p("obs_offset"),
+                    p("points3"), p("slot_of_point"), N, p("obs_point"), p("obs_pose"), p("obs_xy"), M,
+                    C.byref(npt), C.byref(nob)))
+        return out
+
+    def bundle_adjust_landmarks(self, huber_delta=1.0, max_iters=200, stream=None):
+        """orbx_bundle_adjust_landmarks_device: solves every window of the last landmarks block.  Asynchronous;
+        bundle_adjust_landmarks_fetch delivers the results."""
+        f = self._lib.orbx_bundle_adjust_landmarks_device
+        f.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p]
+        self._chk(f(self._h, huber_delta, max_iters, C.c_void_p(stream) if stream else None))
+
+    def bundle_adjust_landmarks_fetch(self, first=0, n=None, points=True):
+        """Windows [first, first + n) of the last solve: poses (n, window_len, 6), a list of summary dicts, and the
+        points (N, 3) in the order of the block (None with points=False)."""
+        v = self.landmarks_view()
+        if n is None:
+            n = v.n_windows - first
+        m = max(n, 1)
+        poses = np.zeros((m, v.window_len, 6))
+        out = (BaSummary * m)()
+        f = self._lib.orbx_bundle_adjust_landmarks_fetch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        cnt = C.c_int(0)
+        pts = None
+        if points:
+            self._chk(f(self._h, first, n, None, None, None, 0, C.byref(cnt)))
+            pts = np.zeros((cnt.value, 3))
+        self._chk(f(self._h, first, n, _ptr(poses), C.cast(out, C.c_void_p), _ptr(pts) if points and pts.size else None,
+                    cnt.value, C.byref(cnt)))
+        return poses[:n], [out[w].as_dict() for w in range(n)], pts
+
+    def bundle_adjust_tracks(self, K, tracks, seen, poses, huber_delta=1.0, max_iters=200):
+        """orbx_bundle_adjust_tracks: one window of host tracks (slots, window_len, 2), seen (slots) and poses
+        (window_len, 6) through both stages.  Returns (poses, summary dict, landmarks status, points (N, 3),
+        slot_of_point (N))."""
+        tracks = np.ascontiguousarray(tracks, np.float32)
+        if tracks.ndim != 3 or tracks.shape[2] != 2:
+            raise ValueError("tracks must be (slots, window_len, 2) float32")
+        slots, wl = tracks.shape[:2]
+        seen = np.ascontiguousarray(seen, np.int32).reshape(-1)
+        if len(seen) != slots:
+            raise ValueError("seen must have one entry per slot")
+        (K, kp) = _d(K, (3, 3))
+        (poses, pp) = _d(poses, (-1, 6))
+        if len(poses) != wl:
+            raise ValueError("poses must be (window_len, 6)")
+        pts = np.zeros((max(slots, 1), 3))
+        sop = np.zeros(max(slots, 1), np.int32)
+        st, cnt, out = C.c_int32(-1), C.c_int(0), BaSummary()
+        f = self._lib.orbx_bundle_adjust_tracks
+        f.argtypes = [C.c_void_p, DP, C.c_void_p, C.c_void_p, C.c_int, C.c_int, DP, C.c_double, C.c_int,
+                      C.POINTER(C.c_int32), C.POINTER(BaSummary), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        self._chk(f(self._h, kp, _ptr(tracks), _ptr(seen), slots, wl, pp, huber_delta, max_iters, C.byref(st),
+                    C.byref(out), _ptr(pts), _ptr(sop), slots, C.byref(cnt)))
+        return poses, out.as_dict(), st.value, pts[:cnt.value].copy(), sop[:cnt.value].copy()
+
+    for f in (landmarks_build, landmarks_view, landmarks_fetch, bundle_adjust_landmarks,
+              bundle_adjust_landmarks_fetch, bundle_adjust_tracks):
+        setattr(Context, f.__name__, f)
+
+
+_landmark_methods()
 
 
 def chain_trajectory(T0, R, t, scale):
