@@ -735,6 +735,80 @@ int orbx_bundle_adjust_tracks(orbx_ctx* ctx, const double* K, const float* track
                               orbx_ba_summary* summary, double* points3, int32_t* slot_of_point, int capacity,
                               int* count);
 
+/* ---- next row: pose and scale of tracked frame pairs, from LK windows ------------
+ * Replaces the host side of the reference's tracking loop between the tracker and the trajectory:
+ *   the "remove lost tracks" compaction of track_optical_flow                  src/feature_tracking.cpp:166-193
+ *   get_pose on the surviving point lists                                      src/feature_tracking.cpp:222-242
+ *   get_scale on them                                                          src/feature_tracking.cpp:244-310
+ *   the same three steps in the bundle-adjustment executable                   src/with_bundle_adjustment.cpp:180-203
+ * for every consecutive frame pair of n_windows tracked windows per call, from the tracks block of
+ * orbx_lk_track_windows_device, with no host round trip.  Window w of window_len = L frames owns L - 1 pairs; the
+ * global pair index is p = w * (L - 1) + k, pair k being frames k and k + 1 of the window.  Rules (DESIGN.md §9
+ * rank 11): the list of pair k is the slots with seen >= k + 2 in ascending slot order (`seen` outside [0, L] is
+ * clamped), point 1 = tracks_xy[w][slot][k], point 2 = tracks_xy[w][slot][k + 1]; the pose is rank 5 unchanged (the
+ * same kernel, normalisation and (seed, iteration) sampling for every pair, the degenerate rule for n < 5); the
+ * points are rank 6 rule 1 with the pair's own R, t; the scale of pair k >= 1 is rank 6 rules 3 / 4 against pair
+ * k - 1 OF THE SAME WINDOW, the two lists joined on the slot (so triplets == n), triplets in ascending slot order;
+ * pair 0 of every window reports scale 1.0, 0 triplets, 0 ratios.  The join on the slot is exact where the
+ * reference aligns its two point lists by list position.  Overlapping windows of three frames
+ * (window_first[i] = i) give a stream its per-frame scales (src/feature_tracking_scale.py:127-164). */
+typedef struct {
+  double E[9], R[9], t[3];
+  int32_t inliers, good, iters, pad;
+} orbx_tracks_pose_result;
+typedef struct {
+  double scale;
+  int32_t triplets, ratios_used;
+} orbx_tracks_scale_result;
+/* Poses, triangulates and scales every pair of n_windows windows, asynchronously on the context's stream (or
+ * `stream`, a hipStream_t).  d_tracks_xy / d_seen: device memory in the layout of orbx_lk_windows_view -- they may BE
+ * that view; a call on another stream than the last windows call's waits for that call's event.  K, prob, threshold,
+ * max_iters, seed: as orbx_batch_pose_consecutive.  ORBX_ERR_INVALID_ARG: the argument rules of
+ * orbx_batch_pose_consecutive for K / prob / threshold / max_iters, any non-finite entry of K, a NULL pointer, n_windows < 1,
+ * slot_capacity < 1, window_len < 2.  ORBX_ERR_UNSUPPORTED: slot_capacity above 10224 (the join holds 16 bytes per
+ * slot in LDS), or n_windows x (window_len - 1) x slot_capacity beyond 32-bit offsets.  On any refusal nothing is
+ * launched or written, the previous block stays fetchable and the context usable.  The block is the entry's OWN
+ * (204 + 50 slot_capacity bytes per pair, scratch included): the ORB batch's matches, poses and scales, the
+ * good-features block, both LK states, the landmarks block and the state of orbx_bundle_adjust_batch stay as they
+ * are.  A caller's stream is used during the call only: later calls, fetches and orbx_destroy wait for an event
+ * recorded behind the call.  src/feature_tracking.cpp:166-193, src/feature_tracking.cpp:222-242,
+ * src/feature_tracking.cpp:244-310, src/with_bundle_adjustment.cpp:180-203 */
+int orbx_tracks_pose_device(orbx_ctx* ctx, const double* K, const float* d_tracks_xy, const int32_t* d_seen,
+                            int n_windows, int slot_capacity, int window_len, double prob, double threshold,
+                            int max_iters, uint64_t seed, void* stream);
+/* Device-side view of the last tracks-pose block (valid until the next call; written on its stream).  Every row past
+ * n[p] is 0.  src/feature_tracking.cpp:222-242, src/feature_tracking.cpp:244-310 */
+typedef struct {
+  const orbx_tracks_pose_result* pose;   /* [n_pairs] */
+  const int32_t* n;                      /* [n_pairs] correspondences of the pair */
+  const orbx_tracks_scale_result* scale; /* [n_pairs] */
+  const int32_t* slot_of;                /* [n_pairs][slot_capacity] the slot of each list position */
+  const uint8_t* mask;                   /* [n_pairs][slot_capacity] recoverPose's final mask */
+  const float* xyz;                      /* [n_pairs][slot_capacity][3] */
+  const uint8_t* valid;                  /* [n_pairs][slot_capacity] */
+  int32_t slot_capacity, window_len, n_windows, n_pairs;
+} orbx_tracks_pose_view;
+int orbx_tracks_pose_results_device(orbx_ctx* ctx, orbx_tracks_pose_view* view);
+/* Waits for the last call and copies pairs [first_pair, first_pair + n): E, R 9 doubles per pair, t 3; counts = the
+ * pairs' list lengths; any output may be NULL.  src/feature_tracking.cpp:66-93,
+ * src/with_bundle_adjustment.cpp:180-203 */
+int orbx_tracks_pose_fetch(orbx_ctx* ctx, int first_pair, int n, double* E, double* R, double* t, int32_t* inliers,
+                           int32_t* good, int32_t* iters, int32_t* counts, double* scale, int32_t* triplets,
+                           int32_t* ratios_used);
+/* One pair's lists, one entry per surviving slot in ascending slot order: the slot, recoverPose's final mask, the
+ * triangulated point and its valid byte; each array may be NULL.  *count = the pair's list length, ORBX_ERR_CAPACITY
+ * if > capacity (nothing else is written).  src/feature_tracking.cpp:182-192, src/feature_tracking.cpp:252-281 */
+int orbx_tracks_pose_pair_fetch(orbx_ctx* ctx, int pair, int32_t* slot_of, uint8_t* mask, float* xyz, uint8_t* valid,
+                                int capacity, int* count);
+/* Host convenience: ONE window of host tracks (n_slots x window_len x 2 floats) and seen (n_slots) as a batch of one;
+ * synchronous; replaces the last tracks-pose block, whose lists orbx_tracks_pose_pair_fetch then delivers.  The
+ * outputs hold window_len - 1 pairs each and may be NULL.  src/feature_tracking.cpp:166-193,
+ * src/feature_tracking.cpp:222-242, src/feature_tracking.cpp:244-310, src/with_bundle_adjustment.cpp:180-203 */
+int orbx_tracks_pose(orbx_ctx* ctx, const double* K, const float* tracks_xy, const int32_t* seen, int n_slots,
+                     int window_len, double prob, double threshold, int max_iters, uint64_t seed, double* E, double* R,
+                     double* t, int32_t* inliers, int32_t* good, int32_t* iters, int32_t* counts, double* scale,
+                     int32_t* triplets, int32_t* ratios_used);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,23 +11,6 @@ using namespace orbx_host;
 
 // ---- relative pose (next row) ---------------------------
 
-namespace {
-bool pose_args_ok(const double* K, double prob, double threshold, int max_iters) {
-  return K && K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) &&
-         std::isfinite(K[5]) && std::isfinite(prob) && std::isfinite(threshold) && threshold >= 0 && max_iters >= 0 &&
-         max_iters <= ORBX_POSE_MAX_ITERS;
-}
-void pose_unpack(const OrbxPoseOut& r, double* E, double* R, double* t, int32_t* inliers, int32_t* good,
-                 int32_t* iters) {
-  if (E) memcpy(E, r.E, sizeof r.E);
-  if (R) memcpy(R, r.R, sizeof r.R);
-  if (t) memcpy(t, r.t, sizeof r.t);
-  if (inliers) *inliers = r.inliers;
-  if (good) *good = r.good;
-  if (iters) *iters = r.iters;
-}
-}  // namespace
-
 extern "C" {
 
 int orbx_estimate_pose(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, int n, const double* K, double prob,
@@ -225,7 +208,7 @@ int orbx_batch_scale_consecutive(orbx_ctx* c, const double* K) {
                                           (const OrbxPoseOut*)c->pose.pb_out.p, K, (float*)c->scale.sb_xyz.p,
                                           (uint8_t*)c->scale.sb_valid.p, (int32_t*)c->scale.sb_mq.p, (int32_t*)c->scale.sb_mt.p,
                                           (int32_t*)c->scale.sb_n.p));
-  HIPCHK(c, orbx_launch_scale_join(s, npairs, cap, (const int32_t*)c->scale.sb_n.p, (const int32_t*)c->scale.sb_mq.p,
+  HIPCHK(c, orbx_launch_scale_join(s, npairs, npairs, cap, (const int32_t*)c->scale.sb_n.p, (const int32_t*)c->scale.sb_mq.p,
                                    (const int32_t*)c->scale.sb_mt.p, (const float*)c->scale.sb_xyz.p,
                                    (const uint8_t*)c->scale.sb_valid.p, (const OrbxPoseOut*)c->pose.pb_out.p,
                                    (OrbxScaleOut*)c->scale.sb_out.p));

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstring>
 #include <initializer_list>
 #include <string>
 #include <vector>
@@ -154,7 +156,7 @@ struct SideWork {
   }
 };
 
-// ---- the context's parts, one per subsystem (orbx_ctx::s, m, lk, lkw, pose, scale, ba, gf, lm) ----
+// ---- the context's parts, one per subsystem (orbx_ctx::s, m, lk, lkw, pose, scale, ba, gf, lm, tp) ----
 
 // stage-API scratch (grown on demand; never touched by the batched path)
 struct StageScratch {
@@ -255,6 +257,19 @@ struct Landmarks {
   }
 };
 
+// pose and scale of tracked frame pairs (orbx_tracks.hip, k_pose_ransac, k_scale_join): the normalised point lists
+// (scratch), the entry's OWN result block (poses | counts | scales | slot_of | mask | xyz | valid), and the staged
+// tracks of the one-window host entry.  Nothing here is shared with the batch pose / scale entries.
+struct TracksPose {
+  DevBuf scr, blk, stage;
+  int n = 0, cap = 0, len = 0;  // windows, slots per window, frames per window of the last call (0: none)
+  SideWork side;                // the event is recorded behind every call
+  void release() {
+    side.release();
+    free_bufs({&scr, &blk, &stage});
+  }
+};
+
 // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames (response maps | key pools | cell grids
 // | per-frame maximum and candidate count), allocated on first use and bounded by ws_limit; the staged host
 // image of the one-frame entries; and the entry's OWN result block (counts | corners), untouched by the ORB path
@@ -333,9 +348,10 @@ struct orbx_ctx {
   hipStream_t last_stream = nullptr;
 
   long long batch_serial = 0;  // bumped by every batch run
-  // The subsystems beside the batched path, each with what it owns.  They meet in four places, visible where the
+  // The subsystems beside the batched path, each with what it owns.  They meet in five places, visible where the
   // calls are made: pose reads the matcher's table, scale checks pose.match_gen against m.gen, the windows
-  // tracker waits for the good-features event, and the landmarks build waits for the windows tracker's.
+  // tracker waits for the good-features event, and the landmarks build and the tracks pose wait for the windows
+  // tracker's.
   orbx_host::StageScratch s;
   orbx_host::Matcher m;
   orbx_host::LkPair lk;
@@ -345,6 +361,7 @@ struct orbx_ctx {
   orbx_host::BundleAdjust ba;
   orbx_host::GoodFeatures gf;
   orbx_host::Landmarks lm;
+  orbx_host::TracksPose tp;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -425,6 +442,21 @@ struct FramesWhat {
 int check_device_frames(orbx_ctx* c, const void* d_frames, int n, int n_min, int n_max, int w, int h, int row_stride,
                         size_t frame_stride, const FramesWhat& what);
 bool finite_all(const double* v, int n);
+// the argument rules of every relative-pose entry (include/orbx.h, rank 5), and one pair's result taken apart
+inline bool pose_args_ok(const double* K, double prob, double threshold, int max_iters) {
+  return K && K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) &&
+         std::isfinite(K[5]) && std::isfinite(prob) && std::isfinite(threshold) && threshold >= 0 && max_iters >= 0 &&
+         max_iters <= ORBX_POSE_MAX_ITERS;
+}
+inline void pose_unpack(const OrbxPoseOut& r, double* E, double* R, double* t, int32_t* inliers, int32_t* good,
+                        int32_t* iters) {
+  if (E) memcpy(E, r.E, sizeof r.E);
+  if (R) memcpy(R, r.R, sizeof r.R);
+  if (t) memcpy(t, r.t, sizeof r.t);
+  if (inliers) *inliers = r.inliers;
+  if (good) *good = r.good;
+  if (iters) *iters = r.iters;
+}
 int gaussian_kernel(int K, float sigma, float* kernel);
 hipError_t launch_blur_auto(int impl, hipStream_t s, const OrbxPlan& P, const OrbxTileMap& tm1, const OrbxTileDesc* tiles2,
                             int ntiles2, int n, const uint8_t* src, uint8_t* dst, int first_level, int kind);

@@ -181,7 +181,8 @@ hipError_t orbx_launch_triangulate_batch(hipStream_t s, int npairs, int cap, con
                                          int32_t* d_npts);
 hipError_t orbx_launch_triangulate_host(hipStream_t s, int n, const float* d_p1, const float* d_p2, const double* K,
                                         const double* R, const double* t, float* d_xyz, uint8_t* d_valid);
-hipError_t orbx_launch_scale_join(hipStream_t s, int npairs, int cap, const int32_t* d_npts, const int32_t* d_mq,
+// chain: consecutive pairs per chain (>= 1); the first pair of every chain has no predecessor
+hipError_t orbx_launch_scale_join(hipStream_t s, int npairs, int chain, int cap, const int32_t* d_npts, const int32_t* d_mq,
                                   const int32_t* d_mt, const float* d_xyz, const uint8_t* d_valid,
                                   const OrbxPoseOut* d_pose, OrbxScaleOut* d_out);
 // a NULL valid array: every point is valid
@@ -230,6 +231,20 @@ inline int orbx_lm_blocks(int cap) { return (cap + ORBX_LM_THREADS - 1) / ORBX_L
 hipError_t orbx_launch_landmarks(hipStream_t s, const double* K9, const double* d_poses, const float* d_tracks,
                                  const int32_t* d_seen, int n_windows, int cap, int window_len, double* d_cand,
                                  uint8_t* d_keep, int32_t* d_partial, int32_t* d_gate, const OrbxLmBlock& out);
+
+// ---- pose and scale of tracked frame pairs (orbx_tracks.hip) --------------------------------
+// Window w of window_len frames owns window_len - 1 pairs, pair p = w * (window_len - 1) + k is frames k, k + 1.
+// Every per-position array has one row of `cap` = slot_capacity per pair.
+// d_tracks / d_seen: the layout of orbx_lk_windows_view.  Writes, per pair, the compacted list of the slots with
+// seen >= k + 2 in ascending slot order: d_pts (what k_pose_ransac reads), d_slot_of, d_npts; and zeroes
+// d_slot_of, d_mask, d_xyz and d_valid past the list.
+hipError_t orbx_launch_tracks_prep(hipStream_t s, int n_windows, int cap, int window_len, const float* d_tracks,
+                                   const int32_t* d_seen, const double* K, OrbxPosePt* d_pts, int32_t* d_npts,
+                                   int32_t* d_slot_of, uint8_t* d_mask, float* d_xyz, uint8_t* d_valid);
+// rank 6 rule 1 over the compacted lists, with the pair's own R, t
+hipError_t orbx_launch_tracks_triangulate(hipStream_t s, int n_windows, int cap, int window_len, const float* d_tracks,
+                                          const int32_t* d_npts, const int32_t* d_slot_of, const OrbxPoseOut* d_pose,
+                                          const double* K, float* d_xyz, uint8_t* d_valid);
 
 // ---- Shi-Tomasi corners (orbx_gftt.hip): n frames per launch, every array per frame ---------
 // d_map: w * h floats; d_max: the largest response as a bit pattern (zeroed by the caller); d_keys: `pool` =

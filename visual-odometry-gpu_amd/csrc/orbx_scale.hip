@@ -25,25 +25,6 @@ constexpr int SCALE_THREADS = 256;
 // their bit patterns order like their values)
 constexpr u64 SCALE_NO_RATIO = ~0ull;
 
-// Ordered compaction over a workgroup of SCALE_THREADS: the exclusive prefix of `has` over the workgroup's threads
-// in thread order, and the workgroup's total.  s_wave: 4 ints of LDS.  Ends with a barrier before s_wave is reused.
-__device__ __forceinline__ int block_scan_excl(int has, int* s_wave, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int incl = wave_scan_incl(has);
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < SCALE_THREADS / 64; w++) {
-    const int c = s_wave[w];
-    before += w < wave ? c : 0;
-    all += c;
-  }
-  __syncthreads();
-  *total = all;
-  return before + incl - has;
-}
-
 // Rule 3's selection: keys[0, n) in LDS hold the ratios' bit patterns (SCALE_NO_RATIO where an index contributes
 // none), r of them are ratios.  The element at sorted position r / 2 is the one with at most r / 2 keys below it
 // and more than r / 2 keys not above it; equal keys are the same double, so whichever thread finds it writes the
@@ -87,7 +68,7 @@ __global__ __launch_bounds__(SCALE_THREADS) void k_triangulate_batch(
     const int m = q < nq ? match[row + q] : -1;
     const int has = (m >= 0 && m < cap) ? 1 : 0;  // never index the next frame's slots with anything else
     int total;
-    const int pos = base + block_scan_excl(has, s_wave, &total);
+    const int pos = base + block_scan_excl<SCALE_THREADS>(has, s_wave, &total);
     if (has) s_q[pos] = q;
     base += total;
   }
@@ -128,10 +109,12 @@ __global__ __launch_bounds__(SCALE_THREADS) void k_triangulate_host(int n, const
   valid[i] = ok ? 1 : 0;
 }
 
-// One workgroup per pair p.  Pair 0 has no predecessor: scale 1.0, no triplets.  Dynamic LDS, 16 bytes per slot
+// One workgroup per pair p.  The pairs form chains of `chain` consecutive pairs (the frames of a batch: one chain of
+// all pairs; the frames of tracked windows: one chain per window).  The first pair of a chain has no predecessor:
+// scale 1.0, no triplets.  Dynamic LDS, 16 bytes per slot
 // of `cap`: [keys: cap u64 | trip_i: cap ints | trip_j: cap ints]; the inverse map (cap ints) lives in the keys'
 // space until the triplets are listed.
-__global__ __launch_bounds__(SCALE_THREADS) void k_scale_join(int cap, const int32_t* __restrict__ npts,
+__global__ __launch_bounds__(SCALE_THREADS) void k_scale_join(int cap, int chain, const int32_t* __restrict__ npts,
                                                               const int32_t* __restrict__ mq,
                                                               const int32_t* __restrict__ mt,
                                                               const float* __restrict__ xyz,
@@ -147,11 +130,11 @@ __global__ __launch_bounds__(SCALE_THREADS) void k_scale_join(int cap, const int
   __shared__ int s_used;
   __shared__ double s_median;
   const int pair = blockIdx.x, tid = threadIdx.x;
-  if (pair == 0) {
+  if (pair % chain == 0) {
     if (tid == 0) {
-      out[0].scale = 1.0;
-      out[0].triplets = 0;
-      out[0].ratios_used = 0;
+      out[pair].scale = 1.0;
+      out[pair].triplets = 0;
+      out[pair].ratios_used = 0;
     }
     return;
   }
@@ -181,7 +164,7 @@ __global__ __launch_bounds__(SCALE_THREADS) void k_scale_join(int cap, const int
     }
     const int has = i >= 0 ? 1 : 0;
     int total;
-    const int pos = nt + block_scan_excl(has, s_wave, &total);
+    const int pos = nt + block_scan_excl<SCALE_THREADS>(has, s_wave, &total);
     if (has) {
       s_ti[pos] = i;
       s_tj[pos] = j;
@@ -319,15 +302,16 @@ hipError_t orbx_launch_triangulate_host(hipStream_t s, int n, const float* d_p1,
   return hipGetLastError();
 }
 
-hipError_t orbx_launch_scale_join(hipStream_t s, int npairs, int cap, const int32_t* d_npts, const int32_t* d_mq,
+hipError_t orbx_launch_scale_join(hipStream_t s, int npairs, int chain, int cap, const int32_t* d_npts, const int32_t* d_mq,
                                   const int32_t* d_mt, const float* d_xyz, const uint8_t* d_valid,
                                   const OrbxPoseOut* d_pose, OrbxScaleOut* d_out) {
   if (npairs <= 0) return hipSuccess;
+  if (chain < 1) return hipErrorInvalidValue;
   const size_t lds = (size_t)cap * 16;
   hipError_t e = allow_lds(k_scale_join, lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_scale_join, dim3(npairs), dim3(SCALE_THREADS), lds, s, cap, d_npts, d_mq, d_mt, d_xyz, d_valid,
-                     d_pose, d_out);
+  hipLaunchKernelGGL(k_scale_join, dim3(npairs), dim3(SCALE_THREADS), lds, s, cap, chain, d_npts, d_mq, d_mt, d_xyz,
+                     d_valid, d_pose, d_out);
   return hipGetLastError();
 }
 

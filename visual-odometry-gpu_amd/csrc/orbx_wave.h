@@ -59,6 +59,27 @@ __device__ __forceinline__ int wave_scan_incl(int v) {
   return v;
 }
 
+// Ordered compaction over a workgroup of THREADS (a multiple of 64): the exclusive prefix of `has` over the
+// workgroup's threads in thread order, and the workgroup's total.  s_wave: THREADS / 64 ints of LDS.  Every thread
+// of the workgroup must call it; it ends with a barrier before s_wave is reused.
+template <int THREADS>
+__device__ __forceinline__ int block_scan_excl(int has, int* s_wave, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int incl = wave_scan_incl(has);
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < THREADS / 64; w++) {
+    const int c = s_wave[w];
+    before += w < wave ? c : 0;
+    all += c;
+  }
+  __syncthreads();
+  *total = all;
+  return before + incl - has;
+}
+
 // packed 16-bit lane arithmetic on a 32-bit register (v_pk_*_u16 / _i16)
 __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) {
   return __builtin_bit_cast(uint32_t, (us2_t)(__builtin_bit_cast(us2_t, a) + __builtin_bit_cast(us2_t, b)));

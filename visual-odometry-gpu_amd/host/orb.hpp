@@ -868,6 +868,52 @@ inline std::vector<Track> track_points_across_window_one_launch(LKTracker& lk, c
   return tracks;
 }
 
+// The motion of every consecutive frame pair of one tracked window: what the reference's
+// tracking loop computes per frame with track_optical_flow's surviving lists, get_pose and get_scale
+// (src/feature_tracking.cpp:66-93, src/with_bundle_adjustment.cpp:180-203), for the window's pairs in one call.
+// tracks / seen: what LKTracker::trackWindow returns (n x n_frames points, n counts).  Pair k is frames k, k + 1: its
+// list is the slots with seen >= k + 2 in ascending slot order.  The scale of pair k >= 1 joins its points with
+// pair k - 1's ON THE SLOT (the reference aligns them by list position, which misaligns after a lost track); pair
+// 0 has scale 1.
+struct PairMotion {
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+  double scale = 1.0;
+  std::vector<int32_t> slots;  // the surviving slots: the pair's correspondence list
+};
+inline std::vector<PairMotion> get_pose_and_scale_on_tracks(const std::vector<Point2f>& tracks,
+                                                            const std::vector<int32_t>& seen, int n_frames,
+                                                            const double K[9], double prob = 0.999,
+                                                            double threshold = 1.0, int max_iters = 1000,
+                                                            uint64_t seed = 0) {
+  if (n_frames < 2) throw std::invalid_argument("get_pose_and_scale_on_tracks: a window has at least two frames");
+  if (tracks.size() != seen.size() * (size_t)n_frames)
+    throw std::invalid_argument("get_pose_and_scale_on_tracks: tracks and seen differ in size");
+  static_assert(sizeof(Point2f) == 2 * sizeof(float), "point layout");
+  const int n = (int)seen.size(), pairs = n_frames - 1;
+  std::vector<PairMotion> out((size_t)pairs);
+  if (n == 0) return out;
+  std::vector<double> R((size_t)9 * pairs), t((size_t)3 * pairs), scale((size_t)pairs);
+  std::vector<int32_t> counts((size_t)pairs);
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_tracks_pose(c, K, reinterpret_cast<const float*>(tracks.data()), seen.data(), n, n_frames, prob,
+                                 threshold, max_iters, seed, nullptr, R.data(), t.data(), nullptr, nullptr, nullptr,
+                                 counts.data(), scale.data(), nullptr, nullptr),
+                "orbx_tracks_pose");
+  for (int p = 0; p < pairs; p++) {
+    PairMotion& m = out[(size_t)p];
+    std::memcpy(m.R, R.data() + 9 * p, sizeof m.R);
+    std::memcpy(m.t, t.data() + 3 * p, sizeof m.t);
+    m.scale = scale[(size_t)p];
+    m.slots.assign((size_t)counts[(size_t)p], 0);
+    int count = 0;
+    detail::check(c,
+                  orbx_tracks_pose_pair_fetch(c, p, m.slots.data(), nullptr, nullptr, nullptr, counts[(size_t)p], &count),
+                  "orbx_tracks_pose_pair_fetch");
+  }
+  return out;
+}
+
 // buildLandmarksFromFirstTwoFramesAndTracks (src/with_bundle_adjustment.cpp:502-575): the baseline gate
 // 0.1 .. 100 on |t0 - t1| of the world -> camera translations, triangulation of every track seen in frame 1 from
 // frames 0 / 1, the reference's depth check `X.z > 0` (on the world-frame point, as there), the track's

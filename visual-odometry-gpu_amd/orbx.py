@@ -44,6 +44,8 @@ EXPORTS = [
     "orbx_lk_workspace_limit", "orbx_lk_track_window",
     "orbx_landmarks_build_device", "orbx_landmarks_results_device", "orbx_landmarks_fetch",
     "orbx_bundle_adjust_landmarks_device", "orbx_bundle_adjust_landmarks_fetch", "orbx_bundle_adjust_tracks",
+    "orbx_tracks_pose_device", "orbx_tracks_pose_results_device", "orbx_tracks_pose_fetch",
+    "orbx_tracks_pose_pair_fetch", "orbx_tracks_pose",
 ]
 
 
@@ -1094,6 +1096,135 @@ def _landmark_methods():
 
 
 _landmark_methods()
+
+
+class TracksPoseView(C.Structure):
+    _fields_ = [("pose", C.c_void_p), ("n", C.c_void_p), ("scale", C.c_void_p), ("slot_of", C.c_void_p),
+                ("mask", C.c_void_p), ("xyz", C.c_void_p), ("valid", C.c_void_p), ("slot_capacity", C.c_int32),
+                ("window_len", C.c_int32), ("n_windows", C.c_int32), ("n_pairs", C.c_int32)]
+
+
+def _tracks_pose_methods():
+    """Pose, triangulated points and relative scale of every consecutive frame pair of tracked windows, from the
+    tracks block on the device (include/orbx.h)."""
+    DP = C.POINTER(C.c_double)
+
+    def _K(K):
+        K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))
+        return K, K.ctypes.data_as(DP)
+
+    def tracks_pose(self, K, tracks, seen=None, n_windows=None, slot_capacity=None, window_len=None, prob=0.999,
+                    threshold=1.0, max_iters=1000, seed=0, stream=None):
+        """orbx_tracks_pose_device.  tracks: an LkWindowsView (lk_windows_view(); seen and the three sizes come from
+        it), or (n_windows, slots, window_len, 2) float32 with seen (n_windows, slots) int32, each a torch device
+        tensor, a numpy array (copied to the device first) or a raw device address (then n_windows, slot_capacity and
+        window_len are required).  Asynchronous; tracks_pose_fetch / tracks_pose_pair_fetch deliver the block."""
+        import torch
+
+        if isinstance(tracks, LkWindowsView):
+            v = tracks
+            tracks, seen = v.tracks_xy, v.seen
+            n_windows, slot_capacity, window_len = v.n_windows, v.slot_capacity, v.window_len
+        uploaded = any(isinstance(a, np.ndarray) for a in (tracks, seen))
+        if isinstance(tracks, np.ndarray):
+            tracks = torch.from_numpy(np.ascontiguousarray(tracks, np.float32)).cuda()
+        if isinstance(seen, np.ndarray):
+            seen = torch.from_numpy(np.ascontiguousarray(seen, np.int32)).cuda()
+        keep = []
+        if torch.is_tensor(tracks):
+            if tracks.dtype != torch.float32 or not tracks.is_cuda or not tracks.is_contiguous() or \
+                    tracks.dim() != 4 or tracks.shape[3] != 2:
+                raise ValueError("tracks must be (n_windows, slots, window_len, 2) float32, contiguous, on the device")
+            shape = tuple(tracks.shape[:3])
+            if (n_windows, slot_capacity, window_len) not in ((None, None, None), shape):
+                raise ValueError("n_windows / slot_capacity / window_len differ from tracks.shape")
+            n_windows, slot_capacity, window_len = shape
+            keep.append(tracks)
+            tracks = tracks.data_ptr()
+        elif None in (n_windows, slot_capacity, window_len):
+            raise ValueError("a raw tracks address needs n_windows, slot_capacity and window_len")
+        if torch.is_tensor(seen):
+            if seen.dtype != torch.int32 or not seen.is_cuda or not seen.is_contiguous() or \
+                    seen.numel() != n_windows * slot_capacity:
+                raise ValueError("seen must be (n_windows, slots) int32, contiguous, on the device")
+            keep.append(seen)
+            seen = seen.data_ptr()
+        if uploaded:
+            torch.cuda.synchronize()  # the uploads above ran on torch's stream
+        self._tp_keep = keep  # kept alive until the next call
+        K, kp = _K(K)
+        f = self._lib.orbx_tracks_pose_device
+        f.argtypes = [C.c_void_p, DP, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                      C.c_int, C.c_uint64, C.c_void_p]
+        self._chk(f(self._h, kp, C.c_void_p(tracks), C.c_void_p(seen), n_windows, slot_capacity, window_len, prob,
+                    threshold, max_iters, seed, C.c_void_p(stream) if stream else None))
+
+    def tracks_pose_view(self):
+        """The device-side block of the last tracks_pose (orbx_tracks_pose_results_device)."""
+        v = TracksPoseView()
+        self._chk(self._lib.orbx_tracks_pose_results_device(self._h, C.byref(v)))
+        return v
+
+    def _fetch_arrays(m):
+        return dict(E=np.zeros((m, 3, 3)), R=np.zeros((m, 3, 3)), t=np.zeros((m, 3)), inliers=np.zeros(m, np.int32),
+                    good=np.zeros(m, np.int32), iters=np.zeros(m, np.int32), n=np.zeros(m, np.int32),
+                    scale=np.zeros(m), triplets=np.zeros(m, np.int32), ratios_used=np.zeros(m, np.int32))
+
+    _ORDER = ("E", "R", "t", "inliers", "good", "iters", "n", "scale", "triplets", "ratios_used")
+
+    def tracks_pose_fetch(self, first=0, n=None):
+        """Pairs [first, first + n) of the last tracks_pose (pair p = w * (window_len - 1) + k): dict of E, R
+        (n, 3, 3), t (n, 3), inliers, good, iters, n (the list lengths), scale, triplets, ratios_used."""
+        if n is None:
+            n = self.tracks_pose_view().n_pairs - first
+        out = _fetch_arrays(max(n, 0))
+        f = self._lib.orbx_tracks_pose_fetch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10
+        self._chk(f(self._h, first, n, *[_ptr(out[k]) for k in _ORDER]))
+        return out
+
+    def tracks_pose_pair_fetch(self, pair, capacity=None):
+        """The lists of one pair, one entry per surviving slot in ascending slot order: dict of slot_of (n,) int32,
+        mask (n,) uint8, xyz (n, 3) float32, valid (n,) uint8.  capacity=None: sized from the pair's count."""
+        f = self._lib.orbx_tracks_pose_pair_fetch
+        f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.POINTER(C.c_int)]
+        cnt = C.c_int(0)
+        if capacity is None:
+            st = f(self._h, pair, None, None, None, None, 0, C.byref(cnt))
+            if st not in (OK, ERR_CAPACITY):
+                self._chk(st)
+            capacity = cnt.value
+        m = max(capacity, 1)
+        slot_of, mask = np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        xyz, valid = np.zeros((m, 3), np.float32), np.zeros(m, np.uint8)
+        self._chk(f(self._h, pair, _ptr(slot_of), _ptr(mask), _ptr(xyz), _ptr(valid), capacity, C.byref(cnt)))
+        k = cnt.value
+        return {"slot_of": slot_of[:k], "mask": mask[:k], "xyz": xyz[:k], "valid": valid[:k]}
+
+    def tracks_pose_window(self, K, tracks, seen, prob=0.999, threshold=1.0, max_iters=1000, seed=0):
+        """orbx_tracks_pose: one window of host tracks (slots, window_len, 2) and seen (slots).  Returns the dict of
+        tracks_pose_fetch for the window's window_len - 1 pairs; tracks_pose_pair_fetch delivers their lists."""
+        tracks = np.ascontiguousarray(tracks, np.float32)
+        if tracks.ndim != 3 or tracks.shape[2] != 2:
+            raise ValueError("tracks must be (slots, window_len, 2) float32")
+        slots, wl = tracks.shape[:2]
+        seen = np.ascontiguousarray(seen, np.int32).reshape(-1)
+        if len(seen) != slots:
+            raise ValueError("seen must have one entry per slot")
+        K, kp = _K(K)
+        out = _fetch_arrays(max(wl - 1, 0))
+        f = self._lib.orbx_tracks_pose
+        f.argtypes = [C.c_void_p, DP, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                      C.c_uint64] + [C.c_void_p] * 10
+        self._chk(f(self._h, kp, _ptr(tracks), _ptr(seen), slots, wl, prob, threshold, max_iters, seed,
+                    *[_ptr(out[k]) for k in _ORDER]))
+        return out
+
+    for f in (tracks_pose, tracks_pose_view, tracks_pose_fetch, tracks_pose_pair_fetch, tracks_pose_window):
+        setattr(Context, f.__name__, f)
+
+
+_tracks_pose_methods()
 
 
 def chain_trajectory(T0, R, t, scale):
