@@ -258,6 +258,12 @@ int orbx_set_top_rows_first(orbx_ctx* ctx, int mode);
  * levels are filled: the padding bytes of its levels are the one thing in the pools that has to stay zero. */
 int orbx_debug_fill_pools(orbx_ctx* ctx, int byte);
 
+/* DEBUG entry, for tests only: reads back one level of one frame of the blurred pyramid of the current lane -- what
+ * the last whole-path batch left in its pool -- after waiting for everything in flight: level_w x level_h bytes of the
+ * current frame size's plan, rows packed, into `out` (`out_bytes` >= level_w * level_h).  Rows that the top-rows-first
+ * pipeline did not produce hold whatever the pool held before the batch. */
+int orbx_debug_read_pyramid_level(orbx_ctx* ctx, int frame, int level, uint8_t* out, size_t out_bytes);
+
 /* Pipelined batches (default off).  With enable = 1, consecutive orbx_detect_and_compute_batch_device calls on the
  * context's own stream (stream = NULL) alternate between two LANES -- each with its own stream and its own working
  * pools; batch k uses the lane of its result block -- so the kernels of one batch overlap the tails and the nearly

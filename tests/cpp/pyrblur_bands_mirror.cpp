@@ -1,0 +1,177 @@
+// pyrblur_bands_mirror.cpp -- host-only restatement of the row bookkeeping of k_pyrblur (csrc/orbx_blur.hip), checked
+// against a straightforward per-row computation over the strip tables the library itself builds (csrc/orbx_plan.h).
+// Test infrastructure only; no GPU.
+//
+//   pyrblur_bands_mirror bands W H SCALE NLEVELS TOP_ROWS
+//       the first-pass table of a W x H frame: per level "level <l> <w> <h> <first-pass rows> <band heights...>", and
+//       "whole <entries of the every-row table>" (tests/test_pyrblur_bands.py asserts its shapes on these lines)
+//   pyrblur_bands_mirror sweep
+//       every level of every frame height 8 .. 400 at scales 1.1, 1.2 and 1.41, every band of the every-row, first-pass
+//       and second-pass tables:
+//         * the y taps of a band's input rows sit one per lane: every request of the row loop (groups of five rows,
+//           rows past the band clamped) must find the tap of ITS level row in a lane 0 .. 63;
+//         * "same source row": the kernel's carried flag -- the CLAMPED upper source row of a request equals the
+//           clamped lower source row of the request before it, false on the first row of a band -- is set exactly
+//           where the per-row computation says the two rows are the same source row (also where REFLECT_101 turns the
+//           order of the level rows round, and at the source's last row); counted per level for the levels resized
+//           through the 8-byte window (scale <= 2).
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../visual-odometry-gpu_amd/csrc/orbx_plan.h"
+
+using namespace orbx_geom;
+
+namespace {
+
+orbx_params params_for(float scale, int nlevels, int W, int H) {
+  orbx_params p{};
+  p.nfeatures = 500;
+  p.scale_factor = scale;
+  p.nlevels = nlevels;
+  p.threshold = 20;
+  p.n = 9;
+  p.nms_window = 3;
+  p.patch_size = 31;
+  p.harris_window = 7;
+  p.harris_k = 0.04f;
+  p.select_mode = ORBX_SELECT_HARRIS;
+  p.blur_levels = ORBX_BLUR_ALL;
+  p.blur_kind = ORBX_BLUR_SEP16;
+  p.max_width = W;
+  p.max_height = H;
+  p.max_batch = 1;
+  return p;
+}
+
+int reflect101(int p, int len) {
+  p = p < 0 ? -p : p;
+  return p >= len ? 2 * len - p - 2 : p;
+}
+
+// source row of level row dy (make_taps, orbx_api.cpp: OpenCV's row index before clipping)
+int ytap_ofs(int dy, int lh, int h0) {
+  const double scale_y = 1. / ((double)lh / h0);
+  const float fy = (float)((dy + 0.5) * scale_y - 0.5);
+  return (int)std::floor(fy);
+}
+
+struct Counts {
+  long long bands = 0, requests = 0, rows = 0, reused = 0, failures = 0;
+};
+
+// one band [y0, y0 + f) of a level of lh rows (source: h0 rows), the kernel's way
+void walk_band(int y0, int f, int lh, int h0, bool count_reuse, Counts* c) {
+  const int yend = std::min(y0 + f, lh), nr = yend - y0 + 4;
+  int lane_row[64];  // lane i: the LEVEL row whose tap it holds (k_pyrblur: one vector load per strip)
+  for (int lane = 0; lane < 64; lane++) lane_row[lane] = reflect101(y0 - 2 + std::min(lane, yend - y0 + 5), lh);
+  int prev_sy1 = -1;  // the kernel's carried row: clamped lower source row of the previous request
+  auto issue = [&](int r) {
+    const int rr = std::min(r, nr + 1);
+    const int lane = rr;  // pyr_issue: v_readlane of lane r
+    const int want = reflect101(y0 - 2 + rr, lh);  // per row
+    c->requests++;
+    if (lane < 0 || lane > 63 || lane_row[lane] != want) {
+      if (c->failures++ < 8)
+        std::printf("FAIL tap lane: lh=%d h0=%d band=[%d,%d) row=%d lane=%d\n", lh, h0, y0, yend, r, lane);
+      return;
+    }
+    if (!count_reuse) return;
+    const int ofs = ytap_ofs(lane_row[lane], lh, h0);
+    const int sy0 = std::min(std::max(ofs, 0), h0 - 1), sy1 = std::min(std::max(ofs + 1, 0), h0 - 1);
+    const bool flag = prev_sy1 >= 0 && sy0 == prev_sy1;  // the predicate: clamped indices, false on a band's first row
+    // per row: the previous request's level row is one above this one and its lower source row is this row's upper one
+    const int prev_rr = std::min(r - 1, nr + 1);
+    bool expect = false;
+    if (r > 0) {
+      const int pofs = ytap_ofs(reflect101(y0 - 2 + prev_rr, lh), lh, h0);
+      expect = std::min(std::max(pofs + 1, 0), h0 - 1) == sy0;
+    }
+    if (flag != expect && c->failures++ < 8)
+      std::printf("FAIL reuse flag: lh=%d h0=%d band=[%d,%d) row=%d\n", lh, h0, y0, yend, r);
+    c->rows++;
+    c->reused += flag ? 1 : 0;
+    prev_sy1 = sy1;
+  };
+  c->bands++;
+  for (int rb = 0; rb < nr; rb += 5)
+    for (int k = 0; k < 5; k++) issue(rb + k);
+}
+
+int cmd_bands(int W, int H, float scale, int nlevels, int top) {
+  const orbx_params p = params_for(scale, nlevels, W, H);
+  OrbxPlan P;
+  OrbxBandMap bm;
+  std::string why;
+  if (build_plan(p, W, H, &P, &why, 4) != ORBX_OK || make_bandmap(P, p.nms_window / 2, &bm, &why, true, nullptr) != ORBX_OK) {
+    std::printf("error %s\n", why.c_str());
+    return 2;
+  }
+  std::vector<OrbxTileDesc> t;
+  std::printf("whole %zu\n", build_pyrblur_tiles(P, ORBX_PYRBLUR_RH, nullptr));
+  std::printf("fast_tile_rows %d\n", bm.nbands);
+  build_pyrblur_tiles(P, ORBX_PYRBLUR_RH, &t, false, 1, &bm, top);
+  for (int l = 0; l < P.nlevels; l++) {
+    std::printf("level %d %d %d %d", l, P.L[l].w, P.L[l].h, pyrblur_first_pass_rows(P, bm, l, top));
+    for (const OrbxTileDesc& d : t)
+      if ((int)d.l == l && d.tx == 0) std::printf(" %d", (int)d.f);
+    std::printf("\n");
+  }
+  return 0;
+}
+
+int cmd_sweep() {
+  Counts c;
+  const float scales[3] = {1.1f, 1.2f, 1.41f};
+  const int W = 500, top = 2;
+  for (float scale : scales) {
+    long long rows[ORBX_MAX_LEVELS] = {}, reused[ORBX_MAX_LEVELS] = {};
+    for (int H = 8; H <= 400; H++) {
+      int nlevels = 8;
+      OrbxPlan P;
+      OrbxBandMap bm;
+      std::string why;
+      // (as many of the 8 levels as the height has: a level below 8 rows is refused)
+      while (nlevels > 1 && build_plan(params_for(scale, nlevels, W, H), W, H, &P, &why, 4) != ORBX_OK) nlevels--;
+      if (build_plan(params_for(scale, nlevels, W, H), W, H, &P, &why, 4) != ORBX_OK ||
+          make_bandmap(P, 1, &bm, &why, true, nullptr) != ORBX_OK) {
+        std::printf("FAIL plan %dx%d scale %.2f: %s\n", W, H, (double)scale, why.c_str());
+        c.failures++;
+        continue;
+      }
+      std::vector<OrbxTileDesc> t;
+      for (int part = 0; part < 3; part++) {
+        build_pyrblur_tiles(P, ORBX_PYRBLUR_RH, &t, false, part, &bm, top);
+        for (const OrbxTileDesc& d : t) {
+          if (d.tx != 0 || d.l == 0) continue;  // (the rows of a band are the same in every strip; level 0 has no taps)
+          Counts one;
+          const bool window_level = level_scale(scale, (int)d.l) <= 2.0f;
+          walk_band(d.ty, d.f, P.L[d.l].h, H, window_level, &one);
+          c.bands += one.bands, c.requests += one.requests, c.failures += one.failures;
+          if (part == 1) rows[d.l] += one.rows, reused[d.l] += one.reused;
+        }
+      }
+    }
+    for (int l = 1; l < 8; l++)
+      if (rows[l])
+        std::printf("scale %.2f level %d (x%.3f): %lld of %lld first-pass input rows share a source row with the row above (%.1f %%)\n",
+                    (double)scale, l, (double)level_scale(scale, l), reused[l], rows[l], 100.0 * (double)reused[l] / (double)rows[l]);
+  }
+  std::printf("%lld bands, %lld row requests, %lld failures\n", c.bands, c.requests, c.failures);
+  return c.failures ? 1 : 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc == 7 && !std::strcmp(argv[1], "bands"))
+    return cmd_bands(std::atoi(argv[2]), std::atoi(argv[3]), (float)std::atof(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]));
+  if (argc == 2 && !std::strcmp(argv[1], "sweep")) return cmd_sweep();
+  std::fprintf(stderr, "usage: %s bands W H SCALE NLEVELS TOP_ROWS | sweep\n", argv[0]);
+  return 2;
+}

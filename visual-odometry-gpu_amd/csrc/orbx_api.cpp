@@ -1115,6 +1115,23 @@ int orbx_debug_fill_pools(orbx_ctx* c, int byte) {
   return ORBX_OK;
 }
 
+// Debug entry (tests): one level of one frame of the current lane's blurred pyramid, rows packed.
+int orbx_debug_read_pyramid_level(orbx_ctx* c, int frame, int level, uint8_t* out, size_t out_bytes) {
+  DeviceGuard _dg(c);
+  if (!c || !out) return ORBX_ERR_INVALID_ARG;
+  if (c->plan_w == 0 || !cur_lane(c).d_pyr_blur) return fail(c, ORBX_ERR_INVALID_ARG, "run a batch first");
+  if (frame < 0 || frame >= c->p.max_batch || level < 0 || level >= c->plan.nlevels)
+    return fail(c, ORBX_ERR_INVALID_ARG, "frame or level out of range");
+  const OrbxLevel& V = c->plan.L[level];
+  if (out_bytes < (size_t)V.w * (size_t)V.h) return fail(c, ORBX_ERR_INVALID_ARG, "out_bytes below level_w * level_h");
+  if (c->last_stream) HIPCHK(c, hipStreamSynchronize(c->last_stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, lanes_sync(c));
+  HIPCHK(c, hipMemcpy2D(out, (size_t)V.w, cur_lane(c).d_pyr_blur + (size_t)frame * (size_t)c->plan.frame_bytes + (size_t)V.img_off,
+                        (size_t)V.pitch, (size_t)V.w, (size_t)V.h, hipMemcpyDeviceToHost));
+  return ORBX_OK;
+}
+
 int orbx_set_fast_early_exit(orbx_ctx* c, int enable) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;

@@ -422,13 +422,18 @@ template <int MODE>
 struct PyrRaw {
   uint32_t q0[MODE == 0 ? 1 : MODE == 1 ? 2 : 4], q1[MODE == 0 ? 1 : MODE == 1 ? 2 : 4];
   int b0, b1;
+  // window mode: the row's upper source row is the lower source row of the row requested before it (wave-uniform;
+  // at a scale s <= 2 that holds for about 2 - s of the rows): its window is not loaded, and pyr_finish_window takes
+  // the horizontal results the previous row left behind
+  bool same;
 };
 
 // issue the loads of input row r of the strip (level row yl = reflect(y0 - 2 + r)).  The row offsets are
 // scalars (buffer loads: frame descriptor + scalar row offset + the lane's constant byte offset), no
 // 64-bit per-lane address arithmetic.
 template <int MODE>
-__device__ __forceinline__ void pyr_issue(const PyrSrc& P, const PyrLane& T, int r, int yl, PyrRaw<MODE>& R) {
+__device__ __forceinline__ void pyr_issue(const PyrSrc& P, const PyrLane& T, int r, int yl, PyrRaw<MODE>& R, int& last_sy1) {
+  R.same = false;
   if (MODE == 0) {
     const int nvalid = P.w - P.x;
     uint32_t v = 0;
@@ -452,10 +457,16 @@ __device__ __forceinline__ void pyr_issue(const PyrSrc& P, const PyrLane& T, int
   R.b1 = (int)(tcc >> 16);
   if (MODE == 1) {
     typedef uint32_t v2u __attribute__((ext_vector_type(2)));
-    const v2u a = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(P.rsrc, T.base, so0, 0));
+    // the CLAMPED source rows are compared, so the flag is right wherever the rows come from: at the first row of a
+    // band (nothing before it), where REFLECT_101 turns the order of the level rows round, at the source's last row
+    R.same = sy0 == last_sy1;
+    last_sy1 = sy1;
+    if (!R.same) {
+      const v2u a = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(P.rsrc, T.base, so0, 0));
+      R.q0[0] = a.x;
+      R.q0[1] = a.y;
+    }
     const v2u b = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(P.rsrc, T.base, so1, 0));
-    R.q0[0] = a.x;
-    R.q0[1] = a.y;
     R.q1[0] = b.x;
     R.q1[1] = b.y;
   } else if (MODE == 3) {
@@ -510,6 +521,38 @@ __device__ __forceinline__ void pyr_stage(const PyrSrc& P, const PyrRaw<3>& R, u
   }
   wave_lds_sync();
 }
+// window mode: OpenCV's fixed-point resize does its horizontal pass per SOURCE row, so the masked horizontal result
+// r & 0xfffff0 of a source row is the same number whichever output row asks for it.  `carry` holds the four results
+// of the previous row's lower source row; where that is this row's upper one (R.same) they are taken over instead of
+// being computed again: a v_perm, a v_dot2 and a v_and less per pixel, and the row's upper window was never loaded.
+__device__ __forceinline__ uint32_t pyr_finish_window(const PyrLane& T, const PyrRaw<1>& R, uint32_t (&carry)[4]) {
+  const uint32_t bs0 = ((uint32_t)R.b0 << 12) & 0xffffffu, bs1 = ((uint32_t)R.b1 << 12) & 0xffffffu;  // b <= 2048
+  uint32_t m0[4];
+  if (R.same) {  // wave-uniform
+#pragma unroll
+    for (int k = 0; k < 4; k++) m0[k] = carry[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t p0 = __builtin_amdgcn_perm(R.q0[1], R.q0[0], T.sel[k]);
+      m0[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, p0), __builtin_bit_cast(us2_t, T.cc[k]), 0u, false) & 0xfffff0u;
+    }
+  }
+  uint32_t out = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t p1 = __builtin_amdgcn_perm(R.q1[1], R.q1[0], T.sel[k]);
+    const uint32_t m1 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, p1), __builtin_bit_cast(us2_t, T.cc[k]), 0u, false) & 0xfffff0u;
+    // (a carried value is below 2^24 like a fresh one, which the compiler cannot see through the row loop: written
+    // as a 64-bit product it becomes a quarter-rate v_mul_hi_u32)
+    uint32_t t0;
+    asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(t0) : "s"(bs0), "v"(m0[k]));
+    const uint32_t t1 = (uint32_t)(((u64)m1 * (u64)bs1) >> 32);
+    out |= ((t0 + t1 + 2u) >> 2) << (8 * k);
+    carry[k] = m1;
+  }
+  return out;
+}
 template <int MODE>
 __device__ __forceinline__ uint32_t pyr_finish(const PyrLane& T, const PyrRaw<MODE>& R, uint8_t* stage = nullptr) {
   if (MODE == 0) return R.q0[0];
@@ -520,10 +563,7 @@ __device__ __forceinline__ uint32_t pyr_finish(const PyrLane& T, const PyrRaw<MO
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     uint32_t p0, p1;  // the pixel pair as two u16 lanes
-    if (MODE == 1) {
-      p0 = __builtin_amdgcn_perm(R.q0[1], R.q0[0], T.sel[k]);
-      p1 = __builtin_amdgcn_perm(R.q1[1], R.q1[0], T.sel[k]);
-    } else if (MODE == 3) {  // the pair's two aligned dwords of each staged row, the pair cut out by v_perm
+    if (MODE == 3) {  // (window mode: pyr_finish_window)  the pair's two aligned dwords of each staged row, the pair cut out by v_perm
       // (an unaligned 16-bit LDS read per pair is legal on gfx950 and took 4x the LDS time)
       // (the four selectors of a lane travel as 4-bit fields of ONE register, sel_k = 0x0c000c00 | ((sel[0] >> 4 k) &
       // 0x00070003): the kernel has no registers to spare, and spilling them costs more than the unpacking)
@@ -553,13 +593,15 @@ __device__ __forceinline__ uint32_t pyr_finish(const PyrLane& T, const PyrRaw<MO
 template <int MODE, bool PATCH>
 __device__ __forceinline__ void pyrblur_strip(const Blur3Strip& S, const PyrSrc& P, const PyrLane& T,
                                               uint8_t* stage = nullptr) {
-  // Loads in flight per wave: the five rows of a group (modes 0 and 1: <= 4 registers per row), or the
-  // next row only (pair-gather mode: 8 registers per row).  With <= 64 registers the kernel keeps 8
+  // Loads in flight per wave: the five rows of a group (level 0: one register per row), four of them (window mode: 4
+  // registers per row), or the next row only (pair-gather mode: 8 registers per row).  With <= 64 registers the kernel keeps 8
   // waves per SIMD, i.e. ALL waves of a 64-frame KITTI batch are resident at once (7.4 per SIMD): at
   // 6 per SIMD the second, partly filled round of waves cost 40 % (100 us instead of 70).
   // (staged mode: the next row only as well, and its registers are free again once they are in LDS)
   constexpr bool ROWWISE = MODE == 2 || MODE == 3;
-  constexpr int NB = MODE == 3 ? 1 : MODE == 2 ? 2 : 5;
+  // (window mode: four rows of a group up front, the fifth into the first one's registers once that row is finished --
+  // the four registers this frees hold the horizontal results carried from row to row, see pyr_finish_window)
+  constexpr int NB = MODE == 3 ? 1 : MODE == 2 ? 2 : MODE == 1 ? 4 : 5;
   const uint32_t k4 = pk_opaque(0x00040004u), k6 = pk_opaque(0x00060006u);
   uint32_t he[5], ho[5];
   PyrRaw<MODE> raw[NB];
@@ -570,9 +612,11 @@ __device__ __forceinline__ void pyrblur_strip(const Blur3Strip& S, const PyrSrc&
   // input row r of the strip is level row y0 - 2 + r; output row y0 + r - 4 is complete after row r
   const int nr = S.yend - S.y0 + 4;  // input rows
   // (rows past the strip, in the last group, are computed from clamped indices and never stored)
+  int last_sy1 = -1;    // window mode: lower source row of the row requested last (rows are requested in order) ...
+  uint32_t carry[4];    // ... and its masked horizontal results, left by the row finished last (finished in order too)
   auto issue = [&](int r, PyrRaw<MODE>& R) {
     const int rr = min(r, nr + 1);
-    pyr_issue<MODE>(P, T, rr, reflect101_s(S.y0 - 2 + rr, S.h), R);
+    pyr_issue<MODE>(P, T, rr, reflect101_s(S.y0 - 2 + rr, S.h), R, last_sy1);
   };
   auto hpass = [&](int rb, int k) {
     if (MODE == 3) {
@@ -588,6 +632,12 @@ __device__ __forceinline__ void pyrblur_strip(const Blur3Strip& S, const PyrSrc&
       return;
     }
     if (MODE == 2 && k < 4) issue(rb + k + 1, raw[(k + 1) & 1]);
+    if constexpr (MODE == 1) {
+      const uint32_t row = pyr_finish_window(T, raw[k & 3], carry);
+      if (k == 0) issue(rb + 4, raw[0]);
+      blur3_h<PATCH>(S, row, 0u, k4, k6, he[k], ho[k]);
+      return;
+    }
     blur3_h<PATCH>(S, pyr_finish<MODE>(T, raw[MODE == 2 ? (k & 1) : MODE == 3 ? 0 : k], stage), 0u, k4, k6, he[k], ho[k]);
   };
   auto fetch_group = [&](int rb) {
@@ -595,7 +645,7 @@ __device__ __forceinline__ void pyrblur_strip(const Blur3Strip& S, const PyrSrc&
       issue(rb, raw[0]);
     } else {
 #pragma unroll
-      for (int k = 0; k < 5; k++) issue(rb + k, raw[ROWWISE ? 0 : k]);
+      for (int k = 0; k < NB; k++) issue(rb + k, raw[ROWWISE ? 0 : k]);
     }
   };
   fetch_group(0);

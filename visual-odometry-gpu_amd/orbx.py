@@ -37,6 +37,7 @@ EXPORTS = [
     "orbx_estimate_pose", "orbx_batch_pose_consecutive", "orbx_batch_pose_fetch", "orbx_batch_pose_mask",
     "orbx_triangulate", "orbx_estimate_scale", "orbx_batch_scale_consecutive", "orbx_batch_scale_fetch",
     "orbx_batch_points_fetch", "orbx_chain_trajectory", "orbx_debug_fill_pools",
+    "orbx_debug_read_pyramid_level",
     "orbx_bundle_adjust", "orbx_bundle_adjust_batch",
     "orbx_corner_min_eigen_val", "orbx_good_features_to_track", "orbx_good_features_batch_device",
     "orbx_good_features_workspace_limit", "orbx_good_features_results_device", "orbx_good_features_fetch",
@@ -322,6 +323,14 @@ class Context:
     def debug_fill_pools(self, byte):
         """DEBUG (tests): fill the working pools of both lanes with `byte` (orbx_debug_fill_pools)."""
         self._chk(self._lib.orbx_debug_fill_pools(self._h, int(byte)))
+
+    def debug_read_pyramid_level(self, frame, level, width, height):
+        """DEBUG (tests): level `level` of frame `frame` of the current lane's blurred pyramid, as left by the last
+        whole-path batch of width x height frames (orbx_debug_read_pyramid_level)."""
+        plan = self.plan(width, height)
+        out = np.zeros((int(plan["level_h"][level]), int(plan["level_w"][level])), np.uint8)
+        self._chk(self._lib.orbx_debug_read_pyramid_level(self._h, int(frame), int(level), _ptr(out), C.c_size_t(out.size)))
+        return out
 
     def lk_track(self, prev, nxt, pts, win=21, max_level=3, max_iters=30, epsilon=0.01):
         """cv::calcOpticalFlowPyrLK(prev, next, pts, ...) as called at feature_tracking.cpp:175-181.
