@@ -815,6 +815,85 @@ int orbx_tracks_pose(orbx_ctx* ctx, const double* K, const float* tracks_xy, con
                      double* t, int32_t* inliers, int32_t* good, int32_t* iters, int32_t* counts, double* scale,
                      int32_t* triplets, int32_t* ratios_used);
 
+/* ---- next row: masked Shi-Tomasi detection that tops up tracked points ----
+ * Replaces, for a tracker whose windows chain on the device,
+ *   the fresh cv::goodFeaturesToTrack that is the BA flavour's only source of points when it has no observations
+ *                                                                          src/with_bundle_adjustment.cpp:586-593
+ *   the re-detection the streaming flavour falls back to when fewer than 150 tracks survive (there: ORB plus the
+ *   matcher, which stays out)                                              src/feature_tracking.cpp:68-71
+ * with what KLT front-ends call goodFeaturesToTrack(img, n_max - n_alive, q, d, mask): the live tracks are carried,
+ * new corners are appended, and no new corner is closer than min_distance to a carried point.  Rules (DESIGN.md §9
+ * rank 12, A-F; tests/gftt_topup_ref.py restates them, results are bit-identical):
+ *   seeds    slot s of frame f is live iff d_seed_seen == NULL or d_seed_seen[f][s] >= seen_min, and usable iff both
+ *            floats are finite, 0 <= x <= width - 1 and 0 <= y <= height - 1 (float compares); others are dropped
+ *   carry    the usable seeds of a frame, float bits unchanged, in ascending slot order, at most max_corners of them:
+ *            carried[f] points at the front of the frame's output, origin = their seed slot
+ *   blocked  (min_distance >= 1) an integer pixel (X, Y) with fadd(fmul(dx, dx), fmul(dy, dy)) < (float)(d * d) for
+ *            some carried seed, dx = (float)X - sx, dy = (float)Y - sy; for the mask entry: a mask byte of 0
+ *   detect   rules 1-6 of rank 8 with the maximum of rule 2 taken over the pixels that are not blocked (OpenCV's
+ *            minMaxLoc with a mask) and blocked pixels no candidates (their values still count in a neighbour's 3x3
+ *            maximum); at most max_corners - carried[f] new corners follow the carried points, origin -1
+ * counts[f] = carried[f] + new corners; slots at or beyond counts[f] are 0 with origin -1: whole arrays compare equal.
+ * min_distance above ORBX_GFTT_TOPUP_MAX_MIN_DISTANCE is ORBX_ERR_UNSUPPORTED (the work per seed is (2R + 2)^2 pixels,
+ * R = ceil(min_distance)). */
+#define ORBX_GFTT_TOPUP_MAX_MIN_DISTANCE 64.0
+/* The top-up of `n` frames in device memory (src/with_bundle_adjustment.cpp:586-593, src/feature_tracking.cpp:68-71),
+ * asynchronously on the context's stream (or `stream`).  Frame, stride, alignment and stream rules are those of
+ * orbx_good_features_batch_device; quality_level and min_distance are checked as there, plus the bound above.
+ * max_corners >= 1, seed_capacity >= 1; d_seed_xy is 4-byte aligned, slot s of frame f at
+ * d_seed_xy + f * seed_frame_stride + s * seed_point_stride (strides in floats; seed_point_stride >= 2,
+ * seed_frame_stride >= (seed_capacity - 1) * seed_point_stride + 2); d_seed_seen is [n][seed_capacity] or NULL.  A
+ * d_seed_xy inside the top-up's own result block is ORBX_ERR_INVALID_ARG.  On any error nothing is written, the
+ * previous top-up result stays fetchable and the context usable.
+ * With the view of orbx_lk_windows_results_device: d_seed_xy = tracks_xy + 2 * (window_len - 1), seed_point_stride =
+ * 2 * window_len, seed_frame_stride = 2 * window_len * slot_capacity, d_seed_seen = seen, seen_min = window_len, and
+ * d_frames / frame_stride picking each window's last frame; points_xy and counts of the result go into the next
+ * orbx_lk_track_windows_device, origin joins its slots to the previous window's.  The plain good-features view is
+ * an equally valid seed source.
+ * The results go to a block of their OWN (slot_capacity = max_corners): the ORB batch, the plain good-features
+ * block, the LK windows block and orbx_lk_track's state stay as they are.  Workspace: the good-features workspace
+ * (its size and the slicing of the plain entries unchanged) plus one bit per pixel -- 4 * ceil(width / 32) * height
+ * bytes per frame of a slice --, allocated beside it for the same number of frames at the first top-up or masked call
+ * and freed with it; results do not depend on the slicing. */
+int orbx_good_features_topup_device(orbx_ctx* ctx, const void* d_frames, int n, int width, int height, int row_stride,
+                                    size_t frame_stride, const float* d_seed_xy, size_t seed_point_stride,
+                                    size_t seed_frame_stride, const int32_t* d_seed_seen, int seen_min,
+                                    int seed_capacity, int max_corners, double quality_level, double min_distance,
+                                    void* stream);
+/* Device-side view of the last top-up's results (src/with_bundle_adjustment.cpp:586-593), valid until the next
+ * top-up or masked call; written on that call's stream. */
+typedef struct {
+  const int32_t* counts;   /* [n] */
+  const int32_t* carried;  /* [n] */
+  const float* points_xy;  /* [n][slot_capacity][2] */
+  const int32_t* origin;   /* [n][slot_capacity] */
+  int32_t slot_capacity;
+  int32_t n;
+} orbx_good_features_topup_view;
+/* Fills the view; ORBX_ERR_INVALID_ARG before any top-up.  src/with_bundle_adjustment.cpp:586-593 */
+int orbx_good_features_topup_results_device(orbx_ctx* ctx, orbx_good_features_topup_view* view);
+/* Waits for the last top-up and copies frames [first, first + n): counts and carried (n entries), points_xy
+ * (n x slot_capacity x 2 floats) and origin (n x slot_capacity); all but counts may be NULL.
+ * src/with_bundle_adjustment.cpp:586-593 */
+int orbx_good_features_topup_fetch(orbx_ctx* ctx, int first, int n, int32_t* counts, int32_t* carried,
+                                   float* points_xy, int32_t* origin);
+/* The top-up of one host image from n_seeds host points (n_seeds >= 0; every seed is live), synchronous
+ * (src/feature_tracking.cpp:68-71).  *count = carried + new points, *carried = points carried; if *count exceeds
+ * `capacity`, ORBX_ERR_CAPACITY is returned, *count is the capacity required and nothing else is written.  Runs as
+ * a top-up of one frame: it replaces the results of the last top-up. */
+int orbx_good_features_topup(orbx_ctx* ctx, const uint8_t* image, int width, int height, int stride,
+                             const float* seeds_xy, int n_seeds, int max_corners, double quality_level,
+                             double min_distance, float* points_xy, int32_t* origin, int capacity, int* count,
+                             int* carried);
+/* cv::goodFeaturesToTrack(image, corners, maxCorners, qualityLevel, minDistance, mask) on one host image
+ * (src/with_bundle_adjustment.cpp:586-593 with the argument the reference leaves empty): a pixel whose mask byte is 0
+ * is no corner and does not count for the maximum that qualityLevel scales; mask_stride >= width.  max_corners <= 0:
+ * no limit.  *count and ORBX_ERR_CAPACITY as orbx_good_features_to_track.  Runs as a top-up of one frame without
+ * seeds: it replaces the results of the last top-up, and leaves the plain good-features block alone. */
+int orbx_good_features_to_track_masked(orbx_ctx* ctx, const uint8_t* image, int width, int height, int stride,
+                                       const uint8_t* mask, int mask_stride, int max_corners, double quality_level,
+                                       double min_distance, float* corners_xy, int capacity, int* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -272,15 +272,20 @@ struct TracksPose {
 
 // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames (response maps | key pools | cell grids
 // | per-frame maximum and candidate count), allocated on first use and bounded by ws_limit; the staged host
-// image of the one-frame entries; and the entry's OWN result block (counts | corners), untouched by the ORB path
+// image of the one-frame entries; and the entry's OWN result block (counts | corners), untouched by the ORB path.
+// Rank 12 (top-up and masked detection) adds, beside the workspace and for the same number of frames, the bit maps
+// of blocked pixels with the masked maxima (bm: allocated at the first top-up or masked call, freed with the
+// workspace), the staged seeds or mask of the host entries, and a result block of its own (tres: counts | carried |
+// points | origin).
 struct GoodFeatures {
-  DevBuf ws, img, res;
+  DevBuf ws, img, res, bm, stage, tres;
   size_t ws_limit = ORBX_GFTT_WORKSPACE_DEFAULT;
-  int n = 0, cap = 0;  // frames and slots per frame of the last good-features batch (n == 0: none)
+  int n = 0, cap = 0;    // frames and slots per frame of the last good-features batch (n == 0: none)
+  int tn = 0, tcap = 0;  // the same of the last top-up
   SideWork side;
   void release() {
     side.release();
-    free_bufs({&ws, &img, &res});
+    free_bufs({&ws, &img, &res, &bm, &stage, &tres});
   }
 };
 

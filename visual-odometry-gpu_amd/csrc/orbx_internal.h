@@ -258,3 +258,23 @@ hipError_t orbx_launch_gftt_select(hipStream_t s, int n, int w, unsigned long lo
                                    const int32_t* d_ncand, double min_distance, int cell, int gw, int gh, int slots,
                                    uint32_t* d_grid, size_t grid_stride, int cap, int32_t* d_counts,
                                    float* d_corners);
+// rank 12 (top-up): d_bits: ceil(w / 32) * h words per frame, a set bit blocks the pixel (zeroed by the caller before
+// orbx_launch_gftt_block, which ORs the carried seeds' neighbourhoods in; orbx_launch_gftt_mask_bits writes every
+// word of ONE frame); d_mmax: the largest unblocked response (zeroed by the caller); d_seed_xy may be NULL (no seeds);
+// max_seeds: the most seeds a frame can carry (sizes the blocking launch); slot_cap: result slots per frame
+hipError_t orbx_launch_gftt_seeds(hipStream_t s, int n, const float* d_seed_xy, size_t point_stride,
+                                  size_t frame_stride, const int32_t* d_seed_seen, int seen_min, int seed_cap, int w,
+                                  int h, int slot_cap, int32_t* d_carried, float* d_points, int32_t* d_origin);
+hipError_t orbx_launch_gftt_block(hipStream_t s, int n, const float* d_points, const int32_t* d_carried, int slot_cap,
+                                  int max_seeds, int w, int h, double min_distance, uint32_t* d_bits);
+hipError_t orbx_launch_gftt_mask_bits(hipStream_t s, const uint8_t* d_mask, int w, int h, int mask_stride,
+                                      uint32_t* d_bits);
+hipError_t orbx_launch_gftt_masked_max(hipStream_t s, const float* d_map, int n, int w, int h, const uint32_t* d_bits,
+                                       uint32_t* d_mmax);
+hipError_t orbx_launch_gftt_candidates_blocked(hipStream_t s, const float* d_map, int n, int w, int h,
+                                               const uint32_t* d_mmax, double quality, unsigned long long* d_keys,
+                                               size_t pool, int32_t* d_ncand, const uint32_t* d_bits);
+hipError_t orbx_launch_gftt_select_topup(hipStream_t s, int n, int w, unsigned long long* d_keys, size_t pool,
+                                         const int32_t* d_ncand, double min_distance, int cell, int gw, int gh,
+                                         int slots, uint32_t* d_grid, size_t grid_stride, int slot_cap,
+                                         const int32_t* d_carried, int32_t* d_counts, float* d_points);

@@ -32,6 +32,7 @@
 //     Fast.cu:8-18) and constructors print nothing;
 //   * HarrisScore takes `float k` (the reference's `int k` truncates 0.04 to 0, D7).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -1136,6 +1137,61 @@ inline void goodFeaturesToTrack(CornerDetector& handle, const cv::Mat& image, st
   for (const Point2f& p : out) corners.emplace_back(p.x, p.y);
 }
 #endif
+
+// cv::goodFeaturesToTrack(image, corners, maxCorners, qualityLevel, minDistance, mask) -- the argument the reference
+// leaves empty (src/with_bundle_adjustment.cpp:586-593): a pixel whose mask byte is 0 is no corner and does not count
+// for the maximum that qualityLevel scales.  corners are ASSIGNED; maxCorners <= 0: no limit.
+inline void goodFeaturesToTrack(CornerDetector& handle, const Image& image, std::vector<Point2f>& corners,
+                                int maxCorners, double qualityLevel, double minDistance, const Image& mask) {
+  if (mask.width != image.width || mask.height != image.height)
+    throw std::runtime_error("goodFeaturesToTrack: mask and image differ in size");
+  orbx_ctx* c = handle.get(image.width, image.height);
+  int count = 0;
+  size_t capacity = maxCorners > 0 ? (size_t)maxCorners : 4096;
+  for (;;) {
+    corners.resize(capacity);
+    const int st = orbx_good_features_to_track_masked(c, image.data, image.width, image.height, image.stride,
+                                                      mask.data, mask.stride, maxCorners, qualityLevel, minDistance,
+                                                      reinterpret_cast<float*>(corners.data()), (int)capacity, &count);
+    if (st == ORBX_ERR_CAPACITY && (size_t)count > capacity) {
+      capacity = (size_t)count;
+      continue;
+    }
+    if (st != ORBX_OK) corners.clear();
+    detail::check(c, st, "goodFeaturesToTrack (mask)");
+    break;
+  }
+  corners.resize((size_t)count);
+}
+
+// What a KLT front-end does between two windows, goodFeaturesToTrack(img, maxCorners - alive, q, d, mask around the
+// live tracks) -- the reference's own answers are a fresh detection (src/with_bundle_adjustment.cpp:586-593) or ORB
+// plus the matcher below 150 survivors (src/feature_tracking.cpp:68-71).  The usable tracked points come first, in
+// their order, then new corners at least minDistance from every one of them; origin[i] is the index into `tracked`
+// a point came from, -1 for a new corner.
+struct ToppedUp {
+  std::vector<Point2f> points;
+  std::vector<int32_t> origin;
+  int carried = 0;
+};
+inline ToppedUp top_up_keypoints(CornerDetector& handle, const Image& img, const std::vector<Point2f>& tracked,
+                                 int maxCorners, double qualityLevel, double minDistance) {
+  orbx_ctx* c = handle.get(img.width, img.height);
+  ToppedUp out;
+  const size_t capacity = (size_t)std::max(maxCorners, 1);
+  out.points.resize(capacity);
+  out.origin.resize(capacity);
+  int count = 0;
+  const int st = orbx_good_features_topup(c, img.data, img.width, img.height, img.stride,
+                                          reinterpret_cast<const float*>(tracked.data()), (int)tracked.size(),
+                                          maxCorners, qualityLevel, minDistance,
+                                          reinterpret_cast<float*>(out.points.data()), out.origin.data(),
+                                          (int)capacity, &count, &out.carried);
+  detail::check(c, st, "top_up_keypoints");
+  out.points.resize((size_t)count);
+  out.origin.resize((size_t)count);
+  return out;
+}
 
 // The initial keypoints of run_bundle_adjustment (src/with_bundle_adjustment.cpp:586-593): the caller's
 // observations of frame 0 if there are any, else goodFeaturesToTrack(img0, 2000, 0.01, 8).

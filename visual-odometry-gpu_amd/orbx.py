@@ -47,6 +47,8 @@ EXPORTS = [
     "orbx_bundle_adjust_landmarks_device", "orbx_bundle_adjust_landmarks_fetch", "orbx_bundle_adjust_tracks",
     "orbx_tracks_pose_device", "orbx_tracks_pose_results_device", "orbx_tracks_pose_fetch",
     "orbx_tracks_pose_pair_fetch", "orbx_tracks_pose",
+    "orbx_good_features_topup_device", "orbx_good_features_topup_results_device", "orbx_good_features_topup_fetch",
+    "orbx_good_features_topup", "orbx_good_features_to_track_masked",
 ]
 
 
@@ -751,15 +753,17 @@ class GoodFeaturesView(C.Structure):
     _fields_ = [("counts", C.c_void_p), ("corners_xy", C.c_void_p), ("slot_capacity", C.c_int32), ("n", C.c_int32)]
 
 
+def _gftt_view(a):
+    # a row-strided uint8 view (a region of a larger image) is handed over as it is
+    if isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1 and \
+            a.strides[0] >= a.shape[1]:
+        return a
+    return _img(a)
+
+
 def _gftt_methods():
     """Shi-Tomasi corners: cv::goodFeaturesToTrack (include/orbx.h; DESIGN.md §9 rank 8)."""
-
-    def _view(a):
-        # a row-strided uint8 view (a region of a larger image) is handed over as it is
-        if isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1 and \
-                a.strides[0] >= a.shape[1]:
-            return a
-        return _img(a)
+    _view = _gftt_view
 
     def corner_min_eigen_val(self, image):
         """cv::cornerMinEigenVal(image, eig, 3, 3): the (h, w) float32 response map."""
@@ -839,6 +843,132 @@ def _gftt_methods():
 
 
 _gftt_methods()
+
+
+class GoodFeaturesTopupView(C.Structure):
+    _fields_ = [("counts", C.c_void_p), ("carried", C.c_void_p), ("points_xy", C.c_void_p), ("origin", C.c_void_p),
+                ("slot_capacity", C.c_int32), ("n", C.c_int32)]
+
+
+def _gftt_topup_methods():
+    """Masked Shi-Tomasi detection that tops up tracked points (include/orbx.h)."""
+
+    def good_features_topup(self, frames, seeds, seen=None, seen_min=0, seed_capacity=None, seed_point_stride=2,
+                            seed_frame_stride=None, max_corners=2000, quality_level=0.01, min_distance=8.0,
+                            stream=None):
+        """orbx_good_features_topup_device.  frames: (n, h, w) uint8, a torch device tensor (any strides with unit
+        pixel stride) or a numpy array (copied to the device first).  seeds: (n, seed_capacity, 2) float32 as a torch
+        device tensor or a numpy array, or a raw device address with seed_capacity, seed_point_stride and
+        seed_frame_stride (in floats) -- e.g. tracks_xy + 8 * (window_len - 1) of lk_windows_view().  seen:
+        (n, seed_capacity) int32 likewise, or None.  Device tensors: the caller has synchronised their producer, or
+        passes the producer's stream.  Asynchronous; good_features_topup_fetch delivers the results."""
+        import torch
+
+        uploaded = any(isinstance(a, np.ndarray) for a in (frames, seeds, seen))
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).cuda()
+        if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda or frames.stride(2) != 1:
+            raise ValueError("frames must be (n, h, w) uint8 on the device with unit pixel stride")
+        n, h, w = frames.shape
+        if isinstance(seeds, np.ndarray):
+            seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.float32)).cuda()
+        if isinstance(seen, np.ndarray):
+            seen = torch.from_numpy(np.ascontiguousarray(seen, np.int32)).cuda()
+        keep = [frames]
+        if torch.is_tensor(seeds):
+            if seeds.dtype != torch.float32 or not seeds.is_cuda or not seeds.is_contiguous() or seeds.dim() != 3 or \
+                    seeds.shape[0] != n or seeds.shape[2] != 2:
+                raise ValueError("seeds must be (n, seed_capacity, 2) float32, contiguous, on the device")
+            seed_capacity, seed_point_stride, seed_frame_stride = seeds.shape[1], 2, 2 * seeds.shape[1]
+            keep.append(seeds)
+            seeds = seeds.data_ptr()
+        elif seed_capacity is None or seed_frame_stride is None:
+            raise ValueError("a raw seed address needs seed_capacity and seed_frame_stride")
+        if torch.is_tensor(seen):
+            if seen.dtype != torch.int32 or not seen.is_cuda or not seen.is_contiguous() or \
+                    seen.numel() != n * seed_capacity:
+                raise ValueError("seen must be (n, seed_capacity) int32, contiguous, on the device")
+            keep.append(seen)
+            seen = seen.data_ptr()
+        if uploaded:
+            torch.cuda.synchronize()  # the uploads above ran on torch's stream
+        self._gft_keep = keep  # kept alive until the next call
+        rs = frames.stride(1)
+        fs = max(frames.stride(0), rs * (h - 1) + w) if n == 1 else frames.stride(0)
+        f = self._lib.orbx_good_features_topup_device
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
+                      C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
+        self._chk(f(self._h, C.c_void_p(frames.data_ptr()), n, w, h, rs, fs, C.c_void_p(seeds), seed_point_stride,
+                    seed_frame_stride, C.c_void_p(seen) if seen else None, seen_min, seed_capacity, max_corners,
+                    quality_level, min_distance, C.c_void_p(stream) if stream else None))
+
+    def good_features_topup_view(self):
+        """The device-side result block of the last top-up (orbx_good_features_topup_results_device)."""
+        v = GoodFeaturesTopupView()
+        self._chk(self._lib.orbx_good_features_topup_results_device(self._h, C.byref(v)))
+        return v
+
+    def good_features_topup_fetch(self, first=0, n=None):
+        """Frames [first, first + n) of the last top-up as whole arrays: counts (n,), carried (n,), points
+        (n, slot_capacity, 2) float32 and origin (n, slot_capacity) int32 -- zero / -1 at and beyond counts[f]."""
+        v = self.good_features_topup_view()
+        if n is None:
+            n = v.n - first
+        m = max(n, 1)
+        counts, carried = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        points = np.zeros((m, v.slot_capacity, 2), np.float32)
+        origin = np.zeros((m, v.slot_capacity), np.int32)
+        f = self._lib.orbx_good_features_topup_fetch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(f(self._h, first, n, _ptr(counts), _ptr(carried), _ptr(points), _ptr(origin)))
+        return counts, carried, points, origin
+
+    def good_features_topup_one(self, image, seeds, max_corners=2000, quality_level=0.01, min_distance=8.0,
+                                capacity=None):
+        """orbx_good_features_topup on one host image and (n, 2) host seeds: points (count, 2) float32, origin
+        (count,) int32 and the number of carried points."""
+        image = _gftt_view(image)
+        h, w = image.shape
+        seeds = np.ascontiguousarray(seeds, np.float32).reshape(-1, 2)
+        if capacity is None:
+            capacity = max(max_corners, 1)
+        points = np.zeros((max(capacity, 1), 2), np.float32)
+        origin = np.zeros(max(capacity, 1), np.int32)
+        cnt, car = C.c_int(0), C.c_int(0)
+        f = self._lib.orbx_good_features_topup
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                      C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self._chk(f(self._h, _ptr(image), w, h, image.strides[0], _ptr(seeds) if len(seeds) else None, len(seeds),
+                    max_corners, quality_level, min_distance, _ptr(points), _ptr(origin), capacity, C.byref(cnt),
+                    C.byref(car)))
+        return points[:cnt.value].copy(), origin[:cnt.value].copy(), car.value
+
+    def good_features_to_track_masked(self, image, mask, max_corners=2000, quality_level=0.01, min_distance=8.0,
+                                      capacity=None):
+        """cv::goodFeaturesToTrack(image, corners, maxCorners, qualityLevel, minDistance, mask): (n, 2) float32
+        corners; a pixel whose mask byte is 0 is no corner.  max_corners <= 0: no limit."""
+        image = _gftt_view(image)
+        h, w = image.shape
+        mask = _gftt_view(mask)
+        if mask.shape != image.shape:
+            raise ValueError("mask and image differ in size")
+        if capacity is None:
+            capacity = max_corners if max_corners > 0 else max((w - 2) * (h - 2), 1)
+        out = np.zeros((max(capacity, 1), 2), np.float32)
+        cnt = C.c_int(0)
+        f = self._lib.orbx_good_features_to_track_masked
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                      C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        self._chk(f(self._h, _ptr(image), w, h, image.strides[0], _ptr(mask), mask.strides[0], max_corners,
+                    quality_level, min_distance, _ptr(out), capacity, C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    for f in (good_features_topup, good_features_topup_view, good_features_topup_fetch, good_features_topup_one,
+              good_features_to_track_masked):
+        setattr(Context, f.__name__, f)
+
+
+_gftt_topup_methods()
 
 
 class LkWindowsView(C.Structure):
