@@ -118,14 +118,66 @@ int SideWork::enter(orbx_ctx* c, hipStream_t s) {
   return ORBX_OK;
 }
 
-int set_workspace_limit(orbx_ctx* c, SideWork& side, DevBuf& ws, size_t* limit, size_t bytes, size_t dflt) {
+int SideWork::after(orbx_ctx* c, const SideWork& producer, hipStream_t s) {
+  if (producer.ev && producer.stream != s) HIPCHK(c, hipStreamWaitEvent(s, producer.ev, 0));
+  return ORBX_OK;
+}
+
+int SideWork::grow(orbx_ctx* c, DevBuf& b, size_t bytes) {
+  if (b.p && b.bytes >= bytes) return ORBX_OK;
+  const int st = wait(c);
+  if (st != ORBX_OK) return st;
+  bytes = align_up_sz(std::max<size_t>(bytes, 256), 256);
+  void* p = nullptr;
+  HIPCHK(c, hipMalloc(&p, bytes));
+  if (b.p) (void)hipFree(b.p);
+  b.p = p;
+  b.bytes = bytes;
+  return ORBX_OK;
+}
+
+int PinnedUpload::send(orbx_ctx* c, void* d_dst, const void* src, size_t n, hipStream_t s) {
+  if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  HIPCHK(c, hipEventSynchronize(ev));  // the previous copy has to have read the mirror
+  if (bytes < n) {
+    if (host) (void)hipHostFree(host);
+    host = nullptr;
+    bytes = 0;
+    HIPCHK(c, hipHostMalloc(&host, align_up_sz(n, 4096), hipHostMallocDefault));
+    bytes = align_up_sz(n, 4096);
+  }
+  std::memcpy(host, src, n);
+  HIPCHK(c, hipMemcpyAsync(d_dst, host, n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(ev, s));
+  return ORBX_OK;
+}
+
+int set_workspace_limit(orbx_ctx* c, SideWork& side, std::initializer_list<DevBuf*> ws, size_t* limit, size_t bytes,
+                        size_t dflt) {
   const int st = side.wait(c);
   if (st != ORBX_OK) return st;
-  if (ws.p) {
-    HIPCHK(c, hipFree(ws.p));
-    ws = DevBuf{};
-  }
+  for (DevBuf* b : ws)
+    if (b->p) {
+      HIPCHK(c, hipFree(b->p));
+      *b = DevBuf{};
+    }
   *limit = bytes ? bytes : dflt;
+  return ORBX_OK;
+}
+
+int stage_tracks(orbx_ctx* c, SideWork& side, DevBuf& stage, const float* tracks_xy, const int32_t* seen, int n_slots,
+                 int window_len, const float** d_tracks, const int32_t** d_seen) {
+  int st = side.enter(c, c->stream);
+  if (st != ORBX_OK) return st;
+  const SideWork::Mark mark{side, c->stream};
+  const size_t tb = sizeof(float) * 2 * (size_t)n_slots * window_len, sb = sizeof(int32_t) * (size_t)n_slots;
+  const size_t o_seen = align_up_sz(tb, 256);
+  if ((st = side.grow(c, stage, o_seen + sb)) != ORBX_OK) return st;
+  uint8_t* d = (uint8_t*)stage.p;
+  HIPCHK(c, hipMemcpyAsync(d, tracks_xy, tb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d + o_seen, seen, sb, hipMemcpyHostToDevice, c->stream));
+  *d_tracks = (const float*)d;
+  *d_seen = (const int32_t*)(d + o_seen);
   return ORBX_OK;
 }
 
@@ -715,7 +767,7 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
   B.copy_compact = false;
   // result block sections are laid out for (n, pool slot capacity)
   B.cap = slots_per_frame(c->plan);
-  B.layout = make_out_layout(n, B.cap);
+  B.layout = OutLayout(n, B.cap);
   static const int use_graph = env_int("ORBX_GRAPH", 1);
   const int tm = c->timing;
   if (use_graph && tm == 0) {
@@ -972,7 +1024,7 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
     CREATE_CHK(hipMemcpy(c->d_gauss, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   {
-    const OutLayout o = make_out_layout((int)B, slots_per_frame(M));  // (the largest block any batch can need)
+    const OutLayout o((int)B, slots_per_frame(M));  // (the largest block any batch can need)
     {
       // The copy stream gets the HIGHEST priority -- not for the copies' sake: streams of one priority share a few
       // hardware queues, and the copy of a batch is enqueued behind a wait for the batch's end.  In a queue shared
@@ -1028,8 +1080,7 @@ int orbx_detect_and_compute_batch_device(orbx_ctx* c, const void* d_frames, int 
   // the kernels address the bytes of one frame with 32-bit offsets (a buffer descriptor per frame)
   if ((unsigned long long)row_stride * (unsigned long long)(height - 1) + (unsigned long long)width > 0x7fffffffull)
     return fail(c, ORBX_ERR_INVALID_ARG, "row_stride * (height - 1) + width exceeds 2^31 - 1");
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  return run_batch(c, (const uint8_t*)d_frames, n, width, height, row_stride, frame_stride, s, true);
+  return run_batch(c, (const uint8_t*)d_frames, n, width, height, row_stride, frame_stride, stream_of(c, stream), true);
 }
 
 int orbx_detect_and_compute_batch_host(orbx_ctx* c, const uint8_t* frames, int n, int width, int height,

@@ -10,26 +10,6 @@ using namespace orbx_host;
 // ---- Shi-Tomasi corners (next row) ------------------------
 namespace {
 
-// the sections of the workspace for m frames of w x h with a cell grid of grid_stride words per frame
-struct GfLayout {
-  size_t map, keys, grid, cnt, total, pool, grid_stride;
-};
-GfLayout gf_layout(int m, int w, int h, size_t grid_stride) {
-  GfLayout o;
-  const size_t px = (size_t)w * h;
-  o.pool = (size_t)(w - 2) * (h - 2);
-  o.grid_stride = grid_stride;
-  o.map = 0;
-  o.keys = align_up_sz(sizeof(float) * px * m, 256);
-  o.grid = align_up_sz(o.keys + sizeof(unsigned long long) * o.pool * m, 256);
-  o.cnt = align_up_sz(o.grid + sizeof(uint32_t) * grid_stride * m, 256);
-  o.total = o.cnt + 2 * sizeof(uint32_t) * (size_t)m;  // maxima, then candidate counts
-  return o;
-}
-// the largest grid of a w x h frame: w * h cells of one slot (cell 1) or, from cell 2 on, at most
-// ceil(w / 2) * ceil(h / 2) cells of four -- both within (w + 1)(h + 1) words
-size_t gf_grid_bound(int w, int h) { return (size_t)(w + 1) * (h + 1); }
-
 struct GfArgs {
   int cap, suppress, cell, gw, gh, slots;
   double quality, min_distance;
@@ -59,27 +39,18 @@ GfArgs gf_args(int w, int h, int max_corners, double quality, double min_distanc
   return a;
 }
 
-// the workspace: allocated once, for as many frames of the largest size as the limit holds (at least one, at most
-// max_batch); the bit maps of rank 12 are allocated for the same number
-size_t gf_workspace_frames(const orbx_ctx* c) {
-  const int mw = c->p.max_width, mh = c->p.max_height;
-  const size_t one = gf_layout(1, mw, mh, gf_grid_bound(mw, mh)).total + 1024;
-  return std::min<size_t>(std::max<size_t>(c->gf.ws_limit / one, 1), (size_t)c->p.max_batch);
+// the workspace: allocated once, for as many frames of the largest size as the limit holds; the bit maps of rank 12
+// are allocated beside it at the first top-up or masked call, for the same number (orbx_layout.h)
+int gf_frames(const orbx_ctx* c) {
+  return (int)gf_workspace_frames(c->gf.ws_limit, c->p.max_width, c->p.max_height, c->p.max_batch);
 }
 int gf_workspace(orbx_ctx* c) {
   if (c->gf.ws.p) return ORBX_OK;
-  const int mw = c->p.max_width, mh = c->p.max_height;
-  ENSURE(c, c->gf.ws, gf_layout((int)gf_workspace_frames(c), mw, mh, gf_grid_bound(mw, mh)).total + 1024);
-  return ORBX_OK;
+  return c->gf.side.grow(c, c->gf.ws, gf_workspace_bytes(gf_frames(c), c->p.max_width, c->p.max_height));
 }
-
-// frames of w x h per slice
-int gf_slice_frames(const orbx_ctx* c, int n, int w, int h, size_t grid_stride) {
-  const size_t one = gf_layout(1, w, h, grid_stride).total + 1024;  // (the sections' alignment: < 1024 bytes)
-  const size_t fit = std::max<size_t>((c->gf.ws.bytes - 1024) / one, 1);
-  const int m = (int)std::min<size_t>(fit, (size_t)n);
-  const int slices = (n + m - 1) / m;
-  return (n + slices - 1) / slices;  // even slices
+int gf_bitmaps(orbx_ctx* c) {
+  if (c->gf.bm.p) return ORBX_OK;
+  return c->gf.side.grow(c, c->gf.bm, gb_bytes(gf_frames(c), c->p.max_width, c->p.max_height));
 }
 
 // enqueues the three stages for n device frames; the results go to gf.res (counts | corners)
@@ -90,17 +61,15 @@ int gf_run(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row_st
   const SideWork::Mark mark{c->gf.side, s};
   c->gf.n = 0;  // (a failed call leaves no "last batch")
   if ((st = gf_workspace(c)) != ORBX_OK) return st;
-  const size_t o_corners = align_up_sz(sizeof(int32_t) * (size_t)n, 256);
-  const size_t res_bytes = o_corners + sizeof(float) * 2 * (size_t)a.cap * n;
-  if (c->gf.res.p && c->gf.res.bytes < res_bytes && (st = c->gf.side.wait(c)) != ORBX_OK) return st;  // (still written?)
-  ENSURE(c, c->gf.res, res_bytes);
+  const GrLayout R(n, a.cap);
+  if ((st = c->gf.side.grow(c, c->gf.res, R.total)) != ORBX_OK) return st;
   const size_t grid_stride = a.suppress ? (size_t)a.gw * a.gh * a.slots : 0;
-  const int per = gf_slice_frames(c, n, w, h, grid_stride);
+  const int per = gf_slice_frames(c->gf.ws.bytes, n, w, h, grid_stride);
   int32_t* d_counts = (int32_t*)c->gf.res.p;
-  float* d_corners = (float*)((uint8_t*)c->gf.res.p + o_corners);
+  float* d_corners = (float*)((uint8_t*)c->gf.res.p + R.corners);
   for (int f0 = 0; f0 < n; f0 += per) {
     const int m = std::min(per, n - f0);
-    const GfLayout L = gf_layout(m, w, h, grid_stride);
+    const GfLayout L(m, w, h, grid_stride);
     uint8_t* ws = (uint8_t*)c->gf.ws.p;
     uint32_t* d_max = (uint32_t*)(ws + L.cnt);
     int32_t* d_ncand = (int32_t*)(d_max + m);
@@ -124,47 +93,12 @@ int gf_upload(orbx_ctx* c, const uint8_t* image, int w, int h, int stride) {
   int st = c->gf.side.enter(c, c->stream);
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->gf.side, c->stream};
-  ENSURE(c, c->gf.img, (size_t)w * h);
+  if ((st = c->gf.side.grow(c, c->gf.img, (size_t)w * h)) != ORBX_OK) return st;
   HIPCHK(c, hipMemcpy2DAsync(c->gf.img.p, w, image, stride, w, h, hipMemcpyHostToDevice, c->stream));
   return ORBX_OK;
 }
 
 // ---- masked detection that tops up tracked points -----------------------
-// the bit maps of blocked pixels of m frames of w x h: the masked maxima first, then ceil(w / 32) * h words per frame
-struct GbLayout {
-  size_t bits, words, total;
-};
-GbLayout gb_layout(int m, int w, int h) {
-  GbLayout o;
-  o.words = (size_t)((w + 31) / 32) * h;
-  o.bits = align_up_sz(sizeof(uint32_t) * (size_t)m, 256);
-  o.total = o.bits + sizeof(uint32_t) * o.words * m;
-  return o;
-}
-// allocated beside the workspace, for the same number of frames of the largest size (+ 512: whatever frames of a
-// smaller size fit by gb_frames fit with their sections' alignment)
-int gf_bitmaps(orbx_ctx* c) {
-  if (c->gf.bm.p) return ORBX_OK;
-  ENSURE(c, c->gf.bm, gb_layout((int)gf_workspace_frames(c), c->p.max_width, c->p.max_height).total + 512);
-  return ORBX_OK;
-}
-// frames of w x h whose bit maps and maxima fit (the maxima's alignment costs less than 256 bytes); at least one
-size_t gb_frames(const orbx_ctx* c, int w, int h) {
-  return std::max<size_t>((c->gf.bm.bytes - 256) / (sizeof(uint32_t) * (gb_layout(1, w, h).words + 1)), 1);
-}
-// the top-up's result block: counts | carried | points | origin
-struct GtLayout {
-  size_t carried, points, origin, total;
-};
-GtLayout gt_layout(int n, int cap) {
-  GtLayout o;
-  o.carried = align_up_sz(sizeof(int32_t) * (size_t)n, 256);
-  o.points = o.carried + align_up_sz(sizeof(int32_t) * (size_t)n, 256);
-  o.origin = o.points + align_up_sz(sizeof(float) * 2 * (size_t)cap * n, 256);
-  o.total = o.origin + sizeof(int32_t) * (size_t)cap * n;
-  return o;
-}
-
 struct GfSeeds {  // d_xy == NULL: none
   const float* d_xy;
   size_t point_stride, frame_stride;
@@ -180,14 +114,14 @@ int gf_topup_run(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int 
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->gf.side, s};
   // the seeds may be the windows tracker's block, written on another stream
-  if (c->lkw.side.ev && c->lkw.side.stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->lkw.side.ev, 0));
+  if ((st = c->gf.side.after(c, c->lkw.side, s)) != ORBX_OK) return st;
   c->gf.tn = 0;  // (a failed call leaves no "last top-up")
   if ((st = gf_workspace(c)) != ORBX_OK || (st = gf_bitmaps(c)) != ORBX_OK) return st;
-  const GtLayout R = gt_layout(n, slot_cap);
-  if (c->gf.tres.p && c->gf.tres.bytes < R.total && (st = c->gf.side.wait(c)) != ORBX_OK) return st;
-  ENSURE(c, c->gf.tres, R.total);
+  const GtLayout R(n, slot_cap);
+  if ((st = c->gf.side.grow(c, c->gf.tres, R.total)) != ORBX_OK) return st;
   const size_t grid_stride = a.suppress ? (size_t)a.gw * a.gh * a.slots : 0;
-  const int per = (int)std::min<size_t>((size_t)gf_slice_frames(c, n, w, h, grid_stride), gb_frames(c, w, h));
+  const int per = (int)std::min<size_t>((size_t)gf_slice_frames(c->gf.ws.bytes, n, w, h, grid_stride),
+                                        gb_frames(c->gf.bm.bytes, w, h));
   uint8_t* res = (uint8_t*)c->gf.tres.p;
   int32_t* d_counts = (int32_t*)res;
   int32_t* d_carried = (int32_t*)(res + R.carried);
@@ -196,8 +130,8 @@ int gf_topup_run(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int 
   const int max_seeds = std::min(seeds.d_xy ? seeds.capacity : 0, slot_cap);
   for (int f0 = 0; f0 < n; f0 += per) {
     const int m = std::min(per, n - f0);
-    const GfLayout L = gf_layout(m, w, h, grid_stride);
-    const GbLayout B = gb_layout(m, w, h);
+    const GfLayout L(m, w, h, grid_stride);
+    const GbLayout B(m, w, h);
     uint8_t* ws = (uint8_t*)c->gf.ws.p;
     uint32_t* d_max = (uint32_t*)(ws + L.cnt);
     int32_t* d_ncand = (int32_t*)(d_max + m);
@@ -247,15 +181,14 @@ int gf_stage(orbx_ctx* c, const void* src, size_t row, size_t rows, size_t src_s
   int st = c->gf.side.enter(c, c->stream);
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->gf.side, c->stream};
-  if (c->gf.stage.p && c->gf.stage.bytes < row * rows && (st = c->gf.side.wait(c)) != ORBX_OK) return st;
-  ENSURE(c, c->gf.stage, row * rows);
+  if ((st = c->gf.side.grow(c, c->gf.stage, row * rows)) != ORBX_OK) return st;
   HIPCHK(c, hipMemcpy2DAsync(c->gf.stage.p, row, src, src_stride, row, rows, hipMemcpyHostToDevice, c->stream));
   return ORBX_OK;
 }
 
 // the one-frame result of the run just enqueued on the context's stream, to host arrays of `capacity` slots
 int gf_topup_deliver(orbx_ctx* c, float* points_xy, int32_t* origin, int capacity, int* count, int* carried) {
-  const GtLayout R = gt_layout(1, c->gf.tcap);
+  const GtLayout R(1, c->gf.tcap);
   const uint8_t* res = (const uint8_t*)c->gf.tres.p;
   int32_t found = 0, kept = 0;
   HIPCHK(c, hipMemcpyAsync(&found, res, sizeof(found), hipMemcpyDeviceToHost, c->stream));
@@ -286,7 +219,7 @@ int orbx_corner_min_eigen_val(orbx_ctx* c, const uint8_t* image, int width, int 
   if ((st = gf_upload(c, image, width, height, stride)) != ORBX_OK) return st;
   const SideWork::Mark mark{c->gf.side, c->stream};
   if ((st = gf_workspace(c)) != ORBX_OK) return st;
-  const GfLayout L = gf_layout(1, width, height, 0);
+  const GfLayout L(1, width, height, 0);
   uint8_t* ws = (uint8_t*)c->gf.ws.p;
   HIPCHK(c, hipMemsetAsync(ws + L.cnt, 0, 2 * sizeof(uint32_t), c->stream));
   HIPCHK(c, orbx_launch_gftt_response(c->stream, (const uint8_t*)c->gf.img.p, 1, width, height, width,
@@ -318,7 +251,7 @@ int orbx_good_features_to_track(orbx_ctx* c, const uint8_t* image, int width, in
     return fail(c, ORBX_ERR_CAPACITY, "corners_xy is too small");
   }
   if (found > 0)
-    HIPCHK(c, hipMemcpy(corners_xy, (const uint8_t*)c->gf.res.p + align_up_sz(sizeof(int32_t), 256),
+    HIPCHK(c, hipMemcpy(corners_xy, (const uint8_t*)c->gf.res.p + GrLayout(1, c->gf.cap).corners,
                         sizeof(float) * 2 * (size_t)found, hipMemcpyDeviceToHost));
   *count = found;
   return ORBX_OK;
@@ -336,19 +269,14 @@ int orbx_good_features_batch_device(orbx_ctx* c, const void* d_frames, int n, in
   if ((st = gf_check_params(c, quality_level, min_distance)) != ORBX_OK) return st;
   return gf_run(c, (const uint8_t*)d_frames, n, width, height, row_stride, frame_stride,
                 gf_args(width, height, max_corners, quality_level, min_distance),
-                stream ? (hipStream_t)stream : c->stream);
+                stream_of(c, stream));
 }
 
 int orbx_good_features_workspace_limit(orbx_ctx* c, size_t bytes) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
-  const int st = set_workspace_limit(c, c->gf.side, c->gf.ws, &c->gf.ws_limit, bytes, ORBX_GFTT_WORKSPACE_DEFAULT);
-  if (st != ORBX_OK) return st;
-  if (c->gf.bm.p) {  // the bit maps go with the workspace
-    HIPCHK(c, hipFree(c->gf.bm.p));
-    c->gf.bm = DevBuf{};
-  }
-  return ORBX_OK;
+  // (the bit maps go with the workspace)
+  return set_workspace_limit(c, c->gf.side, {&c->gf.ws, &c->gf.bm}, &c->gf.ws_limit, bytes, ORBX_GFTT_WORKSPACE_DEFAULT);
 }
 
 int orbx_good_features_results_device(orbx_ctx* c, orbx_good_features_view* v) {
@@ -356,7 +284,7 @@ int orbx_good_features_results_device(orbx_ctx* c, orbx_good_features_view* v) {
   if (!c || !v) return ORBX_ERR_INVALID_ARG;
   if (c->gf.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no good-features batch has run");
   v->counts = (const int32_t*)c->gf.res.p;
-  v->corners_xy = (const float*)((const uint8_t*)c->gf.res.p + align_up_sz(sizeof(int32_t) * (size_t)c->gf.n, 256));
+  v->corners_xy = (const float*)((const uint8_t*)c->gf.res.p + GrLayout(c->gf.n, c->gf.cap).corners);
   v->slot_capacity = c->gf.cap;
   v->n = c->gf.n;
   return ORBX_OK;
@@ -366,7 +294,7 @@ int orbx_good_features_fetch(orbx_ctx* c, int first, int n, int32_t* counts, flo
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
   if (c->gf.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no good-features batch has run");
-  if (!counts || first < 0 || n < 1 || first >= c->gf.n || n > c->gf.n - first)
+  if (!counts || !range_ok(first, n, c->gf.n))
     return fail(c, ORBX_ERR_INVALID_ARG, "counts is NULL or [first, first + n) outside the batch");
   const int st = c->gf.side.wait(c);
   if (st != ORBX_OK) return st;
@@ -375,7 +303,7 @@ int orbx_good_features_fetch(orbx_ctx* c, int first, int n, int32_t* counts, flo
                       hipMemcpyDeviceToHost));
   if (corners_xy) {
     const size_t row = sizeof(float) * 2 * (size_t)c->gf.cap;
-    HIPCHK(c, hipMemcpy(corners_xy, res + align_up_sz(sizeof(int32_t) * (size_t)c->gf.n, 256) + row * first, row * n,
+    HIPCHK(c, hipMemcpy(corners_xy, res + GrLayout(c->gf.n, c->gf.cap).corners + row * first, row * n,
                         hipMemcpyDeviceToHost));
   }
   return ORBX_OK;
@@ -405,14 +333,14 @@ int orbx_good_features_topup_device(orbx_ctx* c, const void* d_frames, int n, in
   const GfSeeds seeds{d_seed_xy, seed_point_stride, seed_frame_stride, d_seed_seen, seen_min, seed_capacity};
   return gf_topup_run(c, (const uint8_t*)d_frames, n, width, height, row_stride, frame_stride, seeds, nullptr,
                       gf_args(width, height, max_corners, quality_level, min_distance), max_corners,
-                      stream ? (hipStream_t)stream : c->stream);
+                      stream_of(c, stream));
 }
 
 int orbx_good_features_topup_results_device(orbx_ctx* c, orbx_good_features_topup_view* v) {
   DeviceGuard _dg(c);
   if (!c || !v) return ORBX_ERR_INVALID_ARG;
   if (c->gf.tn < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no top-up has run");
-  const GtLayout R = gt_layout(c->gf.tn, c->gf.tcap);
+  const GtLayout R(c->gf.tn, c->gf.tcap);
   const uint8_t* res = (const uint8_t*)c->gf.tres.p;
   v->counts = (const int32_t*)res;
   v->carried = (const int32_t*)(res + R.carried);
@@ -428,11 +356,11 @@ int orbx_good_features_topup_fetch(orbx_ctx* c, int first, int n, int32_t* count
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
   if (c->gf.tn < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no top-up has run");
-  if (!counts || first < 0 || n < 1 || first >= c->gf.tn || n > c->gf.tn - first)
+  if (!counts || !range_ok(first, n, c->gf.tn))
     return fail(c, ORBX_ERR_INVALID_ARG, "counts is NULL or [first, first + n) outside the batch");
   const int st = c->gf.side.wait(c);
   if (st != ORBX_OK) return st;
-  const GtLayout R = gt_layout(c->gf.tn, c->gf.tcap);
+  const GtLayout R(c->gf.tn, c->gf.tcap);
   const uint8_t* res = (const uint8_t*)c->gf.tres.p;
   const size_t cnt = sizeof(int32_t) * (size_t)n, slots = (size_t)c->gf.tcap;
   HIPCHK(c, hipMemcpy(counts, res + sizeof(int32_t) * (size_t)first, cnt, hipMemcpyDeviceToHost));

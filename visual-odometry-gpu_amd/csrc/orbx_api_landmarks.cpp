@@ -12,80 +12,6 @@ using namespace orbx_host;
 
 namespace {
 
-// a buffer of the landmarks path of at least `bytes`: the new allocation is made BEFORE the old one is released, so
-// that a failed call keeps what it had
-int lm_grow(orbx_ctx* c, DevBuf& b, size_t bytes) {
-  if (b.p && b.bytes >= bytes) return ORBX_OK;
-  const int st = c->lm.side.wait(c);  // (the old allocation may still be read or written)
-  if (st != ORBX_OK) return st;
-  bytes = align_up_sz(std::max<size_t>(bytes, 256), 256);
-  void* p = nullptr;
-  HIPCHK(c, hipMalloc(&p, bytes));
-  if (b.p) (void)hipFree(b.p);
-  b.p = p;
-  b.bytes = bytes;
-  return ORBX_OK;
-}
-
-struct Taker {
-  size_t off = 0;
-  size_t take(size_t bytes) {
-    const size_t r = off;
-    off = align_up_sz(off + bytes, 256);
-    return r;
-  }
-};
-
-// the result block: every array sized for every slot kept
-struct LmBlock {
-  size_t status, pose_off, pt_off, obs_off, slot, rows, points, oxy, opose, bytes;
-};
-LmBlock lm_block(int n, int cap, int len) {
-  LmBlock L;
-  Taker t;
-  const size_t slots = (size_t)n * cap, noff = (size_t)n + 1;
-  L.status = t.take(sizeof(int32_t) * n);
-  L.pose_off = t.take(sizeof(int32_t) * noff);
-  L.pt_off = t.take(sizeof(int32_t) * noff);
-  L.obs_off = t.take(sizeof(int32_t) * noff);
-  L.slot = t.take(sizeof(int32_t) * slots);
-  L.rows = t.take(sizeof(int32_t) * (slots + n));
-  L.points = t.take(sizeof(double) * 3 * slots);
-  L.oxy = t.take(sizeof(double) * 2 * slots * len);
-  L.opose = t.take(slots * len);
-  L.bytes = t.off;
-  return L;
-}
-// the scratch of a build
-struct LmScratch {
-  size_t poses, gate, partial, keep, cand, bytes;
-};
-LmScratch lm_scratch(int n, int cap, int len) {
-  LmScratch L;
-  Taker t;
-  const size_t slots = (size_t)n * cap;
-  L.poses = t.take(sizeof(double) * 6 * (size_t)n * len);
-  L.gate = t.take(sizeof(int32_t) * n);
-  L.partial = t.take(sizeof(int32_t) * 2 * (size_t)n * orbx_lm_blocks(cap));
-  L.keep = t.take(slots);
-  L.cand = t.take(sizeof(double) * 3 * slots);
-  L.bytes = t.off;
-  return L;
-}
-// what a solve works on and leaves behind
-struct LmSolve {
-  size_t poses, points, out, bytes;
-};
-LmSolve lm_solve(int n, int cap, int len) {
-  LmSolve L;
-  Taker t;
-  L.poses = t.take(sizeof(double) * 6 * (size_t)n * len);
-  L.points = t.take(sizeof(double) * 3 * (size_t)n * cap);
-  L.out = t.take(sizeof(orbx_ba_summary) * (size_t)n);
-  L.bytes = t.off;
-  return L;
-}
-
 OrbxLmBlock lm_pointers(const orbx_ctx* c, const LmBlock& L) {
   uint8_t* b = (uint8_t*)c->lm.blk.p;
   OrbxLmBlock o;
@@ -103,7 +29,7 @@ OrbxLmBlock lm_pointers(const orbx_ctx* c, const LmBlock& L) {
 
 int lm_check_range(orbx_ctx* c, int first, int n) {
   if (c->lm.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no landmarks block has been built");
-  if (first < 0 || n < 1 || first >= c->lm.n || n > c->lm.n - first)
+  if (!range_ok(first, n, c->lm.n))
     return fail(c, ORBX_ERR_INVALID_ARG, "[first, first + n) outside the landmarks block");
   return ORBX_OK;
 }
@@ -119,32 +45,17 @@ int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->lm.side, s};
   // the tracks may be the windows tracker's block, written on another stream
-  if (c->lkw.side.ev && c->lkw.side.stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->lkw.side.ev, 0));
-  const LmBlock B = lm_block(n, cap, len);
-  const LmScratch S = lm_scratch(n, cap, len);
-  if ((st = lm_grow(c, c->lm.scr, S.bytes)) != ORBX_OK) return st;
-  const void* old_blk = c->lm.blk.p;
-  if ((st = lm_grow(c, c->lm.blk, B.bytes)) != ORBX_OK) return st;
-  if (c->lm.blk.p != old_blk) c->lm.n = 0;  // (a larger block: the previous result went with the old one)
-  // The pose table goes up through a pinned mirror (a copy from pageable memory would make the host wait for the
-  // stream).  The mirror is reused: the previous call's copy has to have read it.
-  const size_t table = sizeof(double) * 6 * (size_t)n * len;
-  if (!c->lm.poses_ev) HIPCHK(c, hipEventCreateWithFlags(&c->lm.poses_ev, hipEventDisableTiming));
-  HIPCHK(c, hipEventSynchronize(c->lm.poses_ev));
-  if (c->lm.poses_host_bytes < table) {
-    if (c->lm.poses_host) (void)hipHostFree(c->lm.poses_host);
-    c->lm.poses_host = nullptr;
-    c->lm.poses_host_bytes = 0;
-    HIPCHK(c, hipHostMalloc(&c->lm.poses_host, align_up_sz(table, 4096), hipHostMallocDefault));
-    c->lm.poses_host_bytes = align_up_sz(table, 4096);
-  }
-  // from here on the previous block is being replaced
+  if ((st = c->lm.side.after(c, c->lkw.side, s)) != ORBX_OK) return st;
+  const LmBlock B(n, cap, len);
+  const LmScratch S(n, cap, len);
+  if ((st = c->lm.side.grow(c, c->lm.scr, S.bytes)) != ORBX_OK) return st;
+  if ((st = c->lm.side.grow(c, c->lm.blk, B.bytes)) != ORBX_OK) return st;
+  // from here on the previous block is being replaced (a larger one has already taken its place)
   c->lm.n = 0;
   c->lm.solved = false;
-  std::memcpy(c->lm.poses_host, poses6, table);
   uint8_t* scr = (uint8_t*)c->lm.scr.p;
-  HIPCHK(c, hipMemcpyAsync(scr + S.poses, c->lm.poses_host, table, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipEventRecord(c->lm.poses_ev, s));
+  st = c->lm.poses_up.send(c, scr + S.poses, poses6, sizeof(double) * 6 * (size_t)n * len, s);
+  if (st != ORBX_OK) return st;
   HIPCHK(c, orbx_launch_landmarks(s, K, (const double*)(scr + S.poses), d_tracks, d_seen, n, cap, len,
                                   (double*)(scr + S.cand), scr + S.keep, (int32_t*)(scr + S.partial),
                                   (int32_t*)(scr + S.gate), lm_pointers(c, B)));
@@ -180,15 +91,14 @@ int orbx_landmarks_build_device(orbx_ctx* c, const double* K, const float* d_tra
   if (!c) return ORBX_ERR_INVALID_ARG;
   const int st = lm_check_build(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, poses6);
   if (st != ORBX_OK) return st;
-  return lm_run(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, poses6,
-                stream ? (hipStream_t)stream : c->stream);
+  return lm_run(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, poses6, stream_of(c, stream));
 }
 
 int orbx_landmarks_results_device(orbx_ctx* c, orbx_landmarks_view* v) {
   DeviceGuard _dg(c);
   if (!c || !v) return ORBX_ERR_INVALID_ARG;
   if (c->lm.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no landmarks block has been built");
-  const OrbxLmBlock P = lm_pointers(c, lm_block(c->lm.n, c->lm.cap, c->lm.len));
+  const OrbxLmBlock P = lm_pointers(c, LmBlock(c->lm.n, c->lm.cap, c->lm.len));
   v->status = P.status;
   v->pose_offset = P.pose_off;
   v->point_offset = P.pt_off;
@@ -214,7 +124,7 @@ int orbx_landmarks_fetch(orbx_ctx* c, int first, int n, int32_t* status, int32_t
   if (st != ORBX_OK) return st;
   if (point_capacity < 0 || obs_capacity < 0) return fail(c, ORBX_ERR_INVALID_ARG, "a capacity is negative");
   if ((st = c->lm.side.wait(c)) != ORBX_OK) return st;
-  const OrbxLmBlock P = lm_pointers(c, lm_block(c->lm.n, c->lm.cap, c->lm.len));
+  const OrbxLmBlock P = lm_pointers(c, LmBlock(c->lm.n, c->lm.cap, c->lm.len));
   const size_t noff = (size_t)n + 1;
   std::vector<int32_t> po(noff), oo(noff);
   HIPCHK(c, hipMemcpy(po.data(), P.pt_off + first, sizeof(int32_t) * noff, hipMemcpyDeviceToHost));
@@ -263,27 +173,17 @@ int orbx_bundle_adjust_landmarks_device(orbx_ctx* c, double huber_delta, int max
   if (!c) return ORBX_ERR_INVALID_ARG;
   if (!ba_params_ok(huber_delta, max_iters)) return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
   if (c->lm.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no landmarks block has been built");
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s = stream_of(c, stream);
   int st = c->lm.side.enter(c, s);
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->lm.side, s};
   const int n = c->lm.n, cap = c->lm.cap, len = c->lm.len, ocap = cap * len;
-  // workgroups: as many as windows, bounded by ORBX_BA_MAX_GROUPS and by the workspace budget
-  const size_t per_group =
-      sizeof(double) * ((size_t)ORBX_BA_WS_POINT * cap + (size_t)ORBX_BA_WS_OBS * ocap) + 8 * (size_t)cap;
-  int groups = std::min(n, ORBX_BA_MAX_GROUPS);
-  groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)groups, ORBX_BA_WS_BUDGET / per_group));
-  Taker t;
-  const size_t o_wp = t.take(sizeof(double) * ORBX_BA_WS_POINT * (size_t)cap * groups);
-  const size_t o_wo = t.take(sizeof(double) * ORBX_BA_WS_OBS * (size_t)ocap * groups);
-  const size_t o_slot = t.take(8 * (size_t)cap * groups);
-  const LmSolve V = lm_solve(n, cap, len);
-  if ((st = lm_grow(c, c->lm.ws, t.off)) != ORBX_OK) return st;
-  const void* old_sol = c->lm.sol.p;
-  if ((st = lm_grow(c, c->lm.sol, V.bytes)) != ORBX_OK) return st;
-  if (c->lm.sol.p != old_sol) c->lm.solved = false;
-  const OrbxLmBlock P = lm_pointers(c, lm_block(n, cap, len));
-  const LmScratch S = lm_scratch(n, cap, len);
+  const LmWork W(n, cap, len);
+  const LmSolve V(n, cap, len);
+  if ((st = c->lm.side.grow(c, c->lm.ws, W.bytes)) != ORBX_OK) return st;
+  if ((st = c->lm.side.grow(c, c->lm.sol, V.bytes)) != ORBX_OK) return st;
+  const OrbxLmBlock P = lm_pointers(c, LmBlock(n, cap, len));
+  const LmScratch S(n, cap, len);
   uint8_t* sol = (uint8_t*)c->lm.sol.p;
   uint8_t* ws = (uint8_t*)c->lm.ws.p;
   c->lm.solved = false;
@@ -292,9 +192,9 @@ int orbx_bundle_adjust_landmarks_device(orbx_ctx* c, double huber_delta, int max
                            hipMemcpyDeviceToDevice, s));
   HIPCHK(c, hipMemcpyAsync(sol + V.points, P.points3, sizeof(double) * 3 * (size_t)n * cap, hipMemcpyDeviceToDevice, s));
   const double K4[4] = {c->lm.K[0], c->lm.K[4], c->lm.K[2], c->lm.K[5]};
-  HIPCHK(c, orbx_launch_ba(s, n, groups, max_iters, K4, huber_delta, P.pose_off, P.pt_off, P.obs_off,
+  HIPCHK(c, orbx_launch_ba(s, n, W.groups, max_iters, K4, huber_delta, P.pose_off, P.pt_off, P.obs_off,
                            (double*)(sol + V.poses), (double*)(sol + V.points), P.rows, P.opose, P.oxy, cap, ocap,
-                           (double*)(ws + o_wp), (double*)(ws + o_wo), (unsigned long long*)(ws + o_slot),
+                           (double*)(ws + W.wp), (double*)(ws + W.wo), (unsigned long long*)(ws + W.slot),
                            sol + V.out));
   c->lm.solved = true;
   return ORBX_OK;
@@ -309,8 +209,8 @@ int orbx_bundle_adjust_landmarks_fetch(orbx_ctx* c, int first, int n, double* po
   if (!c->lm.solved) return fail(c, ORBX_ERR_INVALID_ARG, "the landmarks block has not been solved");
   if (capacity < 0) return fail(c, ORBX_ERR_INVALID_ARG, "a capacity is negative");
   if ((st = c->lm.side.wait(c)) != ORBX_OK) return st;
-  const OrbxLmBlock P = lm_pointers(c, lm_block(c->lm.n, c->lm.cap, c->lm.len));
-  const LmSolve V = lm_solve(c->lm.n, c->lm.cap, c->lm.len);
+  const OrbxLmBlock P = lm_pointers(c, LmBlock(c->lm.n, c->lm.cap, c->lm.len));
+  const LmSolve V(c->lm.n, c->lm.cap, c->lm.len);
   const uint8_t* sol = (const uint8_t*)c->lm.sol.p;
   int32_t p0 = 0, p1 = 0;
   HIPCHK(c, hipMemcpy(&p0, P.pt_off + first, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -338,21 +238,11 @@ int orbx_bundle_adjust_tracks(orbx_ctx* c, const double* K, const float* tracks_
   if (st != ORBX_OK) return st;
   if (!ba_params_ok(huber_delta, max_iters) || !lm_status || !summary || capacity < 0)
     return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
-  hipStream_t s = c->stream;
-  if ((st = c->lm.side.enter(c, s)) != ORBX_OK) return st;
-  const size_t tb = sizeof(float) * 2 * (size_t)n_slots * window_len;
-  const size_t o_seen = align_up_sz(tb, 256);
-  {
-    const SideWork::Mark mark{c->lm.side, s};
-    if ((st = lm_grow(c, c->lm.stage, o_seen + sizeof(int32_t) * (size_t)n_slots)) != ORBX_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(c->lm.stage.p, tracks_xy, tb, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync((uint8_t*)c->lm.stage.p + o_seen, seen, sizeof(int32_t) * (size_t)n_slots,
-                             hipMemcpyHostToDevice, s));
-  }
-  const uint8_t* stage = (const uint8_t*)c->lm.stage.p;
-  if ((st = lm_run(c, K, (const float*)stage, (const int32_t*)(stage + o_seen), 1, n_slots, window_len, poses6, s)) !=
-      ORBX_OK)
+  const float* d_tracks;
+  const int32_t* d_seen;
+  if ((st = stage_tracks(c, c->lm.side, c->lm.stage, tracks_xy, seen, n_slots, window_len, &d_tracks, &d_seen)) != ORBX_OK)
     return st;
+  if ((st = lm_run(c, K, d_tracks, d_seen, 1, n_slots, window_len, poses6, c->stream)) != ORBX_OK) return st;
   if ((st = orbx_bundle_adjust_landmarks_device(c, huber_delta, max_iters, nullptr)) != ORBX_OK) return st;
   int np = 0;
   if ((st = orbx_bundle_adjust_landmarks_fetch(c, 0, 1, nullptr, nullptr, nullptr, 0, &np)) != ORBX_OK) return st;

@@ -10,29 +10,6 @@ using namespace orbx_host;
 // ---- pyramidal Lucas-Kanade tracking (src/feature_tracking.cpp:166-193) ------------------
 
 namespace {
-struct LkGeom {
-  int top = 0;
-  int w[ORBX_LK_MAX_LEVELS], h[ORBX_LK_MAX_LEVELS], pitch[ORBX_LK_MAX_LEVELS];
-  size_t img_off[ORBX_LK_MAX_LEVELS], der_off[ORBX_LK_MAX_LEVELS];
-  size_t img_bytes = 0, der_bytes = 0;
-};
-// buildOpticalFlowPyramid: halve ((w+1)/2) until a level would not be larger than the window
-LkGeom lk_geometry(int w, int h, int win, int max_level) {
-  LkGeom g;
-  for (int l = 0; l <= max_level; l++) {
-    const int lw = l == 0 ? w : (g.w[l - 1] + 1) / 2, lh = l == 0 ? h : (g.h[l - 1] + 1) / 2;
-    if (l > 0 && (lw <= win || lh <= win)) break;
-    g.w[l] = lw;
-    g.h[l] = lh;
-    g.pitch[l] = lw;  // tight: a host image with stride == width goes up in ONE contiguous copy
-    g.img_off[l] = g.img_bytes;
-    g.img_bytes += align_up_sz((size_t)g.pitch[l] * lh, 256);
-    g.der_off[l] = g.der_bytes;
-    g.der_bytes += align_up_sz((size_t)lw * lh * 4, 256);
-    g.top = l;
-  }
-  return g;
-}
 OrbxLkPyr lk_pyr(const LkGeom& g, const uint8_t* img, const uint8_t* deriv) {
   OrbxLkPyr P;
   std::memset(&P, 0, sizeof(P));
@@ -77,7 +54,7 @@ int orbx_lk_track(orbx_ctx* c, const uint8_t* prev, int prev_stride, const uint8
   // TermCriteria sanitising of calcOpticalFlowPyrLK
   max_iters = std::min(std::max(max_iters, 0), 100);
   epsilon = std::min(std::max(epsilon, 0.0), 10.0);
-  const LkGeom g = lk_geometry(width, height, win_size, max_level);
+  const LkGeom g(width, height, win_size, max_level);
   int st;
   int ip;  // buffer holding the `prev` pyramid
   if (prev) {
@@ -136,7 +113,7 @@ int orbx_lk_track(orbx_ctx* c, const uint8_t* prev, int prev_stride, const uint8
 int orbx_lk_pyramid_levels(int width, int height, int win_size, int max_level) {
   if (width < 1 || height < 1 || win_size < 3 || win_size > 31 || max_level < 0 || max_level >= ORBX_LK_MAX_LEVELS)
     return -1;
-  return lk_geometry(width, height, win_size, max_level).top + 1;
+  return LkGeom(width, height, win_size, max_level).top + 1;
 }
 
 }  // extern "C"
@@ -146,47 +123,6 @@ int orbx_lk_pyramid_levels(int width, int height, int win_size, int max_level) {
 // frames, track_optical_flow (src/feature_tracking.cpp:166-193) over a stream.
 
 namespace {
-
-// the workspace of ONE frame: the pyramid levels above 0 (level 0 is read in place), then the derivative maps of
-// every level
-struct LkwLayout {
-  LkGeom g;
-  size_t img_bytes, frame_bytes;  // levels 1 .. top; img_bytes + derivative maps
-};
-LkwLayout lkw_layout(int w, int h, int win, int max_level) {
-  LkwLayout o;
-  o.g = lk_geometry(w, h, win, max_level);
-  o.img_bytes = o.g.top >= 1 ? o.g.img_bytes - o.g.img_off[1] : 0;
-  o.frame_bytes = o.img_bytes + o.g.der_bytes;
-  return o;
-}
-
-// a buffer of the windows path of at least `bytes`: the new allocation is made BEFORE the old one is released, so
-// that a failed call keeps what it had
-int lkw_grow(orbx_ctx* c, DevBuf& b, size_t bytes) {
-  if (b.p && b.bytes >= bytes) return ORBX_OK;
-  const int st = c->lkw.side.wait(c);  // (the old allocation may still be read or written)
-  if (st != ORBX_OK) return st;
-  bytes = align_up_sz(std::max<size_t>(bytes, 256), 256);
-  void* p = nullptr;
-  HIPCHK(c, hipMalloc(&p, bytes));
-  if (b.p) (void)hipFree(b.p);
-  b.p = p;
-  b.bytes = bytes;
-  return ORBX_OK;
-}
-
-struct LkwResult {
-  size_t o_seen, o_err, bytes;  // tracks at 0
-};
-LkwResult lkw_result(int n_windows, int cap, int len) {
-  LkwResult r;
-  const size_t slots = (size_t)n_windows * cap;
-  r.o_seen = align_up_sz(sizeof(float) * 2 * slots * len, 256);
-  r.o_err = align_up_sz(r.o_seen + sizeof(int32_t) * slots, 256);
-  r.bytes = r.o_err + sizeof(float) * slots * (len - 1);
-  return r;
-}
 
 FramesWhat lkw_frames_what(int max_frames) {
   return {"frames is NULL", "n_frames outside [2, " + std::to_string(max_frames) + "]"};
@@ -210,34 +146,17 @@ int lkw_run(orbx_ctx* c, const uint8_t* d_frames, int n_frames, int w, int h, in
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->lkw.side, s};
   // points and counts may be the good-features block, written on another stream
-  if (c->gf.side.ev && c->gf.side.stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->gf.side.ev, 0));
-  const LkwLayout L = lkw_layout(w, h, win, max_level);
-  // frames per slice: what the limit holds, at least one window, at most the batch
-  const size_t fit =
-      std::min<size_t>(std::max<size_t>(c->lkw.ws_limit / L.frame_bytes, (size_t)window_len), (size_t)n_frames);
-  const LkwResult R = lkw_result(n_windows, cap, window_len);
-  if ((st = lkw_grow(c, c->lkw.ws, fit * L.frame_bytes + 256)) != ORBX_OK) return st;
-  if ((st = lkw_grow(c, c->lkw.first, sizeof(int32_t) * (size_t)n_windows)) != ORBX_OK) return st;
-  const void* old_res = c->lkw.res.p;
-  if ((st = lkw_grow(c, c->lkw.res, R.bytes)) != ORBX_OK) return st;
-  if (c->lkw.res.p != old_res) c->lkw.n = 0;  // (a larger block: the previous result went with the old one)
-  // The window table goes up through a pinned mirror (a copy from pageable memory would make the host wait for the
-  // stream).  The mirror is reused: the previous call's copy has to have read it.
+  if ((st = c->lkw.side.after(c, c->gf.side, s)) != ORBX_OK) return st;
+  const LkwLayout L(w, h, win, max_level);
+  const size_t fit = lkw_fit(c->lkw.ws_limit, L, window_len, n_frames);  // frames per slice
+  const LkwResult R(n_windows, cap, window_len);
   const size_t table = sizeof(int32_t) * (size_t)n_windows;
-  if (!c->lkw.first_ev) HIPCHK(c, hipEventCreateWithFlags(&c->lkw.first_ev, hipEventDisableTiming));
-  HIPCHK(c, hipEventSynchronize(c->lkw.first_ev));
-  if (c->lkw.first_host_bytes < table) {
-    if (c->lkw.first_host) (void)hipHostFree(c->lkw.first_host);
-    c->lkw.first_host = nullptr;
-    c->lkw.first_host_bytes = 0;
-    HIPCHK(c, hipHostMalloc(&c->lkw.first_host, align_up_sz(table, 4096), hipHostMallocDefault));
-    c->lkw.first_host_bytes = align_up_sz(table, 4096);
-  }
-  // from here on the previous result is being replaced
+  if ((st = c->lkw.side.grow(c, c->lkw.ws, lkw_workspace_bytes(L, fit))) != ORBX_OK) return st;
+  if ((st = c->lkw.side.grow(c, c->lkw.first, table)) != ORBX_OK) return st;
+  if ((st = c->lkw.side.grow(c, c->lkw.res, R.bytes)) != ORBX_OK) return st;
+  // from here on the previous result is being replaced (a larger block has already taken its place)
   c->lkw.n = 0;
-  std::memcpy(c->lkw.first_host, window_first, table);
-  HIPCHK(c, hipMemcpyAsync(c->lkw.first.p, c->lkw.first_host, table, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipEventRecord(c->lkw.first_ev, s));
+  if ((st = c->lkw.first_up.send(c, c->lkw.first.p, window_first, table, s)) != ORBX_OK) return st;
   uint8_t* ws = (uint8_t*)c->lkw.ws.p;
   uint8_t* res = (uint8_t*)c->lkw.res.p;
   const LkGeom& g = L.g;
@@ -255,7 +174,7 @@ int lkw_run(orbx_ctx* c, const uint8_t* d_frames, int n_frames, int w, int h, in
     }
     const int m = hi - lo;
     uint8_t* ws_img = ws;                                // [m][levels 1 .. top]
-    uint8_t* ws_der = ws + align_up_sz(L.img_bytes * m, 256);  // [m][levels 0 .. top]
+    uint8_t* ws_der = ws + lkw_der_offset(L, m);         // [m][levels 0 .. top]
     const uint8_t* f_lo = d_frames + frame_stride * (size_t)lo;
     for (int l = 1; l <= g.top; l++) {
       const uint8_t* src = l == 1 ? f_lo : ws_img + (g.img_off[l - 1] - img_base);
@@ -316,20 +235,20 @@ int orbx_lk_track_windows_device(orbx_ctx* c, const void* d_frames, int n_frames
       return fail(c, ORBX_ERR_INVALID_ARG, "a window does not lie inside the frames");
   return lkw_run(c, (const uint8_t*)d_frames, n_frames, width, height, row_stride, frame_stride, window_first,
                  n_windows, window_len, d_points_xy, d_counts, slot_capacity, win_size, max_level, max_iters, epsilon,
-                 stream ? (hipStream_t)stream : c->stream);
+                 stream_of(c, stream));
 }
 
 int orbx_lk_workspace_limit(orbx_ctx* c, size_t bytes) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
-  return set_workspace_limit(c, c->lkw.side, c->lkw.ws, &c->lkw.ws_limit, bytes, ORBX_LK_WORKSPACE_DEFAULT);
+  return set_workspace_limit(c, c->lkw.side, {&c->lkw.ws}, &c->lkw.ws_limit, bytes, ORBX_LK_WORKSPACE_DEFAULT);
 }
 
 int orbx_lk_windows_results_device(orbx_ctx* c, orbx_lk_windows_view* v) {
   DeviceGuard _dg(c);
   if (!c || !v) return ORBX_ERR_INVALID_ARG;
   if (c->lkw.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
-  const LkwResult R = lkw_result(c->lkw.n, c->lkw.cap, c->lkw.len);
+  const LkwResult R(c->lkw.n, c->lkw.cap, c->lkw.len);
   const uint8_t* res = (const uint8_t*)c->lkw.res.p;
   v->tracks_xy = (const float*)res;
   v->seen = (const int32_t*)(res + R.o_seen);
@@ -344,11 +263,11 @@ int orbx_lk_windows_fetch(orbx_ctx* c, int first, int n, float* tracks_xy, int32
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
   if (c->lkw.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
-  if (first < 0 || n < 1 || first >= c->lkw.n || n > c->lkw.n - first)
+  if (!range_ok(first, n, c->lkw.n))
     return fail(c, ORBX_ERR_INVALID_ARG, "[first, first + n) outside the batch");
   const int st = c->lkw.side.wait(c);
   if (st != ORBX_OK) return st;
-  const LkwResult R = lkw_result(c->lkw.n, c->lkw.cap, c->lkw.len);
+  const LkwResult R(c->lkw.n, c->lkw.cap, c->lkw.len);
   const uint8_t* res = (const uint8_t*)c->lkw.res.p;
   const size_t slots = (size_t)c->lkw.cap, len = (size_t)c->lkw.len;
   if (tracks_xy)
@@ -380,8 +299,8 @@ int orbx_lk_track_window(orbx_ctx* c, const uint8_t* frames, int n_frames, int w
   const size_t tight = (size_t)width * height;
   {
     const SideWork::Mark mark{c->lkw.side, c->stream};
-    if ((st = lkw_grow(c, c->lkw.img, tight * n_frames)) != ORBX_OK) return st;
-    if ((st = lkw_grow(c, c->lkw.pts, sizeof(float) * 2 * (size_t)n)) != ORBX_OK) return st;
+    if ((st = c->lkw.side.grow(c, c->lkw.img, tight * n_frames)) != ORBX_OK) return st;
+    if ((st = c->lkw.side.grow(c, c->lkw.pts, sizeof(float) * 2 * (size_t)n)) != ORBX_OK) return st;
     if (row_stride == width && frame_stride == tight) {
       HIPCHK(c, hipMemcpyAsync(c->lkw.img.p, frames, tight * n_frames, hipMemcpyHostToDevice, c->stream));
     } else {

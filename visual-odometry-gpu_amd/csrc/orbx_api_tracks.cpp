@@ -14,45 +14,6 @@ static_assert(sizeof(orbx_tracks_scale_result) == sizeof(OrbxScaleOut), "orbx_tr
 
 namespace {
 
-// a buffer of the tracks-pose path of at least `bytes`: the new allocation is made BEFORE the old one is released, so
-// that a failed call keeps what it had
-int tp_grow(orbx_ctx* c, DevBuf& b, size_t bytes) {
-  if (b.p && b.bytes >= bytes) return ORBX_OK;
-  const int st = c->tp.side.wait(c);  // (the old allocation may still be read or written)
-  if (st != ORBX_OK) return st;
-  bytes = align_up_sz(std::max<size_t>(bytes, 256), 256);
-  void* p = nullptr;
-  HIPCHK(c, hipMalloc(&p, bytes));
-  if (b.p) (void)hipFree(b.p);
-  b.p = p;
-  b.bytes = bytes;
-  return ORBX_OK;
-}
-
-// the result block: one row of `cap` per pair in every per-position array
-struct TpBlock {
-  size_t pose, n, scale, slot_of, mask, xyz, valid, bytes;
-};
-TpBlock tp_block(int n_windows, int cap, int len) {
-  TpBlock L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t r = off;
-    off = align_up_sz(off + bytes, 256);
-    return r;
-  };
-  const size_t pairs = (size_t)n_windows * (len - 1), e = pairs * cap;
-  L.pose = take(sizeof(OrbxPoseOut) * pairs);
-  L.n = take(sizeof(int32_t) * pairs);
-  L.scale = take(sizeof(OrbxScaleOut) * pairs);
-  L.slot_of = take(sizeof(int32_t) * e);
-  L.mask = take(e);
-  L.xyz = take(sizeof(float) * 3 * e);
-  L.valid = take(e);
-  L.bytes = off;
-  return L;
-}
-
 int tp_pairs(const orbx_ctx* c) { return c->tp.n * (c->tp.len - 1); }
 
 int tp_check(orbx_ctx* c, const double* K, const void* tracks, const void* seen, int n, int cap, int len, double prob,
@@ -76,11 +37,11 @@ int tp_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->tp.side, s};
   // the tracks may be the windows tracker's block, written on another stream
-  if (c->lkw.side.ev && c->lkw.side.stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->lkw.side.ev, 0));
-  const TpBlock B = tp_block(n, cap, len);
+  if ((st = c->tp.side.after(c, c->lkw.side, s)) != ORBX_OK) return st;
+  const TpBlock B(n, cap, len);
   const int pairs = n * (len - 1);
-  if ((st = tp_grow(c, c->tp.scr, sizeof(OrbxPosePt) * (size_t)pairs * cap)) != ORBX_OK) return st;
-  if ((st = tp_grow(c, c->tp.blk, B.bytes)) != ORBX_OK) return st;
+  if ((st = c->tp.side.grow(c, c->tp.scr, tp_scratch_bytes(n, cap, len))) != ORBX_OK) return st;
+  if ((st = c->tp.side.grow(c, c->tp.blk, B.bytes)) != ORBX_OK) return st;
   // from here on the previous block is being replaced (a larger one has already taken its place)
   c->tp.n = 0;
   uint8_t* b = (uint8_t*)c->tp.blk.p;
@@ -114,14 +75,14 @@ int orbx_tracks_pose_device(orbx_ctx* c, const double* K, const float* d_tracks_
   const int st = tp_check(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, prob, threshold, max_iters);
   if (st != ORBX_OK) return st;
   return tp_run(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, prob, threshold, max_iters, seed,
-                stream ? (hipStream_t)stream : c->stream);
+                stream_of(c, stream));
 }
 
 int orbx_tracks_pose_results_device(orbx_ctx* c, orbx_tracks_pose_view* v) {
   DeviceGuard _dg(c);
   if (!c || !v) return ORBX_ERR_INVALID_ARG;
   if (c->tp.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no tracks have been posed");
-  const TpBlock B = tp_block(c->tp.n, c->tp.cap, c->tp.len);
+  const TpBlock B(c->tp.n, c->tp.cap, c->tp.len);
   const uint8_t* b = (const uint8_t*)c->tp.blk.p;
   v->pose = (const orbx_tracks_pose_result*)(b + B.pose);
   v->n = (const int32_t*)(b + B.n);
@@ -143,12 +104,12 @@ int orbx_tracks_pose_fetch(orbx_ctx* c, int first, int n, double* E, double* R, 
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
   if (c->tp.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no tracks have been posed");
-  if (first < 0 || n < 0 || first > tp_pairs(c) || n > tp_pairs(c) - first)
+  if (!range_ok(first, n, tp_pairs(c), 0))
     return fail(c, ORBX_ERR_INVALID_ARG, "pairs outside the last tracks-pose block");
   if (n == 0) return ORBX_OK;
   const int st = c->tp.side.wait(c);
   if (st != ORBX_OK) return st;
-  const TpBlock B = tp_block(c->tp.n, c->tp.cap, c->tp.len);
+  const TpBlock B(c->tp.n, c->tp.cap, c->tp.len);
   const uint8_t* b = (const uint8_t*)c->tp.blk.p;
   if (E || R || t || inliers || good || iters) {
     std::vector<OrbxPoseOut> r((size_t)n);
@@ -182,7 +143,7 @@ int orbx_tracks_pose_pair_fetch(orbx_ctx* c, int pair, int32_t* slot_of, uint8_t
   if (pair < 0 || pair >= tp_pairs(c)) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last tracks-pose block");
   const int st = c->tp.side.wait(c);
   if (st != ORBX_OK) return st;
-  const TpBlock B = tp_block(c->tp.n, c->tp.cap, c->tp.len);
+  const TpBlock B(c->tp.n, c->tp.cap, c->tp.len);
   const uint8_t* b = (const uint8_t*)c->tp.blk.p;
   int32_t np = 0;
   HIPCHK(c, hipMemcpy(&np, (const int32_t*)(b + B.n) + pair, sizeof np, hipMemcpyDeviceToHost));
@@ -206,20 +167,12 @@ int orbx_tracks_pose(orbx_ctx* c, const double* K, const float* tracks_xy, const
   if (!c) return ORBX_ERR_INVALID_ARG;
   int st = tp_check(c, K, tracks_xy, seen, 1, n_slots, window_len, prob, threshold, max_iters);
   if (st != ORBX_OK) return st;
-  hipStream_t s = c->stream;
-  if ((st = c->tp.side.enter(c, s)) != ORBX_OK) return st;
-  const size_t tb = sizeof(float) * 2 * (size_t)n_slots * window_len;
-  const size_t o_seen = align_up_sz(tb, 256);
-  {
-    const SideWork::Mark mark{c->tp.side, s};
-    if ((st = tp_grow(c, c->tp.stage, o_seen + sizeof(int32_t) * (size_t)n_slots)) != ORBX_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(c->tp.stage.p, tracks_xy, tb, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync((uint8_t*)c->tp.stage.p + o_seen, seen, sizeof(int32_t) * (size_t)n_slots,
-                             hipMemcpyHostToDevice, s));
-  }
-  const uint8_t* stage = (const uint8_t*)c->tp.stage.p;
-  if ((st = tp_run(c, K, (const float*)stage, (const int32_t*)(stage + o_seen), 1, n_slots, window_len, prob,
-                   threshold, max_iters, seed, s)) != ORBX_OK)
+  const float* d_tracks;
+  const int32_t* d_seen;
+  if ((st = stage_tracks(c, c->tp.side, c->tp.stage, tracks_xy, seen, n_slots, window_len, &d_tracks, &d_seen)) != ORBX_OK)
+    return st;
+  if ((st = tp_run(c, K, d_tracks, d_seen, 1, n_slots, window_len, prob, threshold, max_iters, seed, c->stream)) !=
+      ORBX_OK)
     return st;
   return orbx_tracks_pose_fetch(c, 0, window_len - 1, E, R, t, inliers, good, iters, counts, scale, triplets,
                                 ratios_used);

@@ -11,10 +11,12 @@
 #include <vector>
 
 #include "orbx_internal.h"
+#include "orbx_layout.h"
 
 namespace orbx_host {
 
-using namespace orbx_geom;  // orbx_plan.h: the geometry of a frame size and the tables built from it
+using namespace orbx_geom;    // orbx_plan.h: the geometry of a frame size and the tables built from it
+using namespace orbx_layout;  // orbx_layout.h: the sections of every block
 
 struct DevBuf {
   void* p = nullptr;
@@ -26,40 +28,9 @@ inline void free_bufs(std::initializer_list<DevBuf*> bufs) {
     if (b->p) (void)hipFree(b->p);
 }
 
-// result block of a batch: one device allocation + one pinned host mirror so
-// a whole batch comes back with a single D2H copy
-// sections: counts | kp16 | angle | desc || kp | lkp | resp | level -- what the reference's own output consists of
-// (keypoints, orientations, descriptors: include/orb.hpp:37) first, so that orbx_batch_prefetch_compact moves one
-// contiguous prefix of `compact` bytes
-struct OutLayout {
-  size_t counts, kp16, kp, lkp, angle, resp, level, desc, compact, total;
-};
-
-inline OutLayout make_out_layout(int n, int cap) {
-  OutLayout o;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t r = off;
-    off = align_up_sz(off + bytes, 256);
-    return r;
-  };
-  const size_t e = (size_t)n * (size_t)cap;
-  // the compact record first (orbx_batch_prefetch_compact copies [0, compact)): 40 bytes per slot
-  o.counts = take(sizeof(int32_t) * (size_t)n);
-  o.kp16 = take(sizeof(uint32_t) * e);
-  o.angle = take(sizeof(float) * e);
-  o.desc = take(sizeof(orbx_descriptor) * e);
-  o.compact = off;
-  o.kp = take(sizeof(orbx_keypoint) * e);
-  o.lkp = take(sizeof(orbx_keypoint) * e);
-  o.resp = take(sizeof(float) * e);
-  o.level = take(sizeof(int32_t) * e);
-  o.total = off;
-  return o;
-}
-
-// One block of the ring of result blocks (orbx_ctx::blocks): the device allocation, its pinned host mirror and
-// what the batch that last wrote it left there.
+// One block of the ring of result blocks (orbx_ctx::blocks): the device allocation (OutLayout of orbx_layout.h), its
+// pinned host mirror -- a whole batch comes back with a single D2H copy -- and what the batch that last wrote it left
+// there.
 struct Block {
   uint8_t* d = nullptr;
   uint8_t* h = nullptr;      // pinned mirror
@@ -129,9 +100,9 @@ int fail(orbx_ctx* c, int status, const std::string& msg);  // (c == NULL: the t
   } while (0)
 
 // Work that runs beside the batched path on ANY caller's stream, with one workspace and one result block per context
-// (good features, LK windows).  `stream` is the stream the last call ran on, kept for COMPARISON only (a caller's
-// stream may be gone by the next call); `ev` is recorded behind that call's work: what later calls, fetches and
-// orbx_destroy wait for.
+// (good features, LK windows, landmarks, tracks pose).  `stream` is the stream the last call ran on, kept for
+// COMPARISON only (a caller's stream may be gone by the next call); `ev` is recorded behind that call's work: what
+// later calls, fetches and orbx_destroy wait for.
 struct SideWork {
   hipStream_t stream = nullptr;
   hipEvent_t ev = nullptr;
@@ -140,6 +111,12 @@ struct SideWork {
   int wait(orbx_ctx* c);
   // a call on stream s: earlier work on another stream has to be done (one workspace, one result block)
   int enter(orbx_ctx* c, hipStream_t s);
+  // a call on s reads what `producer` left, perhaps on another stream: s waits for the producer's event
+  int after(orbx_ctx* c, const SideWork& producer, hipStream_t s);
+  // a buffer of this work of at least `bytes`.  One that grows first waits for the event (the old allocation may
+  // still be read or written); the new allocation is made BEFORE the old one is released, so that a failed call
+  // keeps what it had
+  int grow(orbx_ctx* c, DevBuf& b, size_t bytes);
   // records the event behind whatever a call has enqueued on s, on every way out of the call
   struct Mark {
     SideWork& w;
@@ -153,6 +130,19 @@ struct SideWork {
     if (!ev) return;
     (void)hipEventSynchronize(ev);
     (void)hipEventDestroy(ev);
+  }
+};
+
+// A small host table that goes up through a pinned mirror (a copy from pageable memory would make the host wait for
+// the stream).  The mirror is reused: `ev` is recorded behind every copy, and the next one first waits for it.
+struct PinnedUpload {
+  void* host = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;
+  int send(orbx_ctx* c, void* d_dst, const void* src, size_t n, hipStream_t s);
+  void release() {
+    if (ev) (void)hipEventDestroy(ev);
+    if (host) (void)hipHostFree(host);
   }
 };
 
@@ -188,21 +178,18 @@ struct LkPair {
   }
 };
 
-// Lucas-Kanade over frame windows (k_lk_track_windows): the workspace of one slice of frames (pyramid levels above
-// 0 | derivative maps), bounded by ws_limit; the window table; the staged frames and points of the one-window
-// host entry; and the entry's OWN result block (tracks | seen | err).  Nothing here is shared with orbx_lk_track.
+// Lucas-Kanade over frame windows (k_lk_track_windows): the workspace of one slice of frames, bounded by ws_limit;
+// the window table; the staged frames and points of the one-window host entry; and the entry's OWN result block
+// (LkwLayout, LkwResult of orbx_layout.h).  Nothing here is shared with orbx_lk_track.
 struct LkWindows {
   DevBuf ws, first, img, pts, res;
   size_t ws_limit = ORBX_LK_WORKSPACE_DEFAULT;
   int n = 0, cap = 0, len = 0;  // windows, slots per window, frames per window of the last call (0: none)
   SideWork side;                // the event is recorded behind every windows call
-  void* first_host = nullptr;   // pinned mirror of the window table, and the event behind its upload
-  size_t first_host_bytes = 0;
-  hipEvent_t first_ev = nullptr;
+  PinnedUpload first_up;        // the window table's way up
   void release() {
     side.release();
-    if (first_ev) (void)hipEventDestroy(first_ev);
-    if (first_host) (void)hipHostFree(first_host);
+    first_up.release();
     free_bufs({&ws, &first, &img, &pts, &res});
   }
 };
@@ -236,30 +223,26 @@ struct BundleAdjust {
 };
 
 // landmarks of tracked windows and their bundle adjustment on the device (orbx_landmarks.hip, orbx_ba.hip): the
-// scratch of a build (pose table | gate | partial counts | keep flags | candidate points), the entry's OWN result
-// block (statuses | offsets | slot_of_point | rows | points3 | oxy | opose: what k_ba_lm reads), the solve's copies of
-// poses and points with its summaries, the solve's workspaces, and the staged tracks of the one-window host entry.
-// Nothing here is shared with orbx_bundle_adjust_batch.
+// scratch of a build, the entry's OWN result block (what k_ba_lm reads), the solve's copies of poses and points with
+// its summaries, the solve's workspaces (LmScratch, LmBlock, LmSolve, LmWork of orbx_layout.h), and the staged tracks
+// of the one-window host entry.  Nothing here is shared with orbx_bundle_adjust_batch.
 struct Landmarks {
   DevBuf scr, blk, sol, ws, stage;
   double K[9] = {};
   int n = 0, cap = 0, len = 0;  // windows, slots per window, poses per window of the last build (0: none)
   bool solved = false;          // the block has been solved since it was built
   SideWork side;                // the event is recorded behind every build and every solve
-  void* poses_host = nullptr;   // pinned mirror of the pose table, and the event behind its upload
-  size_t poses_host_bytes = 0;
-  hipEvent_t poses_ev = nullptr;
+  PinnedUpload poses_up;        // the pose table's way up
   void release() {
     side.release();
-    if (poses_ev) (void)hipEventDestroy(poses_ev);
-    if (poses_host) (void)hipHostFree(poses_host);
+    poses_up.release();
     free_bufs({&scr, &blk, &sol, &ws, &stage});
   }
 };
 
 // pose and scale of tracked frame pairs (orbx_tracks.hip, k_pose_ransac, k_scale_join): the normalised point lists
-// (scratch), the entry's OWN result block (poses | counts | scales | slot_of | mask | xyz | valid), and the staged
-// tracks of the one-window host entry.  Nothing here is shared with the batch pose / scale entries.
+// (scratch), the entry's OWN result block (TpBlock of orbx_layout.h), and the staged tracks of the one-window host
+// entry.  Nothing here is shared with the batch pose / scale entries.
 struct TracksPose {
   DevBuf scr, blk, stage;
   int n = 0, cap = 0, len = 0;  // windows, slots per window, frames per window of the last call (0: none)
@@ -270,13 +253,11 @@ struct TracksPose {
   }
 };
 
-// Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames (response maps | key pools | cell grids
-// | per-frame maximum and candidate count), allocated on first use and bounded by ws_limit; the staged host
-// image of the one-frame entries; and the entry's OWN result block (counts | corners), untouched by the ORB path.
-// Rank 12 (top-up and masked detection) adds, beside the workspace and for the same number of frames, the bit maps
-// of blocked pixels with the masked maxima (bm: allocated at the first top-up or masked call, freed with the
-// workspace), the staged seeds or mask of the host entries, and a result block of its own (tres: counts | carried |
-// points | origin).
+// Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames, allocated on first use and bounded by
+// ws_limit; the staged host image of the one-frame entries; and the entry's OWN result block, untouched by the ORB
+// path.  Rank 12 (top-up and masked detection) adds, beside the workspace and for the same number of frames, the bit
+// maps of blocked pixels (bm: allocated at the first top-up or masked call, freed with the workspace), the staged
+// seeds or mask of the host entries, and a result block of its own (tres).  Gf-, Gr-, Gb-, GtLayout of orbx_layout.h.
 struct GoodFeatures {
   DevBuf ws, img, res, bm, stage, tres;
   size_t ws_limit = ORBX_GFTT_WORKSPACE_DEFAULT;
@@ -465,8 +446,18 @@ inline void pose_unpack(const OrbxPoseOut& r, double* E, double* R, double* t, i
 int gaussian_kernel(int K, float sigma, float* kernel);
 hipError_t launch_blur_auto(int impl, hipStream_t s, const OrbxPlan& P, const OrbxTileMap& tm1, const OrbxTileDesc* tiles2,
                             int ntiles2, int n, const uint8_t* src, uint8_t* dst, int first_level, int kind);
-// behind both *_workspace_limit entries: the workspace's users have finished, it is released (the next call allocates
-// one within the new limit), and the limit becomes `bytes`, or `dflt` for 0
-int set_workspace_limit(orbx_ctx* c, SideWork& side, DevBuf& ws, size_t* limit, size_t bytes, size_t dflt);
+// behind both *_workspace_limit entries: the users of the workspace (and of what is sized with it) have finished, it
+// is released (the next call allocates one within the new limit), and the limit becomes `bytes`, or `dflt` for 0
+int set_workspace_limit(orbx_ctx* c, SideWork& side, std::initializer_list<DevBuf*> ws, size_t* limit, size_t bytes,
+                        size_t dflt);
+// the stream an entry runs on: the caller's, or the context's own for NULL
+inline hipStream_t stream_of(const orbx_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
+// [first, first + n) lies inside [0, total) and has at least n_min elements
+inline bool range_ok(int first, int n, int total, int n_min = 1) {
+  return first >= 0 && n >= n_min && n <= total - first;
+}
+// one window's tracks | seen from host arrays into `stage`, on the context's stream (the one-window host entries)
+int stage_tracks(orbx_ctx* c, SideWork& side, DevBuf& stage, const float* tracks_xy, const int32_t* seen, int n_slots,
+                 int window_len, const float** d_tracks, const int32_t** d_seen);
 
 }  // namespace orbx_host
