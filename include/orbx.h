@@ -894,6 +894,58 @@ int orbx_good_features_to_track_masked(orbx_ctx* ctx, const uint8_t* image, int 
                                        const uint8_t* mask, int mask_stride, int max_corners, double quality_level,
                                        double min_distance, float* corners_xy, int capacity, int* count);
 
+/* ---- next row: the forward-backward check of Lucas-Kanade over frame windows ------------
+ * What every KLT front end built on cv::calcOpticalFlowPyrLK puts behind the tracker, and the reference's
+ * trackPointsAcrossWindow (src/with_bundle_adjustment.cpp:464-499) and track_optical_flow
+ * (src/feature_tracking.cpp:166-193) leave out: a point that slid along an edge or jumped to a look-alike patch keeps
+ * status 1.  Here every pair of a window is tracked twice in the one tracking launch, with the arithmetic of
+ * orbx_lk_track both times.  For the slot's point p entering pair k (frames window_first[w] + k - 1 and + k):
+ *   1. forward   (q, status, e) = the pair as orbx_lk_track_windows_device tracks it; status 0 ends the track, reason 1
+ *   2. backward  (r, status) = q tracked from frame k back into frame k - 1, starting at q itself (no initial flow),
+ *                same parameters; status 0 ends the track, reason 2
+ *   3. distance  dx = r.x - p.x, dy = r.y - p.y in float; d2 = (double)dx * dx + (double)dy * dy, the products exact,
+ *                the sum rounded once; the pair passes iff d2 <= (double)fb_threshold * (double)fb_threshold.  A NaN
+ *                d2 fails.  Failing ends the track, reason 3
+ *   4. on a pass tracks[k] = q, err[k - 1] = e, fb_d2[k - 1] = (float)d2, and q enters pair k + 1 with the same bits
+ * tracks_xy, seen and err go into the block of orbx_lk_track_windows_device in its layout: after this call
+ * orbx_lk_windows_results_device and orbx_lk_windows_fetch return them, and the landmarks build, the tracks pose and
+ * the top-up read the view as they read any other.  Beside them, in a buffer of their own:
+ *   fb_d2[w][slot][k - 1]  the squared distance of every pair that passed (the first seen - 1 entries), 0 elsewhere
+ *   lost[w][slot]          0 for a track alive through the window and for the slots at or beyond counts[w], else the
+ *                          reason the track ended, 1 / 2 / 3
+ * fb_threshold: NaN or < 0 is ORBX_ERR_INVALID_ARG (nothing is written, the previous result stays fetchable); 0 (only
+ * points that return exactly) and +inf (only the two status tests) are legal.  Every other argument rule, the slices
+ * under the workspace limit, the stream ordering and the workspace are those of orbx_lk_track_windows_device: the
+ * backward pass reads the pyramids and derivative maps that call builds for every frame of a slice anyway. */
+int orbx_lk_track_windows_fb_device(orbx_ctx* ctx, const void* d_frames, int n_frames, int width, int height,
+                                    int row_stride, size_t frame_stride,
+                                    const int32_t* window_first /* host, [n_windows] */, int n_windows, int window_len,
+                                    const float* d_points_xy /* device, [n_windows][slot_capacity][2] */,
+                                    const int32_t* d_counts /* device, [n_windows]; NULL: every slot is a point */,
+                                    int slot_capacity, int win_size, int max_level, int max_iters, double epsilon,
+                                    float fb_threshold, void* stream);
+/* Device-side view of what the check added to the last windows call (valid until the next one; written on its
+ * stream).  src/with_bundle_adjustment.cpp:464-499 */
+typedef struct {
+  const float* fb_d2;  /* [n_windows][slot_capacity][window_len - 1] */
+  const int32_t* lost; /* [n_windows][slot_capacity] */
+  int32_t slot_capacity, window_len, n_windows;
+} orbx_lk_windows_fb_view;
+/* Fills the view; ORBX_ERR_INVALID_ARG when the last windows call had no forward-backward check (or none has run).
+ * src/with_bundle_adjustment.cpp:464-499 */
+int orbx_lk_windows_fb_results_device(orbx_ctx* ctx, orbx_lk_windows_fb_view* view);
+/* Waits for the last windows call and copies windows [first, first + n) in the view's layout; each of the two arrays
+ * may be NULL.  ORBX_ERR_INVALID_ARG as above.  src/with_bundle_adjustment.cpp:464-499 */
+int orbx_lk_windows_fb_fetch(orbx_ctx* ctx, int first, int n, float* fb_d2, int32_t* lost);
+/* Host convenience, the twin of orbx_lk_track_window: ONE window of n_frames host frames and n host points in; beside
+ * tracks_xy, seen and err (may be NULL), fb_d2 (n x (n_frames - 1)) and lost (n) out, both may be NULL.  Synchronous;
+ * runs as a windows batch of one window with the check and replaces the last windows result.  n == 0: nothing is done.
+ * src/with_bundle_adjustment.cpp:464-499, src/feature_tracking.cpp:166-193 */
+int orbx_lk_track_window_fb(orbx_ctx* ctx, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
+                            size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen,
+                            float* err, int win_size, int max_level, int max_iters, double epsilon, float fb_threshold,
+                            float* fb_d2, int32_t* lost);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,7 +120,8 @@ int orbx_lk_pyramid_levels(int width, int height, int win_size, int max_level) {
 
 // ---- Lucas-Kanade over frame windows ---------------------------------------------------------
 // trackPointsAcrossWindow (src/with_bundle_adjustment.cpp:464-499) for many windows per launch; with windows of two
-// frames, track_optical_flow (src/feature_tracking.cpp:166-193) over a stream.
+// frames, track_optical_flow (src/feature_tracking.cpp:166-193) over a stream.  The entries with the
+// forward-backward check (rank 13) are the same calls with a threshold: one lkw_run, one result block.
 
 namespace {
 
@@ -138,10 +139,18 @@ int lkw_check_params(orbx_ctx* c, int win_size, int max_level, int* max_iters, d
   return ORBX_OK;
 }
 
-// enqueues the pyramids and the tracking of every window on s; arguments are checked
+// fb_threshold of the entries with the forward-backward check (rank 13 rule 6): +inf and 0 are legal
+int lkw_check_fb(orbx_ctx* c, float fb_threshold) {
+  if (!(fb_threshold >= 0.f)) return fail(c, ORBX_ERR_INVALID_ARG, "fb_threshold is NaN or negative");
+  return ORBX_OK;
+}
+
+// enqueues the pyramids and the tracking of every window on s; arguments are checked.  fb_threshold: NULL for the
+// plain tracker, else the threshold of the forward-backward check (rank 13)
 int lkw_run(orbx_ctx* c, const uint8_t* d_frames, int n_frames, int w, int h, int row_stride, size_t frame_stride,
             const int32_t* window_first, int n_windows, int window_len, const float* d_points,
-            const int32_t* d_counts, int cap, int win, int max_level, int max_iters, double epsilon, hipStream_t s) {
+            const int32_t* d_counts, int cap, int win, int max_level, int max_iters, double epsilon,
+            const float* fb_threshold, hipStream_t s) {
   int st = c->lkw.side.enter(c, s);
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->lkw.side, s};
@@ -150,15 +159,18 @@ int lkw_run(orbx_ctx* c, const uint8_t* d_frames, int n_frames, int w, int h, in
   const LkwLayout L(w, h, win, max_level);
   const size_t fit = lkw_fit(c->lkw.ws_limit, L, window_len, n_frames);  // frames per slice
   const LkwResult R(n_windows, cap, window_len);
+  const LkwFbResult FB(n_windows, cap, window_len);
   const size_t table = sizeof(int32_t) * (size_t)n_windows;
   if ((st = c->lkw.side.grow(c, c->lkw.ws, lkw_workspace_bytes(L, fit))) != ORBX_OK) return st;
   if ((st = c->lkw.side.grow(c, c->lkw.first, table)) != ORBX_OK) return st;
   if ((st = c->lkw.side.grow(c, c->lkw.res, R.bytes)) != ORBX_OK) return st;
+  if (fb_threshold && (st = c->lkw.side.grow(c, c->lkw.fbres, FB.bytes)) != ORBX_OK) return st;
   // from here on the previous result is being replaced (a larger block has already taken its place)
   c->lkw.n = 0;
   if ((st = c->lkw.first_up.send(c, c->lkw.first.p, window_first, table, s)) != ORBX_OK) return st;
   uint8_t* ws = (uint8_t*)c->lkw.ws.p;
   uint8_t* res = (uint8_t*)c->lkw.res.p;
+  uint8_t* fbres = (uint8_t*)c->lkw.fbres.p;
   const LkGeom& g = L.g;
   const size_t img_base = g.top >= 1 ? g.img_off[1] : 0;  // workspace offsets count from level 1
   const size_t slot_stride = (size_t)cap;
@@ -200,17 +212,50 @@ int lkw_run(orbx_ctx* c, const uint8_t* d_frames, int n_frames, int w, int h, in
       F.L[l].h = g.h[l];
       F.L[l].pitch = l == 0 ? row_stride : g.pitch[l];
     }
-    HIPCHK(c, orbx_launch_lk_track_windows(
-                  s, F, (const int32_t*)c->lkw.first.p + w0, w1 - w0, window_len, d_points + 2 * slot_stride * w0,
-                  d_counts ? d_counts + w0 : nullptr, cap, (float*)res + 2 * slot_stride * window_len * w0,
-                  (int32_t*)(res + R.o_seen) + slot_stride * w0,
-                  (float*)(res + R.o_err) + slot_stride * (window_len - 1) * w0, win, max_iters, epsilon * epsilon));
+    const int32_t* d_first = (const int32_t*)c->lkw.first.p + w0;
+    const float* pts = d_points + 2 * slot_stride * w0;
+    const int32_t* cnt = d_counts ? d_counts + w0 : nullptr;
+    float* trk = (float*)res + 2 * slot_stride * window_len * w0;
+    int32_t* seen = (int32_t*)(res + R.o_seen) + slot_stride * w0;
+    float* err = (float*)(res + R.o_err) + slot_stride * (window_len - 1) * w0;
+    if (fb_threshold)
+      HIPCHK(c, orbx_launch_lk_track_windows_fb(s, F, d_first, w1 - w0, window_len, pts, cnt, cap, trk, seen, err,
+                                                (float*)fbres + slot_stride * (window_len - 1) * w0,
+                                                (int32_t*)(fbres + FB.o_lost) + slot_stride * w0, win, max_iters,
+                                                epsilon * epsilon, (double)*fb_threshold * (double)*fb_threshold));
+    else
+      HIPCHK(c, orbx_launch_lk_track_windows(s, F, d_first, w1 - w0, window_len, pts, cnt, cap, trk, seen, err, win,
+                                             max_iters, epsilon * epsilon));
     w0 = w1;
   }
+  c->lkw.fb = fb_threshold != nullptr;
   c->lkw.n = n_windows;
   c->lkw.cap = cap;
   c->lkw.len = window_len;
   return ORBX_OK;
+}
+
+// behind orbx_lk_track_windows_device and its twin with the forward-backward check (fb_threshold != NULL)
+int lkw_windows_device(orbx_ctx* c, const void* d_frames, int n_frames, int width, int height, int row_stride,
+                       size_t frame_stride, const int32_t* window_first, int n_windows, int window_len,
+                       const float* d_points_xy, const int32_t* d_counts, int slot_capacity, int win_size,
+                       int max_level, int max_iters, double epsilon, const float* fb_threshold, void* stream) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  int st = check_device_frames(c, d_frames, n_frames, 2, c->p.max_batch, width, height, row_stride, frame_stride,
+                               lkw_frames_what(c->p.max_batch));
+  if (st != ORBX_OK) return st;
+  if ((st = lkw_check_params(c, win_size, max_level, &max_iters, &epsilon)) != ORBX_OK) return st;
+  if (fb_threshold && (st = lkw_check_fb(c, *fb_threshold)) != ORBX_OK) return st;
+  if (!window_first || !d_points_xy) return fail(c, ORBX_ERR_INVALID_ARG, "window_first / d_points_xy is NULL");
+  if (n_windows < 1 || window_len < 2 || slot_capacity < 1)
+    return fail(c, ORBX_ERR_INVALID_ARG, "n_windows < 1, window_len < 2 or slot_capacity < 1");
+  for (int i = 0; i < n_windows; i++)
+    if (window_first[i] < 0 || window_first[i] > n_frames - window_len)
+      return fail(c, ORBX_ERR_INVALID_ARG, "a window does not lie inside the frames");
+  return lkw_run(c, (const uint8_t*)d_frames, n_frames, width, height, row_stride, frame_stride, window_first,
+                 n_windows, window_len, d_points_xy, d_counts, slot_capacity, win_size, max_level, max_iters, epsilon,
+                 fb_threshold, stream_of(c, stream));
 }
 
 }  // namespace
@@ -221,21 +266,19 @@ int orbx_lk_track_windows_device(orbx_ctx* c, const void* d_frames, int n_frames
                                  int row_stride, size_t frame_stride, const int32_t* window_first, int n_windows,
                                  int window_len, const float* d_points_xy, const int32_t* d_counts, int slot_capacity,
                                  int win_size, int max_level, int max_iters, double epsilon, void* stream) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
-  int st = check_device_frames(c, d_frames, n_frames, 2, c->p.max_batch, width, height, row_stride, frame_stride,
-                               lkw_frames_what(c->p.max_batch));
-  if (st != ORBX_OK) return st;
-  if ((st = lkw_check_params(c, win_size, max_level, &max_iters, &epsilon)) != ORBX_OK) return st;
-  if (!window_first || !d_points_xy) return fail(c, ORBX_ERR_INVALID_ARG, "window_first / d_points_xy is NULL");
-  if (n_windows < 1 || window_len < 2 || slot_capacity < 1)
-    return fail(c, ORBX_ERR_INVALID_ARG, "n_windows < 1, window_len < 2 or slot_capacity < 1");
-  for (int i = 0; i < n_windows; i++)
-    if (window_first[i] < 0 || window_first[i] > n_frames - window_len)
-      return fail(c, ORBX_ERR_INVALID_ARG, "a window does not lie inside the frames");
-  return lkw_run(c, (const uint8_t*)d_frames, n_frames, width, height, row_stride, frame_stride, window_first,
-                 n_windows, window_len, d_points_xy, d_counts, slot_capacity, win_size, max_level, max_iters, epsilon,
-                 stream_of(c, stream));
+  return lkw_windows_device(c, d_frames, n_frames, width, height, row_stride, frame_stride, window_first, n_windows,
+                            window_len, d_points_xy, d_counts, slot_capacity, win_size, max_level, max_iters, epsilon,
+                            nullptr, stream);
+}
+
+int orbx_lk_track_windows_fb_device(orbx_ctx* c, const void* d_frames, int n_frames, int width, int height,
+                                    int row_stride, size_t frame_stride, const int32_t* window_first, int n_windows,
+                                    int window_len, const float* d_points_xy, const int32_t* d_counts,
+                                    int slot_capacity, int win_size, int max_level, int max_iters, double epsilon,
+                                    float fb_threshold, void* stream) {
+  return lkw_windows_device(c, d_frames, n_frames, width, height, row_stride, frame_stride, window_first, n_windows,
+                            window_len, d_points_xy, d_counts, slot_capacity, win_size, max_level, max_iters, epsilon,
+                            &fb_threshold, stream);
 }
 
 int orbx_lk_workspace_limit(orbx_ctx* c, size_t bytes) {
@@ -282,9 +325,51 @@ int orbx_lk_windows_fetch(orbx_ctx* c, int first, int n, float* tracks_xy, int32
   return ORBX_OK;
 }
 
-int orbx_lk_track_window(orbx_ctx* c, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
-                         size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen, float* err,
-                         int win_size, int max_level, int max_iters, double epsilon) {
+int orbx_lk_windows_fb_results_device(orbx_ctx* c, orbx_lk_windows_fb_view* v) {
+  DeviceGuard _dg(c);
+  if (!c || !v) return ORBX_ERR_INVALID_ARG;
+  if (c->lkw.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
+  if (!c->lkw.fb) return fail(c, ORBX_ERR_INVALID_ARG, "the last windows call had no forward-backward check");
+  const LkwFbResult FB(c->lkw.n, c->lkw.cap, c->lkw.len);
+  const uint8_t* fbres = (const uint8_t*)c->lkw.fbres.p;
+  v->fb_d2 = (const float*)fbres;
+  v->lost = (const int32_t*)(fbres + FB.o_lost);
+  v->slot_capacity = c->lkw.cap;
+  v->window_len = c->lkw.len;
+  v->n_windows = c->lkw.n;
+  return ORBX_OK;
+}
+
+int orbx_lk_windows_fb_fetch(orbx_ctx* c, int first, int n, float* fb_d2, int32_t* lost) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  if (c->lkw.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no LK windows batch has run");
+  if (!c->lkw.fb) return fail(c, ORBX_ERR_INVALID_ARG, "the last windows call had no forward-backward check");
+  if (!range_ok(first, n, c->lkw.n))
+    return fail(c, ORBX_ERR_INVALID_ARG, "[first, first + n) outside the batch");
+  const int st = c->lkw.side.wait(c);
+  if (st != ORBX_OK) return st;
+  const LkwFbResult FB(c->lkw.n, c->lkw.cap, c->lkw.len);
+  const uint8_t* fbres = (const uint8_t*)c->lkw.fbres.p;
+  const size_t slots = (size_t)c->lkw.cap, len = (size_t)c->lkw.len;
+  if (fb_d2)
+    HIPCHK(c, hipMemcpy(fb_d2, fbres + sizeof(float) * slots * (len - 1) * first, sizeof(float) * slots * (len - 1) * n,
+                        hipMemcpyDeviceToHost));
+  if (lost)
+    HIPCHK(c, hipMemcpy(lost, fbres + FB.o_lost + sizeof(int32_t) * slots * first, sizeof(int32_t) * slots * n,
+                        hipMemcpyDeviceToHost));
+  return ORBX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// behind orbx_lk_track_window and its twin with the forward-backward check (fb_threshold != NULL)
+int lkw_window_host(orbx_ctx* c, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
+                    size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen, float* err,
+                    int win_size, int max_level, int max_iters, double epsilon, const float* fb_threshold, float* fb_d2,
+                    int32_t* lost) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
   // (the host entry stages into a buffer of its own; 65535: blockIdx.z)
@@ -292,6 +377,7 @@ int orbx_lk_track_window(orbx_ctx* c, const uint8_t* frames, int n_frames, int w
                                lkw_frames_what(65535));
   if (st != ORBX_OK) return st;
   if ((st = lkw_check_params(c, win_size, max_level, &max_iters, &epsilon)) != ORBX_OK) return st;
+  if (fb_threshold && (st = lkw_check_fb(c, *fb_threshold)) != ORBX_OK) return st;
   if (n < 0 || (n > 0 && (!pts_xy || !tracks_xy || !seen)))
     return fail(c, ORBX_ERR_INVALID_ARG, "n < 0 or pts_xy / tracks_xy / seen is NULL");
   if (n == 0) return ORBX_OK;  // no points: nothing to track, the last result stays
@@ -312,10 +398,30 @@ int orbx_lk_track_window(orbx_ctx* c, const uint8_t* frames, int n_frames, int w
   }
   const int32_t first = 0;
   if ((st = lkw_run(c, (const uint8_t*)c->lkw.img.p, n_frames, width, height, width, tight, &first, 1, n_frames,
-                    (const float*)c->lkw.pts.p, nullptr, n, win_size, max_level, max_iters, epsilon, c->stream)) !=
-      ORBX_OK)
+                    (const float*)c->lkw.pts.p, nullptr, n, win_size, max_level, max_iters, epsilon, fb_threshold,
+                    c->stream)) != ORBX_OK)
     return st;
-  return orbx_lk_windows_fetch(c, 0, 1, tracks_xy, seen, err);
+  if ((st = orbx_lk_windows_fetch(c, 0, 1, tracks_xy, seen, err)) != ORBX_OK) return st;
+  return fb_threshold ? orbx_lk_windows_fb_fetch(c, 0, 1, fb_d2, lost) : ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_lk_track_window(orbx_ctx* c, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
+                         size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen, float* err,
+                         int win_size, int max_level, int max_iters, double epsilon) {
+  return lkw_window_host(c, frames, n_frames, width, height, row_stride, frame_stride, pts_xy, n, tracks_xy, seen, err,
+                         win_size, max_level, max_iters, epsilon, nullptr, nullptr, nullptr);
+}
+
+int orbx_lk_track_window_fb(orbx_ctx* c, const uint8_t* frames, int n_frames, int width, int height, int row_stride,
+                            size_t frame_stride, const float* pts_xy, int n, float* tracks_xy, int32_t* seen,
+                            float* err, int win_size, int max_level, int max_iters, double epsilon, float fb_threshold,
+                            float* fb_d2, int32_t* lost) {
+  return lkw_window_host(c, frames, n_frames, width, height, row_stride, frame_stride, pts_xy, n, tracks_xy, seen, err,
+                         win_size, max_level, max_iters, epsilon, &fb_threshold, fb_d2, lost);
 }
 
 }  // extern "C"

@@ -180,17 +180,20 @@ struct LkPair {
 
 // Lucas-Kanade over frame windows (k_lk_track_windows): the workspace of one slice of frames, bounded by ws_limit;
 // the window table; the staged frames and points of the one-window host entry; and the entry's OWN result block
-// (LkwLayout, LkwResult of orbx_layout.h).  Nothing here is shared with orbx_lk_track.
+// (LkwLayout, LkwResult of orbx_layout.h).  A call with the forward-backward check (rank 13) writes the same block
+// and, beside it, fb_d2 | lost into a buffer of their own (fbres, LkwFbResult).  Nothing here is shared with
+// orbx_lk_track.
 struct LkWindows {
-  DevBuf ws, first, img, pts, res;
+  DevBuf ws, first, img, pts, res, fbres;
   size_t ws_limit = ORBX_LK_WORKSPACE_DEFAULT;
   int n = 0, cap = 0, len = 0;  // windows, slots per window, frames per window of the last call (0: none)
+  bool fb = false;              // the last call ran the forward-backward check: fbres belongs to it
   SideWork side;                // the event is recorded behind every windows call
   PinnedUpload first_up;        // the window table's way up
   void release() {
     side.release();
     first_up.release();
-    free_bufs({&ws, &first, &img, &pts, &res});
+    free_bufs({&ws, &first, &img, &pts, &res, &fbres});
   }
 };
 

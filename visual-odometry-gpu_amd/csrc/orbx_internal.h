@@ -70,6 +70,14 @@ hipError_t orbx_launch_lk_track_windows(hipStream_t s, const OrbxLkFrames& frame
                                         int n_windows, int window_len, const float* d_points, const int32_t* d_counts,
                                         int slot_capacity, float* d_tracks, int32_t* d_seen, float* d_err, int win,
                                         int max_iters, double eps2);
+// the same with the forward-backward check (k_lk_track_windows_fb): thr2 = the squared
+// threshold in binary64, >= 0 (+inf included); d_fb_d2 [n_windows][slot_capacity][window_len - 1], d_lost
+// [n_windows][slot_capacity]
+hipError_t orbx_launch_lk_track_windows_fb(hipStream_t s, const OrbxLkFrames& frames, const int32_t* d_window_first,
+                                           int n_windows, int window_len, const float* d_points,
+                                           const int32_t* d_counts, int slot_capacity, float* d_tracks, int32_t* d_seen,
+                                           float* d_err, float* d_fb_d2, int32_t* d_lost, int win, int max_iters,
+                                           double eps2, double thr2);
 
 // ---- launchers (orbx_kernels.hip) ------------------------------------------
 // All take the stream explicitly and never synchronise or allocate.

@@ -173,6 +173,17 @@ struct LkwResult {
     bytes = s.end;
   }
 };
+// what the forward-backward check adds, in a buffer of its own: fb_d2 | lost
+struct LkwFbResult {
+  size_t o_lost, bytes;  // fb_d2 at 0
+  LkwFbResult(int n_windows, int cap, int len) {
+    Sections s;
+    const size_t slots = (size_t)n_windows * cap;
+    s.take(sizeof(float) * slots * (len - 1));
+    o_lost = s.take(sizeof(int32_t) * slots);
+    bytes = s.end;
+  }
+};
 
 // ---- landmarks of n tracked windows of cap slots and len poses, and their bundle adjustment ----
 // the result block: every array sized for every slot kept

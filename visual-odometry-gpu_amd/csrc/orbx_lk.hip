@@ -21,6 +21,8 @@
 //                 control flow is wave-uniform, there is no workgroup barrier.
 //   k_lk_track_windows  the same body (lk_track_point) in a loop over the frame pairs of a window: one wavefront
 //                 per (window, point slot), the point handed from pair to pair in registers.
+//   k_lk_track_windows_fb  that loop with the forward-backward check: every pair tracked forward and back again with
+//                 the same body (the two frames swapped), the track ended by the first pair that does not return.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -438,6 +440,83 @@ __global__ __launch_bounds__(256) void k_lk_track_windows(OrbxLkFrames F, const 
   if (lane == 0) seen[at] = k;
 }
 
+// k_lk_track_windows with the forward-backward check: the same grid, wave setup and LDS
+// slices.  Every pair is tracked twice with the one body: p of frame k - 1 forward into frame k (q), then q of
+// frame k back into frame k - 1 (r, from q itself: no initial flow).  The pair passes iff both passes keep the point
+// and |r - p|^2 <= thr2 in binary64 (the products exact, the sum rounded once; NaN fails); the first pair that does
+// not pass ends the track.  Beside the outputs of k_lk_track_windows: fb_d2[window][slot][k - 1] = (float)|r - p|^2
+// of every pair that passed, 0 elsewhere; lost[window][slot] = why the track ended, 1 forward pass, 2 backward pass,
+// 3 distance, 0 for a track alive through the window and for the slots at or beyond counts[window].
+template <int NIT>
+__global__ __launch_bounds__(256) void k_lk_track_windows_fb(OrbxLkFrames F, const int32_t* __restrict__ window_first,
+                                                             int window_len, const float2* __restrict__ points,
+                                                             const int32_t* __restrict__ counts, int cap,
+                                                             float2* __restrict__ tracks, int32_t* __restrict__ seen,
+                                                             float* __restrict__ err, float* __restrict__ fb_d2,
+                                                             int32_t* __restrict__ lost, int win, int max_iters,
+                                                             double eps2, double thr2) {
+  __shared__ short4 s_tpl[4][LK_MAX_WIN * LK_MAX_WIN];
+  __shared__ uint8_t s_jc[4][LK_JC_MAX * LK_JC_MAX];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + wave, w = blockIdx.y;
+  if (slot >= cap) return;  // whole wave
+  const size_t at = (size_t)w * cap + slot;
+  float2* trk = tracks + at * window_len;
+  float* er = err + at * (window_len - 1);
+  float* fb = fb_d2 + at * (window_len - 1);
+  int count = counts ? counts[w] : cap;
+  count = __builtin_amdgcn_readfirstlane(count < cap ? count : cap);
+  int k = 0;       // frames the point has been observed in
+  int reason = 0;  // why the track ended
+  if (slot < count) {
+    const int f0 = __builtin_amdgcn_readfirstlane(window_first[w]);
+    LkWave W = lk_wave_setup(s_tpl[wave], s_jc[wave], lane, win, max_iters, eps2);
+    float2 pp = points[at];
+    pp.x = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pp.x)));
+    pp.y = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pp.y)));
+    if (lane == 0) trk[0] = pp;
+    for (k = 1; k < window_len; k++) {
+      int st;
+      float ev, qx, qy, rx, ry, eb;
+      lk_track_point<NIT>(LkPyrFrame{F, f0 + k - 1}, LkPyrFrame{F, f0 + k}, F.top, pp, W, qx, qy, st, ev);
+      if (!st) {
+        reason = 1;
+        break;
+      }
+      lk_track_point<NIT>(LkPyrFrame{F, f0 + k}, LkPyrFrame{F, f0 + k - 1}, F.top, make_float2(qx, qy), W, rx, ry, st,
+                          eb);
+      if (!st) {
+        reason = 2;
+        break;
+      }
+      const float dx = __fsub_rn(rx, pp.x), dy = __fsub_rn(ry, pp.y);
+      const double d2 = __dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy));
+      if (!(d2 <= thr2)) {  // (NaN fails)
+        reason = 3;
+        break;
+      }
+      pp = make_float2(qx, qy);
+      if (lane == 0) {
+        trk[k] = pp;
+        er[k - 1] = ev;
+        fb[k - 1] = (float)d2;
+      }
+    }
+  }
+  // the zero tail: frames k .. window_len - 1 and their pairs, a lane each
+  for (int j = k + lane; j < window_len; j += 64) {
+    trk[j] = make_float2(0.f, 0.f);
+    if (j > 0) {
+      er[j - 1] = 0.f;
+      fb[j - 1] = 0.f;
+    }
+  }
+  if (lane == 0) {
+    seen[at] = k;
+    lost[at] = reason;
+  }
+}
+
 }  // namespace
 
 hipError_t orbx_launch_lk_pyrdown(hipStream_t s, const uint8_t* d_src, int sw, int sh, int spitch, uint8_t* d_dst,
@@ -499,5 +578,24 @@ hipError_t orbx_launch_lk_track_windows(hipStream_t s, const OrbxLkFrames& frame
   else
     hipLaunchKernelGGL(k_lk_track_windows<0>, grid, dim3(256), 0, s, frames, d_window_first, window_len, pts, d_counts,
                        slot_capacity, trk, d_seen, d_err, win, max_iters, eps2);
+  return hipGetLastError();
+}
+
+hipError_t orbx_launch_lk_track_windows_fb(hipStream_t s, const OrbxLkFrames& frames, const int32_t* d_window_first,
+                                           int n_windows, int window_len, const float* d_points,
+                                           const int32_t* d_counts, int slot_capacity, float* d_tracks, int32_t* d_seen,
+                                           float* d_err, float* d_fb_d2, int32_t* d_lost, int win, int max_iters,
+                                           double eps2, double thr2) {
+  if (n_windows < 1 || n_windows > 65535 || window_len < 2 || slot_capacity < 1) return hipErrorInvalidValue;
+  if (win < 3 || win > LK_MAX_WIN || !(thr2 >= 0.0)) return hipErrorInvalidValue;
+  const dim3 grid((slot_capacity + 3) / 4, n_windows);
+  const float2* pts = reinterpret_cast<const float2*>(d_points);
+  float2* trk = reinterpret_cast<float2*>(d_tracks);
+  if (win == 21)
+    hipLaunchKernelGGL(k_lk_track_windows_fb<7>, grid, dim3(256), 0, s, frames, d_window_first, window_len, pts,
+                       d_counts, slot_capacity, trk, d_seen, d_err, d_fb_d2, d_lost, win, max_iters, eps2, thr2);
+  else
+    hipLaunchKernelGGL(k_lk_track_windows_fb<0>, grid, dim3(256), 0, s, frames, d_window_first, window_len, pts,
+                       d_counts, slot_capacity, trk, d_seen, d_err, d_fb_d2, d_lost, win, max_iters, eps2, thr2);
   return hipGetLastError();
 }

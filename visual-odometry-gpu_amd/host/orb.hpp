@@ -625,6 +625,24 @@ class LKTracker {
   void trackWindow(const std::vector<Image>& imgs, const std::vector<Point2f>& pts0, std::vector<Point2f>& tracks,
                    std::vector<int32_t>& seen, std::vector<float>& err, Size winSize = Size(21, 21), int maxLevel = 3,
                    TermCriteria criteria = TermCriteria()) {
+    trackWindowImpl(imgs, pts0, tracks, seen, err, nullptr, nullptr, nullptr, winSize, maxLevel, criteria);
+  }
+  // The same with the forward-backward check, still ONE launch: every pair is tracked forward
+  // and back again, and a track ends with the first pair whose return lies farther than fbThreshold from its start.
+  // fbD2: pts0.size() x (imgs.size() - 1) squared return distances of the pairs that passed, lost: why each track
+  // ended (0: alive through the window, 1: forward pass, 2: backward pass, 3: distance).
+  void trackWindow(const std::vector<Image>& imgs, const std::vector<Point2f>& pts0, float fbThreshold,
+                   std::vector<Point2f>& tracks, std::vector<int32_t>& seen, std::vector<float>& err,
+                   std::vector<float>& fbD2, std::vector<int32_t>& lost, Size winSize = Size(21, 21), int maxLevel = 3,
+                   TermCriteria criteria = TermCriteria()) {
+    trackWindowImpl(imgs, pts0, tracks, seen, err, &fbThreshold, &fbD2, &lost, winSize, maxLevel, criteria);
+  }
+
+ private:
+  void trackWindowImpl(const std::vector<Image>& imgs, const std::vector<Point2f>& pts0, std::vector<Point2f>& tracks,
+                       std::vector<int32_t>& seen, std::vector<float>& err, const float* fbThreshold,
+                       std::vector<float>* fbD2, std::vector<int32_t>* lost, Size winSize, int maxLevel,
+                       TermCriteria criteria) {
     if (winSize.width != winSize.height) throw std::runtime_error("trackWindow: square windows only");
     if (imgs.size() < 2) throw std::runtime_error("trackWindow: a window has at least two frames");
     const int w = imgs[0].width, h = imgs[0].height, nf = (int)imgs.size(), n = (int)pts0.size();
@@ -641,15 +659,26 @@ class LKTracker {
     tracks.assign((size_t)n * nf, Point2f());
     seen.assign((size_t)n, 0);
     err.assign((size_t)n * (nf - 1), 0.f);
+    if (!fbThreshold) {
+      detail::check(c,
+                    orbx_lk_track_window(c, packed.data(), nf, w, h, w, (size_t)w * h,
+                                         reinterpret_cast<const float*>(pts0.data()), n,
+                                         reinterpret_cast<float*>(tracks.data()), seen.data(), err.data(),
+                                         winSize.width, maxLevel, criteria.maxCount, criteria.epsilon),
+                    "trackWindow");
+      return;
+    }
+    fbD2->assign((size_t)n * (nf - 1), 0.f);
+    lost->assign((size_t)n, 0);
     detail::check(c,
-                  orbx_lk_track_window(c, packed.data(), nf, w, h, w, (size_t)w * h,
-                                       reinterpret_cast<const float*>(pts0.data()), n,
-                                       reinterpret_cast<float*>(tracks.data()), seen.data(), err.data(), winSize.width,
-                                       maxLevel, criteria.maxCount, criteria.epsilon),
+                  orbx_lk_track_window_fb(c, packed.data(), nf, w, h, w, (size_t)w * h,
+                                          reinterpret_cast<const float*>(pts0.data()), n,
+                                          reinterpret_cast<float*>(tracks.data()), seen.data(), err.data(),
+                                          winSize.width, maxLevel, criteria.maxCount, criteria.epsilon, *fbThreshold,
+                                          fbD2->data(), lost->data()),
                   "trackWindow");
   }
 
- private:
   std::shared_ptr<detail::Ctx> ctx_;
 };
 
@@ -866,6 +895,88 @@ inline std::vector<Track> track_points_across_window_one_launch(LKTracker& lk, c
   const size_t nf = imgs_window.size();
   for (size_t i = 0; i < keypoints0.size(); i++)
     for (int k = 1; k < seen[i]; k++) tracks[i].emplace_back(k, xy[i * nf + (size_t)k]);
+  return tracks;
+}
+
+// trackPointsAcrossWindow with the forward-backward check every KLT front end puts behind calcOpticalFlowPyrLK
+// (DESIGN.md §9 rank 13), pair by pair on the host: the live points tracked from frame fi - 1 into frame fi, the
+// survivors tracked back, and a track kept iff both passes keep it and the return lies within thr of the start.  Two
+// LK calls and two compactions per pair.  lost (optional): why each track ended, 0 for one alive through the window,
+// 1 forward pass, 2 backward pass, 3 distance.
+inline std::vector<Track> track_points_across_window_fb(LKTracker& lk, const std::vector<Image>& imgs_window,
+                                                        const std::vector<Point2f>& keypoints0, float thr,
+                                                        std::vector<int32_t>* lost = nullptr) {
+  if (!(thr >= 0.f)) throw std::runtime_error("track_points_across_window_fb: the threshold is NaN or negative");
+  std::vector<Track> tracks(keypoints0.size());
+  std::vector<size_t> live(keypoints0.size());
+  std::vector<Point2f> prev = keypoints0, next, back;
+  for (size_t i = 0; i < keypoints0.size(); i++) {
+    tracks[i].emplace_back(0, keypoints0[i]);
+    live[i] = i;
+  }
+  if (lost) lost->assign(keypoints0.size(), 0);
+  const double thr2 = (double)thr * (double)thr;
+  std::vector<uint8_t> status;
+  std::vector<float> err;
+  for (size_t fi = 1; fi < imgs_window.size() && !live.empty(); fi++) {
+    lk.calcOpticalFlowPyrLK(&imgs_window[fi - 1], imgs_window[fi], prev, next, status, err, Size(21, 21), 3,
+                            TermCriteria(30, 0.01));
+    std::vector<size_t> fwd;
+    std::vector<Point2f> p, q;
+    for (size_t k = 0; k < live.size(); k++)
+      if (status[k]) {
+        fwd.push_back(live[k]);
+        p.push_back(prev[k]);
+        q.push_back(next[k]);
+      } else if (lost) {
+        (*lost)[live[k]] = 1;
+      }
+    live.clear();
+    prev.clear();
+    if (fwd.empty()) break;
+    // back from q: the tracker still holds the pyramid of imgs_window[fi]
+    lk.calcOpticalFlowPyrLK(nullptr, imgs_window[fi - 1], q, back, status, err, Size(21, 21), 3,
+                            TermCriteria(30, 0.01));
+    for (size_t k = 0; k < fwd.size(); k++) {
+      int why = 0;
+      if (!status[k]) {
+        why = 2;
+      } else {
+        const float dx = back[k].x - p[k].x, dy = back[k].y - p[k].y;
+        const double d2 = (double)dx * (double)dx + (double)dy * (double)dy;  // exact products, one rounding
+        if (!(d2 <= thr2)) why = 3;
+      }
+      if (why) {
+        if (lost) (*lost)[fwd[k]] = why;
+        continue;
+      }
+      tracks[fwd[k]].emplace_back((int)fi, q[k]);
+      live.push_back(fwd[k]);
+      prev.push_back(q[k]);
+    }
+  }
+  return tracks;
+}
+
+// The same in one launch (LKTracker::trackWindow with fbThreshold).  Returns exactly what
+// track_points_across_window_fb returns.
+inline std::vector<Track> track_points_across_window_fb_one_launch(LKTracker& lk,
+                                                                   const std::vector<Image>& imgs_window,
+                                                                   const std::vector<Point2f>& keypoints0, float thr,
+                                                                   std::vector<int32_t>* lost = nullptr) {
+  if (!(thr >= 0.f)) throw std::runtime_error("track_points_across_window_fb: the threshold is NaN or negative");
+  std::vector<Track> tracks(keypoints0.size());
+  for (size_t i = 0; i < keypoints0.size(); i++) tracks[i].emplace_back(0, keypoints0[i]);
+  if (lost) lost->assign(keypoints0.size(), 0);
+  if (imgs_window.size() < 2 || keypoints0.empty()) return tracks;
+  std::vector<Point2f> xy;
+  std::vector<int32_t> seen, why;
+  std::vector<float> err, d2;
+  lk.trackWindow(imgs_window, keypoints0, thr, xy, seen, err, d2, why, Size(21, 21), 3, TermCriteria(30, 0.01));
+  const size_t nf = imgs_window.size();
+  for (size_t i = 0; i < keypoints0.size(); i++)
+    for (int k = 1; k < seen[i]; k++) tracks[i].emplace_back(k, xy[i * nf + (size_t)k]);
+  if (lost) *lost = why;
   return tracks;
 }
 

@@ -49,6 +49,8 @@ EXPORTS = [
     "orbx_tracks_pose_pair_fetch", "orbx_tracks_pose",
     "orbx_good_features_topup_device", "orbx_good_features_topup_results_device", "orbx_good_features_topup_fetch",
     "orbx_good_features_topup", "orbx_good_features_to_track_masked",
+    "orbx_lk_track_windows_fb_device", "orbx_lk_windows_fb_results_device", "orbx_lk_windows_fb_fetch",
+    "orbx_lk_track_window_fb",
 ]
 
 
@@ -976,13 +978,22 @@ class LkWindowsView(C.Structure):
                 ("window_len", C.c_int32), ("n_windows", C.c_int32)]
 
 
+class LkWindowsFbView(C.Structure):
+    _fields_ = [("fb_d2", C.c_void_p), ("lost", C.c_void_p), ("slot_capacity", C.c_int32), ("window_len", C.c_int32),
+                ("n_windows", C.c_int32)]
+
+
+LK_FB_ALIVE, LK_FB_FORWARD, LK_FB_BACKWARD, LK_FB_DISTANCE = range(4)  # `lost` of the forward-backward check
+
+
 def _lk_window_methods():
     """Lucas-Kanade over frame windows: trackPointsAcrossWindow for many windows per launch (include/orbx.h;
-    DESIGN.md §9 rank 9)."""
+    DESIGN.md §9 rank 9), with the forward-backward check when fb_threshold is given (rank 13)."""
 
     def lk_track_windows(self, frames, window_first, window_len, points, counts=None, win=21, max_level=3,
-                         max_iters=30, epsilon=0.01, slot_capacity=None, stream=None):
-        """orbx_lk_track_windows_device.  frames: (n, h, w) uint8, a torch device tensor (any strides with unit pixel
+                         max_iters=30, epsilon=0.01, slot_capacity=None, stream=None, fb_threshold=None):
+        """orbx_lk_track_windows_device, or orbx_lk_track_windows_fb_device when fb_threshold is not None (then
+        lk_windows_fb_fetch delivers fb_d2 and lost beside the usual results).  frames: (n, h, w) uint8, a torch device tensor (any strides with unit pixel
         stride; read in place) or a numpy array (copied to the device first).  points: (n_windows, slot_capacity, 2)
         float32 and counts: (n_windows,) int32 or None, each a torch device tensor, a numpy array or a raw device
         address (then slot_capacity is required) -- e.g. the fields of good_features_view().  Device tensors: the
@@ -1025,12 +1036,19 @@ def _lk_window_methods():
         n, h, w = frames.shape
         rs = frames.stride(1)
         fs = max(frames.stride(0), rs * (h - 1) + w) if n == 1 else frames.stride(0)
-        f = self._lib.orbx_lk_track_windows_device
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
-                      C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]
-        self._chk(f(self._h, C.c_void_p(frames.data_ptr()), n, w, h, rs, fs, _ptr(window_first), nw, window_len,
-                    C.c_void_p(points), C.c_void_p(counts) if counts else None, slot_capacity, win, max_level,
-                    max_iters, epsilon, C.c_void_p(stream) if stream else None))
+        args = [self._h, C.c_void_p(frames.data_ptr()), n, w, h, rs, fs, _ptr(window_first), nw, window_len,
+                C.c_void_p(points), C.c_void_p(counts) if counts else None, slot_capacity, win, max_level, max_iters,
+                epsilon]
+        types = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
+                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
+        if fb_threshold is None:
+            f = self._lib.orbx_lk_track_windows_device
+        else:
+            f = self._lib.orbx_lk_track_windows_fb_device
+            args.append(fb_threshold)
+            types.append(C.c_float)
+        f.argtypes = types + [C.c_void_p]
+        self._chk(f(*args, C.c_void_p(stream) if stream else None))
 
     def lk_windows_view(self):
         """The device-side result block of the last windows call (orbx_lk_windows_results_device)."""
@@ -1053,15 +1071,40 @@ def _lk_window_methods():
         self._chk(f(self._h, first, n, _ptr(tracks), _ptr(seen), _ptr(err)))
         return tracks, seen, err
 
+    def lk_windows_fb_view(self):
+        """What the forward-backward check added to the last windows call, on the device
+        (orbx_lk_windows_fb_results_device); raises after a call without the check."""
+        v = LkWindowsFbView()
+        f = self._lib.orbx_lk_windows_fb_results_device
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        self._chk(f(self._h, C.byref(v)))
+        return v
+
+    def lk_windows_fb_fetch(self, first=0, n=None):
+        """Windows [first, first + n) of the last windows call with the check: fb_d2 (n, slots, window_len - 1)
+        float32, the squared forward-backward distance of every pair that passed, and lost (n, slots) int32, 0 or the
+        reason the track ended (LK_FB_FORWARD / LK_FB_BACKWARD / LK_FB_DISTANCE)."""
+        v = self.lk_windows_fb_view()
+        if n is None:
+            n = v.n_windows - first
+        m = max(n, 1)
+        fb_d2 = np.zeros((m, v.slot_capacity, v.window_len - 1), np.float32)
+        lost = np.zeros((m, v.slot_capacity), np.int32)
+        f = self._lib.orbx_lk_windows_fb_fetch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(f(self._h, first, n, _ptr(fb_d2), _ptr(lost)))
+        return fb_d2, lost
+
     def lk_workspace_limit(self, nbytes):
         """Bound of the windows workspace in bytes (0: the default); more frames run in slices of whole windows."""
         f = self._lib.orbx_lk_workspace_limit
         f.argtypes = [C.c_void_p, C.c_size_t]
         self._chk(f(self._h, nbytes))
 
-    def lk_track_window(self, frames, pts, win=21, max_level=3, max_iters=30, epsilon=0.01):
+    def lk_track_window(self, frames, pts, win=21, max_level=3, max_iters=30, epsilon=0.01, fb_threshold=None):
         """orbx_lk_track_window: one window of host frames (n_frames, h, w) and host points (n, 2).  Returns tracks
-        (n, n_frames, 2), seen (n,), err (n, n_frames - 1)."""
+        (n, n_frames, 2), seen (n,), err (n, n_frames - 1); with fb_threshold (orbx_lk_track_window_fb) also fb_d2
+        (n, n_frames - 1) and lost (n,)."""
         frames = np.ascontiguousarray(frames, np.uint8)
         if frames.ndim != 3:
             raise ValueError("frames must be (n_frames, h, w) uint8")
@@ -1071,14 +1114,24 @@ def _lk_window_methods():
         tracks = np.zeros((max(n, 1), nf, 2), np.float32)
         seen = np.zeros(max(n, 1), np.int32)
         err = np.zeros((max(n, 1), max(nf - 1, 1)), np.float32)
-        f = self._lib.orbx_lk_track_window
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
-                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]
-        self._chk(f(self._h, _ptr(frames), nf, w, h, w, w * h, _ptr(pts), n, _ptr(tracks), _ptr(seen), _ptr(err), win,
-                    max_level, max_iters, epsilon))
-        return tracks[:n].copy(), seen[:n].copy(), err[:n, :nf - 1].copy()
+        args = [self._h, _ptr(frames), nf, w, h, w, w * h, _ptr(pts), n, _ptr(tracks), _ptr(seen), _ptr(err), win,
+                max_level, max_iters, epsilon]
+        types = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
+                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]
+        if fb_threshold is None:
+            f = self._lib.orbx_lk_track_window
+            f.argtypes = types
+            self._chk(f(*args))
+            return tracks[:n].copy(), seen[:n].copy(), err[:n, :nf - 1].copy()
+        fb_d2 = np.zeros_like(err)
+        lost = np.zeros(max(n, 1), np.int32)
+        f = self._lib.orbx_lk_track_window_fb
+        f.argtypes = types + [C.c_float, C.c_void_p, C.c_void_p]
+        self._chk(f(*args, fb_threshold, _ptr(fb_d2), _ptr(lost)))
+        return tracks[:n].copy(), seen[:n].copy(), err[:n, :nf - 1].copy(), fb_d2[:n, :nf - 1].copy(), lost[:n].copy()
 
-    for f in (lk_track_windows, lk_windows_view, lk_windows_fetch, lk_workspace_limit, lk_track_window):
+    for f in (lk_track_windows, lk_windows_view, lk_windows_fetch, lk_windows_fb_view, lk_windows_fb_fetch,
+              lk_workspace_limit, lk_track_window):
         setattr(Context, f.__name__, f)
 
 
