@@ -604,8 +604,6 @@ def test_gpu_refusals(pkg):
         s = pkg.orbx.BaSummary()
         s.termination = 77
         f = c._lib.orbx_bundle_adjust
-        f.argtypes = [C.c_void_p, DP, C.c_int, DP, C.c_int, DP, C.c_int, IP, IP, DP, C.c_double, C.c_int,
-                      C.POINTER(pkg.orbx.BaSummary)]
         st = f(c._h, _d(K_KITTI)[1], 5, poses.ctypes.data_as(DP), n, pts.ctypes.data_as(DP), n, op.ctypes.data_as(IP),
                oq.ctypes.data_as(IP), xy.ctypes.data_as(DP), 1.0, 200, C.byref(s))
         assert st == pkg.orbx.ERR_UNSUPPORTED

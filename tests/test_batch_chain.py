@@ -270,10 +270,6 @@ def test_gpu_fetch_edges_on_a_pair_without_matches(pkg, libs):
     zero matches (NULL outputs); batch_pose_fetch of that pair returns the zero result exactly."""
     frames = R.set_u()
     lib = pkg.orbx.load()
-    lib.orbx_batch_match_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                           C.POINTER(C.c_int)]
-    lib.orbx_batch_pose_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    lib.orbx_batch_points_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     with pkg.Context(params(pkg, OKW_U, len(frames))) as c:
         ref = run_and_check(c, libs, frames, OKW_U)
         empty = [i for i, p in enumerate(ref["pairs"]) if matches(p) == 0]

@@ -15,8 +15,6 @@ keypoints, level keypoints, levels and descriptors equal, angles and responses e
 3. the 600 x 1100 context with 594 x 1084 frames whose caps fill in the top rows (first finding; the host
    sweep of tests/test_plan_capacity.py is the check of the arithmetic, this is the end-to-end confirmation).
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -230,17 +228,11 @@ def test_two_stride_pairs_alternate_on_one_pointer(pkg):
 
 
 def _host_entry(pkg):
-    f = pkg.orbx.load().orbx_detect_and_compute_batch_host
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
-    f.restype = C.c_int
-    return f
+    return pkg.orbx.load().orbx_detect_and_compute_batch_host
 
 
 def _device_entry(pkg):
-    f = pkg.orbx.load().orbx_detect_and_compute_batch_device
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p]
-    f.restype = C.c_int
-    return f
+    return pkg.orbx.load().orbx_detect_and_compute_batch_device
 
 
 @pytest.mark.parametrize("n,w,h,rs,gap", [(3, 643, 200, 651, 7), (1, 1241, 200, 1250, 0), (5, 250, 201, 253, 1001)])

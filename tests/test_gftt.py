@@ -312,15 +312,7 @@ def test_orb_state_is_untouched(ctx, kitti):
 # ---- refusals -----------------------------------------------------------------------------------------------------
 def _entries(pkg):
     lib = pkg.orbx.load()
-    one = lib.orbx_good_features_to_track
-    one.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
-                    C.c_int, C.POINTER(C.c_int)]
-    batch = lib.orbx_good_features_batch_device
-    batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_double,
-                      C.c_double, C.c_void_p]
-    eig = lib.orbx_corner_min_eigen_val
-    eig.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    return one, batch, eig
+    return lib.orbx_good_features_to_track, lib.orbx_good_features_batch_device, lib.orbx_corner_min_eigen_val
 
 
 def test_refusals(pkg, ctx, kitti):
@@ -391,7 +383,6 @@ def test_refusals(pkg, ctx, kitti):
     for g in ctx.good_features_fetch():
         same_corners(g, img, (2000, 0.01, 8.0))
     fetch = pkg.orbx.load().orbx_good_features_fetch
-    fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     two = np.full(2, -5, np.int32)
     for first, n in ((1, 2), (2, 1), (0, 3), (1, 2 ** 31 - 1), (-1, 1), (0, 0)):  # beyond the batch
         assert fetch(ctx._h, first, n, two.ctypes.data, None) == o.ERR_INVALID_ARG, (first, n)

@@ -283,8 +283,6 @@ def test_refusals_leave_the_previous_result(pkg, ctx, kitti):
     o = pkg.orbx
     lib = o.load()
     dev = lib.orbx_good_features_topup_device
-    dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
-                    C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
     frames, seed_lists = batch_case(kitti)
     h, w = frames[0].shape
     seeds = pack(seed_lists)
@@ -320,7 +318,6 @@ def test_refusals_leave_the_previous_result(pkg, ctx, kitti):
     assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(got, want))
     # the fetch's range
     fetch = lib.orbx_good_features_topup_fetch
-    fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     three = np.full(3, -5, np.int32)
     for first, n in ((1, 3), (3, 1), (0, 4), (1, 2 ** 31 - 1), (-1, 1), (0, 0)):
         assert fetch(ctx._h, first, n, three.ctypes.data, None, None, None) == o.ERR_INVALID_ARG, (first, n)
@@ -330,8 +327,6 @@ def test_refusals_leave_the_previous_result(pkg, ctx, kitti):
     # the host entries
     img = frames[0]
     one = lib.orbx_good_features_topup
-    one.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
-                    C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     SENT = np.float32(-7.5)
     pts = np.full((64, 2), SENT, np.float32)
     org = np.full(64, -9, np.int32)
@@ -353,8 +348,6 @@ def test_refusals_leave_the_previous_result(pkg, ctx, kitti):
     assert call_one(capacity=need) == o.OK and cnt.value == need and car.value == 15 and np.all(pts[need:] == SENT)
     assert call_one(sxy=None, ns=0) == o.OK and car.value == 0  # no seeds at all
     masked = lib.orbx_good_features_to_track_masked
-    masked.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
-                       C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     mask = np.full((h, w), 255, np.uint8)
     pts[...] = SENT
     cnt.value = -123

@@ -328,8 +328,6 @@ def pose_raw(pkg, c, p1, p2, n, K, prob, threshold, max_iters, seed, with_mask=T
     mask = np.full(max(len(p1), 1), 9, np.uint8) if with_mask else None
     cnt = np.full(3, -5, np.int32)
     f = pkg.orbx.load().orbx_estimate_pose
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, DP, C.c_double, C.c_double, C.c_int,
-                  C.c_uint64] + [C.c_void_p] * 7
     st = f(c._h, p1.ctypes.data, p2.ctypes.data, n, None if K is None else K.ctypes.data_as(DP), prob, threshold,
            max_iters, seed, E.ctypes.data, R.ctypes.data, t.ctypes.data, None if mask is None else mask.ctypes.data,
            cnt.ctypes.data, cnt.ctypes.data + 4, cnt.ctypes.data + 8)
@@ -533,7 +531,6 @@ def test_gpu_pose_refusals(pkg, seq):
         # the batched entry: a matched batch, so that only the arguments can be what is refused
         kitti_batch(pkg, c, np.stack([k0, k1]))
         f = pkg.orbx.load().orbx_batch_pose_consecutive
-        f.argtypes = [C.c_void_p, DP, C.c_double, C.c_double, C.c_int, C.c_uint64]
 
         def batch(**kw):
             a = dict(valid, **kw)

@@ -278,7 +278,6 @@ def test_refusals_leave_the_previous_block(pkg, ctx, libs):
         assert e.value.status == E.ERR_INVALID_ARG
     # the capacity rule of orbx_batch_pose_mask: the count, nothing else written
     f = pkg.orbx.load().orbx_tracks_pose_pair_fetch
-    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.POINTER(C.c_int)]
     cnt, slots = C.c_int(0), np.full(4, 7, np.int32)
     assert block["n"][0] > 4
     assert f(ctx._h, 0, slots.ctypes.data, None, None, None, 4, C.byref(cnt)) == E.ERR_CAPACITY

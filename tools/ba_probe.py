@@ -49,8 +49,6 @@ def main():
     out = (pkg.orbx.BaSummary * a.windows)()
     with pkg.Context(pkg.default_params("gpu")) as c:
         f = c._lib.orbx_bundle_adjust_batch
-        f.argtypes = [C.c_void_p, DP, C.c_int, IP, DP, IP, DP, IP, IP, IP, DP, C.c_double, C.c_int,
-                      C.POINTER(pkg.orbx.BaSummary)]
 
         def once():
             poses, pts = poses0.copy(), pts0.copy()

@@ -57,8 +57,6 @@ def main():
     rot = [[R.rodrigues(p[:3]) for p in sc["poses"][:2]] for sc in scenes]
     with pkg.Context(pkg.default_params("gpu")) as c:
         f = c._lib.orbx_bundle_adjust_batch
-        f.argtypes = [C.c_void_p, DP, C.c_int, IP, DP, IP, DP, IP, IP, IP, DP, C.c_double, C.c_int,
-                      C.POINTER(pkg.orbx.BaSummary)]
         d_tracks, d_seen = torch.from_numpy(tracks).cuda(), torch.from_numpy(seen).cuda()
         torch.cuda.synchronize()
         split = {}

@@ -21,37 +21,87 @@ BLUR_SEP16, BLUR_K273 = 0, 1
 STAGE_PYRAMID, STAGE_BLUR, STAGE_FAST, STAGE_COMPACT, STAGE_HARRIS, STAGE_SELECT, STAGE_DESCRIBE = range(7)
 NUM_STAGE_TIMES = 8
 STAGE_NAMES = ["pyramid", "blur", "fast_nms", "compact", "harris", "select", "describe", "total"]
+POSE_MAX_ITERS = 100000  # ORBX_POSE_MAX_ITERS
+BA_CONVERGENCE, BA_NO_CONVERGENCE, BA_FAILURE, BA_SKIPPED = range(4)
+BA_MAX_POSES = 8
+LK_FB_ALIVE, LK_FB_FORWARD, LK_FB_BACKWARD, LK_FB_DISTANCE = range(4)  # `lost` of the forward-backward check
+LM_OK, LM_BASELINE, LM_EMPTY, LM_BAD_POSE = range(4)
 
-# every symbol include/orbx.h declares (checked by tests/test_abi.py)
-EXPORTS = [
-    "orbx_params_default_gpu", "orbx_params_default_cpu", "orbx_create", "orbx_destroy",
-    "orbx_last_error_string", "orbx_status_string", "orbx_version", "orbx_get_plan",
-    "orbx_detect_and_compute", "orbx_detect_and_compute_batch_device", "orbx_detect_and_compute_batch_host",
-    "orbx_wait", "orbx_batch_results_device", "orbx_batch_results_host", "orbx_batch_fetch", "orbx_batch_prefetch", "orbx_batch_prefetch_compact",
-    "orbx_batch_fetch_previous", "orbx_enable_stage_timing",
-    "orbx_last_stage_times", "orbx_stage_times_history", "orbx_bench_stage", "orbx_set_fast_early_exit",
-    "orbx_set_fused_pyramid_blur", "orbx_set_top_rows_first", "orbx_set_pipelined_batches", "orbx_set_host_results", "orbx_fast_tile_counts", "orbx_pyramid_pixel_counts", "orbx_lk_track", "orbx_lk_pyramid_levels", "orbx_fast_score", "orbx_nms", "orbx_fast",
-    "orbx_orientations", "orbx_brief", "orbx_harris", "orbx_blur5_sep", "orbx_blur5_273", "orbx_conv2d",
-    "orbx_gaussian_blur_conv", "orbx_gaussian_kernel", "orbx_sobel", "orbx_build_pyramid_level",
-    "orbx_select_top", "orbx_knn2", "orbx_match_ratio", "orbx_batch_match_consecutive", "orbx_batch_match_fetch",
-    "orbx_estimate_pose", "orbx_batch_pose_consecutive", "orbx_batch_pose_fetch", "orbx_batch_pose_mask",
-    "orbx_triangulate", "orbx_estimate_scale", "orbx_batch_scale_consecutive", "orbx_batch_scale_fetch",
-    "orbx_batch_points_fetch", "orbx_chain_trajectory", "orbx_debug_fill_pools",
-    "orbx_debug_read_pyramid_level",
-    "orbx_bundle_adjust", "orbx_bundle_adjust_batch",
-    "orbx_corner_min_eigen_val", "orbx_good_features_to_track", "orbx_good_features_batch_device",
-    "orbx_good_features_workspace_limit", "orbx_good_features_results_device", "orbx_good_features_fetch",
-    "orbx_lk_track_windows_device", "orbx_lk_windows_results_device", "orbx_lk_windows_fetch",
-    "orbx_lk_workspace_limit", "orbx_lk_track_window",
-    "orbx_landmarks_build_device", "orbx_landmarks_results_device", "orbx_landmarks_fetch",
-    "orbx_bundle_adjust_landmarks_device", "orbx_bundle_adjust_landmarks_fetch", "orbx_bundle_adjust_tracks",
-    "orbx_tracks_pose_device", "orbx_tracks_pose_results_device", "orbx_tracks_pose_fetch",
-    "orbx_tracks_pose_pair_fetch", "orbx_tracks_pose",
-    "orbx_good_features_topup_device", "orbx_good_features_topup_results_device", "orbx_good_features_topup_fetch",
-    "orbx_good_features_topup", "orbx_good_features_to_track_masked",
-    "orbx_lk_track_windows_fb_device", "orbx_lk_windows_fb_results_device", "orbx_lk_windows_fb_fetch",
-    "orbx_lk_track_window_fb",
-]
+# ---- the prototype of every function include/orbx.h declares: name -> (return type, parameter types), applied once
+# by load() (tests/test_binding_prototypes.py checks it against the header).  Every pointer, the handle included, is
+# a c_void_p: it takes an array's address, a device address, byref(..), a typed pointer or None alike.
+P, I, Z, D, F, U64 = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint64
+_IMAGE = [P, P, I, I, I]  # ctx, image, width, height, stride
+_FRAMES = [P, P, I, I, I, I, Z]  # ctx, frames, n, width, height, row_stride, frame_stride
+_LK = [I, I, I, D]  # win_size, max_level, max_iters, epsilon
+_LK_WINDOWS = _FRAMES + [P, I, I, P, P, I] + _LK  # .. window_first, n_windows, window_len, points, counts, slots ..
+_LK_WINDOW = _FRAMES + [P, I, P, P, P] + _LK  # .. pts, n, tracks, seen, err ..
+_BATCH_FETCH = [P, I, I] + [P] * 7 + [I]
+PROTOTYPES = {
+    # context, whole path, switches and diagnostics
+    "orbx_params_default_gpu": (I, [P]), "orbx_params_default_cpu": (I, [P]), "orbx_create": (I, [P, P]),
+    "orbx_destroy": (None, [P]), "orbx_last_error_string": (C.c_char_p, [P]), "orbx_status_string": (C.c_char_p, [I]),
+    "orbx_version": (C.c_char_p, []), "orbx_get_plan": (I, [P, I, I] + [P] * 6),
+    "orbx_detect_and_compute": (I, _IMAGE + [P] * 6 + [I, P]),
+    "orbx_detect_and_compute_batch_device": (I, _FRAMES + [P]), "orbx_detect_and_compute_batch_host": (I, _FRAMES),
+    "orbx_wait": (I, [P]), "orbx_batch_results_device": (I, [P, P]), "orbx_batch_results_host": (I, [P, I, P]),
+    "orbx_batch_fetch": (I, _BATCH_FETCH), "orbx_batch_fetch_previous": (I, _BATCH_FETCH),
+    "orbx_batch_prefetch": (I, [P]), "orbx_batch_prefetch_compact": (I, [P]),
+    "orbx_enable_stage_timing": (I, [P, I]), "orbx_last_stage_times": (I, [P, P]),
+    "orbx_stage_times_history": (I, [P, I, P]), "orbx_bench_stage": (I, [P, I, I, I, P]),
+    "orbx_set_fast_early_exit": (I, [P, I]), "orbx_set_fused_pyramid_blur": (I, [P, I]),
+    "orbx_set_top_rows_first": (I, [P, I]), "orbx_set_pipelined_batches": (I, [P, I]),
+    "orbx_set_host_results": (I, [P, I]), "orbx_fast_tile_counts": (I, [P, P, P]),
+    "orbx_pyramid_pixel_counts": (I, [P, P, P]), "orbx_debug_fill_pools": (I, [P, I]),
+    "orbx_debug_read_pyramid_level": (I, [P, I, I, P, Z]),
+    "orbx_lk_track": (I, [P, P, I, P, I, I, I, P, I, P, P, P] + _LK), "orbx_lk_pyramid_levels": (I, [I] * 4),
+    # stage operators
+    "orbx_fast_score": (I, _IMAGE + [I, I, P]), "orbx_nms": (I, [P, P, I, I, I, I, F, P, P, P]),
+    "orbx_fast": (I, _IMAGE + [I, I, I, I, P, P, P]), "orbx_orientations": (I, _IMAGE + [P, I, I, P]),
+    "orbx_brief": (I, _IMAGE + [P, P, I, P]), "orbx_harris": (I, _IMAGE + [P, I, I, F, P]),
+    "orbx_blur5_sep": (I, _IMAGE + [P, I]), "orbx_blur5_273": (I, _IMAGE + [P, I]),
+    "orbx_conv2d": (I, _IMAGE + [P, I, P]), "orbx_gaussian_blur_conv": (I, _IMAGE + [I, P]),
+    "orbx_gaussian_kernel": (I, [I, F, P]), "orbx_sobel": (I, _IMAGE + [I, P]),
+    "orbx_build_pyramid_level": (I, _IMAGE + [I, P, P, P]), "orbx_select_top": (I, [P, P, I, I, P, P]),
+    # matcher, pose, scale, bundle adjustment
+    "orbx_knn2": (I, [P, P, I, P, I, P, P]), "orbx_match_ratio": (I, [P, P, I, P, I, D, P, P, P, I, P]),
+    "orbx_batch_match_consecutive": (I, [P, D]), "orbx_batch_match_fetch": (I, [P, I, P, P, P, I, P]),
+    "orbx_estimate_pose": (I, [P, P, P, I, P, D, D, I, U64] + [P] * 7),
+    "orbx_batch_pose_consecutive": (I, [P, P, D, D, I, U64]), "orbx_batch_pose_fetch": (I, [P, I, I] + [P] * 6),
+    "orbx_batch_pose_mask": (I, [P, I, P, I, P]), "orbx_triangulate": (I, [P, P, P, I] + [P] * 5),
+    "orbx_estimate_scale": (I, [P, P, P, I, P, P, I, P, P]), "orbx_batch_scale_consecutive": (I, [P, P]),
+    "orbx_batch_scale_fetch": (I, [P, I, I, P, P, P]), "orbx_batch_points_fetch": (I, [P, I, P, P, I, P]),
+    "orbx_chain_trajectory": (I, [P, P, P, P, I, P]),
+    "orbx_bundle_adjust": (I, [P, P, I, P, I, P, I, P, P, P, D, I, P]),
+    "orbx_bundle_adjust_batch": (I, [P, P, I] + [P] * 8 + [D, I, P]),
+    # good features and their top-up
+    "orbx_corner_min_eigen_val": (I, _IMAGE + [P]), "orbx_good_features_to_track": (I, _IMAGE + [I, D, D, P, I, P]),
+    "orbx_good_features_batch_device": (I, _FRAMES + [I, D, D, P]),
+    "orbx_good_features_workspace_limit": (I, [P, Z]), "orbx_good_features_results_device": (I, [P, P]),
+    "orbx_good_features_fetch": (I, [P, I, I, P, P]),
+    "orbx_good_features_topup_device": (I, _FRAMES + [P, Z, Z, P, I, I, I, D, D, P]),
+    "orbx_good_features_topup_results_device": (I, [P, P]), "orbx_good_features_topup_fetch": (I, [P, I, I] + [P] * 4),
+    "orbx_good_features_topup": (I, _IMAGE + [P, I, I, D, D, P, P, I, P, P]),
+    "orbx_good_features_to_track_masked": (I, _IMAGE + [P, I, I, D, D, P, I, P]),
+    # Lucas-Kanade over frame windows
+    "orbx_lk_track_windows_device": (I, _LK_WINDOWS + [P]),
+    "orbx_lk_track_windows_fb_device": (I, _LK_WINDOWS + [F, P]),
+    "orbx_lk_windows_results_device": (I, [P, P]), "orbx_lk_windows_fb_results_device": (I, [P, P]),
+    "orbx_lk_windows_fetch": (I, [P, I, I, P, P, P]), "orbx_lk_windows_fb_fetch": (I, [P, I, I, P, P]),
+    "orbx_lk_workspace_limit": (I, [P, Z]), "orbx_lk_track_window": (I, _LK_WINDOW),
+    "orbx_lk_track_window_fb": (I, _LK_WINDOW + [F, P, P]),
+    # landmarks, their bundle adjustment, pose and scale of tracked pairs
+    "orbx_landmarks_build_device": (I, [P, P, P, P, I, I, I, P, P]), "orbx_landmarks_results_device": (I, [P, P]),
+    "orbx_landmarks_fetch": (I, [P, I, I] + [P] * 6 + [I] + [P] * 3 + [I, P, P]),
+    "orbx_bundle_adjust_landmarks_device": (I, [P, D, I, P]),
+    "orbx_bundle_adjust_landmarks_fetch": (I, [P, I, I, P, P, P, I, P]),
+    "orbx_bundle_adjust_tracks": (I, [P, P, P, P, I, I, P, D, I, P, P, P, P, I, P]),
+    "orbx_tracks_pose_device": (I, [P, P, P, P, I, I, I, D, D, I, U64, P]),
+    "orbx_tracks_pose_results_device": (I, [P, P]), "orbx_tracks_pose_fetch": (I, [P, I, I] + [P] * 10),
+    "orbx_tracks_pose_pair_fetch": (I, [P, I] + [P] * 4 + [I, P]),
+    "orbx_tracks_pose": (I, [P, P, P, P, I, I, D, D, I, U64] + [P] * 10),
+}
+EXPORTS = list(PROTOTYPES)  # every symbol include/orbx.h declares (checked by tests/test_abi.py)
 
 
 class Params(C.Structure):
@@ -71,6 +121,47 @@ class BatchView(C.Structure):
         ("descriptors", C.c_void_p), ("slot_capacity", C.c_int32), ("n", C.c_int32),
         ("keypoints16", C.c_void_p),
     ]
+
+
+class BaSummary(C.Structure):
+    _fields_ = [("termination", C.c_int32), ("iterations", C.c_int32), ("successful_steps", C.c_int32),
+                ("reserved", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("termination", "iterations", "successful_steps", "initial_cost",
+                                              "final_cost")}
+
+
+class GoodFeaturesView(C.Structure):
+    _fields_ = [("counts", C.c_void_p), ("corners_xy", C.c_void_p), ("slot_capacity", C.c_int32), ("n", C.c_int32)]
+
+
+class GoodFeaturesTopupView(C.Structure):
+    _fields_ = [("counts", C.c_void_p), ("carried", C.c_void_p), ("points_xy", C.c_void_p), ("origin", C.c_void_p),
+                ("slot_capacity", C.c_int32), ("n", C.c_int32)]
+
+
+class LkWindowsView(C.Structure):
+    _fields_ = [("tracks_xy", C.c_void_p), ("seen", C.c_void_p), ("err", C.c_void_p), ("slot_capacity", C.c_int32),
+                ("window_len", C.c_int32), ("n_windows", C.c_int32)]
+
+
+class LkWindowsFbView(C.Structure):
+    _fields_ = [("fb_d2", C.c_void_p), ("lost", C.c_void_p), ("slot_capacity", C.c_int32), ("window_len", C.c_int32),
+                ("n_windows", C.c_int32)]
+
+
+class LandmarksView(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("pose_offset", C.c_void_p), ("point_offset", C.c_void_p),
+                ("obs_offset", C.c_void_p), ("points3", C.c_void_p), ("rows", C.c_void_p), ("obs_pose", C.c_void_p),
+                ("obs_xy", C.c_void_p), ("slot_of_point", C.c_void_p), ("slot_capacity", C.c_int32),
+                ("window_len", C.c_int32), ("n_windows", C.c_int32)]
+
+
+class TracksPoseView(C.Structure):
+    _fields_ = [("pose", C.c_void_p), ("n", C.c_void_p), ("scale", C.c_void_p), ("slot_of", C.c_void_p),
+                ("mask", C.c_void_p), ("xyz", C.c_void_p), ("valid", C.c_void_p), ("slot_capacity", C.c_int32),
+                ("window_len", C.c_int32), ("n_windows", C.c_int32), ("n_pairs", C.c_int32)]
 
 
 class OrbxError(RuntimeError):
@@ -104,7 +195,7 @@ def _share_hip_runtime_with_torch():
 
 
 def load():
-    """Load liborbx.so (raises OSError if it has not been built)."""
+    """Load liborbx.so (raises OSError if it has not been built) and declare every prototype of PROTOTYPES."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -112,13 +203,11 @@ def load():
                           "or `make -C visual-odometry-gpu_amd/csrc` (there is no CPU fallback)")
         _share_hip_runtime_with_torch()
         lib = C.CDLL(LIB_PATH)
-        lib.orbx_last_error_string.restype = C.c_char_p
-        lib.orbx_last_error_string.argtypes = [C.c_void_p]
-        lib.orbx_status_string.restype = C.c_char_p
-        lib.orbx_version.restype = C.c_char_p
-        lib.orbx_create.argtypes = [C.POINTER(Params), C.POINTER(C.c_void_p)]
-        lib.orbx_destroy.argtypes = [C.c_void_p]
-        lib.orbx_destroy.restype = None
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            f = getattr(lib, name, None)  # (a symbol the library lacks is build()'s and tests/test_abi.py's to report)
+            if f is not None:
+                f.restype = restype
+                f.argtypes = argtypes
         _lib = lib
     return _lib
 
@@ -142,6 +231,7 @@ def default_params(flavour="gpu", **kw):
     return p
 
 
+# ---- host arguments
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -153,13 +243,171 @@ def _img(a):
     return a
 
 
+def _gftt_view(a):
+    # a row-strided uint8 view (a region of a larger image) is handed over as it is
+    if isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1 and \
+            a.strides[0] >= a.shape[1]:
+        return a
+    return _img(a)
+
+
 def _kps(k):
-    k = np.ascontiguousarray(k, dtype=np.int32).reshape(-1, 2)
-    return k
+    return np.ascontiguousarray(k, dtype=np.int32).reshape(-1, 2)
 
 
-class Context:
-    """One orbx_ctx: single-threaded, owns all device memory, one per GPU."""
+def _desc(d):
+    return np.ascontiguousarray(d, dtype=np.uint8).reshape(-1, 32)
+
+
+def _f64(a, shape, copy=False):
+    """`a` as a C-contiguous float64 array of `shape` (K: (3, 3)) for _dp(); copy: always one of the binding's own,
+    for an entry that writes in place."""
+    a = np.asarray(a, np.float64).reshape(shape)
+    return np.array(a, order="C") if copy else np.ascontiguousarray(a)
+
+
+def _i32(a):
+    return np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
+
+
+# The arrays of _f64 and _i32 go to the library as typed pointers, which every prototype a caller may have put on the
+# shared function object takes: the table's c_void_p, and a POINTER(c_double) / POINTER(c_int32) of the caller's own.
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _point_pairs(pts1, pts2):
+    p1 = np.ascontiguousarray(np.asarray(pts1, np.float32).reshape(-1, 2))
+    p2 = np.ascontiguousarray(np.asarray(pts2, np.float32).reshape(-1, 2))
+    if p1.shape != p2.shape:
+        raise ValueError("pts1 and pts2 differ in shape")
+    return p1, p2, p1.shape[0]
+
+
+def _observations(obs_point, obs_pose, obs_xy):
+    op, oq, xy = _i32(obs_point), _i32(obs_pose), _f64(obs_xy, (-1, 2), copy=True)
+    if not len(op) == len(oq) == len(xy):
+        raise ValueError("obs_point, obs_pose and obs_xy differ in length")
+    return op, oq, xy
+
+
+def _host_window(tracks, seen):
+    """One window of host tracks (slots, window_len, 2) and seen (slots): (tracks, seen, slots, window_len)."""
+    tracks = np.ascontiguousarray(tracks, np.float32)
+    if tracks.ndim != 3 or tracks.shape[2] != 2:
+        raise ValueError("tracks must be (slots, window_len, 2) float32")
+    seen = np.ascontiguousarray(seen, np.int32).reshape(-1)
+    if len(seen) != tracks.shape[0]:
+        raise ValueError("seen must have one entry per slot")
+    return (tracks, seen) + tracks.shape[:2]
+
+
+def _stream(stream):
+    """A hipStream_t given as an int, or None / 0 for the context's own stream."""
+    return stream or None
+
+
+def _count(n, first, total):
+    """The n of a fetch of [first, first + n); None: everything from `first` on.  total: a number, or a call that
+    yields it (made only then)."""
+    if n is not None:
+        return n
+    return (total() if callable(total) else total) - first
+
+
+# ---- device arguments (free of Context: tests/test_binding_prototypes.py runs their refusals without a GPU)
+def _frame_strides(shape, strides):
+    """(row_stride, frame_stride) of an (n, h, w) batch with these strides.  One frame may come with any stride(0)
+    -- 0 after expand(), the batch's own after a slice -- so it gets at least the frame's own extent."""
+    n, h, w = shape
+    rs = strides[1]
+    return rs, max(strides[0], rs * (h - 1) + w) if n == 1 else strides[0]
+
+
+def _frames_arg(frames):
+    """An (n, h, w) uint8 frames argument, a torch device tensor (any strides with unit pixel stride) or a numpy array
+    (copied to the device): (tensor, n, h, w, row_stride, frame_stride, whether it was uploaded)."""
+    import torch
+
+    uploaded = isinstance(frames, np.ndarray)
+    if uploaded:
+        frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).cuda()
+    if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda or frames.stride(2) != 1:
+        raise ValueError("frames must be (n, h, w) uint8 on the device with unit pixel stride")
+    return (frames,) + tuple(frames.shape) + _frame_strides(frames.shape, frames.stride()) + (uploaded,)
+
+
+def _device_arg(a, dtype, shape_ok, message, keep):
+    """A device array given as a contiguous torch device tensor of `dtype` (checked with shape_ok(tensor), refused
+    with `message`, appended to `keep`), as a numpy array (copied to the device first) or as a raw device address
+    or None (passed through): (address, the tensor or None, whether it was uploaded)."""
+    import torch
+
+    uploaded = isinstance(a, np.ndarray)
+    if uploaded:
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
+    if not torch.is_tensor(a):
+        return a, None, False
+    if a.dtype != getattr(torch, np.dtype(dtype).name) or not a.is_cuda or not a.is_contiguous() or not shape_ok(a):
+        raise ValueError(message)
+    keep.append(a)
+    return a.data_ptr(), a, uploaded
+
+
+def _sync_uploads(*uploaded):
+    if any(uploaded):
+        import torch
+
+        torch.cuda.synchronize()  # the uploads ran on torch's stream
+
+
+def _lk_points_arg(points, n_windows, slot_capacity, keep):
+    """The points of lk_track_windows: (address, slot_capacity, whether they were uploaded)."""
+    points, t, uploaded = _device_arg(
+        points, np.float32, lambda t: t.dim() == 3 and t.shape[0] == n_windows and t.shape[2] == 2,
+        "points must be (n_windows, slot_capacity, 2) float32, contiguous, on the device", keep)
+    if t is None:
+        if slot_capacity is None:
+            raise ValueError("a raw points address needs slot_capacity")
+    elif slot_capacity not in (None, t.shape[1]):
+        raise ValueError("slot_capacity differs from points.shape[1]")
+    else:
+        slot_capacity = t.shape[1]
+    return points, slot_capacity, uploaded
+
+
+def _tracks_args(tracks, seen, n_windows, slot_capacity, window_len):
+    """The tracks block of landmarks_build and tracks_pose: an LkWindowsView (seen and the three sizes come from it),
+    or tracks and seen as torch device tensors, numpy arrays (copied to the device, and waited for) or raw device
+    addresses (then with the three sizes): (tracks address, seen address, n_windows, slot_capacity, window_len, the
+    tensors to keep alive)."""
+    if isinstance(tracks, LkWindowsView):
+        v = tracks
+        tracks, seen = v.tracks_xy, v.seen
+        n_windows, slot_capacity, window_len = v.n_windows, v.slot_capacity, v.window_len
+    keep = []
+    tracks, t, up_tracks = _device_arg(
+        tracks, np.float32, lambda t: t.dim() == 4 and t.shape[3] == 2,
+        "tracks must be (n_windows, slots, window_len, 2) float32, contiguous, on the device", keep)
+    if t is None:
+        if None in (n_windows, slot_capacity, window_len):
+            raise ValueError("a raw tracks address needs n_windows, slot_capacity and window_len")
+    elif (n_windows, slot_capacity, window_len) not in ((None, None, None), tuple(t.shape[:3])):
+        raise ValueError("n_windows / slot_capacity / window_len differ from tracks.shape")
+    else:
+        n_windows, slot_capacity, window_len = t.shape[:3]
+    seen, _, up_seen = _device_arg(seen, np.int32, lambda t: t.numel() == n_windows * slot_capacity,
+                                   "seen must be (n_windows, slots) int32, contiguous, on the device", keep)
+    _sync_uploads(up_tracks, up_seen)
+    return tracks, seen, n_windows, slot_capacity, window_len, keep
+
+
+class _Core:
+    """The context itself, the whole path and the stage operators."""
 
     def __init__(self, params=None, **kw):
         self._lib = load()
@@ -173,8 +421,6 @@ class Context:
         self._h = h
         self._cap_cache = {}
         self._dac = self._lib.orbx_detect_and_compute
-        self._dac.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [
-            C.c_int, C.POINTER(C.c_int)]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -238,16 +484,15 @@ class Context:
     def batch_device(self, d_ptr, n, width, height, row_stride=None, frame_stride=None, stream=None):
         row_stride = width if row_stride is None else row_stride
         frame_stride = row_stride * height if frame_stride is None else frame_stride
-        self._chk(self._lib.orbx_detect_and_compute_batch_device(
-            self._h, C.c_void_p(d_ptr), n, width, height, row_stride, C.c_size_t(frame_stride),
-            C.c_void_p(stream) if stream else None))
+        self._chk(self._lib.orbx_detect_and_compute_batch_device(self._h, d_ptr, n, width, height, row_stride,
+                                                                 frame_stride, _stream(stream)))
 
     def batch_host(self, frames):
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         if frames.ndim != 3:
             raise ValueError("frames must be (n, h, w) uint8")
         n, h, w = frames.shape
-        self._chk(self._lib.orbx_detect_and_compute_batch_host(self._h, _ptr(frames), n, w, h, w, C.c_size_t(w * h)))
+        self._chk(self._lib.orbx_detect_and_compute_batch_host(self._h, _ptr(frames), n, w, h, w, w * h))
 
     def wait(self):
         self._chk(self._lib.orbx_wait(self._h))
@@ -333,7 +578,7 @@ class Context:
         whole-path batch of width x height frames (orbx_debug_read_pyramid_level)."""
         plan = self.plan(width, height)
         out = np.zeros((int(plan["level_h"][level]), int(plan["level_w"][level])), np.uint8)
-        self._chk(self._lib.orbx_debug_read_pyramid_level(self._h, int(frame), int(level), _ptr(out), C.c_size_t(out.size)))
+        self._chk(self._lib.orbx_debug_read_pyramid_level(self._h, int(frame), int(level), _ptr(out), out.size))
         return out
 
     def lk_track(self, prev, nxt, pts, win=21, max_level=3, max_iters=30, epsilon=0.01):
@@ -350,11 +595,8 @@ class Context:
         out = np.zeros((max(n, 1), 2), np.float32)
         st = np.zeros(max(n, 1), np.uint8)
         err = np.zeros(max(n, 1), np.float32)
-        f = self._lib.orbx_lk_track
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]
-        self._chk(f(self._h, _ptr(prev), w, _ptr(nxt), w, w, h, _ptr(pts), n, _ptr(out), _ptr(st), _ptr(err), win,
-                    max_level, max_iters, epsilon))
+        self._chk(self._lib.orbx_lk_track(self._h, _ptr(prev), w, _ptr(nxt), w, w, h, _ptr(pts), n, _ptr(out), _ptr(st),
+                                          _ptr(err), win, max_level, max_iters, epsilon))
         return out[:n].copy(), st[:n].copy(), err[:n].copy()
 
     def fast_tile_counts(self):
@@ -393,8 +635,8 @@ class Context:
         h, w = scores.shape
         kps = np.zeros((max(nfeatures, 1), 2), np.int32)
         cnt, tot = C.c_int(0), C.c_int(0)
-        self._chk(self._lib.orbx_nms(self._h, _ptr(scores), w, h, nms_window, nfeatures, C.c_float(threshold),
-                                     _ptr(kps), C.byref(cnt), C.byref(tot)))
+        self._chk(self._lib.orbx_nms(self._h, _ptr(scores), w, h, nms_window, nfeatures, threshold, _ptr(kps),
+                                     C.byref(cnt), C.byref(tot)))
         return kps[:cnt.value].copy(), tot.value
 
     def fast(self, image, threshold, n, nms_window, nfeatures):
@@ -430,8 +672,8 @@ class Context:
         h, w = image.shape
         kps = _kps(kps)
         out = np.zeros(len(kps), np.float32)
-        self._chk(self._lib.orbx_harris(self._h, _ptr(image), w, h, image.strides[0], _ptr(kps), len(kps), window,
-                                        C.c_float(k), _ptr(out)))
+        self._chk(self._lib.orbx_harris(self._h, _ptr(image), w, h, image.strides[0], _ptr(kps), len(kps), window, k,
+                                        _ptr(out)))
         return out
 
     def blur5_sep(self, image):
@@ -490,12 +732,7 @@ class Context:
         return idx[:kept.value].copy()
 
 
-def _desc(d):
-    d = np.ascontiguousarray(d, dtype=np.uint8).reshape(-1, 32)
-    return d
-
-
-def _matcher_methods():
+class _Matcher:
     def knn2(self, query, train):
         """flann->knnMatch(des1, des2, matches, 2) as exact Hamming 2-NN: (idx[nq,2], dist[nq,2])."""
         q, t = _desc(query), _desc(train)
@@ -510,13 +747,13 @@ def _matcher_methods():
         n = max(len(q), 1)
         qi, ti, d1 = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
         cnt = C.c_int(0)
-        self._chk(self._lib.orbx_match_ratio(self._h, _ptr(q), len(q), _ptr(t), len(t), C.c_double(ratio), _ptr(qi),
-                                             _ptr(ti), _ptr(d1), n, C.byref(cnt)))
+        self._chk(self._lib.orbx_match_ratio(self._h, _ptr(q), len(q), _ptr(t), len(t), ratio, _ptr(qi), _ptr(ti),
+                                             _ptr(d1), n, C.byref(cnt)))
         m = cnt.value
         return qi[:m].copy(), ti[:m].copy(), d1[:m].copy()
 
     def batch_match_consecutive(self, ratio=0.8):
-        self._chk(self._lib.orbx_batch_match_consecutive(self._h, C.c_double(ratio)))
+        self._chk(self._lib.orbx_batch_match_consecutive(self._h, ratio))
 
     def batch_match_fetch(self, pair, capacity):
         qi, ti, d1 = np.zeros(capacity, np.int32), np.zeros(capacity, np.int32), np.zeros(capacity, np.int32)
@@ -526,56 +763,32 @@ def _matcher_methods():
         m = cnt.value
         return qi[:m].copy(), ti[:m].copy(), d1[:m].copy()
 
-    for f in (knn2, match_ratio, batch_match_consecutive, batch_match_fetch):
-        setattr(Context, f.__name__, f)
 
-
-_matcher_methods()
-
-
-POSE_MAX_ITERS = 100000  # ORBX_POSE_MAX_ITERS
-
-
-def _pose_methods():
+class _Pose:
     """Relative pose: findEssentialMat(RANSAC) + recoverPose (include/orbx.h)."""
-
-    def _K(K):
-        K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))
-        return K, K.ctypes.data_as(C.POINTER(C.c_double))
 
     def estimate_pose(self, pts1, pts2, K, prob=0.999, threshold=1.0, max_iters=1000, seed=0):
         """get_pose on (n, 2) point arrays: dict with E, R (3x3), t (3,), mask (n,), inliers, good, iters."""
-        p1 = np.ascontiguousarray(np.asarray(pts1, np.float32).reshape(-1, 2))
-        p2 = np.ascontiguousarray(np.asarray(pts2, np.float32).reshape(-1, 2))
-        if p1.shape != p2.shape:
-            raise ValueError("pts1 and pts2 differ in shape")
-        n = p1.shape[0]
-        K, kp = _K(K)
+        p1, p2, n = _point_pairs(pts1, pts2)
+        K = _f64(K, (3, 3))
         E, R, t = np.zeros(9), np.zeros(9), np.zeros(3)
         mask = np.zeros(max(n, 1), np.uint8)
         inl, good, iters = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        f = self._lib.orbx_estimate_pose
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
-                      C.c_int, C.c_uint64] + [C.c_void_p] * 7
-        self._chk(f(self._h, _ptr(p1), _ptr(p2), n, kp, prob, threshold, max_iters, seed, _ptr(E), _ptr(R), _ptr(t),
-                    _ptr(mask), C.byref(inl), C.byref(good), C.byref(iters)))
+        self._chk(self._lib.orbx_estimate_pose(self._h, _ptr(p1), _ptr(p2), n, _dp(K), prob, threshold, max_iters,
+                                               seed, _ptr(E), _ptr(R), _ptr(t), _ptr(mask), C.byref(inl),
+                                               C.byref(good), C.byref(iters)))
         return {"E": E.reshape(3, 3), "R": R.reshape(3, 3), "t": t, "mask": mask[:n], "inliers": inl.value,
                 "good": good.value, "iters": iters.value}
 
     def batch_pose_consecutive(self, K, prob=0.999, threshold=1.0, max_iters=1000, seed=0):
         """Poses every pair of the last batch_match_consecutive on the device (no host round trip)."""
-        K, kp = _K(K)
-        f = self._lib.orbx_batch_pose_consecutive
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_uint64]
-        self._chk(f(self._h, kp, prob, threshold, max_iters, seed))
-        v = BatchView()
-        self._chk(self._lib.orbx_batch_results_device(self._h, C.byref(v)))
-        self._pose_pairs = v.n - 1
+        K = _f64(K, (3, 3))
+        self._chk(self._lib.orbx_batch_pose_consecutive(self._h, _dp(K), prob, threshold, max_iters, seed))
+        self._pose_pairs = self.batch_view().n - 1
 
     def batch_pose_fetch(self, first=0, n=None):
         """dict of arrays for pairs [first, first + n): E, R (n, 3, 3), t (n, 3), inliers, good, iters (n,)."""
-        if n is None:
-            n = getattr(self, "_pose_pairs", 0) - first
+        n = _count(n, first, getattr(self, "_pose_pairs", 0))
         m = max(n, 0)  # a negative n (nothing posed yet) is the C entry's to refuse
         E, R, t = np.zeros((m, 3, 3)), np.zeros((m, 3, 3)), np.zeros((m, 3))
         inl, good, iters = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
@@ -593,42 +806,27 @@ def _pose_methods():
         self._chk(self._lib.orbx_batch_pose_mask(self._h, pair, _ptr(mask), cnt.value, C.byref(cnt)))
         return mask[:cnt.value]
 
-    for f in (estimate_pose, batch_pose_consecutive, batch_pose_fetch, batch_pose_mask):
-        setattr(Context, f.__name__, f)
+
+def _valid(v, n):
+    if v is None:
+        return None
+    v = np.ascontiguousarray(np.asarray(v).reshape(-1) != 0, np.uint8)
+    if len(v) != n:
+        raise ValueError("a valid array and its point list differ in length")
+    return v
 
 
-_pose_methods()
-
-
-def _scale_methods():
+class _Scale:
     """Triangulation and relative scale: the reference's get_scale (include/orbx.h)."""
-    DP = C.POINTER(C.c_double)
-
-    def _d(a, shape):
-        a = np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
-        return a, a.ctypes.data_as(DP)
-
-    def _valid(v, n):
-        if v is None:
-            return None
-        v = np.ascontiguousarray(np.asarray(v).reshape(-1) != 0, np.uint8)
-        if len(v) != n:
-            raise ValueError("a valid array and its point list differ in length")
-        return v
 
     def triangulate(self, pts1, pts2, K, R, t):
         """cv::triangulatePoints(K [I|0], K [R|t], pts1, pts2) + X/w: (xyz (n, 3) float32, valid (n,) uint8)."""
-        p1 = np.ascontiguousarray(np.asarray(pts1, np.float32).reshape(-1, 2))
-        p2 = np.ascontiguousarray(np.asarray(pts2, np.float32).reshape(-1, 2))
-        if p1.shape != p2.shape:
-            raise ValueError("pts1 and pts2 differ in shape")
-        n = p1.shape[0]
-        (K, kp), (R, rp), (t, tp) = _d(K, (3, 3)), _d(R, (3, 3)), _d(t, (3,))
+        p1, p2, n = _point_pairs(pts1, pts2)
+        K, R, t = _f64(K, (3, 3)), _f64(R, (3, 3)), _f64(t, (3,))
         xyz = np.zeros((max(n, 1), 3), np.float32)
         valid = np.zeros(max(n, 1), np.uint8)
-        f = self._lib.orbx_triangulate
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, DP, DP, DP, C.c_void_p, C.c_void_p]
-        self._chk(f(self._h, _ptr(p1), _ptr(p2), n, kp, rp, tp, _ptr(xyz), _ptr(valid)))
+        self._chk(self._lib.orbx_triangulate(self._h, _ptr(p1), _ptr(p2), n, _dp(K), _dp(R), _dp(t), _ptr(xyz),
+                                             _ptr(valid)))
         return xyz[:n], valid[:n]
 
     def estimate_scale(self, prev_xyz, cur_xyz, prev_valid=None, cur_valid=None):
@@ -637,36 +835,27 @@ def _scale_methods():
         b = np.ascontiguousarray(np.asarray(cur_xyz, np.float32).reshape(-1, 3))
         va, vb = _valid(prev_valid, len(a)), _valid(cur_valid, len(b))
         scale, used = C.c_double(0), C.c_int32(0)
-        f = self._lib.orbx_estimate_scale
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, DP,
-                      C.POINTER(C.c_int32)]
-        self._chk(f(self._h, _ptr(a), _ptr(va), len(a), _ptr(b), _ptr(vb), len(b), C.byref(scale), C.byref(used)))
+        self._chk(self._lib.orbx_estimate_scale(self._h, _ptr(a), _ptr(va), len(a), _ptr(b), _ptr(vb), len(b),
+                                                C.byref(scale), C.byref(used)))
         return scale.value, used.value
 
     def batch_scale_consecutive(self, K):
         """Triangulates and scales every pair of the last batch_pose_consecutive on the device."""
-        K, kp = _d(K, (3, 3))
-        f = self._lib.orbx_batch_scale_consecutive
-        f.argtypes = [C.c_void_p, DP]
-        self._chk(f(self._h, kp))
+        self._chk(self._lib.orbx_batch_scale_consecutive(self._h, _dp(_f64(K, (3, 3)))))
         self._scale_pairs = getattr(self, "_pose_pairs", 0)
 
     def batch_scale_fetch(self, first=0, n=None):
         """dict of arrays for pairs [first, first + n): scale (float64), triplets, ratios_used (int32)."""
-        if n is None:
-            n = getattr(self, "_scale_pairs", 0) - first
+        n = _count(n, first, getattr(self, "_scale_pairs", 0))
         m = max(n, 0)  # a negative n (nothing scaled yet) is the C entry's to refuse
         scale, trip, used = np.zeros(m), np.zeros(m, np.int32), np.zeros(m, np.int32)
-        f = self._lib.orbx_batch_scale_fetch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        self._chk(f(self._h, first, n, _ptr(scale), _ptr(trip), _ptr(used)))
+        self._chk(self._lib.orbx_batch_scale_fetch(self._h, first, n, _ptr(scale), _ptr(trip), _ptr(used)))
         return {"scale": scale, "triplets": trip, "ratios_used": used}
 
     def batch_points_fetch(self, pair, capacity=None):
         """The triangulated points of one pair in batch_match_fetch order: (xyz (n, 3) float32, valid (n,) uint8).
         capacity=None: sized from the pair's match count."""
         f = self._lib.orbx_batch_points_fetch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         cnt = C.c_int(0)
         if capacity is None:
             st = f(self._h, pair, None, None, 0, C.byref(cnt))
@@ -678,51 +867,19 @@ def _scale_methods():
         self._chk(f(self._h, pair, _ptr(xyz), _ptr(valid), capacity, C.byref(cnt)))
         return xyz[:cnt.value], valid[:cnt.value]
 
-    for f in (triangulate, estimate_scale, batch_scale_consecutive, batch_scale_fetch, batch_points_fetch):
-        setattr(Context, f.__name__, f)
 
-
-_scale_methods()
-
-
-BA_CONVERGENCE, BA_NO_CONVERGENCE, BA_FAILURE, BA_SKIPPED = range(4)
-BA_MAX_POSES = 8
-
-
-class BaSummary(C.Structure):
-    _fields_ = [("termination", C.c_int32), ("iterations", C.c_int32), ("successful_steps", C.c_int32),
-                ("reserved", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k in ("termination", "iterations", "successful_steps", "initial_cost",
-                                              "final_cost")}
-
-
-def _ba_methods():
+class _BundleAdjust:
     """Sliding-window bundle adjustment: the reference's Ceres solve (include/orbx.h)."""
-    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-
-    def _d(a, shape):
-        a = np.array(np.asarray(a, np.float64).reshape(shape), order="C")  # a copy: the entry writes in place
-        return a, a.ctypes.data_as(DP)
-
-    def _i(a):
-        a = np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
-        return a, a.ctypes.data_as(IP)
 
     def bundle_adjust(self, K, poses, points, obs_point, obs_pose, obs_xy, huber_delta=1.0, max_iters=200):
         """One window: (poses (W, 6), points (N, 3), summary dict).  poses: angle-axis + translation, world ->
         camera; pose 0 is constant.  The outputs equal the inputs unless the summary says convergence."""
-        (K, kp), (poses, pp), (points, xp) = _d(K, (3, 3)), _d(poses, (-1, 6)), _d(points, (-1, 3))
-        (op, opp), (oq, oqp), (xy, xyp) = _i(obs_point), _i(obs_pose), _d(obs_xy, (-1, 2))
-        if not len(op) == len(oq) == len(xy):
-            raise ValueError("obs_point, obs_pose and obs_xy differ in length")
+        K, poses, points = _f64(K, (3, 3)), _f64(poses, (-1, 6), copy=True), _f64(points, (-1, 3), copy=True)
+        op, oq, xy = _observations(obs_point, obs_pose, obs_xy)
         out = BaSummary()
-        f = self._lib.orbx_bundle_adjust
-        f.argtypes = [C.c_void_p, DP, C.c_int, DP, C.c_int, DP, C.c_int, IP, IP, DP, C.c_double, C.c_int,
-                      C.POINTER(BaSummary)]
-        self._chk(f(self._h, kp, len(poses), pp, len(points), xp, len(op), opp, oqp, xyp, huber_delta, max_iters,
-                    C.byref(out)))
+        self._chk(self._lib.orbx_bundle_adjust(self._h, _dp(K), len(poses), _dp(poses), len(points), _dp(points),
+                                               len(op), _ip(op), _ip(oq), _dp(xy), huber_delta, max_iters,
+                                               C.byref(out)))
         return poses, points, out.as_dict()
 
     def bundle_adjust_batch(self, K, windows, huber_delta=1.0, max_iters=200):
@@ -730,90 +887,53 @@ def _ba_methods():
         obs_xy) with window-local indices; returns a list of (poses, points, summary dict)."""
         n = len(windows)
         cat = lambda k, dt, sh: np.concatenate([np.asarray(w[k], dt).reshape(sh) for w in windows]) if n else np.zeros(sh, dt)
-        off = lambda k, sh: np.concatenate([[0], np.cumsum([len(np.asarray(w[k]).reshape(sh)) for w in windows])]).astype(np.int32)
-        (K, kp) = _d(K, (3, 3))
-        (poses, pp), (points, xp), (xy, xyp) = _d(cat(0, np.float64, (-1, 6)), (-1, 6)), _d(cat(1, np.float64, (-1, 3)), (-1, 3)), _d(cat(4, np.float64, (-1, 2)), (-1, 2))
-        (op, opp), (oq, oqp) = _i(cat(2, np.int32, (-1,))), _i(cat(3, np.int32, (-1,)))
-        (po, pop), (xo, xop), (oo, oop) = _i(off(0, (-1, 6))), _i(off(1, (-1, 3))), _i(off(2, (-1,)))
-        if not len(op) == len(oq) == len(xy):
-            raise ValueError("obs_point, obs_pose and obs_xy differ in length")
+        off = lambda k, sh: _i32(np.concatenate([[0], np.cumsum([len(np.asarray(w[k]).reshape(sh)) for w in windows])]))
+        K = _f64(K, (3, 3))
+        poses, points = _f64(cat(0, np.float64, (-1, 6)), (-1, 6), copy=True), _f64(cat(1, np.float64, (-1, 3)), (-1, 3), copy=True)
+        op, oq, xy = _observations(cat(2, np.int32, (-1,)), cat(3, np.int32, (-1,)), cat(4, np.float64, (-1, 2)))
+        po, xo, oo = off(0, (-1, 6)), off(1, (-1, 3)), off(2, (-1,))
         out = (BaSummary * max(n, 1))()
-        f = self._lib.orbx_bundle_adjust_batch
-        f.argtypes = [C.c_void_p, DP, C.c_int, IP, DP, IP, DP, IP, IP, IP, DP, C.c_double, C.c_int,
-                      C.POINTER(BaSummary)]
-        self._chk(f(self._h, kp, n, pop, pp, xop, xp, oop, opp, oqp, xyp, huber_delta, max_iters, out))
+        self._chk(self._lib.orbx_bundle_adjust_batch(self._h, _dp(K), n, _ip(po), _dp(poses), _ip(xo), _dp(points),
+                                                     _ip(oo), _ip(op), _ip(oq), _dp(xy), huber_delta, max_iters,
+                                                     out))
         return [(poses[po[w]:po[w + 1]], points[xo[w]:xo[w + 1]], out[w].as_dict()) for w in range(n)]
 
-    for f in (bundle_adjust, bundle_adjust_batch):
-        setattr(Context, f.__name__, f)
 
-
-_ba_methods()
-
-
-class GoodFeaturesView(C.Structure):
-    _fields_ = [("counts", C.c_void_p), ("corners_xy", C.c_void_p), ("slot_capacity", C.c_int32), ("n", C.c_int32)]
-
-
-def _gftt_view(a):
-    # a row-strided uint8 view (a region of a larger image) is handed over as it is
-    if isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1 and \
-            a.strides[0] >= a.shape[1]:
-        return a
-    return _img(a)
-
-
-def _gftt_methods():
+class _GoodFeatures:
     """Shi-Tomasi corners: cv::goodFeaturesToTrack (include/orbx.h; DESIGN.md §9 rank 8)."""
-    _view = _gftt_view
 
     def corner_min_eigen_val(self, image):
         """cv::cornerMinEigenVal(image, eig, 3, 3): the (h, w) float32 response map."""
-        image = _view(image)
+        image = _gftt_view(image)
         h, w = image.shape
         out = np.zeros((h, w), np.float32)
-        f = self._lib.orbx_corner_min_eigen_val
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        self._chk(f(self._h, _ptr(image), w, h, image.strides[0], _ptr(out)))
+        self._chk(self._lib.orbx_corner_min_eigen_val(self._h, _ptr(image), w, h, image.strides[0], _ptr(out)))
         return out
 
     def good_features_to_track(self, image, max_corners=2000, quality_level=0.01, min_distance=8.0, capacity=None):
         """cv::goodFeaturesToTrack(image, corners, maxCorners, qualityLevel, minDistance) as called at
         with_bundle_adjustment.cpp:586-593: (n, 2) float32 corners (x, y), strongest first.  max_corners <= 0: no
         limit.  capacity=None: sized for the call (max_corners, or every interior pixel)."""
-        image = _view(image)
+        image = _gftt_view(image)
         h, w = image.shape
         if capacity is None:
             capacity = max_corners if max_corners > 0 else max((w - 2) * (h - 2), 1)
         out = np.zeros((max(capacity, 1), 2), np.float32)
         cnt = C.c_int(0)
-        f = self._lib.orbx_good_features_to_track
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
-                      C.c_int, C.POINTER(C.c_int)]
-        self._chk(f(self._h, _ptr(image), w, h, image.strides[0], max_corners, quality_level, min_distance, _ptr(out),
-                    capacity, C.byref(cnt)))
+        self._chk(self._lib.orbx_good_features_to_track(self._h, _ptr(image), w, h, image.strides[0], max_corners,
+                                                        quality_level, min_distance, _ptr(out), capacity,
+                                                        C.byref(cnt)))
         return out[:cnt.value].copy()
 
     def good_features_batch(self, frames, max_corners=2000, quality_level=0.01, min_distance=8.0, stream=None):
         """orbx_good_features_batch_device on (n, h, w) uint8 frames: a torch device tensor (any strides with unit
         pixel stride; the caller has synchronised its producer, or passes the producer's stream) or a numpy array
         (copied to the device first).  Asynchronous; good_features_fetch delivers the results."""
-        import torch
-
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).cuda()
-            torch.cuda.synchronize()
-        if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda or frames.stride(2) != 1:
-            raise ValueError("frames must be (n, h, w) uint8 on the device with unit pixel stride")
+        frames, n, h, w, rs, fs, uploaded = _frames_arg(frames)
+        _sync_uploads(uploaded)
         self._gf_frames = frames  # kept alive until the next batch
-        n, h, w = frames.shape
-        rs = frames.stride(1)
-        fs = max(frames.stride(0), rs * (h - 1) + w) if n == 1 else frames.stride(0)
-        f = self._lib.orbx_good_features_batch_device
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_double,
-                      C.c_double, C.c_void_p]
-        self._chk(f(self._h, C.c_void_p(frames.data_ptr()), n, w, h, rs, fs, max_corners, quality_level,
-                    min_distance, C.c_void_p(stream) if stream else None))
+        self._chk(self._lib.orbx_good_features_batch_device(self._h, frames.data_ptr(), n, w, h, rs, fs, max_corners,
+                                                            quality_level, min_distance, _stream(stream)))
 
     def good_features_view(self):
         """The device-side result block of the last good-features batch (orbx_good_features_results_device)."""
@@ -824,35 +944,18 @@ def _gftt_methods():
     def good_features_fetch(self, first=0, n=None):
         """Results of frames [first, first + n) of the last good-features batch: a list of (count, 2) float32 arrays."""
         v = self.good_features_view()
-        if n is None:
-            n = v.n - first
+        n = _count(n, first, v.n)
         counts = np.zeros(max(n, 1), np.int32)
         xy = np.zeros((max(n, 1), v.slot_capacity, 2), np.float32)
-        f = self._lib.orbx_good_features_fetch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        self._chk(f(self._h, first, n, _ptr(counts), _ptr(xy)))
+        self._chk(self._lib.orbx_good_features_fetch(self._h, first, n, _ptr(counts), _ptr(xy)))
         return [xy[i, :counts[i]].copy() for i in range(n)]
 
     def good_features_workspace_limit(self, nbytes):
         """Bound of the good-features workspace in bytes (0: the default); a larger batch runs in slices."""
-        f = self._lib.orbx_good_features_workspace_limit
-        f.argtypes = [C.c_void_p, C.c_size_t]
-        self._chk(f(self._h, nbytes))
-
-    for f in (corner_min_eigen_val, good_features_to_track, good_features_batch, good_features_view,
-              good_features_fetch, good_features_workspace_limit):
-        setattr(Context, f.__name__, f)
+        self._chk(self._lib.orbx_good_features_workspace_limit(self._h, nbytes))
 
 
-_gftt_methods()
-
-
-class GoodFeaturesTopupView(C.Structure):
-    _fields_ = [("counts", C.c_void_p), ("carried", C.c_void_p), ("points_xy", C.c_void_p), ("origin", C.c_void_p),
-                ("slot_capacity", C.c_int32), ("n", C.c_int32)]
-
-
-def _gftt_topup_methods():
+class _GoodFeaturesTopup:
     """Masked Shi-Tomasi detection that tops up tracked points (include/orbx.h)."""
 
     def good_features_topup(self, frames, seeds, seen=None, seen_min=0, seed_capacity=None, seed_point_stride=2,
@@ -864,45 +967,22 @@ def _gftt_topup_methods():
         seed_frame_stride (in floats) -- e.g. tracks_xy + 8 * (window_len - 1) of lk_windows_view().  seen:
         (n, seed_capacity) int32 likewise, or None.  Device tensors: the caller has synchronised their producer, or
         passes the producer's stream.  Asynchronous; good_features_topup_fetch delivers the results."""
-        import torch
-
-        uploaded = any(isinstance(a, np.ndarray) for a in (frames, seeds, seen))
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).cuda()
-        if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda or frames.stride(2) != 1:
-            raise ValueError("frames must be (n, h, w) uint8 on the device with unit pixel stride")
-        n, h, w = frames.shape
-        if isinstance(seeds, np.ndarray):
-            seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.float32)).cuda()
-        if isinstance(seen, np.ndarray):
-            seen = torch.from_numpy(np.ascontiguousarray(seen, np.int32)).cuda()
+        frames, n, h, w, rs, fs, up_frames = _frames_arg(frames)
         keep = [frames]
-        if torch.is_tensor(seeds):
-            if seeds.dtype != torch.float32 or not seeds.is_cuda or not seeds.is_contiguous() or seeds.dim() != 3 or \
-                    seeds.shape[0] != n or seeds.shape[2] != 2:
-                raise ValueError("seeds must be (n, seed_capacity, 2) float32, contiguous, on the device")
-            seed_capacity, seed_point_stride, seed_frame_stride = seeds.shape[1], 2, 2 * seeds.shape[1]
-            keep.append(seeds)
-            seeds = seeds.data_ptr()
+        seeds, t, up_seeds = _device_arg(seeds, np.float32,
+                                         lambda t: t.dim() == 3 and t.shape[0] == n and t.shape[2] == 2,
+                                         "seeds must be (n, seed_capacity, 2) float32, contiguous, on the device", keep)
+        if t is not None:
+            seed_capacity, seed_point_stride, seed_frame_stride = t.shape[1], 2, 2 * t.shape[1]
         elif seed_capacity is None or seed_frame_stride is None:
             raise ValueError("a raw seed address needs seed_capacity and seed_frame_stride")
-        if torch.is_tensor(seen):
-            if seen.dtype != torch.int32 or not seen.is_cuda or not seen.is_contiguous() or \
-                    seen.numel() != n * seed_capacity:
-                raise ValueError("seen must be (n, seed_capacity) int32, contiguous, on the device")
-            keep.append(seen)
-            seen = seen.data_ptr()
-        if uploaded:
-            torch.cuda.synchronize()  # the uploads above ran on torch's stream
+        seen, _, up_seen = _device_arg(seen, np.int32, lambda t: t.numel() == n * seed_capacity,
+                                       "seen must be (n, seed_capacity) int32, contiguous, on the device", keep)
+        _sync_uploads(up_frames, up_seeds, up_seen)
         self._gft_keep = keep  # kept alive until the next call
-        rs = frames.stride(1)
-        fs = max(frames.stride(0), rs * (h - 1) + w) if n == 1 else frames.stride(0)
-        f = self._lib.orbx_good_features_topup_device
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
-                      C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
-        self._chk(f(self._h, C.c_void_p(frames.data_ptr()), n, w, h, rs, fs, C.c_void_p(seeds), seed_point_stride,
-                    seed_frame_stride, C.c_void_p(seen) if seen else None, seen_min, seed_capacity, max_corners,
-                    quality_level, min_distance, C.c_void_p(stream) if stream else None))
+        self._chk(self._lib.orbx_good_features_topup_device(
+            self._h, frames.data_ptr(), n, w, h, rs, fs, seeds, seed_point_stride, seed_frame_stride, seen, seen_min,
+            seed_capacity, max_corners, quality_level, min_distance, _stream(stream)))
 
     def good_features_topup_view(self):
         """The device-side result block of the last top-up (orbx_good_features_topup_results_device)."""
@@ -914,15 +994,13 @@ def _gftt_topup_methods():
         """Frames [first, first + n) of the last top-up as whole arrays: counts (n,), carried (n,), points
         (n, slot_capacity, 2) float32 and origin (n, slot_capacity) int32 -- zero / -1 at and beyond counts[f]."""
         v = self.good_features_topup_view()
-        if n is None:
-            n = v.n - first
+        n = _count(n, first, v.n)
         m = max(n, 1)
         counts, carried = np.zeros(m, np.int32), np.zeros(m, np.int32)
         points = np.zeros((m, v.slot_capacity, 2), np.float32)
         origin = np.zeros((m, v.slot_capacity), np.int32)
-        f = self._lib.orbx_good_features_topup_fetch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self._chk(f(self._h, first, n, _ptr(counts), _ptr(carried), _ptr(points), _ptr(origin)))
+        self._chk(self._lib.orbx_good_features_topup_fetch(self._h, first, n, _ptr(counts), _ptr(carried),
+                                                           _ptr(points), _ptr(origin)))
         return counts, carried, points, origin
 
     def good_features_topup_one(self, image, seeds, max_corners=2000, quality_level=0.01, min_distance=8.0,
@@ -937,12 +1015,9 @@ def _gftt_topup_methods():
         points = np.zeros((max(capacity, 1), 2), np.float32)
         origin = np.zeros(max(capacity, 1), np.int32)
         cnt, car = C.c_int(0), C.c_int(0)
-        f = self._lib.orbx_good_features_topup
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
-                      C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        self._chk(f(self._h, _ptr(image), w, h, image.strides[0], _ptr(seeds) if len(seeds) else None, len(seeds),
-                    max_corners, quality_level, min_distance, _ptr(points), _ptr(origin), capacity, C.byref(cnt),
-                    C.byref(car)))
+        self._chk(self._lib.orbx_good_features_topup(
+            self._h, _ptr(image), w, h, image.strides[0], _ptr(seeds) if len(seeds) else None, len(seeds), max_corners,
+            quality_level, min_distance, _ptr(points), _ptr(origin), capacity, C.byref(cnt), C.byref(car)))
         return points[:cnt.value].copy(), origin[:cnt.value].copy(), car.value
 
     def good_features_to_track_masked(self, image, mask, max_corners=2000, quality_level=0.01, min_distance=8.0,
@@ -958,35 +1033,13 @@ def _gftt_topup_methods():
             capacity = max_corners if max_corners > 0 else max((w - 2) * (h - 2), 1)
         out = np.zeros((max(capacity, 1), 2), np.float32)
         cnt = C.c_int(0)
-        f = self._lib.orbx_good_features_to_track_masked
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
-                      C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        self._chk(f(self._h, _ptr(image), w, h, image.strides[0], _ptr(mask), mask.strides[0], max_corners,
-                    quality_level, min_distance, _ptr(out), capacity, C.byref(cnt)))
+        self._chk(self._lib.orbx_good_features_to_track_masked(
+            self._h, _ptr(image), w, h, image.strides[0], _ptr(mask), mask.strides[0], max_corners, quality_level,
+            min_distance, _ptr(out), capacity, C.byref(cnt)))
         return out[:cnt.value].copy()
 
-    for f in (good_features_topup, good_features_topup_view, good_features_topup_fetch, good_features_topup_one,
-              good_features_to_track_masked):
-        setattr(Context, f.__name__, f)
 
-
-_gftt_topup_methods()
-
-
-class LkWindowsView(C.Structure):
-    _fields_ = [("tracks_xy", C.c_void_p), ("seen", C.c_void_p), ("err", C.c_void_p), ("slot_capacity", C.c_int32),
-                ("window_len", C.c_int32), ("n_windows", C.c_int32)]
-
-
-class LkWindowsFbView(C.Structure):
-    _fields_ = [("fb_d2", C.c_void_p), ("lost", C.c_void_p), ("slot_capacity", C.c_int32), ("window_len", C.c_int32),
-                ("n_windows", C.c_int32)]
-
-
-LK_FB_ALIVE, LK_FB_FORWARD, LK_FB_BACKWARD, LK_FB_DISTANCE = range(4)  # `lost` of the forward-backward check
-
-
-def _lk_window_methods():
+class _LkWindows:
     """Lucas-Kanade over frame windows: trackPointsAcrossWindow for many windows per launch (include/orbx.h;
     DESIGN.md §9 rank 9), with the forward-backward check when fb_threshold is given (rank 13)."""
 
@@ -999,56 +1052,21 @@ def _lk_window_methods():
         address (then slot_capacity is required) -- e.g. the fields of good_features_view().  Device tensors: the
         caller has synchronised their producer, or passes the producer's stream.  Asynchronous; lk_windows_fetch
         delivers the results."""
-        import torch
-
-        uploaded = any(isinstance(a, np.ndarray) for a in (frames, points, counts))
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).cuda()
-        if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda or frames.stride(2) != 1:
-            raise ValueError("frames must be (n, h, w) uint8 on the device with unit pixel stride")
+        frames, n, h, w, rs, fs, up_frames = _frames_arg(frames)
         window_first = np.ascontiguousarray(window_first, np.int32).reshape(-1)
         nw = len(window_first)
-        if isinstance(points, np.ndarray):
-            points = torch.from_numpy(np.ascontiguousarray(points, np.float32)).cuda()
-        if isinstance(counts, np.ndarray):
-            counts = torch.from_numpy(np.ascontiguousarray(counts, np.int32)).cuda()
         keep = [frames]
-        if torch.is_tensor(points):
-            if points.dtype != torch.float32 or not points.is_cuda or not points.is_contiguous() or \
-                    points.dim() != 3 or points.shape[0] != nw or points.shape[2] != 2:
-                raise ValueError("points must be (n_windows, slot_capacity, 2) float32, contiguous, on the device")
-            if slot_capacity is None:
-                slot_capacity = points.shape[1]
-            elif slot_capacity != points.shape[1]:
-                raise ValueError("slot_capacity differs from points.shape[1]")
-            keep.append(points)
-            points = points.data_ptr()
-        elif slot_capacity is None:
-            raise ValueError("a raw points address needs slot_capacity")
-        if torch.is_tensor(counts):
-            if counts.dtype != torch.int32 or not counts.is_cuda or not counts.is_contiguous() or counts.numel() != nw:
-                raise ValueError("counts must be (n_windows,) int32, contiguous, on the device")
-            keep.append(counts)
-            counts = counts.data_ptr()
-        if uploaded:
-            torch.cuda.synchronize()  # the uploads above ran on torch's stream
+        points, slot_capacity, up_points = _lk_points_arg(points, nw, slot_capacity, keep)
+        counts, _, up_counts = _device_arg(counts, np.int32, lambda t: t.numel() == nw,
+                                           "counts must be (n_windows,) int32, contiguous, on the device", keep)
+        _sync_uploads(up_frames, up_points, up_counts)
         self._lkw_keep = keep  # kept alive until the next call
-        n, h, w = frames.shape
-        rs = frames.stride(1)
-        fs = max(frames.stride(0), rs * (h - 1) + w) if n == 1 else frames.stride(0)
-        args = [self._h, C.c_void_p(frames.data_ptr()), n, w, h, rs, fs, _ptr(window_first), nw, window_len,
-                C.c_void_p(points), C.c_void_p(counts) if counts else None, slot_capacity, win, max_level, max_iters,
-                epsilon]
-        types = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
-                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
+        args = [self._h, frames.data_ptr(), n, w, h, rs, fs, _ptr(window_first), nw, window_len, points, counts,
+                slot_capacity, win, max_level, max_iters, epsilon]
         if fb_threshold is None:
-            f = self._lib.orbx_lk_track_windows_device
+            self._chk(self._lib.orbx_lk_track_windows_device(*args, _stream(stream)))
         else:
-            f = self._lib.orbx_lk_track_windows_fb_device
-            args.append(fb_threshold)
-            types.append(C.c_float)
-        f.argtypes = types + [C.c_void_p]
-        self._chk(f(*args, C.c_void_p(stream) if stream else None))
+            self._chk(self._lib.orbx_lk_track_windows_fb_device(*args, fb_threshold, _stream(stream)))
 
     def lk_windows_view(self):
         """The device-side result block of the last windows call (orbx_lk_windows_results_device)."""
@@ -1060,24 +1078,19 @@ def _lk_window_methods():
         """Windows [first, first + n) of the last windows call: tracks (n, slots, window_len, 2) float32, seen
         (n, slots) int32, err (n, slots, window_len - 1) float32, zero past `seen` and in unused slots."""
         v = self.lk_windows_view()
-        if n is None:
-            n = v.n_windows - first
+        n = _count(n, first, v.n_windows)
         m = max(n, 1)
         tracks = np.zeros((m, v.slot_capacity, v.window_len, 2), np.float32)
         seen = np.zeros((m, v.slot_capacity), np.int32)
         err = np.zeros((m, v.slot_capacity, v.window_len - 1), np.float32)
-        f = self._lib.orbx_lk_windows_fetch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        self._chk(f(self._h, first, n, _ptr(tracks), _ptr(seen), _ptr(err)))
+        self._chk(self._lib.orbx_lk_windows_fetch(self._h, first, n, _ptr(tracks), _ptr(seen), _ptr(err)))
         return tracks, seen, err
 
     def lk_windows_fb_view(self):
         """What the forward-backward check added to the last windows call, on the device
         (orbx_lk_windows_fb_results_device); raises after a call without the check."""
         v = LkWindowsFbView()
-        f = self._lib.orbx_lk_windows_fb_results_device
-        f.argtypes = [C.c_void_p, C.c_void_p]
-        self._chk(f(self._h, C.byref(v)))
+        self._chk(self._lib.orbx_lk_windows_fb_results_device(self._h, C.byref(v)))
         return v
 
     def lk_windows_fb_fetch(self, first=0, n=None):
@@ -1085,21 +1098,16 @@ def _lk_window_methods():
         float32, the squared forward-backward distance of every pair that passed, and lost (n, slots) int32, 0 or the
         reason the track ended (LK_FB_FORWARD / LK_FB_BACKWARD / LK_FB_DISTANCE)."""
         v = self.lk_windows_fb_view()
-        if n is None:
-            n = v.n_windows - first
+        n = _count(n, first, v.n_windows)
         m = max(n, 1)
         fb_d2 = np.zeros((m, v.slot_capacity, v.window_len - 1), np.float32)
         lost = np.zeros((m, v.slot_capacity), np.int32)
-        f = self._lib.orbx_lk_windows_fb_fetch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        self._chk(f(self._h, first, n, _ptr(fb_d2), _ptr(lost)))
+        self._chk(self._lib.orbx_lk_windows_fb_fetch(self._h, first, n, _ptr(fb_d2), _ptr(lost)))
         return fb_d2, lost
 
     def lk_workspace_limit(self, nbytes):
         """Bound of the windows workspace in bytes (0: the default); more frames run in slices of whole windows."""
-        f = self._lib.orbx_lk_workspace_limit
-        f.argtypes = [C.c_void_p, C.c_size_t]
-        self._chk(f(self._h, nbytes))
+        self._chk(self._lib.orbx_lk_workspace_limit(self._h, nbytes))
 
     def lk_track_window(self, frames, pts, win=21, max_level=3, max_iters=30, epsilon=0.01, fb_threshold=None):
         """orbx_lk_track_window: one window of host frames (n_frames, h, w) and host points (n, 2).  Returns tracks
@@ -1116,46 +1124,18 @@ def _lk_window_methods():
         err = np.zeros((max(n, 1), max(nf - 1, 1)), np.float32)
         args = [self._h, _ptr(frames), nf, w, h, w, w * h, _ptr(pts), n, _ptr(tracks), _ptr(seen), _ptr(err), win,
                 max_level, max_iters, epsilon]
-        types = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
-                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]
         if fb_threshold is None:
-            f = self._lib.orbx_lk_track_window
-            f.argtypes = types
-            self._chk(f(*args))
+            self._chk(self._lib.orbx_lk_track_window(*args))
             return tracks[:n].copy(), seen[:n].copy(), err[:n, :nf - 1].copy()
         fb_d2 = np.zeros_like(err)
         lost = np.zeros(max(n, 1), np.int32)
-        f = self._lib.orbx_lk_track_window_fb
-        f.argtypes = types + [C.c_float, C.c_void_p, C.c_void_p]
-        self._chk(f(*args, fb_threshold, _ptr(fb_d2), _ptr(lost)))
+        self._chk(self._lib.orbx_lk_track_window_fb(*args, fb_threshold, _ptr(fb_d2), _ptr(lost)))
         return tracks[:n].copy(), seen[:n].copy(), err[:n, :nf - 1].copy(), fb_d2[:n, :nf - 1].copy(), lost[:n].copy()
 
-    for f in (lk_track_windows, lk_windows_view, lk_windows_fetch, lk_windows_fb_view, lk_windows_fb_fetch,
-              lk_workspace_limit, lk_track_window):
-        setattr(Context, f.__name__, f)
 
-
-_lk_window_methods()
-
-
-LM_OK, LM_BASELINE, LM_EMPTY, LM_BAD_POSE = range(4)
-
-
-class LandmarksView(C.Structure):
-    _fields_ = [("status", C.c_void_p), ("pose_offset", C.c_void_p), ("point_offset", C.c_void_p),
-                ("obs_offset", C.c_void_p), ("points3", C.c_void_p), ("rows", C.c_void_p), ("obs_pose", C.c_void_p),
-                ("obs_xy", C.c_void_p), ("slot_of_point", C.c_void_p), ("slot_capacity", C.c_int32),
-                ("window_len", C.c_int32), ("n_windows", C.c_int32)]
-
-
-def _landmark_methods():
+class _Landmarks:
     """Landmarks of tracked windows built on the device and bundle-adjusted there:
     buildLandmarksFromFirstTwoFramesAndTracks + the window's solve (include/orbx.h)."""
-    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-
-    def _d(a, shape):
-        a = np.array(np.asarray(a, np.float64).reshape(shape), order="C")
-        return a, a.ctypes.data_as(DP)
 
     def landmarks_build(self, K, tracks, seen, poses, n_windows=None, slot_capacity=None, window_len=None,
                         stream=None):
@@ -1163,43 +1143,13 @@ def _landmark_methods():
         slots) int32, each a torch device tensor, a numpy array (copied to the device first) or a raw device address
         (then n_windows, slot_capacity and window_len are required) -- e.g. the fields of lk_windows_view().  poses:
         host, (n_windows, window_len, 6).  Asynchronous; landmarks_fetch delivers the block."""
-        import torch
-
-        uploaded = any(isinstance(a, np.ndarray) for a in (tracks, seen))
-        if isinstance(tracks, np.ndarray):
-            tracks = torch.from_numpy(np.ascontiguousarray(tracks, np.float32)).cuda()
-        if isinstance(seen, np.ndarray):
-            seen = torch.from_numpy(np.ascontiguousarray(seen, np.int32)).cuda()
-        keep = []
-        if torch.is_tensor(tracks):
-            if tracks.dtype != torch.float32 or not tracks.is_cuda or not tracks.is_contiguous() or \
-                    tracks.dim() != 4 or tracks.shape[3] != 2:
-                raise ValueError("tracks must be (n_windows, slots, window_len, 2) float32, contiguous, on the device")
-            shape = tuple(tracks.shape[:3])
-            if (n_windows, slot_capacity, window_len) not in ((None, None, None), shape):
-                raise ValueError("n_windows / slot_capacity / window_len differ from tracks.shape")
-            n_windows, slot_capacity, window_len = shape
-            keep.append(tracks)
-            tracks = tracks.data_ptr()
-        elif None in (n_windows, slot_capacity, window_len):
-            raise ValueError("a raw tracks address needs n_windows, slot_capacity and window_len")
-        if torch.is_tensor(seen):
-            if seen.dtype != torch.int32 or not seen.is_cuda or not seen.is_contiguous() or \
-                    seen.numel() != n_windows * slot_capacity:
-                raise ValueError("seen must be (n_windows, slots) int32, contiguous, on the device")
-            keep.append(seen)
-            seen = seen.data_ptr()
-        if uploaded:
-            torch.cuda.synchronize()  # the uploads above ran on torch's stream
-        self._lm_keep = keep  # kept alive until the next build
-        (K, kp) = _d(K, (3, 3))
-        (poses, pp) = _d(poses, (-1, 6))
+        tracks, seen, n_windows, slot_capacity, window_len, self._lm_keep = _tracks_args(
+            tracks, seen, n_windows, slot_capacity, window_len)  # (the tensors: kept alive until the next build)
+        K, poses = _f64(K, (3, 3)), _f64(poses, (-1, 6))
         if len(poses) != max(n_windows, 0) * max(window_len, 0):
             raise ValueError("poses must be (n_windows, window_len, 6)")
-        f = self._lib.orbx_landmarks_build_device
-        f.argtypes = [C.c_void_p, DP, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, DP, C.c_void_p]
-        self._chk(f(self._h, kp, C.c_void_p(tracks), C.c_void_p(seen), n_windows, slot_capacity, window_len, pp,
-                    C.c_void_p(stream) if stream else None))
+        self._chk(self._lib.orbx_landmarks_build_device(self._h, _dp(K), tracks, seen, n_windows, slot_capacity,
+                                                        window_len, _dp(poses), _stream(stream)))
 
     def landmarks_view(self):
         """The device-side landmarks block of the last build (orbx_landmarks_results_device)."""
@@ -1211,11 +1161,8 @@ def _landmark_methods():
         """Windows [first, first + n) of the last build in the format of bundle_adjust_batch: a dict of status (n),
         pose_offset / point_offset / obs_offset (n + 1), points3 (N, 3), slot_of_point (N), obs_point / obs_pose (M)
         and obs_xy (M, 2)."""
-        if n is None:
-            n = self.landmarks_view().n_windows - first
+        n = _count(n, first, lambda: self.landmarks_view().n_windows)
         f = self._lib.orbx_landmarks_fetch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 3 + [
-            C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         npt, nob = C.c_int(0), C.c_int(0)
         self._chk(f(self._h, first, n, None, None, None, None, None, None, 0, None, None, None, 0, C.byref(npt),
                     C.byref(nob)))
@@ -1233,77 +1180,55 @@ def _landmark_methods():
     def bundle_adjust_landmarks(self, huber_delta=1.0, max_iters=200, stream=None):
         """orbx_bundle_adjust_landmarks_device: solves every window of the last landmarks block.  Asynchronous;
         bundle_adjust_landmarks_fetch delivers the results."""
-        f = self._lib.orbx_bundle_adjust_landmarks_device
-        f.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p]
-        self._chk(f(self._h, huber_delta, max_iters, C.c_void_p(stream) if stream else None))
+        self._chk(self._lib.orbx_bundle_adjust_landmarks_device(self._h, huber_delta, max_iters, _stream(stream)))
 
     def bundle_adjust_landmarks_fetch(self, first=0, n=None, points=True):
         """Windows [first, first + n) of the last solve: poses (n, window_len, 6), a list of summary dicts, and the
         points (N, 3) in the order of the block (None with points=False)."""
         v = self.landmarks_view()
-        if n is None:
-            n = v.n_windows - first
+        n = _count(n, first, v.n_windows)
         m = max(n, 1)
         poses = np.zeros((m, v.window_len, 6))
         out = (BaSummary * m)()
         f = self._lib.orbx_bundle_adjust_landmarks_fetch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         cnt = C.c_int(0)
         pts = None
         if points:
             self._chk(f(self._h, first, n, None, None, None, 0, C.byref(cnt)))
             pts = np.zeros((cnt.value, 3))
-        self._chk(f(self._h, first, n, _ptr(poses), C.cast(out, C.c_void_p), _ptr(pts) if points and pts.size else None,
-                    cnt.value, C.byref(cnt)))
+        self._chk(f(self._h, first, n, _ptr(poses), out, _ptr(pts) if points and pts.size else None, cnt.value,
+                    C.byref(cnt)))
         return poses[:n], [out[w].as_dict() for w in range(n)], pts
 
     def bundle_adjust_tracks(self, K, tracks, seen, poses, huber_delta=1.0, max_iters=200):
         """orbx_bundle_adjust_tracks: one window of host tracks (slots, window_len, 2), seen (slots) and poses
         (window_len, 6) through both stages.  Returns (poses, summary dict, landmarks status, points (N, 3),
         slot_of_point (N))."""
-        tracks = np.ascontiguousarray(tracks, np.float32)
-        if tracks.ndim != 3 or tracks.shape[2] != 2:
-            raise ValueError("tracks must be (slots, window_len, 2) float32")
-        slots, wl = tracks.shape[:2]
-        seen = np.ascontiguousarray(seen, np.int32).reshape(-1)
-        if len(seen) != slots:
-            raise ValueError("seen must have one entry per slot")
-        (K, kp) = _d(K, (3, 3))
-        (poses, pp) = _d(poses, (-1, 6))
+        tracks, seen, slots, wl = _host_window(tracks, seen)
+        K, poses = _f64(K, (3, 3)), _f64(poses, (-1, 6), copy=True)
         if len(poses) != wl:
             raise ValueError("poses must be (window_len, 6)")
         pts = np.zeros((max(slots, 1), 3))
         sop = np.zeros(max(slots, 1), np.int32)
         st, cnt, out = C.c_int32(-1), C.c_int(0), BaSummary()
-        f = self._lib.orbx_bundle_adjust_tracks
-        f.argtypes = [C.c_void_p, DP, C.c_void_p, C.c_void_p, C.c_int, C.c_int, DP, C.c_double, C.c_int,
-                      C.POINTER(C.c_int32), C.POINTER(BaSummary), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        self._chk(f(self._h, kp, _ptr(tracks), _ptr(seen), slots, wl, pp, huber_delta, max_iters, C.byref(st),
-                    C.byref(out), _ptr(pts), _ptr(sop), slots, C.byref(cnt)))
+        self._chk(self._lib.orbx_bundle_adjust_tracks(self._h, _dp(K), _ptr(tracks), _ptr(seen), slots, wl,
+                                                      _dp(poses), huber_delta, max_iters, C.byref(st), C.byref(out),
+                                                      _ptr(pts), _ptr(sop), slots, C.byref(cnt)))
         return poses, out.as_dict(), st.value, pts[:cnt.value].copy(), sop[:cnt.value].copy()
 
-    for f in (landmarks_build, landmarks_view, landmarks_fetch, bundle_adjust_landmarks,
-              bundle_adjust_landmarks_fetch, bundle_adjust_tracks):
-        setattr(Context, f.__name__, f)
+
+_TRACKS_POSE_ORDER = ("E", "R", "t", "inliers", "good", "iters", "n", "scale", "triplets", "ratios_used")
 
 
-_landmark_methods()
+def _tracks_pose_arrays(m):
+    return dict(E=np.zeros((m, 3, 3)), R=np.zeros((m, 3, 3)), t=np.zeros((m, 3)), inliers=np.zeros(m, np.int32),
+                good=np.zeros(m, np.int32), iters=np.zeros(m, np.int32), n=np.zeros(m, np.int32),
+                scale=np.zeros(m), triplets=np.zeros(m, np.int32), ratios_used=np.zeros(m, np.int32))
 
 
-class TracksPoseView(C.Structure):
-    _fields_ = [("pose", C.c_void_p), ("n", C.c_void_p), ("scale", C.c_void_p), ("slot_of", C.c_void_p),
-                ("mask", C.c_void_p), ("xyz", C.c_void_p), ("valid", C.c_void_p), ("slot_capacity", C.c_int32),
-                ("window_len", C.c_int32), ("n_windows", C.c_int32), ("n_pairs", C.c_int32)]
-
-
-def _tracks_pose_methods():
+class _TracksPose:
     """Pose, triangulated points and relative scale of every consecutive frame pair of tracked windows, from the
     tracks block on the device (include/orbx.h)."""
-    DP = C.POINTER(C.c_double)
-
-    def _K(K):
-        K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))
-        return K, K.ctypes.data_as(DP)
 
     def tracks_pose(self, K, tracks, seen=None, n_windows=None, slot_capacity=None, window_len=None, prob=0.999,
                     threshold=1.0, max_iters=1000, seed=0, stream=None):
@@ -1311,45 +1236,11 @@ def _tracks_pose_methods():
         it), or (n_windows, slots, window_len, 2) float32 with seen (n_windows, slots) int32, each a torch device
         tensor, a numpy array (copied to the device first) or a raw device address (then n_windows, slot_capacity and
         window_len are required).  Asynchronous; tracks_pose_fetch / tracks_pose_pair_fetch deliver the block."""
-        import torch
-
-        if isinstance(tracks, LkWindowsView):
-            v = tracks
-            tracks, seen = v.tracks_xy, v.seen
-            n_windows, slot_capacity, window_len = v.n_windows, v.slot_capacity, v.window_len
-        uploaded = any(isinstance(a, np.ndarray) for a in (tracks, seen))
-        if isinstance(tracks, np.ndarray):
-            tracks = torch.from_numpy(np.ascontiguousarray(tracks, np.float32)).cuda()
-        if isinstance(seen, np.ndarray):
-            seen = torch.from_numpy(np.ascontiguousarray(seen, np.int32)).cuda()
-        keep = []
-        if torch.is_tensor(tracks):
-            if tracks.dtype != torch.float32 or not tracks.is_cuda or not tracks.is_contiguous() or \
-                    tracks.dim() != 4 or tracks.shape[3] != 2:
-                raise ValueError("tracks must be (n_windows, slots, window_len, 2) float32, contiguous, on the device")
-            shape = tuple(tracks.shape[:3])
-            if (n_windows, slot_capacity, window_len) not in ((None, None, None), shape):
-                raise ValueError("n_windows / slot_capacity / window_len differ from tracks.shape")
-            n_windows, slot_capacity, window_len = shape
-            keep.append(tracks)
-            tracks = tracks.data_ptr()
-        elif None in (n_windows, slot_capacity, window_len):
-            raise ValueError("a raw tracks address needs n_windows, slot_capacity and window_len")
-        if torch.is_tensor(seen):
-            if seen.dtype != torch.int32 or not seen.is_cuda or not seen.is_contiguous() or \
-                    seen.numel() != n_windows * slot_capacity:
-                raise ValueError("seen must be (n_windows, slots) int32, contiguous, on the device")
-            keep.append(seen)
-            seen = seen.data_ptr()
-        if uploaded:
-            torch.cuda.synchronize()  # the uploads above ran on torch's stream
-        self._tp_keep = keep  # kept alive until the next call
-        K, kp = _K(K)
-        f = self._lib.orbx_tracks_pose_device
-        f.argtypes = [C.c_void_p, DP, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
-                      C.c_int, C.c_uint64, C.c_void_p]
-        self._chk(f(self._h, kp, C.c_void_p(tracks), C.c_void_p(seen), n_windows, slot_capacity, window_len, prob,
-                    threshold, max_iters, seed, C.c_void_p(stream) if stream else None))
+        tracks, seen, n_windows, slot_capacity, window_len, self._tp_keep = _tracks_args(
+            tracks, seen, n_windows, slot_capacity, window_len)  # (the tensors: kept alive until the next call)
+        K = _f64(K, (3, 3))
+        self._chk(self._lib.orbx_tracks_pose_device(self._h, _dp(K), tracks, seen, n_windows, slot_capacity,
+                                                    window_len, prob, threshold, max_iters, seed, _stream(stream)))
 
     def tracks_pose_view(self):
         """The device-side block of the last tracks_pose (orbx_tracks_pose_results_device)."""
@@ -1357,29 +1248,18 @@ def _tracks_pose_methods():
         self._chk(self._lib.orbx_tracks_pose_results_device(self._h, C.byref(v)))
         return v
 
-    def _fetch_arrays(m):
-        return dict(E=np.zeros((m, 3, 3)), R=np.zeros((m, 3, 3)), t=np.zeros((m, 3)), inliers=np.zeros(m, np.int32),
-                    good=np.zeros(m, np.int32), iters=np.zeros(m, np.int32), n=np.zeros(m, np.int32),
-                    scale=np.zeros(m), triplets=np.zeros(m, np.int32), ratios_used=np.zeros(m, np.int32))
-
-    _ORDER = ("E", "R", "t", "inliers", "good", "iters", "n", "scale", "triplets", "ratios_used")
-
     def tracks_pose_fetch(self, first=0, n=None):
         """Pairs [first, first + n) of the last tracks_pose (pair p = w * (window_len - 1) + k): dict of E, R
         (n, 3, 3), t (n, 3), inliers, good, iters, n (the list lengths), scale, triplets, ratios_used."""
-        if n is None:
-            n = self.tracks_pose_view().n_pairs - first
-        out = _fetch_arrays(max(n, 0))
-        f = self._lib.orbx_tracks_pose_fetch
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10
-        self._chk(f(self._h, first, n, *[_ptr(out[k]) for k in _ORDER]))
+        n = _count(n, first, lambda: self.tracks_pose_view().n_pairs)
+        out = _tracks_pose_arrays(max(n, 0))
+        self._chk(self._lib.orbx_tracks_pose_fetch(self._h, first, n, *[_ptr(out[k]) for k in _TRACKS_POSE_ORDER]))
         return out
 
     def tracks_pose_pair_fetch(self, pair, capacity=None):
         """The lists of one pair, one entry per surviving slot in ascending slot order: dict of slot_of (n,) int32,
         mask (n,) uint8, xyz (n, 3) float32, valid (n,) uint8.  capacity=None: sized from the pair's count."""
         f = self._lib.orbx_tracks_pose_pair_fetch
-        f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.POINTER(C.c_int)]
         cnt = C.c_int(0)
         if capacity is None:
             st = f(self._h, pair, None, None, None, None, 0, C.byref(cnt))
@@ -1396,45 +1276,28 @@ def _tracks_pose_methods():
     def tracks_pose_window(self, K, tracks, seen, prob=0.999, threshold=1.0, max_iters=1000, seed=0):
         """orbx_tracks_pose: one window of host tracks (slots, window_len, 2) and seen (slots).  Returns the dict of
         tracks_pose_fetch for the window's window_len - 1 pairs; tracks_pose_pair_fetch delivers their lists."""
-        tracks = np.ascontiguousarray(tracks, np.float32)
-        if tracks.ndim != 3 or tracks.shape[2] != 2:
-            raise ValueError("tracks must be (slots, window_len, 2) float32")
-        slots, wl = tracks.shape[:2]
-        seen = np.ascontiguousarray(seen, np.int32).reshape(-1)
-        if len(seen) != slots:
-            raise ValueError("seen must have one entry per slot")
-        K, kp = _K(K)
-        out = _fetch_arrays(max(wl - 1, 0))
-        f = self._lib.orbx_tracks_pose
-        f.argtypes = [C.c_void_p, DP, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
-                      C.c_uint64] + [C.c_void_p] * 10
-        self._chk(f(self._h, kp, _ptr(tracks), _ptr(seen), slots, wl, prob, threshold, max_iters, seed,
-                    *[_ptr(out[k]) for k in _ORDER]))
+        tracks, seen, slots, wl = _host_window(tracks, seen)
+        K = _f64(K, (3, 3))
+        out = _tracks_pose_arrays(max(wl - 1, 0))
+        self._chk(self._lib.orbx_tracks_pose(self._h, _dp(K), _ptr(tracks), _ptr(seen), slots, wl, prob, threshold,
+                                             max_iters, seed, *[_ptr(out[k]) for k in _TRACKS_POSE_ORDER]))
         return out
 
-    for f in (tracks_pose, tracks_pose_view, tracks_pose_fetch, tracks_pose_pair_fetch, tracks_pose_window):
-        setattr(Context, f.__name__, f)
 
-
-_tracks_pose_methods()
+class Context(_Core, _Matcher, _Pose, _Scale, _BundleAdjust, _GoodFeatures, _GoodFeaturesTopup, _LkWindows,
+              _Landmarks, _TracksPose):
+    """One orbx_ctx: single-threaded, owns all device memory, one per GPU."""
 
 
 def chain_trajectory(T0, R, t, scale):
     """cur_pose = cur_pose * T.inv(), T = [R | scale * t], over n relative motions (feature_matching.cpp:77-82):
     (n + 1, 4, 4) poses with poses[0] = T0.  Host only."""
-    DP = C.POINTER(C.c_double)
-    T0 = np.ascontiguousarray(np.asarray(T0, np.float64).reshape(4, 4))
-    R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1, 3, 3))
-    t = np.ascontiguousarray(np.asarray(t, np.float64).reshape(-1, 3))
-    scale = np.ascontiguousarray(np.asarray(scale, np.float64).reshape(-1))
+    T0, R, t, scale = _f64(T0, (4, 4)), _f64(R, (-1, 3, 3)), _f64(t, (-1, 3)), _f64(scale, (-1,))
     n = len(R)
     if len(t) != n or len(scale) != n:
         raise ValueError("R, t and scale differ in length")
     poses = np.zeros((n + 1, 4, 4))
-    f = load().orbx_chain_trajectory
-    f.argtypes = [DP, DP, DP, DP, C.c_int, DP]
-    st = f(T0.ctypes.data_as(DP), R.ctypes.data_as(DP), t.ctypes.data_as(DP), scale.ctypes.data_as(DP), n,
-           poses.ctypes.data_as(DP))
+    st = load().orbx_chain_trajectory(_dp(T0), _dp(R), _dp(t), _dp(scale), n, _dp(poses))
     if st != OK:
         raise OrbxError(st, "orbx_chain_trajectory")
     return poses
@@ -1442,7 +1305,7 @@ def chain_trajectory(T0, R, t, scale):
 
 def gaussian_kernel(K, sigma=-1.0):
     out = np.zeros(K * K, np.float32)
-    st = load().orbx_gaussian_kernel(K, C.c_float(sigma), _ptr(out))
+    st = load().orbx_gaussian_kernel(K, sigma, _ptr(out))
     if st != OK:
         raise OrbxError(st, "orbx_gaussian_kernel")
     return out.reshape(K, K)
