@@ -242,6 +242,124 @@ void windows(int n, int cap, int len) {
   }
 }
 
+// ---- matcher, pose, scale, bundle adjustment of staged windows, the pair tracker's points ----
+// Before these parts held one block per call, every array below was a buffer of its own, asked of ensure() with the
+// byte count written here and given that count rounded up to 256 (at least 256).  A block is that chain: every
+// section where the sizes before it, each rounded up, end; at a multiple of 256; and at least as large as the request.
+struct Chain {
+  size_t off = 0;
+  // a section the header puts at `got`, the next one (or the block's end) at `next`, for a buffer of `bytes`
+  void sec(const char* what, size_t got, size_t next, size_t bytes) {
+    check(what, got, off);
+    check("offset % 256", got % 256, 0);
+    check("section holds the request", next >= got && next - got >= bytes, 1);
+    off = A(off + bytes);
+  }
+  void end(const char* what, size_t got) { check(what, got, off); }
+};
+#define SEC(ch, L, name, next, bytes) (ch).sec(#name, (L).name, (next), (bytes))
+
+void match_block(int pairs, int cap) {
+  const MatchBlock b(pairs, cap);
+  const size_t e = (size_t)pairs * cap;
+  Chain c;
+  SEC(c, b, idx, b.dist, sizeof(int32_t) * 2 * e);
+  SEC(c, b, dist, b.match, sizeof(int32_t) * 2 * e);
+  SEC(c, b, match, b.bytes, sizeof(int32_t) * e);
+  c.end("MatchBlock.bytes", b.bytes);
+}
+void pose_block(int pairs, int cap) {
+  const PoseBlock b(pairs, cap);
+  const size_t e = (size_t)pairs * cap;
+  Chain c;
+  SEC(c, b, pts, b.n, 32 * e);  // OrbxPosePt
+  SEC(c, b, n, b.out, sizeof(int32_t) * (size_t)pairs);
+  SEC(c, b, out, b.mask, 184 * (size_t)pairs);  // OrbxPoseOut
+  SEC(c, b, mask, b.bytes, e);
+  c.end("PoseBlock.bytes", b.bytes);
+}
+void scale_block(int pairs, int cap) {
+  const ScaleBlock b(pairs, cap);
+  const size_t e = (size_t)pairs * cap;
+  Chain c;
+  SEC(c, b, xyz, b.valid, sizeof(float) * 3 * e);
+  SEC(c, b, valid, b.mq, e);
+  SEC(c, b, mq, b.mt, sizeof(int32_t) * e);
+  SEC(c, b, mt, b.n, sizeof(int32_t) * e);
+  SEC(c, b, n, b.out, sizeof(int32_t) * (size_t)pairs);
+  SEC(c, b, out, b.bytes, 16 * (size_t)pairs);  // OrbxScaleOut
+  c.end("ScaleBlock.bytes", b.bytes);
+}
+
+// the host-array entries with n points (descriptors): the blocks of one pair, the staged inputs, the pair tracker
+const int kHostN[] = {0, 1, 5, 255, 256, 257, 3000};
+void host_entries(int n) {
+  SHAPE("host entries n=%d", n);
+  if (n > 0) {  // (every entry but orbx_estimate_pose returns before its buffers for n == 0)
+    match_block(1, n);
+    for (int nt : kHostN) {
+      SHAPE("matcher input nq=%d nt=%d", n, nt);
+      const MatchInput b(n, nt);
+      Chain c;
+      SEC(c, b, cnt, b.q, 64);
+      SEC(c, b, q, b.t, 32 * (size_t)n);  // orbx_descriptor
+      SEC(c, b, t, b.bytes, 32 * (size_t)std::max(nt, 1));
+      c.end("MatchInput.bytes", b.bytes);
+    }
+    SHAPE("host entries n=%d", n);
+    {
+      const TriHost b(n);
+      Chain c;
+      SEC(c, b, in, b.xyz, sizeof(float) * 4 * (size_t)n);
+      SEC(c, b, xyz, b.valid, sizeof(float) * 3 * (size_t)n);
+      SEC(c, b, valid, b.bytes, (size_t)n);
+      c.end("TriHost.bytes", b.bytes);
+    }
+    {
+      const ScaleHost b(n);
+      Chain c;
+      SEC(c, b, xyz, b.valid, sizeof(float) * 6 * (size_t)n);
+      SEC(c, b, valid, b.out, 2 * (size_t)n);
+      SEC(c, b, out, b.bytes, 16);  // OrbxScaleOut
+      c.end("ScaleHost.bytes", b.bytes);
+    }
+  }
+  pose_block(1, n > 0 ? n : 1);
+  // the pair tracker's points: tight, as orbx_lk_track had the offsets inline (one mirror, one copy each way)
+  const LkIo io(n);
+  const size_t o_out = sizeof(float) * 2 * (size_t)n, o_err = 2 * o_out, o_st = o_err + sizeof(float) * (size_t)n;
+  EQ(io.next, o_out), EQ(io.err, o_err), EQ(io.status, o_st), EQ(io.bytes, o_st + (size_t)n);
+}
+
+// orbx_bundle_adjust_batch with n windows of W poses, N landmarks and M observations each
+void ba_windows(int n, int W, int N, int M) {
+  const size_t tp = (size_t)n * W, tn = (size_t)n * N, tm = (size_t)n * M;
+  {
+    const BaStage b(n, tp, tn, tm);
+    Chain c;
+    SEC(c, b, off, b.poses, sizeof(int32_t) * 3 * ((size_t)n + 1));
+    SEC(c, b, poses, b.points, sizeof(double) * 6 * tp);
+    SEC(c, b, points, b.rows, sizeof(double) * 3 * tn);
+    SEC(c, b, rows, b.opose, sizeof(int32_t) * (tn + (size_t)n));
+    SEC(c, b, opose, b.oxy, tm);
+    SEC(c, b, oxy, b.out, sizeof(double) * 2 * tm);
+    SEC(c, b, out, b.bytes, 32 * (size_t)n);  // orbx_ba_summary
+    c.end("BaStage.bytes", b.bytes);
+  }
+  // the group count as orbx_bundle_adjust_batch had it, with cap = N and ocap = M
+  const int cap = N, ocap = M;
+  const size_t per_group = sizeof(double) * ((size_t)30 * cap + (size_t)18 * ocap) + 8 * (size_t)cap;
+  int groups = std::min(n, 512);
+  groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)groups, ((size_t)2 << 30) / per_group));
+  const LmWork w(n, (size_t)cap, (size_t)ocap);
+  EQ(w.groups, groups);
+  Chain c;
+  SEC(c, w, wp, w.wo, sizeof(double) * 30 * (size_t)cap * groups);
+  SEC(c, w, wo, w.slot, sizeof(double) * 18 * (size_t)ocap * groups);
+  SEC(c, w, slot, w.bytes, 8 * (size_t)cap * groups);
+  c.end("LmWork.bytes", w.bytes);
+}
+
 }  // namespace
 
 int main() {
@@ -266,6 +384,19 @@ int main() {
            {(size_t)1, one, 2 * one - 1, 3 * one, 7 * one + 5, 64 * one, (size_t)ORBX_GFTT_WORKSPACE_DEFAULT})
         good_features_slices(s[0], s[1], max_batch, limit);
   }
+  for (int pairs = 1; pairs <= 256; pairs++)
+    for (int cap = 1; cap <= 2000; cap++) {
+      SHAPE("chain blocks pairs=%d cap=%d", pairs, cap);
+      match_block(pairs, cap), pose_block(pairs, cap), scale_block(pairs, cap);
+    }
+  for (int n : kHostN) host_entries(n);
+  for (int W = 2; W <= 8; W++)
+    for (int N = 1; N <= 65536; N++)
+      for (int n : {1, 5, 600})
+        for (int M : {N, N * W}) {  // every landmark seen once, or by every pose
+          SHAPE("ba n=%d W=%d N=%d M=%d", n, W, N, M);
+          ba_windows(n, W, N, M);
+        }
   std::printf("%lld values compared, %lld failures\n", g_checks, g_failures);
   return g_failures ? 1 : 0;
 }

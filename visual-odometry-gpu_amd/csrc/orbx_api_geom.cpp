@@ -22,24 +22,23 @@ int orbx_estimate_pose(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, 
       !pose_args_ok(K, prob, threshold, max_iters))
     return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
   const int cap = n > 0 ? n : 1;
-  ENSURE(c, c->pose.ph_in, sizeof(float) * 4 * (size_t)cap);
-  ENSURE(c, c->pose.ph_pts, sizeof(OrbxPosePt) * (size_t)cap);
-  ENSURE(c, c->pose.ph_n, sizeof(int32_t));
-  ENSURE(c, c->pose.ph_out, sizeof(OrbxPoseOut));
-  ENSURE(c, c->pose.ph_mask, (size_t)cap);
+  const PoseBlock L(1, cap);
+  DevBuf& b = c->pose.hblk;
+  ENSURE(c, c->pose.hin, sizeof(float) * 4 * (size_t)cap);
+  ENSURE(c, b, L.bytes);
   hipStream_t s = c->stream;
-  float* d_p1 = (float*)c->pose.ph_in.p;
+  float* d_p1 = (float*)c->pose.hin.p;
   float* d_p2 = d_p1 + 2 * (size_t)cap;
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(d_p1, pts1_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d_p2, pts2_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
   }
-  HIPCHK(c, orbx_launch_pose_prep_host(s, n, d_p1, d_p2, K, (OrbxPosePt*)c->pose.ph_pts.p, (int32_t*)c->pose.ph_n.p));
-  HIPCHK(c, orbx_launch_pose_ransac(s, 1, cap, (const OrbxPosePt*)c->pose.ph_pts.p, (const int32_t*)c->pose.ph_n.p, K, prob,
-                                    threshold, max_iters, seed, (OrbxPoseOut*)c->pose.ph_out.p, (uint8_t*)c->pose.ph_mask.p));
+  HIPCHK(c, orbx_launch_pose_prep_host(s, n, d_p1, d_p2, K, at<OrbxPosePt>(b, L.pts), at<int32_t>(b, L.n)));
+  HIPCHK(c, orbx_launch_pose_ransac(s, 1, cap, at<OrbxPosePt>(b, L.pts), at<int32_t>(b, L.n), K, prob, threshold,
+                                    max_iters, seed, at<OrbxPoseOut>(b, L.out), at<uint8_t>(b, L.mask)));
   OrbxPoseOut r;
-  HIPCHK(c, hipMemcpyAsync(&r, c->pose.ph_out.p, sizeof r, hipMemcpyDeviceToHost, s));
-  if (mask && n > 0) HIPCHK(c, hipMemcpyAsync(mask, c->pose.ph_mask.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(&r, at<OrbxPoseOut>(b, L.out), sizeof r, hipMemcpyDeviceToHost, s));
+  if (mask && n > 0) HIPCHK(c, hipMemcpyAsync(mask, at<uint8_t>(b, L.mask), (size_t)n, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   pose_unpack(r, E, R, t, inliers, good, iters);
   return ORBX_OK;
@@ -52,22 +51,21 @@ int orbx_batch_pose_consecutive(orbx_ctx* c, const double* K, double prob, doubl
   if (!pose_args_ok(K, prob, threshold, max_iters)) return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
   if (c->m.pairs <= 0 || c->m.serial != c->batch_serial)
     return fail(c, ORBX_ERR_INVALID_ARG, "the last batch has not been matched (orbx_batch_match_consecutive)");
-  // the pose buffers are ONE set per context, like the matcher's
+  // the pose block is ONE per context, like the matcher's
   if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
   const Block& B = last_block(c);
   const int npairs = c->m.pairs, cap = B.cap;
-  const size_t e = (size_t)npairs * cap;
-  ENSURE(c, c->pose.pb_pts, sizeof(OrbxPosePt) * e);
-  ENSURE(c, c->pose.pb_n, sizeof(int32_t) * (size_t)npairs);
-  ENSURE(c, c->pose.pb_out, sizeof(OrbxPoseOut) * (size_t)npairs);
-  ENSURE(c, c->pose.pb_mask, e);
+  const PoseBlock L(npairs, cap);
+  DevBuf& b = c->pose.blk;
+  ENSURE(c, b, L.bytes);
   const OutLayout& o = B.layout;
   hipStream_t s = batch_stream(c);
   HIPCHK(c, orbx_launch_pose_prep_batch(s, npairs, cap, (const int32_t*)(B.d + o.counts),
-                                        (const orbx_keypoint*)(B.d + o.kp), (const int32_t*)c->m.match.p, K,
-                                        (OrbxPosePt*)c->pose.pb_pts.p, (int32_t*)c->pose.pb_n.p));
-  HIPCHK(c, orbx_launch_pose_ransac(s, npairs, cap, (const OrbxPosePt*)c->pose.pb_pts.p, (const int32_t*)c->pose.pb_n.p, K, prob,
-                                    threshold, max_iters, seed, (OrbxPoseOut*)c->pose.pb_out.p, (uint8_t*)c->pose.pb_mask.p));
+                                        (const orbx_keypoint*)(B.d + o.kp),
+                                        at<int32_t>(c->m.res, MatchBlock(npairs, cap).match), K,
+                                        at<OrbxPosePt>(b, L.pts), at<int32_t>(b, L.n)));
+  HIPCHK(c, orbx_launch_pose_ransac(s, npairs, cap, at<OrbxPosePt>(b, L.pts), at<int32_t>(b, L.n), K, prob, threshold,
+                                    max_iters, seed, at<OrbxPoseOut>(b, L.out), at<uint8_t>(b, L.mask)));
   c->pose.pairs = npairs;
   c->pose.cap = cap;
   c->pose.stream = s;
@@ -85,7 +83,8 @@ int orbx_batch_pose_fetch(orbx_ctx* c, int first, int n, double* E, double* R, d
     return fail(c, ORBX_ERR_INVALID_ARG, "pairs outside the last posed batch");
   if (n == 0) return ORBX_OK;
   std::vector<OrbxPoseOut> r((size_t)n);
-  HIPCHK(c, hipMemcpyAsync(r.data(), (const OrbxPoseOut*)c->pose.pb_out.p + first, sizeof(OrbxPoseOut) * (size_t)n,
+  const PoseBlock L(c->pose.pairs, c->pose.cap);
+  HIPCHK(c, hipMemcpyAsync(r.data(), at<OrbxPoseOut>(c->pose.blk, L.out) + first, sizeof(OrbxPoseOut) * (size_t)n,
                            hipMemcpyDeviceToHost, c->pose.stream));
   HIPCHK(c, hipStreamSynchronize(c->pose.stream));
   for (int i = 0; i < n; i++)
@@ -99,13 +98,14 @@ int orbx_batch_pose_mask(orbx_ctx* c, int pair, uint8_t* mask, int capacity, int
   if (!c) return ORBX_ERR_INVALID_ARG;
   if (!count || capacity < 0 || (capacity > 0 && !mask)) return fail(c, ORBX_ERR_INVALID_ARG, "bad mask arguments");
   if (pair < 0 || pair >= c->pose.pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last posed batch");
+  const PoseBlock L(c->pose.pairs, c->pose.cap);
   int32_t np = 0;
-  HIPCHK(c, hipMemcpyAsync(&np, (const int32_t*)c->pose.pb_n.p + pair, sizeof np, hipMemcpyDeviceToHost, c->pose.stream));
+  HIPCHK(c, hipMemcpyAsync(&np, at<int32_t>(c->pose.blk, L.n) + pair, sizeof np, hipMemcpyDeviceToHost, c->pose.stream));
   HIPCHK(c, hipStreamSynchronize(c->pose.stream));
   *count = np;
   if (np > capacity) return fail(c, ORBX_ERR_CAPACITY, "capacity smaller than the pair's match count");
   if (np > 0) {
-    HIPCHK(c, hipMemcpyAsync(mask, (const uint8_t*)c->pose.pb_mask.p + (size_t)pair * c->pose.cap, (size_t)np,
+    HIPCHK(c, hipMemcpyAsync(mask, at<uint8_t>(c->pose.blk, L.mask) + (size_t)pair * c->pose.cap, (size_t)np,
                              hipMemcpyDeviceToHost, c->pose.stream));
     HIPCHK(c, hipStreamSynchronize(c->pose.stream));
   }
@@ -126,17 +126,17 @@ int orbx_triangulate(orbx_ctx* c, const float* pts1_xy, const float* pts2_xy, in
       !finite_all(R, 9) || !finite_all(t, 3))
     return fail(c, ORBX_ERR_INVALID_ARG, "bad triangulation arguments");
   if (n == 0) return ORBX_OK;
-  ENSURE(c, c->scale.sh_in, sizeof(float) * 4 * (size_t)n);
-  ENSURE(c, c->scale.sh_xyz, sizeof(float) * 3 * (size_t)n);
-  ENSURE(c, c->scale.sh_valid, (size_t)n);
+  const TriHost L(n);
+  DevBuf& b = c->scale.host;
+  ENSURE(c, b, L.bytes);
   hipStream_t s = c->stream;
-  float* d_p1 = (float*)c->scale.sh_in.p;
+  float* d_p1 = at<float>(b, L.in);
   float* d_p2 = d_p1 + 2 * (size_t)n;
   HIPCHK(c, hipMemcpyAsync(d_p1, pts1_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(d_p2, pts2_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
-  HIPCHK(c, orbx_launch_triangulate_host(s, n, d_p1, d_p2, K, R, t, (float*)c->scale.sh_xyz.p, (uint8_t*)c->scale.sh_valid.p));
-  HIPCHK(c, hipMemcpyAsync(xyz, c->scale.sh_xyz.p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(valid, c->scale.sh_valid.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, orbx_launch_triangulate_host(s, n, d_p1, d_p2, K, R, t, at<float>(b, L.xyz), at<uint8_t>(b, L.valid)));
+  HIPCHK(c, hipMemcpyAsync(xyz, at<float>(b, L.xyz), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(valid, at<uint8_t>(b, L.valid), (size_t)n, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return ORBX_OK;
 }
@@ -156,22 +156,22 @@ int orbx_estimate_scale(orbx_ctx* c, const float* prev_xyz, const uint8_t* prev_
   if ((size_t)m * 8 > ORBX_SCALE_LDS_MAX)
     return fail(c, ORBX_ERR_UNSUPPORTED, "more aligned points than the selection holds in LDS");
   // only the first m points of either list enter
-  ENSURE(c, c->scale.sh_xyz, sizeof(float) * 6 * (size_t)m);
-  ENSURE(c, c->scale.sh_valid, 2 * (size_t)m);
-  ENSURE(c, c->scale.sh_out, sizeof(OrbxScaleOut));
+  const ScaleHost L(m);
+  DevBuf& b = c->scale.host;
+  ENSURE(c, b, L.bytes);
   hipStream_t s = c->stream;
-  float* d_prev = (float*)c->scale.sh_xyz.p;
+  float* d_prev = at<float>(b, L.xyz);
   float* d_cur = d_prev + 3 * (size_t)m;
-  uint8_t* d_pv = (uint8_t*)c->scale.sh_valid.p;
+  uint8_t* d_pv = at<uint8_t>(b, L.valid);
   uint8_t* d_cv = d_pv + m;
   HIPCHK(c, hipMemcpyAsync(d_prev, prev_xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(d_cur, cur_xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
   if (prev_valid) HIPCHK(c, hipMemcpyAsync(d_pv, prev_valid, (size_t)m, hipMemcpyHostToDevice, s));
   if (cur_valid) HIPCHK(c, hipMemcpyAsync(d_cv, cur_valid, (size_t)m, hipMemcpyHostToDevice, s));
   HIPCHK(c, orbx_launch_scale_aligned(s, m, m, d_prev, prev_valid ? d_pv : nullptr, d_cur, cur_valid ? d_cv : nullptr,
-                                      (OrbxScaleOut*)c->scale.sh_out.p));
+                                      at<OrbxScaleOut>(b, L.out)));
   OrbxScaleOut r;
-  HIPCHK(c, hipMemcpyAsync(&r, c->scale.sh_out.p, sizeof r, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(&r, at<OrbxScaleOut>(b, L.out), sizeof r, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   *scale = r.scale;
   *ratios_used = r.ratios_used;
@@ -185,33 +185,29 @@ int orbx_batch_scale_consecutive(orbx_ctx* c, const double* K) {
   if (c->pose.pairs <= 0 || c->pose.serial != c->batch_serial)
     return fail(c, ORBX_ERR_INVALID_ARG, "the last batch has not been posed (orbx_batch_pose_consecutive)");
   // the triangulation reads the match table again: it must still hold the matches the poses were computed from
-  // (a host-array matcher call reuses the scratch and zeroes m.pairs; a second batch match bumps m.gen)
+  // (a host-array matcher call writes the same block and zeroes m.pairs; a second batch match bumps m.gen)
   if (c->m.pairs != c->pose.pairs || c->m.serial != c->batch_serial || c->pose.match_gen != c->m.gen)
     return fail(c, ORBX_ERR_INVALID_ARG, "the match table has been rewritten since the batch was posed");
   const int npairs = c->pose.pairs, cap = c->pose.cap;
   if ((size_t)cap * 16 > ORBX_SCALE_LDS_MAX)
     return fail(c, ORBX_ERR_UNSUPPORTED, "more result slots per frame than the join holds in LDS");
-  // the scale buffers are ONE set per context, like the pose buffers
+  // the scale block is ONE per context, like the pose block
   if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
-  const size_t e = (size_t)npairs * cap;
-  ENSURE(c, c->scale.sb_xyz, sizeof(float) * 3 * e);
-  ENSURE(c, c->scale.sb_valid, e);
-  ENSURE(c, c->scale.sb_mq, sizeof(int32_t) * e);
-  ENSURE(c, c->scale.sb_mt, sizeof(int32_t) * e);
-  ENSURE(c, c->scale.sb_n, sizeof(int32_t) * (size_t)npairs);
-  ENSURE(c, c->scale.sb_out, sizeof(OrbxScaleOut) * (size_t)npairs);
+  const ScaleBlock L(npairs, cap);
+  DevBuf& b = c->scale.blk;
+  ENSURE(c, b, L.bytes);
   const Block& B = last_block(c);
   const OutLayout& o = B.layout;
   hipStream_t s = c->pose.stream;
+  const OrbxPoseOut* d_pose = at<OrbxPoseOut>(c->pose.blk, PoseBlock(npairs, cap).out);
   HIPCHK(c, orbx_launch_triangulate_batch(s, npairs, cap, (const int32_t*)(B.d + o.counts),
-                                          (const orbx_keypoint*)(B.d + o.kp), (const int32_t*)c->m.match.p,
-                                          (const OrbxPoseOut*)c->pose.pb_out.p, K, (float*)c->scale.sb_xyz.p,
-                                          (uint8_t*)c->scale.sb_valid.p, (int32_t*)c->scale.sb_mq.p, (int32_t*)c->scale.sb_mt.p,
-                                          (int32_t*)c->scale.sb_n.p));
-  HIPCHK(c, orbx_launch_scale_join(s, npairs, npairs, cap, (const int32_t*)c->scale.sb_n.p, (const int32_t*)c->scale.sb_mq.p,
-                                   (const int32_t*)c->scale.sb_mt.p, (const float*)c->scale.sb_xyz.p,
-                                   (const uint8_t*)c->scale.sb_valid.p, (const OrbxPoseOut*)c->pose.pb_out.p,
-                                   (OrbxScaleOut*)c->scale.sb_out.p));
+                                          (const orbx_keypoint*)(B.d + o.kp),
+                                          at<int32_t>(c->m.res, MatchBlock(npairs, cap).match), d_pose, K,
+                                          at<float>(b, L.xyz), at<uint8_t>(b, L.valid), at<int32_t>(b, L.mq),
+                                          at<int32_t>(b, L.mt), at<int32_t>(b, L.n)));
+  HIPCHK(c, orbx_launch_scale_join(s, npairs, npairs, cap, at<int32_t>(b, L.n), at<int32_t>(b, L.mq),
+                                   at<int32_t>(b, L.mt), at<float>(b, L.xyz), at<uint8_t>(b, L.valid), d_pose,
+                                   at<OrbxScaleOut>(b, L.out)));
   c->scale.pairs = npairs;
   c->scale.cap = cap;
   c->scale.stream = s;
@@ -226,7 +222,8 @@ int orbx_batch_scale_fetch(orbx_ctx* c, int first, int n, double* scale, int32_t
     return fail(c, ORBX_ERR_INVALID_ARG, "pairs outside the last scaled batch");
   if (n == 0) return ORBX_OK;
   std::vector<OrbxScaleOut> r((size_t)n);
-  HIPCHK(c, hipMemcpyAsync(r.data(), (const OrbxScaleOut*)c->scale.sb_out.p + first, sizeof(OrbxScaleOut) * (size_t)n,
+  const ScaleBlock L(c->scale.pairs, c->scale.cap);
+  HIPCHK(c, hipMemcpyAsync(r.data(), at<OrbxScaleOut>(c->scale.blk, L.out) + first, sizeof(OrbxScaleOut) * (size_t)n,
                            hipMemcpyDeviceToHost, c->scale.stream));
   HIPCHK(c, hipStreamSynchronize(c->scale.stream));
   for (int i = 0; i < n; i++) {
@@ -244,16 +241,17 @@ int orbx_batch_points_fetch(orbx_ctx* c, int pair, float* xyz, uint8_t* valid, i
     return fail(c, ORBX_ERR_INVALID_ARG, "bad point output arguments");
   if (pair < 0 || pair >= c->scale.pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last scaled batch");
   hipStream_t s = c->scale.stream;
+  const ScaleBlock L(c->scale.pairs, c->scale.cap);
   int32_t np = 0;
-  HIPCHK(c, hipMemcpyAsync(&np, (const int32_t*)c->scale.sb_n.p + pair, sizeof np, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(&np, at<int32_t>(c->scale.blk, L.n) + pair, sizeof np, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   *count = np;
   if (np > capacity) return fail(c, ORBX_ERR_CAPACITY, "capacity smaller than the pair's match count");
   if (np > 0) {
     const size_t row = (size_t)pair * c->scale.cap;
-    HIPCHK(c, hipMemcpyAsync(xyz, (const float*)c->scale.sb_xyz.p + 3 * row, sizeof(float) * 3 * (size_t)np,
+    HIPCHK(c, hipMemcpyAsync(xyz, at<float>(c->scale.blk, L.xyz) + 3 * row, sizeof(float) * 3 * (size_t)np,
                              hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(valid, (const uint8_t*)c->scale.sb_valid.p + row, (size_t)np, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(valid, at<uint8_t>(c->scale.blk, L.valid) + row, (size_t)np, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
   }
   return ORBX_OK;
@@ -347,40 +345,31 @@ int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const 
       row[j + 1] += row[j];
     }
   }
-  // workgroups: as many as windows, bounded by ORBX_BA_MAX_GROUPS and by the workspace budget
-  const size_t per_group = sizeof(double) * ((size_t)ORBX_BA_WS_POINT * cap + (size_t)ORBX_BA_WS_OBS * ocap) + 8 * (size_t)cap;
-  int groups = std::min(n_windows, ORBX_BA_MAX_GROUPS);
-  groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)groups, ORBX_BA_WS_BUDGET / per_group));
-  const size_t noff = (size_t)n_windows + 1;
-  ENSURE(c, c->ba.off, sizeof(int32_t) * 3 * noff);
-  ENSURE(c, c->ba.poses, sizeof(double) * 6 * tp);
-  ENSURE(c, c->ba.points, sizeof(double) * 3 * tn);
-  ENSURE(c, c->ba.rows, sizeof(int32_t) * rows.size());
-  ENSURE(c, c->ba.opose, tm);
-  ENSURE(c, c->ba.oxy, sizeof(double) * 2 * tm);
-  ENSURE(c, c->ba.wp, sizeof(double) * ORBX_BA_WS_POINT * (size_t)cap * groups);
-  ENSURE(c, c->ba.wo, sizeof(double) * ORBX_BA_WS_OBS * (size_t)ocap * groups);
-  ENSURE(c, c->ba.slot, 8 * (size_t)cap * groups);
-  ENSURE(c, c->ba.out, sizeof(orbx_ba_summary) * (size_t)n_windows);
+  const BaStage L(n_windows, tp, tn, tm);
+  const LmWork W(n_windows, (size_t)cap, (size_t)ocap);
+  DevBuf &b = c->ba.stage, &ws = c->ba.ws;
+  ENSURE(c, b, L.bytes);
+  ENSURE(c, ws, W.bytes);
   hipStream_t s = c->stream;
-  int32_t* d_off = (int32_t*)c->ba.off.p;
+  const size_t noff = (size_t)n_windows + 1;
+  int32_t* d_off = at<int32_t>(b, L.off);
   HIPCHK(c, hipMemcpyAsync(d_off, pose_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(d_off + noff, point_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(d_off + 2 * noff, obs_offset, sizeof(int32_t) * noff, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba.poses.p, poses6, sizeof(double) * 6 * tp, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba.points.p, points3, sizeof(double) * 3 * tn, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba.rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba.opose.p, opose.data(), tm, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->ba.oxy.p, oxy.data(), sizeof(double) * 2 * tm, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(at<double>(b, L.poses), poses6, sizeof(double) * 6 * tp, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(at<double>(b, L.points), points3, sizeof(double) * 3 * tn, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(at<int32_t>(b, L.rows), rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(at<uint8_t>(b, L.opose), opose.data(), tm, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(at<double>(b, L.oxy), oxy.data(), sizeof(double) * 2 * tm, hipMemcpyHostToDevice, s));
   const double K4[4] = {K[0], K[4], K[2], K[5]};
-  HIPCHK(c, orbx_launch_ba(s, n_windows, groups, max_iters, K4, huber_delta, d_off, d_off + noff, d_off + 2 * noff,
-                           (double*)c->ba.poses.p, (double*)c->ba.points.p, (const int32_t*)c->ba.rows.p,
-                           (const uint8_t*)c->ba.opose.p, (const double*)c->ba.oxy.p, cap, ocap, (double*)c->ba.wp.p,
-                           (double*)c->ba.wo.p, (unsigned long long*)c->ba.slot.p, c->ba.out.p));
+  HIPCHK(c, orbx_launch_ba(s, n_windows, W.groups, max_iters, K4, huber_delta, d_off, d_off + noff, d_off + 2 * noff,
+                           at<double>(b, L.poses), at<double>(b, L.points), at<int32_t>(b, L.rows),
+                           at<uint8_t>(b, L.opose), at<double>(b, L.oxy), cap, ocap, at<double>(ws, W.wp),
+                           at<double>(ws, W.wo), at<unsigned long long>(ws, W.slot), at<void>(b, L.out)));
   // the staged vectors are pageable: their copies above have left the host before the calls returned
-  HIPCHK(c, hipMemcpyAsync(poses6, c->ba.poses.p, sizeof(double) * 6 * tp, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(points3, c->ba.points.p, sizeof(double) * 3 * tn, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(summaries, c->ba.out.p, sizeof(orbx_ba_summary) * (size_t)n_windows, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(poses6, at<double>(b, L.poses), sizeof(double) * 6 * tp, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(points3, at<double>(b, L.points), sizeof(double) * 3 * tn, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(summaries, at<void>(b, L.out), sizeof(orbx_ba_summary) * (size_t)n_windows, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return ORBX_OK;
 }

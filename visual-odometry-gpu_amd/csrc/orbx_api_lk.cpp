@@ -75,32 +75,32 @@ int orbx_lk_track(orbx_ctx* c, const uint8_t* prev, int prev_stride, const uint8
     HIPCHK(c, orbx_launch_lk_scharr(c->stream, pimg + g.img_off[l], g.w[l], g.h[l], g.pitch[l],
                                     reinterpret_cast<int16_t*>((uint8_t*)c->lk.deriv.p + g.der_off[l])));
   uint8_t* hio = nullptr;
-  const size_t o_out = sizeof(float) * 2 * (size_t)n, o_err = 2 * o_out, o_st = o_err + sizeof(float) * (size_t)n;
-  const size_t io_bytes = o_st + (size_t)n;
+  const LkIo L(n);
   if (n > 0) {
-    ENSURE(c, c->lk.io, io_bytes);
-    if (c->lk.host_bytes < io_bytes) {  // pinned staging: small pageable copies cost ~15 us each
+    DevBuf& io = c->lk.io;
+    ENSURE(c, io, L.bytes);
+    if (c->lk.host_bytes < L.bytes) {  // pinned staging: small pageable copies cost ~15 us each
       if (c->lk.host) (void)hipHostFree(c->lk.host);
       c->lk.host = nullptr;
       c->lk.host_bytes = 0;
-      HIPCHK(c, hipHostMalloc(&c->lk.host, align_up_sz(io_bytes, 4096), hipHostMallocDefault));
-      c->lk.host_bytes = align_up_sz(io_bytes, 4096);
+      HIPCHK(c, hipHostMalloc(&c->lk.host, align_up_sz(L.bytes, 4096), hipHostMallocDefault));
+      c->lk.host_bytes = align_up_sz(L.bytes, 4096);
     }
     hio = (uint8_t*)c->lk.host;
-    uint8_t* dio = (uint8_t*)c->lk.io.p;
-    std::memcpy(hio, prev_pts_xy, o_out);
-    HIPCHK(c, hipMemcpyAsync(dio, hio, o_out, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(hio, prev_pts_xy, L.next);
+    HIPCHK(c, hipMemcpyAsync(io.p, hio, L.next, hipMemcpyHostToDevice, c->stream));
     const OrbxLkPyr P = lk_pyr(g, pimg, (const uint8_t*)c->lk.deriv.p);
     const OrbxLkPyr N = lk_pyr(g, (const uint8_t*)c->lk.img[in].p, nullptr);
-    HIPCHK(c, orbx_launch_lk_track(c->stream, P, N, n, (const float*)dio, (float*)(dio + o_out), dio + o_st,
-                                   (float*)(dio + o_err), win_size, max_iters, epsilon * epsilon));
-    HIPCHK(c, hipMemcpyAsync(hio + o_out, dio + o_out, io_bytes - o_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, orbx_launch_lk_track(c->stream, P, N, n, at<float>(io, 0), at<float>(io, L.next), at<uint8_t>(io, L.status),
+                                   at<float>(io, L.err), win_size, max_iters, epsilon * epsilon));
+    // next points | err | status come back in one copy
+    HIPCHK(c, hipMemcpyAsync(hio + L.next, at<uint8_t>(io, L.next), L.bytes - L.next, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n > 0) {
-    std::memcpy(next_pts_xy, hio + o_out, o_out);
-    std::memcpy(status, hio + o_st, (size_t)n);
-    if (err) std::memcpy(err, hio + o_err, sizeof(float) * (size_t)n);
+    std::memcpy(next_pts_xy, hio + L.next, L.next);
+    std::memcpy(status, hio + L.status, (size_t)n);
+    if (err) std::memcpy(err, hio + L.err, sizeof(float) * (size_t)n);
   }
   c->lk.w = width;
   c->lk.h = height;

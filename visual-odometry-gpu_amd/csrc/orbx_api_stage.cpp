@@ -333,35 +333,30 @@ int orbx_select_top(orbx_ctx* c, const float* responses, int n, int keep, int32_
 
 // ---- descriptor matching (next row) -----------------------------------------
 
+// the host-array entry: the result block of one pair of nq slots, L = MatchBlock(1, nq), comes back whole in `r`
 static int knn_host(orbx_ctx* c, const orbx_descriptor* query, int nq, const orbx_descriptor* train, int nt,
-                    double ratio, std::vector<int32_t>* idx, std::vector<int32_t>* dist,
-                    std::vector<int32_t>* match) {
+                    double ratio, const MatchBlock& L, std::vector<int32_t>* r) {
   if (!c) return ORBX_ERR_INVALID_ARG;
   if (nq < 0 || nt < 0 || (nq > 0 && !query) || (nt > 0 && !train))
     return fail(c, ORBX_ERR_INVALID_ARG, "bad matcher arguments");
-  idx->assign((size_t)2 * nq, -1);
-  dist->assign((size_t)2 * nq, -1);
-  match->assign((size_t)nq, -1);
   if (nq == 0) return ORBX_OK;
-  ENSURE(c, c->m.q, sizeof(orbx_descriptor) * (size_t)nq);
-  ENSURE(c, c->m.t, sizeof(orbx_descriptor) * (size_t)std::max(nt, 1));
-  ENSURE(c, c->m.idx, sizeof(int32_t) * 2 * (size_t)nq);
-  ENSURE(c, c->m.dist, sizeof(int32_t) * 2 * (size_t)nq);
-  ENSURE(c, c->m.match, sizeof(int32_t) * (size_t)nq);
-  ENSURE(c, c->m.cnt, 64);
+  r->resize(L.bytes / sizeof(int32_t));
+  const MatchInput I(nq, nt);
+  DevBuf &in = c->m.in, &res = c->m.res;
+  ENSURE(c, in, I.bytes);
+  ENSURE(c, res, L.bytes);
   const int32_t cnt[2] = {nq, nt};
   hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(c->m.cnt.p, cnt, sizeof(cnt), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->m.q.p, query, sizeof(orbx_descriptor) * (size_t)nq, hipMemcpyHostToDevice, s));
-  if (nt > 0) HIPCHK(c, hipMemcpyAsync(c->m.t.p, train, sizeof(orbx_descriptor) * (size_t)nt, hipMemcpyHostToDevice, s));
-  HIPCHK(c, orbx_launch_knn2(s, 1, nq, (const orbx_descriptor*)c->m.q.p, (const int32_t*)c->m.cnt.p, 0,
-                             (const orbx_descriptor*)c->m.t.p, (const int32_t*)c->m.cnt.p + 1, 0, ratio,
-                             (int32_t*)c->m.idx.p, (int32_t*)c->m.dist.p, (int32_t*)c->m.match.p, 0));
-  HIPCHK(c, hipMemcpyAsync(idx->data(), c->m.idx.p, sizeof(int32_t) * 2 * (size_t)nq, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(dist->data(), c->m.dist.p, sizeof(int32_t) * 2 * (size_t)nq, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(match->data(), c->m.match.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(at<int32_t>(in, I.cnt), cnt, sizeof(cnt), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(at<orbx_descriptor>(in, I.q), query, sizeof(orbx_descriptor) * (size_t)nq, hipMemcpyHostToDevice, s));
+  if (nt > 0)
+    HIPCHK(c, hipMemcpyAsync(at<orbx_descriptor>(in, I.t), train, sizeof(orbx_descriptor) * (size_t)nt, hipMemcpyHostToDevice, s));
+  HIPCHK(c, orbx_launch_knn2(s, 1, nq, at<orbx_descriptor>(in, I.q), at<int32_t>(in, I.cnt), 0,
+                             at<orbx_descriptor>(in, I.t), at<int32_t>(in, I.cnt) + 1, 0, ratio, at<int32_t>(res, L.idx),
+                             at<int32_t>(res, L.dist), at<int32_t>(res, L.match), 0));
+  HIPCHK(c, hipMemcpyAsync(r->data(), res.p, L.bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
-  c->m.pairs = 0;  // the scratch no longer holds a batch's matches
+  c->m.pairs = 0;  // the block no longer holds a batch's matches
   return ORBX_OK;
 }
 
@@ -385,12 +380,13 @@ int orbx_knn2(orbx_ctx* c, const orbx_descriptor* query, int nq, const orbx_desc
               int32_t* idx, int32_t* dist) {
   DeviceGuard _dg(c);
   if (c && nq > 0 && (!idx || !dist)) return fail(c, ORBX_ERR_INVALID_ARG, "idx/dist is NULL");
-  std::vector<int32_t> vi, vd, vm;
-  int st = knn_host(c, query, nq, train, nt, 0.8, &vi, &vd, &vm);
+  const MatchBlock L(1, std::max(nq, 0));
+  std::vector<int32_t> r;
+  int st = knn_host(c, query, nq, train, nt, 0.8, L, &r);
   if (st != ORBX_OK) return st;
   if (nq > 0) {
-    std::memcpy(idx, vi.data(), sizeof(int32_t) * 2 * (size_t)nq);
-    std::memcpy(dist, vd.data(), sizeof(int32_t) * 2 * (size_t)nq);
+    std::memcpy(idx, r.data() + L.idx / sizeof(int32_t), sizeof(int32_t) * 2 * (size_t)nq);
+    std::memcpy(dist, r.data() + L.dist / sizeof(int32_t), sizeof(int32_t) * 2 * (size_t)nq);
   }
   return ORBX_OK;
 }
@@ -400,10 +396,12 @@ int orbx_match_ratio(orbx_ctx* c, const orbx_descriptor* query, int nq, const or
   DeviceGuard _dg(c);
   if (c && (!count || capacity < 0 || (capacity > 0 && (!query_idx || !train_idx))))
     return fail(c, ORBX_ERR_INVALID_ARG, "bad match output arguments");
-  std::vector<int32_t> vi, vd, vm;
-  int st = knn_host(c, query, nq, train, nt, ratio, &vi, &vd, &vm);
+  const MatchBlock L(1, std::max(nq, 0));
+  std::vector<int32_t> r;
+  int st = knn_host(c, query, nq, train, nt, ratio, L, &r);
   if (st != ORBX_OK) return st;
-  return compact_matches(c, vm.data(), vd.data(), nq, query_idx, train_idx, dist1, capacity, count);
+  return compact_matches(c, r.data() + L.match / sizeof(int32_t), r.data() + L.dist / sizeof(int32_t), nq, query_idx,
+                         train_idx, dist1, capacity, count);
 }
 
 int orbx_batch_match_consecutive(orbx_ctx* c, double ratio) {
@@ -411,20 +409,20 @@ int orbx_batch_match_consecutive(orbx_ctx* c, double ratio) {
   if (!c) return ORBX_ERR_INVALID_ARG;
   const Block& B = last_block(c);
   if (B.n < 2) return fail(c, ORBX_ERR_INVALID_ARG, "needs a batch of at least two frames");
-  // the match buffers are ONE set per context: a match of the other lane's batch may still be writing them
+  // the match block is ONE per context: a match of the other lane's batch may still be writing it
   if (c->lanes[1].stream) HIPCHK(c, lanes_sync(c));
   const int n = B.n, cap = B.cap;
-  const size_t e = (size_t)(n - 1) * cap;
-  ENSURE(c, c->m.idx, sizeof(int32_t) * 2 * e);
-  ENSURE(c, c->m.dist, sizeof(int32_t) * 2 * e);
-  ENSURE(c, c->m.match, sizeof(int32_t) * e);
+  const MatchBlock L(n - 1, cap);
+  DevBuf& res = c->m.res;
+  ENSURE(c, res, L.bytes);
   const int32_t* counts = (const int32_t*)(B.d + B.layout.counts);
   const orbx_descriptor* desc = (const orbx_descriptor*)(B.d + B.layout.desc);
   hipStream_t s = batch_stream(c);
   // pair p: query = frame p, train = frame p+1 (same arrays, shifted by one slot block)
   HIPCHK(c, orbx_launch_knn2(s, n - 1, cap, desc, counts, (size_t)cap, desc + cap, counts + 1, (size_t)cap, ratio,
-                             (int32_t*)c->m.idx.p, (int32_t*)c->m.dist.p, (int32_t*)c->m.match.p, (size_t)cap));
+                             at<int32_t>(res, L.idx), at<int32_t>(res, L.dist), at<int32_t>(res, L.match), (size_t)cap));
   c->m.pairs = n - 1;
+  c->m.cap = cap;
   c->m.serial = c->batch_serial;
   c->m.gen++;
   return ORBX_OK;
@@ -438,18 +436,20 @@ int orbx_batch_match_fetch(orbx_ctx* c, int pair, int32_t* query_idx, int32_t* t
     return fail(c, ORBX_ERR_INVALID_ARG, "bad match output arguments");
   if (pair < 0 || pair >= c->m.pairs) return fail(c, ORBX_ERR_INVALID_ARG, "pair outside the last matched batch");
   const Block& B = last_block(c);
-  const int cap = B.cap;
+  const int cap = c->m.cap;
+  const MatchBlock L(c->m.pairs, cap);
   hipStream_t s = batch_stream(c);
   int32_t nq = 0;
   std::vector<int32_t> vm((size_t)cap), vd((size_t)2 * cap);
   HIPCHK(c, hipMemcpyAsync(&nq, (const int32_t*)(B.d + B.layout.counts) + pair, sizeof(int32_t),
                            hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(vm.data(), (const int32_t*)c->m.match.p + (size_t)pair * cap, sizeof(int32_t) * cap,
+  HIPCHK(c, hipMemcpyAsync(vm.data(), at<int32_t>(c->m.res, L.match) + (size_t)pair * cap, sizeof(int32_t) * cap,
                            hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(vd.data(), (const int32_t*)c->m.dist.p + (size_t)2 * pair * cap, sizeof(int32_t) * 2 * cap,
+  HIPCHK(c, hipMemcpyAsync(vd.data(), at<int32_t>(c->m.res, L.dist) + (size_t)2 * pair * cap, sizeof(int32_t) * 2 * cap,
                            hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
-  return compact_matches(c, vm.data(), vd.data(), nq, query_idx, train_idx, dist1, capacity, count);
+  // (the rows are as wide as the matched batch's: a later batch's counts never reach past them)
+  return compact_matches(c, vm.data(), vd.data(), std::min(nq, cap), query_idx, train_idx, dist1, capacity, count);
 }
 
 }  // extern "C"

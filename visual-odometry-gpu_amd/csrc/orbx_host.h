@@ -1,6 +1,9 @@
 // orbx_host.h -- what every part of the C-ABI host layer (orbx_api*.cpp) shares: the context and the records it is
 // made of, the error and device guards, and the helpers that more than one of those files calls (defined once, in
-// orbx_api.cpp).  Host only: included by no .hip file, and not part of the public interface.
+// orbx_api.cpp).  Every part owns a few blocks whose sections orbx_layout.h places.  The blocks of the work beside the
+// batched path grow through SideWork::grow; ensure() grows those of the paths that run on the context's stream or the
+// last batch's: the stage scratch, the matcher, the pair tracker, pose, scale and bundle adjustment of staged windows.
+// Host only: included by no .hip file, and not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +25,9 @@ struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
 };
+// section `off` of a block, as the array of T that a launch or a copy takes
+template <class T>
+T* at(const DevBuf& b, size_t off) { return reinterpret_cast<T*>(static_cast<uint8_t*>(b.p) + off); }
 // what a subsystem's release() does with the buffers it owns (nothing may still be using them)
 inline void free_bufs(std::initializer_list<DevBuf*> bufs) {
   for (DevBuf* b : bufs)
@@ -155,20 +161,22 @@ struct StageScratch {
   void release() { free_bufs({&img_a, &img_b, &f32, &u16, &mask, &kps, &f32b, &desc, &i32, &kern, &tiles}); }
 };
 
+// descriptor matcher: ONE result block (MatchBlock of orbx_layout.h) that the host-array entry and the batch entry
+// share, and the staged input of the host-array entry (MatchInput)
 struct Matcher {
-  DevBuf q, t, idx, dist, match, cnt;  // matcher (stage API and batch)
-  int pairs = 0;
+  DevBuf res, in;
+  int pairs = 0, cap = 0;  // pairs and slots per pair of the batch match the block holds (pairs == 0: none)
   long long serial = -1;  // the batch serial (orbx_ctx::batch_serial) the last batch match was made on
   // bumped by every batch match: the pose step records the one it read (Pose::match_gen), so the scale step, which
   // reads m.match again, can tell that the matches are still the ones the poses were computed from
   long long gen = 0;
-  void release() { free_bufs({&q, &t, &idx, &dist, &match, &cnt}); }
+  void release() { free_bufs({&res, &in}); }
 };
 
 // Lucas-Kanade tracker: two image pyramids (ping-pong: the `next` of one call is the
 // `prev` of the following one), the derivative pyramid of the current `prev`, point buffers
 struct LkPair {
-  DevBuf img[2], deriv, io;  // io: prev points | next points | err | status, one block
+  DevBuf img[2], deriv, io;  // io: the point block (LkIo of orbx_layout.h)
   void* host = nullptr;      // pinned mirror of io (one H2D + one D2H per call)
   size_t host_bytes = 0;
   int w = 0, h = 0, top = -1, win = 0, last = -1;  // last: buffer holding the last `next`
@@ -197,32 +205,31 @@ struct LkWindows {
   }
 };
 
-// relative pose (orbx_pose.hip): batched results (pb_*) and the host-array entry's own buffers (ph_*)
+// relative pose (orbx_pose.hip): the batch entry's block (PoseBlock of pairs x cap), and the host-array entry's own
+// block (PoseBlock of one pair) with its staged point lists
 struct Pose {
-  DevBuf pb_pts, pb_n, pb_out, pb_mask, ph_in, ph_pts, ph_n, ph_out, ph_mask;
+  DevBuf blk, hblk, hin;
   int pairs = 0, cap = 0;
   hipStream_t stream = nullptr;
   long long serial = -1;     // the batch serial the last batch pose ran on
   long long match_gen = -1;  // the Matcher::gen it read
-  void release() { free_bufs({&pb_pts, &pb_n, &pb_out, &pb_mask, &ph_in, &ph_pts, &ph_n, &ph_out, &ph_mask}); }
+  void release() { free_bufs({&blk, &hblk, &hin}); }
 };
 
-// triangulation and scale (orbx_scale.hip): batched results (sb_*: points, valid bytes, compact match lists,
-// match counts, scales) and the host-array entries' own buffers (sh_*)
+// triangulation and scale (orbx_scale.hip): the batch entry's block (ScaleBlock of pairs x cap), and the one buffer
+// the two host-array entries lay out in turn (TriHost, ScaleHost)
 struct Scale {
-  DevBuf sb_xyz, sb_valid, sb_mq, sb_mt, sb_n, sb_out, sh_in, sh_xyz, sh_valid, sh_out;
+  DevBuf blk, host;
   int pairs = 0, cap = 0;
   hipStream_t stream = nullptr;
-  void release() {
-    free_bufs({&sb_xyz, &sb_valid, &sb_mq, &sb_mt, &sb_n, &sb_out, &sh_in, &sh_xyz, &sh_valid, &sh_out});
-  }
+  void release() { free_bufs({&blk, &host}); }
 };
 
-// bundle adjustment (orbx_ba.hip): the staged windows (offsets, parameter blocks, CSR observations), the
-// workgroups' workspaces and the summaries; grown on first use
+// bundle adjustment of staged windows (orbx_ba.hip): the windows and their summaries (BaStage of orbx_layout.h) and
+// the workgroups' workspaces (LmWork); grown on first use
 struct BundleAdjust {
-  DevBuf off, poses, points, rows, opose, oxy, wp, wo, slot, out;
-  void release() { free_bufs({&off, &poses, &points, &rows, &opose, &oxy, &wp, &wo, &slot, &out}); }
+  DevBuf stage, ws;
+  void release() { free_bufs({&stage, &ws}); }
 };
 
 // landmarks of tracked windows and their bundle adjustment on the device (orbx_landmarks.hip, orbx_ba.hip): the

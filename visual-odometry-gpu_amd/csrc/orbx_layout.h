@@ -1,7 +1,8 @@
 // orbx_layout.h -- where the sections of every block of the host layer lie (result blocks, workspaces, scratch), and
 // how many frames a workspace holds.  Host arithmetic on plain numbers, no HIP call: like orbx_plan.h it compiles
 // into a stand-alone program (tests/cpp/layout_pins.cpp pins every value).  Not part of the public interface.
-// A layout is a struct of byte offsets that its constructor computes from the block's shape.
+// A layout is a struct of byte offsets that its constructor computes from the block's shape: most take their sections
+// from a private Sections base, member by member in the order of their declaration, which is the order in the block.
 #pragma once
 #include <algorithm>
 
@@ -27,23 +28,14 @@ struct Sections {
 // sections: counts | kp16 | angle | desc || kp | lkp | resp | level -- what the reference's own output consists of
 // (keypoints, orientations, descriptors: include/orb.hpp:37) first, so that orbx_batch_prefetch_compact moves one
 // contiguous prefix of `compact` bytes (40 bytes per slot)
-struct OutLayout {
-  size_t counts, kp16, kp, lkp, angle, resp, level, desc, compact, total;
-  OutLayout() = default;
-  OutLayout(int n, int cap) {
-    Sections s;
-    const size_t e = (size_t)n * (size_t)cap;
-    counts = s.take(sizeof(int32_t) * (size_t)n);
-    kp16 = s.take(sizeof(uint32_t) * e);
-    angle = s.take(sizeof(float) * e);
-    desc = s.take(sizeof(orbx_descriptor) * e);
-    compact = s.off;
-    kp = s.take(sizeof(orbx_keypoint) * e);
-    lkp = s.take(sizeof(orbx_keypoint) * e);
-    resp = s.take(sizeof(float) * e);
-    level = s.take(sizeof(int32_t) * e);
-    total = s.off;
-  }
+struct OutLayout : private Sections {
+  size_t e, counts, kp16, angle, desc, compact, kp, lkp, resp, level, total;
+  OutLayout() : OutLayout(0, 0) {}
+  OutLayout(size_t n, size_t cap)
+      : e(n * cap), counts(take(sizeof(int32_t) * n)), kp16(take(sizeof(uint32_t) * e)), angle(take(sizeof(float) * e)),
+        desc(take(sizeof(orbx_descriptor) * e)), compact(off), kp(take(sizeof(orbx_keypoint) * e)),
+        lkp(take(sizeof(orbx_keypoint) * e)), resp(take(sizeof(float) * e)), level(take(sizeof(int32_t) * e)),
+        total(off) {}
 };
 
 // ---- Shi-Tomasi corners ----
@@ -80,24 +72,16 @@ inline int gf_slice_frames(size_t ws_bytes, int n, int w, int h, size_t grid_str
   return (n + slices - 1) / slices;
 }
 // the result block: counts | corners
-struct GrLayout {
-  size_t corners, total;
-  GrLayout(int n, int cap) {
-    Sections s;
-    s.take(sizeof(int32_t) * (size_t)n);
-    corners = s.take(sizeof(float) * 2 * (size_t)cap * n);
-    total = s.end;
-  }
+struct GrLayout : private Sections {
+  size_t counts, corners, total;
+  GrLayout(size_t n, size_t cap) : counts(take(sizeof(int32_t) * n)), corners(take(sizeof(float) * 2 * cap * n)), total(end) {}
 };
 // the bit maps of blocked pixels of m frames of w x h: the masked maxima first, then ceil(w / 32) * h words per frame
-struct GbLayout {
-  size_t bits, words, total;
-  GbLayout(int m, int w, int h) : words((size_t)((w + 31) / 32) * h) {
-    Sections s;
-    s.take(sizeof(uint32_t) * (size_t)m);
-    bits = s.take(sizeof(uint32_t) * words * m);
-    total = s.end;
-  }
+struct GbLayout : private Sections {
+  size_t words, maxima, bits, total;
+  GbLayout(size_t m, int w, int h)
+      : words((size_t)((w + 31) / 32) * h), maxima(take(sizeof(uint32_t) * m)), bits(take(sizeof(uint32_t) * words * m)),
+        total(end) {}
 };
 // the bit maps of m frames of the largest size (+ 512: whatever frames of a smaller size fit by gb_frames fit with
 // their sections' alignment)
@@ -108,16 +92,11 @@ inline size_t gb_frames(size_t bm_bytes, int w, int h) {
   return std::max<size_t>((bm_bytes - 256) / (sizeof(uint32_t) * (GbLayout(1, w, h).words + 1)), 1);
 }
 // the top-up's result block: counts | carried | points | origin
-struct GtLayout {
-  size_t carried, points, origin, total;
-  GtLayout(int n, int cap) {
-    Sections s;
-    s.take(sizeof(int32_t) * (size_t)n);
-    carried = s.take(sizeof(int32_t) * (size_t)n);
-    points = s.take(sizeof(float) * 2 * (size_t)cap * n);
-    origin = s.take(sizeof(int32_t) * (size_t)cap * n);
-    total = s.end;
-  }
+struct GtLayout : private Sections {
+  size_t counts, carried, points, origin, total;
+  GtLayout(size_t n, size_t cap)
+      : counts(take(sizeof(int32_t) * n)), carried(take(sizeof(int32_t) * n)), points(take(sizeof(float) * 2 * cap * n)),
+        origin(take(sizeof(int32_t) * cap * n)), total(end) {}
 };
 
 // ---- Lucas-Kanade ----
@@ -143,6 +122,11 @@ struct LkGeom {
     der_bytes = der.off;
   }
 };
+// the pair tracker's points, tight (they cross the bus whole, through one pinned mirror): prev | next | err | status
+struct LkIo {
+  size_t next, err, status, bytes;  // prev at 0
+  explicit LkIo(size_t n) : next(sizeof(float) * 2 * n), err(2 * next), status(err + sizeof(float) * n), bytes(status + n) {}
+};
 // the windows tracker's workspace of ONE frame: the pyramid levels above 0 (level 0 is read in place), then the
 // derivative maps of every level
 struct LkwLayout {
@@ -162,112 +146,127 @@ inline size_t lkw_fit(size_t limit, const LkwLayout& L, int window_len, int n_fr
 inline size_t lkw_der_offset(const LkwLayout& L, size_t m) { return align_up_sz(L.img_bytes * m, 256); }
 inline size_t lkw_workspace_bytes(const LkwLayout& L, size_t m) { return m * L.frame_bytes + 256; }
 // the windows tracker's result block: tracks | seen | err
-struct LkwResult {
-  size_t o_seen, o_err, bytes;  // tracks at 0
-  LkwResult(int n_windows, int cap, int len) {
-    Sections s;
-    const size_t slots = (size_t)n_windows * cap;
-    s.take(sizeof(float) * 2 * slots * len);
-    o_seen = s.take(sizeof(int32_t) * slots);
-    o_err = s.take(sizeof(float) * slots * (len - 1));
-    bytes = s.end;
-  }
+struct LkwResult : private Sections {
+  size_t slots, o_tracks, o_seen, o_err, bytes;
+  LkwResult(size_t n_windows, size_t cap, size_t len)
+      : slots(n_windows * cap), o_tracks(take(sizeof(float) * 2 * slots * len)), o_seen(take(sizeof(int32_t) * slots)),
+        o_err(take(sizeof(float) * slots * (len - 1))), bytes(end) {}
 };
 // what the forward-backward check adds, in a buffer of its own: fb_d2 | lost
-struct LkwFbResult {
-  size_t o_lost, bytes;  // fb_d2 at 0
-  LkwFbResult(int n_windows, int cap, int len) {
-    Sections s;
-    const size_t slots = (size_t)n_windows * cap;
-    s.take(sizeof(float) * slots * (len - 1));
-    o_lost = s.take(sizeof(int32_t) * slots);
-    bytes = s.end;
-  }
+struct LkwFbResult : private Sections {
+  size_t slots, o_d2, o_lost, bytes;
+  LkwFbResult(size_t n_windows, size_t cap, size_t len)
+      : slots(n_windows * cap), o_d2(take(sizeof(float) * slots * (len - 1))), o_lost(take(sizeof(int32_t) * slots)),
+        bytes(end) {}
 };
 
 // ---- landmarks of n tracked windows of cap slots and len poses, and their bundle adjustment ----
 // the result block: every array sized for every slot kept
-struct LmBlock {
-  size_t status, pose_off, pt_off, obs_off, slot, rows, points, oxy, opose, bytes;
-  LmBlock(int n, int cap, int len) {
-    Sections s;
-    const size_t slots = (size_t)n * cap, noff = (size_t)n + 1;
-    status = s.take(sizeof(int32_t) * n);
-    pose_off = s.take(sizeof(int32_t) * noff);
-    pt_off = s.take(sizeof(int32_t) * noff);
-    obs_off = s.take(sizeof(int32_t) * noff);
-    slot = s.take(sizeof(int32_t) * slots);
-    rows = s.take(sizeof(int32_t) * (slots + n));
-    points = s.take(sizeof(double) * 3 * slots);
-    oxy = s.take(sizeof(double) * 2 * slots * len);
-    opose = s.take(slots * len);
-    bytes = s.off;
-  }
+struct LmBlock : private Sections {
+  size_t slots, status, pose_off, pt_off, obs_off, slot, rows, points, oxy, opose, bytes;
+  LmBlock(size_t n, size_t cap, size_t len)
+      : slots(n * cap), status(take(sizeof(int32_t) * n)), pose_off(take(sizeof(int32_t) * (n + 1))),
+        pt_off(take(sizeof(int32_t) * (n + 1))), obs_off(take(sizeof(int32_t) * (n + 1))),
+        slot(take(sizeof(int32_t) * slots)), rows(take(sizeof(int32_t) * (slots + n))),
+        points(take(sizeof(double) * 3 * slots)), oxy(take(sizeof(double) * 2 * slots * len)), opose(take(slots * len)),
+        bytes(off) {}
 };
 // the scratch of a build
-struct LmScratch {
+struct LmScratch : private Sections {
   size_t poses, gate, partial, keep, cand, bytes;
-  LmScratch(int n, int cap, int len) {
-    Sections s;
-    const size_t slots = (size_t)n * cap;
-    poses = s.take(sizeof(double) * 6 * (size_t)n * len);
-    gate = s.take(sizeof(int32_t) * n);
-    partial = s.take(sizeof(int32_t) * 2 * (size_t)n * orbx_lm_blocks(cap));
-    keep = s.take(slots);
-    cand = s.take(sizeof(double) * 3 * slots);
-    bytes = s.off;
-  }
+  LmScratch(size_t n, int cap, size_t len)
+      : poses(take(sizeof(double) * 6 * n * len)), gate(take(sizeof(int32_t) * n)),
+        partial(take(sizeof(int32_t) * 2 * n * orbx_lm_blocks(cap))), keep(take(n * cap)),
+        cand(take(sizeof(double) * 3 * n * cap)), bytes(off) {}
 };
 // what a solve works on and leaves behind
-struct LmSolve {
+struct LmSolve : private Sections {
   size_t poses, points, out, bytes;
-  LmSolve(int n, int cap, int len) {
-    Sections s;
-    poses = s.take(sizeof(double) * 6 * (size_t)n * len);
-    points = s.take(sizeof(double) * 3 * (size_t)n * cap);
-    out = s.take(sizeof(orbx_ba_summary) * (size_t)n);
-    bytes = s.off;
-  }
+  LmSolve(size_t n, size_t cap, size_t len)
+      : poses(take(sizeof(double) * 6 * n * len)), points(take(sizeof(double) * 3 * n * cap)),
+        out(take(sizeof(orbx_ba_summary) * n)), bytes(off) {}
 };
-// the workspaces of a solve's workgroups: as many groups as windows, bounded by ORBX_BA_MAX_GROUPS and by the
-// workspace budget
+// the workspaces of a solve's workgroups, for windows of at most cap landmarks and ocap observations: as many groups
+// as windows, bounded by ORBX_BA_MAX_GROUPS and by the workspace budget.  Tracked windows of len poses: ocap = cap * len
 struct LmWork {
   int groups;
   size_t wp, wo, slot, bytes;
-  LmWork(int n, int cap, int len) {
+  LmWork(int n, int cap, int len) : LmWork(n, (size_t)cap, (size_t)cap * len) {}
+  LmWork(int n, size_t cap, size_t ocap) {
     Sections s;
-    const size_t ocap = (size_t)cap * len;
-    const size_t per_group =
-        sizeof(double) * ((size_t)ORBX_BA_WS_POINT * cap + (size_t)ORBX_BA_WS_OBS * ocap) + 8 * (size_t)cap;
+    const size_t per_group = sizeof(double) * (ORBX_BA_WS_POINT * cap + ORBX_BA_WS_OBS * ocap) + 8 * cap;
     groups = std::min(n, ORBX_BA_MAX_GROUPS);
     groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)groups, ORBX_BA_WS_BUDGET / per_group));
-    wp = s.take(sizeof(double) * ORBX_BA_WS_POINT * (size_t)cap * groups);
+    wp = s.take(sizeof(double) * ORBX_BA_WS_POINT * cap * groups);
     wo = s.take(sizeof(double) * ORBX_BA_WS_OBS * ocap * groups);
-    slot = s.take(8 * (size_t)cap * groups);
+    slot = s.take(8 * cap * groups);
     bytes = s.off;
   }
+};
+// the staged windows of orbx_bundle_adjust_batch, n windows with tp poses, tn landmarks and tm observations in all:
+// the three offset tables (n + 1 entries each, back to back) | poses | points | rows | opose | oxy | summaries
+struct BaStage : private Sections {
+  size_t off, poses, points, rows, opose, oxy, out, bytes;
+  BaStage(size_t n, size_t tp, size_t tn, size_t tm)
+      : off(take(sizeof(int32_t) * 3 * (n + 1))), poses(take(sizeof(double) * 6 * tp)),
+        points(take(sizeof(double) * 3 * tn)), rows(take(sizeof(int32_t) * (tn + n))), opose(take(tm)),
+        oxy(take(sizeof(double) * 2 * tm)), out(take(sizeof(orbx_ba_summary) * n)), bytes(Sections::off) {}
 };
 
 // ---- pose and scale of tracked frame pairs ----
 // the result block: one row of `cap` per pair in every per-position array
-struct TpBlock {
-  size_t pose, n, scale, slot_of, mask, xyz, valid, bytes;
-  TpBlock(int n_windows, int cap, int len) {
-    Sections s;
-    const size_t pairs = (size_t)n_windows * (len - 1), e = pairs * cap;
-    pose = s.take(sizeof(OrbxPoseOut) * pairs);
-    n = s.take(sizeof(int32_t) * pairs);
-    scale = s.take(sizeof(OrbxScaleOut) * pairs);
-    slot_of = s.take(sizeof(int32_t) * e);
-    mask = s.take(e);
-    xyz = s.take(sizeof(float) * 3 * e);
-    valid = s.take(e);
-    bytes = s.off;
-  }
+struct TpBlock : private Sections {
+  size_t pairs, e, pose, n, scale, slot_of, mask, xyz, valid, bytes;
+  TpBlock(size_t n_windows, size_t cap, size_t len)
+      : pairs(n_windows * (len - 1)), e(pairs * cap), pose(take(sizeof(OrbxPoseOut) * pairs)),
+        n(take(sizeof(int32_t) * pairs)), scale(take(sizeof(OrbxScaleOut) * pairs)), slot_of(take(sizeof(int32_t) * e)),
+        mask(take(e)), xyz(take(sizeof(float) * 3 * e)), valid(take(e)), bytes(off) {}
 };
 // the scratch: the normalised point lists
 inline size_t tp_scratch_bytes(int n_windows, int cap, int len) {
   return sizeof(OrbxPosePt) * (size_t)n_windows * (len - 1) * cap;
 }
+
+// ---- the descriptor matcher, and pose and scale of the frame pairs of a batch ----
+// one row of `cap` per pair in every per-slot array (e = pairs * cap slots).  The host-array entries use the same
+// blocks with one pair: MatchBlock(1, nq), PoseBlock(1, max(n, 1)).
+// the matcher's result block: idx | dist (two neighbours per slot) | match
+struct MatchBlock : private Sections {
+  size_t idx, dist, match, bytes;
+  MatchBlock(size_t pairs, size_t cap)
+      : idx(take(8 * pairs * cap)), dist(take(8 * pairs * cap)), match(take(4 * pairs * cap)), bytes(off) {}
+};
+// the staged input of the matcher's host entry: cnt (nq, nt) | q | t
+struct MatchInput : private Sections {
+  size_t cnt, q, t, bytes;
+  MatchInput(size_t nq, size_t nt)
+      : cnt(take(64)), q(take(sizeof(orbx_descriptor) * nq)),
+        t(take(sizeof(orbx_descriptor) * std::max<size_t>(nt, 1))), bytes(off) {}
+};
+struct PoseBlock : private Sections {
+  size_t pts, n, out, mask, bytes;
+  PoseBlock(size_t pairs, size_t cap)
+      : pts(take(sizeof(OrbxPosePt) * pairs * cap)), n(take(sizeof(int32_t) * pairs)),
+        out(take(sizeof(OrbxPoseOut) * pairs)), mask(take(pairs * cap)), bytes(off) {}
+};
+// mq | mt: the compact match lists
+struct ScaleBlock : private Sections {
+  size_t xyz, valid, mq, mt, n, out, bytes;
+  ScaleBlock(size_t pairs, size_t cap)
+      : xyz(take(sizeof(float) * 3 * pairs * cap)), valid(take(pairs * cap)), mq(take(sizeof(int32_t) * pairs * cap)),
+        mt(take(sizeof(int32_t) * pairs * cap)), n(take(sizeof(int32_t) * pairs)),
+        out(take(sizeof(OrbxScaleOut) * pairs)), bytes(off) {}
+};
+// the two host-array entries of orbx_scale.hip lay out ONE buffer in turn.  orbx_triangulate of n points: in (both
+// lists) | xyz | valid; orbx_estimate_scale of two lists of m points: prev, cur xyz | prev, cur valid | out
+struct TriHost : private Sections {
+  size_t in, xyz, valid, bytes;
+  explicit TriHost(size_t n) : in(take(sizeof(float) * 4 * n)), xyz(take(sizeof(float) * 3 * n)), valid(take(n)), bytes(off) {}
+};
+struct ScaleHost : private Sections {
+  size_t xyz, valid, out, bytes;
+  explicit ScaleHost(size_t m)
+      : xyz(take(sizeof(float) * 6 * m)), valid(take(2 * m)), out(take(sizeof(OrbxScaleOut))), bytes(off) {}
+};
 
 }  // namespace orbx_layout
