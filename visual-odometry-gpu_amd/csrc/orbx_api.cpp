@@ -228,6 +228,39 @@ int top_rows_env() {
 // Read when a context is created (A/B timing in one process).
 int fast_impl_env() { return env_int("ORBX_FAST_IMPL", 4) == 3 ? 3 : 4; }
 
+// The switches of the unevenly cut first pass (orbx_host.h): fields behind the number of ORBX_TOP_ROWS, separated by
+// colons and read when a context is created (the number itself is read once per process, above) --
+//   ORBX_TOP_ROWS=2:equal          the two tile rows of the first pass stay equal halves (A/B timing)
+//   ORBX_TOP_ROWS=2:68,65,0,61     rows of tile row 0 per level, forced (tests; 0: leave the level to the chooser)
+//   ORBX_TOP_ROWS=2:trace          every decision of the chooser goes to stderr
+void first_split_env(orbx_ctx* c) {
+  const char* e = getenv("ORBX_TOP_ROWS");
+  e = e ? std::strchr(e, ':') : nullptr;
+  while (e && *e == ':') {
+    e++;
+    if (!std::strncmp(e, "equal", 5)) {
+      c->first_split = false;
+    } else if (!std::strncmp(e, "trace", 5)) {
+      c->split_trace = true;
+    } else {
+      for (int l = 0; l < ORBX_MAX_LEVELS; l++) {
+        char* end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end == e) break;
+        c->cut_force[l] = (int)std::min<long>(std::max<long>(v, 0), 0xffff);
+        e = end;
+        if (*e != ',') break;
+        e++;
+      }
+    }
+    e = std::strchr(e, ':');
+  }
+}
+// most rows of a unit of the context's FAST kernel
+int fast_unit_rows_max(const orbx_ctx* c) {
+  return c->fast_impl == 4 ? ORBX_FAST_UNIT_ROWS_MAX : orbx_fast3_tile_h(c->p.nms_window / 2);
+}
+
 // 8-bit bilinear coefficient tables: OpenCV 4.x generic 8UC1 INTER_LINEAR path
 // (imgproc/src/resize.cpp: scale = 1/((double)dst/src); fx = (float)((dx+0.5)*
 // scale-0.5); sx = floor(fx); clamp with fx=0; 11-bit coefficients by cvRound).
@@ -429,6 +462,24 @@ int set_plan(orbx_ctx* c, int w, int h) {
     st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4, nullptr);
   }
   if (st != ORBX_OK) return fail(c, st, why);
+  // the first pass cut unevenly (same number of tile rows, same pool): where the chooser or a forced cut says so
+  if (c->prefs_applied && c->first_split && top_rows_env() == 2) {
+    int first[ORBX_MAX_LEVELS][2] = {};
+    bool any = false;
+    for (int l = 0; l < plan.nlevels; l++) {
+      int a = c->cut_force[l] > 0 ? c->cut_force[l] : c->cut_pref[l];
+      if (a <= 0 || c->bm_fast.tiles_y[l] < 2) continue;
+      const int depth = 2 * c->bm_fast.tile_h[l], umax = fast_unit_rows_max(c);
+      if (c->cut_force[l] > 0)  // (a forced cut goes to the nearest one the kernel can run)
+        a = std::max(std::max(1, depth - umax), std::min(a, std::min(umax, std::min(depth, plan.L[l].h) - 1)));
+      first[l][0] = a;
+      first[l][1] = depth - a;
+      any = true;
+    }
+    if (any)  // (the first call above accepted these tile rows: this one cannot fail, and an illegal pair is ignored)
+      (void)make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4,
+                         c->prefs_applied ? c->tile_h_pref : nullptr, first);
+  }
   const bool grouped = pyr_group_env() > 0;
   const int top = top_rows_env();
   std::vector<OrbxTileDesc> t;
@@ -562,6 +613,11 @@ bool adapt_tile_rows(orbx_ctx* c) {
     if (v) {
       c->need_cur[l] = std::max(c->need_cur[l], std::min<uint32_t>(v, (uint32_t)c->plan.L[l].h));
       any = true;
+      // (the same batch may be counted twice, or not at all: only the shares matter)
+      for (int b = 0; b < ORBX_FILL_BUCKETS; b++) {
+        const uint32_t cnt = c->h_feedback[ORBX_FEEDBACK_HIST + l * ORBX_FILL_BUCKETS + b];
+        c->fill_cur[l][b] += std::min<uint32_t>(cnt, 1u << 20);
+      }
     }
   }
   if (!any || ++c->need_batches < c->need_window) return false;
@@ -601,10 +657,55 @@ bool adapt_tile_rows(orbx_ctx* c) {
     // more tile rows than the level above)
     else if (eff + 2 < std::min(cur, asked)) change = true;
   }
-  if (!grow && !change) return false;
+  // Where to cut the first pass.  Its two tile rows are equal halves by default, and a unit of tile row 1 may leave
+  // only when the rows strictly above it hold the cap: no frame fills its cap in the upper half, so every frame
+  // walks both.  With tile row 0 ending where most frames HAVE filled, the short tile row 1 runs for the others
+  // alone (its units are dispatched a whole tile row of every frame later: the statistics are complete by then).
+  // The cut per level comes from the fill-row histograms of the last two windows and the cost model of
+  // choose_first_cut (orbx_plan.h), for the depth the level has after this decision; the tables are rebuilt for a
+  // cut only if it saves a group or more per strip on some level, or if a cut in force has stopped paying.  Streaming
+  // kernel only (the model counts its groups of 7 rows), and only where the fused selection reports the histograms.
+  const bool heights_change = grow || change;
+  const bool split = c->first_split && top == 2 && c->fast_impl == 4;
+  const int R = c->p.nms_window / 2;
+  int cut_want[ORBX_MAX_LEVELS] = {};
+  bool cut_change = false;
+  for (int l = 0; l < nl; l++) {
+    uint32_t hist[ORBX_FILL_BUCKETS];
+    uint64_t total = 0;
+    for (int b = 0; b < ORBX_FILL_BUCKETS; b++) {
+      hist[b] = c->fill_cur[l][b] + c->fill_prev[l][b];
+      c->fill_prev[l][b] = c->fill_cur[l][b];
+      c->fill_cur[l][b] = 0;
+      total += hist[b];
+    }
+    if (!split || c->cut_force[l] > 0 || c->bm_fast.tiles_y[l] < 2) continue;
+    const int dflt = orbx_fast3_tile_h(R), lh = c->plan.L[l].h;
+    const int bal = (lh + (lh + dflt - 1) / dflt - 1) / ((lh + dflt - 1) / dflt);
+    const int th_after = heights_change ? (want[l] ? want[l] : bal) : c->bm_fast.tile_h[l];
+    const int depth = 2 * th_after;
+    // (new tile-row heights void the cut in force: its pair no longer adds up to the depth)
+    const int in_force = !heights_change && c->bm_fast.first_h[l][0] > 0 ? c->bm_fast.first_h[l][0] : 0;
+    int cost_new = 0;
+    const int cut_new = total && lh > depth ? choose_first_cut(hist, depth, R, ORBX_FAST_UNIT_ROWS_MAX, &cost_new) : 0;
+    const int cost_now = first_pass_cost_milli(hist, depth, in_force ? in_force : depth / 2, R);
+    if (!total || lh <= depth) cost_new = cost_now;
+    const bool pays = cost_now - cost_new >= 1000, stopped = in_force && !cut_new && cost_now > cost_new;
+    cut_want[l] = heights_change || pays || stopped ? cut_new : c->cut_pref[l];
+    if (cut_want[l] != in_force && (pays || stopped)) cut_change = true;
+    if (c->split_trace) {
+      fprintf(stderr, "orbx split: batch %lld level %d need %u depth %d cut %d -> %d (%d -> %d milli-groups) fill rows:",
+              c->batch_serial, l, c->need_prev[l], depth, in_force, cut_want[l], cost_now, cost_new);
+      for (int b = 0; b < ORBX_FILL_BUCKETS; b++)
+        if (hist[b]) fprintf(stderr, " %d:%u", ORBX_FILL_BUCKET_ROWS * (b + 1), hist[b]);
+      fprintf(stderr, "\n");
+    }
+  }
+  if (!grow && !change && !cut_change) return false;
   if (!grow && c->retiles >= 4 && c->need_window < 32) return false;  // (settle first)
-  for (int l = 0; l < nl; l++) c->tile_h_pref[l] = want[l];
+  for (int l = 0; l < nl; l++) c->tile_h_pref[l] = want[l], c->cut_pref[l] = cut_want[l];
   c->retiles++;
+  if (c->split_trace) fprintf(stderr, "orbx split: batch %lld re-tile %d\n", c->batch_serial, c->retiles);
   return true;
 }
 
@@ -726,14 +827,16 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
   if (w != c->learn_w || h != c->learn_h) {
     c->learn_w = w;
     c->learn_h = h;
-    for (int l = 0; l < ORBX_MAX_LEVELS; l++) c->need_cur[l] = c->need_prev[l] = 0, c->tile_h_pref[l] = 0;
+    for (int l = 0; l < ORBX_MAX_LEVELS; l++) c->need_cur[l] = c->need_prev[l] = 0, c->tile_h_pref[l] = c->cut_pref[l] = 0;
+    std::memset(c->fill_cur, 0, sizeof(c->fill_cur));
+    std::memset(c->fill_prev, 0, sizeof(c->fill_prev));
     for (int i = 2; i < ORBX_FEEDBACK_WORDS; i++) c->h_feedback[i] = 0;
     c->need_batches = 0;
     c->need_window = 2;
     c->retiles = 0;
   } else if (w == c->plan_w && h == c->plan_h) {
     bool any_pref = false;
-    for (int l = 0; l < ORBX_MAX_LEVELS; l++) any_pref |= c->tile_h_pref[l] != 0;
+    for (int l = 0; l < ORBX_MAX_LEVELS; l++) any_pref |= c->tile_h_pref[l] != 0 || c->cut_pref[l] != 0 || c->cut_force[l] != 0;
     // (a switch that takes the top-rows-first pipeline away, or brings it back, since the tables were built)
     if (adapt_tile_rows(c) || (any_pref && tile_prefs_apply(c) != c->prefs_applied)) c->plan_w = 0;
   }
@@ -972,6 +1075,7 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
 
   c->fast_impl = fast_impl_env();
   c->blur_impl = blur_impl_env();
+  first_split_env(c);
   st = build_plan(c->p, p->max_width, p->max_height, &c->plan_max, &why, c->fast_impl);
   if (st != ORBX_OK) {
     delete c;

@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256, 6) void k_fast3(const OrbxTileDesc* __restrict
   auto issue_rows = [&](const OrbxTileDesc& d, int f, uint2 (&v)[NP]) {
     const uint8_t* img = pyr + ((size_t)f * (size_t)frame_bytes + d.img_off);
     const int gx = min(max(d.tx * G::TW - 8 + 8 * fc, 0), d.pitch - 8);
-    const int gy0 = d.ty * d.f - R - 3 + fr0;
+    const int gy0 = (int)(d.pad & 0xffffu) - R - 3 + fr0;  // (pad: the unit's first row | rows << 16)
 #pragma unroll
     for (int k = 0; k < NP; k++) {
       const int gy = min(max(gy0 + RPP * k, 0), d.h - 1);
@@ -312,12 +312,13 @@ __global__ __launch_bounds__(256, 6) void k_fast3(const OrbxTileDesc* __restrict
     // everything about this tile in one 64-byte scalar load; the table is shared by all frames
     const OrbxTileDesc d = f3_tile(tiles, tile);
     const int w = d.w, h = d.h;
-    const int tx = d.tx, ty = d.ty;
+    const int tx = d.tx;
     // tile height of this level (<= G::TH; the host balances the tile rows of a level) and the rows
     // each walking thread then owns (K, or K-1 for the shorter tiles)
-    const int th = d.f;
+    // (the unit's own rows: the two tile rows of an unevenly cut first pass are not ty * f and f)
+    const int th = (int)(d.pad >> 16);
     const int keff = (th + 2 * R + G::NSEG - 1) / G::NSEG >= G::K ? G::K : G::K - 1;
-    const int x0 = tx * G::TW, y0 = ty * th;
+    const int x0 = tx * G::TW, y0 = (int)(d.pad & 0xffffu);
 
     // ---- phase 1: the tile's rows (requested during the previous tile) -> LDS; the score tile (with
     // its guard rows) is cleared
@@ -460,7 +461,7 @@ __global__ __launch_bounds__(256, 6) void k_fast3(const OrbxTileDesc* __restrict
     int t5 = tile;
     asm volatile("" : "+s"(t5));
     const OrbxTileDesc e = f3_tile(tiles, t5);
-    const int th5 = e.f, y05 = e.ty * th5, h5 = e.h;
+    const int th5 = (int)(e.pad >> 16), y05 = (int)(e.pad & 0xffffu), h5 = e.h;
     if (tid < 64) {
       static_assert(G::TH <= 64 && G::MASK_DW == 4, "one lane per tile row, two 64-bit words per row");
       int surv = 0;

@@ -66,7 +66,7 @@ __device__ __forceinline__ uint32_t f4_rowmask(int y0, int lo, int hi) {
 }
 
 // grid: one wave per (tile of the frame's band-major strip table, frame), the frame index fastest.
-// Table entry: l, tx = strip, ty = tile row, f = rows per tile row of the level, u0 = cap, u1 = mask words per
+// Table entry: l, tx = strip, ty = tile row, pad = first row | rows << 16 of the unit, u0 = cap, u1 = mask words per
 // row, u2 = strips of the level, stat_index, img_off, mask_off.
 template <int R, bool ZT>
 __global__ __launch_bounds__(64) void k_fast4(const OrbxTileDesc* __restrict__ tiles, int n_tiles, int n_frames,
@@ -95,8 +95,9 @@ __global__ __launch_bounds__(64) void k_fast4(const OrbxTileDesc* __restrict__ t
     const u64 pv = f3_probe_issue(st + d.stat_index, dead, d.ty, lane);
     if (f3_probe_decide(pv, dead, d.ty, d.u2, d.u0, lane)) return;
   }
-  const int w = d.w, h = d.h, pitch = d.pitch, th = d.f;
-  const int y0 = d.ty * th, y1 = min(y0 + th, h);
+  // the unit's own rows (the two tile rows of an unevenly cut first pass are not ty * f and f: build_fast_tiles)
+  const int w = d.w, h = d.h, pitch = d.pitch, th = (int)(d.pad >> 16);
+  const int y0 = (int)(d.pad & 0xffffu), y1 = min(y0 + th, h);
   const int thr = fp.threshold, narc_any = fp.n;
   const bool first = d.tx == 0, last = d.tx + 1 == d.u2;
   const int dw0 = d.tx * C::S;

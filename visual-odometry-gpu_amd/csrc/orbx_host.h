@@ -380,6 +380,13 @@ struct orbx_ctx {
   int tile_h_pref[ORBX_MAX_LEVELS] = {};
   int need_batches = 0, need_window = 2, retiles = 0, learn_w = 0, learn_h = 0;
   bool prefs_applied = false;  // the current tile tables were built with tile_h_pref
+  // unevenly cut first pass (adapt_tile_rows, orbx_plan.h: choose_first_cut): the frames of the current and of the
+  // previous observation window counted by the row their caps filled in, and the rows of tile row 0 chosen from them
+  // (0: equal halves).  Read when the context is created, from the fields behind ORBX_TOP_ROWS' number (orbx_api.cpp,
+  // first_split_env): equal halves only (A/B timing), the rows of tile row 0 forced per level (tests), a trace.
+  uint32_t fill_cur[ORBX_MAX_LEVELS][ORBX_FILL_BUCKETS] = {}, fill_prev[ORBX_MAX_LEVELS][ORBX_FILL_BUCKETS] = {};
+  int cut_pref[ORBX_MAX_LEVELS] = {}, cut_force[ORBX_MAX_LEVELS] = {};
+  bool first_split = true, split_trace = false;
   // ring of event sets: one per timed batched call, so that several calls can be
   // in flight before their stage times are read (no host sync between steps)
   orbx_host::TimingSet evr[ORBX_EVENT_SETS];

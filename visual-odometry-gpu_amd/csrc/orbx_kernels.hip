@@ -828,7 +828,12 @@ __global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(6, 
       // How many rows of the level did it take to fill the cap (all of them if it never filled)?  The maximum over
       // the batch's frames goes to the host, which sizes the first pass of the top-rows-first pipeline by it
       // (orbx_api.cpp, adapt_tile_rows): a heuristic's input, results never depend on it.
-      if (need && cap > 0) atomicMax(&need[l], (uint32_t)last_row + 1u);
+      // ... and the frames counted by that row, in buckets (orbx_plan.h, fill_bucket of last_row + 1): where to cut
+      // the first pass so that most frames' units of its second tile row exit
+      if (need && cap > 0) {
+        atomicMax(&need[l], (uint32_t)last_row + 1u);
+        atomicAdd(&need[ORBX_MAX_LEVELS + l * ORBX_FILL_BUCKETS + min(last_row / ORBX_FILL_BUCKET_ROWS, ORBX_FILL_BUCKETS - 1)], 1u);
+      }
     }
   }
   if (mode == ORBX_SELECT_ROWMAJOR) return;
@@ -1496,7 +1501,9 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
   // (last kernel of a batch: the running totals of the top-rows-first pipeline's second pass go to the host's pinned
   // word pair, which the host reads without waiting when it enqueues later batches -- a copy node less per batch)
   // (+ the rows-needed word of every level: k_level_select above)
-  if (feedback_host && grp == 0 && f == 0 && tid < ORBX_FEEDBACK_WORDS) feedback_host[tid] = feedback[tid];
+  // (+ the fill-row histograms: more words than the workgroup has threads)
+  if (feedback_host && grp == 0 && f == 0)
+    for (int i = tid; i < ORBX_FEEDBACK_WORDS; i += (int)blockDim.x) feedback_host[i] = feedback[i];
   const int slot0 = grp * DESC_KPB;
   if (slot0 >= count) return;  // whole workgroup
   DescLds2& lds = s_lds[wave];

@@ -62,6 +62,9 @@ struct OrbxTileMap {
 #define ORBX_MAX_BANDS 64
 // smallest FAST tile-row height the adaptive first pass may choose (orbx_api.cpp, adapt_tile_rows)
 #define ORBX_MIN_TILE_H 16
+// most rows a unit of the streaming FAST kernel may have: the tags of its score rows repeat after lcm(7 + 2 R, 16)
+// >= 144 rows (orbx_fast4.hip); a tile of the LDS tile kernel holds orbx_fast3_tile_h(R) rows
+#define ORBX_FAST_UNIT_ROWS_MAX 128
 struct OrbxBandMap {
   int32_t nbands;
   int32_t band_begin[ORBX_MAX_BANDS + 1];  // tiles PER FRAME before band b (+ total)
@@ -69,6 +72,9 @@ struct OrbxBandMap {
   int32_t tiles_y[ORBX_MAX_LEVELS];
   int32_t tile_h[ORBX_MAX_LEVELS];       // rows per FAST tile of the level (balanced: ceil(h / tiles_y))
   int32_t xprefix[ORBX_MAX_LEVELS + 1];  // prefix sums of tiles_x
+  // unevenly cut first pass (make_bandmap, first_h): rows of tile rows 0 and 1 of the level, together 2 * tile_h;
+  // {0, 0}: every tile row has tile_h rows
+  int32_t first_h[ORBX_MAX_LEVELS][2];
 };
 
 // One 64-byte record per workgroup, read with a single scalar load: everything a
@@ -77,7 +83,8 @@ struct OrbxBandMap {
 // start of every wave (~20 s_load round trips for the FAST kernel).
 //   FAST table   : one entry per (tile row, level, tx) of ONE frame in band-major order
 //                  (grid = frames x tiles, frame index dispatched fastest); `f` = rows per tile
-//                  of this level.
+//                  of this level, `pad` = the unit's own rows: first row | rows << 16 (the two
+//                  tile rows of an unevenly cut first pass differ from ty * f and f).
 //   pyramid      : one entry per (level, tx, ty) of ONE frame (blockIdx.y = frame); u0/u1/u2
 //                  carry xtab_off / ytab_off / win8 and `f` the rows per wave.
 //   blur         : one entry per (level, 256-px strip, row band): tx = strip, ty = first row,
@@ -93,7 +100,7 @@ struct OrbxTileDesc {
   int32_t u1;  // FAST: mask_wpr       pyramid: ytab_off
   int32_t u2;  // FAST: tiles_x        pyramid: win8
   uint32_t stat_index;  // FAST: first tile-row statistic of (frame, level)
-  uint32_t pad;
+  uint32_t pad;         // FAST: first row | rows << 16 of the unit   fused pyramid + blur: strips of the level
   uint64_t img_off;   // bytes from the pyramid base
   uint64_t mask_off;  // u64 words from the mask base (FAST)
 };
@@ -199,8 +206,13 @@ inline int fast_tiles_x(int w, int nms_radius, bool strips) {
 
 // band-major order of the FAST tiles (levels shrink with the level index, so the
 // levels that have a tile row b are always a prefix of the level list)
+// first_h[l] = {rows of tile row 0, rows of tile row 1}: the two tile rows of the first pass of the top-rows-first
+// pipeline cut UNEVENLY (adapt_tile_rows: tile row 0 ends where most frames have filled their cap, and the units of
+// the short tile row 1 exit for those frames).  The pair must keep the depth of the first pass, 2 * tile_h, so
+// that the tile rows below and their number stay what they are; a pair that does not, that leaves a unit more rows
+// than its kernel holds, or whose tile row 0 swallows the level is ignored (equal tile rows).
 inline int make_bandmap(const OrbxPlan& plan, int nms_radius, OrbxBandMap* bm, std::string* why, bool strips = false,
-                        const int* pref_h = nullptr) {
+                        const int* pref_h = nullptr, const int (*first_h)[2] = nullptr) {
   std::memset(bm, 0, sizeof(*bm));
   const int th = orbx_fast3_tile_h(nms_radius);
   int nb = 0;
@@ -217,6 +229,14 @@ inline int make_bandmap(const OrbxPlan& plan, int nms_radius, OrbxBandMap* bm, s
       if (hh < bm->tile_h[l]) {
         bm->tile_h[l] = hh;
         bm->tiles_y[l] = (plan.L[l].h + hh - 1) / hh;
+      }
+    }
+    if (first_h && first_h[l][0] > 0 && first_h[l][1] > 0) {
+      const int a = first_h[l][0], b = first_h[l][1];
+      const int unit_max = strips ? ORBX_FAST_UNIT_ROWS_MAX : th;
+      if (a + b == 2 * bm->tile_h[l] && bm->tiles_y[l] >= 2 && a < plan.L[l].h && a <= unit_max && b <= unit_max) {
+        bm->first_h[l][0] = a;
+        bm->first_h[l][1] = b;
       }
     }
     bm->xprefix[l + 1] = bm->xprefix[l] + bm->tiles_x[l];
@@ -241,6 +261,13 @@ inline int make_bandmap(const OrbxPlan& plan, int nms_radius, OrbxBandMap* bm, s
   return ORBX_OK;
 }
 
+// first row and rows of tile row b of a level (the last tile row may reach past the level's height: the kernels clip)
+inline void fast_band_rows(const OrbxBandMap& bm, int l, int b, int* y0, int* rows) {
+  const bool cut = bm.first_h[l][0] > 0 && b < 2;
+  *y0 = cut ? (b == 0 ? 0 : bm.first_h[l][0]) : b * bm.tile_h[l];
+  *rows = cut ? bm.first_h[l][b] : bm.tile_h[l];
+}
+
 // The table builders below return the number of entries and fill `out` unless it is NULL (count only).
 
 // FAST tiles of ONE frame in band-major order (the kernel's grid is frames x tiles with
@@ -254,12 +281,15 @@ inline size_t build_fast_tiles(const OrbxPlan& plan, const OrbxBandMap& bm, int 
     for (int l = 0; l < plan.nlevels; l++) {
       if (bm.tiles_y[l] <= b) continue;
       const OrbxLevel& L = plan.L[l];
+      int y0, rows;
+      fast_band_rows(bm, l, b, &y0, &rows);
       for (int tx = 0; tx < bm.tiles_x[l]; tx += strip) {
         OrbxTileDesc d{};
         d.l = l;
         d.tx = tx;
         d.ty = b;
         d.f = bm.tile_h[l];
+        d.pad = (uint32_t)y0 | ((uint32_t)rows << 16);
         d.w = L.w;
         d.h = L.h;
         d.pitch = L.pitch;
@@ -376,12 +406,14 @@ inline size_t blur_tiles_for_impl(int impl, const OrbxPlan& plan, std::vector<Or
 // strips of the fused pyramid + blur kernel for ONE frame: 248-px strips (the halo dwords are
 // computed by lanes 0 / 63) x balanced row bands, with the level's resize-table fields.
 // part 0: every row.  Top-rows-first pipeline (enqueue_batch): part 1 = the rows the FAST tiles of the
-// first `top_rows` tile rows and the descriptors of their keypoints can read -- rows below
-// top_rows * tile_h + ORBX_TOP_MARGIN -- and part 2 = the rest, whose strips carry what the kernel's skip
+// first `top_rows` tile rows and the descriptors of their keypoints can read -- the rows above the end of the
+// last of those tile rows + ORBX_TOP_MARGIN -- and part 2 = the rest, whose strips carry what the kernel's skip
 // test needs (stat_index, mask_off = tile rows of the first pass << 32 | cap).
 inline int pyrblur_first_pass_rows(const OrbxPlan& plan, const OrbxBandMap& bm, int l, int top_rows) {
   if (top_rows <= 0 || bm.tiles_y[l] <= top_rows) return plan.L[l].h;
-  return std::min(plan.L[l].h, top_rows * bm.tile_h[l] + ORBX_TOP_MARGIN);
+  int y0, rows;
+  fast_band_rows(bm, l, top_rows - 1, &y0, &rows);
+  return std::min(plan.L[l].h, y0 + rows + ORBX_TOP_MARGIN);
 }
 inline size_t build_pyrblur_tiles(const OrbxPlan& plan, int max_rows, std::vector<OrbxTileDesc>* out,
                                   bool heavy_first = false, int part = 0, const OrbxBandMap* bm = nullptr,
@@ -551,6 +583,67 @@ inline int table_capacity(const orbx_params& p, const OrbxPlan& M, int fast_impl
   cap->small = build_pyrblur_tiles(M, ORBX_PYRBLUR_RH_SMALL, nullptr) + 64;
   cap->taps = taps_count(M) + 16;
   return ORBX_OK;
+}
+
+// ---- where to cut the first pass of the FAST tile rows --------------------------------------------------------------
+// The selection kernel counts, per level, the frames by the row in which their cap filled ("fill row" F = row of the
+// cap-th survivor + 1; the level's height if it never filled) in buckets of ORBX_FILL_BUCKET_ROWS rows, the last
+// bucket open-ended.  A unit of tile row 1 exits when the rows strictly above it hold `cap` survivors, that is for
+// the frames with F <= rows of tile row 0.
+#define ORBX_FILL_BUCKETS 32
+#define ORBX_FILL_BUCKET_ROWS 4
+inline int fill_bucket(int fill_row) { return std::min(std::max(fill_row - 1, 0) / ORBX_FILL_BUCKET_ROWS, ORBX_FILL_BUCKETS - 1); }
+// frames known to have filled within the first `cut` rows: whole buckets only, so never a frame too many
+inline uint32_t fill_exits(const uint32_t* hist, int cut) {
+  uint32_t n = 0;
+  for (int b = 0; b < ORBX_FILL_BUCKETS - 1 && ORBX_FILL_BUCKET_ROWS * (b + 1) <= cut; b++) n += hist[b];
+  return n;
+}
+// What a unit of the streaming FAST kernel costs, in thousandths of a GROUP (7 centre rows: walk, candidate queue,
+// segment test, NMS and mask store, ~570 instructions on the benchmark stream): a unit of `rows` rows walks
+// ceil((rows + 2 R) / 7) groups after its set-up, and a unit that exits pays for its record and the probe.
+// Counted in the kernel's assembly (tools/isa_stats.py --blocks, R = 1): the blocks before the group loop -- tile
+// record, buffer descriptor, comparison table, clearing the score ring, the first 13 row loads, six rows into the
+// LDS ring -- and the statistics after it are ~690 instructions; entry, record and probe of an exiting unit ~160.
+#define ORBX_FAST4_UNIT_SETUP_MILLI 1200
+#define ORBX_FAST4_UNIT_EXIT_MILLI 280
+struct OrbxUnitCost {
+  int setup_milli, exit_milli;
+};
+inline int fast4_unit_cost_milli(int rows, int nms_radius, const OrbxUnitCost& uc) {
+  return uc.setup_milli + 1000 * ((rows + 2 * nms_radius + 6) / 7);
+}
+// expected cost of the first pass of one strip with tile row 0 of `cut` rows and tile row 1 of depth - cut
+inline int first_pass_cost_milli(const uint32_t* hist, int depth, int cut, int nms_radius,
+                                 const OrbxUnitCost& uc = OrbxUnitCost{ORBX_FAST4_UNIT_SETUP_MILLI, ORBX_FAST4_UNIT_EXIT_MILLI}) {
+  uint64_t total = 0;
+  for (int b = 0; b < ORBX_FILL_BUCKETS; b++) total += hist[b];
+  const uint64_t out = total ? fill_exits(hist, cut) : 0, on = total ? total - out : 1;
+  const uint64_t second = (on * (uint64_t)fast4_unit_cost_milli(depth - cut, nms_radius, uc) + out * (uint64_t)uc.exit_milli) /
+                          (total ? total : 1);
+  return fast4_unit_cost_milli(cut, nms_radius, uc) + (int)second;
+}
+// The rows of tile row 0 that make the first pass cheapest, among the cuts that end tile row 0 on a group boundary
+// ((cut + 2 R) a multiple of 7) and leave both units within unit_max rows; 0: equal halves (an empty histogram, or
+// no cut is cheaper than they are).  *cost_milli: the expected cost of what is returned.
+inline int choose_first_cut(const uint32_t* hist, int depth, int nms_radius, int unit_max, int* cost_milli,
+                            const OrbxUnitCost& uc = OrbxUnitCost{ORBX_FAST4_UNIT_SETUP_MILLI, ORBX_FAST4_UNIT_EXIT_MILLI}) {
+  uint64_t total = 0;
+  for (int b = 0; b < ORBX_FILL_BUCKETS; b++) total += hist[b];
+  int best = 0, best_cost = first_pass_cost_milli(hist, depth, depth / 2, nms_radius, uc);
+  if (total)
+    for (int cut = 7 - (2 * nms_radius) % 7; cut < depth; cut += 7) {
+      if (cut > unit_max || depth - cut > unit_max || cut == depth / 2) continue;
+      // (a cut at which no frame exits only re-partitions the rows: whole groups are adapt_tile_rows' business)
+      if (fill_exits(hist, cut) == 0) continue;
+      const int c = first_pass_cost_milli(hist, depth, cut, nms_radius, uc);
+      if (c < best_cost) {
+        best = cut;
+        best_cost = c;
+      }
+    }
+  if (cost_milli) *cost_milli = best_cost;
+  return best;
 }
 
 }  // namespace orbx_geom
