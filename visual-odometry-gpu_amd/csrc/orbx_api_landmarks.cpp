@@ -1,7 +1,9 @@
 // orbx_api_landmarks.cpp -- host layer of liborbx.so (orbx_host.h): landmarks of tracked windows built on the device
 // and their bundle adjustment on that block.
 // buildLandmarksFromFirstTwoFramesAndTracks (src/with_bundle_adjustment.cpp:502-575) and the solve of the window
-// (src/with_bundle_adjustment.cpp:612-720) for many windows per call.
+// (src/with_bundle_adjustment.cpp:612-720) for many windows per call.  The build behind orbx_landmarks_build_device
+// (poses from the host) is also the build behind orbx_landmarks_build_chained_device (orbx_api_wposes.cpp: poses from
+// the window-poses block on the device, rank 14).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -34,18 +36,23 @@ int lm_check_range(orbx_ctx* c, int first, int n) {
   return ORBX_OK;
 }
 
+}  // namespace
+
+namespace orbx_host {
+
 bool ba_params_ok(double huber_delta, int max_iters) {
   return huber_delta > 0.0 && std::isfinite(huber_delta) && max_iters >= 1 && max_iters <= 1000;
 }
 
 // enqueues the three kernels on s; arguments are checked
 int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
-           const double* poses6, hipStream_t s) {
+           const double* poses6, const double* d_poses6, const int32_t* d_pose_status, hipStream_t s) {
   int st = c->lm.side.enter(c, s);
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->lm.side, s};
-  // the tracks may be the windows tracker's block, written on another stream
+  // the tracks may be the windows tracker's block, written on another stream; so may the chained poses
   if ((st = c->lm.side.after(c, c->lkw.side, s)) != ORBX_OK) return st;
+  if (!poses6 && (st = c->lm.side.after(c, c->wp.side, s)) != ORBX_OK) return st;
   const LmBlock B(n, cap, len);
   const LmScratch S(n, cap, len);
   if ((st = c->lm.side.grow(c, c->lm.scr, S.bytes)) != ORBX_OK) return st;
@@ -54,11 +61,16 @@ int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d
   c->lm.n = 0;
   c->lm.solved = false;
   uint8_t* scr = (uint8_t*)c->lm.scr.p;
-  st = c->lm.poses_up.send(c, scr + S.poses, poses6, sizeof(double) * 6 * (size_t)n * len, s);
-  if (st != ORBX_OK) return st;
+  const size_t pose_bytes = sizeof(double) * 6 * (size_t)n * len;
+  if (poses6) {
+    if ((st = c->lm.poses_up.send(c, scr + S.poses, poses6, pose_bytes, s)) != ORBX_OK) return st;
+  } else {
+    // the solve and the write-back gate read the block as built from here, whatever the next chain writes
+    HIPCHK(c, hipMemcpyAsync(scr + S.poses, d_poses6, pose_bytes, hipMemcpyDeviceToDevice, s));
+  }
   HIPCHK(c, orbx_launch_landmarks(s, K, (const double*)(scr + S.poses), d_tracks, d_seen, n, cap, len,
                                   (double*)(scr + S.cand), scr + S.keep, (int32_t*)(scr + S.partial),
-                                  (int32_t*)(scr + S.gate), lm_pointers(c, B)));
+                                  (int32_t*)(scr + S.gate), lm_pointers(c, B), poses6 ? nullptr : d_pose_status));
   std::memcpy(c->lm.K, K, sizeof c->lm.K);
   c->lm.n = n;
   c->lm.cap = cap;
@@ -68,7 +80,7 @@ int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d
 
 int lm_check_build(orbx_ctx* c, const double* K, const void* tracks, const void* seen, int n, int cap, int len,
                    const double* poses6) {
-  if (!K || !tracks || !seen || !poses6) return fail(c, ORBX_ERR_INVALID_ARG, "K, tracks, seen or poses6 is NULL");
+  if (!K || !tracks || !seen) return fail(c, ORBX_ERR_INVALID_ARG, "K, tracks, seen or poses6 is NULL");
   if (n < 1 || cap < 1 || len < 2 || len > ORBX_BA_MAX_POSES)
     return fail(c, ORBX_ERR_INVALID_ARG, "n_windows < 1, slot_capacity < 1 or window_len outside [2, 8]");
   if (cap > ORBX_BA_MAX_POINTS) return fail(c, ORBX_ERR_UNSUPPORTED, "more slots in a window than 65536");
@@ -76,12 +88,12 @@ int lm_check_build(orbx_ctx* c, const double* K, const void* tracks, const void*
       (unsigned long long)n * cap * len > 0x7fffffffull)
     return fail(c, ORBX_ERR_UNSUPPORTED, "more landmarks or observations in a batch than 32-bit offsets hold");
   if (!finite_all(K, 9)) return fail(c, ORBX_ERR_INVALID_ARG, "K is not finite");
-  for (size_t i = 0; i < 6 * (size_t)n * len; i++)
+  for (size_t i = 0; poses6 && i < 6 * (size_t)n * len; i++)
     if (!std::isfinite(poses6[i])) return fail(c, ORBX_ERR_INVALID_ARG, "a pose is not finite");
   return ORBX_OK;
 }
 
-}  // namespace
+}  // namespace orbx_host
 
 extern "C" {
 
@@ -89,9 +101,11 @@ int orbx_landmarks_build_device(orbx_ctx* c, const double* K, const float* d_tra
                                 int n_windows, int slot_capacity, int window_len, const double* poses6, void* stream) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!poses6) return fail(c, ORBX_ERR_INVALID_ARG, "K, tracks, seen or poses6 is NULL");
   const int st = lm_check_build(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, poses6);
   if (st != ORBX_OK) return st;
-  return lm_run(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, poses6, stream_of(c, stream));
+  return lm_run(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, poses6, nullptr, nullptr,
+                stream_of(c, stream));
 }
 
 int orbx_landmarks_results_device(orbx_ctx* c, orbx_landmarks_view* v) {
@@ -234,6 +248,7 @@ int orbx_bundle_adjust_tracks(orbx_ctx* c, const double* K, const float* tracks_
                               int* count) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
+  if (!poses6) return fail(c, ORBX_ERR_INVALID_ARG, "K, tracks, seen or poses6 is NULL");
   int st = lm_check_build(c, K, tracks_xy, seen, 1, n_slots, window_len, poses6);
   if (st != ORBX_OK) return st;
   if (!ba_params_ok(huber_delta, max_iters) || !lm_status || !summary || capacity < 0)
@@ -242,7 +257,8 @@ int orbx_bundle_adjust_tracks(orbx_ctx* c, const double* K, const float* tracks_
   const int32_t* d_seen;
   if ((st = stage_tracks(c, c->lm.side, c->lm.stage, tracks_xy, seen, n_slots, window_len, &d_tracks, &d_seen)) != ORBX_OK)
     return st;
-  if ((st = lm_run(c, K, d_tracks, d_seen, 1, n_slots, window_len, poses6, c->stream)) != ORBX_OK) return st;
+  if ((st = lm_run(c, K, d_tracks, d_seen, 1, n_slots, window_len, poses6, nullptr, nullptr, c->stream)) != ORBX_OK)
+    return st;
   if ((st = orbx_bundle_adjust_landmarks_device(c, huber_delta, max_iters, nullptr)) != ORBX_OK) return st;
   int np = 0;
   if ((st = orbx_bundle_adjust_landmarks_fetch(c, 0, 1, nullptr, nullptr, nullptr, 0, &np)) != ORBX_OK) return st;

@@ -106,9 +106,9 @@ int fail(orbx_ctx* c, int status, const std::string& msg);  // (c == NULL: the t
   } while (0)
 
 // Work that runs beside the batched path on ANY caller's stream, with one workspace and one result block per context
-// (good features, LK windows, landmarks, tracks pose).  `stream` is the stream the last call ran on, kept for
-// COMPARISON only (a caller's stream may be gone by the next call); `ev` is recorded behind that call's work: what
-// later calls, fetches and orbx_destroy wait for.
+// (good features, LK windows, landmarks, tracks pose, window poses).  `stream` is the stream the last call ran on,
+// kept for COMPARISON only (a caller's stream may be gone by the next call); `ev` is recorded behind that call's
+// work: what later calls, fetches and orbx_destroy wait for.
 struct SideWork {
   hipStream_t stream = nullptr;
   hipEvent_t ev = nullptr;
@@ -152,7 +152,7 @@ struct PinnedUpload {
   }
 };
 
-// ---- the context's parts, one per subsystem (orbx_ctx::s, m, lk, lkw, pose, scale, ba, gf, lm, tp) ----
+// ---- the context's parts, one per subsystem (orbx_ctx::s, m, lk, lkw, pose, scale, ba, gf, lm, tp, wp) ----
 
 // stage-API scratch (grown on demand; never touched by the batched path)
 struct StageScratch {
@@ -263,6 +263,23 @@ struct TracksPose {
   }
 };
 
+// window poses chained from the tracks-pose block and the write-back gate behind a solve (orbx_wposes.hip): what goes
+// up with a chain (WpInput of orbx_layout.h), the chain's OWN result block (WpBlock), the gate's OWN result block
+// (WbBlock), and the staged tracks of the one-window host entry.  The chain reads tp.blk, the gate reads lm.scr and
+// lm.sol, and the chained landmarks build reads blk; none of them writes there.
+struct WindowPoses {
+  DevBuf in, blk, wb, stage;
+  int n = 0, len = 0;        // windows and frames per window of the last chain (0: none)
+  int wb_n = 0, wb_len = 0;  // the same of the last write-back
+  SideWork side;             // the event is recorded behind every chain and every write-back
+  PinnedUpload up;           // T0 | scale0 on their way up
+  void release() {
+    side.release();
+    up.release();
+    free_bufs({&in, &blk, &wb, &stage});
+  }
+};
+
 // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames, allocated on first use and bounded by
 // ws_limit; the staged host image of the one-frame entries; and the entry's OWN result block, untouched by the ORB
 // path.  Rank 12 (top-up and masked detection) adds, beside the workspace and for the same number of frames, the bit
@@ -346,8 +363,9 @@ struct orbx_ctx {
   long long batch_serial = 0;  // bumped by every batch run
   // The subsystems beside the batched path, each with what it owns.  They meet in five places, visible where the
   // calls are made: pose reads the matcher's table, scale checks pose.match_gen against m.gen, the windows
-  // tracker waits for the good-features event, and the landmarks build and the tracks pose wait for the windows
-  // tracker's.
+  // tracker waits for the good-features event, the landmarks build and the tracks pose wait for the windows
+  // tracker's, the window poses wait for the tracks pose's, the chained landmarks build for the window poses', and
+  // the write-back gate for the solve's.
   orbx_host::StageScratch s;
   orbx_host::Matcher m;
   orbx_host::LkPair lk;
@@ -358,6 +376,7 @@ struct orbx_ctx {
   orbx_host::GoodFeatures gf;
   orbx_host::Landmarks lm;
   orbx_host::TracksPose tp;
+  orbx_host::WindowPoses wp;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -476,5 +495,14 @@ inline bool range_ok(int first, int n, int total, int n_min = 1) {
 // one window's tracks | seen from host arrays into `stage`, on the context's stream (the one-window host entries)
 int stage_tracks(orbx_ctx* c, SideWork& side, DevBuf& stage, const float* tracks_xy, const int32_t* seen, int n_slots,
                  int window_len, const float** d_tracks, const int32_t** d_seen);
+// the landmarks build behind its two entries (orbx_api_landmarks.cpp).  lm_check_build: the argument rules; the poses
+// are checked when they come from the host (poses6 != NULL).  lm_run enqueues the build on s with the poses from the
+// host (poses6, through the pinned mirror) or from the window-poses block (poses6 == NULL: d_poses6 and d_pose_status,
+// copied on s behind that block's event)
+bool ba_params_ok(double huber_delta, int max_iters);
+int lm_check_build(orbx_ctx* c, const double* K, const void* tracks, const void* seen, int n, int cap, int len,
+                   const double* poses6);
+int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
+           const double* poses6, const double* d_poses6, const int32_t* d_pose_status, hipStream_t s);
 
 }  // namespace orbx_host

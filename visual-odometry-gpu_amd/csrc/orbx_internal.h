@@ -237,10 +237,25 @@ struct OrbxLmBlock {
 // workgroups of k_lm_triangulate per window = rows of its table of partial counts
 inline int orbx_lm_blocks(int cap) { return (cap + ORBX_LM_THREADS - 1) / ORBX_LM_THREADS; }
 // K9: row-major 3x3 (host); d_poses: 6 * window_len doubles per window; d_tracks / d_seen: the layout of
-// orbx_lk_windows_view; d_cand: 3 rows of n * cap doubles; d_keep: n * cap bytes; d_partial: 2 * n * blocks; d_gate: n
+// orbx_lk_windows_view; d_cand: 3 rows of n * cap doubles; d_keep: n * cap bytes; d_partial: 2 * n * blocks; d_gate: n;
+// d_pose_status: NULL, or the status per window of poses chained on the device (orbx_launch_window_poses): a window
+// that is not 0 there is ORBX_LM_BAD_POSE
 hipError_t orbx_launch_landmarks(hipStream_t s, const double* K9, const double* d_poses, const float* d_tracks,
                                  const int32_t* d_seen, int n_windows, int cap, int window_len, double* d_cand,
-                                 uint8_t* d_keep, int32_t* d_partial, int32_t* d_gate, const OrbxLmBlock& out);
+                                 uint8_t* d_keep, int32_t* d_partial, int32_t* d_gate, const OrbxLmBlock& out,
+                                 const int32_t* d_pose_status = nullptr);
+
+// ---- window poses and the write-back gate (orbx_wposes.hip) ---------------------------------
+// d_pose / d_scale: the tracks-pose block's rows, window w's pairs at w * (window_len - 1); d_T0: 16 doubles and
+// d_scale0: one per window; d_poses6 / d_poses4x4: 6 / 16 doubles per frame, window-major; d_status: one per window
+hipError_t orbx_launch_window_poses(hipStream_t s, int n_windows, int window_len, const OrbxPoseOut* d_pose,
+                                    const OrbxScaleOut* d_scale, const double* d_T0, const double* d_scale0,
+                                    double* d_poses6, double* d_poses4x4, int32_t* d_status);
+// d_solved6 / d_built6: the blocks after the solve and as built; d_summaries: one orbx_ba_summary per window;
+// d_poses4x4: 16 doubles and d_updated: one byte per (window, pose)
+hipError_t orbx_launch_ba_write_back(hipStream_t s, int n_windows, int window_len, const double* d_solved6,
+                                     const double* d_built6, const void* d_summaries, double max_rot,
+                                     double max_trans, double* d_poses4x4, uint8_t* d_updated);
 
 // ---- pose and scale of tracked frame pairs (orbx_tracks.hip) --------------------------------
 // Window w of window_len frames owns window_len - 1 pairs, pair p = w * (window_len - 1) + k is frames k, k + 1.

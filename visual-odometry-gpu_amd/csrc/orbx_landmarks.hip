@@ -53,7 +53,8 @@ __global__ __launch_bounds__(LM_THREADS) void k_lm_triangulate(LmK9 K, const dou
                                                                int window_len, int nblk, size_t total,
                                                                double* __restrict__ cand, uint8_t* __restrict__ keep,
                                                                int32_t* __restrict__ partial,
-                                                               int32_t* __restrict__ gate) {
+                                                               int32_t* __restrict__ gate,
+                                                               const int32_t* __restrict__ pose_status) {
   __shared__ LmWaves S;
   const int tid = threadIdx.x;
   const int win = blockIdx.x / nblk, blk = blockIdx.x % nblk;
@@ -62,7 +63,9 @@ __global__ __launch_bounds__(LM_THREADS) void k_lm_triangulate(LmK9 K, const dou
   // rules 1-2: the same for every lane of the window
   const double* pose = poses + 6 * (size_t)window_len * win;
   double P0[12], P1[12];
-  const int status = lm_window_prepare(K.k, pose, pose + 6, P0, P1);
+  int status = lm_window_prepare(K.k, pose, pose + 6, P0, P1);
+  // poses chained on the device (rank 14): a window whose chain is not finite is a bad pose and owns no landmark
+  if (pose_status && pose_status[win] != 0) status = LM_BAD_POSE;
   double X[3] = {0.0, 0.0, 0.0};
   bool kept = false;
   int obs = 0;
@@ -181,7 +184,8 @@ __global__ __launch_bounds__(LM_THREADS) void k_lm_fill(const float* __restrict_
 
 hipError_t orbx_launch_landmarks(hipStream_t s, const double* K9, const double* d_poses, const float* d_tracks,
                                  const int32_t* d_seen, int n_windows, int cap, int window_len, double* d_cand,
-                                 uint8_t* d_keep, int32_t* d_partial, int32_t* d_gate, const OrbxLmBlock& out) {
+                                 uint8_t* d_keep, int32_t* d_partial, int32_t* d_gate, const OrbxLmBlock& out,
+                                 const int32_t* d_pose_status) {
   if (n_windows < 1 || cap < 1 || cap > ORBX_BA_MAX_POINTS || window_len < 2 || window_len > ORBX_BA_MAX_POSES)
     return hipErrorInvalidValue;
   const int nblk = orbx_lm_blocks(cap);
@@ -190,7 +194,7 @@ hipError_t orbx_launch_landmarks(hipStream_t s, const double* K9, const double* 
   LmK9 K;
   for (int i = 0; i < 9; i++) K.k[i] = K9[i];
   hipLaunchKernelGGL(k_lm_triangulate, dim3((unsigned)(n_windows * nblk)), dim3(LM_THREADS), 0, s, K, d_poses,
-                     d_tracks, d_seen, cap, window_len, nblk, total, d_cand, d_keep, d_partial, d_gate);
+                     d_tracks, d_seen, cap, window_len, nblk, total, d_cand, d_keep, d_partial, d_gate, d_pose_status);
   hipLaunchKernelGGL(k_lm_offsets, dim3(1), dim3(LM_THREADS), 0, s, n_windows, window_len, nblk, d_partial, d_gate,
                      out.status, out.pose_off, out.pt_off, out.obs_off);
   hipLaunchKernelGGL(k_lm_fill, dim3((unsigned)n_windows), dim3(LM_THREADS), 0, s, d_tracks, d_seen, cap, window_len,

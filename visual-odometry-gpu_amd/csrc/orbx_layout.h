@@ -227,6 +227,25 @@ inline size_t tp_scratch_bytes(int n_windows, int cap, int len) {
   return sizeof(OrbxPosePt) * (size_t)n_windows * (len - 1) * cap;
 }
 
+// ---- the poses of n tracked windows of len frames, chained on the device, and the write-back gate ----
+// what goes up with a chain: T0 (16 doubles per window) | scale0 (one per window)
+struct WpInput : private Sections {
+  size_t T0, scale0, bytes;
+  explicit WpInput(size_t n) : T0(take(sizeof(double) * 16 * n)), scale0(take(sizeof(double) * n)), bytes(end) {}
+};
+// the chain's result block: poses6 | poses4x4 | status
+struct WpBlock : private Sections {
+  size_t poses6, poses4x4, status, bytes;
+  WpBlock(size_t n, size_t len)
+      : poses6(take(sizeof(double) * 6 * n * len)), poses4x4(take(sizeof(double) * 16 * n * len)),
+        status(take(sizeof(int32_t) * n)), bytes(off) {}
+};
+// the gate's result block: poses4x4 | updated (one byte per pose)
+struct WbBlock : private Sections {
+  size_t poses4x4, updated, bytes;
+  WbBlock(size_t n, size_t len) : poses4x4(take(sizeof(double) * 16 * n * len)), updated(take(n * len)), bytes(off) {}
+};
+
 // ---- the descriptor matcher, and pose and scale of the frame pairs of a batch ----
 // one row of `cap` per pair in every per-slot array (e = pairs * cap slots).  The host-array entries use the same
 // blocks with one pair: MatchBlock(1, nq), PoseBlock(1, max(n, 1)).

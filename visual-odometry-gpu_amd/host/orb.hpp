@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "../../include/orbx_vo.h"
 
 #ifdef ORBX_WITH_OPENCV
 #include <opencv2/core.hpp>
@@ -1196,6 +1197,65 @@ inline bool run_bundle_adjustment_on_tracks(std::vector<Pose4x4>& pose_window, c
   if (s.termination != ORBX_BA_CONVERGENCE) return true;  // :683
   detail::ba_write_back(pose_window, poses, old, updated);
   return true;
+}
+
+// ---- window poses and the gated window ------------------------------
+// The poses of one window from its pair motions (src/with_bundle_adjustment.cpp:196-208): pose_window[0] = pose0,
+// pose_window[k + 1] = pose_window[k] * [R_k | s_k t_k]^-1 with s_0 = scale0 and the motions' own scale after; blocks
+// receives the world -> camera 6-double block of every pose (:615-628).  orbx_chain_window_poses: the arithmetic the
+// device chain runs, from the same source.
+inline std::vector<Pose4x4> chain_window_poses(const Pose4x4& pose0, const std::vector<PairMotion>& motions,
+                                               double scale0 = 1.0,
+                                               std::vector<std::array<double, 6>>* blocks = nullptr) {
+  const size_t n = motions.size();
+  std::vector<double> R(9 * n), t(3 * n), s(n);
+  for (size_t k = 0; k < n; k++) {
+    std::memcpy(&R[9 * k], motions[k].R, sizeof motions[k].R);
+    std::memcpy(&t[3 * k], motions[k].t, sizeof motions[k].t);
+    s[k] = k == 0 ? scale0 : motions[k].scale;
+  }
+  std::vector<Pose4x4> poses(n + 1);
+  std::vector<std::array<double, 6>> b6(n + 1);
+  static_assert(sizeof(Pose4x4) == 16 * sizeof(double) && sizeof(std::array<double, 6>) == 6 * sizeof(double), "layout");
+  detail::check(nullptr,
+                orbx_chain_window_poses(pose0.data(), R.data(), t.data(), s.data(), (int)n, poses[0].data(), b6[0].data()),
+                "orbx_chain_window_poses");
+  if (blocks) *blocks = std::move(b6);
+  return poses;
+}
+
+struct WindowOdometry {
+  std::vector<Pose4x4> pose_window;  // camera -> world, after the write-back gate
+  std::vector<uint8_t> updated;      // pose i was written back
+  int32_t wp_status = ORBX_WP_OK, lm_status = ORBX_LM_OK;
+  orbx_ba_summary summary{};
+};
+// One window from what LKTracker::trackWindow returns to the gated pose_window, everything between on the device
+// (src/with_bundle_adjustment.cpp:180-208, :502-575, :612-720): pose and scale of every pair, the chain from pose0,
+// landmarks, the solve and the write-back gate, through orbx_window_odometry_tracks.  xy: n x n_frames points,
+// seen: n.  run_bundle_adjustment_on_tracks is the same window with the poses given.
+inline WindowOdometry run_window_odometry_on_tracks(const Pose4x4& pose0, const double K[9],
+                                                    const std::vector<Point2f>& xy, const std::vector<int32_t>& seen,
+                                                    int n_frames, double scale0 = 1.0, double prob = 0.999,
+                                                    double threshold = 1.0, int pose_max_iters = 1000,
+                                                    uint64_t seed = 0, double huber_delta = 1.0, int ba_max_iters = 200,
+                                                    double max_rot = 0.5, double max_trans = 50.0) {
+  static_assert(sizeof(Point2f) == 2 * sizeof(float), "point layout");
+  if (n_frames < 2) throw std::invalid_argument("run_window_odometry_on_tracks: a window has at least two frames");
+  if (seen.empty() || xy.size() != seen.size() * (size_t)n_frames)
+    throw std::invalid_argument("run_window_odometry_on_tracks: xy is not n x n_frames");
+  WindowOdometry out;
+  out.pose_window.resize((size_t)n_frames);
+  out.updated.assign((size_t)n_frames, 0);
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_window_odometry_tracks(c, K, reinterpret_cast<const float*>(xy.data()), seen.data(),
+                                            (int)seen.size(), n_frames, pose0.data(), scale0, prob, threshold,
+                                            pose_max_iters, seed, huber_delta, ba_max_iters, max_rot, max_trans,
+                                            out.pose_window[0].data(), out.updated.data(), &out.wp_status,
+                                            &out.lm_status, &out.summary),
+                "orbx_window_odometry_tracks");
+  return out;
 }
 
 // ---- Shi-Tomasi corners (next row) ----------------------------------
