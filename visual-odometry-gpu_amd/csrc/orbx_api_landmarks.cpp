@@ -1,5 +1,6 @@
 // orbx_api_landmarks.cpp -- host layer of liborbx.so (orbx_host.h): landmarks of tracked windows built on the device
-// and their bundle adjustment on that block.
+// and their bundle adjustment on that block, and the entries of include/orbx_lm.h: the same
+// block built from every view of a track, with a reprojection gate and per-slot diagnostics (rank 15).
 // buildLandmarksFromFirstTwoFramesAndTracks (src/with_bundle_adjustment.cpp:502-575) and the solve of the window
 // (src/with_bundle_adjustment.cpp:612-720) for many windows per call.  The build behind orbx_landmarks_build_device
 // (poses from the host) is also the build behind orbx_landmarks_build_chained_device (orbx_api_wposes.cpp: poses from
@@ -8,9 +9,15 @@
 #include <cmath>
 #include <cstring>
 
+#include "../../include/orbx_lm.h"
 #include "orbx_host.h"
+#include "orbx_lm_math.h"
 
 using namespace orbx_host;
+
+static_assert((int)ORBX_LM_TRI_FIRST_TWO == (int)LM_TRI_FIRST_TWO && (int)ORBX_LM_TRI_ALL_VIEWS == (int)LM_TRI_ALL_VIEWS,
+              "orbx_lm_tri_mode");
+static_assert((int)ORBX_LM_KEPT == (int)LM_KEPT && (int)ORBX_LM_NO_WINDOW == (int)LM_NO_WINDOW, "orbx_lm_reason");
 
 namespace {
 
@@ -36,17 +43,76 @@ int lm_check_range(orbx_ctx* c, int first, int n) {
   return ORBX_OK;
 }
 
+int lm_check_views(orbx_ctx* c, int first, int n) {
+  if (c->lm.n < 1 || !c->lm.has_views)
+    return fail(c, ORBX_ERR_INVALID_ARG, "the last landmarks build was not a views build");
+  if (!range_ok(first, n, c->lm.n))
+    return fail(c, ORBX_ERR_INVALID_ARG, "[first, first + n) outside the landmarks block");
+  return ORBX_OK;
+}
+
+// the pose source of a views build: the host's poses6, or the last window-poses block (poses6 == NULL)
+int lm_build_views(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
+                   const double* poses6, const LmViewsOptions& o, hipStream_t s) {
+  const int st = lm_check_build(c, K, d_tracks, d_seen, n, cap, len, poses6);
+  if (st != ORBX_OK) return st;
+  if (!lm_views_ok(o))
+    return fail(c, ORBX_ERR_INVALID_ARG, "tri_mode outside 0..2, or max_reproj_px negative or not finite");
+  if (poses6) return lm_run(c, K, d_tracks, d_seen, n, cap, len, poses6, nullptr, nullptr, s, &o);
+  if (c->wp.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no window poses have been chained");
+  if (n != c->wp.n || len != c->wp.len)
+    return fail(c, ORBX_ERR_INVALID_ARG, "n_windows or window_len differs from the window-poses block");
+  const WpBlock B((size_t)c->wp.n, (size_t)c->wp.len);
+  return lm_run(c, K, d_tracks, d_seen, n, cap, len, nullptr, at<const double>(c->wp.blk, B.poses6),
+                at<const int32_t>(c->wp.blk, B.status), s, &o);
+}
+
+// one window of host tracks through a build (views: NULL for rank 10's) and the solve
+int lm_tracks(orbx_ctx* c, const double* K, const float* tracks_xy, const int32_t* seen, int n_slots, int window_len,
+              double* poses6, double huber_delta, int max_iters, int32_t* lm_status, orbx_ba_summary* summary,
+              double* points3, int32_t* slot_of_point, int capacity, int* count, const LmViewsOptions* views) {
+  if (!poses6) return fail(c, ORBX_ERR_INVALID_ARG, "K, tracks, seen or poses6 is NULL");
+  int st = lm_check_build(c, K, tracks_xy, seen, 1, n_slots, window_len, poses6);
+  if (st != ORBX_OK) return st;
+  if (views && !lm_views_ok(*views))
+    return fail(c, ORBX_ERR_INVALID_ARG, "tri_mode outside 0..2, or max_reproj_px negative or not finite");
+  if (!ba_params_ok(huber_delta, max_iters) || !lm_status || !summary || capacity < 0)
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  const float* d_tracks;
+  const int32_t* d_seen;
+  if ((st = stage_tracks(c, c->lm.side, c->lm.stage, tracks_xy, seen, n_slots, window_len, &d_tracks, &d_seen)) != ORBX_OK)
+    return st;
+  if ((st = lm_run(c, K, d_tracks, d_seen, 1, n_slots, window_len, poses6, nullptr, nullptr, c->stream, views)) != ORBX_OK)
+    return st;
+  if ((st = orbx_bundle_adjust_landmarks_device(c, huber_delta, max_iters, nullptr)) != ORBX_OK) return st;
+  int np = 0;
+  if ((st = orbx_bundle_adjust_landmarks_fetch(c, 0, 1, nullptr, nullptr, nullptr, 0, &np)) != ORBX_OK) return st;
+  if (count) *count = np;
+  if ((points3 || slot_of_point) && np > capacity)
+    return fail(c, ORBX_ERR_CAPACITY, "bundle_adjust_tracks: capacity is too small");
+  if ((st = orbx_landmarks_fetch(c, 0, 1, lm_status, nullptr, nullptr, nullptr, nullptr, slot_of_point, capacity,
+                                 nullptr, nullptr, nullptr, 0, nullptr, nullptr)) != ORBX_OK)
+    return st;
+  return orbx_bundle_adjust_landmarks_fetch(c, 0, 1, poses6, summary, points3, capacity, nullptr);
+}
+
 }  // namespace
 
 namespace orbx_host {
+
+bool lm_views_ok(const LmViewsOptions& o) {
+  return o.tri_mode >= LM_TRI_FIRST_TWO && o.tri_mode <= LM_TRI_ALL_VIEWS && o.max_reproj_px >= 0.0 &&
+         std::isfinite(o.max_reproj_px);
+}
 
 bool ba_params_ok(double huber_delta, int max_iters) {
   return huber_delta > 0.0 && std::isfinite(huber_delta) && max_iters >= 1 && max_iters <= 1000;
 }
 
-// enqueues the three kernels on s; arguments are checked
+// enqueues the kernels of a build on s (views: those of rank 15, with its options); arguments are checked
 int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
-           const double* poses6, const double* d_poses6, const int32_t* d_pose_status, hipStream_t s) {
+           const double* poses6, const double* d_poses6, const int32_t* d_pose_status, hipStream_t s,
+           const LmViewsOptions* views) {
   int st = c->lm.side.enter(c, s);
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->lm.side, s};
@@ -56,10 +122,14 @@ int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d
   const LmBlock B(n, cap, len);
   const LmScratch S(n, cap, len);
   if ((st = c->lm.side.grow(c, c->lm.scr, S.bytes)) != ORBX_OK) return st;
+  const LmViews V(n, cap, len);
+  if (views && (st = c->lm.side.grow(c, c->lm.views, V.bytes)) != ORBX_OK) return st;
   if ((st = c->lm.side.grow(c, c->lm.blk, B.bytes)) != ORBX_OK) return st;
-  // from here on the previous block is being replaced (a larger one has already taken its place)
+  // from here on the previous block is being replaced (a larger one has already taken its place), and with it the
+  // diagnostics of a views build
   c->lm.n = 0;
   c->lm.solved = false;
+  c->lm.has_views = false;
   uint8_t* scr = (uint8_t*)c->lm.scr.p;
   const size_t pose_bytes = sizeof(double) * 6 * (size_t)n * len;
   if (poses6) {
@@ -68,10 +138,19 @@ int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d
     // the solve and the write-back gate read the block as built from here, whatever the next chain writes
     HIPCHK(c, hipMemcpyAsync(scr + S.poses, d_poses6, pose_bytes, hipMemcpyDeviceToDevice, s));
   }
-  HIPCHK(c, orbx_launch_landmarks(s, K, (const double*)(scr + S.poses), d_tracks, d_seen, n, cap, len,
-                                  (double*)(scr + S.cand), scr + S.keep, (int32_t*)(scr + S.partial),
-                                  (int32_t*)(scr + S.gate), lm_pointers(c, B), poses6 ? nullptr : d_pose_status));
+  const int32_t* pose_status = poses6 ? nullptr : d_pose_status;
+  if (views)
+    HIPCHK(c, orbx_launch_landmarks_views(s, K, (const double*)(scr + S.poses), d_tracks, d_seen, n, cap, len,
+                                          views->tri_mode, views->max_reproj_px, at<double>(c->lm.views, V.table),
+                                          at<uint8_t>(c->lm.views, V.reason), at<float>(c->lm.views, V.reproj_px),
+                                          (double*)(scr + S.cand), scr + S.keep, (int32_t*)(scr + S.partial),
+                                          (int32_t*)(scr + S.gate), lm_pointers(c, B), pose_status));
+  else
+    HIPCHK(c, orbx_launch_landmarks(s, K, (const double*)(scr + S.poses), d_tracks, d_seen, n, cap, len,
+                                    (double*)(scr + S.cand), scr + S.keep, (int32_t*)(scr + S.partial),
+                                    (int32_t*)(scr + S.gate), lm_pointers(c, B), pose_status));
   std::memcpy(c->lm.K, K, sizeof c->lm.K);
+  c->lm.has_views = views != nullptr;
   c->lm.n = n;
   c->lm.cap = cap;
   c->lm.len = len;
@@ -248,27 +327,59 @@ int orbx_bundle_adjust_tracks(orbx_ctx* c, const double* K, const float* tracks_
                               int* count) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!poses6) return fail(c, ORBX_ERR_INVALID_ARG, "K, tracks, seen or poses6 is NULL");
-  int st = lm_check_build(c, K, tracks_xy, seen, 1, n_slots, window_len, poses6);
+  return lm_tracks(c, K, tracks_xy, seen, n_slots, window_len, poses6, huber_delta, max_iters, lm_status, summary,
+                   points3, slot_of_point, capacity, count, nullptr);
+}
+
+// ---- include/orbx_lm.h ----
+
+int orbx_landmarks_build_views_device(orbx_ctx* c, const double* K, const float* d_tracks_xy, const int32_t* d_seen,
+                                      int n_windows, int slot_capacity, int window_len, const double* poses6,
+                                      int tri_mode, double max_reproj_px, void* stream) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  return lm_build_views(c, K, d_tracks_xy, d_seen, n_windows, slot_capacity, window_len, poses6,
+                        LmViewsOptions{tri_mode, max_reproj_px}, stream_of(c, stream));
+}
+
+int orbx_landmarks_views_results_device(orbx_ctx* c, orbx_landmarks_views_view* v) {
+  DeviceGuard _dg(c);
+  if (!c || !v) return ORBX_ERR_INVALID_ARG;
+  const int st = lm_check_views(c, 0, 1);
   if (st != ORBX_OK) return st;
-  if (!ba_params_ok(huber_delta, max_iters) || !lm_status || !summary || capacity < 0)
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
-  const float* d_tracks;
-  const int32_t* d_seen;
-  if ((st = stage_tracks(c, c->lm.side, c->lm.stage, tracks_xy, seen, n_slots, window_len, &d_tracks, &d_seen)) != ORBX_OK)
-    return st;
-  if ((st = lm_run(c, K, d_tracks, d_seen, 1, n_slots, window_len, poses6, nullptr, nullptr, c->stream)) != ORBX_OK)
-    return st;
-  if ((st = orbx_bundle_adjust_landmarks_device(c, huber_delta, max_iters, nullptr)) != ORBX_OK) return st;
-  int np = 0;
-  if ((st = orbx_bundle_adjust_landmarks_fetch(c, 0, 1, nullptr, nullptr, nullptr, 0, &np)) != ORBX_OK) return st;
-  if (count) *count = np;
-  if ((points3 || slot_of_point) && np > capacity)
-    return fail(c, ORBX_ERR_CAPACITY, "bundle_adjust_tracks: capacity is too small");
-  if ((st = orbx_landmarks_fetch(c, 0, 1, lm_status, nullptr, nullptr, nullptr, nullptr, slot_of_point, capacity,
-                                 nullptr, nullptr, nullptr, 0, nullptr, nullptr)) != ORBX_OK)
-    return st;
-  return orbx_bundle_adjust_landmarks_fetch(c, 0, 1, poses6, summary, points3, capacity, nullptr);
+  const LmViews V(c->lm.n, c->lm.cap, c->lm.len);
+  v->reason = at<const uint8_t>(c->lm.views, V.reason);
+  v->reproj_px = at<const float>(c->lm.views, V.reproj_px);
+  v->slot_capacity = c->lm.cap;
+  v->n_windows = c->lm.n;
+  return ORBX_OK;
+}
+
+int orbx_landmarks_views_fetch(orbx_ctx* c, int first, int n, uint8_t* reason, float* reproj_px) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  int st = lm_check_views(c, first, n);
+  if (st != ORBX_OK) return st;
+  if ((st = c->lm.side.wait(c)) != ORBX_OK) return st;
+  const LmViews V(c->lm.n, c->lm.cap, c->lm.len);
+  const size_t s0 = (size_t)first * c->lm.cap, ns = (size_t)n * c->lm.cap;
+  if (reason) HIPCHK(c, hipMemcpy(reason, at<const uint8_t>(c->lm.views, V.reason) + s0, ns, hipMemcpyDeviceToHost));
+  if (reproj_px)
+    HIPCHK(c, hipMemcpy(reproj_px, at<const float>(c->lm.views, V.reproj_px) + s0, sizeof(float) * ns,
+                        hipMemcpyDeviceToHost));
+  return ORBX_OK;
+}
+
+int orbx_bundle_adjust_tracks_views(orbx_ctx* c, const double* K, const float* tracks_xy, const int32_t* seen,
+                                    int n_slots, int window_len, double* poses6, double huber_delta, int max_iters,
+                                    int32_t* lm_status, orbx_ba_summary* summary, double* points3,
+                                    int32_t* slot_of_point, int capacity, int* count, int tri_mode,
+                                    double max_reproj_px) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  const LmViewsOptions o{tri_mode, max_reproj_px};
+  return lm_tracks(c, K, tracks_xy, seen, n_slots, window_len, poses6, huber_delta, max_iters, lm_status, summary,
+                   points3, slot_of_point, capacity, count, &o);
 }
 
 }  // extern "C"

@@ -235,18 +235,21 @@ struct BundleAdjust {
 // landmarks of tracked windows and their bundle adjustment on the device (orbx_landmarks.hip, orbx_ba.hip): the
 // scratch of a build, the entry's OWN result block (what k_ba_lm reads), the solve's copies of poses and points with
 // its summaries, the solve's workspaces (LmScratch, LmBlock, LmSolve, LmWork of orbx_layout.h), and the staged tracks
-// of the one-window host entry.  Nothing here is shared with orbx_bundle_adjust_batch.
+// of the one-window host entry.  A build from every view of a track (rank 15) writes the same block and, beside it,
+// its table of view records and reason | reproj_px into a buffer of their own (views, LmViews).  Nothing here is
+// shared with orbx_bundle_adjust_batch.
 struct Landmarks {
-  DevBuf scr, blk, sol, ws, stage;
+  DevBuf scr, blk, sol, ws, stage, views;
   double K[9] = {};
   int n = 0, cap = 0, len = 0;  // windows, slots per window, poses per window of the last build (0: none)
+  bool has_views = false;       // the last build was a views build: `views` belongs to it
   bool solved = false;          // the block has been solved since it was built
   SideWork side;                // the event is recorded behind every build and every solve
   PinnedUpload poses_up;        // the pose table's way up
   void release() {
     side.release();
     poses_up.release();
-    free_bufs({&scr, &blk, &sol, &ws, &stage});
+    free_bufs({&scr, &blk, &sol, &ws, &stage, &views});
   }
 };
 
@@ -498,11 +501,18 @@ int stage_tracks(orbx_ctx* c, SideWork& side, DevBuf& stage, const float* tracks
 // the landmarks build behind its two entries (orbx_api_landmarks.cpp).  lm_check_build: the argument rules; the poses
 // are checked when they come from the host (poses6 != NULL).  lm_run enqueues the build on s with the poses from the
 // host (poses6, through the pinned mirror) or from the window-poses block (poses6 == NULL: d_poses6 and d_pose_status,
-// copied on s behind that block's event)
+// copied on s behind that block's event).  views: NULL for the build of rank 10, else the options of the build from
+// every view of a track (rank 15), checked by lm_views_ok
+struct LmViewsOptions {
+  int tri_mode;
+  double max_reproj_px;
+};
+bool lm_views_ok(const LmViewsOptions& o);
 bool ba_params_ok(double huber_delta, int max_iters);
 int lm_check_build(orbx_ctx* c, const double* K, const void* tracks, const void* seen, int n, int cap, int len,
                    const double* poses6);
 int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
-           const double* poses6, const double* d_poses6, const int32_t* d_pose_status, hipStream_t s);
+           const double* poses6, const double* d_poses6, const int32_t* d_pose_status, hipStream_t s,
+           const LmViewsOptions* views = nullptr);
 
 }  // namespace orbx_host

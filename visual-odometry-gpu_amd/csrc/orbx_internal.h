@@ -244,6 +244,13 @@ hipError_t orbx_launch_landmarks(hipStream_t s, const double* K9, const double* 
                                  const int32_t* d_seen, int n_windows, int cap, int window_len, double* d_cand,
                                  uint8_t* d_keep, int32_t* d_partial, int32_t* d_gate, const OrbxLmBlock& out,
                                  const int32_t* d_pose_status = nullptr);
+// the build from every view of a track: tri_mode and max_reproj_px as include/orbx_lm.h has
+// them; d_table: 16 doubles per (window, view); d_reason / d_reproj_px: n * cap each; the rest as above
+hipError_t orbx_launch_landmarks_views(hipStream_t s, const double* K9, const double* d_poses, const float* d_tracks,
+                                       const int32_t* d_seen, int n_windows, int cap, int window_len, int tri_mode,
+                                       double max_reproj_px, double* d_table, uint8_t* d_reason, float* d_reproj_px,
+                                       double* d_cand, uint8_t* d_keep, int32_t* d_partial, int32_t* d_gate,
+                                       const OrbxLmBlock& out, const int32_t* d_pose_status = nullptr);
 
 // ---- window poses and the write-back gate (orbx_wposes.hip) ---------------------------------
 // d_pose / d_scale: the tracks-pose block's rows, window w's pairs at w * (window_len - 1); d_T0: 16 doubles and

@@ -179,6 +179,14 @@ struct LmScratch : private Sections {
         partial(take(sizeof(int32_t) * 2 * n * orbx_lm_blocks(cap))), keep(take(n * cap)),
         cand(take(sizeof(double) * 3 * n * cap)), bytes(off) {}
 };
+// what the build from every view of a track (rank 15) adds, in a buffer of its own: the table of view records (16
+// doubles per window and pose) | reason | reproj_px (one per slot)
+struct LmViews : private Sections {
+  size_t slots, table, reason, reproj_px, bytes;
+  LmViews(size_t n, size_t cap, size_t len)
+      : slots(n * cap), table(take(sizeof(double) * 16 * n * len)), reason(take(slots)),
+        reproj_px(take(sizeof(float) * slots)), bytes(end) {}
+};
 // what a solve works on and leaves behind
 struct LmSolve : private Sections {
   size_t poses, points, out, bytes;

@@ -34,31 +34,20 @@ ORBX_PHD bool tri_finite(float f) {
   return (u & 0x7f800000u) != 0x7f800000u;
 }
 
-// rule 1: the DLT of one correspondence in pixel units.  The homogeneous point h is the eigenvector of the
-// smallest eigenvalue of A^T A, by TRI_JACOBI_SWEEPS cyclic Jacobi sweeps over (0,1) (0,2) (0,3) (1,2) (1,3) (2,3);
-// of equal smallest eigenvalues the lowest column wins.
-ORBX_PHD void tri_homogeneous(const double* P1, const double* P2, double x1, double y1, double x2, double y2,
-                              double* h) {
+// rule 1, second half: the eigenvector h of the smallest eigenvalue of the symmetric 4x4 matrix whose UPPER triangle
+// `a` holds (the lower one is filled in here), by TRI_JACOBI_SWEEPS cyclic Jacobi sweeps over (0,1) (0,2) (0,3) (1,2)
+// (1,3) (2,3); of equal smallest eigenvalues the lowest column wins.  Shared by the two-view DLT below and the
+// N-view one of orbx_lm_math.h.
+ORBX_PHD void tri_smallest_eigenvector(double (*a)[4], double* h) {
   ORBX_PNO_CONTRACT
-  double A[4][4], a[4][4], v[4][4];
-ORBX_PUNROLL
-  for (int j = 0; j < 4; j++) {
-    A[0][j] = x1 * P1[8 + j] - P1[j];
-    A[1][j] = y1 * P1[8 + j] - P1[4 + j];
-    A[2][j] = x2 * P2[8 + j] - P2[j];
-    A[3][j] = y2 * P2[8 + j] - P2[4 + j];
-  }
+  double v[4][4];
 ORBX_PUNROLL
   for (int i = 0; i < 4; i++)
 ORBX_PUNROLL
     for (int j = 0; j < 4; j++) {
-      if (j >= i) a[i][j] = A[0][i] * A[0][j] + A[1][i] * A[1][j] + A[2][i] * A[2][j] + A[3][i] * A[3][j];
+      if (j < i) a[i][j] = a[j][i];
       v[i][j] = i == j ? 1.0 : 0.0;
     }
-ORBX_PUNROLL
-  for (int i = 0; i < 4; i++)
-ORBX_PUNROLL
-    for (int j = 0; j < i; j++) a[i][j] = a[j][i];
   for (int sw = 0; sw < TRI_JACOBI_SWEEPS; sw++) {
 ORBX_PUNROLL
     for (int p = 0; p < 3; p++) {
@@ -96,6 +85,27 @@ ORBX_PUNROLL
       h0 = v[0][k], h1 = v[1][k], h2 = v[2][k], h3 = v[3][k];
     }
   h[0] = h0, h[1] = h1, h[2] = h2, h[3] = h3;
+}
+
+// rule 1: the DLT of one correspondence in pixel units.  The homogeneous point h is the eigenvector of the
+// smallest eigenvalue of A^T A (tri_smallest_eigenvector).
+ORBX_PHD void tri_homogeneous(const double* P1, const double* P2, double x1, double y1, double x2, double y2,
+                              double* h) {
+  ORBX_PNO_CONTRACT
+  double A[4][4], a[4][4];
+ORBX_PUNROLL
+  for (int j = 0; j < 4; j++) {
+    A[0][j] = x1 * P1[8 + j] - P1[j];
+    A[1][j] = y1 * P1[8 + j] - P1[4 + j];
+    A[2][j] = x2 * P2[8 + j] - P2[j];
+    A[3][j] = y2 * P2[8 + j] - P2[4 + j];
+  }
+ORBX_PUNROLL
+  for (int i = 0; i < 4; i++)
+ORBX_PUNROLL
+    for (int j = i; j < 4; j++)
+      a[i][j] = A[0][i] * A[0][j] + A[1][i] * A[1][j] + A[2][i] * A[2][j] + A[3][i] * A[3][j];
+  tri_smallest_eigenvector(a, h);
 }
 
 // rule 2: X/w, Y/w, Z/w in double, each cast to float; returns whether the point is valid (w != 0 and three

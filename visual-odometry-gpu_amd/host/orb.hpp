@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "../../include/orbx_lm.h"
 #include "../../include/orbx_vo.h"
 
 #ifdef ORBX_WITH_OPENCV
@@ -1147,20 +1148,19 @@ inline bool run_bundle_adjustment(std::vector<Pose4x4>& pose_window, const doubl
   return true;
 }
 
-// The whole window from what LKTracker::trackWindow returns (DESIGN.md §9 rank 10): landmarks built on the device
-// from the tracks (buildLandmarksFromFirstTwoFramesAndTracks, src/with_bundle_adjustment.cpp:502-575; the DLT in
-// WORLD coordinates, the point kept in binary64) and solved there (src/with_bundle_adjustment.cpp:612-720) through
-// orbx_bundle_adjust_tracks, then the same write-back gate as run_bundle_adjustment.  xy: n x pose_window.size()
-// points, seen: n.  build_landmarks + run_bundle_adjustment triangulate in camera 0's frame through float instead:
-// the two routes differ by that, and both are unpinned against OpenCV / Ceres.  lm_status: the orbx_lm_status of
-// the window; points / slot_of_point: the refined landmarks and the track each came from.  Returns false when
-// there is nothing to solve.
-inline bool run_bundle_adjustment_on_tracks(std::vector<Pose4x4>& pose_window, const double K[9],
-                                            const std::vector<Point2f>& xy, const std::vector<int32_t>& seen,
-                                            orbx_ba_summary* summary = nullptr, std::vector<uint8_t>* updated = nullptr,
-                                            int32_t* lm_status = nullptr, std::vector<Point3d>* points = nullptr,
-                                            std::vector<int32_t>* slot_of_point = nullptr, double huber_delta = 1.0,
-                                            int max_iters = 200) {
+// LandmarkOptions (include/orbx_lm.h): the views a track's point is triangulated from and the
+// largest reprojection error in pixels a landmark may have (0: no gate).  The overload taking them builds the
+// landmarks through orbx_bundle_adjust_tracks_views; the defaults are the reference's own build.
+struct LandmarkOptions {
+  int tri_mode = ORBX_LM_TRI_FIRST_TWO;
+  double max_reproj_px = 0.0;
+};
+namespace detail {
+// behind both overloads of run_bundle_adjustment_on_tracks; options: NULL for the reference's own build
+inline bool ba_on_tracks(std::vector<Pose4x4>& pose_window, const double K[9], const std::vector<Point2f>& xy,
+                         const std::vector<int32_t>& seen, const LandmarkOptions* options, orbx_ba_summary* summary,
+                         std::vector<uint8_t>* updated, int32_t* lm_status, std::vector<Point3d>* points,
+                         std::vector<int32_t>* slot_of_point, double huber_delta, int max_iters) {
   static_assert(sizeof(Point2f) == 2 * sizeof(float), "point layout");
   const int W = (int)pose_window.size();
   const size_t n = seen.size();
@@ -1183,10 +1183,17 @@ inline bool run_bundle_adjustment_on_tracks(std::vector<Pose4x4>& pose_window, c
   std::vector<double> p3(3 * n);
   std::vector<int32_t> slots(n);
   orbx_ctx* c = detail::stage_ctx()->get(8, 8);
-  detail::check(c, orbx_bundle_adjust_tracks(c, K, reinterpret_cast<const float*>(xy.data()), seen.data(), (int)n, W,
-                                             poses.data(), huber_delta, max_iters, &st, &s, p3.data(), slots.data(),
-                                             (int)n, &count),
-                "orbx_bundle_adjust_tracks");
+  if (options)
+    detail::check(c, orbx_bundle_adjust_tracks_views(c, K, reinterpret_cast<const float*>(xy.data()), seen.data(), (int)n,
+                                                     W, poses.data(), huber_delta, max_iters, &st, &s, p3.data(),
+                                                     slots.data(), (int)n, &count, options->tri_mode,
+                                                     options->max_reproj_px),
+                  "orbx_bundle_adjust_tracks_views");
+  else
+    detail::check(c, orbx_bundle_adjust_tracks(c, K, reinterpret_cast<const float*>(xy.data()), seen.data(), (int)n, W,
+                                               poses.data(), huber_delta, max_iters, &st, &s, p3.data(), slots.data(),
+                                               (int)n, &count),
+                  "orbx_bundle_adjust_tracks");
   if (summary) *summary = s;
   if (lm_status) *lm_status = st;
   if (st != ORBX_LM_OK) return false;
@@ -1197,6 +1204,36 @@ inline bool run_bundle_adjustment_on_tracks(std::vector<Pose4x4>& pose_window, c
   if (s.termination != ORBX_BA_CONVERGENCE) return true;  // :683
   detail::ba_write_back(pose_window, poses, old, updated);
   return true;
+}
+}  // namespace detail
+
+// The whole window from what LKTracker::trackWindow returns (DESIGN.md §9 rank 10): landmarks built on the device
+// from the tracks (buildLandmarksFromFirstTwoFramesAndTracks, src/with_bundle_adjustment.cpp:502-575; the DLT in
+// WORLD coordinates, the point kept in binary64) and solved there (src/with_bundle_adjustment.cpp:612-720) through
+// orbx_bundle_adjust_tracks, then the same write-back gate as run_bundle_adjustment.  xy: n x pose_window.size()
+// points, seen: n.  build_landmarks + run_bundle_adjustment triangulate in camera 0's frame through float instead:
+// the two routes differ by that, and both are unpinned against OpenCV / Ceres.  lm_status: the orbx_lm_status of
+// the window; points / slot_of_point: the refined landmarks and the track each came from.  Returns false when
+// there is nothing to solve.
+inline bool run_bundle_adjustment_on_tracks(std::vector<Pose4x4>& pose_window, const double K[9],
+                                            const std::vector<Point2f>& xy, const std::vector<int32_t>& seen,
+                                            orbx_ba_summary* summary = nullptr, std::vector<uint8_t>* updated = nullptr,
+                                            int32_t* lm_status = nullptr, std::vector<Point3d>* points = nullptr,
+                                            std::vector<int32_t>* slot_of_point = nullptr, double huber_delta = 1.0,
+                                            int max_iters = 200) {
+  return detail::ba_on_tracks(pose_window, K, xy, seen, nullptr, summary, updated, lm_status, points, slot_of_point,
+                              huber_delta, max_iters);
+}
+// the same window with the landmarks built by `options` (orbx_bundle_adjust_tracks_views)
+inline bool run_bundle_adjustment_on_tracks(std::vector<Pose4x4>& pose_window, const double K[9],
+                                            const std::vector<Point2f>& xy, const std::vector<int32_t>& seen,
+                                            const LandmarkOptions& options, orbx_ba_summary* summary = nullptr,
+                                            std::vector<uint8_t>* updated = nullptr, int32_t* lm_status = nullptr,
+                                            std::vector<Point3d>* points = nullptr,
+                                            std::vector<int32_t>* slot_of_point = nullptr, double huber_delta = 1.0,
+                                            int max_iters = 200) {
+  return detail::ba_on_tracks(pose_window, K, xy, seen, &options, summary, updated, lm_status, points, slot_of_point,
+                              huber_delta, max_iters);
 }
 
 // ---- window poses and the gated window ------------------------------
