@@ -16,20 +16,6 @@ namespace {
 
 int tp_pairs(const orbx_ctx* c) { return c->tp.n * (c->tp.len - 1); }
 
-int tp_check(orbx_ctx* c, const double* K, const void* tracks, const void* seen, int n, int cap, int len, double prob,
-             double threshold, int max_iters) {
-  if (!pose_args_ok(K, prob, threshold, max_iters) || !finite_all(K, 9))
-    return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
-  if (!tracks || !seen) return fail(c, ORBX_ERR_INVALID_ARG, "tracks or seen is NULL");
-  if (n < 1 || cap < 1 || len < 2)
-    return fail(c, ORBX_ERR_INVALID_ARG, "n_windows < 1, slot_capacity < 1 or window_len < 2");
-  if ((size_t)cap * 16 > ORBX_SCALE_LDS_MAX)
-    return fail(c, ORBX_ERR_UNSUPPORTED, "more slots per window than the join holds in LDS");
-  if ((unsigned long long)n * (unsigned long long)(len - 1) * (unsigned long long)cap > 0x7fffffffull)
-    return fail(c, ORBX_ERR_UNSUPPORTED, "more list positions in a batch than 32-bit offsets hold");
-  return ORBX_OK;
-}
-
 // enqueues the four kernels on s; arguments are checked
 int tp_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
            double prob, double threshold, int max_iters, uint64_t seed, hipStream_t s) {
@@ -64,6 +50,24 @@ int tp_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d
 }
 
 }  // namespace
+
+namespace orbx_host {
+
+int tp_check(orbx_ctx* c, const double* K, const void* tracks, const void* seen, int n, int cap, int len, double prob,
+             double threshold, int max_iters) {
+  if (!pose_args_ok(K, prob, threshold, max_iters) || !finite_all(K, 9))
+    return fail(c, ORBX_ERR_INVALID_ARG, "bad pose arguments");
+  if (!tracks || !seen) return fail(c, ORBX_ERR_INVALID_ARG, "tracks or seen is NULL");
+  if (n < 1 || cap < 1 || len < 2)
+    return fail(c, ORBX_ERR_INVALID_ARG, "n_windows < 1, slot_capacity < 1 or window_len < 2");
+  if ((size_t)cap * 16 > ORBX_SCALE_LDS_MAX)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "more slots per window than the join holds in LDS");
+  if ((unsigned long long)n * (unsigned long long)(len - 1) * (unsigned long long)cap > 0x7fffffffull)
+    return fail(c, ORBX_ERR_UNSUPPORTED, "more list positions in a batch than 32-bit offsets hold");
+  return ORBX_OK;
+}
+
+}  // namespace orbx_host
 
 extern "C" {
 

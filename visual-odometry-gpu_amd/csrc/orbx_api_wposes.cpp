@@ -23,19 +23,37 @@ int wp_check_range(orbx_ctx* c, int first, int n, int total, const char* none, c
   return ORBX_OK;
 }
 
+}  // namespace
+
+namespace orbx_host {
+
 bool gate_params_ok(double max_rot, double max_trans) {
   return max_rot > 0.0 && std::isfinite(max_rot) && max_trans > 0.0 && std::isfinite(max_trans);
 }
 
-// the chain of the last tracks-pose block on s; T0 / scale0: host or NULL
-int wp_run(orbx_ctx* c, const double* T0, const double* scale0, hipStream_t s) {
+// the argument rules of a chain of the last tracks-pose block; nothing is launched
+int wp_check(orbx_ctx* c, const double* T0, const double* scale0, const WpStreamOptions* stream_of_windows) {
   const int n = c->tp.n, len = c->tp.len;
   if (n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no tracks have been posed");
   if (len > ORBX_BA_MAX_POSES) return fail(c, ORBX_ERR_INVALID_ARG, "window_len above ORBX_BA_MAX_POSES");
   if ((T0 && !finite_all(T0, 16 * n)) || (scale0 && !finite_all(scale0, n)))
     return fail(c, ORBX_ERR_INVALID_ARG, "T0 or scale0 is not finite");
-  int st = c->wp.side.enter(c, s);
+  if (stream_of_windows) {
+    if (stream_of_windows->stride < 1 || stream_of_windows->stride > len - 1)
+      return fail(c, ORBX_ERR_INVALID_ARG, "stride outside [1, window_len - 1]");
+    if (!std::isfinite(stream_of_windows->scale0_first))
+      return fail(c, ORBX_ERR_INVALID_ARG, "scale0_first is not finite");
+  }
+  return ORBX_OK;
+}
+
+// the chain of the last tracks-pose block on s; T0 / scale0: host or NULL
+int wp_run(orbx_ctx* c, const double* T0, const double* scale0, hipStream_t s,
+           const WpStreamOptions* stream_of_windows) {
+  int st = wp_check(c, T0, scale0, stream_of_windows);
   if (st != ORBX_OK) return st;
+  const int n = c->tp.n, len = c->tp.len;
+  if ((st = c->wp.side.enter(c, s)) != ORBX_OK) return st;
   const SideWork::Mark mark{c->wp.side, s};
   // the tracks-pose block may have been written on another stream
   if ((st = c->wp.side.after(c, c->tp.side, s)) != ORBX_OK) return st;
@@ -54,6 +72,10 @@ int wp_run(orbx_ctx* c, const double* T0, const double* scale0, hipStream_t s) {
   }
   if ((st = c->wp.up.send(c, c->wp.in.p, up.data(), I.bytes, s)) != ORBX_OK) return st;
   const TpBlock P((size_t)n, (size_t)c->tp.cap, (size_t)len);
+  // a stream of overlapping windows: pair 0's scale of window w + 1 is window w's, gathered behind the upload
+  if (stream_of_windows)
+    HIPCHK(c, orbx_launch_st_scale0(s, n, len, stream_of_windows->stride, stream_of_windows->scale0_first,
+                                    at<const OrbxScaleOut>(c->tp.blk, P.scale), at<double>(c->wp.in, I.scale0)));
   HIPCHK(c, orbx_launch_window_poses(s, n, len, at<const OrbxPoseOut>(c->tp.blk, P.pose),
                                      at<const OrbxScaleOut>(c->tp.blk, P.scale), at<const double>(c->wp.in, I.T0),
                                      at<const double>(c->wp.in, I.scale0), at<double>(c->wp.blk, B.poses6),
@@ -63,7 +85,7 @@ int wp_run(orbx_ctx* c, const double* T0, const double* scale0, hipStream_t s) {
   return ORBX_OK;
 }
 
-}  // namespace
+}  // namespace orbx_host
 
 extern "C" {
 

@@ -152,7 +152,7 @@ struct PinnedUpload {
   }
 };
 
-// ---- the context's parts, one per subsystem (orbx_ctx::s, m, lk, lkw, pose, scale, ba, gf, lm, tp, wp) ----
+// ---- the context's parts, one per subsystem (orbx_ctx::s, m, lk, lkw, pose, scale, ba, gf, lm, tp, wp, st) ----
 
 // stage-API scratch (grown on demand; never touched by the batched path)
 struct StageScratch {
@@ -283,6 +283,22 @@ struct WindowPoses {
   }
 };
 
+// overlapping windows joined into one trajectory (orbx_stitch.hip): what goes up with a stitch and what its kernels
+// hand one another (StInput of orbx_layout.h), the stitch's OWN result block (StBlock), and the staged tracks of the
+// host stream entry.  The stitch reads the caller's poses -- wp.blk or wp.wb when they are a view of those -- and
+// writes nowhere else.
+struct StreamStitch {
+  DevBuf in, blk, stage;
+  int n = 0, len = 0, stride = 0;  // windows, frames per window and stride of the last stitch (n == 0: none)
+  SideWork side;                   // the event is recorded behind every stitch
+  PinnedUpload up;                 // T_start on its way up
+  void release() {
+    side.release();
+    up.release();
+    free_bufs({&in, &blk, &stage});
+  }
+};
+
 // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames, allocated on first use and bounded by
 // ws_limit; the staged host image of the one-frame entries; and the entry's OWN result block, untouched by the ORB
 // path.  Rank 12 (top-up and masked detection) adds, beside the workspace and for the same number of frames, the bit
@@ -368,7 +384,7 @@ struct orbx_ctx {
   // calls are made: pose reads the matcher's table, scale checks pose.match_gen against m.gen, the windows
   // tracker waits for the good-features event, the landmarks build and the tracks pose wait for the windows
   // tracker's, the window poses wait for the tracks pose's, the chained landmarks build for the window poses', and
-  // the write-back gate for the solve's.
+  // the write-back gate for the solve's, and the stitch for the window poses' (chain and gate share one event).
   orbx_host::StageScratch s;
   orbx_host::Matcher m;
   orbx_host::LkPair lk;
@@ -380,6 +396,7 @@ struct orbx_ctx {
   orbx_host::Landmarks lm;
   orbx_host::TracksPose tp;
   orbx_host::WindowPoses wp;
+  orbx_host::StreamStitch st;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -514,5 +531,19 @@ int lm_check_build(orbx_ctx* c, const double* K, const void* tracks, const void*
 int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
            const double* poses6, const double* d_poses6, const int32_t* d_pose_status, hipStream_t s,
            const LmViewsOptions* views = nullptr);
+// the argument rules of orbx_tracks_pose_device (orbx_api_tracks.cpp)
+int tp_check(orbx_ctx* c, const double* K, const void* tracks, const void* seen, int n, int cap, int len, double prob,
+             double threshold, int max_iters);
+// the chain of the last tracks-pose block on s behind its two entries (orbx_api_wposes.cpp).  T0 / scale0: host or
+// NULL.  stream_of_windows: NULL, or the chain of a stream of overlapping windows (rank 16): T0 and scale0 have to be
+// NULL, every window starts at the identity, and scale0 is gathered on the device from the tracks-pose block itself
+struct WpStreamOptions {
+  int stride;
+  double scale0_first;
+};
+int wp_check(orbx_ctx* c, const double* T0, const double* scale0, const WpStreamOptions* stream_of_windows);
+int wp_run(orbx_ctx* c, const double* T0, const double* scale0, hipStream_t s,
+           const WpStreamOptions* stream_of_windows = nullptr);
+bool gate_params_ok(double max_rot, double max_trans);
 
 }  // namespace orbx_host

@@ -264,6 +264,18 @@ hipError_t orbx_launch_ba_write_back(hipStream_t s, int n_windows, int window_le
                                      const double* d_built6, const void* d_summaries, double max_rot,
                                      double max_trans, double* d_poses4x4, uint8_t* d_updated);
 
+// ---- overlapping windows joined into one trajectory (orbx_stitch.hip) ------------------------
+// Window w of window_len frames starts at stream frame w * stride, 1 <= stride <= window_len - 1.
+// d_scale: the tracks-pose block's scale rows; d_scale0: one double per window (the chain's input section)
+hipError_t orbx_launch_st_scale0(hipStream_t s, int n_windows, int window_len, int stride, double scale0_first,
+                                 const OrbxScaleOut* d_scale, double* d_scale0);
+// d_poses4x4: 16 doubles per (window, frame); d_T_start: 16 doubles; d_links: 14 doubles and d_broken: one int32 per
+// window (scratch); d_trajectory4x4 / d_owner: per stream frame; d_anchors4x4 / d_lambda / d_status: per window
+hipError_t orbx_launch_stitch(hipStream_t s, int n_windows, int window_len, int stride, const double* d_poses4x4,
+                              const double* d_T_start, int align_scale, double* d_links, int32_t* d_broken,
+                              double* d_trajectory4x4, int32_t* d_owner, double* d_anchors4x4, double* d_lambda,
+                              int32_t* d_status);
+
 // ---- pose and scale of tracked frame pairs (orbx_tracks.hip) --------------------------------
 // Window w of window_len frames owns window_len - 1 pairs, pair p = w * (window_len - 1) + k is frames k, k + 1.
 // Every per-position array has one row of `cap` = slot_capacity per pair.

@@ -254,6 +254,26 @@ struct WbBlock : private Sections {
   WbBlock(size_t n, size_t len) : poses4x4(take(sizeof(double) * 16 * n * len)), updated(take(n * len)), bytes(off) {}
 };
 
+// ---- n overlapping windows of len frames, window w starting at stream frame w * stride, joined into one trajectory ----
+// the frames of the stream
+inline size_t st_stream_frames(size_t n, size_t len, size_t stride) { return (n - 1) * stride + len; }
+// what goes up with a stitch and what its kernels hand one another: T_start (16 doubles) | links (14 doubles per
+// window: R_rel, t_rel, b_first, b_link) | broken (one int32 per window)
+struct StInput : private Sections {
+  size_t T_start, links, broken, bytes;
+  explicit StInput(size_t n)
+      : T_start(take(sizeof(double) * 16)), links(take(sizeof(double) * 14 * n)), broken(take(sizeof(int32_t) * n)),
+        bytes(end) {}
+};
+// the stitch's result block: trajectory4x4 | owner (one per stream frame) | anchors4x4 | lambda | status (one per window)
+struct StBlock : private Sections {
+  size_t frames, trajectory4x4, owner, anchors4x4, lambda, status, bytes;
+  StBlock(size_t n, size_t len, size_t stride)
+      : frames(st_stream_frames(n, len, stride)), trajectory4x4(take(sizeof(double) * 16 * frames)),
+        owner(take(sizeof(int32_t) * frames)), anchors4x4(take(sizeof(double) * 16 * n)),
+        lambda(take(sizeof(double) * n)), status(take(sizeof(int32_t) * n)), bytes(off) {}
+};
+
 // ---- the descriptor matcher, and pose and scale of the frame pairs of a batch ----
 // one row of `cap` per pair in every per-slot array (e = pairs * cap slots).  The host-array entries use the same
 // blocks with one pair: MatchBlock(1, nq), PoseBlock(1, max(n, 1)).

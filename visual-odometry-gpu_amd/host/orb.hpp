@@ -45,6 +45,7 @@
 
 #include "../../include/orbx.h"
 #include "../../include/orbx_lm.h"
+#include "../../include/orbx_stream.h"
 #include "../../include/orbx_vo.h"
 
 #ifdef ORBX_WITH_OPENCV
@@ -1292,6 +1293,80 @@ inline WindowOdometry run_window_odometry_on_tracks(const Pose4x4& pose0, const 
                                             out.pose_window[0].data(), out.updated.data(), &out.wp_status,
                                             &out.lm_status, &out.summary),
                 "orbx_window_odometry_tracks");
+  return out;
+}
+
+// ---- a stream of overlapping windows joined into one trajectory ------------------------
+// What the reference does across solves, cur_pose = prev_pose * T.inv() and cur_pose = pose_window.back()
+// (src/with_bundle_adjustment.cpp:203, :234-249), for windows that each live in a frame of their own: window w of
+// window_len poses starts at stream frame w * stride.  orbx_stitch_windows: the arithmetic the device stitch runs, from
+// the same source; needs no GPU.
+struct StitchedStream {
+  std::vector<Pose4x4> trajectory;  // camera -> world, one per stream frame; [0] = pose0
+  std::vector<int32_t> owner;       // the window a frame's pose was taken from
+  std::vector<Pose4x4> anchors;     // the stream pose of every window's first frame
+  std::vector<double> lambda;       // the scale every window's translations were multiplied by
+  std::vector<int32_t> status;      // bits of orbx_st_status per window
+};
+inline StitchedStream stitch_windows(const std::vector<Pose4x4>& window_poses, int n_windows, int window_len, int stride,
+                                     const Pose4x4& pose0, bool align_scale = false) {
+  static_assert(sizeof(Pose4x4) == 16 * sizeof(double), "layout");
+  if (n_windows < 1 || window_len < 2 || window_poses.size() != (size_t)n_windows * (size_t)window_len)
+    throw std::invalid_argument("stitch_windows: window_poses is not n_windows x window_len");
+  if (stride < 1 || stride > window_len - 1) throw std::invalid_argument("stitch_windows: stride outside [1, window_len - 1]");
+  const size_t F = (size_t)(n_windows - 1) * stride + window_len, W = (size_t)n_windows;
+  StitchedStream out;
+  out.trajectory.resize(F);
+  out.owner.resize(F);
+  out.anchors.resize(W);
+  out.lambda.resize(W);
+  out.status.resize(W);
+  detail::check(nullptr,
+                orbx_stitch_windows(window_poses[0].data(), n_windows, window_len, stride, pose0.data(), align_scale,
+                                    out.trajectory[0].data(), out.owner.data(), out.anchors[0].data(),
+                                    out.lambda.data(), out.status.data()),
+                "orbx_stitch_windows");
+  return out;
+}
+
+struct StreamOdometry {
+  std::vector<Pose4x4> trajectory;           // camera -> world, one per stream frame
+  std::vector<int32_t> st_status, wp_status, lm_status;  // per window
+  std::vector<orbx_ba_summary> summaries;    // per window
+};
+// A stream of n_windows overlapping windows from what LKTracker::trackWindow returns for each to one trajectory,
+// everything between on the device (src/with_bundle_adjustment.cpp:180-208, :234-249, :502-575, :612-720), through
+// orbx_stream_odometry_tracks.  xy: n_windows x n x n_frames points, seen: n_windows x n.  run_window_odometry_on_tracks
+// is one window of it, with the pose of its first frame and the scale of its first pair handed in.
+inline StreamOdometry run_stream_odometry_on_tracks(const Pose4x4& pose0, const double K[9],
+                                                    const std::vector<Point2f>& xy, const std::vector<int32_t>& seen,
+                                                    int n_windows, int n_frames, int stride, double scale0 = 1.0,
+                                                    const LandmarkOptions& options = LandmarkOptions(),
+                                                    bool align_scale = false, double prob = 0.999,
+                                                    double threshold = 1.0, int pose_max_iters = 1000, uint64_t seed = 0,
+                                                    double huber_delta = 1.0, int ba_max_iters = 200,
+                                                    double max_rot = 0.5, double max_trans = 50.0) {
+  static_assert(sizeof(Point2f) == 2 * sizeof(float), "point layout");
+  if (n_windows < 1 || n_frames < 2 || stride < 1 || stride > n_frames - 1)
+    throw std::invalid_argument("run_stream_odometry_on_tracks: no stream of n_windows windows of n_frames at this stride");
+  if (seen.empty() || seen.size() % (size_t)n_windows || xy.size() != seen.size() * (size_t)n_frames)
+    throw std::invalid_argument("run_stream_odometry_on_tracks: xy is not n_windows x n x n_frames");
+  const size_t W = (size_t)n_windows;
+  StreamOdometry out;
+  out.trajectory.resize((W - 1) * (size_t)stride + (size_t)n_frames);
+  out.st_status.resize(W);
+  out.wp_status.resize(W);
+  out.lm_status.resize(W);
+  out.summaries.resize(W);
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_stream_odometry_tracks(c, K, reinterpret_cast<const float*>(xy.data()), seen.data(), n_windows,
+                                            (int)(seen.size() / W), n_frames, stride, pose0.data(), scale0, prob,
+                                            threshold, pose_max_iters, seed, options.tri_mode, options.max_reproj_px,
+                                            huber_delta, ba_max_iters, max_rot, max_trans, align_scale,
+                                            out.trajectory[0].data(), out.st_status.data(), out.wp_status.data(),
+                                            out.lm_status.data(), out.summaries.data()),
+                "orbx_stream_odometry_tracks");
   return out;
 }
 
