@@ -3,9 +3,10 @@ usage: python tools/fuzz_lk.py [seconds] [seed] [only_iteration]   (the third ar
        python tools/fuzz_lk.py --windows [seconds] [seed]
 --windows: random batches of windows through orbx_lk_track_windows_device (random window starts and lengths, ragged
 counts, strided frames, a random workspace limit) against the oracle chain of tests/lk_window_ref.py."""
-import importlib, sys, time
+import importlib, os, sys, time
 import numpy as np
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 pkg = importlib.import_module("visual-odometry-gpu_amd")
 import oracle_lib as O
 
