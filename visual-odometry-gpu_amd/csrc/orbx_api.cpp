@@ -233,6 +233,7 @@ int fast_impl_env() { return env_int("ORBX_FAST_IMPL", 4) == 3 ? 3 : 4; }
 //   ORBX_TOP_ROWS=2:equal          the two tile rows of the first pass stay equal halves (A/B timing)
 //   ORBX_TOP_ROWS=2:68,65,0,61     rows of tile row 0 per level, forced (tests; 0: leave the level to the chooser)
 //   ORBX_TOP_ROWS=2:trace          every decision of the chooser goes to stderr
+//   ORBX_TOP_ROWS=2:late           no early bands: the first pyramid pass ends below tile row 1 on every level (A/B timing)
 void first_split_env(orbx_ctx* c) {
   const char* e = getenv("ORBX_TOP_ROWS");
   e = e ? std::strchr(e, ':') : nullptr;
@@ -242,6 +243,8 @@ void first_split_env(orbx_ctx* c) {
       c->first_split = false;
     } else if (!std::strncmp(e, "trace", 5)) {
       c->split_trace = true;
+    } else if (!std::strncmp(e, "late", 4)) {
+      c->early_band = false;
     } else {
       for (int l = 0; l < ORBX_MAX_LEVELS; l++) {
         char* end = nullptr;
@@ -487,9 +490,27 @@ int set_plan(orbx_ctx* c, int w, int h) {
   if ((st = upload_tiles(c, T_BLUR, t, "blur tile table exceeds pool")) != ORBX_OK) return st;
   build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped);
   if ((st = upload_tiles(c, T_PYRBLUR, t, "strip table exceeds pool")) != ORBX_OK) return st;
-  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 1, &c->bm_fast, top);
+  // Early bands (orbx_plan.h, pyrblur_early_rows): the rows between h0 + ORBX_TOP_MARGIN and the end of the first pass
+  // go to the second pass, behind a test on tile row 0 alone, on the levels where that pays by the fill rows the last
+  // observation window saw (early_band_pays) -- or, under a forced cut, wherever the band has three rows or more
+  // (tests: no histogram has been seen when their tables are built).
+  for (int l = 0; l < ORBX_MAX_LEVELS; l++) c->early_rows[l] = 0;
+  for (int l = 0; l < plan.nlevels; l++) {
+    const int late = pyrblur_first_pass_rows(plan, c->bm_fast, l, top);
+    const int P = c->early_band ? pyrblur_early_rows(plan, c->bm_fast, l, top, c->p.nms_window / 2) : late;
+    const bool forced = c->cut_force[l] > 0;
+    const bool pays = P < late && (forced ? late - P >= ORBX_PYRBLUR_EARLY_MIN_ROWS
+                                          : early_band_pays(c->fill_last[l], c->bm_fast.first_h[l][0], late - P,
+                                                            pyrblur_row_cost(l, plan.L[l].win8)));
+    c->early_rows[l] = pays ? P : late;
+    if (c->split_trace && c->bm_fast.first_h[l][0] > 0)
+      fprintf(stderr, "orbx early band: level %d cut %d first pass ended at %d, now ends at %d, band %d rows: %s\n", l,
+              c->bm_fast.first_h[l][0], late, c->early_rows[l], late - P,
+              pays ? (forced ? "split (forced cut)" : "split") : !c->early_band ? "late" : "kept");
+  }
+  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 1, &c->bm_fast, top, c->early_rows);
   if ((st = upload_tiles(c, T_PYRBLUR_TOP, t, "strip table exceeds pool")) != ORBX_OK) return st;
-  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 2, &c->bm_fast, top);
+  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 2, &c->bm_fast, top, c->early_rows);
   if ((st = upload_tiles(c, T_PYRBLUR_REST, t, "strip table exceeds pool")) != ORBX_OK) return st;
   c->top_levels = OrbxTopLevels{};
   for (int l = 0; l < plan.nlevels; l++)
@@ -675,6 +696,7 @@ bool adapt_tile_rows(orbx_ctx* c) {
     uint64_t total = 0;
     for (int b = 0; b < ORBX_FILL_BUCKETS; b++) {
       hist[b] = c->fill_cur[l][b] + c->fill_prev[l][b];
+      c->fill_last[l][b] = hist[b];  // (what set_plan decides the early bands from, if this window has it called)
       c->fill_prev[l][b] = c->fill_cur[l][b];
       c->fill_cur[l][b] = 0;
       total += hist[b];
@@ -830,6 +852,7 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
     for (int l = 0; l < ORBX_MAX_LEVELS; l++) c->need_cur[l] = c->need_prev[l] = 0, c->tile_h_pref[l] = c->cut_pref[l] = 0;
     std::memset(c->fill_cur, 0, sizeof(c->fill_cur));
     std::memset(c->fill_prev, 0, sizeof(c->fill_prev));
+    std::memset(c->fill_last, 0, sizeof(c->fill_last));
     for (int i = 2; i < ORBX_FEEDBACK_WORDS; i++) c->h_feedback[i] = 0;
     c->need_batches = 0;
     c->need_window = 2;
@@ -1348,10 +1371,15 @@ int orbx_pyramid_pixel_counts(orbx_ctx* c, long long* produced, long long* total
     for (int l = 0; l < c->plan.nlevels; l++) {
       const OrbxLevel& L = c->plan.L[l];
       const int first = pyrblur_first_pass_rows(c->plan, c->bm_fast, l, top);
-      long long surv = 0;  // the kernel's test: survivors of the first-pass tile rows
-      for (int b = 0; b < std::min(top, c->bm_fast.tiles_y[l]); b++)
+      long long surv = 0, surv0 = 0;  // the kernel's tests: survivors of the first-pass tile rows, and of tile row 0
+      for (int b = 0; b < std::min(top, c->bm_fast.tiles_y[l]); b++) {
         surv += (long long)(uint32_t)h[(size_t)f * ORBX_FAST_STAT_WORDS + (size_t)l * ORBX_MAX_BANDS + b];
-      done += (long long)L.w * (first < L.h && surv >= L.cap ? first : L.h);
+        if (b == 0) surv0 = surv;
+      }
+      // (an early band, rows [early, first), is produced unless tile row 0 alone holds the cap)
+      const int early = c->early_rows[l] > 0 && c->early_rows[l] < first ? c->early_rows[l] : first;
+      const int band = surv0 >= L.cap ? 0 : first - early;
+      done += (long long)L.w * (first < L.h && surv >= L.cap ? early + band : L.h);
     }
   *produced = done;
   return ORBX_OK;

@@ -426,6 +426,13 @@ struct orbx_ctx {
   uint32_t fill_cur[ORBX_MAX_LEVELS][ORBX_FILL_BUCKETS] = {}, fill_prev[ORBX_MAX_LEVELS][ORBX_FILL_BUCKETS] = {};
   int cut_pref[ORBX_MAX_LEVELS] = {}, cut_force[ORBX_MAX_LEVELS] = {};
   bool first_split = true, split_trace = false;
+  // early band of the fused pyramid + blur kernel's second pass (orbx_plan.h: pyrblur_early_rows, early_band_pays):
+  // the histograms the last observation window ended with -- set_plan decides per level from them when it builds the
+  // tables, so only when adapt_tile_rows has them rebuilt --, and the row each level's first pass ends at in the
+  // current tables (the end of tile row 1 + ORBX_TOP_MARGIN where there is no band).  ORBX_TOP_ROWS=2:late: no bands.
+  uint32_t fill_last[ORBX_MAX_LEVELS][ORBX_FILL_BUCKETS] = {};
+  int early_rows[ORBX_MAX_LEVELS] = {};
+  bool early_band = true;
   // ring of event sets: one per timed batched call, so that several calls can be
   // in flight before their stage times are read (no host sync between steps)
   orbx_host::TimingSet evr[ORBX_EVENT_SETS];

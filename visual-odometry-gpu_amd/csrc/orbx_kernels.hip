@@ -1319,11 +1319,14 @@ __device__ __forceinline__ int desc_kind(const DescJob& jb) {
 // column clamped into the level, so that every address stays inside [img, img + pitch * h).  What a clamped
 // address delivers is overwritten with zeros in LDS (desc_zero_outside); the moments never see it, they are
 // taken only where the whole orientation window is inside the level.  rowk[] never exceeds the last row of the
-// neighbourhood, so for KIND == DESC_TOP the lower clamp is all there is.
-template <int KIND>
+// neighbourhood, so for KIND == DESC_TOP the lower clamp is all there is.  RB: the constant bit rowk[] carries
+// above the row (k_describe2); the clamps carry it too, and `base` is less by RB * pitch.
+template <int KIND, uint32_t RB>
 __device__ __forceinline__ void desc_fetch_border(const DescJob& jb, uint32_t base, const int (&rowk)[DESC_NLD],
                                                   const int (&c3)[3], uint32_t (&regs)[DESC_NLD]) {
-  const DescClip cl = desc_clip(jb);
+  DescClip cl = desc_clip(jb);
+  cl.rlo |= (int)RB;
+  cl.rhi |= (int)RB;
   int cb[3];
 #pragma unroll
   for (int m = 0; m < 3; m++) cb[m] = KIND == DESC_TOP ? 4 * c3[m] : min(max(4 * c3[m], cl.clo), cl.chi);
@@ -1460,7 +1463,45 @@ __device__ __forceinline__ i2_t lround_small2(f2_t v) {
   return __builtin_convertvector(v + __builtin_elementwise_copysign(h, v), i2_t);
 }
 
-template <int DESC_KPW, int DESC_NW, int DESC_OCC>
+// The orientation window with a compile-time radius ORAD (rows and columns DESC_R - ORAD ... DESC_R + ORAD of the
+// neighbourhood): which of a lane's DESC_NLD dwords (dword lane + 64k of the row-major 41 x 12 patch) lie in it.
+// Dword k of every lane in [lane_lo(k), lane_hi(k)) is inside; an empty range is a dword no lane needs.
+template <int ORAD>
+struct DescWindow {
+  static constexpr int RD = DESC_PITCH / 4;
+  static constexpr int lo = (DESC_R - ORAD) * RD, hi = (DESC_R + ORAD + 1) * RD;  // the window's dwords [lo, hi)
+  static constexpr int lane_lo(int k) { return lo - 64 * k < 0 ? 0 : lo - 64 * k > 64 ? 64 : lo - 64 * k; }
+  static constexpr int lane_hi(int k) { return hi - 64 * k < 0 ? 0 : hi - 64 * k > 64 ? 64 : hi - 64 * k; }
+  static constexpr bool none(int k) { return lane_lo(k) >= lane_hi(k); }
+  static constexpr bool all(int k) { return lane_lo(k) == 0 && lane_hi(k) == 64; }
+  static constexpr int count() {
+    int n = 0;
+    for (int k = 0; k < DESC_NLD; k++) n += !none(k);
+    return n;
+  }
+};
+// patch_size 31: rows 5 ... 35.  Dword 7 (rows 37 ...) is never inside, dwords 1 ... 5 always, dword 0 from its
+// first dword of row 5 on and dword 6 up to its last dword of row 35.
+static_assert(DescWindow<15>::none(7) && DescWindow<15>::count() == 7, "radius 15: dwords 0 ... 6");
+static_assert(DescWindow<15>::all(1) && DescWindow<15>::all(2) && DescWindow<15>::all(3) && DescWindow<15>::all(4) &&
+                  DescWindow<15>::all(5),
+              "radius 15: dwords 1 ... 5 take no mask");
+static_assert(DescWindow<15>::lane_lo(0) == (DESC_R - 15) * (DESC_PITCH / 4) && DescWindow<15>::lane_hi(0) == 64,
+              "radius 15: dword 0 from the first dword of the window's first row");
+static_assert(DescWindow<15>::lane_lo(6) == 0 &&
+                  DescWindow<15>::lane_hi(6) == (DESC_R + 15 + 1) * (DESC_PITCH / 4) - 6 * 64,
+              "radius 15: dword 6 up to the last dword of the window's last row");
+// S and the row-weighted sum M in one 24-bit multiply-add chain, W = sum (row | 1 << DESC_WS) * rs = M + (S << DESC_WS):
+// at most DESC_NLD dwords with rs <= 4 * 255 and rows < DESC_ROWS, so M <= 8 * 1020 * 40 = 326 400 < 2^19 and
+// S <= 8160 < 2^13; W < 2^32, and both factors stay below 2^24.
+#define DESC_WS 19
+static_assert(DESC_NLD * 1020 * (DESC_ROWS - 1) < (1 << DESC_WS), "M fits below S in W");
+static_assert((long long)DESC_NLD * 1020 < (1ll << (32 - DESC_WS)), "W fits 32 bits");
+static_assert(DESC_ROWS <= (1 << DESC_WS) && DESC_WS < 23, "24-bit factors");
+
+// ORAD: the orientation radius patch_size / 2 the kernel was compiled for (15: the window's dwords and masks are
+// compile-time, see DescWindow), or 0: any patch_size, window tested at run time.
+template <int DESC_KPW, int DESC_NW, int DESC_OCC, int ORAD>
 __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan plan, const uint8_t* __restrict__ pyr, int patch_size,
                                                    const int32_t* __restrict__ sel_count,
                                                    const orbx_keypoint* __restrict__ sel_lkp,
@@ -1507,7 +1548,7 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
   const int slot0 = grp * DESC_KPB;
   if (slot0 >= count) return;  // whole workgroup
   DescLds2& lds = s_lds[wave];
-  const int pr = patch_size / 2;
+  const int pr = ORAD != 0 ? ORAD : patch_size / 2;
   // moment weights of the four bytes of patch dword column c when the keypoint's patch starts
   // `off` bytes into its first dword: {x - x_kp + pr for bytes inside the orientation window
   // (else 0), 1 for bytes inside the window (else 0)}, for v_dot4_u32_u8
@@ -1525,7 +1566,10 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
     s_mw[tid] = make_uint2(xw, on);
   }
   // keypoint-independent geometry of the DESC_NLD patch dwords a lane holds: dword
-  // lane + 64k is (row rowk[k], dword column (c0 + 4k) mod 12)
+  // lane + 64k is (row rowk[k], dword column (c0 + 4k) mod 12).  With a compile-time window rowk[] also carries
+  // bit DESC_WS, the factor of S in the moments' multiply-add chain: the patch addresses take RB * pitch off their
+  // scalar base instead (32-bit offsets wrap, and the 24-bit product keeps the bit: RB + 40 < 2^24).
+  constexpr uint32_t RB = ORAD != 0 ? 1u << DESC_WS : 0u;
   int rowk[DESC_NLD], c3[3];
   uint32_t rin = 0;  // bit k: the dword exists and its row is inside the orientation window
   {
@@ -1534,8 +1578,8 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
     for (int k = 0; k < DESC_NLD; k++) {
       // (the lane dwords past the neighbourhood's end, rows 41 and 42 at k = 7, take its last row: never stored,
       // weight 0 in the moments, and a border keypoint's unconditional loads stay inside the level)
-      rowk[k] = min(row, DESC_ROWS - 1);
-      __builtin_assume(rowk[k] >= 0 && rowk[k] < DESC_ROWS);
+      rowk[k] = min(row, DESC_ROWS - 1) | (int)RB;
+      __builtin_assume(rowk[k] >= (int)RB && rowk[k] < (int)RB + DESC_ROWS);
       if (k < 3) c3[k] = c;
       if (lane + 64 * k < DESC_ROWS * (DESC_PITCH / 4) && row >= DESC_R - pr && row <= DESC_R + pr) rin |= 1u << k;
       row += 5;
@@ -1577,7 +1621,7 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
     const int py0 = jb.y - DESC_R, ax0 = (jb.x - DESC_R) & ~3;
     offs[j] = jb.x - DESC_R - ax0;
     // (wraps for a neighbourhood that starts before the level; the sums below bring it back)
-    const uint32_t base = (uint32_t)(py0 * jb.pitch + ax0);
+    const uint32_t base = (uint32_t)(py0 * jb.pitch + ax0) - RB * (uint32_t)jb.pitch;
     const int kind = desc_kind(jb);
     if (kind == DESC_INSIDE) {
 #pragma unroll
@@ -1588,9 +1632,9 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
           regs[j][k] = *reinterpret_cast<const uint32_t*>(jb.img + (base + (__umul24((uint32_t)rowk[k], (uint32_t)jb.pitch) + 4u * (uint32_t)c3[k % 3])));
       }
     } else if (kind == DESC_TOP) {
-      desc_fetch_border<DESC_TOP>(jb, base, rowk, c3, regs[j]);
+      desc_fetch_border<DESC_TOP, RB>(jb, base, rowk, c3, regs[j]);
     } else {
-      desc_fetch_border<DESC_CLIPPED>(jb, base, rowk, c3, regs[j]);
+      desc_fetch_border<DESC_CLIPPED, RB>(jb, base, rowk, c3, regs[j]);
     }
   }
 
@@ -1610,13 +1654,30 @@ __global__ __launch_bounds__(64 * DESC_NW, DESC_OCC) void k_describe2(OrbxPlan p
 #pragma unroll
       for (int m = 0; m < 3; m++) mw[m] = s_mw[off * (DESC_PITCH / 4) + c3[m]];
       uint32_t X = 0, S = 0, M = 0;
+      if constexpr (ORAD != 0) {
+        // compile-time window: only the dwords some lane needs, a lane-range mask only where the range is not the
+        // whole wave, and S carried above M in one multiply-add chain (bounds: DESC_WS)
+        using Wn = DescWindow<ORAD>;
+        uint32_t W = 0;
 #pragma unroll
-      for (int k = 0; k < DESC_NLD; k++) {
-        const uint32_t z = regs[j][k] & (uint32_t)(-(int32_t)((rin >> k) & 1u));
-        X = __builtin_amdgcn_udot4(z, mw[k % 3].x, X, false);
-        const uint32_t rs = __builtin_amdgcn_udot4(z, mw[k % 3].y, 0u, false);
-        S += rs;
-        M += __umul24((uint32_t)rowk[k], rs);  // (rows < 41, rs <= 1020: the full-rate 24-bit multiply-add)
+        for (int k = 0; k < DESC_NLD; k++) {
+          if (Wn::none(k)) continue;
+          const uint32_t z = Wn::all(k) || (lane >= Wn::lane_lo(k) && lane < Wn::lane_hi(k)) ? regs[j][k] : 0u;
+          X = __builtin_amdgcn_udot4(z, mw[k % 3].x, X, false);
+          const uint32_t rs = __builtin_amdgcn_udot4(z, mw[k % 3].y, 0u, false);
+          W += __umul24((uint32_t)rowk[k], rs);  // (rowk[] carries RB)
+        }
+        S = W >> DESC_WS;
+        M = W & ((1u << DESC_WS) - 1);
+      } else {
+#pragma unroll
+        for (int k = 0; k < DESC_NLD; k++) {
+          const uint32_t z = regs[j][k] & (uint32_t)(-(int32_t)((rin >> k) & 1u));
+          X = __builtin_amdgcn_udot4(z, mw[k % 3].x, X, false);
+          const uint32_t rs = __builtin_amdgcn_udot4(z, mw[k % 3].y, 0u, false);
+          S += rs;
+          M += __umul24((uint32_t)rowk[k], rs);  // (rows < 41, rs <= 1020: the full-rate 24-bit multiply-add)
+        }
       }
       pm[0][j] = (int)X - __mul24(pr, (int)S);  // (S <= 8 x 1020, pr <= 20: 24-bit operands)
       pm[1][j] = (int)M - __mul24(DESC_R, (int)S);
@@ -1993,9 +2054,12 @@ hipError_t orbx_launch_describe(hipStream_t s, const OrbxPlan& plan, int n_frame
   if (plan.out_cap <= 0) return hipSuccess;
   // few keypoints in flight (single frames, small batches): one keypoint per wave, four times the
   // workgroups, a quarter of the serial work per wave; else four per wave
+  // patch_size 31 (the default) runs the kernels compiled for its orientation window, every other size the
+  // run-time window
+  const bool win31 = patch_size == 31;
   if ((long long)plan.out_cap * n_frames <= 8192) {
     dim3 grid(n_frames, (plan.out_cap + 3) / 4);
-    hipLaunchKernelGGL((k_describe2<1, 4, 1>), grid, dim3(256), 0, s, plan, d_pyr, patch_size, d_sel_count, d_sel_lkp,
+    hipLaunchKernelGGL((win31 ? k_describe2<1, 4, 1, 15> : k_describe2<1, 4, 1, 0>), grid, dim3(256), 0, s, plan, d_pyr, patch_size, d_sel_count, d_sel_lkp,
                        d_sel_resp, d_out_count, d_out_lkp, d_out_resp, d_out_level, d_out_kp, d_out_kp16, d_out_angle, d_out_desc, d_feedback,
                        h_feedback, host);
   } else {
@@ -2004,7 +2068,7 @@ hipError_t orbx_launch_describe(hipStream_t s, const OrbxPlan& plan, int n_frame
     // (867 vs 831 us).  Earlier, per 256 frames: 8-wave workgroups at 6 waves per SIMD (the trig -- two threads per
     // keypoint -- fills a wave: -1.8 % instructions) 203 us, 7-wave workgroups 221 us.
     dim3 grid(n_frames, (plan.out_cap + 15) / 16);
-    hipLaunchKernelGGL((k_describe2<4, 4, 6>), grid, dim3(256), 0, s, plan, d_pyr, patch_size, d_sel_count, d_sel_lkp,
+    hipLaunchKernelGGL((win31 ? k_describe2<4, 4, 6, 15> : k_describe2<4, 4, 6, 0>), grid, dim3(256), 0, s, plan, d_pyr, patch_size, d_sel_count, d_sel_lkp,
                        d_sel_resp, d_out_count, d_out_lkp, d_out_resp, d_out_level, d_out_kp, d_out_kp16, d_out_angle, d_out_desc, d_feedback,
                        h_feedback, host);
   }

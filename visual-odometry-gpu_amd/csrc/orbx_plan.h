@@ -415,55 +415,88 @@ inline int pyrblur_first_pass_rows(const OrbxPlan& plan, const OrbxBandMap& bm, 
   fast_band_rows(bm, l, top_rows - 1, &y0, &rows);
   return std::min(plan.L[l].h, y0 + rows + ORBX_TOP_MARGIN);
 }
+//
+// The early band.  With the first pass cut unevenly (make_bandmap, first_h) tile row 0 of a level ends at h0, where
+// most frames have filled their cap: such a frame has every keypoint in rows < h0, and nothing of it reads a row at
+// or below h0 + ORBX_TOP_MARGIN.  The FAST units of the first launch (tile rows 0 and 1) read up to the end of tile
+// row 1, D, plus their context: a pixel's ring reaches 3 rows and the NMS window R rows below a unit's last row, so
+// R + 3 rows for the streaming kernel (orbx_fast4.hip) and for the LDS tile kernel alike (orbx_fast.hip loads its
+// whole LDS tile, more rows than that, but looks at nothing below the unit's rows + R + 3).  So the rows
+// [P, D + ORBX_TOP_MARGIN) with P = max(h0 + ORBX_TOP_MARGIN, D + R + 3) are read only for the frames that did not
+// fill in tile row 0: they can go to the second pass as strips of their own whose skip test looks at tile row 0
+// alone (na = 1).  pyrblur_early_rows: P of a level, or the end of the first pass where there is no such band (no
+// uneven cut, or the first pass covers the level: then the level has no second-pass strips and no verdict).
+inline int pyrblur_early_rows(const OrbxPlan& plan, const OrbxBandMap& bm, int l, int top_rows, int nms_radius) {
+  const int late = pyrblur_first_pass_rows(plan, bm, l, top_rows);
+  if (top_rows != 2 || bm.tiles_y[l] <= top_rows || bm.first_h[l][0] <= 0 || late >= plan.L[l].h) return late;
+  const int h0 = bm.first_h[l][0], D = h0 + bm.first_h[l][1];
+  return std::min(late, std::max(h0 + ORBX_TOP_MARGIN, D + nms_radius + 3));
+}
+// strips per row band of a level: 62 dwords that hold image pixels per strip, one more in the first and in the last
+// strip (their outer neighbour is a reflection, not another strip's dword).  The padding dwords beyond are not
+// written by the kernel: they are zeroed when the plan is set.
+inline int pyrblur_strips_x(int w) {
+  const int dw = (w + 3) / 4;
+  return dw <= 64 ? 1 : (dw - 2 + 61) / 62;
+}
+// estimated instructions per strip row: level 0 copies, the 8-byte-window levels resize, the others gather; a band
+// pays 4 warm-up rows on top of its own
+inline int pyrblur_row_cost(int l, int win8) { return l == 0 ? 35 : win8 == 1 ? 80 : 90; }
+#define ORBX_PYRBLUR_WARMUP_ROWS 4
+// early_rows (optional, parts 1 and 2; only set_plan passes it): per level, the row at which the first pass ends
+// instead of pyrblur_first_pass_rows' (0, or anything outside (0, that row): no early band for the level).
 inline size_t build_pyrblur_tiles(const OrbxPlan& plan, int max_rows, std::vector<OrbxTileDesc>* out,
                                   bool heavy_first = false, int part = 0, const OrbxBandMap* bm = nullptr,
-                                  int top_rows = 0) {
+                                  int top_rows = 0, const int* early_rows = nullptr) {
   size_t cnt = 0;
   if (out) out->clear();
   bool have_reporter = false;
   for (int l = 0; l < plan.nlevels; l++) {
     const OrbxLevel& L = plan.L[l];
-    // dwords that hold image pixels: 62 per strip, one more in the first and in the last strip (their
-    // outer neighbour is a reflection, not another strip's dword).  The padding dwords beyond are not
-    // written by this kernel: they are zeroed when the plan is set.
-    const int dw = (L.w + 3) / 4;
-    const int ntx = dw <= 64 ? 1 : (dw - 2 + 61) / 62;
+    const int ntx = pyrblur_strips_x(L.w);
     const int split = part == 0 ? L.h : pyrblur_first_pass_rows(plan, *bm, l, top_rows);
-    const int r0 = part == 2 ? split : 0, r1 = part == 1 ? split : L.h;
-    if (r1 <= r0) continue;
-    const int nb = (r1 - r0 + max_rows - 1) / max_rows, rows = (r1 - r0 + nb - 1) / nb;
-    for (int b = 0; b < nb; b++)
-      for (int tx = 0; tx < ntx; tx++) {
-        OrbxTileDesc d{};
-        d.l = l;
-        d.tx = tx;
-        d.ty = r0 + b * rows;
-        d.f = std::min(rows, r1 - d.ty);
-        d.w = L.w;
-        d.h = L.h;
-        d.pitch = L.pitch;
-        d.u0 = L.xtab_off;
-        d.u1 = L.ytab_off;
-        d.u2 = L.win8;
-        d.pad = (uint32_t)ntx;
-        d.img_off = (uint64_t)L.img_off;
-        if (part == 2) {
-          d.stat_index = (uint32_t)(l * ORBX_MAX_BANDS);
-          d.mask_off = ((uint64_t)(uint32_t)std::min(top_rows, bm->tiles_y[l]) << 32) | (uint32_t)L.cap;
-          if (b == 0 && tx == 0 && !have_reporter) {  // this strip's wave reports the verdicts of all the frame's levels
-            d.mask_off |= 1ull << 62;
-            have_reporter = true;
+    const int early = part != 0 && early_rows && early_rows[l] > 0 && early_rows[l] < split ? early_rows[l] : split;
+    // row ranges of this part: {first row, end, tile rows of the skip test}
+    const int seg[2][3] = {{part == 2 ? early : 0, part == 1 ? early : part == 2 ? split : L.h, 1},
+                           {split, part == 2 ? L.h : split, std::min(top_rows, bm ? bm->tiles_y[l] : 0)}};
+    for (int s = 0; s < 2; s++) {
+      const int r0 = seg[s][0], r1 = seg[s][1];
+      if (r1 <= r0) continue;
+      const int nb = (r1 - r0 + max_rows - 1) / max_rows, rows = (r1 - r0 + nb - 1) / nb;
+      for (int b = 0; b < nb; b++)
+        for (int tx = 0; tx < ntx; tx++) {
+          OrbxTileDesc d{};
+          d.l = l;
+          d.tx = tx;
+          d.ty = r0 + b * rows;
+          d.f = std::min(rows, r1 - d.ty);
+          d.w = L.w;
+          d.h = L.h;
+          d.pitch = L.pitch;
+          d.u0 = L.xtab_off;
+          d.u1 = L.ytab_off;
+          d.u2 = L.win8;
+          d.pad = (uint32_t)ntx;
+          d.img_off = (uint64_t)L.img_off;
+          if (part == 2) {
+            d.stat_index = (uint32_t)(l * ORBX_MAX_BANDS);
+            d.mask_off = ((uint64_t)(uint32_t)seg[s][2] << 32) | (uint32_t)L.cap;
+            // this strip's wave reports the verdicts of all the frame's levels (never a strip of an early band: the
+            // report comes before the strip's own test, but the levels' verdicts are those of the whole first pass)
+            if (s == 1 && b == 0 && tx == 0 && !have_reporter) {
+              d.mask_off |= 1ull << 62;
+              have_reporter = true;
+            }
+          }
+          if (d.f > 0) {
+            if (out) out->push_back(d);
+            cnt++;
           }
         }
-        if (d.f > 0) {
-          if (out) out->push_back(d);
-          cnt++;
-        }
-      }
+    }
   }
   if (heavy_first && out) {
-    // estimated instructions per strip row: level 0 copies, the 8-byte-window levels resize, the others gather
-    auto cost = [](const OrbxTileDesc& d) { return (d.f + 4) * (d.l == 0 ? 35 : d.u2 == 1 ? 80 : 90); };
+    auto cost = [](const OrbxTileDesc& d) { return (d.f + ORBX_PYRBLUR_WARMUP_ROWS) * pyrblur_row_cost(d.l, d.u2); };
     std::stable_sort(out->begin(), out->end(),
                      [&](const OrbxTileDesc& a, const OrbxTileDesc& b) { return cost(a) > cost(b); });
   }
@@ -560,6 +593,16 @@ struct OrbxTableCapacity {
   size_t small;  // fused pyramid + blur, short bands
   size_t taps;   // resize-tap table (OrbxResizeTap entries)
 };
+// Most strips the early bands add to a second-pass table of the fused pyramid + blur kernel (build_pyrblur_tiles with
+// early_rows): a level's second pass then covers [P, S) and [S, h) in ceil((S - P) / RH) + ceil((h - S) / RH) bands
+// with S - P <= ORBX_TOP_MARGIN <= RH, that is one band more than the ceil(h / RH) of the whole table at most,
+// whatever h, the cut h0 and the depth D are.  (Strips per band grow with the width: the maximum's bound every size.)
+static_assert(ORBX_TOP_MARGIN <= ORBX_PYRBLUR_RH, "an early band is one band");
+inline size_t pyrblur_early_strips_bound(const OrbxPlan& M) {
+  size_t n = 0;
+  for (int l = 0; l < M.nlevels; l++) n += (size_t)pyrblur_strips_x(M.L[l].w);
+  return n;
+}
 inline size_t fast_tiles_upper_bound(const OrbxPlan& M, int nms_radius, bool strips) {
   size_t cap = 0;
   for (int l = 0; l < M.nlevels; l++) {
@@ -579,7 +622,8 @@ inline int table_capacity(const orbx_params& p, const OrbxPlan& M, int fast_impl
   const size_t t1 = blur_tiles_for_impl(blur_impl, M, nullptr);
   const size_t t2 = build_frame_tiles(M, ORBX_PYR2_TW, ORBX_PYR2_TH, true, nullptr);
   const size_t t3 = build_pyrblur_tiles(M, ORBX_PYRBLUR_RH, nullptr);
-  cap->frame = std::max(std::max(t1, t2), t3) + 256;  // (+ the extra bands of a split table)
+  // (+ the extra bands of a split table, + the early bands of a second-pass table)
+  cap->frame = std::max(std::max(t1, t2), t3) + 256 + pyrblur_early_strips_bound(M);
   cap->small = build_pyrblur_tiles(M, ORBX_PYRBLUR_RH_SMALL, nullptr) + 64;
   cap->taps = taps_count(M) + 16;
   return ORBX_OK;
@@ -644,6 +688,25 @@ inline int choose_first_cut(const uint32_t* hist, int depth, int nms_radius, int
     }
   if (cost_milli) *cost_milli = best_cost;
   return best;
+}
+
+// ---- whether a level's early band pays (pyrblur_early_rows) ----------------------------------------------------------
+// Per strip column, with q the share of frames that fill their cap within tile row 0 (fill row <= h0, from the same
+// histogram): those frames save the band's rows and pay for a strip that leaves -- tile record, the probe of the
+// tile-row statistic, return: ORBX_PYRBLUR_SKIP_EXIT instructions, counted in k_pyrblur's assembly along the path of a
+// skipped strip that is not the reporter (profiles/pyramid_early_band) -- and the others pay the warm-up rows of one
+// more band.  In the per-row instruction estimates of build_pyrblur_tiles:
+//   q * rows * cost > (1 - q) * ORBX_PYRBLUR_WARMUP_ROWS * cost + q * ORBX_PYRBLUR_SKIP_EXIT
+// Never for an empty histogram (nothing is known: 1080p, the LDS tile kernel), nor for a band of a row or two.
+#define ORBX_PYRBLUR_SKIP_EXIT 100
+#define ORBX_PYRBLUR_EARLY_MIN_ROWS 3
+inline bool early_band_pays(const uint32_t* hist, int h0, int rows, int row_cost, int exit_cost = ORBX_PYRBLUR_SKIP_EXIT) {
+  uint64_t total = 0;
+  for (int b = 0; b < ORBX_FILL_BUCKETS; b++) total += hist[b];
+  if (!total || rows < ORBX_PYRBLUR_EARLY_MIN_ROWS) return false;
+  const uint64_t out = fill_exits(hist, h0), stay = total - out;
+  return out * (uint64_t)rows * (uint64_t)row_cost >
+         stay * (uint64_t)(ORBX_PYRBLUR_WARMUP_ROWS * row_cost) + out * (uint64_t)exit_cost;
 }
 
 }  // namespace orbx_geom
