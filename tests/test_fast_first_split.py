@@ -1,4 +1,4 @@
-"""The first pass of the FAST tile rows cut unevenly (csrc/orbx_plan.h: make_bandmap with first-pass heights; csrc/orbx_api.cpp:
+"""The first pass of the FAST tile rows cut unevenly (csrc/orbx_plan.h: make_bandmap with first-pass heights; csrc/orbx_adapt.h:
 adapt_tile_rows).  Tile row 0 of a level ends where most frames have filled their cap, and the units of the short
 tile row 1 exit for those frames -- only the partition of the rows into units moves, so every result must stay what the
 oracle computes.  ORBX_TOP_ROWS=2:r0,r1,... forces the rows of tile row 0 per level (read when a context is created); the cuts

@@ -207,7 +207,7 @@ def test_host_results_written_by_the_describe_kernel(pkg, batches256, oracle256,
 
 def test_adaptive_first_pass_changes_the_tile_rows_not_the_results(pkg, batches256, oracle256):
     """The adaptive mode of the top-rows-first pipeline learns in which row the levels' caps fill and shortens the FAST
-    tile rows so that the first pass ends just below (orbx_api.cpp, adapt_tile_rows): after a few batches the tile
+    tile rows so that the first pass ends just below (orbx_adapt.h, adapt_tile_rows): after a few batches the tile
     table of a frame has more, shorter tile rows.  Every batch before, during and after the change equals the oracle;
     with the early exit switched off the default tile rows come back, and again with it on the learned ones."""
     import torch

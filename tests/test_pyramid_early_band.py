@@ -1,5 +1,5 @@
 """The early band of the fused pyramid + blur kernel's second pass (csrc/orbx_plan.h: pyrblur_early_rows,
-build_pyrblur_tiles with early_rows; csrc/orbx_api.cpp: set_plan).  With the first pass of the FAST tile rows cut at h0
+build_pyrblur_tiles with early_rows; csrc/orbx_adapt.h: choose_early_bands).  With the first pass of the FAST tile rows cut at h0
 (tile row 0) and D (end of tile row 1), the pyramid rows [P, D + 21) with P = max(h0 + 21, D + R + 3) leave the first
 pyramid launch and become second-pass strips that are skipped for the frames whose cap filled within tile row 0.  Only
 where rows are produced moves, so every result must stay what the oracle computes; a row that was wrongly left out

@@ -23,7 +23,7 @@ STEP_KERNEL = "k_level_select"  # launched exactly once per step (batch): its di
 
 
 SKIP_STEPS = 0  # warm-up steps of every run (argv[4]): their dispatches are left out -- the adaptive first pass
-# re-partitions the FAST tile rows after the second batch (orbx_api.cpp, adapt_tile_rows)
+# re-partitions the FAST tile rows after the second batch (orbx_adapt.h, adapt_tile_rows)
 
 
 def drop_warmup(rows, steps):

@@ -17,6 +17,7 @@
 #include "orbx_host.h"
 
 using namespace orbx_host;
+using namespace orbx_adapt;
 
 namespace {
 thread_local std::string g_create_error;
@@ -199,9 +200,7 @@ int check_device_frames(orbx_ctx* c, const void* d_frames, int n, int n_min, int
 
 namespace {
 
-// slots per frame of a result block written under plan P (nfeatures too small for any quota: one empty slot)
-int slots_per_frame(const OrbxPlan& P) { return P.out_cap > 0 ? P.out_cap : 1; }
-
+// ---- the environment switches ----
 // an integer environment switch (the ones read once per process keep the value in a static of their reader)
 int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -228,41 +227,50 @@ int top_rows_env() {
 // Read when a context is created (A/B timing in one process).
 int fast_impl_env() { return env_int("ORBX_FAST_IMPL", 4) == 3 ? 3 : 4; }
 
-// The switches of the unevenly cut first pass (orbx_host.h): fields behind the number of ORBX_TOP_ROWS, separated by
-// colons and read when a context is created (the number itself is read once per process, above) --
-//   ORBX_TOP_ROWS=2:equal          the two tile rows of the first pass stay equal halves (A/B timing)
-//   ORBX_TOP_ROWS=2:68,65,0,61     rows of tile row 0 per level, forced (tests; 0: leave the level to the chooser)
-//   ORBX_TOP_ROWS=2:trace          every decision of the chooser goes to stderr
-//   ORBX_TOP_ROWS=2:late           no early bands: the first pyramid pass ends below tile row 1 on every level (A/B timing)
-void first_split_env(orbx_ctx* c) {
-  const char* e = getenv("ORBX_TOP_ROWS");
-  e = e ? std::strchr(e, ':') : nullptr;
-  while (e && *e == ':') {
-    e++;
-    if (!std::strncmp(e, "equal", 5)) {
-      c->first_split = false;
-    } else if (!std::strncmp(e, "trace", 5)) {
-      c->split_trace = true;
-    } else if (!std::strncmp(e, "late", 4)) {
-      c->early_band = false;
-    } else {
-      for (int l = 0; l < ORBX_MAX_LEVELS; l++) {
-        char* end = nullptr;
-        const long v = std::strtol(e, &end, 10);
-        if (end == e) break;
-        c->cut_force[l] = (int)std::min<long>(std::max<long>(v, 0), 0xffff);
-        e = end;
-        if (*e != ',') break;
-        e++;
-      }
-    }
-    e = std::strchr(e, ':');
-  }
+// ORBX_BLUR_IMPL (read when a context is created): 2 (default) k_blur3, 4 pixels per lane; 3: k_blur4, 16 pixels per
+// lane (measured 9 % slower: the blur's vertical pass dominates its instruction count, and 94 registers leave 5
+// waves per SIMD); 1: the first-generation LDS tile kernel.  The strip table is built for the kernel that reads it.
+int blur_impl_env() {
+  const int v = env_int("ORBX_BLUR_IMPL", 2);
+  return v >= 1 && v <= 3 ? v : 2;
 }
-// most rows of a unit of the context's FAST kernel
-int fast_unit_rows_max(const orbx_ctx* c) {
-  return c->fast_impl == 4 ? ORBX_FAST_UNIT_ROWS_MAX : orbx_fast3_tile_h(c->p.nms_window / 2);
+
+// ORBX_FAST_EARLY=0: every tile of FAST + NMS does the full work (results are identical).  Otherwise the tiles that
+// provably cannot contribute to the first `cap` row-major survivors exit early (see decode_band in the kernels).
+int fast_early_env() {
+  static const int v = env_int("ORBX_FAST_EARLY", 1);
+  return v;
 }
+
+// ORBX_FUSE=0: separate pyramid and blur kernels (same results; A/B timing and per-kernel profiles)
+int fuse_env() {
+  static const int v = env_int("ORBX_FUSE", 1);
+  return v;
+}
+
+// ORBX_GRAPH=0: every batch is enqueued launch by launch, none replayed from a captured graph (run_batch)
+int graph_env() {
+  static const int v = env_int("ORBX_GRAPH", 1);
+  return v;
+}
+
+// ORBX_SELECT_SPREAD=0/1 forces the fused / the three-kernel selection (A/B timing); frames whose candidates do not
+// fit the fused kernel's LDS take the three kernels whatever it says (orbx_launch_level_select_auto)
+int select_spread_env() {
+  static const int v = env_int("ORBX_SELECT_SPREAD", -1);
+  return v;
+}
+
+// ---- what the switches and the context's own settings add up to ----
+bool fused_pyrblur(const orbx_ctx* c) {
+  return fuse_env() && c->fuse && c->p.blur_levels == ORBX_BLUR_ALL && c->p.blur_kind == ORBX_BLUR_SEP16;
+}
+bool fast_early_on(const orbx_ctx* c) { return fast_early_env() && c->fast_early; }
+bool blur_enabled(const orbx_ctx* c) { return c->p.blur_levels != ORBX_BLUR_NONE; }
+const uint8_t* final_pyr(const orbx_ctx* c) { return blur_enabled(c) ? cur_lane(c).d_pyr_blur : cur_lane(c).d_pyr; }
+
+// slots per frame of a result block written under plan P (nfeatures too small for any quota: one empty slot)
+int slots_per_frame(const OrbxPlan& P) { return P.out_cap > 0 ? P.out_cap : 1; }
 
 // 8-bit bilinear coefficient tables: OpenCV 4.x generic 8UC1 INTER_LINEAR path
 // (imgproc/src/resize.cpp: scale = 1/((double)dst/src); fx = (float)((dx+0.5)*
@@ -407,12 +415,15 @@ void free_lane(orbx_ctx* c, Lane& L) {
   L.pool_stream = nullptr;
 }
 
-bool fused_pyrblur(const orbx_ctx* c);
-bool fast_early_on(const orbx_ctx* c);
-int top_rows_env();
+// the adaptive first pass (orbx_adapt.h) only where the top-rows-first pipeline can run at all
 bool tile_prefs_apply(const orbx_ctx* c) {
-  return c->top_mode == 2 && top_rows_env() > 0 && fast_early_on(c) && fused_pyrblur(c);
+  return c->adapt.top_mode == 2 && top_rows_env() > 0 && fast_early_on(c) && fused_pyrblur(c);
 }
+// what the scheduler's steps see of the context, and where its trace goes
+OrbxAdaptGeom adapt_geom(const orbx_ctx* c) {
+  return OrbxAdaptGeom{c->plan, c->bm_fast, c->p.nms_window / 2, c->fast_impl, top_rows_env()};
+}
+FILE* adapt_trace(const orbx_ctx* c) { return c->adapt.split_trace ? stderr : nullptr; }
 
 // a table of the new plan goes to its pool
 int upload_tiles(orbx_ctx* c, int table, const std::vector<OrbxTileDesc>& t, const char* too_large) {
@@ -453,36 +464,24 @@ int set_plan(orbx_ctx* c, int w, int h) {
   make_tilemap(plan, ORBX_BLUR_TW, ORBX_BLUR_TH, true, &c->tm_blur);
   // (the adaptive first pass's shorter tile rows only where the top-rows-first pipeline can run at all: with the
   // early exit or the fused kernel switched off every tile works, and the default rows have the smaller halo share)
-  c->prefs_applied = tile_prefs_apply(c);
+  OrbxAdapt& a = c->adapt;
+  a.prefs_applied = tile_prefs_apply(c);
   st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4,
-                    c->prefs_applied ? c->tile_h_pref : nullptr);
-  if (c->prefs_applied && (st != ORBX_OK || (size_t)c->bm_fast.band_begin[c->bm_fast.nbands] > c->tiles[T_FAST].capacity)) {
+                    a.prefs_applied ? a.tile_h_pref : nullptr);
+  if (a.prefs_applied && (st != ORBX_OK || (size_t)c->bm_fast.band_begin[c->bm_fast.nbands] > c->tiles[T_FAST].capacity)) {
     // The learned tile rows give a table the pool cannot hold (the FAST table's capacity is an upper bound over every
     // preference, orbx_plan.h: this is a second line of defence).  What was learned is only a partition of the work:
     // forget it, take the default rows and run the batch -- a failure here would repeat with every batch of this size.
-    for (int l = 0; l < ORBX_MAX_LEVELS; l++) c->tile_h_pref[l] = 0;
-    c->prefs_applied = false;
+    forget_tile_rows(a);
     st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4, nullptr);
   }
   if (st != ORBX_OK) return fail(c, st, why);
   // the first pass cut unevenly (same number of tile rows, same pool): where the chooser or a forced cut says so
-  if (c->prefs_applied && c->first_split && top_rows_env() == 2) {
-    int first[ORBX_MAX_LEVELS][2] = {};
-    bool any = false;
-    for (int l = 0; l < plan.nlevels; l++) {
-      int a = c->cut_force[l] > 0 ? c->cut_force[l] : c->cut_pref[l];
-      if (a <= 0 || c->bm_fast.tiles_y[l] < 2) continue;
-      const int depth = 2 * c->bm_fast.tile_h[l], umax = fast_unit_rows_max(c);
-      if (c->cut_force[l] > 0)  // (a forced cut goes to the nearest one the kernel can run)
-        a = std::max(std::max(1, depth - umax), std::min(a, std::min(umax, std::min(depth, plan.L[l].h) - 1)));
-      first[l][0] = a;
-      first[l][1] = depth - a;
-      any = true;
-    }
-    if (any)  // (the first call above accepted these tile rows: this one cannot fail, and an illegal pair is ignored)
-      (void)make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4,
-                         c->prefs_applied ? c->tile_h_pref : nullptr, first);
-  }
+  // (the first call above accepted these tile rows: this one cannot fail, and an illegal pair is ignored)
+  int first[ORBX_MAX_LEVELS][2] = {};
+  if (first_pass_heights(a, adapt_geom(c), first))
+    (void)make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4,
+                       a.prefs_applied ? a.tile_h_pref : nullptr, first);
   const bool grouped = pyr_group_env() > 0;
   const int top = top_rows_env();
   std::vector<OrbxTileDesc> t;
@@ -490,27 +489,10 @@ int set_plan(orbx_ctx* c, int w, int h) {
   if ((st = upload_tiles(c, T_BLUR, t, "blur tile table exceeds pool")) != ORBX_OK) return st;
   build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped);
   if ((st = upload_tiles(c, T_PYRBLUR, t, "strip table exceeds pool")) != ORBX_OK) return st;
-  // Early bands (orbx_plan.h, pyrblur_early_rows): the rows between h0 + ORBX_TOP_MARGIN and the end of the first pass
-  // go to the second pass, behind a test on tile row 0 alone, on the levels where that pays by the fill rows the last
-  // observation window saw (early_band_pays) -- or, under a forced cut, wherever the band has three rows or more
-  // (tests: no histogram has been seen when their tables are built).
-  for (int l = 0; l < ORBX_MAX_LEVELS; l++) c->early_rows[l] = 0;
-  for (int l = 0; l < plan.nlevels; l++) {
-    const int late = pyrblur_first_pass_rows(plan, c->bm_fast, l, top);
-    const int P = c->early_band ? pyrblur_early_rows(plan, c->bm_fast, l, top, c->p.nms_window / 2) : late;
-    const bool forced = c->cut_force[l] > 0;
-    const bool pays = P < late && (forced ? late - P >= ORBX_PYRBLUR_EARLY_MIN_ROWS
-                                          : early_band_pays(c->fill_last[l], c->bm_fast.first_h[l][0], late - P,
-                                                            pyrblur_row_cost(l, plan.L[l].win8)));
-    c->early_rows[l] = pays ? P : late;
-    if (c->split_trace && c->bm_fast.first_h[l][0] > 0)
-      fprintf(stderr, "orbx early band: level %d cut %d first pass ended at %d, now ends at %d, band %d rows: %s\n", l,
-              c->bm_fast.first_h[l][0], late, c->early_rows[l], late - P,
-              pays ? (forced ? "split (forced cut)" : "split") : !c->early_band ? "late" : "kept");
-  }
-  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 1, &c->bm_fast, top, c->early_rows);
+  choose_early_bands(a, adapt_geom(c), adapt_trace(c));
+  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 1, &c->bm_fast, top, a.early_rows);
   if ((st = upload_tiles(c, T_PYRBLUR_TOP, t, "strip table exceeds pool")) != ORBX_OK) return st;
-  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 2, &c->bm_fast, top, c->early_rows);
+  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 2, &c->bm_fast, top, a.early_rows);
   if ((st = upload_tiles(c, T_PYRBLUR_REST, t, "strip table exceeds pool")) != ORBX_OK) return st;
   c->top_levels = OrbxTopLevels{};
   for (int l = 0; l < plan.nlevels; l++)
@@ -538,24 +520,6 @@ hipError_t launch_pyramid_auto(orbx_ctx* c, hipStream_t s, int n, const uint8_t*
                               d_in, in_stride, in_frame_stride, c->d_taps, cur_lane(c).d_pyr);
 }
 
-
-bool blur_enabled(const orbx_ctx* c) { return c->p.blur_levels != ORBX_BLUR_NONE; }
-// ORBX_FUSE=0: separate pyramid and blur kernels (same results; A/B timing and per-kernel profiles)
-bool fused_pyrblur(const orbx_ctx* c) {
-  static const int env = env_int("ORBX_FUSE", 1);
-  return env && c->fuse && c->p.blur_levels == ORBX_BLUR_ALL && c->p.blur_kind == ORBX_BLUR_SEP16;
-}
-const uint8_t* final_pyr(const orbx_ctx* c);
-
-// FAST + NMS of the batched path.  Tiles that provably cannot contribute to the
-// first `cap` row-major survivors exit early (see decode_band in the kernels);
-// ORBX_FAST_EARLY=0 disables that (every tile does the full work).
-int fast_early_env() {  // ORBX_FAST_EARLY=0: every tile does the full work (results are identical)
-  static const int v = env_int("ORBX_FAST_EARLY", 1);
-  return v;
-}
-bool fast_early_on(const orbx_ctx* c) { return fast_early_env() && c->fast_early; }
-
 // FAST + NMS over tiles [first, first + count) of the context's band-major table
 hipError_t launch_fast_tiles(orbx_ctx* c, hipStream_t s, int first, int count, int n, OrbxFastParams fp,
                              unsigned long long* stat, int chunk_scale = 1) {
@@ -576,159 +540,6 @@ hipError_t launch_fast_whole(orbx_ctx* c, hipStream_t s, int n, OrbxFastParams f
   // (a two-launch variant -- tile row 0 first, the rest in strips of several tiles per
   // workgroup -- was measured slower: the kernel boundary costs more than the cheaper exits save)
   return launch_fast_tiles(c, s, 0, c->tiles[T_FAST].count, n, fp, stat);
-}
-
-// ORBX_BLUR_IMPL (read when a context is created): 2 (default) k_blur3, 4 pixels per lane; 3: k_blur4, 16 pixels per
-// lane (measured 9 % slower: the blur's vertical pass dominates its instruction count, and 94 registers leave 5
-// waves per SIMD); 1: the first-generation LDS tile kernel.  The strip table is built for the kernel that reads it.
-int blur_impl_env() {
-  const int v = env_int("ORBX_BLUR_IMPL", 2);
-  return v >= 1 && v <= 3 ? v : 2;
-}
-const uint8_t* final_pyr(const orbx_ctx* c) { return blur_enabled(c) ? cur_lane(c).d_pyr_blur : cur_lane(c).d_pyr; }
-
-// Top-rows-first pipeline: wanted for the next batch?  (Eligibility -- fused kernel, early exit on, large
-// batch -- is checked where the launches are made.)
-bool top_rows_wanted(const orbx_ctx* c) {
-  if (top_rows_env() <= 0 || c->top_mode == 0) return false;
-  return c->top_mode == 1 || c->top_on;
-}
-// adaptive mode: look at the totals the second passes have reported so far (no waiting: whatever has arrived)
-void top_rows_update(orbx_ctx* c) {
-  if (c->top_mode != 2 || !c->h_feedback) return;
-  // ONE 64-bit load of the pinned pair (the device writes it as one 8-byte store of two lanes' dwords at best: a torn
-  // or stale pair, or a low half that has wrapped, only misleads this heuristic for one batch -- results never
-  // depend on it)
-  const uint64_t both = *reinterpret_cast<const volatile uint64_t*>(c->h_feedback);
-  const uint32_t sk = (uint32_t)both, pr = (uint32_t)(both >> 32);
-  const uint32_t dsk = sk - c->feedback_seen[0], dpr = pr - c->feedback_seen[1];
-  if (dsk + dpr > 0) {
-    c->feedback_seen[0] = sk;
-    c->feedback_seen[1] = pr;
-    const bool pays = 4ull * dsk >= (unsigned long long)(dsk + dpr);  // a quarter of the levels skipped
-    if (!pays && c->top_on) c->top_single_batches = 0;
-    c->top_on = pays;
-  }
-  if (!c->top_on && ++c->top_single_batches >= 128) {  // probe again
-    c->top_on = true;
-    c->top_single_batches = 0;
-  }
-}
-
-// Adaptive first pass.  The top-rows-first pipeline produces and searches the first ORBX_TOP_ROWS FAST tile rows of
-// every level before anything else; with the default tile rows (<= 47 rows, balanced) that is ~90 rows per level,
-// while a level's cap is typically full after 40-75 rows on the benchmark stream -- and everything a first-pass tile
-// row holds beyond that row is work nobody reads.  The selection kernel reports, per level, the row in which the
-// cap filled (maximum over the frames of a batch; the whole level if it never did); from the maximum over the last
-// two observation windows, plus a margin, this picks SHORTER tile rows for the level, so that the first pass ends
-// just below that row.  Only the partition of the work changes, never a result; a stream whose caps fill lower
-// gets taller tile rows back (at most the default), and a frame whose cap is not full after the first pass is
-// finished by the second one as always.  Returns true if the tile tables must be rebuilt (the caller forces
-// set_plan, which waits for the batches in flight: it happens a few times per stream, not per batch).
-bool adapt_tile_rows(orbx_ctx* c) {
-  if (!tile_prefs_apply(c) || !c->h_feedback || c->plan_w <= 0) return false;
-  const int top = top_rows_env(), nl = c->plan.nlevels;
-  bool any = false;
-  for (int l = 0; l < nl; l++) {
-    const uint32_t v = c->h_feedback[2 + l];  // (whatever has arrived; a stale or torn word only misleads the heuristic)
-    if (v) {
-      c->need_cur[l] = std::max(c->need_cur[l], std::min<uint32_t>(v, (uint32_t)c->plan.L[l].h));
-      any = true;
-      // (the same batch may be counted twice, or not at all: only the shares matter)
-      for (int b = 0; b < ORBX_FILL_BUCKETS; b++) {
-        const uint32_t cnt = c->h_feedback[ORBX_FEEDBACK_HIST + l * ORBX_FILL_BUCKETS + b];
-        c->fill_cur[l][b] += std::min<uint32_t>(cnt, 1u << 20);
-      }
-    }
-  }
-  if (!any || ++c->need_batches < c->need_window) return false;
-  // end of an observation window (2, 4, 8, 16, then every 32 batches)
-  c->need_batches = 0;
-  c->need_window = std::min(2 * c->need_window, 32);
-  bool change = false, grow = false;
-  int want[ORBX_MAX_LEVELS] = {};
-  for (int l = 0; l < nl; l++) {
-    const uint32_t need = std::max(c->need_cur[l], c->need_prev[l]);
-    c->need_prev[l] = c->need_cur[l];
-    c->need_cur[l] = 0;
-    if (need == 0) {
-      want[l] = c->tile_h_pref[l];
-      continue;
-    }
-    const int rows = (int)need + std::max(4, (int)need / 10);  // margin: the next frames' caps may fill a little lower
-    // the default tile rows of the level (make_bandmap: <= dflt rows, balanced)
-    const int dflt = orbx_fast3_tile_h(c->p.nms_window / 2), lh = c->plan.L[l].h;
-    const int bal = (lh + (lh + dflt - 1) / dflt - 1) / ((lh + dflt - 1) / dflt);
-    int hh = (rows + top - 1) / top;
-    // the streaming FAST kernel walks whole groups of 7 centre rows (tile rows + 2 x NMS radius): a height that is
-    // one or two rows into a new group gives them back where at least 3 rows of margin remain (measured: level 0 at
-    // 40 instead of 41 rows, FAST -4.6 %, pyramid -2.9 %; rounding every level to a group boundary costs more than
-    // it saves)
-    if (c->fast_impl == 4) {
-      const int over = (hh + 2 * (c->p.nms_window / 2)) % 7;
-      if ((over == 1 || over == 2) && top * (hh - over) >= (int)need + 3) hh -= over;
-    }
-    if (hh >= bal || lh <= top * hh) hh = 0;  // the default rows do
-    const int eff = hh ? hh : bal, cur = c->bm_fast.tile_h[l], asked = c->tile_h_pref[l] ? c->tile_h_pref[l] : bal;
-    // (a level that neither must grow nor gains three rows keeps its height when another level makes the tables change)
-    want[l] = ((eff > cur && (int)need > top * cur) || eff + 2 < std::min(cur, asked)) ? hh : c->tile_h_pref[l];
-    // the first pass has become too short for this stream -- caps fill BELOW it (the margin is used up): follow
-    if (eff > cur && (int)need > top * cur) grow = true;
-    // shrink only for a gain of three rows or more (`cur` may be taller than what was asked for: a level never has
-    // more tile rows than the level above)
-    else if (eff + 2 < std::min(cur, asked)) change = true;
-  }
-  // Where to cut the first pass.  Its two tile rows are equal halves by default, and a unit of tile row 1 may leave
-  // only when the rows strictly above it hold the cap: no frame fills its cap in the upper half, so every frame
-  // walks both.  With tile row 0 ending where most frames HAVE filled, the short tile row 1 runs for the others
-  // alone (its units are dispatched a whole tile row of every frame later: the statistics are complete by then).
-  // The cut per level comes from the fill-row histograms of the last two windows and the cost model of
-  // choose_first_cut (orbx_plan.h), for the depth the level has after this decision; the tables are rebuilt for a
-  // cut only if it saves a group or more per strip on some level, or if a cut in force has stopped paying.  Streaming
-  // kernel only (the model counts its groups of 7 rows), and only where the fused selection reports the histograms.
-  const bool heights_change = grow || change;
-  const bool split = c->first_split && top == 2 && c->fast_impl == 4;
-  const int R = c->p.nms_window / 2;
-  int cut_want[ORBX_MAX_LEVELS] = {};
-  bool cut_change = false;
-  for (int l = 0; l < nl; l++) {
-    uint32_t hist[ORBX_FILL_BUCKETS];
-    uint64_t total = 0;
-    for (int b = 0; b < ORBX_FILL_BUCKETS; b++) {
-      hist[b] = c->fill_cur[l][b] + c->fill_prev[l][b];
-      c->fill_last[l][b] = hist[b];  // (what set_plan decides the early bands from, if this window has it called)
-      c->fill_prev[l][b] = c->fill_cur[l][b];
-      c->fill_cur[l][b] = 0;
-      total += hist[b];
-    }
-    if (!split || c->cut_force[l] > 0 || c->bm_fast.tiles_y[l] < 2) continue;
-    const int dflt = orbx_fast3_tile_h(R), lh = c->plan.L[l].h;
-    const int bal = (lh + (lh + dflt - 1) / dflt - 1) / ((lh + dflt - 1) / dflt);
-    const int th_after = heights_change ? (want[l] ? want[l] : bal) : c->bm_fast.tile_h[l];
-    const int depth = 2 * th_after;
-    // (new tile-row heights void the cut in force: its pair no longer adds up to the depth)
-    const int in_force = !heights_change && c->bm_fast.first_h[l][0] > 0 ? c->bm_fast.first_h[l][0] : 0;
-    int cost_new = 0;
-    const int cut_new = total && lh > depth ? choose_first_cut(hist, depth, R, ORBX_FAST_UNIT_ROWS_MAX, &cost_new) : 0;
-    const int cost_now = first_pass_cost_milli(hist, depth, in_force ? in_force : depth / 2, R);
-    if (!total || lh <= depth) cost_new = cost_now;
-    const bool pays = cost_now - cost_new >= 1000, stopped = in_force && !cut_new && cost_now > cost_new;
-    cut_want[l] = heights_change || pays || stopped ? cut_new : c->cut_pref[l];
-    if (cut_want[l] != in_force && (pays || stopped)) cut_change = true;
-    if (c->split_trace) {
-      fprintf(stderr, "orbx split: batch %lld level %d need %u depth %d cut %d -> %d (%d -> %d milli-groups) fill rows:",
-              c->batch_serial, l, c->need_prev[l], depth, in_force, cut_want[l], cost_now, cost_new);
-      for (int b = 0; b < ORBX_FILL_BUCKETS; b++)
-        if (hist[b]) fprintf(stderr, " %d:%u", ORBX_FILL_BUCKET_ROWS * (b + 1), hist[b]);
-      fprintf(stderr, "\n");
-    }
-  }
-  if (!grow && !change && !cut_change) return false;
-  if (!grow && c->retiles >= 4 && c->need_window < 32) return false;  // (settle first)
-  for (int l = 0; l < nl; l++) c->tile_h_pref[l] = want[l], c->cut_pref[l] = cut_want[l];
-  c->retiles++;
-  if (c->split_trace) fprintf(stderr, "orbx split: batch %lld re-tile %d\n", c->batch_serial, c->retiles);
-  return true;
 }
 
 // the launches of the whole path for n frames already on the device, into result block B (the plan, the current
@@ -758,7 +569,7 @@ int enqueue_batch(orbx_ctx* c, Block& B, const uint8_t* d_frames, int n, int row
   //   4. FAST on the remaining tile rows (their tiles exit the same way).
   // What a skipped strip leaves in the pool (rows of an earlier batch) is never read.  Results are
   // identical either way (tests/test_gpu_parity.py, tests/test_batch64_parity.py).
-  const bool two_pass = fused && !small && fast_early_on(c) && top_rows_wanted(c) && rest.count > 0 &&
+  const bool two_pass = fused && !small && fast_early_on(c) && top_rows_wanted(c->adapt, top_rows_env()) && rest.count > 0 &&
                         c->bm_fast.nbands > top_rows_env();
   // tile-row statistics of the FAST early exit: zeroed up front so that the events around the FAST stage bracket
   // the kernel alone -- except in the top-rows-first pipeline, whose first pyramid pass clears them itself: a
@@ -805,10 +616,7 @@ int enqueue_batch(orbx_ctx* c, Block& B, const uint8_t* d_frames, int n, int row
   HIPCHK(c, mark(4, false));  // (compaction, Harris and selection are one kernel: its time is the "select" slot)
   HIPCHK(c, mark(5, false));
   const OutLayout& o = B.layout;
-  // ORBX_SELECT_SPREAD=0/1 forces the fused / the three-kernel selection (A/B timing); frames whose candidates do not
-  // fit the fused kernel's LDS take the three kernels whatever it says (orbx_launch_level_select_auto)
-  static const int spread = env_int("ORBX_SELECT_SPREAD", -1);
-  HIPCHK(c, orbx_launch_level_select_auto(s, P, n, c->p.select_mode, spread, L.d_mask, final_pyr(c), c->d_gauss,
+  HIPCHK(c, orbx_launch_level_select_auto(s, P, n, c->p.select_mode, select_spread_env(), L.d_mask, final_pyr(c), c->d_gauss,
                                           c->p.harris_window, c->p.harris_k, L.d_lcand, L.d_lcount, L.d_lresp,
                                           L.d_cand, L.d_resp, L.d_cand_count, two_pass ? c->d_feedback + 2 : nullptr));
   HIPCHK(c, mark(6, false));
@@ -846,22 +654,22 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
   // set_plan waits for both lanes before it changes them.)
   // adaptive first pass (adapt_tile_rows): what was learned belongs to one frame size; new tile-row heights make
   // set_plan below rebuild the tables (it waits for the batches in flight; this batch then runs unpipelined)
-  if (w != c->learn_w || h != c->learn_h) {
-    c->learn_w = w;
-    c->learn_h = h;
-    for (int l = 0; l < ORBX_MAX_LEVELS; l++) c->need_cur[l] = c->need_prev[l] = 0, c->tile_h_pref[l] = c->cut_pref[l] = 0;
-    std::memset(c->fill_cur, 0, sizeof(c->fill_cur));
-    std::memset(c->fill_prev, 0, sizeof(c->fill_prev));
-    std::memset(c->fill_last, 0, sizeof(c->fill_last));
-    for (int i = 2; i < ORBX_FEEDBACK_WORDS; i++) c->h_feedback[i] = 0;
-    c->need_batches = 0;
-    c->need_window = 2;
-    c->retiles = 0;
+  // (h_feedback is never NULL in a context that orbx_create has returned: no guard here or at the verdict below)
+  OrbxAdapt& a = c->adapt;
+  if (w != a.learn_w || h != a.learn_h) {
+    new_frame_size(a, w, h, const_cast<uint32_t*>(c->h_feedback));
   } else if (w == c->plan_w && h == c->plan_h) {
     bool any_pref = false;
-    for (int l = 0; l < ORBX_MAX_LEVELS; l++) any_pref |= c->tile_h_pref[l] != 0 || c->cut_pref[l] != 0 || c->cut_force[l] != 0;
+    for (int l = 0; l < ORBX_MAX_LEVELS; l++) any_pref |= a.tile_h_pref[l] != 0 || a.cut_pref[l] != 0 || a.cut_force[l] != 0;
+    // ONE snapshot of the pinned feedback words per batch, without waiting: whatever has arrived (orbx_adapt.h; the
+    // words of the plan's levels, which lie in front: the cache lines the device has just written are the cost)
+    const bool apply = tile_prefs_apply(c);
+    const int used = ORBX_FEEDBACK_HIST + c->plan.nlevels * ORBX_FILL_BUCKETS;
+    uint32_t words[ORBX_FEEDBACK_WORDS];
+    for (int i = 0; apply && i < used; i++) words[i] = c->h_feedback[i];
     // (a switch that takes the top-rows-first pipeline away, or brings it back, since the tables were built)
-    if (adapt_tile_rows(c) || (any_pref && tile_prefs_apply(c) != c->prefs_applied)) c->plan_w = 0;
+    if (adapt_tile_rows(a, adapt_geom(c), words, apply, c->batch_serial, adapt_trace(c)) || (any_pref && apply != a.prefs_applied))
+      c->plan_w = 0;
   }
   const bool lanes = may_pipeline && c->pipelined && s == c->stream && w == c->plan_w && h == c->plan_h;
   c->lane = lanes ? c->next_lane : 0;
@@ -876,7 +684,7 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
   }
   int st = set_plan(c, w, h);
   if (st != ORBX_OK) return st;
-  top_rows_update(c);
+  top_rows_update(a, *reinterpret_cast<const volatile uint64_t*>(c->h_feedback));
   // this batch writes the other result block; if that block is still the source of an
   // asynchronous D2H copy (orbx_batch_prefetch two batches ago), the kernels wait for the copy
   const int blk = (c->blk + 1) % orbx_ctx::kBlocks;
@@ -894,10 +702,9 @@ int run_batch(orbx_ctx* c, const uint8_t* d_frames, int n, int w, int h, int row
   // result block sections are laid out for (n, pool slot capacity)
   B.cap = slots_per_frame(c->plan);
   B.layout = OutLayout(n, B.cap);
-  static const int use_graph = env_int("ORBX_GRAPH", 1);
   const int tm = c->timing;
-  if (use_graph && tm == 0) {
-    const OrbxGraphKey key{d_frames, frame_stride, n, w, h, row_stride, (fast_early_on(c) ? 1 : 0) | (fused_pyrblur(c) ? 2 : 0) | (top_rows_wanted(c) ? 4 : 0) | (lanes ? 8 : 0) | (c->lane << 4) | (c->host_results ? 64 : 0),
+  if (graph_env() && tm == 0) {
+    const OrbxGraphKey key{d_frames, frame_stride, n, w, h, row_stride, (fast_early_on(c) ? 1 : 0) | (fused_pyrblur(c) ? 2 : 0) | (top_rows_wanted(a, top_rows_env()) ? 4 : 0) | (lanes ? 8 : 0) | (c->lane << 4) | (c->host_results ? 64 : 0),
                            c->plan_serial, blk};
     int gi = -1;
     for (int i = 0; i < orbx_ctx::kGraphs; i++)
@@ -1100,7 +907,7 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
 
   c->fast_impl = fast_impl_env();
   c->blur_impl = blur_impl_env();
-  first_split_env(c);
+  first_split_fields(c->adapt, getenv("ORBX_TOP_ROWS"));
   st = build_plan(c->p, p->max_width, p->max_height, &c->plan_max, &why, c->fast_impl);
   if (st != ORBX_OK) {
     delete c;
@@ -1329,9 +1136,9 @@ int orbx_set_fused_pyramid_blur(orbx_ctx* c, int enable) {
 int orbx_set_top_rows_first(orbx_ctx* c, int mode) {
   DeviceGuard _dg(c);
   if (!c || mode < 0 || mode > 2) return ORBX_ERR_INVALID_ARG;
-  c->top_mode = mode;
-  c->top_on = true;
-  c->top_single_batches = 0;
+  c->adapt.top_mode = mode;
+  c->adapt.top_on = true;
+  c->adapt.top_single_batches = 0;
   return ORBX_OK;
 }
 
@@ -1377,7 +1184,7 @@ int orbx_pyramid_pixel_counts(orbx_ctx* c, long long* produced, long long* total
         if (b == 0) surv0 = surv;
       }
       // (an early band, rows [early, first), is produced unless tile row 0 alone holds the cap)
-      const int early = c->early_rows[l] > 0 && c->early_rows[l] < first ? c->early_rows[l] : first;
+      const int early_l = c->adapt.early_rows[l], early = early_l > 0 && early_l < first ? early_l : first;
       const int band = surv0 >= L.cap ? 0 : first - early;
       done += (long long)L.w * (first < L.h && surv >= L.cap ? early + band : L.h);
     }

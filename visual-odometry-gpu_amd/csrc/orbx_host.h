@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "orbx_adapt.h"
 #include "orbx_internal.h"
 #include "orbx_layout.h"
 
@@ -403,36 +404,12 @@ struct orbx_ctx {
   int blur_impl = 2;  // ORBX_BLUR_IMPL, read at creation (launch_blur_auto)
   int fast_impl = 4;  // 4: streaming kernel (orbx_fast4.hip, the default), 3: LDS tile kernel (orbx_fast.hip); ORBX_FAST_IMPL, read at creation
   int fuse = 1;  // pyramid + blur in one kernel when blur runs on every level (orbx_set_fused_pyramid_blur)
-  // Top-rows-first pipeline (enqueue_batch): 0 never, 1 whenever eligible, 2 adaptive -- the second pass
-  // counts the (frame, level)s it skipped / had to produce (d_feedback, running totals, written to the pinned
-  // h_feedback by the last kernel of every two-pass batch and read WITHOUT waiting at the start of later ones); while
-  // fewer than a quarter are skipped the batches run in one pass, and every 128th one probes again.
-  int top_mode = 2;
-  bool top_on = true;          // the adaptive verdict
-  int top_single_batches = 0;  // one-pass batches since the verdict turned negative
+  // the scheduler of the first pass (orbx_adapt.h): what it has learned and its switches, and the words the device
+  // reports into -- running totals and per-level fill rows (ORBX_FEEDBACK_WORDS, orbx_plan.h), written to the pinned
+  // h_feedback by the last kernel of every two-pass batch and read WITHOUT waiting at the start of later ones
+  OrbxAdapt adapt;
   uint32_t* d_feedback = nullptr;
   volatile uint32_t* h_feedback = nullptr;
-  uint32_t feedback_seen[2] = {0, 0};
-  // adaptive first pass (adapt_tile_rows): rows each level needed to fill its cap -- maximum of the current and of
-  // the previous observation window --, the tile-row heights chosen from them (0: the default), bookkeeping
-  uint32_t need_cur[ORBX_MAX_LEVELS] = {}, need_prev[ORBX_MAX_LEVELS] = {};
-  int tile_h_pref[ORBX_MAX_LEVELS] = {};
-  int need_batches = 0, need_window = 2, retiles = 0, learn_w = 0, learn_h = 0;
-  bool prefs_applied = false;  // the current tile tables were built with tile_h_pref
-  // unevenly cut first pass (adapt_tile_rows, orbx_plan.h: choose_first_cut): the frames of the current and of the
-  // previous observation window counted by the row their caps filled in, and the rows of tile row 0 chosen from them
-  // (0: equal halves).  Read when the context is created, from the fields behind ORBX_TOP_ROWS' number (orbx_api.cpp,
-  // first_split_env): equal halves only (A/B timing), the rows of tile row 0 forced per level (tests), a trace.
-  uint32_t fill_cur[ORBX_MAX_LEVELS][ORBX_FILL_BUCKETS] = {}, fill_prev[ORBX_MAX_LEVELS][ORBX_FILL_BUCKETS] = {};
-  int cut_pref[ORBX_MAX_LEVELS] = {}, cut_force[ORBX_MAX_LEVELS] = {};
-  bool first_split = true, split_trace = false;
-  // early band of the fused pyramid + blur kernel's second pass (orbx_plan.h: pyrblur_early_rows, early_band_pays):
-  // the histograms the last observation window ended with -- set_plan decides per level from them when it builds the
-  // tables, so only when adapt_tile_rows has them rebuilt --, and the row each level's first pass ends at in the
-  // current tables (the end of tile row 1 + ORBX_TOP_MARGIN where there is no band).  ORBX_TOP_ROWS=2:late: no bands.
-  uint32_t fill_last[ORBX_MAX_LEVELS][ORBX_FILL_BUCKETS] = {};
-  int early_rows[ORBX_MAX_LEVELS] = {};
-  bool early_band = true;
   // ring of event sets: one per timed batched call, so that several calls can be
   // in flight before their stage times are read (no host sync between steps)
   orbx_host::TimingSet evr[ORBX_EVENT_SETS];

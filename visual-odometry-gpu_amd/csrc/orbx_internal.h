@@ -16,12 +16,6 @@ __host__ __device__ inline int orbx_mask_x(const OrbxLevel& L, int xw, int b) {
 // FAST early-exit state per frame (u64 words): tile-row statistics [level][band], then one
 // "dead from band" word per level
 #define ORBX_FAST_STAT_WORDS (ORBX_MAX_LEVELS * ORBX_MAX_BANDS + ORBX_MAX_LEVELS)
-// feedback words of the top-rows-first pipeline (device, mirrored in pinned host memory by the batch's last kernel):
-// [0] levels skipped, [1] levels produced (running totals), [2 + l] rows level l needed to fill its cap (maximum
-// over the frames of the last batch; 0: not reported), [ORBX_FEEDBACK_HIST + l * ORBX_FILL_BUCKETS + b] frames of the
-// last batch whose level l filled its cap in a row of bucket b (orbx_plan.h, fill_bucket; the fused selection only)
-#define ORBX_FEEDBACK_HIST (2 + ORBX_MAX_LEVELS)
-#define ORBX_FEEDBACK_WORDS (ORBX_FEEDBACK_HIST + ORBX_MAX_LEVELS * ORBX_FILL_BUCKETS)
 // the levels whose lower rows the second pass of the top-rows-first pipeline may skip (orbx_api.cpp, enqueue_batch)
 struct OrbxTopLevels {
   int32_t n;

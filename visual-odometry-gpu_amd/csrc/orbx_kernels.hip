@@ -827,7 +827,7 @@ __global__ __launch_bounds__(LVL_THREADS) __attribute__((amdgpu_waves_per_eu(6, 
       sel_count[f * nl + l] = keep;
       // How many rows of the level did it take to fill the cap (all of them if it never filled)?  The maximum over
       // the batch's frames goes to the host, which sizes the first pass of the top-rows-first pipeline by it
-      // (orbx_api.cpp, adapt_tile_rows): a heuristic's input, results never depend on it.
+      // (orbx_adapt.h, adapt_tile_rows): a heuristic's input, results never depend on it.
       // ... and the frames counted by that row, in buckets (orbx_plan.h, fill_bucket of last_row + 1): where to cut
       // the first pass so that most frames' units of its second tile row exit
       if (need && cap > 0) {

@@ -60,7 +60,7 @@ struct OrbxTileMap {
 
 // band-major workgroup order of the FAST kernel (see decode_band)
 #define ORBX_MAX_BANDS 64
-// smallest FAST tile-row height the adaptive first pass may choose (orbx_api.cpp, adapt_tile_rows)
+// smallest FAST tile-row height the adaptive first pass may choose (orbx_adapt.h, adapt_tile_rows)
 #define ORBX_MIN_TILE_H 16
 // most rows a unit of the streaming FAST kernel may have: the tags of its score rows repeat after lcm(7 + 2 R, 16)
 // >= 144 rows (orbx_fast4.hip); a tile of the LDS tile kernel holds orbx_fast3_tile_h(R) rows
@@ -637,6 +637,12 @@ inline int table_capacity(const orbx_params& p, const OrbxPlan& M, int fast_impl
 #define ORBX_FILL_BUCKETS 32
 #define ORBX_FILL_BUCKET_ROWS 4
 inline int fill_bucket(int fill_row) { return std::min(std::max(fill_row - 1, 0) / ORBX_FILL_BUCKET_ROWS, ORBX_FILL_BUCKETS - 1); }
+// feedback words of the top-rows-first pipeline (device, mirrored in pinned host memory by the batch's last kernel):
+// [0] levels skipped, [1] levels produced (running totals), [2 + l] rows level l needed to fill its cap (maximum
+// over the frames of the last batch; 0: not reported), [ORBX_FEEDBACK_HIST + l * ORBX_FILL_BUCKETS + b] frames of the
+// last batch whose level l filled its cap in a row of bucket b (fill_bucket; the fused selection only)
+#define ORBX_FEEDBACK_HIST (2 + ORBX_MAX_LEVELS)
+#define ORBX_FEEDBACK_WORDS (ORBX_FEEDBACK_HIST + ORBX_MAX_LEVELS * ORBX_FILL_BUCKETS)
 // frames known to have filled within the first `cut` rows: whole buckets only, so never a frame too many
 inline uint32_t fill_exits(const uint32_t* hist, int cut) {
   uint32_t n = 0;
