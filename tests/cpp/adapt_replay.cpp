@@ -3,7 +3,8 @@
 // reset on a new frame size and the parser of ORBX_TOP_ROWS' fields.  Scripted streams assert the value every rule
 // gives; a seeded stream per geometry folds every step into a hash whose expected value was recorded from the code
 // as it stood BEFORE these rules moved into the header (inside orbx_api.cpp), so the move itself is pinned.  Calls the
-// code the library itself runs, and rebuilds the band map after a re-tile the way set_plan does.  Test
+// code the library itself runs, and rebuilds the tables after a re-tile with the builder set_plan calls
+// (csrc/orbx_tables.h: build_tile_tables), in pools sized by table_capacity for the stream's own frame size.  Test
 // infrastructure only; built with -fsanitize=address,undefined by tests/test_cpp_adapt.py.
 #include <cinttypes>
 #include <cstdio>
@@ -11,9 +12,9 @@
 #include <string>
 
 // ---- the scheduler under test -----------------------------------------------------------------------------------------
-#include "../../visual-odometry-gpu_amd/csrc/orbx_adapt.h"
+#include "../../visual-odometry-gpu_amd/csrc/orbx_tables.h"
 
-using namespace orbx_adapt;
+using namespace orbx_tables;
 
 namespace {
 
@@ -29,13 +30,15 @@ int g_fail = 0;
     }                                                     \
   } while (0)
 
-// a context as far as the scheduler sees it: the plan and band map of one frame size, the record, the feedback words
+// a context as far as the scheduler sees it: the plan and the tables of one frame size, the record, the feedback words
 struct Sched {
   orbx_params p{};
   int fast_impl = 4, top = 2;
   bool prefs_on = true;  // what tile_prefs_apply answers: adaptive mode, fused kernel, early exit on
   OrbxPlan plan{};
-  OrbxBandMap bm{};
+  OrbxTableCapacity cap{};
+  OrbxPlanTables tables;
+  OrbxBandMap& bm = tables.bm_fast;
   OrbxAdapt a{};
   uint32_t words[ORBX_FEEDBACK_WORDS] = {};
   long long serial = 0;
@@ -58,23 +61,16 @@ struct Sched {
     std::string why;
     const int st = build_plan(p, w, h, &plan, &why, fast_impl);
     CHECK(st == ORBX_OK, "build_plan: %s", why.c_str());
+    CHECK(table_capacity(p, plan, fast_impl, 2, &cap, &why) == ORBX_OK, "table_capacity: %s", why.c_str());
     new_frame_size(a, w, h, words);
     rebuild();
   }
   // what set_plan does with the record
   void rebuild() {
     std::string why;
-    a.prefs_applied = prefs_on;
-    int st = make_bandmap(plan, R(), &bm, &why, fast_impl == 4, a.prefs_applied ? a.tile_h_pref : nullptr);
-    if (a.prefs_applied && st != ORBX_OK) {
-      forget_tile_rows(a);
-      st = make_bandmap(plan, R(), &bm, &why, fast_impl == 4, nullptr);
-    }
-    CHECK(st == ORBX_OK, "make_bandmap: %s", why.c_str());
-    int first[ORBX_MAX_LEVELS][2] = {};
-    if (first_pass_heights(a, geom(), first))
-      (void)make_bandmap(plan, R(), &bm, &why, fast_impl == 4, a.prefs_applied ? a.tile_h_pref : nullptr, first);
-    choose_early_bands(a, geom(), trace);
+    const OrbxTableSwitches sw{fast_impl, 2, top, true, prefs_on};
+    const int st = build_tile_tables(plan, R(), sw, cap, a, trace, &tables, &why);
+    CHECK(st == ORBX_OK, "build_tile_tables: %s", why.c_str());
   }
   // one batch: the observation step on the words as they stand, and the tables rebuilt if it says so
   bool step() {

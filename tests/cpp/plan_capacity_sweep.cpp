@@ -1,7 +1,7 @@
 // plan_capacity_sweep.cpp -- host-only sweep over (maximum, frame, tile-row preference) triples: every table a
 // frame needs must fit the pool a context created for the maximum allocates, or the frame must be rejected for a
-// reason that has nothing to do with the maximum.  Calls the code the library itself runs (csrc/orbx_plan.h:
-// build_plan, make_bandmap, the table builders, table_capacity).  Test infrastructure only.
+// reason that has nothing to do with the maximum.  Calls the code the library itself runs (csrc/orbx_tables.h:
+// plan_with_taps; csrc/orbx_plan.h: make_bandmap, the table builders, table_capacity).  Test infrastructure only.
 //
 //   plan_capacity_sweep [--maxima N] [--threads T] [--parent-sizing]
 //
@@ -17,9 +17,9 @@
 #include <thread>
 #include <vector>
 
-#include "../../visual-odometry-gpu_amd/csrc/orbx_plan.h"
+#include "../../visual-odometry-gpu_amd/csrc/orbx_tables.h"
 
-using namespace orbx_geom;
+using namespace orbx_tables;
 
 namespace {
 
@@ -99,6 +99,7 @@ void sweep_one(const Config& cfg, int W, int H, const std::vector<std::pair<int,
     }
   };
   const int dflt = orbx_fast3_tile_h(r);
+  std::vector<OrbxResizeTap> taps;
   std::uniform_int_distribution<int> any_pref(0, dflt + 12);
   for (const auto& wh : frames) {
     const int w = wh.first, h = wh.second;
@@ -106,8 +107,9 @@ void sweep_one(const Config& cfg, int W, int H, const std::vector<std::pair<int,
     OrbxPlan P;
     OrbxBandMap bm0;
     // a frame the library refuses whatever the context's maximum is: a level below 8 x 8, a cap above
-    // ORBX_MAX_SELECT, more default tile rows than ORBX_MAX_BANDS (none of these looks at M)
-    if (build_plan(p, w, h, &P, &why, cfg.fast_impl) != ORBX_OK || make_bandmap(P, r, &bm0, &why, strips, nullptr) != ORBX_OK) {
+    // ORBX_MAX_SELECT, more default tile rows than ORBX_MAX_BANDS (none of these looks at M).  P is the plan the
+    // library runs, with the resize modes its taps give the levels (win8).
+    if (plan_with_taps(p, w, h, cfg.fast_impl, &P, &taps, &why) != ORBX_OK || make_bandmap(P, r, &bm0, &why, strips, nullptr) != ORBX_OK) {
       t->frames_rejected++;
       continue;
     }
@@ -119,16 +121,30 @@ void sweep_one(const Config& cfg, int W, int H, const std::vector<std::pair<int,
     // the tables that do not depend on the tile-row preferences
     size_t n;
     if ((n = taps_count(P)) > cap2.taps) fail(w, h, nullptr, "resize-tap table", n, cap2.taps);
+    if (taps.size() != n) fail(w, h, nullptr, "resize-tap table (built)", taps.size(), n);
     if ((n = blur_tiles_for_impl(2, P, nullptr)) > cap2.frame) fail(w, h, nullptr, "blur strip table (k_blur3)", n, cap2.frame);
     if ((n = blur_tiles_for_impl(3, P, nullptr)) > cap3.frame) fail(w, h, nullptr, "blur strip table (k_blur4)", n, cap3.frame);
-    // (the plan's win8 fields are zero here -- make_taps sets them --: 16-row pyramid tiles on every level above 0,
-    // which is the most tiles any win8 assignment gives)
+    // The tables that read win8, each under the plan the library runs and under the same plan with win8 zeroed, which
+    // is what table_capacity sees of the maximum: 16-row pyramid tiles on every level above 0, claimed to be the most
+    // tiles any win8 assignment gives -- so the real count must not exceed the zeroed one, for any table.
+    OrbxPlan Z = P;
+    for (int l = 0; l < Z.nlevels; l++) Z.L[l].win8 = 0;
+    size_t nz;
+    if ((nz = build_frame_tiles(Z, ORBX_PYR2_TW, ORBX_PYR2_TH, true, nullptr)) > std::min(cap2.frame, cap3.frame))
+      fail(w, h, nullptr, "pyramid tile table", nz, std::min(cap2.frame, cap3.frame));
     if ((n = build_frame_tiles(P, ORBX_PYR2_TW, ORBX_PYR2_TH, true, nullptr)) > std::min(cap2.frame, cap3.frame))
-      fail(w, h, nullptr, "pyramid tile table", n, std::min(cap2.frame, cap3.frame));
+      fail(w, h, nullptr, "pyramid tile table (real win8)", n, std::min(cap2.frame, cap3.frame));
+    if (n > nz) fail(w, h, nullptr, "pyramid tile table: real win8 against win8 zeroed", n, nz);
+    if ((nz = build_pyrblur_tiles(Z, ORBX_PYRBLUR_RH, nullptr)) > std::min(cap2.frame, cap3.frame))
+      fail(w, h, nullptr, "pyramid+blur strip table", nz, std::min(cap2.frame, cap3.frame));
     if ((n = build_pyrblur_tiles(P, ORBX_PYRBLUR_RH, nullptr)) > std::min(cap2.frame, cap3.frame))
-      fail(w, h, nullptr, "pyramid+blur strip table", n, std::min(cap2.frame, cap3.frame));
+      fail(w, h, nullptr, "pyramid+blur strip table (real win8)", n, std::min(cap2.frame, cap3.frame));
+    if (n > nz) fail(w, h, nullptr, "pyramid+blur strip table: real win8 against win8 zeroed", n, nz);
+    if ((nz = build_pyrblur_tiles(Z, ORBX_PYRBLUR_RH_SMALL, nullptr)) > cap2.small)
+      fail(w, h, nullptr, "pyramid+blur short-band table", nz, cap2.small);
     if ((n = build_pyrblur_tiles(P, ORBX_PYRBLUR_RH_SMALL, nullptr)) > cap2.small)
-      fail(w, h, nullptr, "pyramid+blur short-band table", n, cap2.small);
+      fail(w, h, nullptr, "pyramid+blur short-band table (real win8)", n, cap2.small);
+    if (n > nz) fail(w, h, nullptr, "pyramid+blur short-band table: real win8 against win8 zeroed", n, nz);
     // tile-row preferences: none, every uniform value, random per-level vectors
     int pref[ORBX_MAX_LEVELS];
     const int nuniform = dflt - ORBX_MIN_TILE_H + 1, nrandom = 6;

@@ -54,7 +54,7 @@ int reflect101(int p, int len) {
   return p >= len ? 2 * len - p - 2 : p;
 }
 
-// source row of level row dy (make_taps, orbx_api.cpp: OpenCV's row index before clipping)
+// source row of level row dy (make_taps, orbx_plan.h:OpenCV's row index before clipping)
 int ytap_ofs(int dy, int lh, int h0) {
   const double scale_y = 1. / ((double)lh / h0);
   const float fy = (float)((dy + 0.5) * scale_y - 0.5);

@@ -1,6 +1,6 @@
 """The scheduler of the first pass on the host (no GPU): tests/cpp/adapt_replay.cpp replays batches through the
-library's own steps (csrc/orbx_adapt.h) under AddressSanitizer and UBSan, rebuilding the band map after every re-tile
-the way set_plan does, on 1241 x 376 (both FAST layouts) and on 160 x 160, whose upper levels have one tile row --
+library's own steps (csrc/orbx_adapt.h) under AddressSanitizer and UBSan, rebuilding the tables after every re-tile
+with the builder set_plan calls (csrc/orbx_tables.h: build_tile_tables), on 1241 x 376 (both FAST layouts) and on 160 x 160, whose upper levels have one tile row --
 
 * scripted streams with the value every rule gives: observation windows of 2, 4, 8, 16, 32, 32 batches that an
   all-zero batch does not advance; grow at once, shrink only for three rows, settle after four re-tiles; whole groups

@@ -17,7 +17,7 @@
 #include "orbx_host.h"
 
 using namespace orbx_host;
-using namespace orbx_adapt;
+using namespace orbx_tables;  // (and through it orbx_adapt)
 
 namespace {
 thread_local std::string g_create_error;
@@ -272,78 +272,6 @@ const uint8_t* final_pyr(const orbx_ctx* c) { return blur_enabled(c) ? cur_lane(
 // slots per frame of a result block written under plan P (nfeatures too small for any quota: one empty slot)
 int slots_per_frame(const OrbxPlan& P) { return P.out_cap > 0 ? P.out_cap : 1; }
 
-// 8-bit bilinear coefficient tables: OpenCV 4.x generic 8UC1 INTER_LINEAR path
-// (imgproc/src/resize.cpp: scale = 1/((double)dst/src); fx = (float)((dx+0.5)*
-// scale-0.5); sx = floor(fx); clamp with fx=0; 11-bit coefficients by cvRound).
-// OpenCV is not part of this image: PARITY UNPINNED (DESIGN.md "Pyramid").
-void make_taps(OrbxPlan& plan, std::vector<OrbxResizeTap>* taps) {
-  taps->assign(taps_count(plan), OrbxResizeTap{0, 0, 0});
-  for (int l = 1; l < plan.nlevels; l++) {
-    const OrbxLevel& L = plan.L[l];
-    const double scale_x = 1. / ((double)L.w / plan.w0), scale_y = 1. / ((double)L.h / plan.h0);
-    for (int dx = 0; dx < L.w; dx++) {
-      float fx = (float)((dx + 0.5) * scale_x - 0.5);
-      int sx = (int)std::floor(fx);
-      fx -= (float)sx;
-      if (sx < 0) {
-        fx = 0;
-        sx = 0;
-      }
-      if (sx >= plan.w0 - 1) {
-        fx = 0;
-        sx = plan.w0 - 1;
-      }
-      OrbxResizeTap& t = (*taps)[L.xtab_off + dx];
-      t.ofs = sx;
-      t.c0 = (int16_t)std::lrintf((1.f - fx) * 2048.f);
-      t.c1 = (int16_t)std::lrintf(fx * 2048.f);
-      if (sx == plan.w0 - 1) {
-        // src[w0-1]*c0 (+ src[w0-1]*0) == src[w0-2]*0 + src[w0-1]*c0: same sum, but the
-        // kernel may now always fetch the pair (ofs, ofs+1) with one 16-bit load
-        t.ofs = plan.w0 - 2;
-        t.c1 = t.c0;
-        t.c0 = 0;
-      }
-    }
-    // can k_pyramid2 fetch the pairs of outputs 4g..4g+3 with one 8-byte window?
-    {
-      bool ok = plan.w0 >= 8;
-      for (int dx = 0; dx + 3 < L.w && ok; dx += 4)
-        ok = (*taps)[L.xtab_off + dx + 3].ofs + 1 - (*taps)[L.xtab_off + dx].ofs <= 7;
-      // (a trailing partial group only adds padding taps with ofs 0, which the kernel never uses)
-      for (int dx = L.w & ~3; dx < L.w && ok; dx++)
-        ok = (*taps)[L.xtab_off + dx].ofs + 1 - (*taps)[L.xtab_off + (L.w & ~3)].ofs <= 7;
-      plan.L[l].win8 = ok ? 1 : 0;
-      if (!ok && plan.w0 >= 8) {
-        // ... or stage the source rows of a strip through LDS (k_pyrblur): every 256-pixel strip of the level must
-        // read its pairs from at most ORBX_PYR_STAGE_BYTES of a source row (scales up to ~3.2; orbx_internal.h).  The span starts at
-        // the first pair, moved down so that its dwords END with the source row -- the buffer descriptor of the
-        // frame returns zero for a dword that straddles the frame's last byte, which the dword holding the last
-        // bytes of the last source row would do at any other alignment; where that is impossible (first strip: the
-        // span cannot start before the row) the strip must not reach that dword.
-        bool ok3 = true;
-        for (int x0 = 0; x0 < L.w && ok3; x0 += ORBX_PYRBLUR_TW) {
-          const int ofs_first = (*taps)[L.xtab_off + x0].ofs, ofs_last = (*taps)[L.xtab_off + std::min(x0 + 255, L.w - 1)].ofs;
-          const int want = ofs_first - ((ofs_first - plan.w0) & 3), span0 = std::max(want, 0);
-          ok3 = ofs_last + 2 - span0 <= ORBX_PYR_STAGE_BYTES;
-          if (want < 0 && (plan.w0 & 3) && ofs_last + 2 > (plan.w0 & ~3)) ok3 = false;
-        }
-        if (ok3) plan.L[l].win8 = 3;
-      }
-    }
-    for (int dy = 0; dy < L.h; dy++) {
-      float fy = (float)((dy + 0.5) * scale_y - 0.5);
-      int sy = (int)std::floor(fy);
-      fy -= (float)sy;
-      OrbxResizeTap& t = (*taps)[L.ytab_off + dy];
-      t.ofs = sy;  // rows are clamped in the kernel, weights kept (OpenCV clips the row index only)
-      t.c0 = (int16_t)std::lrintf((1.f - fy) * 2048.f);
-      t.c1 = (int16_t)std::lrintf(fy * 2048.f);
-    }
-  }
-}
-
-
 int validate_params(const orbx_params& p, std::string* why) {
   auto bad = [&](const char* m) {
     *why = m;
@@ -425,35 +353,29 @@ OrbxAdaptGeom adapt_geom(const orbx_ctx* c) {
 }
 FILE* adapt_trace(const orbx_ctx* c) { return c->adapt.split_trace ? stderr : nullptr; }
 
-// a table of the new plan goes to its pool
-int upload_tiles(orbx_ctx* c, int table, const std::vector<OrbxTileDesc>& t, const char* too_large) {
-  TileTable& T = c->tiles[table];
-  if (t.size() > T.capacity) return fail(c, ORBX_ERR_UNSUPPORTED, too_large);
-  if (!t.empty())  // (no second pass / no FAST tile at all: nothing to copy)
-    HIPCHK(c, hipMemcpy(T.d, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
-  T.count = (int)t.size();
-  return ORBX_OK;
-}
-
+// The tables of a frame size: built on the host (orbx_tables.h: the plan with its taps, then every table, each
+// checked against its pool), then copied to the pools and committed.
 int set_plan(orbx_ctx* c, int w, int h) {
   if (w == c->plan_w && h == c->plan_h) return ORBX_OK;
   if (w < 8 || h < 8 || w > c->p.max_width || h > c->p.max_height)
     return fail(c, ORBX_ERR_INVALID_ARG, "frame size outside [8, max_width] x [8, max_height]");
   OrbxPlan plan;
   std::string why;
-  int st = build_plan(c->p, w, h, &plan, &why, c->fast_impl);
+  int st = plan_with_taps(c->p, w, h, c->fast_impl, &plan, &c->h_taps, &why);
   if (st != ORBX_OK) return fail(c, st, why);
-  make_taps(plan, &c->h_taps);
-  if (c->h_taps.size() > c->taps_capacity) return fail(c, ORBX_ERR_UNSUPPORTED, "resize table exceeds pool");
-  // the table may still be in use by an in-flight batch of the previous size
+  if (c->h_taps.size() > c->table_cap.taps) return fail(c, ORBX_ERR_UNSUPPORTED, "resize table exceeds pool");
+  // no plan is set until every table below is in place: a call that fails on the way must not leave the previous
+  // size's (plan_w, plan_h) standing for tables that are half replaced
+  c->plan_w = c->plan_h = 0;
+  OrbxPlanTables& T = c->scratch;
+  const OrbxTableSwitches sw{c->fast_impl, c->blur_impl, top_rows_env(), pyr_group_env() > 0, tile_prefs_apply(c)};
+  st = build_tile_tables(plan, c->p.nms_window / 2, sw, c->table_cap, c->adapt, adapt_trace(c), &T, &why);
+  if (st != ORBX_OK) return fail(c, st, why);
+  // the tables may still be in use by an in-flight batch of the previous size
   HIPCHK(c, hipStreamSynchronize(batch_stream(c)));
   HIPCHK(c, lanes_sync(c));
   HIPCHK(c, hipMemcpy(c->d_taps, c->h_taps.data(), c->h_taps.size() * sizeof(OrbxResizeTap),
                       hipMemcpyHostToDevice));
-  // no plan is set until every table below is in place: a call that fails on the way must not leave the previous
-  // size's (plan_w, plan_h) standing for tables that are half replaced
-  c->plan_w = c->plan_h = 0;
-  c->plan = plan;
   // the fused pyramid + blur kernel writes only the dwords that hold image pixels; consumers rely on the
   // padding bytes of a level being zero (BRIEF's zero-extension), and another frame size re-uses the pool
   // (both lanes' pools; on the context's stream, and waited for: batches may run on a caller's stream)
@@ -461,53 +383,16 @@ int set_plan(orbx_ctx* c, int w, int h) {
     if (L.d_pyr_blur)
       HIPCHK(c, hipMemsetAsync(L.d_pyr_blur, 0, (size_t)c->p.max_batch * (size_t)c->plan_max.frame_bytes, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  make_tilemap(plan, ORBX_BLUR_TW, ORBX_BLUR_TH, true, &c->tm_blur);
-  // (the adaptive first pass's shorter tile rows only where the top-rows-first pipeline can run at all: with the
-  // early exit or the fused kernel switched off every tile works, and the default rows have the smaller halo share)
-  OrbxAdapt& a = c->adapt;
-  a.prefs_applied = tile_prefs_apply(c);
-  st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4,
-                    a.prefs_applied ? a.tile_h_pref : nullptr);
-  if (a.prefs_applied && (st != ORBX_OK || (size_t)c->bm_fast.band_begin[c->bm_fast.nbands] > c->tiles[T_FAST].capacity)) {
-    // The learned tile rows give a table the pool cannot hold (the FAST table's capacity is an upper bound over every
-    // preference, orbx_plan.h: this is a second line of defence).  What was learned is only a partition of the work:
-    // forget it, take the default rows and run the batch -- a failure here would repeat with every batch of this size.
-    forget_tile_rows(a);
-    st = make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4, nullptr);
+  for (int i = 0; i < kTileTables; i++) {
+    const std::vector<OrbxTileDesc>& t = T.tiles[i];
+    if (!t.empty())  // (no second pass / no FAST tile at all: nothing to copy)
+      HIPCHK(c, hipMemcpy(c->tiles[i].d, t.data(), t.size() * sizeof(OrbxTileDesc), hipMemcpyHostToDevice));
+    c->tiles[i].count = (int)t.size();
   }
-  if (st != ORBX_OK) return fail(c, st, why);
-  // the first pass cut unevenly (same number of tile rows, same pool): where the chooser or a forced cut says so
-  // (the first call above accepted these tile rows: this one cannot fail, and an illegal pair is ignored)
-  int first[ORBX_MAX_LEVELS][2] = {};
-  if (first_pass_heights(a, adapt_geom(c), first))
-    (void)make_bandmap(plan, c->p.nms_window / 2, &c->bm_fast, &why, c->fast_impl == 4,
-                       a.prefs_applied ? a.tile_h_pref : nullptr, first);
-  const bool grouped = pyr_group_env() > 0;
-  const int top = top_rows_env();
-  std::vector<OrbxTileDesc> t;
-  blur_tiles_for_impl(c->blur_impl, plan, &t);
-  if ((st = upload_tiles(c, T_BLUR, t, "blur tile table exceeds pool")) != ORBX_OK) return st;
-  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped);
-  if ((st = upload_tiles(c, T_PYRBLUR, t, "strip table exceeds pool")) != ORBX_OK) return st;
-  choose_early_bands(a, adapt_geom(c), adapt_trace(c));
-  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 1, &c->bm_fast, top, a.early_rows);
-  if ((st = upload_tiles(c, T_PYRBLUR_TOP, t, "strip table exceeds pool")) != ORBX_OK) return st;
-  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH, &t, grouped, 2, &c->bm_fast, top, a.early_rows);
-  if ((st = upload_tiles(c, T_PYRBLUR_REST, t, "strip table exceeds pool")) != ORBX_OK) return st;
-  c->top_levels = OrbxTopLevels{};
-  for (int l = 0; l < plan.nlevels; l++)
-    if (pyrblur_first_pass_rows(plan, c->bm_fast, l, top) < plan.L[l].h) {
-      const int i = c->top_levels.n++;
-      c->top_levels.stat_index[i] = l * ORBX_MAX_BANDS;
-      c->top_levels.rows[i] = std::min(top, c->bm_fast.tiles_y[l]);
-      c->top_levels.cap[i] = plan.L[l].cap;
-    }
-  build_pyrblur_tiles(plan, ORBX_PYRBLUR_RH_SMALL, &t);
-  if ((st = upload_tiles(c, T_PYRBLUR_SMALL, t, "strip table exceeds pool")) != ORBX_OK) return st;
-  build_frame_tiles(plan, ORBX_PYR2_TW, ORBX_PYR2_TH, true, &t);
-  if ((st = upload_tiles(c, T_PYR2, t, "pyramid tile table exceeds pool")) != ORBX_OK) return st;
-  build_fast_tiles(plan, c->bm_fast, 0, 1, &t);
-  if ((st = upload_tiles(c, T_FAST, t, "FAST tile table exceeds pool")) != ORBX_OK) return st;
+  c->plan = plan;
+  c->tm_blur = T.tm_blur;
+  c->bm_fast = T.bm_fast;
+  c->top_levels = T.top_levels;
   c->plan_serial++;
   c->plan_w = w;
   c->plan_h = h;
@@ -942,16 +827,11 @@ int orbx_create(const orbx_params* p, orbx_ctx** out) {
     orbx_destroy(c);
     return fail(nullptr, st, why);
   }
-  for (TileTable& T : c->tiles) T.capacity = tcap.frame;
-  c->tiles[T_FAST].capacity = tcap.fast;
-  c->tiles[T_PYRBLUR_SMALL].capacity = tcap.small;
-  for (TileTable& T : c->tiles)
-    CREATE_CHK(hipMalloc((void**)&T.d, std::max<size_t>(T.capacity, 1) * sizeof(OrbxTileDesc)));
-  {
-    // level sizes of smaller frames never exceed those of the largest frame
-    c->taps_capacity = tcap.taps;
-    CREATE_CHK(hipMalloc((void**)&c->d_taps, c->taps_capacity * sizeof(OrbxResizeTap)));
-  }
+  c->table_cap = tcap;
+  for (int i = 0; i < kTileTables; i++)
+    CREATE_CHK(hipMalloc((void**)&c->tiles[i].d, std::max<size_t>(tile_table_capacity(tcap, i), 1) * sizeof(OrbxTileDesc)));
+  // (level sizes of smaller frames never exceed those of the largest frame)
+  CREATE_CHK(hipMalloc((void**)&c->d_taps, tcap.taps * sizeof(OrbxResizeTap)));
   {
     const int K = p->harris_window;
     std::vector<float> g((size_t)K * K);

@@ -13,9 +13,9 @@
 #include <string>
 #include <vector>
 
-#include "orbx_adapt.h"
 #include "orbx_internal.h"
 #include "orbx_layout.h"
+#include "orbx_tables.h"
 
 namespace orbx_host {
 
@@ -69,24 +69,11 @@ struct Lane {
   hipStream_t pool_stream = nullptr;
 };
 
-// a per-workgroup tile descriptor table (see OrbxTileDesc) of the current plan, in a pool sized for the largest frame
+// a per-workgroup tile descriptor table (see OrbxTileDesc; T_* of orbx_tables.h) of the current plan, in a pool sized
+// for the largest frame (orbx_ctx::table_cap)
 struct TileTable {
   OrbxTileDesc* d = nullptr;
   int count = 0;
-  size_t capacity = 0;
-};
-enum {
-  T_FAST,  // one frame, band-major
-  T_BLUR,
-  T_PYR2,
-  T_PYRBLUR,  // fused pyramid + blur strips
-  // the same strips cut into short row bands: few frames per call (the reference's one-frame call shape)
-  // fill the chip only with many short waves, where a large batch wants few tall ones
-  T_PYRBLUR_SMALL,
-  // top-rows-first pipeline: the strips of the first pass and of the second one
-  T_PYRBLUR_TOP,
-  T_PYRBLUR_REST,
-  kTileTables
 };
 
 // the events of one timed batched call
@@ -341,9 +328,11 @@ struct orbx_ctx {
   OrbxPlan plan_max{};
   OrbxTileMap tm_blur{};  // 5x5 /273 variant (LDS tile kernel)
   OrbxBandMap bm_fast{};
-  orbx_host::TileTable tiles[orbx_host::kTileTables];
+  orbx_host::TileTable tiles[kTileTables];
   OrbxTopLevels top_levels{};  // the levels the second pass may skip
   std::vector<OrbxResizeTap> h_taps;
+  OrbxPlanTables scratch;        // set_plan builds the next size's tables here (a re-tile reuses the vectors)
+  orbx_geom::OrbxTableCapacity table_cap{};  // entries of the table pools and of d_taps (orbx_plan.h: table_capacity)
   int plan_w = 0, plan_h = 0;
 
   uint8_t* d_in = nullptr;  // staged host frames, tight pitch (max_batch frames of max_width x max_height)
@@ -354,7 +343,6 @@ struct orbx_ctx {
   int g_next = 0;
   int plan_serial = 0;  // bumped whenever set_plan rebuilds the plan / tables
   OrbxResizeTap* d_taps = nullptr;
-  size_t taps_capacity = 0;
   float* d_gauss = nullptr;
   // Result blocks.  A ring of kBlocks, used in turn by consecutive batches, each with a pinned host
   // mirror: the D2H copy of batch i (orbx_batch_prefetch, on its own copy stream) overlaps the

@@ -16,14 +16,6 @@ __host__ __device__ inline int orbx_mask_x(const OrbxLevel& L, int xw, int b) {
 // FAST early-exit state per frame (u64 words): tile-row statistics [level][band], then one
 // "dead from band" word per level
 #define ORBX_FAST_STAT_WORDS (ORBX_MAX_LEVELS * ORBX_MAX_BANDS + ORBX_MAX_LEVELS)
-// the levels whose lower rows the second pass of the top-rows-first pipeline may skip (orbx_api.cpp, enqueue_batch)
-struct OrbxTopLevels {
-  int32_t n;
-  int32_t stat_index[ORBX_MAX_LEVELS];  // first tile-row statistic of the level
-  int32_t rows[ORBX_MAX_LEVELS];        // FAST tile rows of the first pass
-  int32_t cap[ORBX_MAX_LEVELS];
-};
-
 struct OrbxFastParams {
   int32_t threshold, n, nms_radius;
 };

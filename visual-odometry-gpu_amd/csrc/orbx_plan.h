@@ -112,6 +112,14 @@ struct OrbxResizeTap {
   int16_t c0, c1;  // weights of src[ofs], src[ofs+1]; c0+c1 ~ 2048
 };
 
+// the levels whose lower rows the second pass of the top-rows-first pipeline may skip (orbx_api.cpp, enqueue_batch)
+struct OrbxTopLevels {
+  int32_t n;
+  int32_t stat_index[ORBX_MAX_LEVELS];  // first tile-row statistic of the level
+  int32_t rows[ORBX_MAX_LEVELS];        // FAST tile rows of the first pass
+  int32_t cap[ORBX_MAX_LEVELS];
+};
+
 // tile geometry of the FAST/NMS kernel (orbx_fast.hip): 128 output pixels wide (two mask words per
 // row); 34 dword columns x 7 row segments of walking threads, 7 rows per walk (at most 8: a flag byte per
 // pixel column), so the score region of a tile has 49 rows and a tile 49 - 2 * nms_radius output rows
@@ -569,11 +577,82 @@ inline int build_plan(const orbx_params& p, int w0, int h0, OrbxPlan* plan, std:
   return ORBX_OK;
 }
 
-// entries of the resize-tap table of a plan (make_taps in orbx_api.cpp fills them; at least one)
+// entries of the resize-tap table of a plan (make_taps below fills them; at least one)
 inline size_t taps_count(const OrbxPlan& plan) {
   size_t total = 0;
   for (int l = 1; l < plan.nlevels; l++) total += (size_t)align_up(plan.L[l].w, 4) + align_up(plan.L[l].h, 4);
   return total ? total : 1;
+}
+
+// 8-bit bilinear coefficient tables: OpenCV 4.x generic 8UC1 INTER_LINEAR path
+// (imgproc/src/resize.cpp: scale = 1/((double)dst/src); fx = (float)((dx+0.5)*
+// scale-0.5); sx = floor(fx); clamp with fx=0; 11-bit coefficients by cvRound).
+// OpenCV is not part of this image: PARITY UNPINNED (DESIGN.md "Pyramid").
+inline void make_taps(OrbxPlan& plan, std::vector<OrbxResizeTap>* taps) {
+  taps->assign(taps_count(plan), OrbxResizeTap{0, 0, 0});
+  for (int l = 1; l < plan.nlevels; l++) {
+    const OrbxLevel& L = plan.L[l];
+    const double scale_x = 1. / ((double)L.w / plan.w0), scale_y = 1. / ((double)L.h / plan.h0);
+    for (int dx = 0; dx < L.w; dx++) {
+      float fx = (float)((dx + 0.5) * scale_x - 0.5);
+      int sx = (int)std::floor(fx);
+      fx -= (float)sx;
+      if (sx < 0) {
+        fx = 0;
+        sx = 0;
+      }
+      if (sx >= plan.w0 - 1) {
+        fx = 0;
+        sx = plan.w0 - 1;
+      }
+      OrbxResizeTap& t = (*taps)[L.xtab_off + dx];
+      t.ofs = sx;
+      t.c0 = (int16_t)std::lrintf((1.f - fx) * 2048.f);
+      t.c1 = (int16_t)std::lrintf(fx * 2048.f);
+      if (sx == plan.w0 - 1) {
+        // src[w0-1]*c0 (+ src[w0-1]*0) == src[w0-2]*0 + src[w0-1]*c0: same sum, but the
+        // kernel may now always fetch the pair (ofs, ofs+1) with one 16-bit load
+        t.ofs = plan.w0 - 2;
+        t.c1 = t.c0;
+        t.c0 = 0;
+      }
+    }
+    // can k_pyramid2 fetch the pairs of outputs 4g..4g+3 with one 8-byte window?
+    {
+      bool ok = plan.w0 >= 8;
+      for (int dx = 0; dx + 3 < L.w && ok; dx += 4)
+        ok = (*taps)[L.xtab_off + dx + 3].ofs + 1 - (*taps)[L.xtab_off + dx].ofs <= 7;
+      // (a trailing partial group only adds padding taps with ofs 0, which the kernel never uses)
+      for (int dx = L.w & ~3; dx < L.w && ok; dx++)
+        ok = (*taps)[L.xtab_off + dx].ofs + 1 - (*taps)[L.xtab_off + (L.w & ~3)].ofs <= 7;
+      plan.L[l].win8 = ok ? 1 : 0;
+      if (!ok && plan.w0 >= 8) {
+        // ... or stage the source rows of a strip through LDS (k_pyrblur): every 256-pixel strip of the level must
+        // read its pairs from at most ORBX_PYR_STAGE_BYTES of a source row (scales up to ~3.2; orbx_internal.h).  The span starts at
+        // the first pair, moved down so that its dwords END with the source row -- the buffer descriptor of the
+        // frame returns zero for a dword that straddles the frame's last byte, which the dword holding the last
+        // bytes of the last source row would do at any other alignment; where that is impossible (first strip: the
+        // span cannot start before the row) the strip must not reach that dword.
+        bool ok3 = true;
+        for (int x0 = 0; x0 < L.w && ok3; x0 += ORBX_PYRBLUR_TW) {
+          const int ofs_first = (*taps)[L.xtab_off + x0].ofs, ofs_last = (*taps)[L.xtab_off + std::min(x0 + 255, L.w - 1)].ofs;
+          const int want = ofs_first - ((ofs_first - plan.w0) & 3), span0 = std::max(want, 0);
+          ok3 = ofs_last + 2 - span0 <= ORBX_PYR_STAGE_BYTES;
+          if (want < 0 && (plan.w0 & 3) && ofs_last + 2 > (plan.w0 & ~3)) ok3 = false;
+        }
+        if (ok3) plan.L[l].win8 = 3;
+      }
+    }
+    for (int dy = 0; dy < L.h; dy++) {
+      float fy = (float)((dy + 0.5) * scale_y - 0.5);
+      int sy = (int)std::floor(fy);
+      fy -= (float)sy;
+      OrbxResizeTap& t = (*taps)[L.ytab_off + dy];
+      t.ofs = sy;  // rows are clamped in the kernel, weights kept (OpenCV clips the row index only)
+      t.c0 = (int16_t)std::lrintf((1.f - fy) * 2048.f);
+      t.c1 = (int16_t)std::lrintf(fy * 2048.f);
+    }
+  }
 }
 
 // ---- what a context allocates for the tables of ANY frame it accepts ----------------------------------------------
@@ -612,7 +691,7 @@ inline size_t fast_tiles_upper_bound(const OrbxPlan& M, int nms_radius, bool str
   return cap;
 }
 // M: build_plan of the maximum (its win8 fields still zero: the pyramid tiles of the pool are then the short ones,
-// ORBX_PYR2_TH rows -- the most).  Fails where the maximum itself has no FAST table (make_bandmap's reasons).
+// ORBX_PYR2_TH rows -- the most: tests/cpp/plan_capacity_sweep.cpp compares with the real win8 of every frame).  Fails where the maximum itself has no FAST table (make_bandmap's reasons).
 inline int table_capacity(const orbx_params& p, const OrbxPlan& M, int fast_impl, int blur_impl, OrbxTableCapacity* cap,
                           std::string* why) {
   OrbxBandMap bm;
