@@ -67,7 +67,7 @@ def main():
         kw = dict(nfeatures=int(rng.choice([0, 1, 7, 100, 500, 2000])), nlevels=nl, scale_factor=sf,
                   threshold=int(rng.choice([0, 1, 5, 12, 20, 20, 35, 60, 120])), n=int(rng.choice([9, 9, 9, 12, 16, 5, 1])),
                   nms_window=int(rng.choice([0, 3, 3, 3, 5, 7])), patch_size=int(rng.choice([31, 31, 9, 15, 1, 41])),
-                  harris_window=int(rng.choice([7, 7, 5, 3])), harris_k=float(rng.choice([0.04, 0.06, 0.0])),
+                  harris_window=int(rng.choice([7, 7, 5, 3, 1, 9, 11, 13, 15])), harris_k=float(rng.choice([0.04, 0.06, 0.0])),
                   blur_levels=int(rng.integers(0, 3)), blur_kind=int(rng.integers(0, 2)))
         mode = int(rng.integers(0, 2))
         B = 40 if big else int(rng.choice([1, 2, 5, 9]))
