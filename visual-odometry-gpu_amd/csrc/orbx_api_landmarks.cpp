@@ -151,6 +151,7 @@ int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d
                                     (int32_t*)(scr + S.gate), lm_pointers(c, B), pose_status));
   std::memcpy(c->lm.K, K, sizeof c->lm.K);
   c->lm.has_views = views != nullptr;
+  c->lm.gen++;
   c->lm.n = n;
   c->lm.cap = cap;
   c->lm.len = len;
@@ -169,6 +170,39 @@ int lm_check_build(orbx_ctx* c, const double* K, const void* tracks, const void*
   if (!finite_all(K, 9)) return fail(c, ORBX_ERR_INVALID_ARG, "K is not finite");
   for (size_t i = 0; poses6 && i < 6 * (size_t)n * len; i++)
     if (!std::isfinite(poses6[i])) return fail(c, ORBX_ERR_INVALID_ARG, "a pose is not finite");
+  return ORBX_OK;
+}
+
+// the solve behind orbx_bundle_adjust_landmarks_device and orbx_bundle_adjust_landmarks_pnp_device
+int lm_solve(orbx_ctx* c, double huber_delta, int max_iters, hipStream_t s, const double* d_poses6,
+             const SideWork* producer) {
+  if (!ba_params_ok(huber_delta, max_iters)) return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
+  if (c->lm.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no landmarks block has been built");
+  int st = c->lm.side.enter(c, s);
+  if (st != ORBX_OK) return st;
+  const SideWork::Mark mark{c->lm.side, s};
+  if (producer && (st = c->lm.side.after(c, *producer, s)) != ORBX_OK) return st;
+  const int n = c->lm.n, cap = c->lm.cap, len = c->lm.len, ocap = cap * len;
+  const LmWork W(n, cap, len);
+  const LmSolve V(n, cap, len);
+  if ((st = c->lm.side.grow(c, c->lm.ws, W.bytes)) != ORBX_OK) return st;
+  if ((st = c->lm.side.grow(c, c->lm.sol, V.bytes)) != ORBX_OK) return st;
+  const OrbxLmBlock P = lm_pointers(c, LmBlock(n, cap, len));
+  const LmScratch S(n, cap, len);
+  uint8_t* sol = (uint8_t*)c->lm.sol.p;
+  uint8_t* ws = (uint8_t*)c->lm.ws.p;
+  c->lm.solved = false;
+  // the block stays as built: the solve reads and writes copies of its poses and points
+  const void* poses_from = d_poses6 ? (const void*)d_poses6 : (const void*)((const uint8_t*)c->lm.scr.p + S.poses);
+  HIPCHK(c, hipMemcpyAsync(sol + V.poses, poses_from, sizeof(double) * 6 * (size_t)n * len, hipMemcpyDeviceToDevice,
+                           s));
+  HIPCHK(c, hipMemcpyAsync(sol + V.points, P.points3, sizeof(double) * 3 * (size_t)n * cap, hipMemcpyDeviceToDevice, s));
+  const double K4[4] = {c->lm.K[0], c->lm.K[4], c->lm.K[2], c->lm.K[5]};
+  HIPCHK(c, orbx_launch_ba(s, n, W.groups, max_iters, K4, huber_delta, P.pose_off, P.pt_off, P.obs_off,
+                           (double*)(sol + V.poses), (double*)(sol + V.points), P.rows, P.opose, P.oxy, cap, ocap,
+                           (double*)(ws + W.wp), (double*)(ws + W.wo), (unsigned long long*)(ws + W.slot),
+                           sol + V.out));
+  c->lm.solved = true;
   return ORBX_OK;
 }
 
@@ -264,33 +298,7 @@ int orbx_landmarks_fetch(orbx_ctx* c, int first, int n, int32_t* status, int32_t
 int orbx_bundle_adjust_landmarks_device(orbx_ctx* c, double huber_delta, int max_iters, void* stream) {
   DeviceGuard _dg(c);
   if (!c) return ORBX_ERR_INVALID_ARG;
-  if (!ba_params_ok(huber_delta, max_iters)) return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
-  if (c->lm.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no landmarks block has been built");
-  hipStream_t s = stream_of(c, stream);
-  int st = c->lm.side.enter(c, s);
-  if (st != ORBX_OK) return st;
-  const SideWork::Mark mark{c->lm.side, s};
-  const int n = c->lm.n, cap = c->lm.cap, len = c->lm.len, ocap = cap * len;
-  const LmWork W(n, cap, len);
-  const LmSolve V(n, cap, len);
-  if ((st = c->lm.side.grow(c, c->lm.ws, W.bytes)) != ORBX_OK) return st;
-  if ((st = c->lm.side.grow(c, c->lm.sol, V.bytes)) != ORBX_OK) return st;
-  const OrbxLmBlock P = lm_pointers(c, LmBlock(n, cap, len));
-  const LmScratch S(n, cap, len);
-  uint8_t* sol = (uint8_t*)c->lm.sol.p;
-  uint8_t* ws = (uint8_t*)c->lm.ws.p;
-  c->lm.solved = false;
-  // the block stays as built: the solve reads and writes copies of its poses and points
-  HIPCHK(c, hipMemcpyAsync(sol + V.poses, (const uint8_t*)c->lm.scr.p + S.poses, sizeof(double) * 6 * (size_t)n * len,
-                           hipMemcpyDeviceToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(sol + V.points, P.points3, sizeof(double) * 3 * (size_t)n * cap, hipMemcpyDeviceToDevice, s));
-  const double K4[4] = {c->lm.K[0], c->lm.K[4], c->lm.K[2], c->lm.K[5]};
-  HIPCHK(c, orbx_launch_ba(s, n, W.groups, max_iters, K4, huber_delta, P.pose_off, P.pt_off, P.obs_off,
-                           (double*)(sol + V.poses), (double*)(sol + V.points), P.rows, P.opose, P.oxy, cap, ocap,
-                           (double*)(ws + W.wp), (double*)(ws + W.wo), (unsigned long long*)(ws + W.slot),
-                           sol + V.out));
-  c->lm.solved = true;
-  return ORBX_OK;
+  return lm_solve(c, huber_delta, max_iters, stream_of(c, stream), nullptr, nullptr);
 }
 
 int orbx_bundle_adjust_landmarks_fetch(orbx_ctx* c, int first, int n, double* poses6, orbx_ba_summary* summaries,

@@ -232,6 +232,7 @@ struct Landmarks {
   int n = 0, cap = 0, len = 0;  // windows, slots per window, poses per window of the last build (0: none)
   bool has_views = false;       // the last build was a views build: `views` belongs to it
   bool solved = false;          // the block has been solved since it was built
+  long long gen = 0;            // bumped by every build: what the PnP batch records (Pnp::lm_gen)
   SideWork side;                // the event is recorded behind every build and every solve
   PinnedUpload poses_up;        // the pose table's way up
   void release() {
@@ -284,6 +285,20 @@ struct StreamStitch {
     side.release();
     up.release();
     free_bufs({&in, &blk, &stage});
+  }
+};
+
+// perspective-n-point over the landmarks block (orbx_pnp.hip): the gathered correspondences (PnpScratch of
+// orbx_layout.h) and the entry's OWN result block (PnpBlock), and the same pair for the one problem of the host-array
+// entry.  The batch reads lm.blk and lm.scr; the seeded solve reads blk's poses.  Nothing is written elsewhere.
+struct Pnp {
+  DevBuf scr, blk, hscr, hblk;
+  int n = 0, cap = 0, len = 0;  // windows, slots per window, frames per window of the last batch (0: none)
+  long long lm_gen = -1;        // the Landmarks::gen of the block the last batch read
+  SideWork side;                // the event is recorded behind every call
+  void release() {
+    side.release();
+    free_bufs({&scr, &blk, &hscr, &hblk});
   }
 };
 
@@ -373,7 +388,8 @@ struct orbx_ctx {
   // calls are made: pose reads the matcher's table, scale checks pose.match_gen against m.gen, the windows
   // tracker waits for the good-features event, the landmarks build and the tracks pose wait for the windows
   // tracker's, the window poses wait for the tracks pose's, the chained landmarks build for the window poses', and
-  // the write-back gate for the solve's, and the stitch for the window poses' (chain and gate share one event).
+  // the write-back gate for the solve's, and the stitch for the window poses' (chain and gate share one event); the
+  // PnP batch waits for the landmarks' event (build and solve share one) and the seeded solve for the PnP batch's.
   orbx_host::StageScratch s;
   orbx_host::Matcher m;
   orbx_host::LkPair lk;
@@ -386,6 +402,7 @@ struct orbx_ctx {
   orbx_host::TracksPose tp;
   orbx_host::WindowPoses wp;
   orbx_host::StreamStitch st;
+  orbx_host::Pnp pnp;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -517,5 +534,10 @@ int wp_check(orbx_ctx* c, const double* T0, const double* scale0, const WpStream
 int wp_run(orbx_ctx* c, const double* T0, const double* scale0, hipStream_t s,
            const WpStreamOptions* stream_of_windows = nullptr);
 bool gate_params_ok(double max_rot, double max_trans);
+// the solve of the landmarks block on s behind orbx_bundle_adjust_landmarks_device and its PnP-seeded twin
+// (orbx_api_landmarks.cpp): d_poses6 is what the solve's poses copy is taken from -- NULL: the poses the block was
+// built from -- and `producer`, when not NULL, the work that wrote them, perhaps on another stream
+int lm_solve(orbx_ctx* c, double huber_delta, int max_iters, hipStream_t s, const double* d_poses6,
+             const SideWork* producer);
 
 }  // namespace orbx_host

@@ -250,6 +250,30 @@ hipError_t orbx_launch_ba_write_back(hipStream_t s, int n_windows, int window_le
                                      const double* d_built6, const void* d_summaries, double max_rot,
                                      double max_trans, double* d_poses4x4, uint8_t* d_updated);
 
+// ---- perspective-n-point with RANSAC (orbx_pnp.hip) -----------------------------------------
+// one correspondence of a problem: the world point and its pixel
+struct OrbxPnpCorr {
+  double X[3], x, y;
+};
+struct OrbxPnpRecord {  // = orbx_pnp_record
+  double pose6[6];
+  int32_t inliers, iters, n_corr, status;
+  double rms_px;
+};
+// what a batch reads: sections of the landmarks block and the poses it was built from.  status == NULL: ONE problem
+// whose n_pre correspondences are in d_corr already (the host-array entry), with `seed` as its own seed
+struct OrbxPnpIn {
+  const int32_t *status, *pt_off, *obs_off, *rows;
+  const double *points3, *oxy, *built6;
+};
+// One workgroup per problem (window w, frame k >= 2), problem w * (window_len - 2) + k - 2.  d_corr / d_cidx / d_mask:
+// one row of `cap` per problem; d_rec: one record per problem; d_seeded6: 6 doubles per (window, frame).  The seed of
+// problem (w, k) is pnp_problem_seed(seed, k).
+hipError_t orbx_launch_pnp(hipStream_t s, int n_windows, int window_len, int cap, const OrbxPnpIn& in, int n_pre,
+                           const double* K4, double prob, double threshold_px, int max_iters, uint64_t seed,
+                           int refine_iters, int min_inliers, OrbxPnpCorr* d_corr, int32_t* d_cidx,
+                           OrbxPnpRecord* d_rec, double* d_seeded6, uint8_t* d_mask);
+
 // ---- overlapping windows joined into one trajectory (orbx_stitch.hip) ------------------------
 // Window w of window_len frames starts at stream frame w * stride, 1 <= stride <= window_len - 1.
 // d_scale: the tracks-pose block's scale rows; d_scale0: one double per window (the chain's input section)

@@ -254,6 +254,23 @@ struct WbBlock : private Sections {
   WbBlock(size_t n, size_t len) : poses4x4(take(sizeof(double) * 16 * n * len)), updated(take(n * len)), bytes(off) {}
 };
 
+// ---- perspective-n-point over the landmarks block: n windows of len >= 3 frames of cap slots, one problem per
+// (window, frame >= 2) ----
+// the result block: records | seeded poses6 (n x len x 6) | mask (one row of cap bytes per problem)
+struct PnpBlock : private Sections {
+  size_t problems, records, poses6, mask, bytes;
+  PnpBlock(size_t n, size_t cap, size_t len)
+      : problems(n * (len - 2)), records(take(sizeof(OrbxPnpRecord) * problems)),
+        poses6(take(sizeof(double) * 6 * n * len)), mask(take(problems * cap)), bytes(off) {}
+};
+// the scratch: every problem's gathered correspondences | the point each came from
+struct PnpScratch : private Sections {
+  size_t corr, cidx, bytes;
+  PnpScratch(size_t n, size_t cap, size_t len)
+      : corr(take(sizeof(OrbxPnpCorr) * n * (len - 2) * cap)), cidx(take(sizeof(int32_t) * n * (len - 2) * cap)),
+        bytes(off) {}
+};
+
 // ---- n overlapping windows of len frames, window w starting at stream frame w * stride, joined into one trajectory ----
 // the frames of the stream
 inline size_t st_stream_frames(size_t n, size_t len, size_t stride) { return (n - 1) * stride + len; }

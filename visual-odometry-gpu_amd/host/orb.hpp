@@ -45,6 +45,7 @@
 
 #include "../../include/orbx.h"
 #include "../../include/orbx_lm.h"
+#include "../../include/orbx_pnp.h"
 #include "../../include/orbx_stream.h"
 #include "../../include/orbx_vo.h"
 
@@ -1368,6 +1369,48 @@ inline StreamOdometry run_stream_odometry_on_tracks(const Pose4x4& pose0, const 
                                             out.lm_status.data(), out.summaries.data()),
                 "orbx_stream_odometry_tracks");
   return out;
+}
+
+// ---- perspective-n-point with RANSAC ----------------------------------------------------
+// cv::solvePnPRansac(objectPoints, imagePoints, cameraMatrix, distCoeffs, rvec, tvec, useExtrinsicGuess,
+//                    iterationsCount, reprojectionError, confidence, inliers)
+// in the call shape OpenCV gives it; the reference calls none -- its window poses come from the chain of
+// src/with_bundle_adjustment.cpp:196-208 alone.  No distortion coefficients and no extrinsic guess.  K: row-major 3x3.
+// rvec (angle-axis) and tvec are world -> camera and are ASSIGNED only when a pose was found (the return value);
+// inliers receives the indices of the inliers as OpenCV's does.  P3P samples, at most refine_iters Levenberg-Marquardt
+// steps on the inliers of the best model; a model needs min_inliers inliers.  The samples depend on (seed, iteration).
+struct PnPInfo {
+  int32_t status = 0;  // an orbx_pnp_status
+  int32_t inliers = 0, iters = 0;
+  double rms_px = 0.0;
+};
+inline bool solvePnPRansac(const std::vector<Point3d>& objectPoints, const std::vector<Point2d>& imagePoints,
+                           const double K[9], double rvec[3], double tvec[3], int iterationsCount = 100,
+                           double reprojectionError = 8.0, double confidence = 0.99,
+                           std::vector<int>* inliers = nullptr, uint64_t seed = 0, int refine_iters = 10,
+                           int min_inliers = 4, PnPInfo* info = nullptr) {
+  static_assert(sizeof(Point3d) == 3 * sizeof(double) && sizeof(Point2d) == 2 * sizeof(double), "point layouts");
+  if (objectPoints.size() != imagePoints.size())
+    throw std::invalid_argument("solvePnPRansac: objectPoints and imagePoints differ in size");
+  const int n = (int)objectPoints.size();
+  std::vector<uint8_t> mask((size_t)n, 0);
+  double pose6[6];
+  PnPInfo r;
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_pnp_ransac(c, n > 0 ? &objectPoints[0].x : nullptr, n > 0 ? &imagePoints[0].x : nullptr, n, K,
+                                confidence, reprojectionError, iterationsCount, seed, refine_iters, min_inliers, pose6,
+                                n > 0 ? mask.data() : nullptr, &r.inliers, &r.iters, &r.rms_px, &r.status),
+                "orbx_pnp_ransac");
+  if (info) *info = r;
+  if (inliers) {
+    inliers->clear();
+    for (int i = 0; i < n; i++)
+      if (mask[(size_t)i]) inliers->push_back(i);
+  }
+  if (r.status != ORBX_PNP_OK) return false;
+  for (int i = 0; i < 3; i++) rvec[i] = pose6[i], tvec[i] = pose6[3 + i];
+  return true;
 }
 
 // ---- Shi-Tomasi corners (next row) ----------------------------------
