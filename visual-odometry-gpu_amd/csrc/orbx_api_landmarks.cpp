@@ -112,13 +112,13 @@ bool ba_params_ok(double huber_delta, int max_iters) {
 // enqueues the kernels of a build on s (views: those of rank 15, with its options); arguments are checked
 int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
            const double* poses6, const double* d_poses6, const int32_t* d_pose_status, hipStream_t s,
-           const LmViewsOptions* views) {
+           const LmViewsOptions* views, const SideWork* producer) {
   int st = c->lm.side.enter(c, s);
   if (st != ORBX_OK) return st;
   const SideWork::Mark mark{c->lm.side, s};
   // the tracks may be the windows tracker's block, written on another stream; so may the chained poses
   if ((st = c->lm.side.after(c, c->lkw.side, s)) != ORBX_OK) return st;
-  if (!poses6 && (st = c->lm.side.after(c, c->wp.side, s)) != ORBX_OK) return st;
+  if (!poses6 && (st = c->lm.side.after(c, producer ? *producer : c->wp.side, s)) != ORBX_OK) return st;
   const LmBlock B(n, cap, len);
   const LmScratch S(n, cap, len);
   if ((st = c->lm.side.grow(c, c->lm.scr, S.bytes)) != ORBX_OK) return st;

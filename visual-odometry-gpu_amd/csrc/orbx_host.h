@@ -302,6 +302,22 @@ struct Pnp {
   }
 };
 
+// landmarks carried into the next generation of windows and the PnP of every frame of those windows against them
+// (orbx_carry.hip, k_pnp_ransac; rank 18): the carry block (CarryBlock of orbx_layout.h), the carried PnP's scratch and
+// its OWN result block (CarryPnpScratch, CarryPnpBlock), and the staged arrays of the one-window host entry
+// (CarryStage).  The carry reads lm.blk or lm.sol and the caller's origin; the carried PnP reads blk and the caller's
+// tracks; the carried landmarks build reads pblk.  Nothing is written elsewhere.
+struct Carry {
+  DevBuf blk, pscr, pblk, stage;
+  int n = 0, cap = 0;              // windows and slots per window of the last carry (0: none)
+  int pn = 0, pcap = 0, plen = 0;  // windows, slots and frames per window of the last carried PnP (0: none)
+  SideWork side;                   // the event is recorded behind every carry and every carried PnP
+  void release() {
+    side.release();
+    free_bufs({&blk, &pscr, &pblk, &stage});
+  }
+};
+
 // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames, allocated on first use and bounded by
 // ws_limit; the staged host image of the one-frame entries; and the entry's OWN result block, untouched by the ORB
 // path.  Rank 12 (top-up and masked detection) adds, beside the workspace and for the same number of frames, the bit
@@ -389,7 +405,9 @@ struct orbx_ctx {
   // tracker waits for the good-features event, the landmarks build and the tracks pose wait for the windows
   // tracker's, the window poses wait for the tracks pose's, the chained landmarks build for the window poses', and
   // the write-back gate for the solve's, and the stitch for the window poses' (chain and gate share one event); the
-  // PnP batch waits for the landmarks' event (build and solve share one) and the seeded solve for the PnP batch's.
+  // PnP batch waits for the landmarks' event (build and solve share one) and the seeded solve for the PnP batch's; the
+  // carry waits for the landmarks' and the top-up's, the carried PnP for the windows tracker's, and the carried
+  // landmarks build for the carried PnP's (carry and carried PnP share one event).
   orbx_host::StageScratch s;
   orbx_host::Matcher m;
   orbx_host::LkPair lk;
@@ -403,6 +421,7 @@ struct orbx_ctx {
   orbx_host::WindowPoses wp;
   orbx_host::StreamStitch st;
   orbx_host::Pnp pnp;
+  orbx_host::Carry carry;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -508,7 +527,8 @@ int stage_tracks(orbx_ctx* c, SideWork& side, DevBuf& stage, const float* tracks
 // are checked when they come from the host (poses6 != NULL).  lm_run enqueues the build on s with the poses from the
 // host (poses6, through the pinned mirror) or from the window-poses block (poses6 == NULL: d_poses6 and d_pose_status,
 // copied on s behind that block's event).  views: NULL for the build of rank 10, else the options of the build from
-// every view of a track (rank 15), checked by lm_views_ok
+// every view of a track (rank 15), checked by lm_views_ok.  producer: the work that wrote d_poses6 when that is not the
+// window-poses block (the carried PnP, rank 18)
 struct LmViewsOptions {
   int tri_mode;
   double max_reproj_px;
@@ -519,7 +539,7 @@ int lm_check_build(orbx_ctx* c, const double* K, const void* tracks, const void*
                    const double* poses6);
 int lm_run(orbx_ctx* c, const double* K, const float* d_tracks, const int32_t* d_seen, int n, int cap, int len,
            const double* poses6, const double* d_poses6, const int32_t* d_pose_status, hipStream_t s,
-           const LmViewsOptions* views = nullptr);
+           const LmViewsOptions* views = nullptr, const SideWork* producer = nullptr);
 // the argument rules of orbx_tracks_pose_device (orbx_api_tracks.cpp)
 int tp_check(orbx_ctx* c, const double* K, const void* tracks, const void* seen, int n, int cap, int len, double prob,
              double threshold, int max_iters);

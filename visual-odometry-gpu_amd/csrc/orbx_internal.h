@@ -272,7 +272,31 @@ struct OrbxPnpIn {
 hipError_t orbx_launch_pnp(hipStream_t s, int n_windows, int window_len, int cap, const OrbxPnpIn& in, int n_pre,
                            const double* K4, double prob, double threshold_px, int max_iters, uint64_t seed,
                            int refine_iters, int min_inliers, OrbxPnpCorr* d_corr, int32_t* d_cidx,
-                           OrbxPnpRecord* d_rec, double* d_seeded6, uint8_t* d_mask);
+                           OrbxPnpRecord* d_rec, double* d_seeded6, uint8_t* d_mask,
+                           const int32_t* d_ncorr = nullptr);
+// d_ncorr != NULL (rank 18; `in` empty, d_seeded6 NULL): one workgroup per (window, frame k >= 0), problem
+// w * window_len + k, every row of d_corr / d_cidx gathered already by orbx_launch_carry_gather; d_ncorr: the
+// problem's count, or -1 for ORBX_PNP_SKIPPED; the mask is indexed by d_cidx (the slot)
+
+// ---- landmarks carried into the next window (orbx_carry.hip) --------------------------------
+enum { CARRY_OK = 0, CARRY_LOST = 1 };
+// the old block a carry reads: status [n], pt_off [n + 1], the ascending slot_of_point and the coordinates (3 doubles)
+// of every landmark, and the old windows' slot capacity
+struct OrbxCarryIn {
+  const int32_t *status, *pt_off, *slot;
+  const double* src;
+  int old_cap;
+};
+// d_origin / d_point: n_windows * cap; d_xyz: 3 doubles per slot; d_count: one per window
+hipError_t orbx_launch_carry_join(hipStream_t s, const OrbxCarryIn& in, const int32_t* d_origin, int n_windows, int cap,
+                                  double* d_xyz, int32_t* d_point, int32_t* d_count);
+// d_corr / d_cidx: one row of `cap` per problem (w, k), problem w * window_len + k; d_ncorr: one per problem
+hipError_t orbx_launch_carry_gather(hipStream_t s, const double* d_xyz, const int32_t* d_point, const int32_t* d_count,
+                                    const float* d_tracks, const int32_t* d_seen, int n_windows, int cap, int window_len,
+                                    OrbxPnpCorr* d_corr, int32_t* d_cidx, int32_t* d_ncorr);
+// d_rec: window_len records per window; d_poses6: 6 doubles per (window, frame); d_wstatus: one per window
+hipError_t orbx_launch_carry_fill(hipStream_t s, const OrbxPnpRecord* d_rec, int n_windows, int window_len,
+                                  double* d_poses6, int32_t* d_wstatus);
 
 // ---- overlapping windows joined into one trajectory (orbx_stitch.hip) ------------------------
 // Window w of window_len frames starts at stream frame w * stride, 1 <= stride <= window_len - 1.

@@ -271,6 +271,39 @@ struct PnpScratch : private Sections {
         bytes(off) {}
 };
 
+// ---- landmarks carried into n windows of cap slots, and the PnP of every one of their len >= 2 frames against them ----
+// the carry block: xyz (3 doubles per slot) | point (one per slot) | count (one per window)
+struct CarryBlock : private Sections {
+  size_t slots, xyz, point, count, bytes;
+  CarryBlock(size_t n, size_t cap)
+      : slots(n * cap), xyz(take(sizeof(double) * 3 * slots)), point(take(sizeof(int32_t) * slots)),
+        count(take(sizeof(int32_t) * n)), bytes(off) {}
+};
+// the carried PnP's result block: records (one per (window, frame)) | poses6 (n x len x 6) | window_status (one per
+// window) | mask (one row of cap bytes per problem)
+struct CarryPnpBlock : private Sections {
+  size_t problems, records, poses6, status, mask, bytes;
+  CarryPnpBlock(size_t n, size_t cap, size_t len)
+      : problems(n * len), records(take(sizeof(OrbxPnpRecord) * problems)), poses6(take(sizeof(double) * 6 * problems)),
+        status(take(sizeof(int32_t) * n)), mask(take(problems * cap)), bytes(off) {}
+};
+// its scratch: every problem's gathered correspondences | the slot each came from | the problem's count
+struct CarryPnpScratch : private Sections {
+  size_t corr, cidx, ncorr, bytes;
+  CarryPnpScratch(size_t n, size_t cap, size_t len)
+      : corr(take(sizeof(OrbxPnpCorr) * n * len * cap)), cidx(take(sizeof(int32_t) * n * len * cap)),
+        ncorr(take(sizeof(int32_t) * n * len)), bytes(off) {}
+};
+// what goes up with the one-window host entry: status (1) | pt_off (2) | slot_of_point | points3 (n_old each) | origin
+// | seen (n_slots each) | tracks (n_slots x len x 2 floats)
+struct CarryStage : private Sections {
+  size_t status, pt_off, slot, points, origin, seen, tracks, bytes;
+  CarryStage(size_t n_old, size_t n_slots, size_t len)
+      : status(take(sizeof(int32_t))), pt_off(take(sizeof(int32_t) * 2)), slot(take(sizeof(int32_t) * n_old)),
+        points(take(sizeof(double) * 3 * n_old)), origin(take(sizeof(int32_t) * n_slots)),
+        seen(take(sizeof(int32_t) * n_slots)), tracks(take(sizeof(float) * 2 * n_slots * len)), bytes(off) {}
+};
+
 // ---- n overlapping windows of len frames, window w starting at stream frame w * stride, joined into one trajectory ----
 // the frames of the stream
 inline size_t st_stream_frames(size_t n, size_t len, size_t stride) { return (n - 1) * stride + len; }

@@ -7,6 +7,9 @@
 //             stride the correspondences to score every model, one lane selects in (iteration, model) order
 //   refine    Levenberg-Marquardt on the best model's inliers, sums by rule 9
 //   final     mask, inlier count and RMS of the pose that is kept, the record and the seeded pose
+// The problems of rank 18 (every frame of a window against landmarks carried from the window before, orbx_carry.hip)
+// come gathered and skip the prologue; they differ from the host-array problem in where the count, the seed and the
+// mask's index come from, nowhere in the arithmetic.
 // All arithmetic comes from orbx_pnp_math.h, compiled with -ffp-contract=off, so each problem's result equals the
 // sequential restatement (tests/cpp/pnp_sequential.cpp) bit for bit.  No atomics.
 #include <hip/hip_runtime.h>
@@ -28,6 +31,9 @@ struct PnpArgs {
   double prob, thr2;
   uint64_t seed;
   int n_pre;  // the correspondences of a problem that comes gathered (in.status == NULL)
+  // not NULL: EVERY problem comes gathered (orbx_carry.hip, rank 18), frames 0 and 1 included: its count, or -1 for a
+  // window with nothing carried; the seed is the problem's by its frame and the mask is indexed through cidx
+  const int32_t* ncorr;
   int window_len, cap, max_iters, refine_iters, min_inliers;
   OrbxPnpCorr* corr;
   int32_t* cidx;
@@ -93,11 +99,13 @@ __device__ __forceinline__ void pnp_pass(const PnpArgs& a, const OrbxPnpCorr* C,
 __global__ __launch_bounds__(PNP_THREADS) void k_pnp_ransac(const PnpArgs a) {
   __shared__ PnpShared S;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int per_win = a.window_len - 2;
-  const int prob_i = blockIdx.x, w = prob_i / per_win, k = 2 + prob_i % per_win;
+  const bool carried = a.ncorr != nullptr;
+  const int k0 = carried ? 0 : 2, per_win = a.window_len - k0;
+  const int prob_i = blockIdx.x, w = prob_i / per_win, k = k0 + prob_i % per_win;
   const int cap = a.cap;
   const bool gathered = a.in.status == nullptr;
-  const uint64_t seed = gathered ? a.seed : pnp_problem_seed(a.seed, (uint32_t)k);
+  const bool by_index = gathered && !carried;  // the host-array problem: its own seed, the mask in its own order
+  const uint64_t seed = by_index ? a.seed : pnp_problem_seed(a.seed, (uint32_t)k);
   OrbxPnpCorr* C = a.corr + (size_t)prob_i * cap;
   int32_t* CI = a.cidx + (size_t)prob_i * cap;
   uint8_t* M = a.mask + (size_t)prob_i * cap;
@@ -112,7 +120,10 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_ransac(const PnpArgs a) {
     if (k == 2 && tid < 12) seeded[tid] = built[tid];
   }
   int status = PNP_OK, n = 0, iters = 0;
-  if (gathered) {
+  if (carried) {
+    n = a.ncorr[prob_i];
+    if (n < 0) n = 0, status = PNP_SKIPPED;
+  } else if (gathered) {
     n = a.n_pre;
   } else if (a.in.status[w] != LM_OK) {
     status = PNP_SKIPPED;
@@ -289,7 +300,7 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_ransac(const PnpArgs a) {
     const OrbxPnpCorr q = C[p];
     double e2;
     if (pnp_inlier(a.K4, Mk, q.X, q.x, q.y, a.thr2, &e2)) {
-      M[gathered ? p : CI[p]] = 1;
+      M[by_index ? p : CI[p]] = 1;
       sum[0] = sum[0] + e2;
       cnt++;
     }
@@ -313,8 +324,9 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_ransac(const PnpArgs a) {
 hipError_t orbx_launch_pnp(hipStream_t s, int n_windows, int window_len, int cap, const OrbxPnpIn& in, int n_pre,
                            const double* K4, double prob, double threshold_px, int max_iters, uint64_t seed,
                            int refine_iters, int min_inliers, OrbxPnpCorr* d_corr, int32_t* d_cidx,
-                           OrbxPnpRecord* d_rec, double* d_seeded6, uint8_t* d_mask) {
-  if (n_windows <= 0 || window_len < 3) return hipSuccess;
+                           OrbxPnpRecord* d_rec, double* d_seeded6, uint8_t* d_mask, const int32_t* d_ncorr) {
+  const int per_win = window_len - (d_ncorr ? 0 : 2);
+  if (n_windows <= 0 || per_win < 1) return hipSuccess;
   PnpArgs a;
   a.in = in;
   for (int i = 0; i < 4; i++) a.K4[i] = K4[i];
@@ -322,9 +334,10 @@ hipError_t orbx_launch_pnp(hipStream_t s, int n_windows, int window_len, int cap
   a.thr2 = threshold_px * threshold_px;
   a.seed = seed;
   a.n_pre = n_pre;
+  a.ncorr = d_ncorr;
   a.window_len = window_len, a.cap = cap, a.max_iters = max_iters, a.refine_iters = refine_iters;
   a.min_inliers = min_inliers;
   a.corr = d_corr, a.cidx = d_cidx, a.rec = d_rec, a.seeded6 = d_seeded6, a.mask = d_mask;
-  hipLaunchKernelGGL(k_pnp_ransac, dim3(n_windows * (window_len - 2)), dim3(PNP_THREADS), 0, s, a);
+  hipLaunchKernelGGL(k_pnp_ransac, dim3(n_windows * per_win), dim3(PNP_THREADS), 0, s, a);
   return hipGetLastError();
 }

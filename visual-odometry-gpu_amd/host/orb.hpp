@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "../../include/orbx_carry.h"
 #include "../../include/orbx_lm.h"
 #include "../../include/orbx_pnp.h"
 #include "../../include/orbx_stream.h"
@@ -1411,6 +1412,50 @@ inline bool solvePnPRansac(const std::vector<Point3d>& objectPoints, const std::
   if (r.status != ORBX_PNP_OK) return false;
   for (int i = 0; i < 3; i++) rvec[i] = pose6[i], tvec[i] = pose6[3 + i];
   return true;
+}
+
+// ---- landmarks carried into the next window and the window localised against them -------
+// The map-tracking step of a KLT front-end, where the reference re-detects at every solve
+// (src/with_bundle_adjustment.cpp:586-593) and chains cur_pose = prev_pose * T.inv()
+// (src/with_bundle_adjustment.cpp:196-208): the new window's slot s continues the old window's slot origin[s] (-1: a
+// fresh point), the old window's landmarks are old_points with old_slot_of_point (ascending), and EVERY frame of the
+// new window -- tracks (slots x n_frames) and seen, the layout of track_points_across_window's one-launch forms -- is
+// localised against the carried landmarks by solvePnPRansac's rules, in the old window's own metric frame.
+struct CarriedWindow {
+  std::vector<orbx_pnp_record> records;  // one per frame
+  std::vector<double> poses6;            // n_frames x 6: angle-axis and translation, world -> camera
+  int32_t status = ORBX_CARRY_LOST;      // an orbx_carry_status
+  std::vector<int32_t> carried_point;    // per slot: the landmark's index in old_points, or -1
+  bool ok() const { return status == ORBX_CARRY_OK; }
+};
+inline CarriedWindow localise_carried_window(const std::vector<Point3d>& old_points,
+                                             const std::vector<int32_t>& old_slot_of_point,
+                                             const std::vector<int32_t>& origin, const std::vector<Point2f>& tracks,
+                                             const std::vector<int32_t>& seen, int n_frames, const double K[9],
+                                             int iterationsCount = 100, double reprojectionError = 8.0,
+                                             double confidence = 0.99, uint64_t seed = 0, int refine_iters = 10,
+                                             int min_inliers = 4) {
+  static_assert(sizeof(Point3d) == 3 * sizeof(double) && sizeof(Point2f) == 2 * sizeof(float), "point layouts");
+  if (old_points.size() != old_slot_of_point.size())
+    throw std::invalid_argument("localise_carried_window: old_points and old_slot_of_point differ in size");
+  if (n_frames < 2) throw std::invalid_argument("localise_carried_window: a window has at least two frames");
+  if (origin.size() != seen.size() || tracks.size() != seen.size() * (size_t)n_frames)
+    throw std::invalid_argument("localise_carried_window: origin, tracks and seen differ in size");
+  const int n_old = (int)old_points.size(), n = (int)seen.size();
+  CarriedWindow out;
+  out.records.resize((size_t)n_frames);
+  out.poses6.assign((size_t)6 * n_frames, 0.0);
+  out.carried_point.assign((size_t)n, -1);
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_localise_carried_window(c, n_old > 0 ? &old_points[0].x : nullptr,
+                                             n_old > 0 ? old_slot_of_point.data() : nullptr, n_old, origin.data(),
+                                             reinterpret_cast<const float*>(tracks.data()), seen.data(), n, n_frames, K,
+                                             confidence, reprojectionError, iterationsCount, seed, refine_iters,
+                                             min_inliers, out.records.data(), out.poses6.data(), &out.status,
+                                             out.carried_point.data()),
+                "orbx_localise_carried_window");
+  return out;
 }
 
 // ---- Shi-Tomasi corners (next row) ----------------------------------
