@@ -738,6 +738,7 @@ void orbx_destroy(orbx_ctx* c) {
   // every subsystem releases what it owns.  The landmarks before the windows tracker, the tracker before the good
   // features: each waits for its own event before its buffers go, and each may be reading the next one's block.
   c->carry.release();
+  c->reloc.release();
   c->pnp.release();
   c->st.release();
   c->wp.release();

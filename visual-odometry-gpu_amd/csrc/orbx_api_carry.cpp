@@ -137,6 +137,7 @@ int orbx_landmarks_carry_device(orbx_ctx* c, const int32_t* d_origin, int n_wind
   // the block and its solve may have been written on another stream; so may the top-up's origin
   if ((st = c->carry.side.after(c, c->lm.side, s)) != ORBX_OK) return st;
   if ((st = c->carry.side.after(c, c->gf.side, s)) != ORBX_OK) return st;
+  if ((st = c->carry.side.after(c, c->reloc.side, s)) != ORBX_OK) return st;  // (or the re-association's, rank 19)
   const LmBlock L((size_t)c->lm.n, (size_t)c->lm.cap, (size_t)c->lm.len);
   const LmSolve V((size_t)c->lm.n, (size_t)c->lm.cap, (size_t)c->lm.len);
   OrbxCarryIn in;

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/orbx_reloc.h"
 #include "orbx_internal.h"
 #include "orbx_layout.h"
 #include "orbx_tables.h"
@@ -318,6 +319,24 @@ struct Carry {
   }
 };
 
+// descriptors at caller-held points and the re-association of two described sets (orbx_reloc.hip; rank 19): the
+// level-0 frames of one slice (ws, bounded by ws_limit), the OK slots of every frame in slot order (list), the two
+// banks' OWN result blocks (PdBlock of orbx_layout.h), the staged image and points of the one-image host entry
+// (PdStage); the re-association's scratch (the best key per train slot), its OWN result block (RaBlock) and the staged
+// sets of the one-window host entry (RaStage).  The describe reads the caller's frames and points, the re-association
+// the caller's descriptors and states -- the banks, when they are views of those; nothing is written elsewhere.
+struct Reloc {
+  DevBuf ws, list, bank[2], stage, best, rblk, rstage;
+  size_t ws_limit = ORBX_PD_WORKSPACE_DEFAULT;
+  int n[2] = {0, 0}, cap[2] = {0, 0};  // frames and slots per frame of each bank (n == 0: not written)
+  int rn = 0, rq = 0, rt = 0;          // windows, query and train slots of the last re-association (rn == 0: none)
+  SideWork side;                       // the event is recorded behind every describe and every re-association
+  void release() {
+    side.release();
+    free_bufs({&ws, &list, &bank[0], &bank[1], &stage, &best, &rblk, &rstage});
+  }
+};
+
 // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames, allocated on first use and bounded by
 // ws_limit; the staged host image of the one-frame entries; and the entry's OWN result block, untouched by the ORB
 // path.  Rank 12 (top-up and masked detection) adds, beside the workspace and for the same number of frames, the bit
@@ -407,7 +426,9 @@ struct orbx_ctx {
   // the write-back gate for the solve's, and the stitch for the window poses' (chain and gate share one event); the
   // PnP batch waits for the landmarks' event (build and solve share one) and the seeded solve for the PnP batch's; the
   // carry waits for the landmarks' and the top-up's, the carried PnP for the windows tracker's, and the carried
-  // landmarks build for the carried PnP's (carry and carried PnP share one event).
+  // landmarks build for the carried PnP's (carry and carried PnP share one event); the point descriptors wait for the
+  // good features' and the windows tracker's, and the carry also for the re-association's (describe and
+  // re-association share one event).
   orbx_host::StageScratch s;
   orbx_host::Matcher m;
   orbx_host::LkPair lk;
@@ -422,6 +443,7 @@ struct orbx_ctx {
   orbx_host::StreamStitch st;
   orbx_host::Pnp pnp;
   orbx_host::Carry carry;
+  orbx_host::Reloc reloc;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;

@@ -298,6 +298,28 @@ hipError_t orbx_launch_carry_gather(hipStream_t s, const double* d_xyz, const in
 hipError_t orbx_launch_carry_fill(hipStream_t s, const OrbxPnpRecord* d_rec, int n_windows, int window_len,
                                   double* d_poses6, int32_t* d_wstatus);
 
+// ---- descriptors at caller-held points and the re-association (orbx_reloc.hip) --------------
+enum { PD_NONE = 0, PD_BORDER = 1, PD_OK = 2 };  // = orbx_pd_state
+#define PD_R_MIN 20  // rule C: the BRIEF pattern's reach (18) plus the 5x5 box (2)
+// how k_pd_level0 makes the level-0 image: an orbx_blur_kind, or the plain copy
+#define PD_LEVEL0_COPY 2
+// d_level0: n images of pitch x h bytes (pitch a multiple of 4, >= w), img_stride (a multiple of 4) apart
+hipError_t orbx_launch_pd_level0(hipStream_t s, const uint8_t* d_frames, int n, int w, int h, int row_stride,
+                                 size_t frame_stride, int kind, uint8_t* d_level0, int pitch, size_t img_stride);
+// n <= 65535 frames.  d_xy / d_seen / d_counts: the point source of frame 0 of the n (d_seen, d_counts may be NULL);
+// d_state / d_angle / d_desc / d_list: one row of `cap` per frame; d_n_ok: one per frame.  d_list is scratch
+hipError_t orbx_launch_pd_describe(hipStream_t s, const uint8_t* d_level0, int n, int w, int h, int pitch,
+                                   size_t img_stride, const float* d_xy, size_t point_stride, size_t xy_frame_stride,
+                                   const int32_t* d_seen, int seen_min, const int32_t* d_counts, int cap, int patch_size,
+                                   int32_t* d_state, float* d_angle, orbx_descriptor* d_desc, int32_t* d_n_ok,
+                                   int32_t* d_list);
+// n_windows <= 65535, qcap <= 2^22.  d_best: n_windows * tcap words of scratch (unique only); d_origin / d_dist:
+// n_windows * qcap; d_count: one per window
+hipError_t orbx_launch_reassociate(hipStream_t s, int n_windows, const orbx_descriptor* d_qdesc,
+                                   const int32_t* d_qstate, int qcap, const orbx_descriptor* d_tdesc,
+                                   const int32_t* d_tstate, int tcap, double ratio, int max_distance, int unique,
+                                   uint32_t* d_best, int32_t* d_origin, int32_t* d_dist, int32_t* d_count);
+
 // ---- overlapping windows joined into one trajectory (orbx_stitch.hip) ------------------------
 // Window w of window_len frames starts at stream frame w * stride, 1 <= stride <= window_len - 1.
 // d_scale: the tracks-pose block's scale rows; d_scale0: one double per window (the chain's input section)

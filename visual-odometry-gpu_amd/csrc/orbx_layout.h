@@ -304,6 +304,46 @@ struct CarryStage : private Sections {
         seen(take(sizeof(int32_t) * n_slots)), tracks(take(sizeof(float) * 2 * n_slots * len)), bytes(off) {}
 };
 
+// ---- descriptors at caller-held points of n frames of cap slots, and the re-association of two described sets ----
+// the level-0 image of a w x h frame in the workspace: rows padded to a multiple of 4 bytes (describe_wave fetches
+// aligned dwords), images a multiple of 256 bytes apart
+inline int pd_pitch(int w) { return (w + 3) & ~3; }
+inline size_t pd_img_stride(int w, int h) { return align_up_sz((size_t)pd_pitch(w) * h, 256); }
+// frames of w x h per slice of n frames within `limit` bytes: what fits (at least one, at most a grid dimension's
+// 65535), in even slices
+inline int pd_slice_frames(size_t limit, int n, int w, int h) {
+  const size_t fit = std::max<size_t>(limit / pd_img_stride(w, h), 1);
+  const int m = (int)std::min<size_t>(std::min<size_t>(fit, (size_t)n), 65535);
+  const int slices = (n + m - 1) / m;
+  return (n + slices - 1) / slices;
+}
+// a bank's result block: desc (32 bytes per slot) | angle | state (one per slot each) | n_ok (one per frame)
+struct PdBlock : private Sections {
+  size_t slots, desc, angle, state, n_ok, bytes;
+  PdBlock(size_t n, size_t cap)
+      : slots(n * cap), desc(take(sizeof(orbx_descriptor) * slots)), angle(take(sizeof(float) * slots)),
+        state(take(sizeof(int32_t) * slots)), n_ok(take(sizeof(int32_t) * n)), bytes(off) {}
+};
+// what goes up with the one-image host entry: the image (tight rows) | the points (two floats each)
+struct PdStage : private Sections {
+  size_t img, xy, bytes;
+  PdStage(size_t w, size_t h, size_t n_points) : img(take(w * h)), xy(take(sizeof(float) * 2 * n_points)), bytes(off) {}
+};
+// the re-association's result block of n windows of qcap query slots: origin | dist (one per slot each) | count
+struct RaBlock : private Sections {
+  size_t slots, origin, dist, count, bytes;
+  RaBlock(size_t n, size_t qcap)
+      : slots(n * qcap), origin(take(sizeof(int32_t) * slots)), dist(take(sizeof(int32_t) * slots)),
+        count(take(sizeof(int32_t) * n)), bytes(off) {}
+};
+// what goes up with the one-window host entry: query desc | query state | train desc | train state
+struct RaStage : private Sections {
+  size_t qdesc, qstate, tdesc, tstate, bytes;
+  RaStage(size_t nq, size_t nt)
+      : qdesc(take(sizeof(orbx_descriptor) * nq)), qstate(take(sizeof(int32_t) * nq)),
+        tdesc(take(sizeof(orbx_descriptor) * nt)), tstate(take(sizeof(int32_t) * nt)), bytes(off) {}
+};
+
 // ---- n overlapping windows of len frames, window w starting at stream frame w * stride, joined into one trajectory ----
 // the frames of the stream
 inline size_t st_stream_frames(size_t n, size_t len, size_t stride) { return (n - 1) * stride + len; }

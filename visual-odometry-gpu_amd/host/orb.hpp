@@ -47,6 +47,7 @@
 #include "../../include/orbx_carry.h"
 #include "../../include/orbx_lm.h"
 #include "../../include/orbx_pnp.h"
+#include "../../include/orbx_reloc.h"
 #include "../../include/orbx_stream.h"
 #include "../../include/orbx_vo.h"
 
@@ -339,6 +340,19 @@ class ORB {
     if (responses) responses->resize(count);
     if (levels) levels->resize(count);
   }
+  // descriptors at points the caller holds (include/orbx_reloc.h): n (x, y) pairs described at
+  // level 0 under this object's parameters; angles in radians, states orbx_pd_state.  Outputs are assigned.
+  void describePoints(const orbx::Image& image, const float* points_xy, int n, std::vector<float>& orientations,
+                      std::vector<ORBDescriptor>& descriptors, std::vector<int32_t>& states) {
+    orbx_ctx* c = ctx_->get(image.width, image.height);
+    orientations.assign((size_t)n, 0.f);
+    descriptors.assign((size_t)n, ORBDescriptor{});
+    states.assign((size_t)n, (int32_t)ORBX_PD_NONE);
+    orbx::detail::check(c,
+                        orbx_describe_points(c, image.data, image.width, image.height, image.stride, points_xy, n,
+                                             orientations.data(), orbx::detail::ds(descriptors), states.data()),
+                        "ORB::describePoints");
+  }
   const orbx_params& params() const { return ctx_->params(); }
 
  private:
@@ -501,6 +515,29 @@ class Feature2D {
   }
   // orb->detect(img, kp)
   void detect(const Image& image, std::vector<KeyPoint>& keypoints) { run(image, keypoints, nullptr); }
+  // orb->compute(img, kp, des), cv::Feature2D::compute's contract: keypoints that cannot be described (their state
+  // is not ORBX_PD_OK: not finite, outside the image or closer than max(patch_size / 2, 20) to a border) are REMOVED,
+  // the rest keep their order, `angle` is filled in degrees and row i of `descriptors` belongs to keypoint i.  The
+  // octaves are ignored: every keypoint is described at level 0, at pt rounded to the nearest pixel (ties to even),
+  // as include/orbx_reloc.h states.  The reference computes with the detection, src/feature_tracking.cpp:201
+  void compute(const Image& image, std::vector<KeyPoint>& keypoints, DescriptorMat& descriptors) {
+    static_assert(sizeof(Point2f) == 2 * sizeof(float), "point layout");
+    std::vector<Point2f> pts;
+    KeyPoint::convert(keypoints, pts);
+    std::vector<int32_t> states;
+    orb_.describePoints(image, pts.empty() ? nullptr : &pts[0].x, (int)pts.size(), angles_, desc_, states);
+    size_t kept = 0;
+    descriptors.d.clear();
+    for (size_t i = 0; i < keypoints.size(); i++) {
+      if (states[i] != ORBX_PD_OK) continue;
+      keypoints[kept] = keypoints[i];
+      keypoints[kept].angle = angle_degrees(angles_[i]);
+      descriptors.d.push_back(desc_[i]);
+      kept++;
+    }
+    keypoints.resize(kept);
+    descriptors.rows = (int)kept;
+  }
   int descriptorSize() const { return 32; }
   const orbx_params& params() const { return orb_.params(); }
 
@@ -555,6 +592,55 @@ class Feature2D {
   std::vector<ORBDescriptor> desc_;
   std::vector<int32_t> levels_;
 };
+
+// ---- descriptors at held points and the re-association by descriptor -----------------------
+// The device half of the reference's ORB + matcher fallback below 150 tracks (src/feature_tracking.cpp:68-71,
+// :203-219), on host arrays: describe_points describes `points` on `image` at level 0 under the stage context's
+// parameters (the GPU defaults: patch 31, no blur), reassociate joins two described sets -- only ORBX_PD_OK slots take
+// part, ratio test, distance gate, and with `unique` one query per train slot -- into origin[q] = the train slot or
+// -1, the array orbx::localise_carried_window takes as `origin`.
+struct PointDescriptors {
+  std::vector<float> angle;             // radians; 0 where the state is not ORBX_PD_OK
+  std::vector<ORBDescriptor> desc;      // zeros where the state is not ORBX_PD_OK
+  std::vector<int32_t> state;           // an orbx_pd_state per point
+};
+inline PointDescriptors describe_points(const Image& image, const std::vector<Point2f>& points) {
+  static_assert(sizeof(Point2f) == 2 * sizeof(float), "point layout");
+  const int n = (int)points.size();
+  PointDescriptors out;
+  out.angle.assign((size_t)n, 0.f);
+  out.desc.assign((size_t)n, ORBDescriptor{});
+  out.state.assign((size_t)n, (int32_t)ORBX_PD_NONE);
+  orbx_ctx* c = detail::stage_ctx()->get(image.width, image.height);
+  detail::check(c,
+                orbx_describe_points(c, image.data, image.width, image.height, image.stride,
+                                     n > 0 ? &points[0].x : nullptr, n, out.angle.data(), detail::ds(out.desc),
+                                     out.state.data()),
+                "orbx_describe_points");
+  return out;
+}
+struct Reassociation {
+  std::vector<int32_t> origin, dist;  // per query: the train slot and the Hamming distance to it, or -1
+  int32_t count = 0;
+};
+inline Reassociation reassociate(const PointDescriptors& query, const PointDescriptors& train, double ratio = 0.8,
+                                 int max_distance = 256, bool unique = true) {
+  if (query.desc.size() != query.state.size() || train.desc.size() != train.state.size())
+    throw std::invalid_argument("reassociate: desc and state differ in size");
+  const int nq = (int)query.desc.size(), nt = (int)train.desc.size();
+  Reassociation out;
+  out.origin.assign((size_t)nq, -1);
+  out.dist.assign((size_t)nq, -1);
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_reassociate(c, nq > 0 ? reinterpret_cast<const orbx_descriptor*>(query.desc.data()) : nullptr,
+                                 nq > 0 ? query.state.data() : nullptr, nq,
+                                 nt > 0 ? reinterpret_cast<const orbx_descriptor*>(train.desc.data()) : nullptr,
+                                 nt > 0 ? train.state.data() : nullptr, nt, ratio, max_distance, unique ? 1 : 0,
+                                 out.origin.data(), out.dist.data(), &out.count),
+                "orbx_reassociate");
+  return out;
+}
 
 // VisualOdom::get_matches (src/feature_matching.cpp:155-183): detect + describe frame 2,
 // 2-NN match frame 1 -> 2, keep `m.distance < 0.8 * n.distance`, return the matched points.
