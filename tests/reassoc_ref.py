@@ -108,6 +108,26 @@ def flip(desc, rng, nbits):
     return d
 
 
+def pool_window(rng, qcap, tcap, size=40):
+    """One window in the manner of test_matcher.tie_heavy, both sets drawn from a pool of `size` descriptors: (qdesc
+    (qcap, 32), tdesc (tcap, 32)).  The first train slots hold distinct pool descriptors, so a query's copy is alone at
+    distance 0 and is accepted -- equal queries, of whatever 256-block, tie for that train slot under `unique` --
+    unless one of the later train slots (one in twenty holds a pool descriptor, the rest random bytes) repeats it:
+    d1 == d2, the ratio fails.  A fifth of the queries have one to three bits flipped: the same train slot at a larger
+    distance."""
+    pool = rng.integers(0, 256, (size, 32), dtype=np.uint8)
+    tdesc = rng.integers(0, 256, (tcap, 32), dtype=np.uint8)
+    m = min(size, tcap)
+    tdesc[:m] = pool[rng.permutation(size)[:m]]
+    rep = np.flatnonzero(rng.random(tcap) < 0.05)
+    rep = rep[rep >= m]
+    tdesc[rep] = pool[rng.integers(0, size, len(rep))]
+    qdesc = pool[rng.integers(0, size, qcap)]
+    for q in np.flatnonzero(rng.random(qcap) < 0.2):
+        qdesc[q] = flip(qdesc[q], rng, int(rng.integers(1, 4)))
+    return qdesc, tdesc
+
+
 def synthetic_windows(qcap=70, tcap=300, seed=11):
     """Three windows of seeded random 256-bit descriptors: (qdesc (3, qcap, 32), qstate, tdesc (3, tcap, 32), tstate).
     0: 250 OK train slots (others NONE / BORDER with random bytes that must not take part), queries that are copies of

@@ -16,9 +16,11 @@ Only calls that DESIGN.md §9 and include/orbx.h define are drawn; no draw is on
 tests/test_side_random_ref.py checks the draws on the CPU (classes covered, restatement against numpy),
 tests/test_side_random.py runs them on the GPU, tools/fuzz_sides.py runs an open index range."""
 import atexit
+import contextlib
 import ctypes as C
 import importlib
 import os
+import pathlib
 import shutil
 import subprocess
 import sys
@@ -26,11 +28,15 @@ import tempfile
 
 import numpy as np
 
+import carry_ref as CR
 import gftt_ref as G
 import gftt_topup_ref as T
 import landmarks_ref as LR
 import landmarks_seq as LS
 import landmarks_views_seq as VS
+import oracle_lib as O
+import pnp_seq as PS
+import reassoc_ref as RR
 import stitch_seq as SS
 import tracks_pose_ref as TR
 import window_poses_ref as WR
@@ -45,7 +51,7 @@ if os.path.join(ROOT, "tools") not in sys.path:
     sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fuzz_parity  # noqa: E402  (its image kinds)
 
-FAMILIES = ("matcher", "pose", "scale", "ba", "corners", "tracks", "landmarks")
+FAMILIES = ("matcher", "pose", "scale", "ba", "corners", "tracks", "landmarks", "pnp", "carry", "reloc")
 # the one small context every draw of a test or a campaign runs on
 CONTEXT = dict(max_width=160, max_height=160, max_batch=8)
 
@@ -70,6 +76,32 @@ GF_DISTANCES = (0.0, 0.5, 1.0)
 GF_MAX_CORNERS = (1, 5, 64, 65, 2000)
 GF_SEED_COUNTS = (1, 255, 256, 257)
 GF_LDS_KEYS = 8192  # k_gftt_select sorts candidate lists up to this length in LDS, longer ones in the key pool
+PNP_SLOTS = (1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 513)
+PNP_WINDOW_LEN = (3, 4, 5, 8)
+PNP_ITERS = (0, 1, 63, 64, 65, 128, 300)
+PNP_PROB = (0.5, 0.99, 0.999)
+PNP_THRESHOLD = (0.5, 1.0, 2.0)
+PNP_REFINE = (0, 1, 10, 20)
+PNP_MIN_INLIERS = (4, 30)
+PNP_KINDS = ("clean", "outliers", "ragged", "baseline", "three", "junk", "plane", "padded")
+PNP_CHUNK = 64     # k_pnp_ransac solves this many samples per round
+PNP_LANES = 256    # ... with a workgroup of this many lanes: every `p += PNP_THREADS` loop runs twice beyond it
+CARRY_SLOTS = (1, 5, 63, 64, 65, 255, 256, 257, 513)
+CARRY_KINDS = ("generations", "outliers", "origins", "ragged", "old_baseline", "old_bad_pose", "three", "junk")
+RELOC_WIDTHS = (41, 42, 43, 63, 64, 65, 66, 67, 127, 128, 129, 157, 158, 159, 160)
+RELOC_HEIGHTS = (41, 47, 48, 49, 63, 64, 65, 160)
+RELOC_SLOTS = (1, 3, 4, 5, 255, 256, 257, 513)
+RA_CAPS = (1, 2, 255, 256, 257, 512, 513)
+RA_KINDS = ("flipped", "pool", "mixed", "one", "none")
+RA_RATIOS = (0.7, 0.8, 1.0)
+RA_MAX_DISTANCE = (0, 40, 256)
+RA_INPUTS = ("arrays", "banks", "host")
+# the contexts of the reloc family: the level-0 kind (blur_levels 2: the blur of blur_kind; otherwise the copy) and
+# patch_size are context parameters.  Draw `index` runs on RELOC_CONTEXTS[(index // 4) % 5]
+RELOC_CONTEXTS = (dict(blur_levels=0, blur_kind=0, patch_size=31), dict(blur_levels=2, blur_kind=0, patch_size=9),
+                  dict(blur_levels=2, blur_kind=1, patch_size=15), dict(blur_levels=1, blur_kind=0, patch_size=1),
+                  dict(blur_levels=2, blur_kind=0, patch_size=41))
+RELOC_LEVEL0 = ("copy", "sep16", "k273", "copy", "sep16")  # what RELOC_CONTEXTS[i] describes on
 
 _LIBS = {}
 _TMP = []
@@ -82,6 +114,9 @@ def seq_lib(name):
     if not _TMP:
         _TMP.append(tempfile.mkdtemp(prefix="side_random_"))
         atexit.register(shutil.rmtree, _TMP[0], ignore_errors=True)
+    if name == "pnp":  # (its prototypes are pnp_seq's)
+        _LIBS[name] = PS.compile_so(pathlib.Path(_TMP[0]))
+        return _LIBS[name]
     out = os.path.join(_TMP[0], name + "_sequential.so")  # (pose, scale, ba, st, wp, lm, lm_views)
     subprocess.check_call(TS.CXX + ["-o", out, os.path.join(ROOT, "tests", "cpp", name + "_sequential.cpp")])
     lib = C.CDLL(out)
@@ -683,10 +718,521 @@ def diff_landmarks(got, exp):
     return out
 
 
+# ---- window PnP over the landmarks block (rank 17) ---------------------------------------------------------------
+def _weighted(rng, names, weights):
+    return names[int(rng.choice(len(names), p=np.asarray(weights, float) / sum(weights)))]
+
+
+def _pnp_params(rng, index):
+    """the parameters of a PnP call: max_iters in turn by the index, the others drawn"""
+    seed = int(rng.integers(0, 2**32)) if rng.random() < 0.5 else int(rng.integers(2**32, 2**64, dtype=np.uint64))
+    return dict(prob=PNP_PROB[int(rng.integers(0, 3))], threshold_px=PNP_THRESHOLD[int(rng.integers(0, 3))],
+                max_iters=PNP_ITERS[index % len(PNP_ITERS)], seed=seed,
+                refine_iters=PNP_REFINE[int(rng.integers(0, 4))],
+                min_inliers=PNP_MIN_INLIERS[int(rng.integers(0, 4)) == 0])
+
+
+def _pnp_scene(rng, kind, W, cap):
+    """One window of `cap` slots by the kinds of test_pnp.batch_scenes: (scene, declared outlier share, live slots)."""
+    import test_pnp as TPN
+
+    s = int(rng.integers(0, 2**31))
+    share = 0.0
+    if kind == "plane" and cap < 4:
+        kind = "clean"
+    if kind == "outliers":  # 10 to 50 % of the observations of frames >= 2; above 30 % with pixel noise as well
+        share = float(rng.uniform(0.1, 0.5))
+        sc = LR.make_scene(s, W=W, slots=cap, min_seen=W, outliers=share, pose_pert=0.002,
+                           sigma=0.3 if share > 0.3 and rng.random() < 0.5 else 0.0)
+        if rng.random() < 0.4:  # one frame with 55 to 75 % of random pixels: RANSAC runs beyond its first chunk there
+            k, share = int(rng.integers(2, W)), float(rng.uniform(0.55, 0.75))
+            bad = rng.random(cap) < share
+            junk = np.c_[rng.uniform(0, LR.IMG_W, cap), rng.uniform(0, LR.IMG_H, cap)].astype(np.float32)
+            sc["tracks"][:, k] = np.where((bad & (sc["seen"] > k))[:, None], junk, sc["tracks"][:, k])
+    elif kind == "ragged":
+        sc = LR.make_scene(s, W=W, slots=cap, min_seen=(0, 2)[int(rng.integers(0, 2))], pose_pert=0.002)
+    elif kind == "junk":  # a dozen live slots, one frame >= 2 of random pixels
+        live = min(cap, 12)
+        sc = TPN.pad(LR.make_scene(s, W=W, slots=live, min_seen=W), cap)
+        k = int(rng.integers(2, W))
+        sc["tracks"][:live, k] = np.c_[rng.uniform(0, LR.IMG_W, live), rng.uniform(0, LR.IMG_H, live)]
+    elif kind == "plane":  # four points of the plane z = 12
+        sc = TPN.pad(LR.make_scene(s, W=W, slots=4, min_seen=W), cap)
+        pix = np.array([[300.0, 80.0, 1.0], [900.0, 100.0, 1.0], [350.0, 300.0, 1.0], [880.0, 290.0, 1.0]])
+        sc["tracks"][:4] = TPN.project(sc["true_poses"], (np.linalg.inv(LR.K_KITTI) @ pix.T).T * 12.0)
+    elif kind == "padded":  # seen = 0 behind the live slots: n_corr < cap
+        live = int(rng.integers(cap // 2 + 1, cap + 1))
+        sc = TPN.pad(LR.make_scene(s, W=W, slots=live, min_seen=W, pose_pert=0.002), cap)
+    else:
+        sc = LR.make_scene(s, W=W, slots=cap, min_seen=W, pose_pert=0.0 if kind == "baseline" else 0.002)
+    if kind == "baseline":
+        sc["poses"][1, 3:] = sc["poses"][0, 3:] + np.array([0.01, 0.0, 0.02])
+    if kind == "three":
+        sc["seen"][3:] = 0
+        sc["tracks"][3:] = 0
+    return sc, share, int((sc["seen"] >= 2).sum())
+
+
+def draw_pnp(seed, index):
+    """A batch of windows through orbx_landmarks_build_device and orbx_window_poses_pnp_device; on two draws of four
+    one of its problems through the host entry orbx_pnp_ransac too, on every fourth one of at most 257 slots the solve
+    seeded with the PnP poses (orbx_bundle_adjust_landmarks_pnp_device)."""
+    rng = _rng("pnp", seed, index)
+    cap = _pick(rng, index, 0, PNP_SLOTS, 1, 600)
+    W = PNP_WINDOW_LEN[(index // 2) % 4]
+    n = int(rng.integers(1, 7))
+    kinds = tuple(_weighted(rng, PNP_KINDS, (3, 3, 1, 1, 1, 1, 1, 2)) for _ in range(n))
+    made = [_pnp_scene(rng, k, W, cap) for k in kinds]
+    scenes = [m[0] for m in made]
+    poses, tracks, seen = LR.stack(scenes)
+    params = _pnp_params(rng, index)
+    K = LR.K_KITTI
+    pnp = seq_lib("pnp")
+    block = LS.seq_build(seq_lib("lm"), K, poses, tracks, seen)
+    exp = dict(block=block, pnp=PS.windows(pnp, K, block, poses, cap, **params))
+    d = dict(family="pnp", seed=seed, index=index, cap=cap, W=W, kinds=kinds, scenes=scenes, params=params, K=K,
+             shares=[m[1] for m in made], live=[m[2] for m in made], poses=poses, tracks=tracks, seen=seen,
+             host=None, solve=None)
+    w, k = int(rng.integers(0, n)), int(rng.integers(2, W))
+    delta, ba_iters = BA_DELTA[int(rng.integers(0, 2))], int(rng.integers(1, 21))
+    # problem (w, k) on host arrays, under the seed the batch gives frame k: on two draws of four, an odd and an even
+    # index, so that the host entry meets the boundary capacities (even indices) and the uniform ones (odd) alike
+    if index % 4 in (1, 2):
+        pts, _, op, oq, xy = LS.window_of(block, w)
+        sel = oq == k
+        one = dict(params, seed=int(pnp.seq_pnp_problem_seed(params["seed"], k)))
+        d["host"] = dict(w=w, k=k, points3=pts[op[sel]], pixels=xy[sel], params=one)
+        exp["host"] = PS.problem(pnp, K, pts[op[sel]], xy[sel], **one)
+    if index % 4 == 2 and cap <= 257:  # the solve from the seeded poses, as draw_landmarks restates it
+        d["solve"] = dict(delta=delta, max_iters=ba_iters)
+        solved, sums, pts3 = np.array(exp["pnp"]["poses6"], np.float64), [], []
+        for v in range(n):
+            if block["status"][v] != LR.OK:
+                sums.append(dict(termination=BA_SKIPPED, iterations=0, successful_steps=0, initial_cost=0.0,
+                                 final_cost=0.0))
+                continue
+            p3, _, op, oq, xy = LS.window_of(block, v)
+            solved[v], x, sm = LS.seq_ba(seq_lib("ba"), K, exp["pnp"]["poses6"][v], p3, op, oq, xy, delta, ba_iters)
+            sums.append(sm)
+            pts3.append(x)
+        exp["solve"] = dict(solved=solved, summaries=sums, points=np.concatenate(pts3) if pts3 else np.zeros((0, 3)))
+    d["expected"] = exp
+    return d
+
+
+def _fetch_bytes(pkg, address, shape, dtype):
+    """a whole device array, its tails included"""
+    out = np.zeros(shape, dtype)
+    hip = pkg.orbx.load()
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    if out.nbytes and hip.hipMemcpy(out.ctypes.data, address, out.nbytes, 2) != 0:
+        raise RuntimeError("hipMemcpy of a result block failed")
+    return out
+
+
+def run_pnp(c, d):
+    pkg = importlib.import_module("visual-odometry-gpu_amd")
+    PNP = pkg.orbx_pnp
+    c.landmarks_build(d["K"], d["tracks"], d["seen"], d["poses"])
+    got = dict(block=c.landmarks_fetch())
+    PNP.window_poses_pnp(c, **d["params"])
+    f = PNP.window_poses_pnp_fetch(c)  # waits for the call
+    v = PNP.window_poses_pnp_view(c)
+    # every mask row to the slot capacity: the zeros behind a window's points too
+    mask = _fetch_bytes(pkg, v.mask, (v.n_windows, v.window_len - 2, v.slot_capacity), np.uint8)
+    got["pnp"] = dict(records=f["records"], poses6=f["poses6"], mask=mask)
+    got["mask_lists"] = f["masks"]
+    if d["host"] is not None:
+        h = d["host"]
+        got["host"] = PNP.pnp_ransac(c, h["points3"], h["pixels"], d["K"], **h["params"])
+        again = PNP.window_poses_pnp_fetch(c, masks=False)  # the batched block is still there behind the host entry
+        got["pnp_again"] = dict(records=again["records"], poses6=again["poses6"])
+    if d["solve"] is not None:
+        PNP.bundle_adjust_landmarks_pnp(c, d["solve"]["delta"], d["solve"]["max_iters"])
+        s = c.bundle_adjust_landmarks_fetch()
+        got["solve"] = dict(solved=s[0], summaries=s[1], points=s[2])
+    return got
+
+
+def _diff_records(got, exp, name):
+    if got.dtype != PS.RECORD or got.shape != exp.shape:
+        return ["%s: %s %s != %s" % (name, got.dtype, got.shape, exp.shape)]
+    out = ["%s.%s" % (name, k) for k in PS.RECORD.names
+           if np.ascontiguousarray(got[k]).tobytes() != np.ascontiguousarray(exp[k]).tobytes()]
+    return out or (["%s (padding)" % name] if got.tobytes() != exp.tobytes() else [])
+
+
+def _diff_summaries(got, exp):
+    out = []
+    if len(got) != len(exp):
+        out.append("summaries: %d != %d" % (len(got), len(exp)))
+    for w, (g, e) in enumerate(zip(got, exp)):
+        if set(g) != set(e) or any(np.float64(g[k]).tobytes() != np.float64(e[k]).tobytes() for k in e):
+            out.append("summary %d: %r != %r" % (w, g, e))
+    return out
+
+
+def diff_pnp(got, exp):
+    if "pnp" in got and "mask_lists" not in got:  # an expected result compared with itself (the reproducibility test)
+        got = dict(got, mask_lists=None)
+    out = ["block.%s" % k for k in LS.KEYS + ("pose_offset",) if not SS.bits_equal(got["block"][k], exp["block"][k])]
+    out += _diff_records(got["pnp"]["records"], exp["pnp"]["records"], "records")
+    out += ["pnp.%s" % k for k in ("poses6", "mask") if not same_bits(got["pnp"][k], exp["pnp"][k])]
+    if got["mask_lists"] is not None:  # what the mask fetch hands out: one byte per point of the window
+        off = exp["block"]["point_offset"]
+        for w, rows in enumerate(got["mask_lists"]):
+            for k, m in enumerate(rows):
+                if not same_bits(m, exp["pnp"]["mask"][w, k, :off[w + 1] - off[w]]):
+                    out.append("mask fetch (%d, %d)" % (w, k + 2))
+    if ("host" in exp) != ("host" in got) or ("solve" in exp) != ("solve" in got):
+        return out + ["keys %s != %s" % (sorted(got), sorted(exp))]
+    if "host" in exp:
+        g, e = got["host"], exp["host"]
+        out += ["host.%s" % k for k in ("pose6", "mask") if not same_bits(g[k], e[k])]
+        out += ["host.%s" % k for k in ("inliers", "iters", "status") if g[k] != e[k]]
+        if np.float64(g["rms_px"]).tobytes() != np.float64(e["rms_px"]).tobytes():
+            out.append("host.rms_px")
+        if "pnp_again" in got:
+            out += _diff_records(got["pnp_again"]["records"], exp["pnp"]["records"], "records behind the host entry")
+            if not same_bits(got["pnp_again"]["poses6"], exp["pnp"]["poses6"]):
+                out.append("poses6 behind the host entry")
+    if "solve" in exp:
+        out += ["solve.%s" % k for k in ("solved", "points") if not SS.bits_equal(got["solve"][k], exp["solve"][k])]
+        out += _diff_summaries(got["solve"]["summaries"], exp["solve"]["summaries"])
+    return out
+
+
+# ---- landmark carry and the carried PnP (rank 18) ----------------------------------------------------------------
+def _carry_window(rng, kind, W, old_cap, cap):
+    """One old window of old_cap slots and its successor of cap slots: (old, new), each a dict of tracks and seen (old:
+    poses too; new: origin and the share of replaced pixels)."""
+    s = int(rng.integers(0, 2**31))
+    m = min(old_cap, cap)
+    if kind in ("origins", "ragged"):
+        # an old window whose seen runs from 0 to W (slots below 2 own no landmark) and a successor put together slot
+        # by slot
+        live = int(rng.integers(max(1, old_cap // 2), old_cap + 1))
+        stream = CR.make_stream(s, 2 * W - 1, live + cap)
+        old = CR.window(stream, 0, W, np.arange(live), rng.integers(0, W + 1, live))
+        origin, ids = np.full(cap, -1, np.int32), live + np.arange(cap)  # fresh points unless carried
+        for t in range(cap):
+            u = int(rng.integers(0, 12)) if kind == "origins" else int(rng.integers(0, 4))
+            if u < 5:  # an old slot, with or without a landmark
+                origin[t] = int(rng.integers(0, live))
+                ids[t] = origin[t]
+            elif u == 5:  # at or beyond the old capacity
+                origin[t] = (old_cap, old_cap + 5, 2**31 - 1)[int(rng.integers(0, 3))]
+            elif u == 6:  # negative, other than -1
+                origin[t] = (-7, -2, -2**31)[int(rng.integers(0, 3))]
+            elif u == 7 and t > 0:  # the origin of the slot before: two new slots name one old slot
+                origin[t], ids[t] = origin[t - 1], ids[t - 1]
+            elif u == 8:  # a padding slot of the old window
+                origin[t] = int(rng.integers(live, old_cap)) if live < old_cap else -1
+        seen = np.full(cap, W, np.int32)
+        if kind == "ragged":  # 0 .. W + 2, and pixels that are not finite
+            seen = rng.integers(0, W + 3, cap).astype(np.int32)
+        new = CR.window(stream, W - 1, W, ids, seen)
+        new["origin"] = origin
+        if kind == "ragged":
+            for t in rng.integers(0, cap, cap // 8 + 1):
+                new["tracks"][t, int(rng.integers(0, W)), int(rng.integers(0, 2))] = \
+                    np.float32([np.nan, np.inf, -np.inf][int(rng.integers(0, 3))])
+    else:
+        old_slots = m if kind != "junk" else min(m, 12)
+        fresh = min(10, cap - old_slots)
+        min_seen = W if kind in ("outliers", "junk") or rng.random() < 0.5 else 2
+        stream, old, new = CR.two_generations(s % 2**30, W, old_slots, fresh, min_seen=min_seen, cap=cap)
+    pad = old_cap - len(old["seen"])
+    old = dict(tracks=np.concatenate([old["tracks"], np.zeros((pad, W, 2), np.float32)]),
+               seen=np.concatenate([old["seen"], np.zeros(pad, np.int32)]), poses=old["true_poses"].copy(),
+               ids=old["ids"])
+    share = 0.0
+    if kind == "outliers":  # 10 to 50 % of the new window's pixels replaced, in four windows of ten 55 to 75 %
+        share = float(rng.uniform(0.1, 0.5)) if rng.random() < 0.6 else float(rng.uniform(0.55, 0.75))
+        bad = rng.random((cap, W)) < share
+        junk = np.stack([rng.uniform(0, LR.IMG_W, (cap, W)), rng.uniform(0, LR.IMG_H, (cap, W))], -1).astype(np.float32)
+        new["tracks"] = np.where(bad[..., None], junk, new["tracks"])
+    elif kind == "old_baseline":
+        old["poses"][1, 3:] = old["poses"][0, 3:] + np.array([0.01, 0.0, 0.02])
+    elif kind == "old_bad_pose":
+        old["poses"][int(rng.integers(0, 2)), :3] = np.array([0.0, 2e5, 0.0])
+    elif kind == "three":
+        new["origin"][3:] = -1
+    elif kind == "junk":  # one frame of random pixels: frame 0 or 1 loses the window, a later one keeps the pose before
+        k = int(rng.integers(0, W))
+        new["tracks"][:, k] = np.c_[rng.uniform(0, LR.IMG_W, cap), rng.uniform(0, LR.IMG_H, cap)]
+    new["share"] = share
+    return old, new
+
+
+def draw_carry(seed, index):
+    """Old windows through orbx_landmarks_build_device, their successors' origin through orbx_landmarks_carry_device,
+    the successors' tracks through orbx_window_poses_pnp_carried_device; the blocks of both fetched whole."""
+    rng = _rng("carry", seed, index)
+    cap = _pick(rng, index, 0, CARRY_SLOTS, 1, 600)
+    old_cap = _pick(rng, index, 5, CARRY_SLOTS, 1, 600)  # (salt 5: an odd shift, the two are boundary values in turn)
+    if index % 4 == 0:  # both on a boundary
+        old_cap = CARRY_SLOTS[(index // 4) % len(CARRY_SLOTS)]
+    W = PNP_WINDOW_LEN[(index // 2) % 4]
+    n = int(rng.integers(1, 7))
+    kinds = tuple(_weighted(rng, CARRY_KINDS, (3, 3, 2, 2, 1, 1, 1, 1)) for _ in range(n))
+    pairs = [_carry_window(rng, k, W, old_cap, cap) for k in kinds]
+    olds, news = [p[0] for p in pairs], [p[1] for p in pairs]
+    params = _pnp_params(rng, index)
+    K = CR.K
+    old_poses, old_tracks, old_seen = CR.stack_old(olds)
+    origin, tracks, seen = CR.stack_new(news)
+    block = LS.seq_build(seq_lib("lm"), K, old_poses, old_tracks, old_seen)
+    # the source: the block's points as built, or (every fourth draw of at most 257 old slots) as solved.  Neither
+    # holds a coordinate that is not finite -- the build drops such a landmark, the solve hands its input back when a
+    # step fails -- so rule A's finite test is left to tests/test_carry.py's case of the host entry, whose old points are the caller's
+    solve, points = None, None
+    if index % 4 == 3 and old_cap <= 257:
+        solve = dict(delta=BA_DELTA[int(rng.integers(0, 2))], max_iters=int(rng.integers(1, 21)))
+        pts3 = [LS.seq_ba(seq_lib("ba"), K, old_poses[w], *(LS.window_of(block, w)[i] for i in (0, 2, 3, 4)),
+                          solve["delta"], solve["max_iters"])[1]
+                for w in range(n) if block["status"][w] == LR.OK]
+        points = np.concatenate(pts3) if pts3 else np.zeros((0, 3))
+    carry = CR.join(block, origin, old_cap, points)
+    loc = CR.localise(seq_lib("pnp"), carry, tracks, seen, **params)
+    return dict(family="carry", seed=seed, index=index, cap=cap, old_cap=old_cap, W=W, kinds=kinds, olds=olds,
+                news=news, params=params, K=K, old=(old_poses, old_tracks, old_seen), origin=origin, tracks=tracks,
+                seen=seen, solve=solve, points=points, expected=dict(block=block, carry=carry, loc=loc))
+
+
+def run_carry(c, d):
+    pkg = importlib.import_module("visual-odometry-gpu_amd")
+    CA = pkg.orbx_carry
+    old_poses, old_tracks, old_seen = d["old"]
+    c.landmarks_build(d["K"], old_tracks, old_seen, old_poses)
+    got = dict(block=c.landmarks_fetch())
+    if d["solve"] is not None:
+        c.bundle_adjust_landmarks(d["solve"]["delta"], d["solve"]["max_iters"])
+    CA.landmarks_carry(c, d["origin"], source=CR.CARRY_BUILT if d["solve"] is None else CR.CARRY_SOLVED)
+    got["carry"] = CA.landmarks_carry_fetch(c)
+    CA.window_poses_pnp_carried(c, d["K"], d["tracks"], d["seen"], **d["params"])
+    got["loc"] = CA.window_poses_pnp_carried_fetch(c)
+    return got
+
+
+def diff_carry(got, exp):
+    out = ["block.%s" % k for k in LS.KEYS + ("pose_offset",) if not SS.bits_equal(got["block"][k], exp["block"][k])]
+    out += ["carry.%s" % k for k in ("xyz", "point", "count") if not same_bits(got["carry"][k], exp["carry"][k])]
+    out += _diff_records(got["loc"]["records"], exp["loc"]["records"], "records")
+    out += ["loc.%s" % k for k in ("poses6", "mask", "window_status") if not same_bits(got["loc"][k], exp["loc"][k])]
+    return out
+
+
+# ---- point descriptors and the re-association (rank 19) ----------------------------------------------------------
+PD_R = 20  # rule C's reach for every patch_size up to 41
+
+
+def _reloc_specials(w, h, r=PD_R):
+    """test_reloc.case_points' fixed points for a w x h frame: the .5 ties of both parities, R and R - 1 from every
+    border, what is not usable"""
+    return np.float32([
+        (20.5, 20.0), (21.5, 20.0), (20.0, 20.5), (20.0, 21.5), (22.5, 23.5), (r, r), (r - 1, r), (r, r - 1),
+        (w - 1 - r, h - 1 - r), (w - r, h - 1 - r), (w - 1 - r, h - r), (w - 1 - r, r), (r, h - 1 - r),
+        (w - 1 - r + 0.49, r + 1.0), (w - 1 - r + 0.5, r + 1.0), (w - 1 - r + 0.51, r + 1.0), (r - 0.5, r + 2.0),
+        (r - 0.51, r + 2.0), (r + 2.0, h - 1 - r + 0.5), (r + 2.0, h - 1 - r + 0.51), (np.nan, r), (r, np.nan),
+        (np.inf, r), (r, -np.inf), (-1.0, r), (r, -0.25), (w - 1.0, h - 1.0), (w - 0.99, r), (r, h - 0.5), (1e9, r),
+        (0.0, 0.0), (-0.0, r + 3.0)])
+
+
+def _reloc_points(rng, n, cap, w, h, near=None):
+    """(n, cap, 2) float32: the specials, uniform floats inside rule C's interior and over the whole frame (and a
+    little beyond it), and -- with `near`, the points of the other bank -- copies of those, some moved by less than
+    half a pixel"""
+    sp = _reloc_specials(w, h)
+    pts = np.zeros((n, cap, 2), np.float32)
+    for f in range(n):
+        u = rng.random(cap)
+        inside = np.c_[rng.uniform(PD_R - 0.5, w - 1 - PD_R + 0.5, cap), rng.uniform(PD_R - 0.5, h - 1 - PD_R + 0.5, cap)]
+        frame = np.c_[rng.uniform(-2.0, w + 1.0, cap), rng.uniform(-2.0, h + 1.0, cap)]
+        pts[f] = np.where((u < 0.75)[:, None], inside, frame)
+        special = rng.random(cap) < (0.5 if cap <= 5 else 0.2)
+        pts[f, special] = sp[rng.integers(0, len(sp), int(special.sum()))]
+        if near is not None:
+            take = rng.random(cap) < 0.6
+            src = near[f, rng.integers(0, near.shape[1], cap)]
+            moved = src + np.where(rng.random((cap, 1)) < 0.5, rng.uniform(-0.45, 0.45, (cap, 2)), 0.0).astype(np.float32)
+            pts[f, take] = moved[take]
+    return pts
+
+
+def _reloc_bank(rng, index, bank, frames, params, near=None):
+    """one orbx_describe_points_device call: points, layout and gates, and rules A-E on the oracle per frame"""
+    n, h, w = frames.shape
+    cap = RELOC_SLOTS[(index + 3 * bank) % len(RELOC_SLOTS)]
+    pts = _reloc_points(rng, n, cap, w, h, near)
+    layout = ("pairs", "lk")[int(rng.integers(0, 2))]
+    lk = (int(rng.integers(2, 7)), 0)
+    lk = (lk[0], int(rng.integers(0, lk[0])))  # (window_len, frame) of an LK-shaped tracks block
+    seen_min = int(rng.integers(0, 5))
+    seen = rng.integers(0, 6, (n, cap)).astype(np.int32) if seen_min else None
+    counts = None
+    if rng.random() < 0.6:  # ragged: 0, the capacity, anything between
+        counts = np.array([(0, cap, int(rng.integers(0, cap + 1)), int(rng.integers(0, cap + 1)))[int(rng.integers(0, 4))]
+                           for _ in range(n)], np.int32)
+    ref = [RR.describe_points(frames[f], pts[f], params, seen=None if seen is None else seen[f], seen_min=seen_min,
+                              count=None if counts is None else int(counts[f])) for f in range(n)]
+    exp = dict(desc=np.stack([r["desc"] for r in ref]), angle=np.stack([r["angle"] for r in ref]),
+               state=np.stack([r["state"] for r in ref]), n_ok=np.array([r["n_ok"] for r in ref], np.int32))
+    return dict(points=pts, layout=layout, lk=lk, seen=seen, seen_min=seen_min, counts=counts,
+                pix=np.stack([r["pix"] for r in ref])), exp
+
+
+def _ra_sets(rng, kind, n, qcap, tcap):
+    """n windows of one kind: (qdesc (n, qcap, 32), qstate, tdesc (n, tcap, 32), tstate)"""
+    qdesc = rng.integers(0, 256, (n, qcap, 32), dtype=np.uint8)
+    tdesc = rng.integers(0, 256, (n, tcap, 32), dtype=np.uint8)
+    qstate = np.full((n, qcap), RR.PD_OK, np.int32)
+    tstate = np.full((n, tcap), RR.PD_OK, np.int32)
+    for w in range(n):
+        if kind == "pool":
+            qdesc[w], tdesc[w] = RR.pool_window(rng, qcap, tcap)  # test_matcher.tie_heavy's pool, with matches
+        else:  # copies of train slots with 0 .. 60 bits flipped among random descriptors
+            for q in np.flatnonzero(rng.random(qcap) < 0.7):
+                qdesc[w, q] = RR.flip(tdesc[w, int(rng.integers(0, tcap))], rng, int(rng.integers(0, 61)))
+        if kind == "mixed":
+            qstate[w] = rng.choice([RR.PD_NONE, RR.PD_BORDER, RR.PD_OK], qcap, p=[0.15, 0.15, 0.7])
+            tstate[w] = rng.choice([RR.PD_NONE, RR.PD_BORDER, RR.PD_OK], tcap, p=[0.15, 0.15, 0.7])
+        elif kind == "one":
+            tstate[w] = rng.choice([RR.PD_NONE, RR.PD_BORDER], tcap)
+            tstate[w, int(rng.integers(0, tcap))] = RR.PD_OK
+        elif kind == "none":
+            tstate[w] = rng.choice([RR.PD_NONE, RR.PD_BORDER], tcap)
+    return qdesc, qstate, tdesc, tstate
+
+
+def draw_reloc(seed, index):
+    """Two orbx_describe_points_device calls, one per bank, on one batch of frames, and one re-association: of uploaded
+    descriptor sets (orbx_reassociate_device), of the two banks' views (the chain on the device) or of one window of
+    host arrays (orbx_reassociate), in turn."""
+    rng = _rng("reloc", seed, index)
+    context = (index // 4) % len(RELOC_CONTEXTS)
+    params = O.gpu_params(**RELOC_CONTEXTS[context])
+    w, h = RELOC_WIDTHS[index % len(RELOC_WIDTHS)], RELOC_HEIGHTS[(index // 2) % len(RELOC_HEIGHTS)]
+    nf = int(rng.integers(1, 5))
+    frames = np.stack([fuzz_parity.image(rng, h, w) for _ in range(nf)])
+    # frames as regions of a parent buffer: the row stride equal to the width or above it, garbage in between
+    rs = w + (0, int(rng.integers(1, 24)))[int(rng.integers(0, 2))]
+    base, fs = int(rng.integers(0, 8)), rs * h + int(rng.integers(0, 50))
+    garbage = rng.integers(0, 256, base + nf * fs, dtype=np.uint8)
+    b0, e0 = _reloc_bank(rng, index, 0, frames, params)
+    b1, e1 = _reloc_bank(rng, index, 1, frames, params, near=b0["points"])
+    kind = _weighted(rng, RA_KINDS, (3, 3, 2, 1, 1))
+    source = RA_INPUTS[index % 3]
+    ra = dict(kind=kind, input=source, ratio=RA_RATIOS[int(rng.integers(0, 3))],
+              max_distance=RA_MAX_DISTANCE[int(rng.integers(0, 3))], unique=int(rng.random() < 0.7))
+    big = rng.random() < 0.5  # half of the query sets beyond one workgroup of k_ra_knn2
+    qcap = (257, 512, 513)[int(rng.integers(0, 3))] if big else RA_CAPS[int(rng.integers(0, len(RA_CAPS)))]
+    tcap = RA_CAPS[int(rng.integers(0, len(RA_CAPS)))]
+    nw = 1 if source == "host" else int(rng.integers(1, 5))
+    sets = _ra_sets(rng, kind, nw, qcap, tcap)
+    if source == "banks":  # queries: bank 1, train: bank 0
+        ra["kind"] = "described"
+        sets = (e1["desc"], e1["state"], e0["desc"], e0["state"])
+    ra.update(zip(("qdesc", "qstate", "tdesc", "tstate"), sets))
+    exp = dict(banks=[e0, e1], ra=RR.reassociate(*sets, ra["ratio"], ra["max_distance"], ra["unique"]))
+    return dict(family="reloc", seed=seed, index=index, context=context, frames=frames, row_stride=rs,
+                layout=(base, rs, fs), garbage=garbage, banks=[b0, b1], ra=ra, expected=exp)
+
+
+_RELOC_CTX = {}
+
+
+def _close_reloc_context():
+    for c in _RELOC_CTX.values():
+        c.close()
+    _RELOC_CTX.clear()
+
+
+def reloc_context(pkg, i):
+    """RELOC_CONTEXTS[i] opened on CONTEXT's sizes; one is open at a time, the one before is closed first, and
+    context(pkg, "reloc") closes the last one when its block ends"""
+    if i not in _RELOC_CTX:
+        _close_reloc_context()
+        _RELOC_CTX[i] = pkg.Context(pkg.default_params("gpu", **dict(CONTEXT, **RELOC_CONTEXTS[i])))
+    return _RELOC_CTX[i]
+
+
+@contextlib.contextmanager
+def context(pkg, family):
+    """What a sweep or a campaign of `family` runs inside: the one small context of CONTEXT, handed to run() -- or,
+    for the reloc family, None: run_reloc opens RELOC_CONTEXTS one after another, and the last one is closed here."""
+    if family == "reloc":
+        try:
+            yield None
+        finally:
+            _close_reloc_context()
+    else:
+        with pkg.Context(pkg.default_params("gpu", **CONTEXT)) as c:
+            yield c
+
+
+def run_reloc(c, d):
+    """(on the family's own context of the draw; `c` is None under context(pkg, "reloc"))"""
+    import torch
+
+    pkg = importlib.import_module("visual-odometry-gpu_amd")
+    RL = pkg.orbx_reloc
+    c = reloc_context(pkg, d["context"])
+    frames = d["frames"]
+    nf, h, w = frames.shape
+    base, rs, fs = d["layout"]
+    buf = d["garbage"].copy()
+    np.lib.stride_tricks.as_strided(buf[base:], shape=(nf, h, w), strides=(fs, rs, 1))[...] = frames
+    t = torch.as_strided(torch.from_numpy(buf).cuda(), (nf, h, w), (fs, rs, 1), base)
+    got = dict(banks=[])
+    for bank, b in enumerate(d["banks"]):
+        pts = b["points"]
+        if b["layout"] == "lk":  # frame k of a tracks block (n, slots, window_len, 2)
+            L, k = b["lk"]
+            block = np.full((nf, pts.shape[1], L, 2), -7.0, np.float32)
+            block[:, :, k] = pts
+            xy = torch.from_numpy(block).cuda()[:, :, k]
+        else:
+            xy = torch.from_numpy(pts).cuda()
+        seen = None if b["seen"] is None else torch.from_numpy(b["seen"]).cuda()
+        counts = None if b["counts"] is None else torch.from_numpy(b["counts"]).cuda()
+        torch.cuda.synchronize()
+        RL.describe_points(c, t, xy, bank=bank, seen=seen, seen_min=b["seen_min"], counts=counts)
+        if d["ra"]["input"] != "banks":  # (the chain on the device fetches nothing in between)
+            got["banks"].append(RL.point_descriptors_fetch(c, bank))
+    r = d["ra"]
+    if r["input"] == "host":
+        one = RL.reassociate_host(c, r["qdesc"][0], r["qstate"][0], r["tdesc"][0], r["tstate"][0], r["ratio"],
+                                  r["max_distance"], r["unique"])
+        got["ra"] = dict(origin=one["origin"][None], dist=one["dist"][None], count=np.array([one["count"]], np.int32))
+    else:
+        if r["input"] == "banks":
+            RL.reassociate(c, RL.point_descriptors_view(c, 1), train_desc=RL.point_descriptors_view(c, 0),
+                           ratio=r["ratio"], max_distance=r["max_distance"], unique=r["unique"])
+        else:
+            RL.reassociate(c, r["qdesc"], r["qstate"], r["tdesc"], r["tstate"], ratio=r["ratio"],
+                           max_distance=r["max_distance"], unique=r["unique"])
+        got["ra"] = RL.reassociate_fetch(c)
+    if r["input"] == "banks":
+        got["banks"] = [RL.point_descriptors_fetch(c, bank) for bank in (0, 1)]
+    return got
+
+
+def diff_reloc(got, exp):
+    out = []
+    for bank, (g, e) in enumerate(zip(got["banks"], exp["banks"])):
+        out += ["bank %d %s" % (bank, k) for k in ("state", "n_ok", "desc", "angle") if not same_bits(g[k], e[k])]
+    out += ["re-association %s" % k for k in ("origin", "dist", "count") if not same_bits(got["ra"][k], exp["ra"][k])]
+    return out
+
+
 # ---- the common face ---------------------------------------------------------------------------------------------
-_DRAW = dict(matcher=draw_matcher, pose=draw_pose, scale=draw_scale, ba=draw_ba, corners=draw_corners, tracks=draw_tracks, landmarks=draw_landmarks)
-_RUN = dict(matcher=run_matcher, pose=run_pose, scale=run_scale, ba=run_ba, corners=run_corners, tracks=run_tracks, landmarks=run_landmarks)
-_DIFF = dict(matcher=diff_matcher, pose=diff_pose, scale=diff_scale, ba=diff_ba, corners=diff_corners, tracks=diff_tracks, landmarks=diff_landmarks)
+_DRAW = dict(matcher=draw_matcher, pose=draw_pose, scale=draw_scale, ba=draw_ba, corners=draw_corners, tracks=draw_tracks, landmarks=draw_landmarks,
+             pnp=draw_pnp, carry=draw_carry, reloc=draw_reloc)
+_RUN = dict(matcher=run_matcher, pose=run_pose, scale=run_scale, ba=run_ba, corners=run_corners, tracks=run_tracks, landmarks=run_landmarks,
+            pnp=run_pnp, carry=run_carry, reloc=run_reloc)
+_DIFF = dict(matcher=diff_matcher, pose=diff_pose, scale=diff_scale, ba=diff_ba, corners=diff_corners, tracks=diff_tracks, landmarks=diff_landmarks,
+             pnp=diff_pnp, carry=diff_carry, reloc=diff_reloc)
 
 
 def draw(family, seed, index):
@@ -717,6 +1263,12 @@ def elements(family, d):
         return "pairs", len(d["pairs"])
     if family == "landmarks":
         return "slots", d["seen"].size
+    if family == "pnp":
+        return "problems", d["expected"]["pnp"]["records"].size
+    if family == "carry":
+        return "problems", d["expected"]["loc"]["records"].size
+    if family == "reloc":
+        return "slots", sum(p["points"].size // 2 for p in d["banks"]) + d["ra"]["qstate"].size
     return "windows", len(d["windows"])
 
 
@@ -744,4 +1296,21 @@ def describe(family, d):
     if family == "landmarks":
         return "%d slots, W %d, build %s gate %g, min_seen %d, windows %s, delta %g, max_iters %d" % (
             d["slots"], d["W"], d["build"], d["gate"], d["min_seen"], d["kinds"], d["delta"], d["max_iters"])
+    if family == "pnp":
+        return "%d slots, W %d, windows %s, %r, host problem %s, seeded solve %s" % (
+            d["cap"], d["W"], d["kinds"], d["params"], None if d["host"] is None else (d["host"]["w"], d["host"]["k"]),
+            d["solve"])
+    if family == "carry":
+        return "%d slots from %d old ones, W %d, windows %s, source %s, %r" % (
+            d["cap"], d["old_cap"], d["W"], d["kinds"], "built" if d["solve"] is None else "solved %r" % d["solve"],
+            d["params"])
+    if family == "reloc":
+        a, r = d["banks"], d["ra"]
+        return ("context %d %r; %d frames %dx%d row stride %d; banks %s; re-association %s of %s: %d windows, %d "
+                "queries, %d train slots, ratio %g, max_distance %d, unique %d" % (
+                    d["context"], RELOC_CONTEXTS[d["context"]], d["frames"].shape[0], d["frames"].shape[2],
+                    d["frames"].shape[1], d["row_stride"],
+                    [(p["points"].shape[1], p["layout"], p["seen_min"], "counts" if p["counts"] is not None else "no counts")
+                     for p in a], r["kind"], r["input"], len(r["qstate"]), r["qstate"].shape[1], r["tstate"].shape[1],
+                    r["ratio"], r["max_distance"], r["unique"]))
     return "%d windows, delta %g, max_iters %d: %s" % (len(d["windows"]), d["delta"], d["max_iters"], d["names"])

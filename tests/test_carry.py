@@ -331,6 +331,32 @@ def test_callers_streams(pkg, ctx, seq, mixed):
     torch.cuda.synchronize()
 
 
+def test_host_entry_drops_landmarks_that_are_not_finite(pkg, ctx, seq, mixed):
+    """Rule A's finite test.  Neither source of the batched carry can hold such a coordinate (the build drops the
+    landmark, the solve hands its input back when a step fails), so it is reached through the host entry, whose old
+    points are the caller's."""
+    olds, news = [m[:1] for m in mixed]
+    build_old(ctx, olds)
+    block = ctx.landmarks_fetch()
+    pts, slots, _, _, _ = LS.window_of(block, 0)
+    new = news[0]
+    clean = R.join(block, new["origin"][None], R.MIX_CAP)
+    bad = pts.copy()
+    bad[3, 0], bad[10, 2], bad[20, 1], bad[64] = np.nan, np.inf, -np.inf, (np.nan, np.inf, 0.0)
+    carry = R.join(block, new["origin"][None], R.MIX_CAP, points=bad)
+    dropped = np.flatnonzero((clean["point"][0] >= 0) & (carry["point"][0] < 0))
+    assert sorted(new["origin"][dropped].tolist()) == sorted(slots[[3, 10, 20, 64]].tolist())
+    assert not carry["xyz"][0, dropped].any() and np.isfinite(carry["xyz"]).all() and carry["count"][0] == 61
+    ref = R.localise(seq, carry, new["tracks"][None], new["seen"][None], **PARAMS)
+    assert (ref["records"]["status"] == S.OK).all() and (ref["records"]["n_corr"] == 61).all()
+    one = pkg.orbx_carry.localise_carried_window(ctx, bad, slots, new["origin"], new["tracks"], new["seen"], K, **PARAMS)
+    assert one["carried_point"].tobytes() == carry["point"][0].tobytes()
+    assert one["records"].tobytes() == ref["records"][0].tobytes()
+    assert one["poses6"].tobytes() == ref["poses6"][0].tobytes() and one["window_status"] == R.CARRY_OK
+    got = pkg.orbx_carry.landmarks_carry_fetch(ctx)  # the entry's own batch of one
+    assert got["xyz"].tobytes() == carry["xyz"].tobytes() and got["count"].tobytes() == carry["count"].tobytes()
+
+
 def test_host_entry(pkg, ctx, seq, mixed):
     olds, news = mixed
     build_old(ctx, olds)

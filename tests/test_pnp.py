@@ -161,6 +161,36 @@ def test_bit_parity_with_other_parameters(pkg, ctx, seq, change):
         assert (ref["records"]["status"][:2] == S.OK).all()
 
 
+BIG = 513  # more than two workgroups' worth of lanes: every loop over the correspondences runs three times
+
+
+@pytest.mark.parametrize("change", [dict(), dict(max_iters=64, prob=1.0)])
+def test_bit_parity_beyond_one_workgroup_of_correspondences(pkg, ctx, seq, change):
+    """257 and 513 live slots: the prologue's compaction carries its count across chunks, the scoring loop, the
+    refinement's lane sums, the inlier counts and the mask clear all take a second and a third pass.  With
+    max_iters = 64 under prob = 1 (no sample count ever suffices) the outlier window stops on the edge of the first
+    chunk of 64 samples."""
+    scenes = [pad(L.make_scene(740, W=W, slots=257, min_seen=W, pose_pert=0.002), BIG),
+              L.make_scene(741, W=W, slots=BIG, min_seen=W, outliers=0.3, pose_pert=0.002)]
+    params = dict(PARAMS, **change)
+    got, ref, block, _ = run_and_compare(pkg, ctx, seq, scenes, BIG, **params)
+    rec = ref["records"]
+    assert (rec["status"] == S.OK).all()
+    assert (rec["n_corr"][0] == 257).all() and (rec["inliers"][0] == 257).all()  # 256 < n_corr < cap
+    assert (rec["n_corr"][1] == BIG).all()
+    assert (rec["inliers"][1] > 256).all() and (rec["inliers"][1] < 0.85 * BIG).all()  # 30 % outliers
+    assert any(ref["mask"][1, k, 256:].any() and not ref["mask"][1, k, 256:].all() for k in range(W - 2))
+    if change:
+        assert (rec["iters"][1] == 64).all() and (rec["iters"][0] < 64).all()
+    else:
+        assert (rec["iters"] < 64).all()
+    for w in range(2):
+        for k in range(2, W):
+            er, et = PR.pose_error(got["poses6"][w, k], L.rodrigues(scenes[w]["true_poses"][k, :3]),
+                                   scenes[w]["true_poses"][k, 3:])
+            assert er < 1e-4 and et < 1e-2, (w, k, er, et)
+
+
 def test_bit_parity_window_len_3(pkg, ctx, seq):
     """one problem per window"""
     scenes = [L.make_scene(720 + w, W=3, slots=65, min_seen=0, pose_pert=0.002) for w in range(4)]

@@ -1,9 +1,12 @@
 """ORB descriptors at caller-held points and the re-association by descriptor on the device (DESIGN.md §9 rank 19;
 include/orbx_reloc.h).  state, n_ok, the descriptor bytes and the angle BITS are compared with tests/reassoc_ref.py's
 restatement of rules A-E on the CPU oracle; origin, dist and count with its restatement of rules F-J; everything for
-equality.  The shapes are the smallest at which the kernels can still go wrong: 96 slots (no multiple of the classify
-workgroup's 256, 24 describe workgroups of which most leave early), a frame smaller than the context's maximum, one
-with a row stride above its width, 300 train slots (two LDS tiles, the second one partial)."""
+equality.  The first cases are small: 96 slots (no multiple of the classify workgroup's 256, 24 describe workgroups of
+which most leave early), a frame smaller than the context's maximum, one with a row stride above its width, 300 train
+slots (two LDS tiles, the second one partial).  They are below the sizes at which k_pd_classify carries its base from
+one chunk of 256 slots into the next, k_ra_knn2 has a second workgroup per window and k_ra_unique a second chunk, and
+their widths are multiples of 4; the cases of 513 slots on 67 x 50 and 130 x 47 frames and of 513 x 256 and 257 x 513
+descriptor sets are there for those."""
 import numpy as np
 import pytest
 
@@ -145,6 +148,61 @@ def test_describe_parity(pkg, oracle, case, blur_levels, blur_kind):
         assert o.point_descriptors_view(ctx, 0).slot_capacity == CAP and o.point_descriptors_view(ctx, 0).n == 1
 
 
+BIG = 513  # beyond two chunks of the classify workgroup: its base is carried twice, the third chunk is partial
+
+
+def big_points(w, h, rng, r=20):
+    """BIG points for a w x h frame: case_points' fixed ones, then three random floats inside rule C's interior for
+    every one anywhere in the frame -- OK slots in every chunk of 256, with other states between them"""
+    pts = np.zeros((BIG, 2), np.float32)
+    pts[:CAP] = case_points(w, h, rng, r)
+    n = BIG - CAP
+    inside = np.c_[rng.uniform(r - 0.5, w - 1 - r + 0.5, n), rng.uniform(r - 0.5, h - 1 - r + 0.5, n)]
+    anywhere = np.c_[rng.uniform(-1, w, n), rng.uniform(-1, h, n)]
+    pts[CAP:] = np.where((np.arange(n) % 4 < 3)[:, None], inside, anywhere)
+    return pts
+
+
+@pytest.mark.parametrize("blur_levels,blur_kind", [(0, 0), (2, 0), (2, 1)])
+def test_describe_parity_on_narrow_frames_of_many_slots(pkg, oracle, blur_levels, blur_kind):
+    """67 x 50 and 130 x 47: widths that are no multiple of 4 (the last dword of a level-0 row is partial: the pixels
+    inside the width are what is checked here -- the zeros k_pd_level0 writes from the width to the pitch are read by no
+    OK slot, 20 pixels from every border, and no entry fetches the level-0 image), one of them a single tile of 64 and three more pixels, rows that start at
+    every byte offset; 513 slots each"""
+    import torch
+
+    rng = np.random.default_rng(23)
+    p = oracle.gpu_params(blur_levels=blur_levels, blur_kind=blur_kind)
+    params = pkg.default_params("gpu", max_width=W, max_height=H, max_batch=4, blur_levels=blur_levels,
+                                blur_kind=blur_kind)
+    with pkg.Context(params) as ctx:
+        for (w, h), pitch in (((67, 50), 67), ((130, 47), 141)):
+            imgs = rng.integers(0, 256, (2, h, w), dtype=np.uint8)
+            imgs[1] = np.clip(np.add.outer(np.arange(h) * 3, np.arange(w) * 2) % 256 + rng.integers(0, 9, (h, w)), 0, 255)
+            pts = np.stack([big_points(w, h, rng) for _ in range(2)])
+            counts = np.array([BIG, 400], np.int32)
+            ref = [R.describe_points(imgs[f], pts[f], p, count=int(counts[f])) for f in range(2)]
+            st = np.stack([r["state"] for r in ref])
+            assert ref[0]["n_ok"] > 256 and ref[1]["n_ok"] > 200
+            for lo in (0, 256):  # OK slots in every chunk, and others among them
+                assert (st[0, lo:lo + 256] == R.PD_OK).any() and (st[0, lo:lo + 256] != R.PD_OK).any()
+            assert st[0, 512] == R.PD_OK and (st[1, 400:] == R.PD_NONE).all()
+            assert all((st[f] == s).sum() >= 8 for f in range(2) for s in (R.PD_NONE, R.PD_BORDER, R.PD_OK))
+            parent = np.full((2, h, pitch), 255, np.uint8)  # (what lies between the width and the row stride is not the image)
+            parent[:, :, :w] = imgs
+            frames = torch.from_numpy(parent).cuda()[:, :, :w]
+            torch.cuda.synchronize()
+            o = pkg.orbx_reloc
+            o.describe_points(ctx, frames, pts, counts=counts)
+            got = o.point_descriptors_fetch(ctx, 0)
+            for f in range(2):
+                r = ref[f]
+                assert got["state"][f].tolist() == r["state"].tolist(), (w, f)
+                assert got["n_ok"][f] == r["n_ok"], (w, f)
+                assert got["desc"][f].tobytes() == r["desc"].tobytes(), (w, f)
+                assert np.array_equal(bits(got["angle"][f]), bits(r["angle"])), (w, f)
+
+
 @pytest.mark.parametrize("blur_levels,interior", [(0, 37), (2, 82)])  # (counted on the CPU oracle)
 def test_agreement_with_the_orb_path(pkg, crop, blur_levels, interior):
     """the interior level-0 keypoints of detect_and_compute, given back as float points, yield the angle bits and the
@@ -194,6 +252,45 @@ def test_reassociation_parity(pkg, ctx, sets, unique, ratio, max_distance):
     none = o.reassociate_host(ctx, qdesc[0], qstate[0], tdesc[0][:0], tstate[0][:0], ratio, max_distance, unique)
     assert (none["origin"] == -1).all() and (none["dist"] == -1).all() and none["count"] == 0
     assert o.reassociate_host(ctx, qdesc[0][:0], qstate[0][:0], tdesc[0], tstate[0])["count"] == 0
+
+
+@pytest.mark.parametrize("qcap,tcap", [(513, 256), (257, 513)])
+def test_reassociation_parity_beyond_one_workgroup_of_queries(pkg, ctx, qcap, tcap):
+    """More than 256 query slots: k_ra_knn2 runs two or three workgroups per window, whose queries lower one train
+    slot's key from different workgroups, and k_ra_unique walks its chunks more than once; 256 and 513 train slots: a
+    train set of one full LDS tile, and of two and one slot."""
+    rng = np.random.default_rng(31)
+    sets = [R.pool_window(rng, qcap, tcap) for _ in range(2)]
+    qdesc, tdesc = np.stack([s[0] for s in sets]), np.stack([s[1] for s in sets])
+    qstate, tstate = np.full((2, qcap), R.PD_OK, np.int32), np.full((2, tcap), R.PD_OK, np.int32)
+    qstate[1, ::7], tstate[1, 5::11] = R.PD_BORDER, R.PD_NONE
+    # the first query of the second workgroup: a copy of the first query that is accepted at distance 0
+    before = R.reassociate(qdesc, qstate, tdesc, tstate, 0.8, 256, 0)
+    for w in range(2):
+        qdesc[w, 256] = qdesc[w, np.flatnonzero(before["dist"][w, :256] == 0)[0]]
+    plain = R.reassociate(qdesc, qstate, tdesc, tstate, 0.8, 256, 0)
+    uniq = R.reassociate(qdesc, qstate, tdesc, tstate, 0.8, 256, 1)
+    # the sets are what they are there for: accepted queries in every block of 256, train slots that queries of
+    # different blocks tie for at one distance, and one that the nearer query of another block takes
+    tie = nearer = False
+    for w in range(2):
+        o, d = plain["origin"][w], plain["dist"][w]
+        assert all((o[lo:lo + 256] >= 0).any() for lo in range(0, qcap, 256))
+        for t in np.unique(o[o >= 0]):
+            qs = np.flatnonzero(o == t)
+            nearest = qs[d[qs] == d[qs].min()]
+            tie = tie or len(set((nearest // 256).tolist())) > 1
+            nearer = nearer or (d[qs[0]] > d[qs].min() and nearest[0] // 256 != qs[0] // 256)
+    assert tie and (nearer or qcap == 257)  # (257: the second workgroup's one live query is the copy made above)
+    assert (uniq["count"] < plain["count"]).all() and (uniq["count"] > 20).all()
+    o = pkg.orbx_reloc
+    for unique, ref in ((0, plain), (1, uniq)):
+        o.reassociate(ctx, qdesc, qstate, tdesc, tstate, ratio=0.8, max_distance=256, unique=unique)
+        got = o.reassociate_fetch(ctx)
+        for k in ("origin", "dist", "count"):
+            assert got[k].dtype == np.int32 and got[k].tobytes() == ref[k].tobytes(), (unique, k)
+        one = o.reassociate_host(ctx, qdesc[1], qstate[1], tdesc[1], tstate[1], 0.8, 256, unique)
+        assert one["origin"].tobytes() == ref["origin"][1].tobytes() and one["count"] == ref["count"][1]
 
 
 def test_the_shifted_crops_end_to_end_on_the_device(pkg, ctx):

@@ -21,17 +21,23 @@ GPU has its N halved.
                                       comes from beyond that is not established.)
   tracks     640  4.4 s      2.6 s
   landmarks  96   4.0 s      1.7 s
+  pnp        64   3.2 s      1.1 s   (halved from 128, 4.6 s on the CPU, which took 14.7 s as the first GPU test of a
+                                      process -- it then pays what the corners test pays above, and compiles the three
+                                      restatements it needs; 128 was not timed in this module's order)
+  carry      128  4.1 s      1.3 s   (160 took 5.1 s on the CPU)
+  reloc      96   3.7 s      1.6 s   (on its own five contexts, side_random.RELOC_CONTEXTS, one open at a time and
+                                      the last one closed when the sweep ends: side_random.context)
 """
 import pytest
 
 import side_random as S
 
 SEED = 20261020
-N = dict(matcher=144, pose=640, scale=320, ba=48, corners=32, tracks=640, landmarks=96)
+N = dict(matcher=144, pose=640, scale=320, ba=48, corners=32, tracks=640, landmarks=96, pnp=64, carry=128, reloc=96)
 
 
 def sweep(pkg, family):
-    with pkg.Context(pkg.default_params("gpu", **S.CONTEXT)) as c:
+    with S.context(pkg, family) as c:  # (reloc: its own contexts, closed when the block ends)
         for index in range(N[family]):
             d = S.draw(family, SEED, index)
             S.compare(family, S.run(family, c, d), d)  # (the message carries (family, seed, index))
@@ -70,3 +76,18 @@ def test_gpu_tracks_chain_stitch_random(pkg):
 @pytest.mark.gpu
 def test_gpu_landmarks_solve_write_back_random(pkg):
     sweep(pkg, "landmarks")
+
+
+@pytest.mark.gpu
+def test_gpu_window_pnp_random(pkg):
+    sweep(pkg, "pnp")
+
+
+@pytest.mark.gpu
+def test_gpu_carry_and_carried_pnp_random(pkg):
+    sweep(pkg, "carry")
+
+
+@pytest.mark.gpu
+def test_gpu_describe_points_and_reassociate_random(pkg):
+    sweep(pkg, "reloc")  # (on side_random.RELOC_CONTEXTS, one after another: side_random.context)

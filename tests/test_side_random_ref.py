@@ -16,7 +16,9 @@ import landmarks_ref as LR
 import landmarks_seq as LS
 import landmarks_views_seq as VS
 import oracle_lib as O
+import pnp_seq as PS
 import pose_ref as P
+import reassoc_ref as RR
 import side_random as S
 import stitch_ref as SR
 import tracks_pose_ref as TR
@@ -435,3 +437,327 @@ def test_landmarks_classes_and_builds_against_numpy():
                                   sorted(terms), gated, worst, SVD_REL_BOUND, compared, marginal, decisions))
     assert marginal <= MARGINAL_CAP * decisions, (marginal, decisions)
     assert worst <= SVD_REL_BOUND, worst
+
+
+def ransac_classes(records, max_iters, into):
+    """where the runs of a records array ended: inside the first chunk of 64 by the stopping rule, on the chunk's
+    edge, in a later chunk, or at max_iters"""
+    for r in records.ravel():
+        if r["status"] != PS.OK:
+            continue
+        it = int(r["iters"])
+        into.add("ended on the edge of the first chunk" if it == S.PNP_CHUNK else
+                 "ran to max_iters" if it == max_iters else
+                 "stopped in the first chunk" if it < S.PNP_CHUNK else "stopped in a later chunk")
+
+
+RANSAC_WANT = {"stopped in the first chunk", "ended on the edge of the first chunk", "stopped in a later chunk",
+               "ran to max_iters"}
+
+
+def assert_pnp_parameters(ds):
+    ps = [d["params"] for d in ds]
+    assert {p["max_iters"] for p in ps} == set(S.PNP_ITERS) == {0, 1, 63, 64, 65, 128, 300}
+    assert {p["prob"] for p in ps} == set(S.PNP_PROB) == {0.5, 0.99, 0.999}
+    assert {p["threshold_px"] for p in ps} == set(S.PNP_THRESHOLD) == {0.5, 1.0, 2.0}
+    assert {p["refine_iters"] for p in ps} == set(S.PNP_REFINE) == {0, 1, 10, 20}
+    assert {p["min_inliers"] for p in ps} == set(S.PNP_MIN_INLIERS) == {4, 30}
+    assert any(p["seed"] < 2**32 for p in ps) and any(p["seed"] >= 2**32 for p in ps)
+
+
+def size_classes(rec, cap, into):
+    ok = rec["status"] == PS.OK
+    for name, m in (("n_corr > 256", rec["n_corr"] > S.PNP_LANES), ("inliers > 256", ok & (rec["inliers"] > S.PNP_LANES)),
+                    ("256 < n_corr < cap", (rec["n_corr"] > S.PNP_LANES) & (rec["n_corr"] < cap)),
+                    ("n_corr == cap", rec["n_corr"] == cap)):
+        if m.any():
+            into.add(name)
+
+
+SIZE_WANT = {"n_corr > 256", "inliers > 256", "256 < n_corr < cap", "n_corr == cap"}
+
+
+def test_pnp_classes_and_restatement_against_the_true_poses():
+    import pnp_ref as PR
+
+    ds = draws("pnp")
+    assert {d["cap"] for d in ds} >= set(S.PNP_SLOTS) == {1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 513}
+    assert max(d["cap"] for d in ds) <= 600 and sum(d["cap"] not in S.PNP_SLOTS for d in ds) >= len(ds) // 4
+    assert {d["W"] for d in ds} == set(S.PNP_WINDOW_LEN) == {3, 4, 5, 8}
+    assert {len(d["kinds"]) for d in ds} == {1, 2, 3, 4, 5, 6}
+    assert {k for d in ds for k in d["kinds"]} == set(S.PNP_KINDS)
+    assert_pnp_parameters(ds)
+    assert sum(d["host"] is not None for d in ds) == len(ds) // 2
+    assert sum(d["solve"] is not None for d in ds) >= 2 and all(d["cap"] <= 257 for d in ds if d["solve"] is not None)
+    status, stops, sizes = set(), set(), set()
+    for d in ds:
+        rec = d["expected"]["pnp"]["records"]
+        status |= {int(v) for v in rec["status"].ravel()}
+        ransac_classes(rec, d["params"]["max_iters"], stops)
+        size_classes(rec, d["cap"], sizes)
+        # a record that is not OK is empty but for its counts, and its pose is the built one
+        bad = rec["status"] != PS.OK
+        assert not rec["inliers"][bad].any() and not rec["rms_px"][bad].any() and not d["expected"]["pnp"]["mask"][bad].any()
+        assert d["expected"]["pnp"]["poses6"][:, 2:][bad].tobytes() == d["poses"][:, 2:][bad].tobytes()
+        assert d["expected"]["pnp"]["poses6"][:, :2].tobytes() == d["poses"][:, :2].tobytes()
+    assert status == {PS.OK, PS.SKIPPED, PS.FEW_POINTS, PS.NO_MODEL}, status
+    assert stops >= RANSAC_WANT, RANSAC_WANT - stops
+    assert sizes >= SIZE_WANT, SIZE_WANT - sizes
+    host_status = {d["expected"]["host"]["status"] for d in ds if d["host"] is not None}
+    terms = {sm["termination"] for d in ds if d["solve"] is not None for sm in d["expected"]["solve"]["summaries"]}
+    # the restatement's poses against the scene's true ones, within the bounds tests/test_pnp.py asserts on the device
+    # (1e-4 rad, 1e-2 units; the poses were handed out 2e-3 off).  The windows are chosen by what they were drawn as,
+    # not by how they came out: clean or padded, or at most 30 % outliers (those have no pixel noise) under a max_iters
+    # of 63 or more (a sample of three is free of outliers with probability 0.34 or more: none in 63 has a chance below
+    # 1e-11, while a max_iters of 1 leaves the one sample's model, OK with a dozen inliers), with at least 30 slots that
+    # own a landmark; every OK problem of such a window is compared.
+    worst_r = worst_t = 0.0
+    compared = ok_windows = chosen = 0
+    for d in ds:
+        rec = d["expected"]["pnp"]["records"]
+        for w, (kind, sc) in enumerate(zip(d["kinds"], d["scenes"])):
+            has_ok = bool((rec["status"][w] == PS.OK).any())
+            ok_windows += has_ok
+            few = kind == "outliers" and d["shares"][w] <= 0.3 and d["params"]["max_iters"] >= 63
+            if not (kind in ("clean", "padded") or few) or d["live"][w] < 30:
+                continue
+            chosen += has_ok
+            for k in range(2, d["W"]):
+                if rec["status"][w, k - 2] != PS.OK:
+                    continue
+                er, et = PR.pose_error(d["expected"]["pnp"]["poses6"][w, k], LR.rodrigues(sc["true_poses"][k, :3]),
+                                       sc["true_poses"][k, 3:])
+                worst_r, worst_t, compared = max(worst_r, er), max(worst_t, et), compared + 1
+                assert er < 1e-4 and et < 1e-2, (d["seed"], d["index"], w, k, er, et)
+    assert 3 * chosen >= ok_windows and compared >= 30, (chosen, ok_windows, compared)
+    print("pnp: %d draws, %d windows, %d problems, status %s, host-entry status %s, seeded-solve terminations %s, "
+          "classes %s; PnP pose vs the true pose on %d problems of %d of %d windows with an OK problem: worst %.3g rad "
+          "(bound 1e-4), %.3g units (bound 1e-2)" % (
+              len(ds), sum(len(d["kinds"]) for d in ds), sum(d["expected"]["pnp"]["records"].size for d in ds),
+              sorted(status), sorted(host_status), sorted(terms), sorted(stops | sizes), compared, chosen, ok_windows,
+              worst_r, worst_t))
+
+
+def test_carry_classes_and_join_against_a_dictionary():
+    ds = draws("carry")
+    assert {d["cap"] for d in ds} >= set(S.CARRY_SLOTS) == {1, 5, 63, 64, 65, 255, 256, 257, 513}
+    assert {d["old_cap"] for d in ds} >= set(S.CARRY_SLOTS)
+    assert sum(d["cap"] in S.CARRY_SLOTS and d["old_cap"] in S.CARRY_SLOTS for d in ds) >= len(ds) // 10
+    assert max(max(d["cap"], d["old_cap"]) for d in ds) <= 600 and any(d["cap"] != d["old_cap"] for d in ds)
+    assert {d["W"] for d in ds} == set(S.PNP_WINDOW_LEN) == {3, 4, 5, 8}
+    assert {len(d["kinds"]) for d in ds} == {1, 2, 3, 4, 5, 6}
+    assert {k for d in ds for k in d["kinds"]} == set(S.CARRY_KINDS)
+    assert {d["solve"] is None for d in ds} == {False, True}
+    assert_pnp_parameters(ds)
+    origins, status, wstatus, stops, sizes, old_status = set(), set(), set(), set(), set(), set()
+    slots = carried = 0
+    for d in ds:
+        block, carry, loc = (d["expected"][k] for k in ("block", "carry", "loc"))
+        src = block["points3"] if d["points"] is None else d["points"]
+        old_status |= {int(v) for v in block["status"]}
+        # rule A by a dictionary look-up of each window's slot_of_point
+        for w in range(len(d["kinds"])):
+            p0, p1 = int(block["point_offset"][w]), int(block["point_offset"][w + 1])
+            owner = {int(s): j for j, s in enumerate(block["slot_of_point"][p0:p1])}
+            assert block["status"][w] == LR.OK or not owner
+            named = {}
+            for s, o in enumerate(d["origin"][w].tolist()):
+                j = owner.get(o, -1) if 0 <= o < d["old_cap"] else -1
+                what = (d["seed"], d["index"], w, s)
+                assert carry["point"][w, s] == j, what
+                assert carry["xyz"][w, s].tobytes() == (src[p0 + j] if j >= 0 else np.zeros(3)).tobytes(), what
+                origins.add("-1" if o == -1 else "negative" if o < 0 else "beyond the old capacity" if o >= d["old_cap"]
+                            else "an old slot with a landmark" if j >= 0 else "an old slot without a landmark")
+                if j >= 0 and o in named:
+                    origins.add("two new slots naming one old slot")
+                named[o] = s
+            assert carry["count"][w] == (carry["point"][w] >= 0).sum()
+            slots, carried = slots + d["cap"], carried + int(carry["count"][w])
+        seen, px = d["seen"], d["tracks"]
+        live = np.arange(d["W"])[None, None, :] < seen[..., None]
+        for name, m in (("seen of 0", seen == 0), ("seen above window_len", seen > d["W"]),
+                        ("a live pixel that is not finite", (~np.isfinite(px).all(-1) & live).any(-1))):
+            if (m & (carry["point"] >= 0)).any():
+                origins.add(name)
+        rec = loc["records"]
+        status |= {int(v) for v in rec["status"].ravel()}
+        wstatus |= {int(v) for v in loc["window_status"]}
+        ransac_classes(rec, d["params"]["max_iters"], stops)
+        size_classes(rec, d["cap"], sizes)
+        bad = rec["status"] != PS.OK
+        assert not rec["pose6"][bad].any() and not rec["inliers"][bad].any() and not loc["mask"][bad].any()
+        # a window whose frames 0 and 1 are OK but a later one is not keeps the pose before: rule E
+        for w in np.flatnonzero(loc["window_status"] == S.CR.CARRY_OK):
+            for k in np.flatnonzero(bad[w]):
+                stops.add("a frame that keeps the pose before it")
+                assert loc["poses6"][w, k].tobytes() == loc["poses6"][w, k - 1].tobytes()
+    want = {"-1", "negative", "beyond the old capacity", "an old slot with a landmark", "an old slot without a landmark",
+            "two new slots naming one old slot", "seen of 0", "seen above window_len", "a live pixel that is not finite"}
+    assert origins >= want, want - origins
+    assert old_status == {LR.OK, LR.BASELINE, LR.EMPTY, LR.BAD_POSE}, old_status
+    assert status == {PS.OK, PS.SKIPPED, PS.FEW_POINTS, PS.NO_MODEL}, status
+    assert wstatus == {S.CR.CARRY_OK, S.CR.CARRY_LOST}
+    assert stops >= RANSAC_WANT | {"a frame that keeps the pose before it"}, stops
+    assert sizes >= SIZE_WANT, SIZE_WANT - sizes
+    print("carry: %d draws, %d windows, %d new slots of which %d carried, old status %s, origins and tracks %s, record "
+          "status %s, window status %s, classes %s; the join == a dictionary look-up on every slot (worst difference 0)"
+          % (len(ds), sum(len(d["kinds"]) for d in ds), slots, carried, sorted(old_status), sorted(origins),
+             sorted(status), sorted(wstatus), sorted(stops | sizes)))
+
+
+def plain_describe(img, points, level0_kind, seen, seen_min, count):
+    """Rules A-E without reassoc_ref.describe_points: the level-0 image from the oracle's whole-image blurs, the pixel
+    by Python's round (ties to even), the state by plain comparisons; then the oracle at every OK pixel of the frame."""
+    h, w = img.shape
+    level0 = {"copy": lambda a: a, "sep16": O.blur5_sep, "k273": O.blur5_273}[level0_kind](np.ascontiguousarray(img))
+    state, pix = [], []
+    for s, (x, y) in enumerate(points.tolist()):
+        gated = (count is not None and s >= count) or (seen is not None and seen[s] < seen_min)
+        if gated or not (math.isfinite(x) and math.isfinite(y) and 0 <= x <= w - 1 and 0 <= y <= h - 1):
+            state.append(RR.PD_NONE)
+            continue
+        X, Y = round(x), round(y)
+        inside = S.PD_R <= X <= w - 1 - S.PD_R and S.PD_R <= Y <= h - 1 - S.PD_R
+        state.append(RR.PD_OK if inside else RR.PD_BORDER)
+        if inside:
+            pix.append((X, Y))
+    return np.array(state, np.int32), np.array(pix, np.int32).reshape(-1, 2), level0
+
+
+def test_reloc_classes_and_restatements_against_the_oracle():
+    ds = draws("reloc")
+    assert {d["frames"].shape[2] for d in ds} == set(S.RELOC_WIDTHS) == \
+        {41, 42, 43, 63, 64, 65, 66, 67, 127, 128, 129, 157, 158, 159, 160}
+    assert {d["frames"].shape[1] for d in ds} == set(S.RELOC_HEIGHTS) == {41, 47, 48, 49, 63, 64, 65, 160}
+    assert {d["frames"].shape[0] for d in ds} == {1, 2, 3, 4}
+    assert any(d["frames"].shape[1:] != (160, 160) for d in ds)  # below the context's maximum
+    assert {d["row_stride"] > d["frames"].shape[2] for d in ds} == {False, True}
+    for bank in (0, 1):
+        bs = [d["banks"][bank] for d in ds]
+        assert {b["points"].shape[1] for b in bs} == set(S.RELOC_SLOTS) == {1, 3, 4, 5, 255, 256, 257, 513}
+        assert {b["layout"] for b in bs} == {"pairs", "lk"}
+        assert any(b["seen"] is None for b in bs) and {b["seen_min"] for b in bs} == {0, 1, 2, 3, 4}
+        assert any(b["counts"] is None for b in bs)
+        cs = [(int(c), b["points"].shape[1]) for b in bs if b["counts"] is not None for c in b["counts"]]
+        assert any(c == 0 for c, _ in cs) and any(c == cap for c, cap in cs) and any(0 < c < cap for c, cap in cs)
+    used = {d["context"] for d in ds}
+    assert {S.RELOC_LEVEL0[i] for i in used} == {"copy", "sep16", "k273"}
+    assert {S.RELOC_CONTEXTS[i]["patch_size"] for i in used} == {1, 9, 15, 31, 41}
+    # the re-association
+    ras = [d["ra"] for d in ds]
+    for k in ("qstate", "tstate"):
+        assert {r[k].shape[1] for r in ras if r["input"] != "banks"} == set(S.RA_CAPS) == {1, 2, 255, 256, 257, 512, 513}
+    both = sum(r["qstate"].shape[1] in S.RA_CAPS and r["tstate"].shape[1] in S.RA_CAPS for r in ras)
+    assert both >= len(ds) // 10
+    assert {r["qstate"].shape[0] for r in ras} == {1, 2, 3, 4}
+    assert {r["kind"] for r in ras} == set(S.RA_KINDS) | {"described"}
+    assert {r["input"] for r in ras} == set(S.RA_INPUTS)
+    assert {r["ratio"] for r in ras} == {0.7, 0.8, 1.0} and {r["max_distance"] for r in ras} == {0, 40, 256}
+    assert {r["unique"] for r in ras} == {0, 1}
+    special = set()
+    for d in ds:
+        for b in d["banks"]:
+            p = b["points"].reshape(-1, 2)
+            with np.errstate(invalid="ignore"):
+                frac = p - np.floor(p)
+                for name, m in (("NaN", np.isnan(p).any(1)), ("+inf", (p == np.inf).any(1)), ("-inf", (p == -np.inf).any(1)),
+                                ("negative", (p < 0).any(1)), ("-0.0", ((p == 0) & np.signbit(p)).any(1)),
+                                (".5 tie to an even pixel", ((frac == 0.5) & (np.floor(p) % 2 == 0)).any(1)),
+                                (".5 tie to an odd pixel", ((frac == 0.5) & (np.floor(p) % 2 == 1)).any(1))):
+                    if m.any():
+                        special.add(name)
+    want = {"NaN", "+inf", "-inf", "negative", "-0.0", ".5 tie to an even pixel", ".5 tie to an odd pixel"}
+    assert special >= want, want - special
+    # rules A-E: every state in every kind of level-0 image, R and R - 1 from every border, and the restatement's
+    # OK slots against the oracle on the whole frame
+    states, borders = set(), set()
+    frames = ok_slots = 0
+    big = False
+    for d in ds:
+        kind = S.RELOC_LEVEL0[d["context"]]
+        patch = S.RELOC_CONTEXTS[d["context"]]["patch_size"]
+        nf, h, w = d["frames"].shape
+        for b, e in zip(d["banks"], d["expected"]["banks"]):
+            for f in range(nf):
+                what = (d["seed"], d["index"], f)
+                state, pix, level0 = plain_describe(d["frames"][f], b["points"][f], kind,
+                                                    None if b["seen"] is None else b["seen"][f], b["seen_min"],
+                                                    None if b["counts"] is None else int(b["counts"][f]))
+                assert state.tolist() == e["state"][f].tolist(), what
+                ok = state == RR.PD_OK
+                assert e["n_ok"][f] == ok.sum() and np.array_equal(b["pix"][f][ok], pix), what
+                angle = O.orientations(level0, pix, patch)
+                desc = O.brief(level0, pix, angle)[0]
+                assert e["desc"][f][ok].tobytes() == desc.tobytes(), what
+                assert np.array_equal(S.bits(e["angle"][f][ok]), S.bits(angle)), what
+                assert not e["desc"][f][~ok].any() and not S.bits(e["angle"][f])[~ok].any(), what
+                states |= {(kind, int(s)) for s in np.unique(state)}
+                big = big or e["n_ok"][f] > 256
+                for name, m in (("x == R", pix[:, 0] == S.PD_R), ("x == w - 1 - R", pix[:, 0] == w - 1 - S.PD_R),
+                                ("y == R", pix[:, 1] == S.PD_R), ("y == h - 1 - R", pix[:, 1] == h - 1 - S.PD_R)):
+                    if m.any():
+                        borders.add(name)
+                live = state != RR.PD_NONE
+                px = b["pix"][f]
+                for name, m in (("x == R - 1", px[:, 0] == S.PD_R - 1), ("x == w - R", px[:, 0] == w - S.PD_R),
+                                ("y == R - 1", px[:, 1] == S.PD_R - 1), ("y == h - R", px[:, 1] == h - S.PD_R)):
+                    if (m & live).any():
+                        borders.add(name)
+                        assert (state[m & live] == RR.PD_BORDER).all(), what
+                frames, ok_slots = frames + 1, ok_slots + int(ok.sum())
+    assert states == {(k, s) for k in ("copy", "sep16", "k273") for s in (RR.PD_NONE, RR.PD_BORDER, RR.PD_OK)}, states
+    assert len(borders) == 8, borders
+    assert big  # n_ok > 256 in some frame: k_pd_classify carries its base into a second chunk with OK slots behind it
+    # rules F-J: rule G against the oracle's knn2 on the compacted OK sets, as tests/test_reassoc_ref.py does; the
+    # classes of the accepted queries
+    found = set()
+    windows = queries = accepted = 0
+    for d in ds:
+        r, e = d["ra"], d["expected"]["ra"]
+        for w in range(len(r["qstate"])):
+            qd, qs, td, ts = (r[k][w] for k in ("qdesc", "qstate", "tdesc", "tstate"))
+            okq, okt = np.flatnonzero(qs == RR.PD_OK), np.flatnonzero(ts == RR.PD_OK)
+            idx, dist = O.knn2(qd[okq], td[okt]) if len(okt) else (np.full((len(okq), 2), -1), np.full((len(okq), 2), -1))
+            two = idx[:, 1] >= 0
+            d1, d2 = dist[:, 0].astype(np.float32).astype(np.float64), dist[:, 1].astype(np.float32).astype(np.float64)
+            passed = two & (d1 < r["ratio"] * d2) & (dist[:, 0] <= r["max_distance"])
+            origin = np.full(len(qs), -1, np.int64)
+            if len(okt):
+                origin[okq[passed]] = okt[idx[passed, 0]]
+            dd = np.full(len(qs), -1, np.int64)
+            dd[okq[passed]] = dist[passed, 0]
+            what = (d["seed"], d["index"], w)
+            if r["unique"]:  # rule I, written out on the oracle's neighbours: the smallest d1, then the lowest slot
+                for t in np.unique(origin[origin >= 0]):
+                    qs_t = np.flatnonzero(origin == t)
+                    keep = qs_t[np.lexsort((qs_t, dd[qs_t]))[0]]
+                    tie = qs_t[dd[qs_t] == dd[keep]]
+                    if len(tie) > 1 and len(set((tie // 256).tolist())) > 1:
+                        found.add("a unique tie between queries of different 256-blocks")
+                    if len(qs_t) > 1 and dd[qs_t].min() < dd[qs_t].max():
+                        found.add("a train slot kept by the nearer query")
+                    lose = qs_t[qs_t != keep]
+                    origin[lose], dd[lose] = -1, -1
+            assert np.array_equal(e["origin"][w], origin) and np.array_equal(e["dist"][w], dd), what
+            assert e["count"][w] == (origin >= 0).sum(), what
+            if (origin[256:] >= 0).any():
+                found.add("accepted queries at slots >= 256")
+            if (origin >= 256).any():
+                found.add("accepted train slots >= 256")
+            if (two & (dist[:, 0] == dist[:, 1])).any():
+                found.add("d1 == d2")
+            if len(okt) == 1:
+                found.add("one OK train slot")
+            if len(okt) == 0:
+                found.add("no OK train slot")
+            if r["input"] == "banks" and (origin >= 0).any():
+                found.add("matches between the two banks")
+            windows, queries, accepted = windows + 1, queries + len(qs), accepted + int((origin >= 0).sum())
+    want = {"a unique tie between queries of different 256-blocks", "a train slot kept by the nearer query",
+            "accepted queries at slots >= 256", "accepted train slots >= 256", "d1 == d2", "one OK train slot",
+            "no OK train slot", "matches between the two banks"}
+    assert found >= want, want - found
+    print("reloc: %d draws; described %d frames, %d OK slots, every state on every level-0 kind, borders %s, points %s; "
+          "re-associated %d windows, %d queries, %d accepted, classes %s; rules A-E == the oracle on the whole frame "
+          "and rules F-J == the oracle's knn2 on the compacted sets, on all (worst difference 0)" % (
+              len(ds), frames, ok_slots, sorted(borders), sorted(special), windows, queries, accepted, sorted(found)))

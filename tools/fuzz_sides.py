@@ -43,7 +43,7 @@ def campaign(family, budget, seed):
     t0 = t_print = time.time()
     index = total = 0
     name = "elements"
-    with pkg.Context(pkg.default_params("gpu", **S.CONTEXT)) as c:
+    with S.context(pkg, family) as c:
         while time.time() - t0 < budget:
             if time.time() - t_print > 30:
                 t_print = time.time()
@@ -67,7 +67,7 @@ def main():
     families = [a.family] if a.family else list(S.FAMILIES)
     if a.only is not None:
         for f in families:
-            with pkg.Context(pkg.default_params("gpu", **S.CONTEXT)) as c:
+            with S.context(pkg, f) as c:
                 one(c, f, a.seed, a.only, verbose=True)
             print("draw (%s, %d, %d) ok" % (f, a.seed, a.only), flush=True)
         return
