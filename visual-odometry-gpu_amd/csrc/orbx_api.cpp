@@ -744,6 +744,7 @@ void orbx_destroy(orbx_ctx* c) {
   c->wp.release();
   c->tp.release();
   c->lm.release();
+  c->prior.release();  // (behind the landmarks' event, which its work ran under)
   c->lkw.release();
   c->gf.release();
   c->s.release();

@@ -271,14 +271,14 @@ int orbx_chain_trajectory(const double* T0, const double* R, const double* t, co
 
 static_assert(sizeof(orbx_ba_summary) == 32, "orbx_ba_summary is the kernel's BaSummary");
 
-extern "C" {
+namespace orbx_host {
 
-int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const int32_t* pose_offset, double* poses6,
-                             const int32_t* point_offset, double* points3, const int32_t* obs_offset,
-                             const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
-                             double huber_delta, int max_iters, orbx_ba_summary* summaries) {
-  DeviceGuard _dg(c);
-  if (!c) return ORBX_ERR_INVALID_ARG;
+// orbx_bundle_adjust_batch, and with `prior` its twin with landmark priors (orbx_api_prior.cpp, rank 20): the same
+// checks, staging and workspaces; the priors go up beside the stage as [points][4] and the solve is k_ba_lm<true>
+int ba_batch(orbx_ctx* c, const double* K, int n_windows, const int32_t* pose_offset, double* poses6,
+             const int32_t* point_offset, double* points3, const int32_t* obs_offset, const int32_t* obs_point,
+             const int32_t* obs_pose, const double* obs_xy, double huber_delta, int max_iters,
+             orbx_ba_summary* summaries, const BaPriorArgs* prior) {
   if (!K || !finite_all(K, 9) || n_windows < 0 || !(huber_delta > 0.0) || !std::isfinite(huber_delta) ||
       max_iters < 1 || max_iters > 1000)
     return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
@@ -307,6 +307,18 @@ int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const 
     if (!std::isfinite(points3[i])) return fail(c, ORBX_ERR_INVALID_ARG, "a point is not finite");
   for (size_t i = 0; i < 2 * tm; i++)
     if (!std::isfinite(obs_xy[i])) return fail(c, ORBX_ERR_INVALID_ARG, "an observation is not finite");
+  std::vector<double> prior4;  // rule P1: anchor and weight per landmark; no arrays: every weight is 0
+  if (prior) {
+    prior4.assign(4 * tn, 0.0);
+    for (size_t j = 0; prior->xyz && j < tn; j++) {
+      const double lam = prior->weight[j];
+      const double* A = prior->xyz + 3 * j;
+      if (!(lam >= 0.0) || !std::isfinite(lam)) return fail(c, ORBX_ERR_INVALID_ARG, "a prior weight is negative or not finite");
+      if (lam > 0.0 && !finite_all(A, 3))
+        return fail(c, ORBX_ERR_INVALID_ARG, "an anchor under a positive weight is not finite");
+      prior4[4 * j] = A[0], prior4[4 * j + 1] = A[1], prior4[4 * j + 2] = A[2], prior4[4 * j + 3] = lam;
+    }
+  }
   // CSR by (landmark, pose), per window (src/with_bundle_adjustment.cpp:651-666 adds the residual blocks landmark by
   // landmark)
   std::vector<int32_t> rows(tn + (size_t)n_windows), order;
@@ -350,6 +362,7 @@ int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const 
   DevBuf &b = c->ba.stage, &ws = c->ba.ws;
   ENSURE(c, b, L.bytes);
   ENSURE(c, ws, W.bytes);
+  if (prior) ENSURE(c, c->ba.prior, sizeof(double) * prior4.size());
   hipStream_t s = c->stream;
   const size_t noff = (size_t)n_windows + 1;
   int32_t* d_off = at<int32_t>(b, L.off);
@@ -362,16 +375,39 @@ int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const 
   HIPCHK(c, hipMemcpyAsync(at<uint8_t>(b, L.opose), opose.data(), tm, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(at<double>(b, L.oxy), oxy.data(), sizeof(double) * 2 * tm, hipMemcpyHostToDevice, s));
   const double K4[4] = {K[0], K[4], K[2], K[5]};
-  HIPCHK(c, orbx_launch_ba(s, n_windows, W.groups, max_iters, K4, huber_delta, d_off, d_off + noff, d_off + 2 * noff,
-                           at<double>(b, L.poses), at<double>(b, L.points), at<int32_t>(b, L.rows),
-                           at<uint8_t>(b, L.opose), at<double>(b, L.oxy), cap, ocap, at<double>(ws, W.wp),
-                           at<double>(ws, W.wo), at<unsigned long long>(ws, W.slot), at<void>(b, L.out)));
+  if (prior) {
+    HIPCHK(c, hipMemcpyAsync(c->ba.prior.p, prior4.data(), sizeof(double) * prior4.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(c, orbx_launch_ba_prior(s, n_windows, W.groups, max_iters, K4, huber_delta, d_off, d_off + noff,
+                                   d_off + 2 * noff, at<double>(b, L.poses), at<double>(b, L.points),
+                                   at<int32_t>(b, L.rows), at<uint8_t>(b, L.opose), at<double>(b, L.oxy), cap, ocap,
+                                   at<double>(ws, W.wp), at<double>(ws, W.wo), at<unsigned long long>(ws, W.slot),
+                                   at<void>(b, L.out), at<const double>(c->ba.prior, 0), prior->start));
+  } else {
+    HIPCHK(c, orbx_launch_ba(s, n_windows, W.groups, max_iters, K4, huber_delta, d_off, d_off + noff, d_off + 2 * noff,
+                             at<double>(b, L.poses), at<double>(b, L.points), at<int32_t>(b, L.rows),
+                             at<uint8_t>(b, L.opose), at<double>(b, L.oxy), cap, ocap, at<double>(ws, W.wp),
+                             at<double>(ws, W.wo), at<unsigned long long>(ws, W.slot), at<void>(b, L.out)));
+  }
   // the staged vectors are pageable: their copies above have left the host before the calls returned
   HIPCHK(c, hipMemcpyAsync(poses6, at<double>(b, L.poses), sizeof(double) * 6 * tp, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(points3, at<double>(b, L.points), sizeof(double) * 3 * tn, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(summaries, at<void>(b, L.out), sizeof(orbx_ba_summary) * (size_t)n_windows, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return ORBX_OK;
+}
+
+}  // namespace orbx_host
+
+extern "C" {
+
+int orbx_bundle_adjust_batch(orbx_ctx* c, const double* K, int n_windows, const int32_t* pose_offset, double* poses6,
+                             const int32_t* point_offset, double* points3, const int32_t* obs_offset,
+                             const int32_t* obs_point, const int32_t* obs_pose, const double* obs_xy,
+                             double huber_delta, int max_iters, orbx_ba_summary* summaries) {
+  DeviceGuard _dg(c);
+  if (!c) return ORBX_ERR_INVALID_ARG;
+  return ba_batch(c, K, n_windows, pose_offset, poses6, point_offset, points3, obs_offset, obs_point, obs_pose, obs_xy,
+                  huber_delta, max_iters, summaries, nullptr);
 }
 
 int orbx_bundle_adjust(orbx_ctx* c, const double* K, int n_poses, double* poses6, int n_points, double* points3,

@@ -175,7 +175,7 @@ int lm_check_build(orbx_ctx* c, const double* K, const void* tracks, const void*
 
 // the solve behind orbx_bundle_adjust_landmarks_device and orbx_bundle_adjust_landmarks_pnp_device
 int lm_solve(orbx_ctx* c, double huber_delta, int max_iters, hipStream_t s, const double* d_poses6,
-             const SideWork* producer) {
+             const SideWork* producer, const double* d_prior, int start) {
   if (!ba_params_ok(huber_delta, max_iters)) return fail(c, ORBX_ERR_INVALID_ARG, "bad bundle-adjustment arguments");
   if (c->lm.n < 1) return fail(c, ORBX_ERR_INVALID_ARG, "no landmarks block has been built");
   int st = c->lm.side.enter(c, s);
@@ -198,10 +198,17 @@ int lm_solve(orbx_ctx* c, double huber_delta, int max_iters, hipStream_t s, cons
                            s));
   HIPCHK(c, hipMemcpyAsync(sol + V.points, P.points3, sizeof(double) * 3 * (size_t)n * cap, hipMemcpyDeviceToDevice, s));
   const double K4[4] = {c->lm.K[0], c->lm.K[4], c->lm.K[2], c->lm.K[5]};
-  HIPCHK(c, orbx_launch_ba(s, n, W.groups, max_iters, K4, huber_delta, P.pose_off, P.pt_off, P.obs_off,
-                           (double*)(sol + V.poses), (double*)(sol + V.points), P.rows, P.opose, P.oxy, cap, ocap,
-                           (double*)(ws + W.wp), (double*)(ws + W.wo), (unsigned long long*)(ws + W.slot),
-                           sol + V.out));
+  if (d_prior) {
+    HIPCHK(c, orbx_launch_ba_prior(s, n, W.groups, max_iters, K4, huber_delta, P.pose_off, P.pt_off, P.obs_off,
+                                   (double*)(sol + V.poses), (double*)(sol + V.points), P.rows, P.opose, P.oxy, cap,
+                                   ocap, (double*)(ws + W.wp), (double*)(ws + W.wo),
+                                   (unsigned long long*)(ws + W.slot), sol + V.out, d_prior, start));
+  } else {
+    HIPCHK(c, orbx_launch_ba(s, n, W.groups, max_iters, K4, huber_delta, P.pose_off, P.pt_off, P.obs_off,
+                             (double*)(sol + V.poses), (double*)(sol + V.points), P.rows, P.opose, P.oxy, cap, ocap,
+                             (double*)(ws + W.wp), (double*)(ws + W.wo), (unsigned long long*)(ws + W.slot),
+                             sol + V.out));
+  }
   c->lm.solved = true;
   return ORBX_OK;
 }

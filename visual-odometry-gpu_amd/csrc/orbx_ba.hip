@@ -84,8 +84,11 @@ struct BaWin {
 };
 
 // cost, point blocks, W blocks, then one pose block per pass; S.red[0] = sum rho on return (before the pose passes),
-// S.gmax = max |gradient|.  first: also the Jacobi scales and the depth check.
-__device__ void ba_linearize(const BaWin& w, BaShared& S, bool first, double* sum_rho) {
+// S.gmax = max |gradient|.  first: also the Jacobi scales and the depth check.  PRIOR (rank 20): `prior` holds the
+// window's anchors and weights, four doubles per landmark; a landmark's prior comes behind its last observation
+// (rule P1), so sum rho, V, the gradient and the Jacobi scales all include it.
+template <bool PRIOR>
+__device__ void ba_linearize(const BaWin& w, BaShared& S, bool first, double* sum_rho, const double* prior) {
   const int tid = threadIdx.x;
   double acc1[1] = {0.0}, gm[1] = {0.0};
   int bad = 0;
@@ -106,6 +109,10 @@ __device__ void ba_linearize(const BaWin& w, BaShared& S, bool first, double* su
 #pragma unroll
         for (int k = 0; k < 18; k++) w.wo[k * w.ocap + o] = Wb[k];
       }
+    }
+    if (PRIOR) {  // (loaded here, behind the loop: the four doubles are not live across the observations)
+      const double A[3] = {prior[4 * j], prior[4 * j + 1], prior[4 * j + 2]};
+      ba_prior_accum(X, A, prior[4 * j + 3], V, gp, &acc1[0]);
     }
 #pragma unroll
     for (int k = 0; k < 6; k++) w.wp[(Q_V + k) * w.cap + j] = V[k];
@@ -156,6 +163,10 @@ __device__ void ba_linearize(const BaWin& w, BaShared& S, bool first, double* su
   __syncthreads();
 }
 
+// PRIOR = false is the solve of rank 7 and takes none of the prior's paths: prior and start are not read.  PRIOR = true
+// (rank 20): prior is [points][4], anchor and weight of every landmark in the batch's point order; start is
+// ORBX_PRIOR_START_GIVEN (0) or ORBX_PRIOR_START_ANCHOR (1).
+template <bool PRIOR>
 __global__ __launch_bounds__(BA_THREADS) void k_ba_lm(int n_windows, int max_iters, BaK4 K, double delta,
                                                       const int32_t* __restrict__ pose_off,
                                                       const int32_t* __restrict__ pt_off,
@@ -166,7 +177,8 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_lm(int n_windows, int max_ite
                                                       const double* __restrict__ obs_xy, int cap, int ocap,
                                                       double* __restrict__ ws_pt, double* __restrict__ ws_obs,
                                                       unsigned long long* __restrict__ ws_slot,
-                                                      BaSummary* __restrict__ out) {
+                                                      BaSummary* __restrict__ out,
+                                                      const double* __restrict__ prior, int start) {
   __shared__ BaShared S;
   const int tid = threadIdx.x;
   BaWin w;
@@ -188,12 +200,17 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_lm(int n_windows, int max_ite
     w.oxy = obs_xy + 2 * (size_t)obs_off[win];
     double* g_pose = poses + 6 * (size_t)pose_off[win];
     double* g_pt = points + 3 * (size_t)pt_off[win];
+    const double* g_prior = PRIOR ? prior + 4 * (size_t)pt_off[win] : nullptr;
     // ---- set-up: accepted parameters, the landmark's pose -> observation table
     if (tid < 6 * W) S.x[tid] = g_pose[tid];
     if (tid == 0) S.bad = 0, S.done = 0;
     for (int j = tid; j < N; j += BA_THREADS) {
 #pragma unroll
       for (int k = 0; k < 3; k++) w.wp[(Q_X + k) * cap + j] = g_pt[3 * j + k];
+      if (PRIOR && start == 1 && g_prior[4 * j + 3] > 0.0) {  // rule P5: an anchored landmark starts at its anchor
+#pragma unroll
+        for (int k = 0; k < 3; k++) w.wp[(Q_X + k) * cap + j] = g_prior[4 * j + k];
+      }
       unsigned long long sl = ~0ull;
       const int r0 = w.row[j];
       for (int o = r0; o < w.row[j + 1]; o++) {
@@ -209,7 +226,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_lm(int n_windows, int max_ite
     }
     __syncthreads();
     double sum_rho;
-    ba_linearize(w, S, true, &sum_rho);
+    ba_linearize<PRIOR>(w, S, true, &sum_rho, g_prior);
     if (tid == 0) {
       const double cost = 0.5 * sum_rho;
       S.T.radius = BA_RADIUS0, S.T.decrease = 2.0, S.T.cost = cost;
@@ -342,6 +359,13 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_lm(int n_windows, int max_ite
             double z;
             acc4[3] = acc4[3] + ba_obs_cost(w.K.k, S.Pc[w.opose[o]], cd, w.oxy[2 * o], w.oxy[2 * o + 1], w.delta, &z);
           }
+          if (PRIOR) {  // rule P2: the landmark's prior term right behind its observations'
+            const double lam = g_prior[4 * j + 3];
+            if (lam > 0.0) {
+              const double A[3] = {g_prior[4 * j], g_prior[4 * j + 1], g_prior[4 * j + 2]};
+              acc4[3] = acc4[3] + ba_prior_cost(cd, A, lam);
+            }
+          }
         }
       }
       block_reduce<4>(acc4, S);
@@ -367,7 +391,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_lm(int n_windows, int max_ite
         if (tid < 6 * W) S.x[tid] = S.cand[tid];
         if (tid < W) S.Px[tid] = S.Pc[tid];
         __syncthreads();
-        ba_linearize(w, S, false, &sum_rho);
+        ba_linearize<PRIOR>(w, S, false, &sum_rho, g_prior);
         if (tid == 0 && S.gmax <= BA_GRADIENT_TOL) S.sum.termination = BA_CONVERGENCE, S.done = 1;
       }
       if (tid == 0 && !S.done && S.T.radius <= BA_RADIUS_MIN) S.sum.termination = BA_CONVERGENCE, S.done = 1;
@@ -400,8 +424,27 @@ hipError_t orbx_launch_ba(hipStream_t s, int n_windows, int groups, int max_iter
     return hipErrorInvalidValue;
   BaK4 K;
   for (int i = 0; i < 4; i++) K.k[i] = K4[i];
-  hipLaunchKernelGGL(k_ba_lm, dim3(groups), dim3(BA_THREADS), 0, s, n_windows, max_iters, K, delta, d_pose_off,
+  hipLaunchKernelGGL(k_ba_lm<false>, dim3(groups), dim3(BA_THREADS), 0, s, n_windows, max_iters, K, delta, d_pose_off,
                      d_pt_off, d_obs_off, d_poses, d_points, d_rows, d_obs_pose, d_obs_xy, cap, ocap, d_ws_pt,
-                     d_ws_obs, d_ws_slot, (BaSummary*)d_out);
+                     d_ws_obs, d_ws_slot, (BaSummary*)d_out, (const double*)nullptr, 0);
+  return hipGetLastError();
+}
+
+// the same solve with landmark priors (rank 20): d_prior is [points][4] in the batch's point order, start an
+// orbx_prior_start
+hipError_t orbx_launch_ba_prior(hipStream_t s, int n_windows, int groups, int max_iters, const double* K4, double delta,
+                                const int32_t* d_pose_off, const int32_t* d_pt_off, const int32_t* d_obs_off,
+                                double* d_poses, double* d_points, const int32_t* d_rows, const uint8_t* d_obs_pose,
+                                const double* d_obs_xy, int cap, int ocap, double* d_ws_pt, double* d_ws_obs,
+                                unsigned long long* d_ws_slot, void* d_out, const double* d_prior, int start) {
+  if (n_windows <= 0) return hipSuccess;
+  if (groups < 1 || groups > n_windows || max_iters < 1 || max_iters > 1000 || cap < 1 || ocap < 1 || !d_prior ||
+      (start != 0 && start != 1))
+    return hipErrorInvalidValue;
+  BaK4 K;
+  for (int i = 0; i < 4; i++) K.k[i] = K4[i];
+  hipLaunchKernelGGL(k_ba_lm<true>, dim3(groups), dim3(BA_THREADS), 0, s, n_windows, max_iters, K, delta, d_pose_off,
+                     d_pt_off, d_obs_off, d_poses, d_points, d_rows, d_obs_pose, d_obs_xy, cap, ocap, d_ws_pt,
+                     d_ws_obs, d_ws_slot, (BaSummary*)d_out, d_prior, start);
   return hipGetLastError();
 }

@@ -480,3 +480,22 @@ ORBX_PHD int ba_trust_decide(BaTrust* T, bool solved, double model, double cand_
   ba_trust_reject(T);
   return BA_STEP_REJECTED;
 }
+
+// ---- landmark priors (rules P1 and P2) --------------------------------------------------------
+// The residual block sqrt(lam) (X - A) of one landmark, with no loss function and no square root taken:
+// rho += lam |X - A|^2, the diagonal of V += lam, gp += lam (X - A).  Called after the landmark's last observation.
+// lam = 0 (anything that is not > 0) is no operation at all: every accumulator keeps its bits.
+ORBX_PHD void ba_prior_accum(const double* X, const double* A, double lam, double* V, double* gp, double* rho) {
+  ORBX_PNO_CONTRACT
+  if (!(lam > 0.0)) return;
+  const double d0 = X[0] - A[0], d1 = X[1] - A[1], d2 = X[2] - A[2];
+  *rho = *rho + lam * ((d0 * d0 + d1 * d1) + d2 * d2);
+  V[0] = V[0] + lam, V[3] = V[3] + lam, V[5] = V[5] + lam;
+  gp[0] = gp[0] + lam * d0, gp[1] = gp[1] + lam * d1, gp[2] = gp[2] + lam * d2;
+}
+// rho of the same block at X: the landmark's term of the candidate's cost, behind its observations' (rule P2)
+ORBX_PHD double ba_prior_cost(const double* X, const double* A, double lam) {
+  ORBX_PNO_CONTRACT
+  const double d0 = X[0] - A[0], d1 = X[1] - A[1], d2 = X[2] - A[2];
+  return lam * ((d0 * d0 + d1 * d1) + d2 * d2);
+}

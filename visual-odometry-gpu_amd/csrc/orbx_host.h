@@ -217,8 +217,8 @@ struct Scale {
 // bundle adjustment of staged windows (orbx_ba.hip): the windows and their summaries (BaStage of orbx_layout.h) and
 // the workgroups' workspaces (LmWork); grown on first use
 struct BundleAdjust {
-  DevBuf stage, ws;
-  void release() { free_bufs({&stage, &ws}); }
+  DevBuf stage, ws, prior;  // prior: [points][4] of a call with landmark priors (rank 20)
+  void release() { free_bufs({&stage, &ws, &prior}); }
 };
 
 // landmarks of tracked windows and their bundle adjustment on the device (orbx_landmarks.hip, orbx_ba.hip): the
@@ -317,6 +317,16 @@ struct Carry {
     side.release();
     free_bufs({&blk, &pscr, &pblk, &stage});
   }
+};
+
+// landmark priors of a carried window (orbx_prior.hip; rank 20): the priors' OWN block (PriorBlock of orbx_layout.h),
+// gathered from lm.blk and carry.blk; the solve with priors reads it.  It runs under the landmarks' event (lm.side),
+// as the builds and solves of the block it belongs to do.
+struct Priors {
+  DevBuf blk;
+  int n = 0, cap = 0;     // windows and slots per window of the landmarks block it was gathered for (0: none)
+  long long lm_gen = -1;  // the Landmarks::gen of that block
+  void release() { free_bufs({&blk}); }
 };
 
 // descriptors at caller-held points and the re-association of two described sets (orbx_reloc.hip; rank 19): the
@@ -444,6 +454,7 @@ struct orbx_ctx {
   orbx_host::Pnp pnp;
   orbx_host::Carry carry;
   orbx_host::Reloc reloc;
+  orbx_host::Priors prior;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;
@@ -579,7 +590,19 @@ bool gate_params_ok(double max_rot, double max_trans);
 // the solve of the landmarks block on s behind orbx_bundle_adjust_landmarks_device and its PnP-seeded twin
 // (orbx_api_landmarks.cpp): d_poses6 is what the solve's poses copy is taken from -- NULL: the poses the block was
 // built from -- and `producer`, when not NULL, the work that wrote them, perhaps on another stream
+// d_prior, when not NULL: [points][4] in the block's point order, and the solve is the one with landmark priors
+// (rank 20) from `start`, an orbx_prior_start
 int lm_solve(orbx_ctx* c, double huber_delta, int max_iters, hipStream_t s, const double* d_poses6,
-             const SideWork* producer);
+             const SideWork* producer, const double* d_prior = nullptr, int start = 0);
+// the staged solve behind orbx_bundle_adjust_batch (orbx_api_geom.cpp) and, with `prior`, behind
+// orbx_bundle_adjust_prior_batch (orbx_api_prior.cpp): xyz / weight both NULL means every weight is 0
+struct BaPriorArgs {
+  const double *xyz, *weight;
+  int start;
+};
+int ba_batch(orbx_ctx* c, const double* K, int n_windows, const int32_t* pose_offset, double* poses6,
+             const int32_t* point_offset, double* points3, const int32_t* obs_offset, const int32_t* obs_point,
+             const int32_t* obs_pose, const double* obs_xy, double huber_delta, int max_iters,
+             orbx_ba_summary* summaries, const BaPriorArgs* prior);
 
 }  // namespace orbx_host

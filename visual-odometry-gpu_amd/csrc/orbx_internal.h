@@ -205,6 +205,13 @@ hipError_t orbx_launch_ba(hipStream_t s, int n_windows, int groups, int max_iter
                           double* d_poses, double* d_points, const int32_t* d_rows, const uint8_t* d_obs_pose,
                           const double* d_obs_xy, int cap, int ocap, double* d_ws_pt, double* d_ws_obs,
                           unsigned long long* d_ws_slot, void* d_out);
+// the same solve with landmark priors: d_prior holds anchor (3) and weight (1) of every landmark
+// in the batch's point order, landmark j of window w at 4 * (d_pt_off[w] + j); start: an orbx_prior_start
+hipError_t orbx_launch_ba_prior(hipStream_t s, int n_windows, int groups, int max_iters, const double* K4, double delta,
+                                const int32_t* d_pose_off, const int32_t* d_pt_off, const int32_t* d_obs_off,
+                                double* d_poses, double* d_points, const int32_t* d_rows, const uint8_t* d_obs_pose,
+                                const double* d_obs_xy, int cap, int ocap, double* d_ws_pt, double* d_ws_obs,
+                                unsigned long long* d_ws_slot, void* d_out, const double* d_prior, int start);
 
 // ---- landmarks of tracked windows (orbx_landmarks.hip) ---------------------------------------
 // The block k_lm_fill writes is the block orbx_launch_ba reads: status [n], three offset arrays [n + 1], points3
@@ -297,6 +304,14 @@ hipError_t orbx_launch_carry_gather(hipStream_t s, const double* d_xyz, const in
 // d_rec: window_len records per window; d_poses6: 6 doubles per (window, frame); d_wstatus: one per window
 hipError_t orbx_launch_carry_fill(hipStream_t s, const OrbxPnpRecord* d_rec, int n_windows, int window_len,
                                   double* d_poses6, int32_t* d_wstatus);
+
+// ---- landmark priors of a carried window (orbx_prior.hip; DESIGN.md §9 rank 20, rule P6) ---------------------------
+// d_status / d_pt_off / d_slot_of_point: the landmarks block's; d_carry_xyz / d_carry_point: the carry block's, of the
+// same n_windows and cap; d_prior: 4 doubles per landmark in the block's point order; d_count: one per window
+hipError_t orbx_launch_prior_gather(hipStream_t s, const int32_t* d_status, const int32_t* d_pt_off,
+                                    const int32_t* d_slot_of_point, const double* d_carry_xyz,
+                                    const int32_t* d_carry_point, int n_windows, int cap, double weight,
+                                    double* d_prior, int32_t* d_count);
 
 // ---- descriptors at caller-held points and the re-association (orbx_reloc.hip) --------------
 enum { PD_NONE = 0, PD_BORDER = 1, PD_OK = 2 };  // = orbx_pd_state

@@ -304,6 +304,16 @@ struct CarryStage : private Sections {
         seen(take(sizeof(int32_t) * n_slots)), tracks(take(sizeof(float) * 2 * n_slots * len)), bytes(off) {}
 };
 
+// ---- landmark priors of the landmarks block of n windows of cap slots (rank 20) ----
+// the priors block: prior (anchor and weight, 4 doubles per landmark, in the block's point order) | count (one per
+// window) | pt_off (a copy of the landmarks block's n + 1 point offsets: the priors stay fetchable after a rebuild)
+struct PriorBlock : private Sections {
+  size_t slots, prior, count, pt_off, bytes;
+  PriorBlock(size_t n, size_t cap)
+      : slots(n * cap), prior(take(sizeof(double) * 4 * slots)), count(take(sizeof(int32_t) * n)),
+        pt_off(take(sizeof(int32_t) * (n + 1))), bytes(off) {}
+};
+
 // ---- descriptors at caller-held points of n frames of cap slots, and the re-association of two described sets ----
 // the level-0 image of a w x h frame in the workspace: rows padded to a multiple of 4 bytes (describe_wave fetches
 // aligned dwords), images a multiple of 256 bytes apart

@@ -47,6 +47,7 @@
 #include "../../include/orbx_carry.h"
 #include "../../include/orbx_lm.h"
 #include "../../include/orbx_pnp.h"
+#include "../../include/orbx_prior.h"
 #include "../../include/orbx_reloc.h"
 #include "../../include/orbx_stream.h"
 #include "../../include/orbx_vo.h"
@@ -1541,6 +1542,45 @@ inline CarriedWindow localise_carried_window(const std::vector<Point3d>& old_poi
                                              min_inliers, out.records.data(), out.poses6.data(), &out.status,
                                              out.carried_point.data()),
                 "orbx_localise_carried_window");
+  return out;
+}
+
+// ---- landmark priors in the window solve --------------------------------------------------
+// The reference's Ceres problem of one window (src/with_bundle_adjustment.cpp:612-679: reprojection residuals,
+// HuberLoss, pose 0 constant) with one more residual block sqrt(weight) (X - anchor) per anchored landmark, which ties
+// the window to the map the anchors come from and fixes the scale the reference leaves free.  poses6 (6 per pose:
+// angle-axis and translation, world -> camera) and points are the start and, on ORBX_BA_CONVERGENCE only, the result.
+// anchors and weights are one per point, or both empty: no priors.  start: an orbx_prior_start.
+struct PriorSolve {
+  std::vector<double> poses6;
+  std::vector<Point3d> points;
+  orbx_ba_summary summary{};
+  bool converged() const { return summary.termination == ORBX_BA_CONVERGENCE; }
+};
+inline PriorSolve bundle_adjust_with_priors(const double K[9], const std::vector<double>& poses6,
+                                            const std::vector<Point3d>& points, const std::vector<int32_t>& obs_point,
+                                            const std::vector<int32_t>& obs_pose, const std::vector<Point2d>& obs_xy,
+                                            const std::vector<Point3d>& anchors, const std::vector<double>& weights,
+                                            int start = ORBX_PRIOR_START_GIVEN, double huber_delta = 1.0,
+                                            int max_iters = 200) {
+  static_assert(sizeof(Point3d) == 3 * sizeof(double) && sizeof(Point2d) == 2 * sizeof(double), "point layouts");
+  if (poses6.size() % 6 != 0) throw std::invalid_argument("bundle_adjust_with_priors: poses6 holds 6 doubles per pose");
+  if (obs_point.size() != obs_pose.size() || obs_point.size() != obs_xy.size())
+    throw std::invalid_argument("bundle_adjust_with_priors: obs_point, obs_pose and obs_xy differ in size");
+  if (anchors.size() != weights.size() || (!anchors.empty() && anchors.size() != points.size()))
+    throw std::invalid_argument("bundle_adjust_with_priors: anchors and weights are one per point, or both empty");
+  PriorSolve out;
+  out.poses6 = poses6;
+  out.points = points;
+  const int n = (int)points.size(), m = (int)obs_point.size();
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_bundle_adjust_prior(c, K, (int)(poses6.size() / 6), out.poses6.data(), n,
+                                         n > 0 ? &out.points[0].x : nullptr, m, obs_point.data(), obs_pose.data(),
+                                         m > 0 ? &obs_xy[0].x : nullptr, anchors.empty() ? nullptr : &anchors[0].x,
+                                         anchors.empty() ? nullptr : weights.data(), start, huber_delta, max_iters,
+                                         &out.summary),
+                "orbx_bundle_adjust_prior");
   return out;
 }
 
