@@ -739,6 +739,7 @@ void orbx_destroy(orbx_ctx* c) {
   // features: each waits for its own event before its buffers go, and each may be reading the next one's block.
   c->carry.release();
   c->reloc.release();
+  c->search.release();  // (its gated half ran under the re-association's event, waited for just above)
   c->pnp.release();
   c->st.release();
   c->wp.release();

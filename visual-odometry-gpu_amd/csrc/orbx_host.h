@@ -347,6 +347,23 @@ struct Reloc {
   }
 };
 
+// the search by projection (orbx_search.hip; rank 21): the projection's OWN result block (SpBlock of orbx_layout.h)
+// and the staged arrays of its one-window host entry (SpStage), under an event of their own; the gated
+// re-association's scratch (SgScratch), its candidates block (SgBlock) and the staged sets of its one-window host entry
+// (SgStage), which run under the re-association's event (Reloc::side): the gated call replaces Reloc::rblk.  The
+// projection reads lm.blk or lm.sol and the caller's poses; the gated call reads the caller's arrays -- the banks and
+// the projection block, when they are views of those; nothing is written elsewhere.
+struct Search {
+  DevBuf blk, stage, gscr, gblk, gstage;
+  int n = 0, cap = 0;    // windows and old slots per window of the last projection (0: none)
+  int gn = 0, gq = 0;    // windows and query slots of the last gated re-association (0: none)
+  SideWork side;         // the event is recorded behind every projection
+  void release() {
+    side.release();
+    free_bufs({&blk, &stage, &gscr, &gblk, &gstage});
+  }
+};
+
 // Shi-Tomasi corners (orbx_gftt.hip): the workspace of one slice of frames, allocated on first use and bounded by
 // ws_limit; the staged host image of the one-frame entries; and the entry's OWN result block, untouched by the ORB
 // path.  Rank 12 (top-up and masked detection) adds, beside the workspace and for the same number of frames, the bit
@@ -438,7 +455,9 @@ struct orbx_ctx {
   // carry waits for the landmarks' and the top-up's, the carried PnP for the windows tracker's, and the carried
   // landmarks build for the carried PnP's (carry and carried PnP share one event); the point descriptors wait for the
   // good features' and the windows tracker's, and the carry also for the re-association's (describe and
-  // re-association share one event).
+  // re-association share one event); the projection waits for the landmarks', the carry's and the window poses'
+  // events (its poses may be theirs), and the gated re-association for the projection's, the good features' and the
+  // windows tracker's.
   orbx_host::StageScratch s;
   orbx_host::Matcher m;
   orbx_host::LkPair lk;
@@ -455,6 +474,7 @@ struct orbx_ctx {
   orbx_host::Carry carry;
   orbx_host::Reloc reloc;
   orbx_host::Priors prior;
+  orbx_host::Search search;
 
   int timing = 0;  // 0 off, 1 all stages, 2 blur + fast only
   int fast_early = 1;

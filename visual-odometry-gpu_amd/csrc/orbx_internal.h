@@ -335,6 +335,36 @@ hipError_t orbx_launch_reassociate(hipStream_t s, int n_windows, const orbx_desc
                                    const int32_t* d_tstate, int tcap, double ratio, int max_distance, int unique,
                                    uint32_t* d_best, int32_t* d_origin, int32_t* d_dist, int32_t* d_count);
 
+// rules I-J alone, on origin / dist / best as a 2-NN kernel left them (the gated re-association of rank 21 ends with it)
+hipError_t orbx_launch_ra_unique(hipStream_t s, int n_windows, int qcap, int tcap, int unique, const uint32_t* d_best,
+                                 int32_t* d_origin, int32_t* d_dist, int32_t* d_count);
+
+// ---- the search by projection (orbx_search.hip) ----------------------------------------------
+// `in`: the old block as the carry reads it; d_pose6: one predicted pose per window, pose_stride doubles apart; K4 (host)
+// = fx, fy, cx, cy; d_xy: 2 doubles per slot, d_depth / d_state: one per slot, d_count: one per window.  cap <= 65536
+hipError_t orbx_launch_sp_project(hipStream_t s, const OrbxCarryIn& in, int n_windows, int cap, const double* d_pose6,
+                                  size_t pose_stride, const double* K4, int width, int height, double margin_px,
+                                  double* d_xy, double* d_depth, int32_t* d_state, int32_t* d_count);
+// the most cells of a window's grid: its counts, then its starts, are one LDS table of a workgroup
+#define ORBX_SG_CELLS_MAX 4096
+// a window's grid: cell (cx, cy) = clamped floor((x - x0) * inv), floor((y - y0) * inv), nx * ny <= ORBX_SG_CELLS_MAX
+struct OrbxSgGrid {
+  double x0, y0, inv;
+  int32_t nx, ny;
+};
+// n_windows <= 65535, capacities <= 2^22.  Scratch: d_grids: one per window; d_starts: ORBX_SG_CELLS_MAX + 1 per window;
+// d_sslot / d_sxy (2 doubles) / d_sdesc: one per train slot, the window's positioned OK train slots in cell order;
+// d_best: n_windows * tcap words (unique only).  d_origin / d_dist / d_candidates: n_windows * qcap; d_count: one per
+// window.  d_tpstate may be NULL
+hipError_t orbx_launch_reassociate_gated(hipStream_t s, int n_windows, const orbx_descriptor* d_qdesc,
+                                         const int32_t* d_qstate, const float* d_qxy, size_t point_stride,
+                                         size_t xy_frame_stride, int qcap, const orbx_descriptor* d_tdesc,
+                                         const int32_t* d_tstate, const double* d_txy, const int32_t* d_tpstate,
+                                         int tcap, double radius_px, double ratio, int max_distance, int accept_lone,
+                                         int unique, OrbxSgGrid* d_grids, int32_t* d_starts, int32_t* d_sslot,
+                                         double* d_sxy, orbx_descriptor* d_sdesc, uint32_t* d_best, int32_t* d_origin,
+                                         int32_t* d_dist, int32_t* d_candidates, int32_t* d_count);
+
 // ---- overlapping windows joined into one trajectory (orbx_stitch.hip) ------------------------
 // Window w of window_len frames starts at stream frame w * stride, 1 <= stride <= window_len - 1.
 // d_scale: the tracks-pose block's scale rows; d_scale0: one double per window (the chain's input section)

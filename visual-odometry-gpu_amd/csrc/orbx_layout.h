@@ -354,6 +354,46 @@ struct RaStage : private Sections {
         tdesc(take(sizeof(orbx_descriptor) * nt)), tstate(take(sizeof(int32_t) * nt)), bytes(off) {}
 };
 
+// ---- the search by projection (rank 21) ----
+// the projection's result block of n windows of cap old slots: xy (2 doubles per slot) | depth | state (one per slot
+// each) | count (one per window)
+struct SpBlock : private Sections {
+  size_t slots, xy, depth, state, count, bytes;
+  SpBlock(size_t n, size_t cap)
+      : slots(n * cap), xy(take(sizeof(double) * 2 * slots)), depth(take(sizeof(double) * slots)),
+        state(take(sizeof(int32_t) * slots)), count(take(sizeof(int32_t) * n)), bytes(off) {}
+};
+// what goes up with the one-window host entry: status (1) | pt_off (2) | slot_of_point | points3 (n_old each) | pose6
+struct SpStage : private Sections {
+  size_t status, pt_off, slot, points, pose6, bytes;
+  explicit SpStage(size_t n_old)
+      : status(take(sizeof(int32_t))), pt_off(take(sizeof(int32_t) * 2)), slot(take(sizeof(int32_t) * n_old)),
+        points(take(sizeof(double) * 3 * n_old)), pose6(take(sizeof(double) * 6)), bytes(off) {}
+};
+// the gated re-association's scratch of n windows of tcap train slots: grids (one per window) | starts (cells_max + 1
+// per window) | and the sorted list, one record per train slot: slot | xy (2 doubles) | desc (32 bytes)
+struct SgScratch : private Sections {
+  size_t slots, grids, starts, sslot, sxy, sdesc, bytes;
+  SgScratch(size_t n, size_t tcap, size_t grid_bytes, size_t cells_max)
+      : slots(n * tcap), grids(take(grid_bytes * n)), starts(take(sizeof(int32_t) * (cells_max + 1) * n)),
+        sslot(take(sizeof(int32_t) * slots)), sxy(take(sizeof(double) * 2 * slots)), sdesc(take(32 * slots)),
+        bytes(off) {}
+};
+// its block of its own beside the re-association's RaBlock: candidates (one per query slot)
+struct SgBlock : private Sections {
+  size_t slots, candidates, bytes;
+  SgBlock(size_t n, size_t qcap) : slots(n * qcap), candidates(take(sizeof(int32_t) * slots)), bytes(off) {}
+};
+// what goes up with the one-window host entry: query desc | state | xy (2 floats) | train desc | state | xy (2 doubles)
+// | pstate
+struct SgStage : private Sections {
+  size_t qdesc, qstate, qxy, tdesc, tstate, txy, tpstate, bytes;
+  SgStage(size_t nq, size_t nt)
+      : qdesc(take(32 * nq)), qstate(take(sizeof(int32_t) * nq)), qxy(take(sizeof(float) * 2 * nq)),
+        tdesc(take(32 * nt)), tstate(take(sizeof(int32_t) * nt)), txy(take(sizeof(double) * 2 * nt)),
+        tpstate(take(sizeof(int32_t) * nt)), bytes(off) {}
+};
+
 // ---- n overlapping windows of len frames, window w starting at stream frame w * stride, joined into one trajectory ----
 // the frames of the stream
 inline size_t st_stream_frames(size_t n, size_t len, size_t stride) { return (n - 1) * stride + len; }

@@ -327,3 +327,10 @@ hipError_t orbx_launch_reassociate(hipStream_t s, int n_windows, const orbx_desc
                      d_dist, d_count);
   return hipGetLastError();
 }
+
+hipError_t orbx_launch_ra_unique(hipStream_t s, int n_windows, int qcap, int tcap, int unique, const uint32_t* d_best,
+                                 int32_t* d_origin, int32_t* d_dist, int32_t* d_count) {
+  hipLaunchKernelGGL(k_ra_unique, dim3(n_windows), dim3(PD_THREADS), 0, s, qcap, tcap, unique, d_best, d_origin,
+                     d_dist, d_count);
+  return hipGetLastError();
+}

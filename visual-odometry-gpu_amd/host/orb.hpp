@@ -49,6 +49,7 @@
 #include "../../include/orbx_pnp.h"
 #include "../../include/orbx_prior.h"
 #include "../../include/orbx_reloc.h"
+#include "../../include/orbx_search.h"
 #include "../../include/orbx_stream.h"
 #include "../../include/orbx_vo.h"
 
@@ -1581,6 +1582,81 @@ inline PriorSolve bundle_adjust_with_priors(const double K[9], const std::vector
                                          anchors.empty() ? nullptr : weights.data(), start, huber_delta, max_iters,
                                          &out.summary),
                 "orbx_bundle_adjust_prior");
+  return out;
+}
+
+// ---- the search by projection ------------------------------------------------------------
+// ORB-SLAM's SearchByProjection, where the reference keeps no point across a solve
+// (src/with_bundle_adjustment.cpp:586-593) and its only matcher is the global ratio test
+// (src/feature_tracking.cpp:203-219).  project_landmarks: the old window's landmarks -- old_points with the ascending
+// old_slot_of_point, as localise_carried_window takes them -- under a predicted pose6 (angle-axis and translation,
+// world -> camera), per OLD SLOT.  reassociate_gated: the matcher of two described sets whose candidates lie within
+// radius_px of the predictions; its origin is what localise_carried_window takes.
+struct ProjectedLandmarks {
+  std::vector<Point2d> xy;     // per old slot: the predicted pixel, zeros unless the state is ORBX_PROJ_OK
+  std::vector<double> depth;   // per old slot
+  std::vector<int32_t> state;  // per old slot: an orbx_proj_state
+  int32_t count = 0;           // the ORBX_PROJ_OK slots
+};
+inline ProjectedLandmarks project_landmarks(const std::vector<Point3d>& old_points,
+                                            const std::vector<int32_t>& old_slot_of_point, int slot_capacity,
+                                            const double K[9], const double pose6[6], int width, int height,
+                                            double margin_px = 0.0) {
+  static_assert(sizeof(Point3d) == 3 * sizeof(double) && sizeof(Point2d) == 2 * sizeof(double), "point layouts");
+  if (old_points.size() != old_slot_of_point.size())
+    throw std::invalid_argument("project_landmarks: old_points and old_slot_of_point differ in size");
+  if (slot_capacity < 1) throw std::invalid_argument("project_landmarks: slot_capacity < 1");
+  const int n_old = (int)old_points.size();
+  ProjectedLandmarks out;
+  out.xy.assign((size_t)slot_capacity, Point2d{0.0, 0.0});
+  out.depth.assign((size_t)slot_capacity, 0.0);
+  out.state.assign((size_t)slot_capacity, ORBX_PROJ_NONE);
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_project_landmarks(c, n_old > 0 ? &old_points[0].x : nullptr,
+                                       n_old > 0 ? old_slot_of_point.data() : nullptr, n_old, slot_capacity, K, pose6,
+                                       width, height, margin_px, &out.xy[0].x, out.depth.data(), out.state.data(),
+                                       &out.count),
+                "orbx_project_landmarks");
+  return out;
+}
+
+struct GatedMatches {
+  std::vector<int32_t> origin;      // per query: the train slot, or -1
+  std::vector<int32_t> dist;        // per query: the Hamming distance to it, or -1
+  std::vector<int32_t> candidates;  // per query: the train slots inside its gate
+  int32_t count = 0;                // the accepted queries
+};
+// train_pstate: one orbx_proj_state per train slot (ProjectedLandmarks::state), or empty: every slot is positioned
+inline GatedMatches reassociate_gated(const std::vector<ORBDescriptor>& query_desc,
+                                      const std::vector<int32_t>& query_state, const std::vector<Point2f>& query_xy,
+                                      const std::vector<ORBDescriptor>& train_desc,
+                                      const std::vector<int32_t>& train_state, const std::vector<Point2d>& train_xy,
+                                      const std::vector<int32_t>& train_pstate, double radius_px, double ratio = 0.8,
+                                      int max_distance = 256, bool accept_lone = false, bool unique = true) {
+  static_assert(sizeof(ORBDescriptor) == sizeof(orbx_descriptor) && sizeof(Point2f) == 2 * sizeof(float) &&
+                    sizeof(Point2d) == 2 * sizeof(double),
+                "layouts");
+  if (query_desc.size() != query_state.size() || query_desc.size() != query_xy.size())
+    throw std::invalid_argument("reassociate_gated: query_desc, query_state and query_xy differ in size");
+  if (train_desc.size() != train_state.size() || train_desc.size() != train_xy.size() ||
+      (!train_pstate.empty() && train_pstate.size() != train_desc.size()))
+    throw std::invalid_argument("reassociate_gated: the train arrays differ in size");
+  const int nq = (int)query_desc.size(), nt = (int)train_desc.size();
+  GatedMatches out;
+  out.origin.assign((size_t)nq, -1);
+  out.dist.assign((size_t)nq, -1);
+  out.candidates.assign((size_t)nq, 0);
+  orbx_ctx* c = detail::stage_ctx()->get(8, 8);
+  detail::check(c,
+                orbx_reassociate_gated(c, reinterpret_cast<const orbx_descriptor*>(query_desc.data()),
+                                       query_state.data(), reinterpret_cast<const float*>(query_xy.data()), nq,
+                                       reinterpret_cast<const orbx_descriptor*>(train_desc.data()), train_state.data(),
+                                       nt > 0 ? &train_xy[0].x : nullptr,
+                                       train_pstate.empty() ? nullptr : train_pstate.data(), nt, radius_px, ratio,
+                                       max_distance, accept_lone ? 1 : 0, unique ? 1 : 0, out.origin.data(),
+                                       out.dist.data(), &out.count, out.candidates.data()),
+                "orbx_reassociate_gated");
   return out;
 }
 
